@@ -8,8 +8,14 @@
 
 `python bench.py --gpus N --steps K --warmup W`; for N>1 the driver launches one rank per GPU with
 torch.distributed.run (sampling shards by video: no data-path collective, "weak" scaling).
-Rank 0 prints ONE JSON line with `roofline` (dominant kernel = fp32-MFMA implicit-GEMM conv) and
-`cpu_baseline` (the CPU oracle timed on this host on a bounded sample).
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, rank 0 prints ONE JSON line
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).
+`--dump-outputs DIR` writes what the last timed step computed (the four `sample_*` arrays a caller of
+sample_one_video receives) to DIR/<name>.npy in float32; the inputs are seeded, so two builds compare output for output.
+`--full` adds the secondary legs to the line: `box` (clock / power samples, fp32-MFMA calibration), `blocks` (further
+timed blocks of K steps), `roofline` (dominant kernel = fp32-MFMA implicit-GEMM conv) and `warp`, `gpu_eager_baseline`,
+`cpu_baseline` (the CPU oracle timed on this host on a bounded sample), `train` and `lfae_train`; the `--no-*`,
+`--blocks`, `--train-*` and `--lfae-train-*` options shape those legs and take effect only with `--full`.
 """
 import argparse
 import json
@@ -853,6 +859,27 @@ def lfae_train_bench(dev, rank, world, steps, warmup, batch):
     return out
 
 
+DUMP_BUDGET_BYTES = (64 << 20) - (1 << 16)        # 64 MB in all, the .npy headers included
+
+
+def dump_outputs(model, out_dir):
+    """The last step's results as a caller of sample_one_video receives them -> out_dir/<name>.npy (float32).  Beyond the 64 MB budget
+    (--batch > 1) every array is cut to a fixed sample of its elements: flat indices drawn without replacement from a seeded generator,
+    in ascending order, so two runs of the same arguments write the same elements."""
+    import numpy as np
+    names = ("sample_vid_grid", "sample_vid_conf", "sample_out_vid", "sample_warped_vid")
+    arrays = {n: getattr(model, n).detach().float().cpu().numpy() for n in names}
+    total = sum(a.size for a in arrays.values()) * 4
+    keep = min(1.0, DUMP_BUDGET_BYTES / total)
+    os.makedirs(out_dir, exist_ok=True)
+    for i, (n, a) in enumerate(arrays.items()):
+        if keep < 1.0:
+            idx = np.sort(np.random.default_rng(20240 + i).choice(a.size, int(a.size * keep), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, n + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    log("outputs of the last timed step -> %s (%s)" % (out_dir, "whole arrays" if keep == 1.0 else "seeded sample, %.1f %% of each array" % (100 * keep)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -869,7 +896,14 @@ def main():
     ap.add_argument("--blocks", type=int, default=3, help="timed blocks of K steps: block 0 is the headline, the others are reported beside it")
     ap.add_argument("--batch", type=int, default=1,
                     help="videos per GPU per step; 1 = BASELINE.json configs[1] (latency mode), >1 = throughput mode")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs (box state, extra blocks, roofline, warp, baselines, training); off: headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (sample_* arrays, float32, <= 64 MB in all) to DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:       # a plain run times the headline and nothing else
+        args.blocks, args.train_steps, args.lfae_train_steps = 1, 0, 0
+        args.no_roofline = args.no_cpu_baseline = args.no_gpu_eager_baseline = True
 
     if args.gpus > 1 and "RANK" not in os.environ:      # plain `python bench.py --gpus N`: become the launcher
         sys.exit(self_launch(args.gpus))
@@ -921,32 +955,37 @@ def main():
     log("model built; timing %d + %d sampling steps" % (args.warmup, args.steps))
     from cvpr23_lfdm_amd import ops as _ops
     from cvpr23_lfdm_amd._build import source_fingerprint
-    box = {"state_before": gpu_state(local)}
-    try:
-        box["calib_before"] = _ops.calib_mfma(dev)
-    except Exception as e:
-        box["calib_before"] = {"error": repr(e)[:200]}
+    box = None
+    if args.full:
+        box = {"state_before": gpu_state(local)}
+        try:
+            box["calib_before"] = _ops.calib_mfma(dev)
+        except Exception as e:
+            box["calib_before"] = {"error": repr(e)[:200]}
     per_rank = []
     elapsed = timed_region(run_step, args.steps, args.warmup, world, torch.cuda.synchronize, per_rank)
     log("headline: %.2f ms per video" % (1e3 * elapsed / args.steps))
-    box["state_after"] = gpu_state(local)
+    if args.dump_outputs and rank == 0:         # before anything else runs on the model: these are the last timed step's results
+        dump_outputs(model, args.dump_outputs)
     # Reconciliation aid (round-3 verdict: the driver's box ran the same commit 13 % slower than the evidence run with nothing on the
-    # line to tell why).  The headline above is the contract's ONE timed block; two more blocks of the same K follow with the shader
-    # clock / power sampled while they run, and the fp32-MFMA calibration kernel brackets the whole thing.
+    # line to tell why).  The headline above is the contract's ONE timed block; with --full two more blocks of the same K follow with
+    # the shader clock / power sampled while they run, and the fp32-MFMA calibration kernel brackets the whole thing.
     blocks_ms = [1e3 * elapsed / args.steps]
-    if args.blocks > 1:
-        with StateSampler(local) as smp:
-            for _ in range(args.blocks - 1):
-                el = timed_region(run_step, args.steps, 0, world, torch.cuda.synchronize)
-                blocks_ms.append(1e3 * el / args.steps)
-        box["during_extra_blocks"] = smp.summary()
-    try:
-        box["calib_after"] = _ops.calib_mfma(dev)
-    except Exception as e:
-        box["calib_after"] = {"error": repr(e)[:200]}
-    box["calib_note"] = ("lfdm_calib_mfma_f32: 256 workgroups x 4 waves x 4 chains of v_mfma_f32_32x32x2_f32 on pseudo-random operands; "
-                         "tflops vs the 157.3 peak and mhz (shader cycles / 100 MHz real-time ticks inside the kernel) say what THIS box "
-                         "delivers; compare across runs before comparing videos/s")
+    if args.full:
+        box["state_after"] = gpu_state(local)
+        if args.blocks > 1:
+            with StateSampler(local) as smp:
+                for _ in range(args.blocks - 1):
+                    el = timed_region(run_step, args.steps, 0, world, torch.cuda.synchronize)
+                    blocks_ms.append(1e3 * el / args.steps)
+            box["during_extra_blocks"] = smp.summary()
+        try:
+            box["calib_after"] = _ops.calib_mfma(dev)
+        except Exception as e:
+            box["calib_after"] = {"error": repr(e)[:200]}
+        box["calib_note"] = ("lfdm_calib_mfma_f32: 256 workgroups x 4 waves x 4 chains of v_mfma_f32_32x32x2_f32 on pseudo-random operands; "
+                             "tflops vs the 157.3 peak and mhz (shader cycles / 100 MHz real-time ticks inside the kernel) say what THIS box "
+                             "delivers; compare across runs before comparing videos/s")
     srt = sorted(blocks_ms)
     blocks = {"ms_per_step": [round(v, 2) for v in blocks_ms], "median": round(srt[len(srt) // 2], 2), "min": round(srt[0], 2),
               "max": round(srt[-1], 2), "note": "block 0 is the headline (`value`, `ms_per_step`); every block = %d steps between barrier + sync" % args.steps}
@@ -971,8 +1010,10 @@ def main():
                        "sampler": "DDIM-100 eta=1, cond_scale=1", "parallelism": "replicas x%d (videos sharded, no collective)" % world},
             "gflop_per_video_reference_dataflow": GFLOP_PER_VIDEO_REFERENCE,
             "whole_job_tflops_reference_dataflow": round(value * GFLOP_PER_VIDEO_REFERENCE / 1e3, 2),
-            "blocks": blocks, "box": box, "build": source_fingerprint(), "rccl_ranks": rccl_ranks,
+            "blocks": blocks, "build": source_fingerprint(), "rccl_ranks": rccl_ranks,
         }
+        if box is not None:
+            line["box"] = box
         def guarded(fn, *a):                 # the secondary measurements must never cost the headline line
             try:
                 return fn(*a)

@@ -1,6 +1,8 @@
 """cvpr23_lfdm_amd/datasets.py (MUG / MHAD / NATOPS with the reference's directory conventions, splits and item pipeline)
 against the reference's own dataset classes on synthetic trees - run in a fresh interpreter where the reference's
-DM/datasets_*.py can be imported with the repository's imageio / cv2 stand-ins (those packages are not installed)."""
+DM/datasets_*.py can be imported with the repository's imageio / cv2 stand-ins (those packages are not installed).
+What the reference's classes return is stored in tests/golden/datasets_reference.json (catalogue, labels, names and a
+SHA-256 of every item's bytes; `PYTHONPATH=. python tests/test_datasets.py` rewrites it where the reference tree is present)."""
 import json
 import os
 import subprocess
@@ -14,6 +16,8 @@ from cvpr23_lfdm_amd import io_compat as C
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = os.environ.get("LFDM_REFERENCE_ROOT", "/root/reference")
+LIVE = os.path.isfile(os.path.join(REF, "DM", "datasets_mug.py"))
+GOLDEN = os.path.join(REPO, "tests", "golden", "datasets_reference.json")
 
 
 def _frames(d, n, hw=(60, 80), seed=0):
@@ -57,9 +61,9 @@ def test_catalogues_and_items(tmp_path):
 
 
 WORKER = r'''
-import importlib.util, json, os, sys
+import hashlib, importlib.util, json, os, sys
 import numpy as np
-repo, ref, tmp = sys.argv[1:4]
+repo, ref, tmp, which = sys.argv[1:5]
 sys.path[:] = [os.path.join(repo, "oracle", "ref_shims")] + [p for p in sys.path if os.path.abspath(p or ".") != repo] + [repo]
 def load(name, path):
     spec = importlib.util.spec_from_file_location(name, path); mod = importlib.util.module_from_spec(spec)
@@ -71,30 +75,57 @@ import torchvision.transforms as T
 sys.modules.setdefault("torchvision.transforms.functional", T)        # only imported; colour jitter is off in this comparison
 T.functional = T
 from cvpr23_lfdm_amd import datasets as DS
-out = {}
+out = []
 cases = [("mug", "MUG", dict(color_jitter=False, sampling="random")), ("mug", "MUG", dict(color_jitter=False, sampling="very_random")),
          ("mug", "MUG_test", {}), ("mhad", "MHAD", dict(color_jitter=False, sampling="random")), ("mhad", "MHAD_test", {}),
          ("natops", "NATOPS", dict(color_jitter=False)), ("natops", "NATOPS_test", {})]
-worst = 0.0
 for ds_name, cls, kw in cases:
-    rmod = load("ref_datasets_" + ds_name, os.path.join(ref, "DM", "datasets_%s.py" % ds_name))
     root = os.path.join(tmp, {"mug": "MUG", "mhad": "MHAD", "natops": "NATOPS"}[ds_name])
-    a, b = getattr(DS, cls)(root, num_frames=6, image_size=48, **kw), getattr(rmod, cls)(root, num_frames=6, image_size=48, **kw)
-    assert len(a) == len(b) > 0 and a.video_path_list == b.video_path_list, (cls, a.video_path_list, b.video_path_list)
+    if which == "reference":
+        mod = load("ref_datasets_" + ds_name, os.path.join(ref, "DM", "datasets_%s.py" % ds_name))
+    else:
+        mod = DS
+    a = getattr(mod, cls)(root, num_frames=6, image_size=48, **kw)
+    items = []
     for i in range(len(a)):
-        np.random.seed(7 + i); va, la, na = a[i]
-        np.random.seed(7 + i); vb, lb, nb = b[i]
-        assert la == lb and na == nb and va.shape == vb.shape and va.dtype == vb.dtype, (cls, i, la, lb, na, nb)
-        worst = max(worst, float(np.abs(va - vb).max()))
-print(json.dumps({"worst": worst, "cases": len(cases)}))
+        np.random.seed(7 + i); v, label, name = a[i]
+        items.append({"label": label, "name": name, "shape": list(v.shape), "dtype": str(v.dtype),
+                      "sha256": hashlib.sha256(np.ascontiguousarray(v).tobytes()).hexdigest()})
+    out.append({"class": cls, "kw": kw, "videos": [os.path.relpath(p, root) for p in a.video_path_list], "items": items})
+print(json.dumps(out))
 '''
 
 
-@pytest.mark.skipif(not os.path.isfile(os.path.join(REF, "DM", "datasets_mug.py")), reason="reference tree not present")
+def _items(tmp, which):
+    """Catalogue and items (a hash of each item's bytes) of the seven cases, from this repository's classes or the reference's."""
+    r = subprocess.run([sys.executable, "-c", WORKER, REPO, REF, tmp, which], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                       text=True, env=dict(os.environ, PYTHONPATH="", MPLBACKEND="Agg"), cwd=tmp)
+    assert r.returncode == 0, r.stdout[-3000:]
+    return json.loads([l for l in r.stdout.splitlines() if l.startswith("[")][-1])
+
+
 def test_items_match_the_reference_classes(tmp_path):
     _trees(str(tmp_path))
-    r = subprocess.run([sys.executable, "-c", WORKER, REPO, REF, str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                       text=True, env=dict(os.environ, PYTHONPATH="", MPLBACKEND="Agg"), cwd=str(tmp_path))
-    assert r.returncode == 0, r.stdout[-3000:]
-    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
-    assert out["cases"] == 7 and out["worst"] == 0.0, out          # same files, same indices, same resize: bit-identical items
+    ours = _items(str(tmp_path), "ours")
+    with open(GOLDEN) as f:
+        want = json.load(f)
+    if LIVE:            # where the reference tree is present: its classes, live, and the stored record must agree
+        ref = _items(str(tmp_path), "reference")
+        assert ref == want, "tests/golden/datasets_reference.json differs from the live reference"
+    assert len(want) == 7 and all(c["items"] for c in want)
+    for a, b in zip(ours, want):          # same files, same indices, same resize: bit-identical items
+        assert (a["class"], a["videos"]) == (b["class"], b["videos"]), (a["class"], a["videos"], b["videos"])
+        assert a["items"] == b["items"], (a["class"], a["items"], b["items"])
+    assert len(ours) == len(want)
+
+
+if __name__ == "__main__":          # rewrites the stored record of the reference's classes (needs the reference tree)
+    import tempfile
+    assert LIVE, "the reference tree is needed to record its classes"
+    with tempfile.TemporaryDirectory() as d:
+        _trees(d)
+        rec = _items(d, "reference")
+    with open(GOLDEN, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    print("wrote", GOLDEN)

@@ -149,7 +149,7 @@ def test_bench_gpus2_over_rccl():
         pytest.skip("needs two GPUs for RCCL: %d visible" % n)
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "LFDM_DIST_BACKEND")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--blocks", "1",
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--blocks", "1",
                         "--no-cpu-baseline", "--no-roofline", "--train-steps", "2"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                        env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -1,15 +1,45 @@
-"""Live check of the oracle against the unmodified reference (only where /root/reference exists - i.e. in
-the build container; skipped on the GPU box, where the committed fixtures of tests/golden/ stand in)."""
+"""The oracle against the unmodified reference.  What the reference computes for these checks is stored in
+tests/golden/oracle_vs_reference.npz (written by `PYTHONPATH=.:oracle python tests/test_oracle_vs_reference.py` where the reference tree is present),
+so every check runs anywhere; where the reference tree is present the checks take the reference live and also pin the stored
+values to it.  Only the CPU speed calibration needs the reference itself."""
+import json
+import os
+
+import numpy as np
 import pytest
 import torch
 
 import reference_loader
 
-pytestmark = pytest.mark.skipif(not reference_loader.reference_available(), reason="reference tree not present")
+LIVE = reference_loader.reference_available()
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "oracle_vs_reference.npz")
+_stored = None
 
 
-def test_unet_and_sampler_match_live_reference():
-    import lfdm_oracle as O
+def _gold(key):
+    global _stored
+    if _stored is None:
+        _stored = dict(np.load(GOLDEN))
+    return _stored[key]
+
+
+def reference_value(key, live_fn):
+    """The reference's value for `key`: computed live when the reference tree is present (and then it must equal the stored one),
+    the stored one otherwise.  Tensors are stored as arrays, anything else as JSON."""
+    if not LIVE:
+        v = _gold(key)
+        return json.loads(str(v)) if v.dtype.kind == "U" else torch.from_numpy(v)
+    v = live_fn()
+    if os.path.exists(GOLDEN):
+        g = _gold(key)
+        if torch.is_tensor(v):
+            assert torch.equal(torch.from_numpy(g), v), "stored %s differs from the live reference" % key
+        else:
+            assert json.loads(str(g)) == json.loads(json.dumps(v)), "stored %s differs from the live reference" % key
+    return v
+
+
+def _live_unet():
     import synth
     ref = reference_loader.load_reference()
     b, t, s = 1, 2, 8
@@ -18,15 +48,42 @@ def test_unet_and_sampler_match_live_reference():
     m.unet.load_state_dict(synth.unet_state(seed=99))
     m.generator.load_state_dict(synth.generator_state(seed=98))
     m.eval()
-    dsd = {"denoise_fn." + k: v for k, v in synth.unet_state(seed=99).items()}
     x, time, cond = synth.unet_inputs(b, t, s, seed=12)
     with torch.no_grad():
-        want = m.unet(x, time, cond=cond, null_cond_prob=0.)
+        return m.unet(x, time, cond=cond, null_cond_prob=0.)
+
+
+def test_unet_and_sampler_match_live_reference():
+    import lfdm_oracle as O
+    import synth
+    b, t, s = 1, 2, 8
+    want = reference_value("unet", _live_unet)
+    dsd = {"denoise_fn." + k: v for k, v in synth.unet_state(seed=99).items()}
+    x, time, cond = synth.unet_inputs(b, t, s, seed=12)
     got = O.unet_forward(dsd, x, time, cond)
     assert float((got - want).abs().max()) < 1e-5
-    # drop-in import path resolves to the reference here (reference root precedes the repo root)
-    import DM.modules.video_flow_diffusion_model as mod
-    assert mod.__file__.startswith(reference_loader.REFERENCE_ROOT)
+    if LIVE:
+        # drop-in import path resolves to the reference here (reference root precedes the repo root)
+        import DM.modules.video_flow_diffusion_model as mod
+        assert mod.__file__.startswith(reference_loader.REFERENCE_ROOT)
+
+
+def _live_optimizer(learn_null_cond):
+    """The reference's parameter order and the param_groups of its optimizer_diff (the state itself is made by the test)."""
+    import synth
+    ref = reference_loader.load_reference()
+    rm = ref.vfdm.FlowDiffusion(img_size=8, num_frames=2, sampling_timesteps=5, is_train=True, config_pth=synth.CONFIG, pretrained_pth="",
+                                learn_null_cond=learn_null_cond)
+    groups = rm.optimizer_diff.state_dict()["param_groups"]
+    return {"names": [k for k, _ in rm.diffusion.named_parameters()], "shapes": [list(p.shape) for p in rm.diffusion.parameters()],
+            "param_groups": [dict(g, betas=list(g["betas"])) for g in groups]}
+
+
+def _reference_optimizer_state(rec):
+    """The optimizer_diff state dict the reference's training script would save, with a recognisable moment per parameter."""
+    state = {i: {"step": torch.tensor(3.0), "exp_avg": torch.full(shape, float(i + 1)), "exp_avg_sq": torch.full(shape, 0.5 * (i + 1))}
+             for i, shape in enumerate(rec["shapes"])}
+    return {"state": state, "param_groups": [dict(g, betas=tuple(g["betas"])) for g in rec["param_groups"]]}
 
 
 @pytest.mark.parametrize("learn_null_cond", [False, True])
@@ -36,17 +93,15 @@ def test_optimizer_state_of_the_reference_loads_into_flat_adam(learn_null_cond):
     moment on the right parameter (train_video_flow_diffusion_mug.py:181 `model.optimizer_diff.load_state_dict`)."""
     import synth
     from cvpr23_lfdm_amd import FlowDiffusion
-    ref = reference_loader.load_reference()
+    rec = reference_value("optimizer_%d" % learn_null_cond, lambda: _live_optimizer(learn_null_cond))
     # (learn_null_cond: the root-level null_cond_emb parameter comes FIRST in the reference's named_parameters())
     kw = dict(img_size=8, num_frames=2, sampling_timesteps=5, is_train=True, config_pth=synth.CONFIG, pretrained_pth="",
               learn_null_cond=learn_null_cond)
-    rm, om = ref.vfdm.FlowDiffusion(**kw), FlowDiffusion(**kw)
-    rnames = [k for k, _ in rm.diffusion.named_parameters()]
+    om = FlowDiffusion(**kw)
+    rnames = rec["names"]
     assert rnames == [k for k, _ in om.diffusion.named_parameters()]
-    for i, p in enumerate(rm.diffusion.parameters()):            # a recognisable moment per parameter
-        rm.optimizer_diff.state[p] = {"step": torch.tensor(3.0), "exp_avg": torch.full_like(p, float(i + 1)),
-                                      "exp_avg_sq": torch.full_like(p, 0.5 * (i + 1))}
-    sd = rm.optimizer_diff.state_dict()
+    assert rec["shapes"] == [list(p.shape) for p in om.diffusion.parameters()]
+    sd = _reference_optimizer_state(rec)
     om.optimizer_diff.load_state_dict(sd)
     got = om.optimizer_diff.state_dict()
     assert got["param_groups"][0]["betas"] == sd["param_groups"][0]["betas"] and len(got["state"]) == len(rnames)
@@ -56,7 +111,7 @@ def test_optimizer_state_of_the_reference_loads_into_flat_adam(learn_null_cond):
     # the moments are folded into the flat buffers at the first use: every one must have its parameter's size
     om.optimizer_diff.ensure_flat()
     # ... and a state saved for another parameter order is refused with a clear message instead of being mis-assigned
-    bad = rm.optimizer_diff.state_dict()
+    bad = _reference_optimizer_state(rec)
     bad["state"][0], bad["state"][1] = bad["state"][1], bad["state"][0]
     om2 = FlowDiffusion(**kw)
     om2.optimizer_diff.load_state_dict(bad)
@@ -68,23 +123,35 @@ def test_optimizer_state_of_the_reference_loads_into_flat_adam(learn_null_cond):
 def test_bg_predictor_types_match_live_reference(bg_type):
     """oracle.bg_predictor for every bg_type against LFAE/modules/bg_motion_predictor.py:15-57 itself (eval mode, small encoder)."""
     import lfdm_oracle as O
+    sd, src, drv = _bg_case(bg_type)
+    if bg_type != "zero":
+        assert set(reference_value("bg_%s_keys" % bg_type, lambda: sorted(_live_bg(bg_type)[0].state_dict()))) == set(sd)
+    want = reference_value("bg_%s" % bg_type, lambda: _live_bg(bg_type)[1])
+    with torch.no_grad():
+        got = O.bg_predictor({k: v.float() for k, v in sd.items()}, src, drv, bg_type=bg_type, num_blocks=2)
+    assert float((got - want).abs().max()) < 1e-5
+
+
+def _bg_case(bg_type):
     from cvpr23_lfdm_amd import params as P
-    ref = reference_loader.load_reference()
-    import LFAE.modules.bg_motion_predictor as bgm
     kw = dict(block_expansion=8, max_features=32, num_blocks=2, bg_type=bg_type)
-    net = bgm.BGMotionPredictor(num_channels=3, **kw).eval()
     sd = P.synthetic_state_dict(P.bg_predictor_spec(num_channels=3, **kw), 6262)
     if bg_type != "zero":
         sd["fc.weight"] = sd["fc.weight"] * 0.05
         sd["fc.bias"] = torch.tensor(P.BG_FC_BIAS[bg_type], dtype=torch.float32) + 0.2 * sd["fc.bias"]
-        assert set(net.state_dict()) == set(sd)
-    net.load_state_dict(sd)
     g = torch.Generator().manual_seed(79)
     src, drv = torch.rand(2, 3, 32, 32, generator=g), torch.rand(2, 3, 32, 32, generator=g)
+    return sd, src, drv
+
+
+def _live_bg(bg_type):
+    reference_loader.load_reference()
+    import LFAE.modules.bg_motion_predictor as bgm
+    net = bgm.BGMotionPredictor(num_channels=3, block_expansion=8, max_features=32, num_blocks=2, bg_type=bg_type).eval()
+    sd, src, drv = _bg_case(bg_type)
+    net.load_state_dict(sd)
     with torch.no_grad():
-        want = net(src, drv)
-        got = O.bg_predictor({k: v.float() for k, v in sd.items()}, src, drv, bg_type=bg_type, num_blocks=2)
-    assert float((got - want).abs().max()) < 1e-5
+        return net, net(src, drv)
 
 
 @pytest.mark.parametrize("estimate_affine", [True, False])
@@ -92,25 +159,39 @@ def test_region_predictor_without_pca_matches_live_reference(estimate_affine):
     """oracle.region_predictor(pca_based=False) against LFAE/modules/region_predictor.py:28-117 itself (regression head / centres only)."""
     import lfdm_oracle as O
     from cvpr23_lfdm_amd import params as P
-    reference_loader.load_reference()
-    import LFAE.modules.region_predictor as rpm
     kw = dict(block_expansion=8, max_features=32, num_blocks=2, temperature=0.1, scale_factor=0.25, pca_based=False, pad=3)
-    net = rpm.RegionPredictor(num_regions=4, num_channels=3, estimate_affine=estimate_affine, **kw).eval()
     sd = P.synthetic_state_dict(P.region_predictor_spec(num_regions=4, num_channels=3, estimate_affine=estimate_affine, **kw), 7171)
     from cvpr23_lfdm_amd.flow_diffusion import RegionPredictor
     ours = RegionPredictor(num_regions=4, num_channels=3, estimate_affine=estimate_affine, **kw)
-    assert [k for k, _ in net.named_parameters()] == [k for k, _ in ours.named_parameters()]                   # registration order
+    tag = "region_%d" % estimate_affine
+    names = reference_value(tag + "_names", lambda: [k for k, _ in _live_region_net(estimate_affine).named_parameters()])
+    assert names == [k for k, _ in ours.named_parameters()]                   # registration order
     if estimate_affine:       # and the regression head's identity initialisation (region_predictor.py:46-47)
-        assert torch.equal(ours.get("jacobian.bias").detach(), net.jacobian.bias.detach()) and float(ours.get("jacobian.weight").abs().max()) == 0.0
-    assert set(net.state_dict()) == set(sd)
-    net.load_state_dict(sd)
+        ref_bias = reference_value(tag + "_jacobian_bias", lambda: _live_region_net(True).jacobian.bias.detach().clone())
+        assert torch.equal(ours.get("jacobian.bias").detach(), ref_bias) and float(ours.get("jacobian.weight").abs().max()) == 0.0
+    assert set(reference_value(tag + "_keys", lambda: sorted(_live_region_net(estimate_affine).state_dict()))) == set(sd)
     x = torch.rand(2, 3, 64, 64, generator=torch.Generator().manual_seed(80))
     with torch.no_grad():
-        want = net(x)
         got = O.region_predictor({k: v.float() for k, v in sd.items()}, x, pca_based=False, num_blocks=2)
-    assert set(got) == set(want)
-    for key in want:
-        assert float((got[key] - want[key]).abs().max()) < 1e-5, key
+    want_keys = reference_value(tag + "_out_keys", lambda: sorted(_live_region(estimate_affine, sd, x)))
+    assert set(got) == set(want_keys)
+    for key in want_keys:
+        want = reference_value(tag + "_" + key, lambda: _live_region(estimate_affine, sd, x)[key])
+        assert float((got[key] - want).abs().max()) < 1e-5, key
+
+
+def _live_region_net(estimate_affine):
+    reference_loader.load_reference()
+    import LFAE.modules.region_predictor as rpm
+    return rpm.RegionPredictor(num_regions=4, num_channels=3, estimate_affine=estimate_affine, block_expansion=8, max_features=32, num_blocks=2,
+                               temperature=0.1, scale_factor=0.25, pca_based=False, pad=3).eval()
+
+
+def _live_region(estimate_affine, sd, x):
+    net = _live_region_net(estimate_affine)
+    net.load_state_dict(sd)
+    with torch.no_grad():
+        return net(x)
 
 
 @pytest.mark.parametrize("use_deformed_source", [True, False])
@@ -118,19 +199,26 @@ def test_pixelwise_flow_predictor_matches_live_reference(use_deformed_source):
     """oracle.pixelwise_flow_predictor against LFAE/modules/pixelwise_flow_predictor.py:17-137 itself on a small hourglass, with and
     without the deformed sources in the hourglass input (:116-119; every LFDM yaml sets use_deformed_source: True)."""
     import lfdm_oracle as O
-    from cvpr23_lfdm_amd import params as P
-    reference_loader.load_reference()
-    import LFAE.modules.pixelwise_flow_predictor as pfm
     k = 4
-    net = pfm.PixelwiseFlowPredictor(block_expansion=8, num_blocks=2, max_features=32, num_regions=k, num_channels=3, estimate_occlusion_map=True,
-                                     scale_factor=0.25, use_covar_heatmap=True, use_deformed_source=use_deformed_source, revert_axis_swap=True).eval()
+    gsd, sub, src, drv, sr, bg = _pixelwise_case(use_deformed_source)
+    tag = "pixelwise_%d" % use_deformed_source
+    assert set(reference_value(tag + "_keys", lambda: sorted(_live_pixelwise_net(use_deformed_source).state_dict()))) == set(sub)
+    with torch.no_grad():
+        got = O.pixelwise_flow_predictor({key: v.float() for key, v in gsd.items()}, src, drv, sr, bg, num_regions=k,
+                                         use_deformed_source=use_deformed_source, num_blocks=2)
+    for key in ("optical_flow", "occlusion_map"):
+        want = reference_value(tag + "_" + key, lambda: _live_pixelwise(use_deformed_source, sub, src, drv, sr, bg)[key])
+        assert float((got[key] - want).abs().max()) < 2e-5, key
+
+
+def _pixelwise_case(use_deformed_source):
+    from cvpr23_lfdm_amd import params as P
+    k = 4
     spec = P.generator_spec(num_channels=3, block_expansion=8, max_features=32, num_down_blocks=1, num_bottleneck_blocks=1, num_regions=k,
                             fp_block_expansion=8, fp_max_features=32, fp_num_blocks=2, use_deformed_source=use_deformed_source)
     gsd = P.synthetic_state_dict(spec, 4242)
     pre = "pixelwise_flow_predictor."
     sub = {key[len(pre):]: v for key, v in gsd.items() if key.startswith(pre)}
-    assert set(net.state_dict()) == set(sub)
-    net.load_state_dict(sub)
     g = torch.Generator().manual_seed(81)
     n = 2
     src = torch.rand(n, 3, 64, 64, generator=g)
@@ -139,12 +227,21 @@ def test_pixelwise_flow_predictor_matches_live_reference(use_deformed_source):
                   "affine": torch.eye(2).view(1, 1, 2, 2) * 0.15 + 0.03 * torch.rand(n, k, 2, 2, generator=g)}
     drv, sr = mk(), mk()
     bg = torch.eye(3).view(1, 3, 3).repeat(n, 1, 1) + 0.05 * torch.rand(n, 3, 3, generator=g)
+    return gsd, sub, src, drv, sr, bg
+
+
+def _live_pixelwise_net(use_deformed_source):
+    reference_loader.load_reference()
+    import LFAE.modules.pixelwise_flow_predictor as pfm
+    return pfm.PixelwiseFlowPredictor(block_expansion=8, num_blocks=2, max_features=32, num_regions=4, num_channels=3, estimate_occlusion_map=True,
+                                      scale_factor=0.25, use_covar_heatmap=True, use_deformed_source=use_deformed_source, revert_axis_swap=True).eval()
+
+
+def _live_pixelwise(use_deformed_source, sub, src, drv, sr, bg):
+    net = _live_pixelwise_net(use_deformed_source)
+    net.load_state_dict(sub)
     with torch.no_grad():
-        want = net(src, drv, sr, bg_params=bg)
-        got = O.pixelwise_flow_predictor({key: v.float() for key, v in gsd.items()}, src, drv, sr, bg, num_regions=k,
-                                         use_deformed_source=use_deformed_source, num_blocks=2)
-    for key in ("optical_flow", "occlusion_map"):
-        assert float((got[key] - want[key]).abs().max()) < 2e-5, key
+        return net(src, drv, sr, bg_params=bg)
 
 
 def test_p_losses_tensor_cond_quirk_is_stated(monkeypatch):
@@ -154,15 +251,16 @@ def test_p_losses_tensor_cond_quirk_is_stated(monkeypatch):
     a tensor condition trains with `none_cond_mask = None` (cvpr23_lfdm_amd/diffusion.py p_losses) - what the reference's own
     multi-GPU flavour does with a tensor (video_flow_diffusion_multiGPU.py, mask passed by the caller)."""
     import synth
-    ref = reference_loader.load_reference()
     b, t, s = 1, 2, 8
-    rm = ref.vfdm.FlowDiffusion(img_size=s, num_frames=t, sampling_timesteps=3, is_train=True, config_pth=synth.CONFIG, pretrained_pth="")
     x0 = torch.zeros(b, 3, t, s, s)
     fea = torch.zeros(b, 256, t, s, s)
     tt = torch.zeros(b, dtype=torch.long)
     cond = torch.zeros(b, 768)
-    with pytest.raises(UnboundLocalError):
-        rm.diffusion.p_losses(x0, tt, fea, cond=cond)
+    if LIVE:            # the reference's own behaviour, where its tree is present
+        ref = reference_loader.load_reference()
+        rm = ref.vfdm.FlowDiffusion(img_size=s, num_frames=t, sampling_timesteps=3, is_train=True, config_pth=synth.CONFIG, pretrained_pth="")
+        with pytest.raises(UnboundLocalError):
+            rm.diffusion.p_losses(x0, tt, fea, cond=cond)
 
     from cvpr23_lfdm_amd import FlowDiffusion
     import cvpr23_lfdm_amd.unet_train as ut
@@ -213,6 +311,7 @@ print("CALIB " + json.dumps({"shape": [b, 259, t, s, s], "threads": torch.get_nu
 """
 
 
+@pytest.mark.skipif(not LIVE, reason="times the reference itself: reference tree not present")
 def test_port_speed_is_calibrated_against_the_reference():
     """bench.py's `cpu_baseline` times the PORT (oracle/lfdm_oracle.py: /root/reference does not travel to the GPU box).  This pins what that
     number means: the reference's own `Unet3D.forward` and the port's `unet_forward` on the SAME cores, same C2-shape input (B = 1, 259
@@ -241,3 +340,40 @@ def test_port_speed_is_calibrated_against_the_reference():
         with open(os.path.join(root, "profiles", "port_vs_reference_cpu.json"), "w") as f:
             json.dump(rec, f, indent=1)
     assert 0.85 <= rec["port_over_reference"] <= 1.15, rec
+
+
+def _record():
+    """Every reference value the checks above use -> tests/golden/oracle_vs_reference.npz (needs the reference tree)."""
+    import lfdm_oracle  # noqa: F401
+    from cvpr23_lfdm_amd import params as P
+    assert LIVE, "the reference tree is needed to record its values"
+    out = {"unet": _live_unet()}
+    for lnc in (False, True):
+        out["optimizer_%d" % lnc] = _live_optimizer(lnc)
+    for bg_type in ("zero", "shift", "affine", "perspective"):
+        net, want = _live_bg(bg_type)
+        out["bg_%s_keys" % bg_type], out["bg_%s" % bg_type] = sorted(net.state_dict()), want
+    kw = dict(block_expansion=8, max_features=32, num_blocks=2, temperature=0.1, scale_factor=0.25, pca_based=False, pad=3)
+    for ea in (True, False):
+        tag = "region_%d" % ea
+        net = _live_region_net(ea)
+        out[tag + "_names"], out[tag + "_keys"] = [k for k, _ in net.named_parameters()], sorted(net.state_dict())
+        if ea:
+            out[tag + "_jacobian_bias"] = net.jacobian.bias.detach().clone()
+        sd = P.synthetic_state_dict(P.region_predictor_spec(num_regions=4, num_channels=3, estimate_affine=ea, **kw), 7171)
+        want = _live_region(ea, sd, torch.rand(2, 3, 64, 64, generator=torch.Generator().manual_seed(80)))
+        out[tag + "_out_keys"] = sorted(want)
+        out.update({tag + "_" + key: v for key, v in want.items()})
+    for uds in (True, False):
+        out["pixelwise_%d_keys" % uds] = sorted(_live_pixelwise_net(uds).state_dict())
+        _, sub, src, drv, sr, bg = _pixelwise_case(uds)
+        want = _live_pixelwise(uds, sub, src, drv, sr, bg)
+        for key in ("optical_flow", "occlusion_map"):
+            out["pixelwise_%d_%s" % (uds, key)] = want[key]
+    arrays = {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.array(json.dumps(v))) for k, v in out.items()}
+    np.savez_compressed(GOLDEN, **arrays)
+    print("wrote %s (%d entries)" % (GOLDEN, len(arrays)))
+
+
+if __name__ == "__main__":
+    _record()
