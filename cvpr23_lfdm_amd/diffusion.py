@@ -14,6 +14,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _native, ops
+from .unet import check_num_frames
 
 
 def cosine_beta_schedule(timesteps, s=0.008):
@@ -43,6 +44,7 @@ class GaussianDiffusion(nn.Module):
                  use_dynamic_thres=False, dynamic_thres_percentile=0.9, null_cond_prob=0.1,
                  per_element_loss=False):
         super().__init__()
+        check_num_frames(num_frames)
         # True = the *_multiGPU.py flavour of the reference (video_flow_diffusion_multiGPU.py:857-880):
         # un-reduced loss tensor and `(loss, null_cond_mask)` as the return value of p_losses / forward
         self.per_element_loss = per_element_loss

@@ -17,7 +17,7 @@ from .diffusion import GaussianDiffusion
 from .generator import Generator
 from .params import ParamTree, bg_predictor_spec, build_tree, region_predictor_spec
 from .optim import FlatAdam, GradAllReduce
-from .unet import Unet3D
+from .unet import Unet3D, check_num_frames
 
 
 class RegionPredictor(ParamTree):
@@ -73,6 +73,7 @@ class FlowDiffusion(nn.Module):
         bert-base-cased for `cond=list[str]` (the reference downloads it with torch.hub; see text.py).  LFDM_BERT_PATH in
         the environment is the default, so unchanged caller scripts pick it up."""
         super().__init__()
+        check_num_frames(num_frames)        # (before the checkpoint and the config are read)
         self.use_residual_flow = use_residual_flow
         self.only_use_flow = only_use_flow
         checkpoint = torch.load(pretrained_pth, map_location="cpu") if pretrained_pth != "" else None

@@ -14,6 +14,18 @@ from . import ops
 from .params import ParamTree, build_tree, unet_spec, weights_epoch
 
 BERT_MODEL_DIM = 768
+# Every temporal-attention kernel (csrc/attention*.hip, attn_lowres.hip, train_attention.hip) holds one pixel's whole sequence of
+# frames in a wavefront's registers and is built for 1 ... 64 frames.
+MAX_FRAMES = 64
+
+
+def check_num_frames(num_frames):
+    """ValueError for a frame count the temporal-attention kernels are not built for - at construction / call time, not at the
+    first temporal-attention launch in the middle of a sample or training step."""
+    if not 1 <= int(num_frames) <= MAX_FRAMES:
+        raise ValueError("num_frames = %d: the temporal-attention kernels are built for 1 ... %d frames" % (int(num_frames), MAX_FRAMES))
+
+
 # Default-on fusions keep ONE switch each for A/B profiling and for the bit-compare tests (LFDM_x=0 -> the separate launches):
 _LOWRES_ATTN = os.environ.get("LFDM_LOWRES_ATTN", "1") != "0"       # one-launch attention blocks at <= 64 pixels per frame
 # measured (tools/bench_attn_lowres.py, profiles/r03_f_bench_attn_lowres.txt): the one-launch kernels win at <= 64 pixels per frame
@@ -577,6 +589,7 @@ class Unet3D(ParamTree):
         (fea may differ per frame here; the samplers use the cheaper split path where it is constant)."""
         if self.has_cond and cond is None:
             raise AssertionError("cond must be passed in if cond_dim specified")
+        check_num_frames(x.shape[2])
         # :542-543: drawn BEFORE the null-condition mask (it consumes the RNG for 0 < prob < 1)
         if focus_present_mask is None and prob_focus_present in (0, 1):      # (no random draw, no device round trip)
             focus = [True] * x.shape[0] if prob_focus_present == 1 else None

@@ -44,6 +44,37 @@ def test_unet_forward(backend, variant):
         assert_close(out.cpu(), ref, 2e-4, "unet forward (%s, null=%s)" % (variant, null_prob))
 
 
+@pytest.mark.parametrize("num_frames", [1, 17, 64])
+def test_unet_forward_frames(backend, num_frames):
+    """Unet3D.forward at frame counts the headline shapes do not reach: one frame (BASELINE configs[0], a 32x32 latent), 17 (the
+    32-frame temporal kernels) and 64 (the limit: the 64-frame kernels) against the oracle."""
+    dev = backend
+    _skip_slow_emu(dev)
+    b, s = {1: (2, 32), 17: (1, 16), 64: (1, 8)}[num_frames] if dev == "cuda" else (1, 8)
+    m, dsd, _ = synth.build_flow_diffusion(dev, img_size=s, num_frames=num_frames, sampling_timesteps=5)
+    x, time, cond = synth.unet_inputs(b, num_frames, s, seed=4)
+    ref = O.unet_forward(dsd, x, time, cond)
+    with torch.no_grad():
+        out = m.unet.forward(x.to(dev), time.to(dev), cond=cond.to(dev))
+    assert_close(out.cpu(), ref, 2e-4, "unet forward, %d frames" % num_frames)
+
+
+def test_frame_limit():
+    """Every temporal-attention kernel stops at 64 frames: a model for more (or none) is refused when it is constructed, and a UNet
+    call with more frames before any launch - not by the first temporal-attention launch in the middle of a sample or training step."""
+    from cvpr23_lfdm_amd.unet_train import unet_train_forward
+    for bad in (65, 0):
+        with pytest.raises(ValueError, match="64"):
+            synth.build_flow_diffusion("cpu", img_size=8, num_frames=bad, sampling_timesteps=1)
+    m, _, _ = synth.build_flow_diffusion("cpu", img_size=8, num_frames=64, sampling_timesteps=1)
+    assert m.diffusion.num_frames == 64
+    x, time, cond = synth.unet_inputs(1, 65, 4)
+    with pytest.raises(ValueError, match="64"), torch.no_grad():
+        m.unet.forward(x, time, cond=cond)
+    with pytest.raises(ValueError, match="64"):
+        unet_train_forward(m.unet, x[:, :3], x[:, 3:, 0].contiguous(), time, cond)
+
+
 def test_generator(backend):
     dev = backend
     _skip_slow_emu(dev)
@@ -90,6 +121,29 @@ def test_sample_one_video(backend, sampler, tmp_path):
         io_compat.mimsave(str(tmp_path / "demo.gif"), frames)
         with Image.open(str(tmp_path / "demo.gif")) as gif:
             assert gif.n_frames == z["t"] and gif.size == (5 * z["hw"], z["hw"])
+
+
+def test_sample_one_video_single_frame(backend):
+    """BASELINE configs[0] (demo_mug.py): one 128x128 frame, a one-step schedule (timesteps = sampling_timesteps = 1: one DDPM step)
+    against the oracle on a noise tape - decoded and warped frames, grid and confidence."""
+    dev = backend
+    _skip_slow_emu(dev)
+    t, s, hw, total = 1, 32, 128, 1
+    m, dsd, gsd = synth.build_flow_diffusion(dev, img_size=s, num_frames=t, sampling_timesteps=1, timesteps=total)
+    assert not m.diffusion.is_ddim_sampling and m.diffusion.num_timesteps == 1
+    sched = O.make_schedule(total)                # (the reference's one-entry schedule)
+    for k, v in sched.items():
+        assert torch.equal(getattr(m.diffusion, k).cpu(), v), k
+    img, cond = synth.inputs(1, hw, seed=13)
+    sd = dict(dsd)
+    sd.update(sched)
+    ref = O.sample_one_video(sd, gsd, img, cond, t, s, 1, timesteps=total, noise_fn=synth.NoiseTape(13))
+    m.diffusion.noise_source = synth.NoiseTape(13)
+    m.set_sample_input(sample_img=img.to(dev), sample_text=cond.to(dev))
+    m.sample_one_video(cond_scale=1.0)
+    for k in ("sample_vid_grid", "sample_vid_conf", "sample_warped_vid", "sample_out_vid"):
+        assert getattr(m, k).shape[2] == 1, k
+        assert_close(getattr(m, k).cpu(), ref[k], 1e-3, "%s (one frame, one DDPM step)" % k)
 
 
 @pytest.mark.parametrize("mode", ["cfg2", "cfg0", "residual_flow"])

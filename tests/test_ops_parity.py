@@ -193,40 +193,71 @@ def test_conv_downsample_gather(backend, case):
         assert_close(from_cl(out.cpu(), n, h // 2, w // 2), ref, TOL, "Downsample on the gather form, operand-order pack %s" % (wpw is not None))
 
 
-@pytest.mark.parametrize("case", [dict(c0=64, c1=0, cout=128, b=2, t=2, hw=(4, 4), nchunk=2), dict(c0=256, c1=256, cout=256, b=1, t=5, hw=(8, 8), nchunk=5),
-                                  dict(c0=512, c1=512, cout=512, b=1, t=40, hw=(4, 4), nchunk=10, big=True), dict(c0=64, c1=0, cout=128, b=1, t=40, hw=(16, 16), nchunk=80, big=True)],
-                         ids=lambda c: "-".join("%s%s" % (k, v) for k, v in c.items()))
-def test_conv_pointwise_residual_groupnorm(backend, case):
+def _pw_tile(k, coutp, m):
+    """(TN, KW) lfdm_conv_pw_shape picks without overrides: K across KW waves while the slices stay multiples of 32; 96-column tiles
+    per wave for a few wide-output rows, else 32.  The workgroup's column width is BN = (4 / KW) * TN * 32."""
+    kw = 4 if k % 128 == 0 else 2 if k % 64 == 0 else 1
+    return (3 if m <= 1024 and coutp >= 768 and coutp % ((4 // kw) * 96) == 0 else 1), kw
+
+
+# The residual-GroupNorm epilogue fills a (gamma, beta) table of BN columns with 256 threads.  The cases cover every (TN, KW) tile shape, i.e.
+# BN = 32 ... 384: the planner's own choice (both backends; TN = 3, KW = 1 is the 384-column tile) and forced shapes (tn / kw: the
+# LFDM_PW_TN / LFDM_PW_KW overrides are read by the emulator and by a `--knobs` build only), cout multiples of 384 and of 256, 8 and 32 groups.
+_RES_GN_CASES = [
+    dict(c0=64, c1=0, cout=128, b=2, t=2, hw=(4, 4), nchunk=2),
+    dict(c0=256, c1=256, cout=256, b=1, t=5, hw=(8, 8), nchunk=5),
+    dict(c0=96, c1=0, cout=768, b=1, t=2, hw=(4, 4), nchunk=2),                         # natural TN = 3, KW = 1: BN = 384
+    dict(c0=96, c1=0, cout=1152, b=1, t=2, hw=(4, 4), nchunk=2, groups=32),             # ... three 384-column tiles, 36-channel groups
+    dict(c0=96, c1=96, cout=768, b=2, t=2, hw=(4, 4), nchunk=1, groups=32),             # natural TN = 3, KW = 2: BN = 192
+    dict(c0=128, c1=0, cout=768, b=1, t=2, hw=(4, 4), nchunk=2, groups=32),             # natural TN = 3, KW = 4: BN = 96
+    dict(c0=96, c1=0, cout=384, b=1, t=2, hw=(4, 4), nchunk=2),                         # natural TN = 1, KW = 1: BN = 128
+    dict(c0=64, c1=0, cout=512, b=1, t=2, hw=(4, 4), nchunk=1, groups=32),              # natural TN = 1, KW = 2: BN = 64
+] + [dict(c0=128, c1=0, cout=cout, b=1, t=2, hw=(4, 4), nchunk=2, groups=g, tn=tn, kw=kw)
+     for tn in (1, 2, 3) for kw in (1, 2, 4) for cout, g in ((384, 8), (512, 32), (768, 32))] + [
+    dict(c0=512, c1=512, cout=512, b=1, t=40, hw=(4, 4), nchunk=10, big=True),
+    dict(c0=64, c1=0, cout=128, b=1, t=40, hw=(16, 16), nchunk=80, big=True),
+    dict(c0=96, c1=0, cout=768, b=1, t=40, hw=(4, 4), nchunk=10, big=True),             # 640 rows: still the 384-column tile
+]
+
+
+@pytest.mark.parametrize("case", _RES_GN_CASES, ids=lambda c: "-".join("%s%s" % (k, v) for k, v in c.items()))
+def test_conv_pointwise_residual_groupnorm(backend, case, monkeypatch):
     """lfdm_conv_params.res_gn_*: ResnetBlock.forward's `h + res_conv(x)` (video_flow_diffusion.py:226-238) with block2's GroupNorm + SiLU folded into
     the res_conv launch - the residual operand is the RAW convolution output, its statistics arrive as chunked (sum, sum of squares) partials -
-    against conv1x1(cat(x0, x1)) + bias + silu(group_norm(raw)); out aliases the residual, as the sampler uses it."""
+    against a float64 conv1x1(cat(x0, x1)) + bias + silu(group_norm(raw)); out aliases the residual, as the sampler uses it."""
     dev = backend
     if case.get("big") and not big(dev):
         pytest.skip("full-size shape runs on the GPU")
+    if "tn" in case and dev != "cpu":
+        pytest.skip("tile-shape overrides are read by the emulator and by a --knobs build only; the GPU runs the planner's shapes above")
+    for k_, e_ in (("tn", "LFDM_PW_TN"), ("kw", "LFDM_PW_KW")):
+        if k_ in case:
+            monkeypatch.setenv(e_, str(case[k_]))
     c0, c1, cout, b, t, nchunk = (case[k] for k in ("c0", "c1", "cout", "b", "t", "nchunk"))
+    groups = case.get("groups", 8)
     h, w = case["hw"]
     n, pixels = b * t, t * h * w
     x = rnd(n, c0 + c1, h, w, seed=1)
     wt = rnd(cout, c0 + c1, 1, 1, seed=2, scale=1.0 / math.sqrt(c0 + c1))
     bias, gamma, beta = rnd(cout, seed=3), rnd(cout, seed=4) * 0.3 + 1, rnd(cout, seed=5) * 0.3
     raw = rnd(n * h * w, cout, seed=6) * 1.5 + 0.2                                     # channels-last rows of the raw block2 convolution
-    rs = raw.view(b, pixels, cout)
-    act = F.silu(F.group_norm(rs.permute(0, 2, 1), 8, gamma, beta, eps=1e-5).permute(0, 2, 1)).reshape(n * h * w, cout)
-    ref = to_cl(F.conv2d(x, wt, bias)) + act
-    rg = rs.view(b, nchunk, pixels // nchunk, 8, cout // 8)
-    partial = torch.stack([rg.sum(dim=(2, 4)), (rg * rg).sum(dim=(2, 4))], dim=-1).contiguous().view(b * nchunk, 16)
+    rs = raw.double().view(b, pixels, cout)
+    act = F.silu(F.group_norm(rs.permute(0, 2, 1), groups, gamma.double(), beta.double(), eps=1e-5).permute(0, 2, 1)).reshape(n * h * w, cout)
+    ref = to_cl(F.conv2d(x.double(), wt.double(), bias.double())) + act
+    rg = rs.view(b, nchunk, pixels // nchunk, groups, cout // groups)
+    partial = torch.stack([rg.sum(dim=(2, 4)), (rg * rg).sum(dim=(2, 4))], dim=-1).float().contiguous().view(b * nchunk, 2 * groups)
     xs = to_cl(x).to(dev)
     src0, src1 = (xs, None) if not c1 else (xs[:, :c0].contiguous(), xs[:, c0:].contiguous())
     out = raw.clone().to(dev)
-    res_gn = dict(partial=partial.to(dev), nchunk=nchunk, pixels=pixels, gamma=gamma.to(dev), beta=beta.to(dev), groups=8)
+    res_gn = dict(partial=partial.to(dev), nchunk=nchunk, pixels=pixels, gamma=gamma.to(dev), beta=beta.to(dev), groups=groups)
     kw = dict(src1=src1, bias=bias.to(dev), residual=out, out=out, res_gn=res_gn)
     pp, _ = ops.conv_params(src0, ops.pack_conv_weight(wt).to(dev), cout, 1, 1, n, h, w, **kw)
     assert ops.conv_schedule(pp) == 3
     got = ops.conv2d_cl(src0, ops.pack_conv_weight(wt).to(dev), cout, 1, 1, n, h, w, **kw)
-    assert_close(got.cpu(), ref, TOL, "1x1 convolution + GroupNorm + SiLU of the raw residual")
+    tn, kw_ = (case["tn"], case["kw"]) if "tn" in case else _pw_tile(c0 + c1, (cout + 31) // 32 * 32, n * h * w)
+    assert_close(got.cpu(), ref, TOL, "1x1 convolution + GroupNorm + SiLU of the raw residual, TN %d KW %d" % (tn, kw_))
     with pytest.raises(RuntimeError):            # a 3x3 convolution cannot take it: refused, not mis-computed
         ops.conv2d_cl(src0, ops.pack_conv_weight(rnd(cout, c0 + c1, 3, 3, seed=9)).to(dev), cout, 3, 3, n, h, w, **kw)
-
 
 
 def test_conv_pointwise_plan():
@@ -925,6 +956,201 @@ def test_attention_lowres(backend, c, frames, s, mode):
         kw = {}
     out = ops.attention_lowres_cl(unet_to_cl(x).to(dev), wf.to(dev), wsum.to(dev), b, frames, hw, mode, **kw)
     assert_close(out.cpu(), ref, TOL, "low-res LN + qkv + attention, mode %d" % mode)
+
+
+# ------------------------------------------------------------------------------------------
+# Dispatch edges.  Every attention launcher picks a template instantiation from the sequence length (frames in mode 0, pixels in mode 1),
+# the pointwise convolution a tile shape from the geometry; the parity tests above pin the shapes the shipped configurations use.  The tests
+# below reach every branch of every ladder at its edges, against float64 references.  Coverage (test ids without the backend):
+#
+#   lfdm_temporal_attention_fused_out_cl_f32 (C = 64)
+#     <16,16> frames 1, 2, 16 | <32,32> 17, 32 | <48,40> 33, 40 | <48,48> 41, 48 | <64,64> 49, 64: each at 1 / 2 / 4 / 8 waves per sequence
+#     and the launcher's own choice          test_temporal_attention_block_frame_edges[<frames>]
+#   lfdm_temporal_attention_fused_cl_f32
+#     temporal_attn_fused_kernel<16|32|48|64, 64>        test_temporal_attention_fused_frame_edges[64-<frames>]
+#     temporal_attn_fused_wide_kernel<16|32|48|64>       test_temporal_attention_fused_frame_edges[128-<frames>], [192-<frames>]
+#   lfdm_attention_lowres_cl_f32  attn_lowres_kernel<1|2|3|4>
+#     mode 0 (frames 1 ... 64)                           test_attention_frame_edges[<frames>]
+#     mode 1 (pixels 1, 16 | 17, 32 | 33, 48 | 49, 64)   test_spatial_attention_token_edges[<hw>]
+#   lfdm_attention_cl_f32  attention_kernel<16|32|48|64>: mode 0 and mode 1 in the same two tests
+#   lfdm_linear_attention_lowres_cl_f32
+#     linattn_lowres_kernel<1,false> hw 1 | <2,false> 17, 32 | <4,false> 64 | <4,true> 193, 256
+#                                                        test_linear_attention_lowres_pixel_edges[<hw>]
+#     65 ... 192 pixels (not built) refused              test_linear_attention_lowres_refuses_unbuilt_widths
+#   65 frames / 65 tokens refused by every softmax-attention entry point, forward and backward
+#                                                        test_attention_refuses_65_tokens
+#   lfdm_attention_bwd_cl_f32  attention_bwd_kernel<16,4> 1, 4 | <32,4> 17, 32 | <48,4,40> 36, 40 | <48,4> 44 | <64,2> 64
+#                                                        tests/test_train_ops.py::test_attention_temporal_bwd[<frames>]
+#     mode 1: <16,4> 1, 16 | <32,4> 17, 32 | <64,2> 64   tests/test_train_ops.py::test_attention_spatial_bwd[<hw>]
+#   conv_pw_kernel<TN, KW> with the residual-GroupNorm epilogue, BN = 32 ... 384 columns
+#                                                        test_conv_pointwise_residual_groupnorm (the table above it)
+#   whole model: tests/test_end_to_end.py::test_unet_forward_frames[1|17|64], ::test_sample_one_video_single_frame (BASELINE configs[0]),
+#   tests/test_unet_train.py::test_unet_train_grads[one_frame]; the 64-frame limit at construction: tests/test_end_to_end.py::test_frame_limit
+FRAME_EDGES = [1, 2, 16, 17, 32, 33, 40, 41, 48, 49, 64]
+
+
+def _temporal_tables(frames, dev):
+    """Relative-position bias (8, f, f) and rotary tables of `frames` frames: float64 copies for the reference, fp32 kernel arguments."""
+    emb = rnd(32, 8, seed=4)
+    bias = O.rel_pos_bias(emb, frames)
+    freqs = 1.0 / (10000 ** (torch.arange(0, 32, 2).float() / 32))
+    cos, sin = O.rotary_tables(freqs, frames)
+    kw = dict(bias=bias.contiguous().to(dev), rot_cos=cos[:, 0::2].contiguous().to(dev), rot_sin=sin[:, 0::2].contiguous().to(dev))
+    return bias.double(), (cos.double(), sin.double()), kw
+
+
+def _ln_qkv_case(c, b, frames, hw, mode, dev):
+    """x (b, c, frames, hw, 1), the gamma-folded to_qkv weight and the float64 attention of LayerNorm(x) (CL row order (b, t, pix))."""
+    x = rnd(b, c, frames, hw, 1, seed=1) * 2 + 0.5
+    gamma = rnd(1, c, 1, 1, 1, seed=2) * 0.3 + 1
+    wf = (rnd(768, c, seed=3, scale=1.0 / math.sqrt(c)) * gamma.reshape(1, c)).contiguous()
+    normed = O.channel_layernorm(x.double(), torch.ones((), dtype=torch.float64))
+    if mode == 0:
+        bias, rot, kw = _temporal_tables(frames, dev)
+        tokens = normed.permute(0, 3, 4, 2, 1).reshape(b, hw, frames, c)
+        ref = _attention_ref(tokens @ wf.double().t(), bias, rot).permute(0, 2, 1, 3).reshape(-1, 256)
+    else:
+        kw = {}
+        tokens = normed.permute(0, 2, 3, 4, 1).reshape(b, frames, hw, c)
+        ref = _attention_ref(tokens @ wf.double().t(), None, None).reshape(-1, 256)
+    return x, wf, ref, kw
+
+
+@pytest.mark.parametrize("frames", FRAME_EDGES)
+def test_temporal_attention_block_frame_edges(backend, frames, monkeypatch):
+    """The whole temporal-attention block in one launch (C = 64, every UNet level-0 block) at every frame-count edge and every
+    waves-per-sequence split; on the GPU at the level-0 pixel count (1024 sequences)."""
+    dev = backend
+    b, hw = (1, 1024) if big(dev) else (1, 2)
+    x, wf, ref, kw = _ln_qkv_case(64, b, frames, hw, 0, dev)
+    wo = rnd(64, 256, seed=9, scale=1.0 / 16)
+    xcl = unet_to_cl(x)
+    ref_out = xcl.double() + ref @ wo.double().t()
+    wqp, wop = ops.pack_tattn_weights(wf, wo)
+    for nw in ("1", "2", "4", "8", None):
+        if nw is None:
+            monkeypatch.delenv("LFDM_TATTN_OUT_NW", raising=False)
+        else:
+            monkeypatch.setenv("LFDM_TATTN_OUT_NW", nw)
+        got = ops.temporal_attention_fused_out_cl(xcl.to(dev), wqp.to(dev), wop.to(dev), b, frames, hw, **kw)
+        assert_close(got.cpu(), ref_out, TOL, "temporal attention block, %d frames, %s waves per sequence" % (frames, nw))
+
+
+@pytest.mark.parametrize("frames", FRAME_EDGES)
+@pytest.mark.parametrize("c", [64, 128, 192])
+def test_temporal_attention_fused_frame_edges(backend, c, frames):
+    """LayerNorm + to_qkv + temporal attention in one launch: the C = 64 kernel and the wide (C > 64) kernel at every frame-count edge."""
+    dev = backend
+    b, hw = ((1, 1024) if c == 64 else (2, 64)) if big(dev) else (1, 2)
+    x, wf, ref, kw = _ln_qkv_case(c, b, frames, hw, 0, dev)
+    out = ops.temporal_attention_fused_cl(unet_to_cl(x).to(dev), wf.to(dev), b, frames, hw, **kw)
+    assert_close(out.cpu(), ref, TOL, "fused LN + qkv + temporal attention, C %d, %d frames" % (c, frames))
+
+
+@pytest.mark.parametrize("frames", FRAME_EDGES)
+def test_attention_frame_edges(backend, frames):
+    """Mode 0 (over the frames of a pixel, rotary + relative-position bias) of the low-resolution fused attention and of the unfused
+    attention core at every frame-count edge."""
+    dev = backend
+    b, hw = (2, 64) if big(dev) else (1, 2)
+    x, wf, ref, kw = _ln_qkv_case(128, b, frames, hw, 0, dev)
+    wsum = wf.double().sum(dim=1).float()
+    out = ops.attention_lowres_cl(unet_to_cl(x).to(dev), wf.to(dev), wsum.to(dev), b, frames, hw, 0, **kw)
+    assert_close(out.cpu(), ref, TOL, "low-res LN + qkv + attention, mode 0, %d frames" % frames)
+    qkv = rnd(b, frames, hw, 768, seed=5)
+    bias, rot, kw = _temporal_tables(frames, dev)
+    ref = _attention_ref(qkv.double().permute(0, 2, 1, 3), bias, rot).permute(0, 2, 1, 3).reshape(-1, 256)
+    out = ops.attention_cl(qkv.reshape(-1, 768).to(dev), b, frames, hw, 0, **kw)
+    assert_close(out.cpu(), ref, TOL, "attention core, mode 0, %d frames" % frames)
+
+
+@pytest.mark.parametrize("hw", [1, 16, 17, 32, 33, 48, 49, 64])
+def test_spatial_attention_token_edges(backend, hw):
+    """Mode 1 (over the pixels of a frame: the mid blocks; 49 ... 64 = the 8x8 level of the 256x256 configuration) of the low-resolution
+    fused attention and of the unfused attention core at every token-count edge."""
+    dev = backend
+    b, frames = (2, 40) if big(dev) else (1, 2)
+    x, wf, ref, _ = _ln_qkv_case(128, b, frames, hw, 1, dev)
+    wsum = wf.double().sum(dim=1).float()
+    out = ops.attention_lowres_cl(unet_to_cl(x).to(dev), wf.to(dev), wsum.to(dev), b, frames, hw, 1)
+    assert_close(out.cpu(), ref, TOL, "low-res LN + qkv + attention, mode 1, %d pixels" % hw)
+    qkv = rnd(b, frames, hw, 768, seed=5)
+    ref = _attention_ref(qkv.double(), None, None).reshape(-1, 256)
+    out = ops.attention_cl(qkv.reshape(-1, 768).to(dev), b, frames, hw, 1)
+    assert_close(out.cpu(), ref, TOL, "attention core, mode 1, %d pixels" % hw)
+
+
+def _linear_attention_ref(x, wf):
+    """float64 LayerNorm (gamma folded into wf) + to_qkv + SpatialLinearAttention core; x (nf, hw, c)."""
+    nf, hw, c = x.shape
+    xd = x.double()
+    normed = (xd - xd.mean(dim=-1, keepdim=True)) / (xd.var(dim=-1, unbiased=False, keepdim=True) + 1e-5).sqrt()
+    qkv = normed @ wf.double().t()
+    q, k, v = [z.reshape(nf, hw, 8, 32).permute(0, 2, 3, 1) for z in qkv.chunk(3, dim=-1)]  # b h d n
+    q = q.softmax(dim=-2) * (32 ** -0.5)
+    k = k.softmax(dim=-1)
+    ctx = torch.einsum("bhdn,bhen->bhde", k, v)
+    return torch.einsum("bhde,bhdn->bhen", ctx, q).permute(0, 3, 1, 2).reshape(nf * hw, 256)
+
+
+@pytest.mark.parametrize("hw", [1, 17, 32, 64, 193, 256])
+def test_linear_attention_lowres_pixel_edges(backend, hw):
+    """LayerNorm + to_qkv + linear attention in one launch at every pixel-count edge of its ladder (1 - 2 - 4 row tiles, the split-row form)."""
+    dev = backend
+    c, nf = (128, 40) if big(dev) else (64, 2)
+    x = rnd(nf, hw, c, seed=1) * 2 + 0.3
+    gamma = rnd(c, seed=2) * 0.3 + 1
+    wf = (rnd(768, c, seed=3, scale=1.0 / math.sqrt(c)) * gamma.reshape(1, -1)).contiguous()
+    wsum = wf.double().sum(dim=1).float()
+    assert ops.linear_attention_lowres_ok(hw, c)
+    out = ops.linear_attention_lowres_cl(x.reshape(-1, c).to(dev), wf.to(dev), wsum.to(dev), nf, hw)
+    assert_close(out.cpu(), _linear_attention_ref(x, wf), TOL, "low-res LN + qkv + linear attention, %d pixels" % hw)
+
+
+@pytest.mark.parametrize("hw", [65, 128, 192, 257])
+def test_linear_attention_lowres_refuses_unbuilt_widths(backend, hw):
+    """65 ... 192 pixels per frame (and more than 256) are not built: refused by the entry point, not mis-computed."""
+    dev = backend
+    c, nf = 64, 1
+    assert not ops.linear_attention_lowres_ok(hw, c)
+    x = rnd(nf * hw, c, seed=1).to(dev)
+    wf = rnd(768, c, seed=3).to(dev)
+    out = torch.full((nf * hw, 256), 7.0, device=dev)
+    with pytest.raises(RuntimeError):
+        ops.linear_attention_lowres_cl(x, wf, wf.sum(dim=1).contiguous(), nf, hw, out=out)
+    assert bool((out == 7.0).all())
+
+
+def test_attention_refuses_65_tokens(backend):
+    """Every softmax-attention kernel stops at 64 tokens per sequence: 65 frames (mode 0) or 65 pixels (mode 1) are refused by each entry
+    point, forward and backward, before anything is written."""
+    from cvpr23_lfdm_amd import train_ops
+    dev = backend
+    b, hw, frames = 1, 1, 65
+    _, _, kw = _temporal_tables(frames, dev)
+    x = rnd(frames * hw, 64, seed=1).to(dev)
+    xw = rnd(frames * hw, 128, seed=1).to(dev)
+    wf, wf128 = rnd(768, 64, seed=2).to(dev), rnd(768, 128, seed=2).to(dev)
+    wqp, wop = (t.to(dev) for t in ops.pack_tattn_weights(rnd(768, 64, seed=2), rnd(64, 256, seed=3)))
+    qkv = rnd(frames * hw, 768, seed=4).to(dev)
+    calls = {
+        "temporal_attention_fused_out_cl": lambda: ops.temporal_attention_fused_out_cl(x, wqp, wop, b, frames, hw, **kw),
+        "temporal_attention_fused_cl C 64": lambda: ops.temporal_attention_fused_cl(x, wf, b, frames, hw, **kw),
+        "temporal_attention_fused_cl C 128": lambda: ops.temporal_attention_fused_cl(xw, wf128, b, frames, hw, **kw),
+        "attention_lowres_cl mode 0": lambda: ops.attention_lowres_cl(xw, wf128, wf128.sum(dim=1).contiguous(), b, frames, hw, 0, **kw),
+        "attention_lowres_cl mode 1": lambda: ops.attention_lowres_cl(xw, wf128, wf128.sum(dim=1).contiguous(), b, 1, frames, 1),
+        "attention_cl mode 0": lambda: ops.attention_cl(qkv, b, frames, hw, 0, **kw),
+        "attention_cl mode 1": lambda: ops.attention_cl(qkv, b, 1, frames, 1),
+        "attention_bwd mode 0": lambda: train_ops.attention_bwd(qkv, rnd(frames * hw, 256, seed=5).to(dev), b, frames, hw, 0, **kw),
+        "attention_bwd mode 1": lambda: train_ops.attention_bwd(qkv, rnd(frames * hw, 256, seed=5).to(dev), b, 1, frames, 1),
+    }
+    for what, call in calls.items():
+        try:
+            call()
+        except RuntimeError as e:
+            assert "64" in str(e), (what, str(e))       # the message names the limit
+            continue
+        pytest.fail("%s accepted a 65-token sequence" % what)
 
 
 @pytest.mark.parametrize("cin,k,h,w", [(16, 7, 20, 18), (64, 7, 16, 16), (32, 3, 5, 33)])

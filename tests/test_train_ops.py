@@ -129,7 +129,8 @@ def _attention_ref(qkv_tokens, bias, rotary):
     return out.transpose(-2, -3).reshape(*qkv_tokens.shape[:-1], 256)
 
 
-@pytest.mark.parametrize("frames", [4, 36, 40, 44, 64])      # 33..40 frames: the 40-row / five-wave form (36: zero rows inside the tile)
+# 1 / 17 / 32 (the dispatch edges of <16,4> and <32,4>; the float64 reference): see the coverage table of tests/test_ops_parity.py
+@pytest.mark.parametrize("frames", [1, 4, 17, 32, 36, 40, 44, 64])      # 33..40 frames: the 40-row / five-wave form (36: zero rows inside the tile)
 def test_attention_temporal_bwd(backend, frames):
     import lfdm_oracle as O
     dev = backend
@@ -137,31 +138,41 @@ def test_attention_temporal_bwd(backend, frames):
     if not big(dev) and frames >= 36:
         b, s = 1, (3 if frames == 40 else 1)     # few sequences under the emulator; 64 frames = the 2-wave LP=64 variant
     hw = s * s
-    qkv = rnd(b, frames, hw, 768, seed=1).requires_grad_(True)
+    dt = torch.float64 if frames in (1, 17, 32) else torch.float32
+    qkv32 = rnd(b, frames, hw, 768, seed=1)
+    qkv = qkv32.to(dt).requires_grad_(True)
     emb = rnd(32, 8, seed=2)
-    bias = O.rel_pos_bias(emb, frames).clone().requires_grad_(True)
+    bias32 = O.rel_pos_bias(emb, frames)
+    bias = bias32.to(dt).clone().requires_grad_(True)
     freqs = 1.0 / (10000 ** (torch.arange(0, 32, 2).float() / 32))
     cos, sin = O.rotary_tables(freqs, frames)
-    out = _attention_ref(qkv.permute(0, 2, 1, 3), bias, (cos, sin)).permute(0, 2, 1, 3).reshape(-1, 256)
+    out = _attention_ref(qkv.permute(0, 2, 1, 3), bias, (cos.to(dt), sin.to(dt))).permute(0, 2, 1, 3).reshape(-1, 256)
     dout = rnd(*out.shape, seed=3)
-    out.backward(dout)
-    dqkv, dbias = train_ops.attention_bwd(qkv.detach().reshape(-1, 768).to(dev), dout.to(dev), b, frames, hw, 0,
-                                          bias=bias.detach().contiguous().to(dev),
+    out.backward(dout.to(dt))
+    dqkv, dbias = train_ops.attention_bwd(qkv32.reshape(-1, 768).to(dev), dout.to(dev), b, frames, hw, 0,
+                                          bias=bias32.contiguous().to(dev),
                                           rot_cos=cos[:, 0::2].contiguous().to(dev), rot_sin=sin[:, 0::2].contiguous().to(dev))
     assert_close(dqkv.cpu(), qkv.grad.reshape(-1, 768), TOL, "temporal attention dqkv")
+    if frames == 1:
+        # one key per query: the softmax is the constant 1, so the bias has no gradient (and no scale to normalise by)
+        assert float(bias.grad.abs().max()) == 0.0
+        assert float(dbias.cpu().abs().max()) == 0.0, "temporal attention dbias at one frame"
+        return
     sc = float(bias.grad.abs().max())
     assert_close(dbias.cpu() / sc, bias.grad / sc, TOL, "temporal attention dbias")
 
 
-@pytest.mark.parametrize("hw", [16, 64])
+@pytest.mark.parametrize("hw", [1, 16, 17, 32, 64])       # 1 / 17 / 32: dispatch edges, float64 reference
 def test_attention_spatial_bwd(backend, hw):
     dev = backend
     b, frames = 1, 3
-    qkv = rnd(b, frames, hw, 768, seed=3).requires_grad_(True)
+    dt = torch.float64 if hw in (1, 17, 32) else torch.float32
+    qkv32 = rnd(b, frames, hw, 768, seed=3)
+    qkv = qkv32.to(dt).requires_grad_(True)
     out = _attention_ref(qkv, None, None).reshape(-1, 256)
     dout = rnd(*out.shape, seed=4)
-    out.backward(dout)
-    dqkv, _ = train_ops.attention_bwd(qkv.detach().reshape(-1, 768).to(dev), dout.to(dev), b, frames, hw, 1)
+    out.backward(dout.to(dt))
+    dqkv, _ = train_ops.attention_bwd(qkv32.reshape(-1, 768).to(dev), dout.to(dev), b, frames, hw, 1)
     assert_close(dqkv.cpu(), qkv.grad.reshape(-1, 768), TOL, "spatial attention dqkv")
 
 

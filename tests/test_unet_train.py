@@ -45,7 +45,7 @@ def _run(dev, b, t, s, learn_null=False, null_mask=None, use_deconv=True, paddin
     assert worst[1] < 2e-3, "largest relative gradient error %.3e at %s" % (worst[1], worst[0])
 
 
-@pytest.mark.parametrize("case", ["plain", "null_cond", "upconv_reflect", "focus_mixed", "focus_all"])
+@pytest.mark.parametrize("case", ["plain", "null_cond", "upconv_reflect", "focus_mixed", "focus_all", "one_frame"])
 def test_unet_train_grads(backend, case):
     dev = backend
     if dev == "cpu":
@@ -62,5 +62,7 @@ def test_unet_train_grads(backend, case):
         _run(dev, 3, 3, 8, focus=[True, False, True])
     elif case == "focus_all":        # (:313-317: to_qkv's q / k rows get no gradient from the blocks' temporal attentions)
         _run(dev, 2, 3, 8, focus=[True, True])
+    elif case == "one_frame":        # BASELINE configs[0]'s T = 1: one-entry softmax in every temporal attention, no bias gradient
+        _run(dev, 2, 1, 8)
     else:   # the NATOPS configuration: learned null cond, nearest-upsample + reflect-pad Upsample
         _run(dev, 1, 2, 8, learn_null=True, use_deconv=False, padding_mode="reflect")
