@@ -130,6 +130,7 @@ _SIGNATURES = {
     "lfdm_abi_version": (i32, []),
     "lfdm_calib_mfma_f32": (i32, [f32p, i32, i32, stream_t]),
     "lfdm_conv2d_cl_f32": (i32, [C.POINTER(ConvParams), stream_t]),
+    "lfdm_conv2d_cl_wino_bf16": (i32, [C.POINTER(ConvParams), C.c_void_p, stream_t]),
     "lfdm_conv2d_partial_bytes": (sz, [C.POINTER(ConvParams)]),
     "lfdm_conv2d_plan": (i32, [C.POINTER(ConvParams), C.POINTER(i32), C.POINTER(i32)]),
     "lfdm_conv2d_plan_slabs": (i32, [C.POINTER(ConvParams)]),
@@ -149,6 +150,7 @@ _SIGNATURES = {
     "lfdm_attention_lowres_cl_f32": (i32, [f32p, i32, i32, f32p, f32p, f32p, i32, i32, i32, i32, f32p, f32p, f32p, f32, stream_t]),
     "lfdm_pack_wino_weight_f32": (i32, [f32p, i32, i32, i32, i32, i32, f32p, stream_t]),
     "lfdm_pack_wino4_weight_f32": (i32, [f32p, i32, i32, i32, i32, f32p, stream_t]),
+    "lfdm_pack_wino_weight_bf16": (i32, [f32p, i32, i32, i32, i32, C.c_void_p, stream_t]),
     "lfdm_pack_conv_weight_f32": (i32, [f32p, i32, i32, i32, i64, i64, i32, f32p, stream_t]),
     "lfdm_lfae_motion_inputs_f32": (i32, [f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p, C.c_float, i32, i32, i32, i32, i32, i32,
                                           f32p, i32, f32p, stream_t]),

@@ -702,6 +702,7 @@ void launch_conv(const lfdm_conv_params& p, bool fast, bool simple, dim3 grid, h
 
 int lfdm_conv_ksw_launch(const lfdm_conv_params& p, int bn, hipStream_t stream);   // conv_ksw.hip
 int lfdm_conv_wino_launch(const lfdm_conv_params& p, int bn, bool fuse_reduce, int bal_whole, hipStream_t stream);  // conv_wino.hip
+int lfdm_conv_wino_bf16_launch(const lfdm_conv_params& p, const void* weight_bf16, int bn, bool fuse_reduce, int bal_whole, hipStream_t stream);
 int lfdm_conv_pw_launch(const lfdm_conv_params& p, hipStream_t stream);            // conv_pw.hip
 int lfdm_conv_wino4_launch(const lfdm_conv_params& p, hipStream_t stream);         // conv_wino4.hip
 
@@ -990,8 +991,10 @@ extern "C" int lfdm_conv2d_plan_slabs(const lfdm_conv_params* p) {
   return pl.ksplit + extra;
 }
 
-extern "C" int lfdm_conv2d_cl_f32(const lfdm_conv_params* pp, lfdm_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+namespace {
+
+// lfdm_conv2d_cl_f32, and with wino_bf16 != NULL lfdm_conv2d_cl_wino_bf16: the same checks and the same plan, the Winograd launch on bf16 operands
+int conv2d_run(const lfdm_conv_params* pp, const void* wino_bf16, hipStream_t stream) {
   if (!pp) { lfdm_set_error("conv2d: null params"); return LFDM_EINVAL; }
   lfdm_conv_params p = *pp;
   if (!p.src0 || !p.weight || !p.out || p.c0 <= 0 || p.c1 < 0 || (p.c1 > 0 && !p.src1) ||
@@ -1018,6 +1021,11 @@ extern "C" int lfdm_conv2d_cl_f32(const lfdm_conv_params* pp, lfdm_stream_t stre
     return LFDM_EINVAL;
   }
   const ConvPlan pl = make_plan(p);
+  if (wino_bf16 && (pl.kind != 2 || p.pool2 || (((uintptr_t)wino_bf16) & 15) != 0)) {
+    lfdm_set_error("conv2d_cl_wino_bf16: only where lfdm_conv2d_schedule picks the Winograd F(2x2,3x3) schedule (2), without pool2, with a 16-byte "
+                   "aligned bf16 pack (lfdm_pack_wino_weight_bf16)");
+    return LFDM_EINVAL;
+  }
   if (p.groups > 1 && pl.kind != 2) { lfdm_set_error("conv2d: groups > 1 is only built for the Winograd schedule (3x3, stride 1, zero pad)"); return LFDM_EINVAL; }
   if (p.pool2 && (pl.kind != 2 || p.residual || p.gn_partial || pp->ksplit > 1 || p.act == LFDM_ACT_NONE)) {
     lfdm_set_error("conv2d: pool2 exists on the Winograd schedule only (3x3, stride 1, zero pad 1, even size, C % 16 == 0): out = (hq/2, wq/2), "
@@ -1068,7 +1076,8 @@ extern "C" int lfdm_conv2d_cl_f32(const lfdm_conv_params* pp, lfdm_stream_t stre
     rc = lfdm_conv_ksw_launch(p, pl.bn, stream);
   } else if (pl.kind == 2) {
     const int bal = p.partial ? wino_balance(pl, p, nullptr) : 0;
-    rc = lfdm_conv_wino_launch(p, pl.bn, bal > 0 || splitk_fused(pl, p), bal, stream);
+    rc = wino_bf16 ? lfdm_conv_wino_bf16_launch(p, wino_bf16, pl.bn, bal > 0 || splitk_fused(pl, p), bal, stream)
+                   : lfdm_conv_wino_launch(p, pl.bn, bal > 0 || splitk_fused(pl, p), bal, stream);
   } else if (pl.kind == 3) {
     rc = lfdm_conv_pw_launch(p, stream);
   } else if (pl.kind == 4) {
@@ -1104,4 +1113,13 @@ extern "C" int lfdm_conv2d_cl_f32(const lfdm_conv_params* pp, lfdm_stream_t stre
     rc = lfdm_check_launch("conv_splitk_reduce");
   }
   return rc;
+}
+
+}  // namespace
+
+extern "C" int lfdm_conv2d_cl_f32(const lfdm_conv_params* p, lfdm_stream_t stream) { return conv2d_run(p, nullptr, (hipStream_t)stream); }
+
+extern "C" int lfdm_conv2d_cl_wino_bf16(const lfdm_conv_params* p, const void* weight_wino_bf16, lfdm_stream_t stream) {
+  if (!weight_wino_bf16) { lfdm_set_error("conv2d_cl_wino_bf16: null bf16 pack"); return LFDM_EINVAL; }
+  return conv2d_run(p, weight_wino_bf16, (hipStream_t)stream);
 }

@@ -58,14 +58,24 @@ constexpr int LDM = WN + 4;       // LDS row stride of the half-transformed M pl
 // slice order - bit-identical to conv_splitk_reduce_vec_kernel, whoever arrives last - and runs the epilogue (bias, GroupNorm partial sums,
 // residual, activation) itself.  The fence-based form of this hand-off (round 2, KSW schedule) measured neutral: its release wrote back the
 // XCD's whole L2 from every workgroup's tail - the cost found in the BatchNorm reduce (profiles/r05_p_bench_bn.txt, r05_q_*).
-template <bool ACT, int NT, bool POOL = false, bool FUSE = false>
+// BF (opt-in, lfdm_conv2d_cl_wino_bf16): the K loop on v_mfma_f32_32x32x16_bf16 - ONE MFMA per (position, column tile, chunk) where the fp32
+// form issues eight.  Operands rounded once, to nearest even: V = B^T d B (fp32) at the conversion, U from its own pack (lfdm_pack_wino_weight_bf16:
+// [pos][chunk][column][kh][8] bf16, one 16-byte fragment load per lane, 1 KB contiguous per instruction); fp32 accumulation, everything after the
+// K loop unchanged.  BF_VF32 keeps V fp32 in LDS and converts the A fragment at load_a; BF_VB16 converts in the input transform and keeps V as
+// bf16 in LDS (half the LDS bytes written and read per chunk; the epilogue planes still set the footprint).  Both round at the same point.
+constexpr int BF_NONE = 0, BF_VF32 = 1, BF_VB16 = 2;
+constexpr int LDVB = WKC + 8;     // LDS row stride of V in bf16 elements (BF_VB16: 48-byte rows, 16-byte aligned)
+
+template <bool ACT, int NT, bool POOL = false, bool FUSE = false, int BF = BF_NONE>
 __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv_wino_kernel(lfdm_conv_params p, int bal_whole) {
   static_assert(!FUSE || (NT == 1 && !POOL), "in-launch split-K reduction: the plain 32-column workgroup only");
+  static_assert(BF == BF_NONE || !POOL, "bf16 operands: not built for the pooled (LFAE encoder) form");
   constexpr int WNB = WN * NT;      // output channels per workgroup
   constexpr int LD = LDV;
   constexpr int VSZ = 16 * WT * LD;
   __shared__ __attribute__((aligned(16))) float smem[VSZ];   // V during the loop; >= 8*WT*LDM for the epilogue planes
   static_assert(VSZ >= 8 * WT * LDM, "epilogue planes must fit in the V buffer");
+  static_assert(16 * WT * LDVB / 2 <= VSZ, "bf16 V must fit in the V buffer");
   __shared__ float s_gn[2][4][WNB];
 
   const int tid = (int)threadIdx.x;
@@ -200,14 +210,23 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv_wino_kernel(lfdm_co
     }
   };
   // ---- weight fragments: lane (co = n0 + l31, k-slot kh) holds U[pos][16*chunk + 8*kh + s][co], s = 0..7 ----
-  const lfdm_buf bufw = lfdm_make_buf(p.weight_wino + (int64_t)grp * 16 * nchunks_all * wcoutp * WKC,
-                                      (uint32_t)((int64_t)16 * nchunks_all * wcoutp * WKC * 4));
-  float4 bfrag[4][NT][2];
+  // (bf16: p.weight_wino points at the bf16 pack - lfdm_conv_wino_launch - whose elements are 2 bytes)
+  const lfdm_buf bufw = BF == BF_NONE
+                            ? lfdm_make_buf(p.weight_wino + (int64_t)grp * 16 * nchunks_all * wcoutp * WKC,
+                                            (uint32_t)((int64_t)16 * nchunks_all * wcoutp * WKC * 4))
+                            : lfdm_make_buf(reinterpret_cast<const char*>(p.weight_wino) + (int64_t)grp * 16 * nchunks_all * wcoutp * WKC * 2,
+                                            (uint32_t)((int64_t)16 * nchunks_all * wcoutp * WKC * 2));
+  float4 bfrag[4][NT][BF == BF_NONE ? 2 : 1];
   auto fetch_b = [&](int pi, int chunk) {
     const int pos = 4 * wave + pi;
 #pragma unroll
     for (int ct = 0; ct < NT; ++ct) {
       const int n = n0 + WN * ct + l31 - grp * wcoutp;          // column inside the (group's) filter pack
+      if constexpr (BF != BF_NONE) {
+        // bf16 pack [pos][chunk][column][kh][8]: lane (column, kh) reads its 8 k values with ONE 16-byte load
+        const uint32_t off = (n < wcoutp) ? (uint32_t)(((((int64_t)pos * nchunks_all + chunk) * wcoutp + n) * 2 + kh) * 16) : LFDM_BUF_OOB;
+        bfrag[pi][ct][0] = lfdm_buf_load_f4(bufw, off);
+      } else {
       // pack [pos][chunk][j = 0, 1][column][kh][4] (round 4): the lanes of ONE load instruction (32 columns x 2 k-slots x 16 bytes) read a
       // contiguous 1 KB - the previous [pos][chunk][column][16] order made each instruction touch half of every lane's 32-byte piece,
       // twice the L1 line look-ups per byte on the kernel's dominant stream
@@ -216,6 +235,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv_wino_kernel(lfdm_co
                                : LFDM_BUF_OOB;
       bfrag[pi][ct][0] = lfdm_buf_load_f4(bufw, off);
       bfrag[pi][ct][1] = lfdm_buf_load_f4(bufw, off == LFDM_BUF_OOB ? LFDM_BUF_OOB : off + (uint32_t)wcoutp * 32u);
+      }
     }
   };
 
@@ -238,6 +258,14 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv_wino_kernel(lfdm_co
            : i == 2 ? make_float2(d2.x - d1.x, d2.y - d1.y)
                     : make_float2(d1.x - d3.x, d1.y - d3.y);
     }
+    if constexpr (BF == BF_VB16) {       // the channel pair as one packed bf16 word; rows of LDVB / 2 words
+      uint32_t* dw = reinterpret_cast<uint32_t*>(V) + ((4 * i) * WT + x_tile) * (LDVB / 2) + x_c2;
+      dw[0] = lfdm_cvt_pk_bf16(r[0].x - r[2].x, r[0].y - r[2].y);
+      dw[WT * (LDVB / 2)] = lfdm_cvt_pk_bf16(r[1].x + r[2].x, r[1].y + r[2].y);
+      dw[2 * WT * (LDVB / 2)] = lfdm_cvt_pk_bf16(r[2].x - r[1].x, r[2].y - r[1].y);
+      dw[3 * WT * (LDVB / 2)] = lfdm_cvt_pk_bf16(r[1].x - r[3].x, r[1].y - r[3].y);
+      return;
+    }
     float* dst = V + ((4 * i) * WT + x_tile) * LD + 2 * x_c2;
     *reinterpret_cast<float2*>(dst) = make_float2(r[0].x - r[2].x, r[0].y - r[2].y);
     *reinterpret_cast<float2*>(dst + WT * LD) = make_float2(r[1].x + r[2].x, r[1].y + r[2].y);
@@ -259,6 +287,17 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv_wino_kernel(lfdm_co
         const float b = (s8 & 3) == 0 ? bq.x : (s8 & 3) == 1 ? bq.y : (s8 & 3) == 2 ? bq.z : bq.w;
         acc[pi][ct] = mfma_32x32x2(a[s8], b, acc[pi][ct]);
       }
+  };
+  auto load_a_bf16 = [&](const float* V, int pi) {             // the same A fragment as 8 bf16 (k = 8*kh .. 8*kh+7)
+    if constexpr (BF == BF_VB16)
+      return lfdm_bf16x8_bits(*reinterpret_cast<const float4*>(reinterpret_cast<const uint16_t*>(V) + ((4 * wave + pi) * WT + l31) * LDVB + 8 * kh));
+    float4 a0, a1;
+    load_a(V, pi, a0, a1);
+    return lfdm_cvt_bf16x8(a0, a1);
+  };
+  auto mfma_pos_bf16 = [&](const lfdm_bf16x8& a, int pi) {     // ONE MFMA per column tile covers the chunk's 16 channels
+#pragma unroll
+    for (int ct = 0; ct < NT; ++ct) acc[pi][ct] = mfma_32x32x16_bf16(a, lfdm_bf16x8_bits(bfrag[pi][ct][0]), acc[pi][ct]);
   };
   const int kc_last = kc_end - 1;
   auto clampc = [&](int c) { return c < kc_last ? c : kc_last; };     // re-fetching the last chunk is harmless
@@ -287,9 +326,13 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv_wino_kernel(lfdm_co
       fetch_patch(patch, nxt, valid_mask);     // in flight under this round's MFMAs
 #pragma unroll
       for (int pi = 0; pi < 4; ++pi) {
-        float4 a0, a1;
-        load_a(Vs, pi, a0, a1);
-        mfma_pos(a0, a1, pi);
+        if constexpr (BF != BF_NONE) {
+          mfma_pos_bf16(load_a_bf16(Vs, pi), pi);
+        } else {
+          float4 a0, a1;
+          load_a(Vs, pi, a0, a1);
+          mfma_pos(a0, a1, pi);
+        }
         fetch_b(pi, nxt);                                        // refilled in place for the next round
       }
       __syncthreads();
@@ -529,17 +572,8 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv_wino_kernel(lfdm_co
 // whose 16 transformed values lie side by side in the packed layout [pos][chunk][half][n][kh][e] - one 16-byte store per position, and
 // adjacent threads (kh, then n) store adjacent 16 bytes: a wavefront writes 1 KB contiguous per position.  (One thread per (k, n) pair wrote
 // 4 bytes at a 32-byte stride, 16 times: the multi-filter re-pack of a training step ran at 0.58 TB/s, profiles/r05_n_lfae_census.txt.)
-__device__ __forceinline__ void pack_wino_item(const float* __restrict__ w, int ld_o, int cout, int cin, int coutp, int dgrad,
-                                               float* __restrict__ out, int64_t idx) {
-  const int K = dgrad ? cout : cin;                     // reduction channels of the target convolution
-  const int N = dgrad ? cin : cout;                     // its output channels
-  if (idx >= (int64_t)(K / 4) * coutp) return;
-  const int kh2 = (int)(idx & 1);
-  const int n = (int)((idx >> 1) % coutp);
-  const int rest = (int)((idx >> 1) / coutp);           // chunk * 2 + half
-  const int half = rest & 1, chunk = rest >> 1;
-  const int k0 = chunk * WKC + 8 * kh2 + 4 * half;
-  float u[16][4];
+// (wino_filter_u4: the transform of the four reduction channels k0 .. k0+3 into output channel n, zero for n >= N)
+__device__ __forceinline__ void wino_filter_u4(const float* __restrict__ w, int ld_o, int N, int dgrad, int k0, int n, float (&u)[16][4]) {
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     float g[9];
@@ -568,11 +602,45 @@ __device__ __forceinline__ void pack_wino_item(const float* __restrict__ w, int 
       u[4 * i + 3][e] = r[i][2];
     }
   }
+}
+
+__device__ __forceinline__ void pack_wino_item(const float* __restrict__ w, int ld_o, int cout, int cin, int coutp, int dgrad,
+                                               float* __restrict__ out, int64_t idx) {
+  const int K = dgrad ? cout : cin;                     // reduction channels of the target convolution
+  const int N = dgrad ? cin : cout;                     // its output channels
+  if (idx >= (int64_t)(K / 4) * coutp) return;
+  const int kh2 = (int)(idx & 1);
+  const int n = (int)((idx >> 1) % coutp);
+  const int rest = (int)((idx >> 1) / coutp);           // chunk * 2 + half
+  const int half = rest & 1, chunk = rest >> 1;
+  const int k0 = chunk * WKC + 8 * kh2 + 4 * half;
+  float u[16][4];
+  wino_filter_u4(w, ld_o, N, dgrad, k0, n, u);
   const int nch = K / WKC;
 #pragma unroll
   for (int pos = 0; pos < 16; ++pos)
     *reinterpret_cast<float4*>(out + ((((((int64_t)pos) * nch + chunk) * 2 + half) * coutp + n) * 2 + kh2) * 4) =
         make_float4(u[pos][0], u[pos][1], u[pos][2], u[pos][3]);
+}
+
+// bf16 form (conv_wino_kernel BF): one thread per (16-channel chunk, output channel n, kh) - the eight reduction channels 16 chunk + 8 kh + s,
+// s = 0..7, each element the round-to-nearest-even bf16 of the value the fp32 pack holds (the same transform, in the same order), stored
+// as [pos][chunk][n][kh][8]: one 16-byte store per position, a wavefront writes 1 KB contiguous
+__global__ __launch_bounds__(256) void pack_wino_bf16_kernel(const float* __restrict__ w, int ld_o, int cout, int cin, int coutp,
+                                                             lfdm_bf16x8* __restrict__ out) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)(cin / 8) * coutp) return;
+  const int kh2 = (int)(idx & 1);
+  const int n = (int)((idx >> 1) % coutp);
+  const int chunk = (int)((idx >> 1) / coutp);
+  float u[16][4], v[16][4];
+  wino_filter_u4(w, ld_o, cout, 0, chunk * WKC + 8 * kh2, n, u);
+  wino_filter_u4(w, ld_o, cout, 0, chunk * WKC + 8 * kh2 + 4, n, v);
+  const int nch = cin / WKC;
+#pragma unroll
+  for (int pos = 0; pos < 16; ++pos)
+    out[(((int64_t)pos * nch + chunk) * coutp + n) * 2 + kh2] =
+        lfdm_cvt_bf16x8(make_float4(u[pos][0], u[pos][1], u[pos][2], u[pos][3]), make_float4(v[pos][0], v[pos][1], v[pos][2], v[pos][3]));
 }
 
 __global__ __launch_bounds__(256) void pack_wino_kernel(const float* __restrict__ w, int ld_o, int cout, int cin, int coutp,
@@ -613,11 +681,61 @@ extern "C" int lfdm_pack_wino_weight_f32(const float* w, int ld_o, int cout, int
   return lfdm_check_launch("pack_wino_weight");
 }
 
+extern "C" int lfdm_pack_wino_weight_bf16(const float* w, int ld_o, int cout, int cin, int coutp, void* out, lfdm_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!w || !out || cout <= 0 || cin <= 0 || cin % WKC != 0 || coutp < cout || coutp % 32 != 0 || ld_o < cin * 9 || (((uintptr_t)out) & 15) != 0) {
+    lfdm_set_error("pack_wino_weight_bf16: input channels must be a multiple of 16, coutp a multiple of 32 >= the output channels, out 16-byte aligned");
+    return LFDM_EINVAL;
+  }
+  const int64_t total = (int64_t)(cin / 8) * coutp;
+  LFDM_LAUNCH(pack_wino_bf16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, w, ld_o, cout, cin, coutp,
+              static_cast<lfdm_bf16x8*>(out));
+  return lfdm_check_launch("pack_wino_weight_bf16");
+}
+
 extern "C" int lfdm_pack_wino_weights_multi_f32(const lfdm_pack_wino_job* jobs, int n_jobs, int total_blocks, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!jobs || n_jobs <= 0 || total_blocks <= 0) { lfdm_set_error("pack_wino_weights_multi: needs a device job table and its workgroup count"); return LFDM_EINVAL; }
   LFDM_LAUNCH(pack_wino_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, stream, jobs, n_jobs);
   return lfdm_check_launch("pack_wino_weights_multi");
+}
+
+namespace {
+
+// the bf16-operand instantiations: every (ACT, NT, FUSE) the fp32 dispatch below can pick, not the pooled form (lfdm_conv2d_cl_wino_bf16 refuses it).
+// The layout of V in LDS is BF_VB16 (HISTORY.md: the A/B against BF_VF32); --knobs builds also carry BF_VF32 (LFDM_WINO_BF16_VF32=1).
+template <int BF>
+void launch_wino_bf16(const lfdm_conv_params& p, int bn, bool fuse_reduce, int bal_whole, dim3 grid, hipStream_t stream) {
+  const bool act = p.act != LFDM_ACT_NONE;
+  if (fuse_reduce) {
+    if (bal_whole > 0) {
+      const unsigned jobs = grid.x * grid.y * grid.z;
+      LFDM_LAUNCH((conv_wino_kernel<false, 1, false, true, BF>), dim3((unsigned)bal_whole + 2u * (jobs - (unsigned)bal_whole)), dim3(256), 0, stream, p, bal_whole);
+    } else {
+      LFDM_LAUNCH((conv_wino_kernel<false, 1, false, true, BF>), grid, dim3(256), 0, stream, p, 0);
+    }
+  } else if (bn == 64 && act) LFDM_LAUNCH((conv_wino_kernel<true, 2, false, false, BF>), grid, dim3(256), 0, stream, p, 0);
+  else if (bn == 64) LFDM_LAUNCH((conv_wino_kernel<false, 2, false, false, BF>), grid, dim3(256), 0, stream, p, 0);
+  else if (act) LFDM_LAUNCH((conv_wino_kernel<true, 1, false, false, BF>), grid, dim3(256), 0, stream, p, 0);
+  else LFDM_LAUNCH((conv_wino_kernel<false, 1, false, false, BF>), grid, dim3(256), 0, stream, p, 0);
+}
+
+}  // namespace
+
+// The same launch with bf16 operands (lfdm_conv2d_cl_wino_bf16, conv_igemm.hip: same plan, pool2 refused there): the kernel reads the bf16 pack
+// through p.weight_wino of a copy of the parameters.
+int lfdm_conv_wino_bf16_launch(const lfdm_conv_params& p_, const void* weight_bf16, int bn, bool fuse_reduce, int bal_whole, hipStream_t stream) {
+  lfdm_conv_params p = p_;
+  p.weight_wino = static_cast<const float*>(weight_bf16);
+  const int64_t ntiles = (int64_t)p.n_img * (p.hq / 2) * (p.wq / 2);
+  const dim3 grid((unsigned)((ntiles + WT - 1) / WT), (unsigned)((p.coutp + bn - 1) / bn), p.ksplit > 1 ? p.ksplit : 1);
+#if defined(LFDM_TUNING_KNOBS) || defined(LFDM_EMU_BUILD)
+  const char* e = lfdm_knob("LFDM_WINO_BF16_VF32");      // (read per call: tools/bench_wino_bf16.py --vlds alternates the layouts in one process)
+  if (e && e[0] == '1') launch_wino_bf16<BF_VF32>(p, bn, fuse_reduce, bal_whole, grid, stream);
+  else
+#endif
+    launch_wino_bf16<BF_VB16>(p, bn, fuse_reduce, bal_whole, grid, stream);
+  return lfdm_check_launch("conv_wino_bf16");
 }
 
 // grid (tile blocks, column tiles, ksplit).  Called by lfdm_conv2d_cl_f32 (conv_igemm.hip).

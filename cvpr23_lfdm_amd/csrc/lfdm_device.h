@@ -19,6 +19,57 @@ typedef emu_f32x4 f32x4;
 static inline f32x16 mfma_32x32x2(float a, float b, f32x16 c) { return emu_mfma_32x32x2(a, b, c); }
 static inline f32x4 mfma_16x16x4(float a, float b, f32x4 c) { return emu_mfma_16x16x4(a, b, c); }
 static inline f32x4 mfma_4x4x1(float a, float b, f32x4 c) { return emu_mfma_4x4x1(a, b, c); }
+// bf16 operands (the opt-in Winograd K loop, conv_wino.hip): raw bits, k order.  RNE float -> bf16 as v_cvt_pk_bf16_f32 rounds
+// (NaN stays a quiet NaN); the MFMA model multiplies exactly (bf16 x bf16 fits an fp32 significand) and accumulates in fp32 in k order.
+struct lfdm_bf16x8 { uint16_t h[8]; };
+static inline uint16_t lfdm_f32_to_bf16(float f) {
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (uint16_t)(u >> 16);
+}
+static inline float lfdm_bf16_to_f32(uint16_t h) {
+  const uint32_t u = (uint32_t)h << 16;
+  float f;
+  memcpy(&f, &u, 4);
+  return f;
+}
+static inline lfdm_bf16x8 lfdm_cvt_bf16x8(float4 a0, float4 a1) {
+  const float f[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+  lfdm_bf16x8 r;
+  for (int i = 0; i < 8; ++i) r.h[i] = lfdm_f32_to_bf16(f[i]);
+  return r;
+}
+static inline uint32_t lfdm_cvt_pk_bf16(float lo, float hi) { return (uint32_t)lfdm_f32_to_bf16(lo) | ((uint32_t)lfdm_f32_to_bf16(hi) << 16); }
+static inline lfdm_bf16x8 lfdm_bf16x8_bits(float4 v) {
+  lfdm_bf16x8 r;
+  memcpy(&r, &v, 16);
+  return r;
+}
+// v_mfma_f32_32x32x16_bf16: A[i][k] = element k & 7 of lane i + 32 (k >> 3), B[k][j] = element k & 7 of lane j + 32 (k >> 3);
+// D as v_mfma_f32_32x32x2_f32.  Lane l first takes its partner l ^ 32's operands (then it holds A row / B column l & 31 whole),
+// then reads every A row it needs from the lane that holds it.
+static inline f32x16 mfma_32x32x16_bf16(lfdm_bf16x8 a, lfdm_bf16x8 b, f32x16 c) {
+  struct Pair { lfdm_bf16x8 a, b; };
+  struct Whole { lfdm_bf16x8 a[2], b[2]; };
+  const unsigned lane = emu::lane_id(), h = lane >> 5;
+  const Pair other = emu::wave_read_from(Pair{a, b}, lane ^ 32u);
+  Whole mine;
+  mine.a[h] = a;
+  mine.a[1 - h] = other.a;
+  mine.b[h] = b;
+  mine.b[1 - h] = other.b;
+  for (int r = 0; r < 16; ++r) {
+    const unsigned row = (r & 3) + 8 * (r >> 2) + 4 * h;
+    const Whole src = emu::wave_read_from(mine, row);
+    float acc = c[r];
+    for (int k = 0; k < 16; ++k)
+      acc = fmaf(lfdm_bf16_to_f32(src.a[k >> 3].h[k & 7]), lfdm_bf16_to_f32(mine.b[k >> 3].h[k & 7]), acc);
+    c[r] = acc;
+  }
+  return c;
+}
 #else
 #include <hip/hip_runtime.h>
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -37,6 +88,24 @@ __device__ __forceinline__ f32x4 mfma_16x16x4(float a, float b, f32x4 c) {
 // of lane 4b+j.  Full MFMA rate with only FOUR output columns per block: the shape for skinny-N contractions.
 __device__ __forceinline__ f32x4 mfma_4x4x1(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0);
+}
+// bf16 operands (the opt-in Winograd K loop, conv_wino.hip): lane l holds A[i = l&31][k = 8*(l>>5) .. +7] and B[k = 8*(l>>5) .. +7][j = l&31];
+// D as v_mfma_f32_32x32x2_f32, accumulated in fp32.  The conversions are v_cvt_pk_bf16_f32 (round to nearest even on gfx950).
+typedef __bf16 lfdm_bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 lfdm_bf16x2 __attribute__((ext_vector_type(2)));
+typedef float lfdm_f32x8 __attribute__((ext_vector_type(8)));
+typedef float lfdm_f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ lfdm_bf16x8 lfdm_cvt_bf16x8(float4 a0, float4 a1) {
+  const lfdm_f32x8 f = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+  return __builtin_convertvector(f, lfdm_bf16x8);
+}
+__device__ __forceinline__ uint32_t lfdm_cvt_pk_bf16(float lo, float hi) {
+  const lfdm_f32x2 f = {lo, hi};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, lfdm_bf16x2));
+}
+__device__ __forceinline__ lfdm_bf16x8 lfdm_bf16x8_bits(float4 v) { return __builtin_bit_cast(lfdm_bf16x8, v); }
+__device__ __forceinline__ f32x16 mfma_32x32x16_bf16(lfdm_bf16x8 a, lfdm_bf16x8 b, f32x16 c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 #endif
 

@@ -225,7 +225,8 @@ class GaussianDiffusion(nn.Module):
             variants.append(torch.zeros(batch, pk["cond.n"], device=dev))
 
         # ---- static step state ----------------------------------------------------------------
-        key = (batch, frames, s, len(variants), float(cond_scale), bool(ddim), steps, id(pk))
+        # (the convolution precision explicitly: both modes share one pack - id(pk) does not tell a graph captured in the other mode apart)
+        key = (batch, frames, s, len(variants), float(cond_scale), bool(ddim), steps, id(pk), unet.conv_precision)
         plan = self._plans.get(key)
         if plan is None:
             plan = {

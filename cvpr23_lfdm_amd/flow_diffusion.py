@@ -68,10 +68,12 @@ class FlowDiffusion(nn.Module):
                  ddim_sampling_eta=1., timesteps=1000, dim_mults=(1, 2, 4, 8), lr=1e-4,
                  adam_betas=(0.9, 0.99), is_train=True, only_use_flow=True, use_residual_flow=False,
                  learn_null_cond=False, use_deconv=True, padding_mode="zeros", pretrained_pth="",
-                 config_pth="", bert_path=None):
+                 config_pth="", bert_path=None, *, conv_precision="fp32"):
         """Reference signature (video_flow_diffusion_model.py:19-37) + `bert_path`: a local Hugging Face directory of
         bert-base-cased for `cond=list[str]` (the reference downloads it with torch.hub; see text.py).  LFDM_BERT_PATH in
-        the environment is the default, so unchanged caller scripts pick it up."""
+        the environment is the default, so unchanged caller scripts pick it up.
+        conv_precision (keyword only): Unet3D.conv_precision of the denoiser - "fp32" (default) or "bf16", the opt-in faster sampling mode
+        whose Winograd 3x3 convolutions run on bf16 operands (sampling and the eval branch of p_losses; training stays fp32)."""
         super().__init__()
         check_num_frames(num_frames)        # (before the checkpoint and the config are read)
         self.use_residual_flow = use_residual_flow
@@ -94,6 +96,7 @@ class FlowDiffusion(nn.Module):
         self.unet = Unet3D(dim=64, channels=3 + 256, out_grid_dim=2, out_conf_dim=1, dim_mults=dim_mults,
                            use_bert_text_cond=True, learn_null_cond=learn_null_cond,
                            use_final_activation=False, use_deconv=use_deconv, padding_mode=padding_mode)
+        self.unet.conv_precision = conv_precision
         self.diffusion = GaussianDiffusion(self.unet, image_size=img_size, num_frames=num_frames,
                                            sampling_timesteps=sampling_timesteps, timesteps=timesteps,
                                            loss_type='l2', use_dynamic_thres=True,

@@ -222,6 +222,28 @@ def pack_wino_weight(w, coutp=None, dgrad=False, out=None):
     return out
 
 
+def pack_wino_weight_bf16(w, coutp=None):
+    """(Cout, Cin, 3, 3) -> the bf16 operands of the opt-in bf16 Winograd launch (conv2d_cl(weight_wino_bf16=...), lfdm_conv2d_cl_wino_bf16):
+    a torch.bfloat16 tensor [16][Cin/16][coutp][16] (position, channel chunk, output channel, channel in chunk - plain order), each element
+    the round-to-nearest-even bf16 of the value pack_wino_weight(w) holds.  lfdm_pack_wino_weight_bf16."""
+    lib = _lib()
+    if w.dim() == 5:
+        w = w[:, :, 0]
+    cout, cin, kh, kw = w.shape
+    assert kh == 3 and kw == 3 and w.dtype == torch.float32 and cin % 16 == 0
+    assert w.stride(3) == 1 and w.stride(2) == 3 and w.stride(1) == 9, "input-channel slices of a contiguous filter only"
+    _chk(lib, w)
+    coutp = coutp or (cout + 31) // 32 * 32
+    out = torch.empty(16, cin // 16, coutp, 16, dtype=torch.bfloat16, device=w.device)
+    lib.check(lib.lfdm_pack_wino_weight_bf16(_p(w), w.stride(0), cout, cin, coutp, _p(out), _stream(lib)), "lfdm_pack_wino_weight_bf16")
+    return out
+
+
+def pack_wino_weight_grouped_bf16(ws):
+    """pack_wino_weight_grouped in bf16: (G, 16, Cin_g/16, Cout_g, 16) bfloat16, each group's pack_wino_weight_bf16 back to back."""
+    return torch.stack([pack_wino_weight_bf16(w.contiguous(), coutp=w.shape[0]) for w in ws]).contiguous()
+
+
 _PACK_JOB_TABLES = {}
 
 
@@ -400,12 +422,38 @@ def conv_launch(p):
     lib.check(lib.lfdm_conv2d_cl_f32(C.byref(p), _stream(lib)), "lfdm_conv2d_cl_f32")
 
 
+def _chk_wino_bf16(lib, p, wwb):
+    """The bf16 pack that goes with the fp32 Winograd pack of `p` (same filter, same shape)."""
+    if wwb.dtype != torch.bfloat16 or not wwb.is_contiguous():
+        raise TypeError("weight_wino_bf16: a contiguous torch.bfloat16 pack (pack_wino_weight_bf16) expected, got %s" % wwb.dtype)
+    if (lib.kind == "hip") != wwb.is_cuda:
+        raise RuntimeError("weight_wino_bf16 must live where the library runs (GPU for hip, CPU for emu)")
+    ww = p._keep[8]
+    if ww is None or tuple(wwb.shape) != tuple(ww.shape):
+        raise ValueError("weight_wino_bf16 needs weight_wino (the fp32 pack that decides the plan) of the same shape")
+
+
+def conv_launch_wino_bf16(p, weight_wino_bf16):
+    """lfdm_conv2d_cl_wino_bf16: the launch conv_launch(p) would run, on bf16 operands (the library refuses geometries that are not on the
+    Winograd F(2x2) schedule)."""
+    lib = _lib()
+    _chk_wino_bf16(lib, p, weight_wino_bf16)
+    lib.check(lib.lfdm_conv2d_cl_wino_bf16(C.byref(p), _p(weight_wino_bf16), _stream(lib)), "lfdm_conv2d_cl_wino_bf16")
+
+
 def conv2d_cl(src0, weight, cout, kh, kw, n_img, hi, wi, *, partial=None, gn_partial=None, gn_groups=8,
-              gn_pixels=0, **kw_):
-    """One convolution (see conv_params for the keywords).  Split-K scratch is allocated on demand."""
+              gn_pixels=0, weight_wino_bf16=None, **kw_):
+    """One convolution (see conv_params for the keywords).  Split-K scratch is allocated on demand.
+    weight_wino_bf16 (with weight_wino): the Winograd F(2x2) launch on bf16 operands (pack_wino_weight_bf16 of the same filter) - only where
+    the library picks that schedule for these parameters (WinogradUnavailable otherwise)."""
     lib = _lib()
     _chk(lib, partial, gn_partial)
     p, out = conv_params(src0, weight, cout, kh, kw, n_img, hi, wi, **kw_)
+    if weight_wino_bf16 is not None:
+        _chk_wino_bf16(lib, p, weight_wino_bf16)
+        if kw_.get("pool2") or lib.lfdm_conv2d_schedule(C.byref(p)) != 2:
+            raise WinogradUnavailable("bf16 operands exist on the Winograd F(2x2,3x3) schedule only, without pool2: the library would not run it "
+                                      "for this geometry")
     if (weight is None or kw_.get("pool2")) and lib.lfdm_conv2d_schedule(C.byref(p)) not in ((2,) if kw_.get("pool2") else (2, 4)):
         raise WinogradUnavailable("the library would not run the Winograd schedule for this geometry: pass the direct-form pack / "
                                   "run the pooling as a launch of its own")
@@ -416,7 +464,10 @@ def conv2d_cl(src0, weight, cout, kh, kw, n_img, hi, wi, *, partial=None, gn_par
         if partial is None or partial.numel() < need:
             partial = torch.empty(need, dtype=torch.float32, device=src0.device)
         p.partial = _p(partial)
-    conv_launch(p)
+    if weight_wino_bf16 is not None:
+        conv_launch_wino_bf16(p, weight_wino_bf16)
+    else:
+        conv_launch(p)
     return out
 
 

@@ -110,6 +110,24 @@ class Unet3D(ParamTree):
         self._pk_sig = None
         self._bufs = {}
         self._buf_gen = 0
+        self._conv_precision = "fp32"
+
+    CONV_PRECISIONS = ("fp32", "bf16")
+
+    @property
+    def conv_precision(self):
+        """Operand precision of the 3x3 convolutions on the Winograd F(2x2,3x3) schedule in `forward` (sampling, the eval branch of p_losses):
+        "fp32" (default) or "bf16" - the transform-domain GEMM on bf16 operands rounded to nearest even, summed in fp32
+        (lfdm_conv2d_cl_wino_bf16; DESIGN.md, "bf16-operand Winograd convolutions").  Every other launch - the stem, the pointwise / implicit
+        GEMM / deconvolution schedules, attention, GroupNorm, the sampler - is the same in both modes, and training (unet_train_forward and its
+        autograd kernels) is always fp32.  Switching never changes the fp32 packs: "fp32" again reproduces the fp32 results bit for bit."""
+        return self._conv_precision
+
+    @conv_precision.setter
+    def conv_precision(self, value):
+        if value not in self.CONV_PRECISIONS:
+            raise ValueError("conv_precision must be one of %s, got %r" % (self.CONV_PRECISIONS, value))
+        self._conv_precision = value
 
     # ------------------------------------------------------------------ plumbing
     def _apply(self, fn, *a, **k):
@@ -151,11 +169,13 @@ class Unet3D(ParamTree):
     # ------------------------------------------------------------------ weight packing
     def packed(self):
         sig = self._signature()
-        if self._pk is not None and self._pk_sig == sig:
-            return self._pk
-        with torch.no_grad():
-            self._pk = self._pack()
-        self._pk_sig = sig
+        if self._pk is None or self._pk_sig != sig:
+            with torch.no_grad():
+                self._pk = self._pack()
+            self._pk_sig = sig
+        if self._conv_precision == "bf16" and "wino_bf16" not in self._pk:
+            with torch.no_grad():
+                self._pk["wino_bf16"] = self._pack_wino_bf16()
         return self._pk
 
     def _pack(self):
@@ -278,6 +298,22 @@ class Unet3D(ParamTree):
         pk["tables"] = {}
         return pk
 
+    def _pack_wino_bf16(self):
+        """bf16 mode: the bf16 operands of every filter that has a Winograd pack, keyed by the address of that fp32 pack (which _conv is handed).
+        Built from the parameters as _pack builds the fp32 packs; added to the same pack, so the fp32 packs and their addresses never change."""
+        g = lambda k: self.get(k).detach().float().contiguous()
+        pk, out = self._pk, {}
+        for key, ww in pk.items():
+            if not (isinstance(key, str) and key.endswith("proj.ww")) or ww is None:
+                continue
+            out[ww.data_ptr()] = ops.pack_wino_weight_bf16(g(key[:-len("ww")] + "weight"))
+        if "heads.block1.ww" in pk:
+            hp = ("final_conv.0.", "occlusion_map.0.")
+            w1 = torch.cat([g(h + "block1.proj.weight") for h in hp], dim=0).contiguous()
+            out[pk["heads.block1.ww"].data_ptr()] = ops.pack_wino_weight_bf16(w1)
+            out[pk["heads.block2.ww"].data_ptr()] = ops.pack_wino_weight_grouped_bf16([g(h + "block2.proj.weight")[:, :, 0] for h in hp])
+        return out
+
     def _tables(self, pk, frames):
         t = pk["tables"].get(frames)
         if t is None:
@@ -335,6 +371,9 @@ class Unet3D(ParamTree):
         if sched == 2:
             counters = self._tile_counters(src0.device)
             p.tile_counters, p.tile_counters_len = counters.data_ptr(), counters.numel()
+        wwb = None
+        if self._conv_precision == "bf16" and p.weight_wino is not None:
+            wwb = self._pk["wino_bf16"][ww.data_ptr()]
         if gn is not None:
             p.gn_partial = 1      # (placeholder: "fused statistics wanted" changes the plan - schedules 3 / 4 have none; include/lfdm_hip.h)
         tile_rows, ksplit = ops.conv_plan(p)
@@ -362,7 +401,10 @@ class Unet3D(ParamTree):
                 nchunk = pixels // tile_rows * (parts if in_tile else 1)
                 stats = (self._buf("gn.partial", batch * nchunk, 2 * groups), nchunk)
                 p.gn_partial, p.gn_groups, p.gn_pixels = stats[0].data_ptr(), groups, pixels
-        ops.conv_launch(p)
+        if wwb is not None and ops.conv_schedule(p) == 2:
+            ops.conv_launch_wino_bf16(p, wwb)      # (bf16 mode: the same plan on bf16 operands)
+        else:
+            ops.conv_launch(p)
         return (y, stats) if gn is not None else y
 
     def _tile_counters(self, dev):

@@ -172,6 +172,13 @@ typedef struct lfdm_conv_params {
 } lfdm_conv_params;
 
 int lfdm_conv2d_cl_f32(const lfdm_conv_params* p, lfdm_stream_t stream);
+/* Opt-in lower-precision form of the Winograd F(2x2,3x3) schedule: runs exactly the launch lfdm_conv2d_cl_f32 would run for `p` (same plan:
+ * tile_rows, ksplit, slabs, GroupNorm partial layout, tile counters - every buffer sized for p stays valid) with the transform-domain GEMM on
+ * bf16 operands: V = B^T d B (fp32) and U rounded once, to nearest even, to bf16; products summed in fp32; input and output transforms,
+ * bias, residual, activation, statistics and split-K sums stay fp32.  weight_wino_bf16: lfdm_pack_wino_weight_bf16 of the filter whose fp32
+ * pack is p->weight_wino (or, grouped, the groups' bf16 packs back to back); 16-byte aligned.  Refused (LFDM_EINVAL) wherever
+ * lfdm_conv2d_schedule(p) != 2, and for pool2. */
+int lfdm_conv2d_cl_wino_bf16(const lfdm_conv_params* p, const void* weight_wino_bf16, lfdm_stream_t stream);
 /* the schedule the library will use for this geometry: rows of the output tile (32 / 64 / 128 / 160) and the
  * split-K factor (the given one if p->ksplit >= 1).  Fill in gn_partial (any non-NULL value) BEFORE asking when fused
  * GroupNorm statistics are wanted: the pointwise schedule (3) has none, so the request changes the plan. */
@@ -436,6 +443,10 @@ int lfdm_pack_wino_weight_f32(const float* w, int ld_o, int cout, int cin, int c
 /* the F(4x4,3x3) filters of lfdm_conv_params.weight_wino4: out[36][cin/8][coutp][8] (zero for output channels >= cout), same `w`
  * addressing as above; cin % 8 == 0, coutp % 32 == 0, coutp >= cout.  (ABI version 5.) */
 int lfdm_pack_wino4_weight_f32(const float* w, int ld_o, int cout, int cin, int coutp, float* out, lfdm_stream_t stream);
+/* the bf16 operands of lfdm_conv2d_cl_wino_bf16: out[16][cin/16][coutp][16] of 16-bit bf16 words (last axis: k-slot kh, then 8 channels -
+ * the channel inside the chunk, in order), each the round-to-nearest-even bf16 of the element lfdm_pack_wino_weight_f32 (dgrad = 0) holds
+ * for the same filter (zero for output channels >= cout).  Same `w` addressing; cin % 16 == 0, coutp % 32 == 0, coutp >= cout, out 16-byte aligned. */
+int lfdm_pack_wino_weight_bf16(const float* w, int ld_o, int cout, int cin, int coutp, void* out, lfdm_stream_t stream);
 
 /* PixelwiseFlowPredictor around its hourglass (LFAE/modules/pixelwise_flow_predictor.py:48-128) for all N = batch*frames driving
  * frames of a training step, frame n = b*frames + t using source image / source regions b:

@@ -36,6 +36,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--out", default="demo_out")
+    ap.add_argument("--conv-precision", choices=("fp32", "bf16"), default="fp32",
+                    help="operands of the UNet's Winograd 3x3 convolutions: bf16 is the faster, lower-precision sampling mode (DESIGN.md)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("tools/demo.py needs a GPU: the sampling path is liblfdm_hip.so only")
@@ -45,7 +47,7 @@ def main():
 
     model = FlowDiffusion(is_train=False, img_size=args.size // 4, num_frames=args.frames, sampling_timesteps=args.steps,
                           null_cond_prob=0.1, config_pth=args.config, pretrained_pth=args.lfae_ckpt,
-                          bert_path=None if args.synthetic else args.bert)          # demo_mug.py:80-88
+                          bert_path=None if args.synthetic else args.bert, conv_precision=args.conv_precision)          # demo_mug.py:80-88
     if args.synthetic:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import synth
