@@ -276,6 +276,81 @@ __global__ __launch_bounds__(256) void sampler_update_kernel(float* __restrict__
   }
 }
 
+// Multistep form of the update (lfdm_sampler_step_ms_f32: DPM-Solver++ on the thresholded data prediction m = clamp(x0,-s,s)/s):
+//   x <- k_x*x + k_m*m + k_prev*m_prev,   hist <- m       coef[step] = { c_x, c_eps, k_x, k_m, k_prev, - }
+// m_prev is the previous step's m, read from hist and replaced by this step's m by the same thread (one buffer suffices).  eps is not an
+// operand any more (pass 0 consumed it).  k_prev == 0 / k_x == 0 skip their operand: on a first-order step hist may be uninitialised
+// memory.  Prefetch and end-of-step housekeeping as in sampler_update_kernel.  grid (nblk, B)
+__global__ __launch_bounds__(256) void sampler_update_ms_kernel(float* __restrict__ x,
+                                                                float* __restrict__ hist,
+                                                                const float* __restrict__ x0buf,
+                                                                float* __restrict__ x0_out, int64_t n,
+                                                                const float* __restrict__ coef,
+                                                                const int32_t* step_dev,      // (no __restrict__: advance_dev is the same word)
+                                                                Ranks rk, unsigned* __restrict__ hists, int hist_samples,
+                                                                unsigned* __restrict__ ticket, int32_t* advance_dev) {
+  __shared__ unsigned s_part[256], s_res[4];
+  const int b = blockIdx.y;
+  float* xb = x + (int64_t)b * n;
+  float* hb = hist + (int64_t)b * n;
+  const float* x0b = x0buf + (int64_t)b * n;
+  float* x0o = x0_out ? x0_out + (int64_t)b * n : nullptr;
+  constexpr int PRE = 8;               // requested before the five histogram scans, like sampler_update_kernel's
+  const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+  float p_x0[PRE], p_x[PRE], p_m[PRE];
+#pragma unroll
+  for (int k = 0; k < PRE; ++k) {
+    const int64_t i = i0 + k * stride;
+    const bool in = i < n;
+    p_x0[k] = in ? x0b[i] : 0.f;
+    p_x[k] = in ? xb[i] : 0.f;
+    p_m[k] = in ? hb[i] : 0.f;         // (possibly uninitialised memory: only used when k_prev != 0)
+  }
+  float s = 1.0f;                       // rk.frac < 0: static clamp to [-1, 1]
+  if (rk.frac >= 0.f) {
+    s = resolve_quantile(hists + (int64_t)b * HIST_PER_SAMPLE, rk, s_part, s_res);
+    s = fmaxf(s, 1.0f);
+  }
+  const float* c = coef + (int64_t)(*step_dev) * 6;
+  const float k_x = c[2], k_m = c[3], k_prev = c[4];
+#pragma unroll
+  for (int k = 0; k < PRE; ++k) {
+    const int64_t i = i0 + k * stride;
+    if (i < n) {
+      const float m = fminf(fmaxf(p_x0[k], -s), s) / s;
+      if (x0o) x0o[i] = m;
+      float v = k_m * m;
+      if (k_prev != 0.f) v += k_prev * p_m[k];
+      if (k_x != 0.f) v += k_x * p_x[k];
+      hb[i] = m;
+      xb[i] = v;
+    }
+  }
+  for (int64_t i = i0 + PRE * stride; i < n; i += stride) {
+    const float m = fminf(fmaxf(x0b[i], -s), s) / s;
+    if (x0o) x0o[i] = m;
+    float v = k_m * m;
+    if (k_prev != 0.f) v += k_prev * hb[i];
+    if (k_x != 0.f) v += k_x * xb[i];
+    hb[i] = m;
+    xb[i] = v;
+  }
+  // end-of-step housekeeping by the workgroup that finishes last, exactly as in sampler_update_kernel
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned total = gridDim.x * gridDim.y;
+    const bool last = lfdm_ticket_take(ticket) == total - 1;
+    if (last) lfdm_ticket_reset(ticket);
+    s_res[0] = last ? 1u : 0u;
+  }
+  __syncthreads();
+  if (s_res[0]) {
+    const int64_t nz = (int64_t)hist_samples * HIST_PER_SAMPLE;
+    for (int64_t i = threadIdx.x; i < nz; i += 256) hists[i] = 0u;
+    if (advance_dev && threadIdx.x == 0) *advance_dev += 1;
+  }
+}
+
 // classifier-free guidance: out = null + (cond - null) * scale   (reference :525-526)
 __global__ __launch_bounds__(256) void cfg_combine_kernel(const float* __restrict__ cond_eps,
                                                           const float* __restrict__ null_eps,
@@ -424,4 +499,40 @@ extern "C" int lfdm_sampler_step_f32(float* x, const float* eps, const float* no
   LFDM_LAUNCH(sampler_update_kernel, grid, block, 0, stream, x, eps, noise, x0buf, x0_out, n, coef,
               (const int32_t*)step_dev, rk, hists, fold_clear ? batch : 0, ticket, advance ? step_dev : (int32_t*)nullptr);
   return lfdm_check_launch("sampler_step");
+}
+
+extern "C" int lfdm_sampler_step_ms_f32(float* x, const float* eps, float* hist, float* x0_out, int batch, int64_t n,
+                                        const float* coef, int32_t* step_dev, float quantile, int advance, void* ws,
+                                        size_t ws_bytes, lfdm_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!x || !eps || !hist || !coef || !step_dev || batch <= 0 || n <= 0 || n >= (1 << 24)) {
+    lfdm_set_error("sampler_step_ms: bad arguments (n < 2^24)");
+    return LFDM_EINVAL;
+  }
+  if (!ws || ws_bytes < lfdm_sampler_ws_bytes(batch, n)) {
+    lfdm_set_error("sampler_step_ms: workspace too small");
+    return LFDM_EWORKSPACE;
+  }
+  unsigned* hists = reinterpret_cast<unsigned*>(ws);
+  float* x0buf = reinterpret_cast<float*>(hists + (size_t)batch * HIST_PER_SAMPLE);
+  const bool dynamic = quantile >= 0.f;
+  if (dynamic && quantile > 1.f) {
+    lfdm_set_error("sampler_step_ms: quantile must lie in [0, 1] (or be negative for the static clamp to [-1, 1])");
+    return LFDM_EINVAL;
+  }
+  Ranks rk = make_ranks(n, dynamic ? quantile : 0.f);
+  if (!dynamic) rk.frac = -1.f;
+  const bool fold_clear = batch <= 2;             // as lfdm_sampler_step_f32: larger batches keep the clearing launch
+  if (!fold_clear) {
+    const int64_t nz = (int64_t)batch * HIST_PER_SAMPLE;
+    LFDM_LAUNCH(zero_u32_kernel, dim3((unsigned)((nz + 255) / 256 > 64 ? 64 : (nz + 255) / 256)), dim3(256), 0, stream, hists, nz);
+  }
+  unsigned* ticket = reinterpret_cast<unsigned*>(x0buf + (size_t)batch * n);
+  const dim3 grid(blocks_for(n), batch), block(256);
+  LFDM_LAUNCH(quantile_pass0_kernel, grid, block, 0, stream, (const float*)x, eps, x0buf, n, coef,
+              (const int32_t*)step_dev, hists);         // x0 = c_x*x - c_eps*eps: columns 0-1, the same table stride
+  if (dynamic) run_select(x0buf, batch, n, rk, hists, stream);
+  LFDM_LAUNCH(sampler_update_ms_kernel, grid, block, 0, stream, x, hist, (const float*)x0buf, x0_out, n, coef,
+              (const int32_t*)step_dev, rk, hists, fold_clear ? batch : 0, ticket, advance ? step_dev : (int32_t*)nullptr);
+  return lfdm_check_launch("sampler_step_ms");
 }

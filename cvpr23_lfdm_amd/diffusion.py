@@ -7,6 +7,7 @@ scalars live in device tables indexed by a device step counter, the reference's 
 syncs are gone).  Noise comes from torch's generator in the reference's order
 (SURVEY.md Appendix D), so a fixed seed reproduces.
 """
+import math
 import os
 
 import torch
@@ -42,9 +43,14 @@ class GaussianDiffusion(nn.Module):
     def __init__(self, denoise_fn, *, image_size, num_frames, text_use_bert_cls=False, channels=3,
                  timesteps=1000, sampling_timesteps=250, ddim_sampling_eta=1., loss_type='l1',
                  use_dynamic_thres=False, dynamic_thres_percentile=0.9, null_cond_prob=0.1,
-                 per_element_loss=False):
+                 per_element_loss=False, sampler="reference"):
+        """Reference signature + `sampler` (keyword): what `sample()` runs.  "reference" (default): the reference's own pair, DDIM when
+        sampling_timesteps < timesteps, ancestral DDPM otherwise.  "dpmpp_2m": DPM-Solver++(2M) (Lu et al. 2022), the second-order multistep
+        rule on the thresholded data prediction, one UNet evaluation per step, on the reference's DDIM time grid; "dpmpp_1": its first-order
+        form on every step.  Both are deterministic: nothing is drawn after x_T and `ddim_sampling_eta` is ignored (`_ms_step_tables`)."""
         super().__init__()
         check_num_frames(num_frames)
+        self.sampler = sampler
         # True = the *_multiGPU.py flavour of the reference (video_flow_diffusion_multiGPU.py:857-880):
         # un-reduced loss tensor and `(loss, null_cond_mask)` as the return value of p_losses / forward
         self.per_element_loss = per_element_loss
@@ -90,6 +96,18 @@ class GaussianDiffusion(nn.Module):
         # (rank, world) under sharded data parallelism (FlowDiffusion.enable_data_parallel): the training step's random
         # draws are made for the GLOBAL batch on every rank (identical generators) and sliced
         self.rank_shard = None
+
+    SAMPLERS = ("reference", "dpmpp_1", "dpmpp_2m")
+
+    @property
+    def sampler(self):
+        return self._sampler
+
+    @sampler.setter
+    def sampler(self, value):
+        if value not in self.SAMPLERS:
+            raise ValueError("sampler must be one of %s, got %r" % (self.SAMPLERS, value))
+        self.__dict__["_sampler"] = value
 
     def skip_step_draws(self, total, sample_shape, device, prob_focus_present=0.):
         """Advance the default generator exactly as one training step over `total` videos does (t :899, noise :858, the
@@ -172,15 +190,74 @@ class GaussianDiffusion(nn.Module):
             self.__dict__["_tables_cache"] = hit
         return hit[1], hit[2], hit[3], hit[4]
 
+    def _ms_step_tables(self, sampler):
+        """Timestep list and the (steps, 6) table {c_x, c_eps, k_x, k_m, k_prev, 0} of lfdm_sampler_step_ms_f32 for "dpmpp_2m" / "dpmpp_1":
+            m_i = threshold(c_x x - c_eps eps);   x <- k_x x + k_m m_i + k_prev m_{i-1}
+        Nodes: the DDIM grid `ddim_times()`.  The node at timestep `time` sits at a = alphas_cumprod[time] - the level the UNet is conditioned
+        on and x0 is predicted with (c_x, c_eps: the same two buffers as `_step_tables`) - and the end of the last step (time_next = 0) at
+        a = 1, sigma = 0.  (Not the DDIM row's alphas_cumprod_prev[time]: eps = (x - alpha_s x0) / sigma_s must hold on the level x0 was
+        predicted on.)  alpha = sqrt(a), sigma = sqrt(1 - a), lambda = log(alpha / sigma), h_i = lambda_n - lambda_s, r_i = h_{i-1} / h_i,
+        k_i = alpha_n - sigma_n alpha_s / sigma_s  (= -alpha_n (exp(-h_i) - 1), finite at the last node):
+            first step, LAST step (h = inf: lower-order final) and every "dpmpp_1" step:  k_x = sigma_n / sigma_s, k_m = k_i, k_prev = 0
+            otherwise:                            k_x = sigma_n / sigma_s, k_m = k_i (1 + 1 / (2 r_i)), k_prev = -k_i / (2 r_i)
+        evaluated in double on the host from the registered (fp32) buffers and rounded to fp32 once.  No noise, `ddim_sampling_eta` unused.
+        A grid whose timesteps do not strictly decrease (sampling_timesteps close to timesteps) is refused."""
+        if sampler not in ("dpmpp_1", "dpmpp_2m"):
+            raise ValueError("_ms_step_tables: sampler must be 'dpmpp_1' or 'dpmpp_2m', got %r" % (sampler,))
+        pairs = self.ddim_times()
+        for time, time_next in pairs:
+            if not (0 <= time_next < time < self.num_timesteps):
+                raise ValueError("sampler %r needs strictly decreasing timesteps: sampling_timesteps=%d on %d timesteps gives the step %d -> %d"
+                                 % (sampler, self.sampling_timesteps, self.num_timesteps, time, time_next))
+        acp = self.alphas_cumprod.detach().double().cpu()
+        c_x = self.sqrt_recip_alphas_cumprod.detach().float().cpu()
+        c_eps = self.sqrt_recipm1_alphas_cumprod.detach().float().cpu()
+
+        def level(time, end):
+            a = 1.0 if end else float(acp[time])
+            return math.sqrt(a), math.sqrt(1.0 - a)
+
+        rows, times, h_prev = [], [], None
+        for i, (time, time_next) in enumerate(pairs):
+            last = i == len(pairs) - 1
+            (al_s, sg_s), (al_n, sg_n) = level(time, False), level(time_next, last)
+            if not (sg_s > 0.0 and al_s > 0.0 and (last or sg_n > 0.0)):
+                raise ValueError("sampler %r: degenerate noise level at timestep %d" % (sampler, time))
+            k_x = sg_n / sg_s
+            k = al_n - sg_n * al_s / sg_s
+            h = math.inf if last else math.log(al_n / sg_n) - math.log(al_s / sg_s)
+            if sampler == "dpmpp_1" or i == 0 or last:
+                k_m, k_prev = k, 0.0
+            else:
+                half_inv_r = 0.5 * h / h_prev
+                k_m, k_prev = k * (1.0 + half_inv_r), -k * half_inv_r
+            h_prev = h
+            rows.append([float(c_x[time]), float(c_eps[time]), k_x, k_m, k_prev, 0.0])
+            times.append(time)
+        return times, torch.tensor(rows, dtype=torch.float64).float().contiguous()
+
+    def _ms_step_tables_on(self, sampler, dev):
+        """`_ms_step_tables` on `dev` in the shape `_step_tables_on` returns (no step draws), kept per (sampler, schedule) like it."""
+        key = (sampler, self.sampling_timesteps, self.num_timesteps, str(dev),
+               tuple((k, v._version, v.data_ptr()) for k, v in self.named_buffers(recurse=False)))
+        hit = self.__dict__.get("_ms_tables_cache")
+        if hit is None or hit[0] != key:
+            times, coef = self._ms_step_tables(sampler)
+            hit = (key, times, coef.to(dev), torch.tensor(times, dtype=torch.int32, device=dev), [False] * len(times))
+            self.__dict__["_ms_tables_cache"] = hit
+        return hit[1], hit[2], hit[3], hit[4]
+
     # ------------------------------------------------------------------ sampling
     @torch.no_grad()
     def sample(self, fea, cond=None, cond_scale=1., batch_size=16):
-        """Reference :762-775.  fea: planar (B, 256, S, S); cond: (B, 768) tensor or list[str]."""
+        """Reference :762-775.  fea: planar (B, 256, S, S); cond: (B, 768) tensor or list[str].  Runs `self.sampler`."""
         device = next(self.denoise_fn.parameters()).device
         if cond is not None:
             cond = self._embed(cond, device)
         batch = cond.shape[0] if cond is not None else batch_size
         shape = (batch, self.channels, self.num_frames, self.image_size, self.image_size)
+        if self.sampler != "reference":
+            return self._sample(fea, shape, cond, cond_scale, True, sampler=self.sampler)
         return self._sample(fea, shape, cond, cond_scale, self.is_ddim_sampling)
 
     @torch.no_grad()
@@ -191,13 +268,14 @@ class GaussianDiffusion(nn.Module):
     def ddim_sample(self, fea, shape, cond=None, cond_scale=1., clip_denoised=True):
         return self._sample(fea, shape, cond, cond_scale, True)
 
-    def _sample(self, fea, shape, cond, cond_scale, ddim):
+    def _sample(self, fea, shape, cond, cond_scale, ddim, sampler="reference"):
         unet = self.denoise_fn
         pk = unet.packed()
         dev = next(unet.parameters()).device
         batch, ch, frames, s, _ = shape
         n = ch * frames * s * s
-        times, coef_dev, t_table, draws = self._step_tables_on(ddim, dev)
+        multistep = sampler != "reference"
+        times, coef_dev, t_table, draws = self._ms_step_tables_on(sampler, dev) if multistep else self._step_tables_on(ddim, dev)
         steps = len(times)
 
         # ---- per-call constants -------------------------------------------------------------
@@ -226,7 +304,8 @@ class GaussianDiffusion(nn.Module):
 
         # ---- static step state ----------------------------------------------------------------
         # (the convolution precision explicitly: both modes share one pack - id(pk) does not tell a graph captured in the other mode apart)
-        key = (batch, frames, s, len(variants), float(cond_scale), bool(ddim), steps, id(pk), unet.conv_precision)
+        # (... and the sampler: a graph captured for one update rule must never be replayed for another)
+        key = (batch, frames, s, len(variants), float(cond_scale), bool(ddim), steps, id(pk), unet.conv_precision, sampler)
         plan = self._plans.get(key)
         if plan is None:
             plan = {
@@ -238,6 +317,8 @@ class GaussianDiffusion(nn.Module):
                 "noise": torch.empty(shape, device=dev), "step": torch.zeros(1, dtype=torch.int32, device=dev),
                 "ss": torch.empty(batch, pk["cond.n"], device=dev),
                 "ws": ops.sampler_ws(batch, n, dev), "graph": None, "pk": pk,
+                # m_{i-1} of the multistep samplers; never cleared: the first step of a video is first order and does not read it
+                "hist": torch.empty(shape, device=dev) if multistep else None,
             }
             self._plans = {key: plan}      # keep one plan (static buffers are large)
         if plan["graph"] is not None and plan.get("buf_gen") != unet._buf_gen:
@@ -265,8 +346,11 @@ class GaussianDiffusion(nn.Module):
                 r = unet.stem(pk, x2, b["fea_term"], 2 * batch, frames, s)
                 unet.run_trunk(pk, r, ss2, 2 * batch, frames, s, eps2)
                 ops.cfg_combine(eps2[:batch], eps2[batch:], b["scale"], eps)      # null + (cond - null) * scale
-            ops.sampler_step(x, eps, noise, b["coef"], step_dev, quantile=self.dynamic_thres_percentile if self.use_dynamic_thres else -1.0,
-                             ws=plan["ws"])
+            quantile = self.dynamic_thres_percentile if self.use_dynamic_thres else -1.0
+            if multistep:
+                ops.sampler_step_ms(x, eps, plan["hist"], b["coef"], step_dev, quantile=quantile, ws=plan["ws"])
+            else:
+                ops.sampler_step(x, eps, noise, b["coef"], step_dev, quantile=quantile, ws=plan["ws"])
 
         use_graph = (_native.library().kind == "hip" and os.environ.get("LFDM_NO_GRAPH", "0") != "1")
         self._draw(x)                                   # x_T  (:753 / :788)
@@ -303,7 +387,8 @@ class GaussianDiffusion(nn.Module):
         # span).  The step's noise draw is captured with the step (torch's graph-safe philox state: the draws are the ones the
         # eager loop makes, tests/test_end_to_end.py); a replayed noise tape (`noise_source`, the parity tests) cannot be captured
         # and keeps one step per replay.
-        chunk = int(os.environ.get("LFDM_GRAPH_STEPS", "10")) if (use_graph and self.noise_source is None) else 1
+        # (the multistep samplers draw nothing after x_T: a noise tape does not stand in their way)
+        chunk = int(os.environ.get("LFDM_GRAPH_STEPS", "10")) if (use_graph and (self.noise_source is None or multistep)) else 1
         if chunk <= 1:
             for i in range(steps):
                 if draws[i]:

@@ -68,14 +68,18 @@ class FlowDiffusion(nn.Module):
                  ddim_sampling_eta=1., timesteps=1000, dim_mults=(1, 2, 4, 8), lr=1e-4,
                  adam_betas=(0.9, 0.99), is_train=True, only_use_flow=True, use_residual_flow=False,
                  learn_null_cond=False, use_deconv=True, padding_mode="zeros", pretrained_pth="",
-                 config_pth="", bert_path=None, *, conv_precision="fp32"):
+                 config_pth="", bert_path=None, *, conv_precision="fp32", sampler="reference"):
         """Reference signature (video_flow_diffusion_model.py:19-37) + `bert_path`: a local Hugging Face directory of
         bert-base-cased for `cond=list[str]` (the reference downloads it with torch.hub; see text.py).  LFDM_BERT_PATH in
         the environment is the default, so unchanged caller scripts pick it up.
         conv_precision (keyword only): Unet3D.conv_precision of the denoiser - "fp32" (default) or "bf16", the opt-in faster sampling mode
-        whose Winograd 3x3 convolutions run on bf16 operands (sampling and the eval branch of p_losses; training stays fp32)."""
+        whose Winograd 3x3 convolutions run on bf16 operands (sampling and the eval branch of p_losses; training stays fp32).
+        sampler (keyword only): GaussianDiffusion.sampler - "reference" (default: DDIM / DDPM as the reference chooses), "dpmpp_2m"
+        (DPM-Solver++(2M): second order, deterministic, meant for few steps) or "dpmpp_1"; composes with conv_precision."""
         super().__init__()
         check_num_frames(num_frames)        # (before the checkpoint and the config are read)
+        if sampler not in GaussianDiffusion.SAMPLERS:
+            raise ValueError("sampler must be one of %s, got %r" % (GaussianDiffusion.SAMPLERS, sampler))
         self.use_residual_flow = use_residual_flow
         self.only_use_flow = only_use_flow
         checkpoint = torch.load(pretrained_pth, map_location="cpu") if pretrained_pth != "" else None
@@ -100,7 +104,7 @@ class FlowDiffusion(nn.Module):
         self.diffusion = GaussianDiffusion(self.unet, image_size=img_size, num_frames=num_frames,
                                            sampling_timesteps=sampling_timesteps, timesteps=timesteps,
                                            loss_type='l2', use_dynamic_thres=True,
-                                           null_cond_prob=null_cond_prob, ddim_sampling_eta=ddim_sampling_eta)
+                                           null_cond_prob=null_cond_prob, ddim_sampling_eta=ddim_sampling_eta, sampler=sampler)
         bert_path = bert_path or os.environ.get("LFDM_BERT_PATH")
         if bert_path:
             from .text import BertTextEncoder

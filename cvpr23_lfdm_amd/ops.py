@@ -876,6 +876,23 @@ def sampler_step(x, eps, noise, coef, step_dev, *, quantile=0.9, advance=True, x
     return x
 
 
+def sampler_step_ms(x, eps, hist, coef, step_dev, *, quantile=0.9, advance=True, x0_out=None, ws=None):
+    """lfdm_sampler_step_ms_f32: x <- k_x*x + k_m*m + k_prev*hist, hist <- m (the thresholded data prediction of this step);
+    coef rows {c_x, c_eps, k_x, k_m, k_prev, 0} (GaussianDiffusion._ms_step_tables)."""
+    lib = _lib()
+    _chk(lib, x, eps, hist, coef, step_dev, x0_out, ws)
+    batch = x.shape[0]
+    n = x.numel() // batch
+    if hist.numel() != x.numel():
+        raise ValueError("sampler_step_ms: hist must have x's %d elements, got %d" % (x.numel(), hist.numel()))
+    if ws is None:
+        ws = sampler_ws(batch, n, x.device)
+    lib.check(lib.lfdm_sampler_step_ms_f32(_p(x), _p(eps), _p(hist), _p(x0_out), batch, n, _p(coef),
+                                           _p(step_dev), quantile, int(advance), _p(ws), ws.numel() * 4,
+                                           _stream(lib)), "lfdm_sampler_step_ms_f32")
+    return x
+
+
 def cfg_combine(cond_eps, null_eps, scale, out):
     lib = _lib()
     _chk(lib, cond_eps, null_eps, out)

@@ -328,6 +328,18 @@ int lfdm_sampler_step_f32(float* x, const float* eps, const float* noise, float*
                           int batch, int64_t n, const float* coef, int32_t* step_dev,
                           float quantile, int advance, void* ws, size_t ws_bytes,
                           lfdm_stream_t stream);
+/* Multistep sampler step (additive, ABI version unchanged): DPM-Solver++ (Lu et al. 2022; "2M", and its first-order form) on the THRESHOLDED
+ * data prediction.  Pass 0, the quantile selection and the launch sequence are lfdm_sampler_step_f32's; only the update differs:
+ *   x0 = c_x*x - c_eps*eps;  m = clamp(x0, -s, s) / s  (s as above);   x <- k_x*x + k_m*m + k_prev*m_prev;   hist <- m
+ *   coef[step] = { c_x, c_eps, k_x, k_m, k_prev, unused }      (the same 6-float row stride, columns 0-1 with the same meaning)
+ * hist (B, n), in/out: m of the previous step on entry, m of this step on return (each element is read, then written, by one thread;
+ * it must not alias x, eps or x0_out).  The raw eps is not used after x0, and there is no noise operand: the rule is deterministic.
+ * A coefficient that is exactly 0 skips its operand: a first-order row (k_prev == 0: the first and the last step of a video) may be
+ * handed a hist of UNINITIALISED memory, NaNs included, and neither reads its values into the result nor needs it cleared.
+ * x0_out optional (B, n): receives m as well.  ws, quantile, advance, step_dev: as lfdm_sampler_step_f32 (one workspace may serve both). */
+int lfdm_sampler_step_ms_f32(float* x, const float* eps, float* hist, float* x0_out, int batch, int64_t n,
+                             const float* coef, int32_t* step_dev, float quantile, int advance, void* ws,
+                             size_t ws_bytes, lfdm_stream_t stream);
 /* classifier-free guidance combine of Unet3D.forward_with_cond_scale (:525-526):
  * out = null_eps + (cond_eps - null_eps) * scale   (out may alias an input) */
 int lfdm_cfg_combine_f32(const float* cond_eps, const float* null_eps, float scale, float* out,

@@ -1,0 +1,430 @@
+"""sampler="dpmpp_2m" / "dpmpp_1": DPM-Solver++ (Lu et al. 2022) on the thresholded data prediction, on the reference's DDIM time grid
+(DESIGN.md 4.2).  Five groups: the coefficient tables against an independent double evaluation; one step of lfdm_sampler_step_ms_f32 against
+a torch double model; second-order convergence on a Gaussian whose probability-flow ODE has a closed form; whole videos against a loop over
+the oracle's own pieces; and the plumbing (history, plan keys, chunked graphs, composition with conv_precision) on the GPU.
+
+Every formula is written out again here (numpy / torch double) from the contract, not imported from the package."""
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import lfdm_oracle as O
+import synth
+from util import assert_close, rnd
+
+
+def big(dev):
+    return dev == "cuda"
+
+
+def diffusion(sampler, steps, total=1000, **kw):
+    from cvpr23_lfdm_amd import GaussianDiffusion
+    return GaussianDiffusion(torch.nn.Identity(), image_size=8, num_frames=4, timesteps=total, sampling_timesteps=steps,
+                             loss_type="l2", sampler=sampler, **kw)
+
+
+def levels(total, steps):
+    """[(time, alpha_s, sigma_s, alpha_n, sigma_n)] in double from the fp32 alphas_cumprod: node at `time` on alphas_cumprod[time],
+    the end of the last step on a = 1."""
+    acp = O.make_schedule(total)["alphas_cumprod"].double().numpy()
+    pairs = O.ddim_time_pairs(total, steps)
+    out = []
+    for i, (time, time_next) in enumerate(pairs):
+        a_s = acp[time]
+        a_n = 1.0 if i == len(pairs) - 1 else acp[time_next]
+        out.append((time, math.sqrt(a_s), math.sqrt(1.0 - a_s), math.sqrt(a_n), math.sqrt(1.0 - a_n)))
+    return out
+
+
+def expected_rows(total, steps, sampler):
+    """(k_x, k_m, k_prev) per step in double, from the contract."""
+    lv = levels(total, steps)
+    rows, h_prev = [], None
+    for i, (_, al_s, sg_s, al_n, sg_n) in enumerate(lv):
+        last = i == len(lv) - 1
+        k = al_n - sg_n * al_s / sg_s
+        h = math.inf if last else math.log(al_n / sg_n) - math.log(al_s / sg_s)
+        if sampler == "dpmpp_1" or i == 0 or last:
+            rows.append((sg_n / sg_s, k, 0.0))
+        else:
+            r = h_prev / h
+            rows.append((sg_n / sg_s, k * (1.0 + 1.0 / (2.0 * r)), -k / (2.0 * r)))
+        h_prev = h
+    return np.array(rows)
+
+
+# ------------------------------------------------------------------------------------------ 1. tables (host only)
+@pytest.mark.parametrize("steps", [1, 2, 3, 20, 100])
+def test_tables(steps):
+    total = 1000
+    sched = O.make_schedule(total)
+    pairs = O.ddim_time_pairs(total, steps)
+    for sampler in ("dpmpp_2m", "dpmpp_1"):
+        d = diffusion(sampler, steps, total)
+        times, coef = d._ms_step_tables(sampler)
+        assert times == [p[0] for p in pairs] and coef.shape == (steps, 6) and coef.dtype == torch.float32
+        for i, t in enumerate(times):                   # x0 on the level the UNet is conditioned on: the reference's two buffers
+            assert torch.equal(coef[i, 0], sched["sqrt_recip_alphas_cumprod"][t]) and torch.equal(coef[i, 1], sched["sqrt_recipm1_alphas_cumprod"][t])
+        assert float(coef[:, 5].abs().max()) == 0.0
+        want = expected_rows(total, steps, sampler)
+        got = coef[:, 2:5].double().numpy()
+        assert np.all(np.abs(got - want) <= 1e-6 * np.abs(want)), (sampler, np.abs(got - want).max())
+        assert got[0, 2] == 0.0 and tuple(got[-1]) == (0.0, 1.0, 0.0)             # first and last row first order, the last one x <- m
+        if sampler == "dpmpp_1":
+            assert np.all(got[:, 2] == 0.0)
+        elif steps > 2:
+            assert np.all(got[1:-1, 2] < 0.0) and np.all(got[1:-1, 1] > expected_rows(total, steps, "dpmpp_1")[1:-1, 1])
+    # "dpmpp_1" = the eps-form DDIM rule (eta = 0) on the same levels wherever nothing is clamped
+    d = diffusion("dpmpp_1", steps, total)
+    _, coef = d._ms_step_tables("dpmpp_1")
+    c = coef.double().numpy()
+    rng = np.random.Generator(np.random.PCG64(steps))
+    worst = 0.0
+    for i, (_, al_s, sg_s, al_n, sg_n) in enumerate(levels(total, steps)):
+        x, eps = rng.standard_normal(256), rng.standard_normal(256)
+        x0 = c[i, 0] * x - c[i, 1] * eps
+        got = c[i, 2] * x + c[i, 3] * x0
+        ref = al_n * x0 + sg_n * eps
+        err = np.abs(got - ref).max() / max(1.0, np.abs(ref).max())
+        worst = max(worst, err)
+        assert err <= 1e-6, (i, err)
+    print("dpmpp_1 vs eps-form DDIM, %d steps: worst relative error %.2e" % (steps, worst))
+
+
+def test_tables_refuse_repeated_nodes_and_bad_names():
+    from cvpr23_lfdm_amd import FlowDiffusion, GaussianDiffusion
+    d = diffusion("dpmpp_2m", 1000, 1000)                         # linspace(0, 1000, 1002) truncated to int repeats timesteps
+    assert any(a <= b for a, b in d.ddim_times())
+    with pytest.raises(ValueError, match="strictly decreasing"):
+        d._ms_step_tables("dpmpp_2m")
+    with pytest.raises(ValueError, match="strictly decreasing"):
+        d._ms_step_tables_on("dpmpp_1", torch.device("cpu"))
+    diffusion("dpmpp_2m", 999, 1000)._ms_step_tables("dpmpp_2m")     # every timestep once: fine
+    with pytest.raises(ValueError, match="sampler"):
+        GaussianDiffusion(torch.nn.Identity(), image_size=8, num_frames=4, sampler="dpm")
+    with pytest.raises(ValueError, match="sampler"):
+        FlowDiffusion(config_pth=synth.CONFIG, is_train=False, sampler="heun")
+    d = diffusion("reference", 10)
+    assert d.sampler == "reference"
+    with pytest.raises(ValueError, match="sampler"):
+        d.sampler = "dpmpp_3m"
+    assert d.sampler == "reference"
+    with pytest.raises(ValueError):
+        d._ms_step_tables("reference")
+
+
+def test_tables_are_kept_per_sampler_and_schedule():
+    d = diffusion("dpmpp_2m", 10, 50)
+    cpu = torch.device("cpu")
+    t1, c1, tt1, dr1 = d._ms_step_tables_on("dpmpp_2m", cpu)
+    t2, c2, tt2, _ = d._ms_step_tables_on("dpmpp_2m", cpu)
+    assert c1 is c2 and tt1 is tt2 and tt1.tolist() == t1 and dr1 == [False] * 10
+    _, c3, _, _ = d._ms_step_tables_on("dpmpp_1", cpu)
+    assert c3 is not c1 and not torch.equal(c3, c1)
+    d.alphas_cumprod.mul_(0.5)                                      # an in-place write bumps the buffer's version counter
+    _, c4, _, _ = d._ms_step_tables_on("dpmpp_1", cpu)
+    assert not torch.equal(c4, c3)
+    # the reference tables are what they were
+    ref = diffusion("reference", 10, 50)
+    two = diffusion("dpmpp_2m", 10, 50)
+    for a, b in zip(ref._step_tables(True), two._step_tables(True)):
+        assert torch.equal(a, b) if isinstance(a, torch.Tensor) else a == b
+
+
+# ------------------------------------------------------------------------------------------ 2. one step of the op
+def _m_model(x0, s):
+    s = s.view(-1, 1)
+    return torch.maximum(torch.minimum(x0, s), -s) / s
+
+
+@pytest.mark.parametrize("n", [1061, 1200007])
+@pytest.mark.parametrize("batch", [1, 2, 3])
+@pytest.mark.parametrize("dynamic", [True, False])
+def test_step_ms(backend, dynamic, batch, n):
+    """Row 1 of the table is a first-order step on a history full of NaN, row 2 a second-order step on the history row 1 left.  c_x, c_eps are
+    powers of two: x0 = c_x x - c_eps eps then has ONE rounding whether or not the compiler contracts it into an FMA, so the test knows the
+    kernel's x0 - and with it the threshold - bit for bit.  n = 1 200 007 > 8 x 512 x 256: the loop behind the prefetched elements runs."""
+    from cvpr23_lfdm_amd import ops
+    dev = backend
+    if n > 1 << 20 and not big(dev):
+        pytest.skip("above 8 x 512 x 256 elements per sample: GPU only")
+    q = 0.9 if dynamic else -1.0
+    table = torch.tensor([[9., 9., 9., 9., 9., 9.], [2.0, 0.5, 0.8125, 0.37, 0.0, 0.0], [0.5, 0.25, 0.9, 0.61, -0.23, 0.0]])
+    x, e1, e2 = rnd(batch, n, seed=1), rnd(batch, n, seed=2), rnd(batch, n, seed=3)
+    if batch > 1:
+        x[1] *= 0.1                      # |x0| stays below 1 here: the dynamic threshold sits on its floor s = 1
+        e1[1] *= 0.1
+
+    def thresholds(x0):
+        if not dynamic:
+            return torch.ones(batch)
+        return ops.abs_quantile(x0.to(dev).contiguous(), 0.9).cpu().clamp_min(1.0)
+
+    def run():
+        xd, hist, x0_out = x.clone().to(dev), torch.full((batch, n), float("nan")).to(dev), torch.empty(batch, n).to(dev)
+        step = torch.tensor([1], dtype=torch.int32).to(dev)
+        ws = ops.sampler_ws(batch, n, dev)
+        ops.sampler_step_ms(xd, e1.to(dev), hist, table.to(dev), step, quantile=q, x0_out=x0_out, ws=ws)
+        first = (xd.cpu().clone(), hist.cpu().clone(), x0_out.cpu().clone(), int(step.cpu()[0]))
+        ops.sampler_step_ms(xd, e2.to(dev), hist, table.to(dev), step, quantile=q, ws=ws)
+        return first, (xd.cpu(), hist.cpu(), int(step.cpu()[0]))
+
+    (x1, h1, o1, s1), (x2, h2, s2) = run()
+    # first-order step
+    c = table[1]
+    x0 = c[0] * x - c[1] * e1                                          # (exact products, one rounding)
+    s = thresholds(x0)
+    if dynamic:
+        assert float(s[0]) > 1.0 and (batch == 1 or float(s[1]) == 1.0)
+    m1 = _m_model(x0, s)
+    assert s1 == 2 and s2 == 3
+    assert torch.isfinite(x1).all() and torch.isfinite(h1).all()
+    assert torch.equal(h1, m1), "m differs from clamp(x0, -s, s) / s with s = max(abs_quantile, 1): %.3e" % float((h1 - m1).abs().max())
+    assert torch.equal(o1, h1)
+    ref1 = float(c[2]) * x.double() + float(c[3]) * m1.double()
+    err1 = float((x1.double() - ref1).abs().max())
+    # second-order step, history updated in place
+    c = table[2]
+    x0 = c[0] * x1 - c[1] * e2
+    m2 = _m_model(x0, thresholds(x0))
+    assert torch.equal(h2, m2)
+    ref2 = float(c[2]) * x1.double() + float(c[3]) * m2.double() + float(c[4]) * m1.double()
+    err2 = float((x2.double() - ref2).abs().max())
+    print("step_ms %s B=%d n=%d: max abs err first order %.2e, second order %.2e" % ("dynamic" if dynamic else "static", batch, n, err1, err2))
+    assert err1 <= 1e-5 and err2 <= 1e-5, (err1, err2)
+    assert float((x2.double() - (float(c[2]) * x1.double() + float(c[3]) * m2.double())).abs().max()) > 1e-2, "history not used"
+    # the same calls again: the same bits
+    (y1, g1, p1, _), (y2, g2, _) = run()
+    for a, b in ((x1, y1), (h1, g1), (o1, p1), (x2, y2), (h2, g2)):
+        assert torch.equal(a, b)
+
+
+def test_step_ms_refuses_bad_arguments(backend):
+    from cvpr23_lfdm_amd import ops
+    dev = backend
+    x, eps = torch.zeros(1, 300).to(dev), torch.zeros(1, 300).to(dev)
+    table, step = torch.zeros(1, 6).to(dev), torch.zeros(1, dtype=torch.int32).to(dev)
+    with pytest.raises(ValueError, match="hist"):
+        ops.sampler_step_ms(x, eps, torch.zeros(1, 299).to(dev), table, step)
+    with pytest.raises(RuntimeError, match="quantile"):
+        ops.sampler_step_ms(x, eps, torch.zeros(1, 300).to(dev), table, step, quantile=1.5)
+
+
+# ------------------------------------------------------------------------------------------ 3. analytic convergence
+MU, SD = 0.3, 0.2
+
+
+def _gauss_eps(x, al, sg):
+    """The optimal eps-predictor for i.i.d. N(MU, SD^2) data at level (alpha, sigma)."""
+    return sg * (x - al * MU) / (al * al * SD * SD + sg * sg)
+
+
+def _drive(dev, sampler, steps, x_t):
+    """All steps but the last: (the op's x, the test's own double recurrence, the exact ODE solution) at the second-to-last node."""
+    from cvpr23_lfdm_amd import ops
+    d = diffusion(sampler, steps)
+    _, coef = d._ms_step_tables(sampler)
+    lv = levels(1000, steps)
+    rows = expected_rows(1000, steps, sampler)
+    n = x_t.numel()
+    xd, hist = x_t.clone().view(1, n).to(dev), torch.full((1, n), float("nan")).to(dev)
+    step = torch.zeros(1, dtype=torch.int32).to(dev)
+    ws, coef_dev = ops.sampler_ws(1, n, dev), coef.to(dev)
+    x64, m_prev, peak = x_t.double().numpy().copy(), None, 0.0
+    for i in range(steps - 1):
+        _, al_s, sg_s, _, _ = lv[i]
+        eps = _gauss_eps(xd.double(), al_s, sg_s).float()
+        ops.sampler_step_ms(xd, eps, hist, coef_dev, step, quantile=-1.0, ws=ws)
+        e64 = _gauss_eps(x64, al_s, sg_s)
+        m = np.clip((x64 - sg_s * e64) / al_s, -1.0, 1.0)
+        peak = max(peak, float(np.abs((x64 - sg_s * e64) / al_s).max()))
+        x64 = rows[i, 0] * x64 + rows[i, 1] * m + (rows[i, 2] * m_prev if rows[i, 2] != 0.0 else 0.0)
+        m_prev = m
+    assert int(step.cpu()[0]) == steps - 1
+    assert peak < 1.0, "the clamp must stay inactive for the closed form to hold (max |x0| %.3f)" % peak
+    _, al_0, sg_0, _, _ = lv[0]
+    _, al_e, sg_e, _, _ = lv[steps - 1]
+    x0 = x_t.double().numpy()
+    exact = al_e * MU + math.sqrt(al_e ** 2 * SD ** 2 + sg_e ** 2) * (x0 - al_0 * MU) / math.sqrt(al_0 ** 2 * SD ** 2 + sg_0 ** 2)
+    return xd.cpu().double().numpy().reshape(-1), x64, exact
+
+
+@pytest.mark.parametrize("steps", [10, 20, 40])
+def test_second_order_convergence(backend, steps):
+    """Data N(0.3, 0.2^2): eps*(x, a) = sigma (x - alpha mu) / (alpha^2 s^2 + sigma^2) and the probability-flow ODE keeps
+    (x - alpha mu) / sqrt(alpha^2 s^2 + sigma^2) constant.  A double numpy model of the two recurrences gives max errors (first order / 2M)
+    8.0e-2 / 1.35e-2, 6.6e-2 / 6.1e-3, 4.3e-2 / 1.07e-2 at 10 / 20 / 40 steps: ratios 5.9, 10.7, 4.0.  The bar is half the smallest."""
+    dev = backend
+    x_t = rnd(4096, seed=17)
+    errs = {}
+    for sampler in ("dpmpp_1", "dpmpp_2m"):
+        got, model, exact = _drive(dev, sampler, steps, x_t)
+        assert np.abs(got - model).max() <= 1e-5, (sampler, np.abs(got - model).max())
+        errs[sampler] = float(np.abs(got - exact).max())
+    print("%d steps: max error against the exact ODE solution, dpmpp_1 %.3e, dpmpp_2m %.3e (ratio %.1f)"
+          % (steps, errs["dpmpp_1"], errs["dpmpp_2m"], errs["dpmpp_1"] / errs["dpmpp_2m"]))
+    assert errs["dpmpp_2m"] <= 0.5 * errs["dpmpp_1"], errs
+
+
+# ------------------------------------------------------------------------------------------ 4. whole samples against the oracle
+def _skip_slow_emu(dev):
+    if dev == "cpu" and os.environ.get("LFDM_EMU_E2E", "0") != "1":
+        pytest.skip("end-to-end under the emulator is opt-in (LFDM_EMU_E2E=1); it runs on the GPU")
+
+
+def oracle_dpmpp_2m(sd, gsd, img, cond, frames, s, steps, total, cond_scale, noise_fn):
+    """sample_one_video with the DPM-Solver++(2M) loop in place of O.sample: the oracle's UNet, x0 prediction and dynamic threshold, the
+    update of the contract in double."""
+    fea = O.generator_compute_fea(gsd, img)
+    b = cond.shape[0]
+    x = noise_fn((b, 3, frames, s, s))
+    fea_rep = fea.unsqueeze(2).repeat(1, 1, frames, 1, 1)
+    lv = levels(total, steps)
+    m_prev, h_prev = None, None
+    for i, (time, al_s, sg_s, al_n, sg_n) in enumerate(lv):
+        last = i == len(lv) - 1
+        t = torch.full((b,), time, dtype=torch.long)
+        eps = O.unet_forward_with_cond_scale(sd, torch.cat([x, fea_rep], dim=1), t, cond, cond_scale)
+        m = O.dynamic_threshold(O.predict_start_from_noise(sd, x, t, eps)).double()
+        k = al_n - sg_n * al_s / sg_s
+        h = math.inf if last else math.log(al_n / sg_n) - math.log(al_s / sg_s)
+        if i == 0 or last:
+            new = (sg_n / sg_s) * x.double() + k * m
+        else:
+            r = h_prev / h
+            new = (sg_n / sg_s) * x.double() + k * (1 + 1 / (2 * r)) * m - k / (2 * r) * m_prev
+        x, m_prev, h_prev = new.float(), m, h
+    grid, conf = x[:, :2], (x[:, 2:3] + 1) * 0.5
+    outs, warps = [], []
+    for f in range(frames):
+        g = O.generator_forward_with_flow(gsd, img, grid[:, :, f].permute(0, 2, 3, 1), conf[:, :, f])
+        outs.append(g["prediction"])
+        warps.append(g["deformed"])
+    return {"sample_vid_grid": grid, "sample_vid_conf": conf, "sample_out_vid": torch.stack(outs, dim=2),
+            "sample_warped_vid": torch.stack(warps, dim=2)}
+
+
+@pytest.mark.parametrize("cond_scale", [1.0, 2.0])
+def test_sample_one_video_dpmpp_2m(backend, cond_scale):
+    """Six steps: first-order start, four second-order steps, first-order end; cond_scale 2 goes through the batched guidance pass."""
+    dev = backend
+    _skip_slow_emu(dev)
+    z = dict(b=1, t=2, s=8, hw=32) if dev == "cpu" else dict(b=2, t=8, s=16, hw=64)
+    steps, total = 6, 1000
+    m, dsd, gsd = synth.build_flow_diffusion(dev, img_size=z["s"], num_frames=z["t"], sampling_timesteps=steps, timesteps=total,
+                                             sampler="dpmpp_2m")
+    assert m.diffusion.sampler == "dpmpp_2m"
+    img, cond = synth.inputs(z["b"], z["hw"])
+    sd = dict(dsd)
+    sd.update(O.make_schedule(total))
+    ref = oracle_dpmpp_2m(sd, gsd, img, cond, z["t"], z["s"], steps, total, cond_scale, synth.NoiseTape(11))
+    m.diffusion.noise_source = synth.NoiseTape(11)
+    m.set_sample_input(sample_img=img.to(dev), sample_text=cond.to(dev))
+    m.sample_one_video(cond_scale=cond_scale)
+    for k in ("sample_vid_grid", "sample_vid_conf", "sample_warped_vid", "sample_out_vid"):
+        assert_close(getattr(m, k).cpu(), ref[k], 1e-3, "%s (dpmpp_2m, cond_scale %g)" % (k, cond_scale))
+
+
+# ------------------------------------------------------------------------------------------ 5. plumbing on the GPU
+def _gpu():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from cvpr23_lfdm_amd import _native
+    _native._set_library_for_tests(None)
+
+
+def _video(m, seed):
+    img, cond = synth.inputs(1, 32, seed=seed)
+    m.diffusion.noise_source = synth.NoiseTape(seed)
+    m.set_sample_input(sample_img=img.cuda(), sample_text=cond.cuda())
+    m.sample_one_video(cond_scale=1.0)
+    return torch.cat((m.sample_vid_grid, m.sample_vid_conf), dim=1).clone()
+
+
+KW = dict(img_size=8, num_frames=4, sampling_timesteps=7)
+
+
+@pytest.mark.gpu
+def test_consecutive_videos_equal_fresh_models():
+    """The second video of a model (replayed graph, history buffer left by the first video) equals a fresh model's, bit for bit."""
+    _gpu()
+    m, _, _ = synth.build_flow_diffusion("cuda", sampler="dpmpp_2m", **KW)
+    both = [_video(m, 5), _video(m, 6)]
+    for seed, got in zip((5, 6), both):
+        fresh, _, _ = synth.build_flow_diffusion("cuda", sampler="dpmpp_2m", **KW)
+        assert torch.equal(got, _video(fresh, seed)), "video with tape %d" % seed
+    assert not torch.equal(both[0], both[1])
+
+
+@pytest.mark.gpu
+def test_graph_chunks_do_not_change_the_result(monkeypatch):
+    _gpu()
+    outs = {}
+    for k in ("1", "10", "3"):
+        monkeypatch.setenv("LFDM_GRAPH_STEPS", k)
+        m, _, _ = synth.build_flow_diffusion("cuda", sampler="dpmpp_2m", **KW)
+        outs[k] = [_video(m, 5), _video(m, 6)]
+    for k in ("10", "3"):
+        for a, b in zip(outs["1"], outs[k]):
+            assert torch.equal(a, b), "LFDM_GRAPH_STEPS=%s" % k
+    monkeypatch.setenv("LFDM_GRAPH_STEPS", "10")
+    m, _, _ = synth.build_flow_diffusion("cuda", sampler="dpmpp_2m", **KW)      # ... and without a tape: x_T from torch's generator
+    m.diffusion.noise_source = None
+    img, cond = synth.inputs(1, 32, seed=5)
+    m.set_sample_input(sample_img=img.cuda(), sample_text=cond.cuda())
+    vids = []
+    for _ in range(2):
+        torch.manual_seed(77)
+        m.sample_one_video(cond_scale=1.0)
+        vids.append(m.sample_vid_grid.clone())
+    assert torch.equal(vids[0], vids[1]) and torch.isfinite(vids[0]).all()
+
+
+@pytest.mark.gpu
+def test_reference_sampler_is_untouched_by_a_multistep_video():
+    """One model: DDIM, a dpmpp_2m video, DDIM again - the two DDIM videos are equal bit for bit and equal a model that never left
+    "reference" (the plan key carries the sampler: no graph of one update rule is replayed for another)."""
+    _gpu()
+    m, _, _ = synth.build_flow_diffusion("cuda", **KW)
+    assert m.diffusion.sampler == "reference"
+    before = _video(m, 5)
+    m.diffusion.sampler = "dpmpp_2m"
+    two = _video(m, 5)
+    m.diffusion.sampler = "dpmpp_1"
+    one = _video(m, 5)
+    m.diffusion.sampler = "reference"
+    after = _video(m, 5)
+    assert torch.equal(before, after)
+    assert not torch.equal(before, two) and not torch.equal(two, one)
+    fresh, _, _ = synth.build_flow_diffusion("cuda", sampler="dpmpp_2m", **KW)
+    assert torch.equal(two, _video(fresh, 5))
+
+
+@pytest.mark.gpu
+def test_composes_with_bf16_convolutions():
+    _gpu()
+    m, _, _ = synth.build_flow_diffusion("cuda", conv_precision="bf16", sampler="dpmpp_2m", **KW)
+    fp32, _, _ = synth.build_flow_diffusion("cuda", sampler="dpmpp_2m", **KW)
+    a, b = _video(m, 5), _video(fp32, 5)
+    assert torch.isfinite(a).all() and torch.isfinite(m.sample_out_vid).all()
+    assert not torch.equal(a, b), "bf16 mode ran the fp32 convolutions"
+
+
+@pytest.mark.gpu
+def test_functional_wrapper_takes_the_sampler():
+    _gpu()
+    from cvpr23_lfdm_amd.flow_diffusion import FlowDiffusionFunctional
+    m = FlowDiffusionFunctional(img_size=8, num_frames=4, sampling_timesteps=7, is_train=False, config_pth=synth.CONFIG,
+                                sampler="dpmpp_2m")
+    assert m.diffusion.sampler == "dpmpp_2m"
+    m.unet.load_state_dict(synth.unet_state())
+    m.generator.load_state_dict(synth.generator_state())
+    m.eval().cuda()
+    ref, _, _ = synth.build_flow_diffusion("cuda", sampler="dpmpp_2m", **KW)
+    img, cond = synth.inputs(1, 32, seed=5)
+    m.diffusion.noise_source = synth.NoiseTape(5)
+    out = m.sample_one_video(img.cuda(), cond.cuda(), 1.0)
+    assert torch.equal(torch.cat((out["sample_vid_grid"], out["sample_vid_conf"]), dim=1), _video(ref, 5))

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
-"""lfdm_sampler_step_f32 at the C2 latent (B=1, 3x40x32x32): us per step (graph replay)."""
+"""lfdm_sampler_step_f32 and lfdm_sampler_step_ms_f32 at the C2 latent (B=1, 3x40x32x32): us per step (graph replay), alternating."""
 import os
+import statistics
 import sys
 
 import torch
@@ -8,24 +9,38 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cvpr23_lfdm_amd import ops  # noqa: E402
 
-for b, shape in ((1, (3, 40, 32, 32)), (16, (3, 40, 32, 32)), (4, (3, 40, 64, 64))):
-    x, eps, noise = [torch.randn(b, *shape, device="cuda") for _ in range(3)]
-    n = x[0].numel()
-    table = torch.rand(4, 6, device="cuda")
-    step = torch.zeros(1, dtype=torch.int32, device="cuda")
-    ws = ops.sampler_ws(b, n, "cuda")
-    fn = lambda: ops.sampler_step(x, eps, noise, table, step, ws=ws, advance=False)
-    for _ in range(3):
-        fn()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for _ in range(10):
-            fn()
-    torch.cuda.synchronize()
+
+def replay_us(g):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(10):
         g.replay()
     e1.record()
     torch.cuda.synchronize()
-    print("B=%2d n=%7d: %.1f us per sampler step" % (b, n, e0.elapsed_time(e1) * 1e3 / 100))
+    return e0.elapsed_time(e1) * 1e3 / 100
+
+
+for b, shape in ((1, (3, 40, 32, 32)), (16, (3, 40, 32, 32)), (4, (3, 40, 64, 64))):
+    x, eps, noise, hist = [torch.randn(b, *shape, device="cuda") for _ in range(4)]
+    n = x[0].numel()
+    table = torch.rand(4, 6, device="cuda")            # every coefficient non-zero: the multistep update reads its history
+    step = torch.zeros(1, dtype=torch.int32, device="cuda")
+    ws = ops.sampler_ws(b, n, "cuda")
+    fns = {"sampler_step": lambda: ops.sampler_step(x, eps, noise, table, step, ws=ws, advance=False),
+           "sampler_step_ms": lambda: ops.sampler_step_ms(x, eps, hist, table, step, ws=ws, advance=False)}
+    graphs = {}
+    for name, fn in fns.items():
+        for _ in range(3):
+            fn()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for _ in range(10):
+                fn()
+        graphs[name] = g
+    torch.cuda.synchronize()
+    times = {name: [] for name in graphs}
+    for _ in range(5):
+        for name, g in graphs.items():
+            times[name].append(replay_us(g))
+    print("B=%2d n=%7d: %s" % (b, n, ",  ".join("%s %.1f us per step (min %.1f, max %.1f)" % (k, statistics.median(t), min(t), max(t))
+                                                  for k, t in times.items())))

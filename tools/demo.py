@@ -31,13 +31,15 @@ def main():
     ap.add_argument("--text", nargs="+", default=["happiness"])
     ap.add_argument("--frames", type=int, default=40)
     ap.add_argument("--size", type=int, default=128)
-    ap.add_argument("--steps", type=int, default=100, help="DDIM steps (sampling_timesteps)")
+    ap.add_argument("--steps", type=int, default=100, help="sampler steps (sampling_timesteps): DDIM, or --sampler's")
     ap.add_argument("--cond-scale", type=float, default=1.0)
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--out", default="demo_out")
     ap.add_argument("--conv-precision", choices=("fp32", "bf16"), default="fp32",
                     help="operands of the UNet's Winograd 3x3 convolutions: bf16 is the faster, lower-precision sampling mode (DESIGN.md)")
+    ap.add_argument("--sampler", choices=("reference", "dpmpp_1", "dpmpp_2m"), default="reference",
+                    help="reference: DDIM / DDPM as the reference samples; dpmpp_2m: DPM-Solver++(2M), second order, for few --steps (DESIGN.md 4.2)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("tools/demo.py needs a GPU: the sampling path is liblfdm_hip.so only")
@@ -47,7 +49,8 @@ def main():
 
     model = FlowDiffusion(is_train=False, img_size=args.size // 4, num_frames=args.frames, sampling_timesteps=args.steps,
                           null_cond_prob=0.1, config_pth=args.config, pretrained_pth=args.lfae_ckpt,
-                          bert_path=None if args.synthetic else args.bert, conv_precision=args.conv_precision)          # demo_mug.py:80-88
+                          bert_path=None if args.synthetic else args.bert, conv_precision=args.conv_precision,
+                          sampler=args.sampler)          # demo_mug.py:80-88
     if args.synthetic:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import synth
