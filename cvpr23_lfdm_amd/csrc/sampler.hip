@@ -7,6 +7,7 @@
 // LDS-privatised histograms merged by integer atomics (order independent -> deterministic).
 // All step-dependent scalars come from a device table indexed by a device counter so the captured
 // hipGraph of one step can be replayed for every step.
+#include <stdio.h>
 #include <stdlib.h>
 #include "lfdm_device.h"
 #include "../../include/lfdm_hip.h"
@@ -199,7 +200,91 @@ __global__ __launch_bounds__(256) void quantile_out_kernel(Ranks rk, const unsig
   if (threadIdx.x == 0) q_out[b] = q;
 }
 
+// Known-frame conditioning (replacement method; lfdm_sampler_step_known_f32): the operands of the update kernels' KNOWN variant.
+// The plain instantiations carry the empty form as their last argument, so everything in front of it sits where it sat.
+template <bool KNOWN>
+struct KnownOps {};
+template <>
+struct KnownOps<true> {
+  const float* known;          // (B, n)
+  const float* known_noise;    // (B, n)
+  const unsigned char* mask;   // (B, frames), non-zero = known
+  const float* level;          // (steps + 1, 2): row step + 1 = (a, s) after this step
+  unsigned frames, frame_elems;
+};
+
+// x[b, i] <- a * known + s * known_noise where the frame (i / frame_elems) % frames of sample b is known (x_T, once per video).  grid (nblk, B)
+__global__ __launch_bounds__(256) void known_blend_kernel(float* __restrict__ x, const float* __restrict__ known,
+                                                          const float* __restrict__ known_noise,
+                                                          const unsigned char* __restrict__ mask, float a, float s, unsigned n,
+                                                          unsigned frames, unsigned frame_elems) {
+  const int b = blockIdx.y;
+  const int64_t off = (int64_t)b * n;
+  const unsigned char* mb = mask + (int64_t)b * frames;
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u)
+    if (mb[(i / frame_elems) % frames]) x[off + i] = a * known[off + i] + s * known_noise[off + i];
+}
+
+// The KNOWN variant's registers: level pair, and mask byte / known / known_noise of the PRE prefetched elements.  Empty for the plain variant.
+template <bool KNOWN, int PRE>
+struct KnownPre {
+  __device__ __forceinline__ void head(const KnownOps<KNOWN>&, const int32_t*, int, int64_t) {}
+  __device__ __forceinline__ void load(const KnownOps<KNOWN>&, int, bool, int64_t) {}
+  __device__ __forceinline__ float pick(int, float v) const { return v; }
+  __device__ __forceinline__ float tail(const KnownOps<KNOWN>&, int64_t, float v) { return v; }
+};
+template <int PRE>
+struct KnownPre<true, PRE> {
+  float a, s, kn[PRE], kz[PRE];
+  unsigned mk[PRE];
+  int64_t off;
+  const unsigned char* mb;
+  // Frame of the thread's current element, kept incrementally: the thread walks i0, i0 + stride, ... (n < 2^24, 32-bit), so one division per
+  // thread and one of the (uniform) stride replace a division and a modulo per element - sixteen of them stood in front of the prefetch loads.
+  unsigned fr, rem, d_fr, d_rem;
+  __device__ __forceinline__ void head(const KnownOps<true>& kf, const int32_t* step_dev, int b, int64_t n) {
+    const float* lv = kf.level + 2 * ((int64_t)(*step_dev) + 1);
+    a = lv[0];
+    s = lv[1];
+    off = (int64_t)b * n;
+    mb = kf.mask + (int64_t)b * kf.frames;
+    const unsigned i0 = blockIdx.x * 256u + threadIdx.x, stride = gridDim.x * 256u;
+    fr = (i0 / kf.frame_elems) % kf.frames;
+    rem = i0 % kf.frame_elems;
+    d_fr = (stride / kf.frame_elems) % kf.frames;
+    d_rem = stride % kf.frame_elems;
+  }
+  __device__ __forceinline__ void next(const KnownOps<true>& kf) {     // fr + d_fr + 1 <= 2 * frames - 1: one subtraction is enough
+    rem += d_rem;
+    const bool carry = rem >= kf.frame_elems;
+    rem -= carry ? kf.frame_elems : 0u;
+    fr += d_fr + (carry ? 1u : 0u);
+    fr -= fr >= kf.frames ? kf.frames : 0u;
+  }
+  // called for k = 0 .. PRE - 1 in order, then tail() for every further element in order
+  __device__ __forceinline__ void load(const KnownOps<true>& kf, int k, bool in, int64_t i) {
+    const unsigned u = in ? (unsigned)i : 0u;
+    mk[k] = in ? mb[fr] : 0u;
+    kn[k] = in ? kf.known[off + u] : 0.f;
+    kz[k] = in ? kf.known_noise[off + u] : 0.f;
+    next(kf);
+  }
+  __device__ __forceinline__ float pick(int k, float v) const { return mk[k] ? a * kn[k] + s * kz[k] : v; }
+  __device__ __forceinline__ float tail(const KnownOps<true>& kf, int64_t i, float v) {
+    if (mb[fr]) v = a * kf.known[off + i] + s * kf.known_noise[off + i];
+    next(kf);
+    return v;
+  }
+};
+
+// KNOWN: the final store of x selects a * known + s * known_noise at the frames the byte mask marks; x0_out, the threshold, the housekeeping and
+// every other frame are the plain variant's.  What was chosen for the loads: the step counter and, behind it, the level pair are requested first
+// (that two-trip chain runs under the five histogram scans, like the operands); the mask byte, known and known_noise of the PRE prefetched
+// elements are loaded UNCONDITIONALLY in the same batch as today's prefetch (no round trip in front of the search; values at unmasked frames
+// are loaded but only ever pass through a select, so they may be NaN); the loop behind the prefetched elements branches on the mask byte.
+// The frame index of an element is carried along, not divided out (KnownPre).
 // grid (nblk, B)
+template <bool KNOWN>
 __global__ __launch_bounds__(256) void sampler_update_kernel(float* __restrict__ x,
                                                              const float* __restrict__ eps,
                                                              const float* __restrict__ noise,
@@ -208,7 +293,7 @@ __global__ __launch_bounds__(256) void sampler_update_kernel(float* __restrict__
                                                              const float* __restrict__ coef,
                                                              const int32_t* step_dev,      // (no __restrict__: advance_dev is the same word)
                                                              Ranks rk, unsigned* __restrict__ hists, int hist_samples,
-                                                             unsigned* __restrict__ ticket, int32_t* advance_dev) {
+                                                             unsigned* __restrict__ ticket, int32_t* advance_dev, KnownOps<KNOWN> kf) {
   __shared__ unsigned s_part[256], s_res[4];
   const int b = blockIdx.y;
   float* xb = x + (int64_t)b * n;
@@ -221,6 +306,8 @@ __global__ __launch_bounds__(256) void sampler_update_kernel(float* __restrict__
   constexpr int PRE = 8;
   const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
   float p_x0[PRE], p_e[PRE], p_x[PRE], p_n[PRE];
+  KnownPre<KNOWN, PRE> kp;
+  kp.head(kf, step_dev, b, n);
 #pragma unroll
   for (int k = 0; k < PRE; ++k) {
     const int64_t i = i0 + k * stride;
@@ -229,6 +316,7 @@ __global__ __launch_bounds__(256) void sampler_update_kernel(float* __restrict__
     p_e[k] = in ? eb[i] : 0.f;
     p_x[k] = in ? xb[i] : 0.f;
     p_n[k] = (in && nb) ? nb[i] : 0.f;
+    kp.load(kf, k, in, i);
   }
   float s = 1.0f;                       // rk.frac < 0: static clipping, x0.clamp(-1, 1) (use_dynamic_thres=False, :729-732)
   if (rk.frac >= 0.f) {
@@ -246,6 +334,7 @@ __global__ __launch_bounds__(256) void sampler_update_kernel(float* __restrict__
       float v = k_x0 * x0 + k_eps * p_e[k];
       if (k_x != 0.f) v += k_x * p_x[k];
       if (k_noise != 0.f && nb) v += k_noise * p_n[k];
+      v = kp.pick(k, v);
       xb[i] = v;
     }
   }
@@ -256,6 +345,7 @@ __global__ __launch_bounds__(256) void sampler_update_kernel(float* __restrict__
     float v = k_x0 * x0 + k_eps * eb[i];
     if (k_x != 0.f) v += k_x * xb[i];
     if (k_noise != 0.f && nb) v += k_noise * nb[i];
+    v = kp.tail(kf, i, v);
     xb[i] = v;
   }
   // End-of-step housekeeping by the workgroup that finishes last (every workgroup has read the histograms and the step counter before
@@ -280,7 +370,9 @@ __global__ __launch_bounds__(256) void sampler_update_kernel(float* __restrict__
 //   x <- k_x*x + k_m*m + k_prev*m_prev,   hist <- m       coef[step] = { c_x, c_eps, k_x, k_m, k_prev, - }
 // m_prev is the previous step's m, read from hist and replaced by this step's m by the same thread (one buffer suffices).  eps is not an
 // operand any more (pass 0 consumed it).  k_prev == 0 / k_x == 0 skip their operand: on a first-order step hist may be uninitialised
-// memory.  Prefetch and end-of-step housekeeping as in sampler_update_kernel.  grid (nblk, B)
+// memory.  Prefetch, end-of-step housekeeping and the KNOWN variant (only the store of x differs: hist and x0_out receive m at every frame)
+// as in sampler_update_kernel.  grid (nblk, B)
+template <bool KNOWN>
 __global__ __launch_bounds__(256) void sampler_update_ms_kernel(float* __restrict__ x,
                                                                 float* __restrict__ hist,
                                                                 const float* __restrict__ x0buf,
@@ -288,7 +380,7 @@ __global__ __launch_bounds__(256) void sampler_update_ms_kernel(float* __restric
                                                                 const float* __restrict__ coef,
                                                                 const int32_t* step_dev,      // (no __restrict__: advance_dev is the same word)
                                                                 Ranks rk, unsigned* __restrict__ hists, int hist_samples,
-                                                                unsigned* __restrict__ ticket, int32_t* advance_dev) {
+                                                                unsigned* __restrict__ ticket, int32_t* advance_dev, KnownOps<KNOWN> kf) {
   __shared__ unsigned s_part[256], s_res[4];
   const int b = blockIdx.y;
   float* xb = x + (int64_t)b * n;
@@ -298,6 +390,8 @@ __global__ __launch_bounds__(256) void sampler_update_ms_kernel(float* __restric
   constexpr int PRE = 8;               // requested before the five histogram scans, like sampler_update_kernel's
   const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
   float p_x0[PRE], p_x[PRE], p_m[PRE];
+  KnownPre<KNOWN, PRE> kp;
+  kp.head(kf, step_dev, b, n);
 #pragma unroll
   for (int k = 0; k < PRE; ++k) {
     const int64_t i = i0 + k * stride;
@@ -305,6 +399,7 @@ __global__ __launch_bounds__(256) void sampler_update_ms_kernel(float* __restric
     p_x0[k] = in ? x0b[i] : 0.f;
     p_x[k] = in ? xb[i] : 0.f;
     p_m[k] = in ? hb[i] : 0.f;         // (possibly uninitialised memory: only used when k_prev != 0)
+    kp.load(kf, k, in, i);
   }
   float s = 1.0f;                       // rk.frac < 0: static clamp to [-1, 1]
   if (rk.frac >= 0.f) {
@@ -322,6 +417,7 @@ __global__ __launch_bounds__(256) void sampler_update_ms_kernel(float* __restric
       float v = k_m * m;
       if (k_prev != 0.f) v += k_prev * p_m[k];
       if (k_x != 0.f) v += k_x * p_x[k];
+      v = kp.pick(k, v);
       hb[i] = m;
       xb[i] = v;
     }
@@ -332,6 +428,7 @@ __global__ __launch_bounds__(256) void sampler_update_ms_kernel(float* __restric
     float v = k_m * m;
     if (k_prev != 0.f) v += k_prev * hb[i];
     if (k_x != 0.f) v += k_x * xb[i];
+    v = kp.tail(kf, i, v);
     hb[i] = m;
     xb[i] = v;
   }
@@ -462,24 +559,54 @@ extern "C" int lfdm_abs_quantile_f32(const float* x, int batch, int64_t n, float
   return lfdm_check_launch("abs_quantile");
 }
 
-extern "C" int lfdm_sampler_step_f32(float* x, const float* eps, const float* noise, float* x0_out,
-                                     int batch, int64_t n, const float* coef, int32_t* step_dev,
-                                     float quantile, int advance, void* ws, size_t ws_bytes,
-                                     lfdm_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (!x || !eps || !coef || !step_dev || batch <= 0 || n <= 0 || n >= (1 << 24)) {
-    lfdm_set_error("sampler_step: bad arguments (n < 2^24)");
+namespace {
+
+// argument check of the known-frame operands; on success fills kf
+int make_known(const char* what, const float* known, const float* known_noise, const unsigned char* frame_mask, const float* level,
+               int64_t n, int frames, int64_t frame_elems, KnownOps<true>* kf) {
+  char msg[160];
+  if (!known || !known_noise || !frame_mask || !level) {
+    snprintf(msg, sizeof msg, "%s: known, known_noise, frame_mask and level must all be given", what);
+    lfdm_set_error(msg);
+    return LFDM_EINVAL;
+  }
+  if (frames <= 0 || frame_elems <= 0 || n <= 0 || n >= (1 << 24) || n % ((int64_t)frames * frame_elems) != 0) {
+    snprintf(msg, sizeof msg, "%s: n = %lld must be a multiple of frames * frame_elems = %d * %lld (n < 2^24)", what, (long long)n, frames,
+             (long long)frame_elems);
+    lfdm_set_error(msg);
+    return LFDM_EINVAL;
+  }
+  kf->known = known;
+  kf->known_noise = known_noise;
+  kf->mask = frame_mask;
+  kf->level = level;
+  kf->frames = (unsigned)frames;
+  kf->frame_elems = (unsigned)frame_elems;
+  return 0;
+}
+
+// The one launch sequence of every sampler step: [histogram clear for batch > 2] pass 0, two select passes, update.  MS: the multistep update
+// (second = hist) instead of the DDIM / DDPM one (second = noise); KNOWN: the update kernel's known-frame instantiation.
+template <bool MS, bool KNOWN>
+int run_step(const char* what, float* x, const float* eps, float* second, float* x0_out, int batch, int64_t n, const float* coef,
+             int32_t* step_dev, float quantile, int advance, void* ws, size_t ws_bytes, KnownOps<KNOWN> kf, hipStream_t stream) {
+  char msg[160];
+  if (!x || !eps || (MS && !second) || !coef || !step_dev || batch <= 0 || n <= 0 || n >= (1 << 24)) {
+    snprintf(msg, sizeof msg, "%s: bad arguments (n < 2^24)", what);
+    lfdm_set_error(msg);
     return LFDM_EINVAL;
   }
   if (!ws || ws_bytes < lfdm_sampler_ws_bytes(batch, n)) {
-    lfdm_set_error("sampler_step: workspace too small");
+    snprintf(msg, sizeof msg, "%s: workspace too small", what);
+    lfdm_set_error(msg);
     return LFDM_EWORKSPACE;
   }
   unsigned* hists = reinterpret_cast<unsigned*>(ws);
   float* x0buf = reinterpret_cast<float*>(hists + (size_t)batch * HIST_PER_SAMPLE);
   const bool dynamic = quantile >= 0.f;           // quantile < 0: static clipping to [-1, 1] (GaussianDiffusion's own default)
   if (dynamic && quantile > 1.f) {
-    lfdm_set_error("sampler_step: quantile must lie in [0, 1] (or be negative for the static clamp to [-1, 1])");
+    snprintf(msg, sizeof msg, "%s: quantile must lie in [0, 1] (or be negative for the static clamp to [-1, 1])", what);
+    lfdm_set_error(msg);
     return LFDM_EINVAL;
   }
   Ranks rk = make_ranks(n, dynamic ? quantile : 0.f);
@@ -494,45 +621,66 @@ extern "C" int lfdm_sampler_step_f32(float* x, const float* eps, const float* no
   unsigned* ticket = reinterpret_cast<unsigned*>(x0buf + (size_t)batch * n);
   const dim3 grid(blocks_for(n), batch), block(256);
   LFDM_LAUNCH(quantile_pass0_kernel, grid, block, 0, stream, (const float*)x, eps, x0buf, n, coef,
-              (const int32_t*)step_dev, hists);         // (also the x0 = c_x*x - c_eps*eps pass)
+              (const int32_t*)step_dev, hists);         // (also the x0 = c_x*x - c_eps*eps pass: columns 0-1 of either table)
   if (dynamic) run_select(x0buf, batch, n, rk, hists, stream);
-  LFDM_LAUNCH(sampler_update_kernel, grid, block, 0, stream, x, eps, noise, x0buf, x0_out, n, coef,
-              (const int32_t*)step_dev, rk, hists, fold_clear ? batch : 0, ticket, advance ? step_dev : (int32_t*)nullptr);
-  return lfdm_check_launch("sampler_step");
+  if (MS)
+    LFDM_LAUNCH((sampler_update_ms_kernel<KNOWN>), grid, block, 0, stream, x, second, (const float*)x0buf, x0_out, n, coef,
+                (const int32_t*)step_dev, rk, hists, fold_clear ? batch : 0, ticket, advance ? step_dev : (int32_t*)nullptr, kf);
+  else
+    LFDM_LAUNCH((sampler_update_kernel<KNOWN>), grid, block, 0, stream, x, eps, (const float*)second, x0buf, x0_out, n, coef,
+                (const int32_t*)step_dev, rk, hists, fold_clear ? batch : 0, ticket, advance ? step_dev : (int32_t*)nullptr, kf);
+  return lfdm_check_launch(what);
+}
+
+}  // namespace
+
+extern "C" int lfdm_sampler_step_f32(float* x, const float* eps, const float* noise, float* x0_out,
+                                     int batch, int64_t n, const float* coef, int32_t* step_dev,
+                                     float quantile, int advance, void* ws, size_t ws_bytes,
+                                     lfdm_stream_t stream_) {
+  return run_step<false, false>("sampler_step", x, eps, const_cast<float*>(noise), x0_out, batch, n, coef, step_dev, quantile, advance, ws,
+                                ws_bytes, KnownOps<false>{}, (hipStream_t)stream_);
 }
 
 extern "C" int lfdm_sampler_step_ms_f32(float* x, const float* eps, float* hist, float* x0_out, int batch, int64_t n,
                                         const float* coef, int32_t* step_dev, float quantile, int advance, void* ws,
                                         size_t ws_bytes, lfdm_stream_t stream_) {
+  return run_step<true, false>("sampler_step_ms", x, eps, hist, x0_out, batch, n, coef, step_dev, quantile, advance, ws, ws_bytes,
+                               KnownOps<false>{}, (hipStream_t)stream_);
+}
+
+extern "C" int lfdm_sampler_step_known_f32(float* x, const float* eps, const float* noise, float* x0_out, int batch, int64_t n,
+                                           const float* coef, int32_t* step_dev, float quantile, int advance, void* ws,
+                                           size_t ws_bytes, const float* known, const float* known_noise,
+                                           const unsigned char* frame_mask, const float* level, int frames, int64_t frame_elems,
+                                           lfdm_stream_t stream_) {
+  KnownOps<true> kf;
+  if (int rc = make_known("sampler_step_known", known, known_noise, frame_mask, level, n, frames, frame_elems, &kf)) return rc;
+  return run_step<false, true>("sampler_step_known", x, eps, const_cast<float*>(noise), x0_out, batch, n, coef, step_dev, quantile,
+                               advance, ws, ws_bytes, kf, (hipStream_t)stream_);
+}
+
+extern "C" int lfdm_sampler_step_ms_known_f32(float* x, const float* eps, float* hist, float* x0_out, int batch, int64_t n,
+                                              const float* coef, int32_t* step_dev, float quantile, int advance, void* ws,
+                                              size_t ws_bytes, const float* known, const float* known_noise,
+                                              const unsigned char* frame_mask, const float* level, int frames, int64_t frame_elems,
+                                              lfdm_stream_t stream_) {
+  KnownOps<true> kf;
+  if (int rc = make_known("sampler_step_ms_known", known, known_noise, frame_mask, level, n, frames, frame_elems, &kf)) return rc;
+  return run_step<true, true>("sampler_step_ms_known", x, eps, hist, x0_out, batch, n, coef, step_dev, quantile, advance, ws, ws_bytes, kf,
+                              (hipStream_t)stream_);
+}
+
+extern "C" int lfdm_known_blend_f32(float* x, const float* known, const float* known_noise, const unsigned char* frame_mask, float a,
+                                    float s, int batch, int64_t n, int frames, int64_t frame_elems, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!x || !eps || !hist || !coef || !step_dev || batch <= 0 || n <= 0 || n >= (1 << 24)) {
-    lfdm_set_error("sampler_step_ms: bad arguments (n < 2^24)");
+  KnownOps<true> kf;
+  if (!x || batch <= 0) {
+    lfdm_set_error("known_blend: bad arguments");
     return LFDM_EINVAL;
   }
-  if (!ws || ws_bytes < lfdm_sampler_ws_bytes(batch, n)) {
-    lfdm_set_error("sampler_step_ms: workspace too small");
-    return LFDM_EWORKSPACE;
-  }
-  unsigned* hists = reinterpret_cast<unsigned*>(ws);
-  float* x0buf = reinterpret_cast<float*>(hists + (size_t)batch * HIST_PER_SAMPLE);
-  const bool dynamic = quantile >= 0.f;
-  if (dynamic && quantile > 1.f) {
-    lfdm_set_error("sampler_step_ms: quantile must lie in [0, 1] (or be negative for the static clamp to [-1, 1])");
-    return LFDM_EINVAL;
-  }
-  Ranks rk = make_ranks(n, dynamic ? quantile : 0.f);
-  if (!dynamic) rk.frac = -1.f;
-  const bool fold_clear = batch <= 2;             // as lfdm_sampler_step_f32: larger batches keep the clearing launch
-  if (!fold_clear) {
-    const int64_t nz = (int64_t)batch * HIST_PER_SAMPLE;
-    LFDM_LAUNCH(zero_u32_kernel, dim3((unsigned)((nz + 255) / 256 > 64 ? 64 : (nz + 255) / 256)), dim3(256), 0, stream, hists, nz);
-  }
-  unsigned* ticket = reinterpret_cast<unsigned*>(x0buf + (size_t)batch * n);
-  const dim3 grid(blocks_for(n), batch), block(256);
-  LFDM_LAUNCH(quantile_pass0_kernel, grid, block, 0, stream, (const float*)x, eps, x0buf, n, coef,
-              (const int32_t*)step_dev, hists);         // x0 = c_x*x - c_eps*eps: columns 0-1, the same table stride
-  if (dynamic) run_select(x0buf, batch, n, rk, hists, stream);
-  LFDM_LAUNCH(sampler_update_ms_kernel, grid, block, 0, stream, x, hist, (const float*)x0buf, x0_out, n, coef,
-              (const int32_t*)step_dev, rk, hists, fold_clear ? batch : 0, ticket, advance ? step_dev : (int32_t*)nullptr);
-  return lfdm_check_launch("sampler_step_ms");
+  if (int rc = make_known("known_blend", known, known_noise, frame_mask, /*level: not an operand*/ known, n, frames, frame_elems, &kf)) return rc;
+  LFDM_LAUNCH(known_blend_kernel, dim3(blocks_for(n), batch), dim3(256), 0, stream, x, known, known_noise, frame_mask, a, s, (unsigned)n,
+              kf.frames, kf.frame_elems);
+  return lfdm_check_launch("known_blend");
 }

@@ -247,28 +247,83 @@ class GaussianDiffusion(nn.Module):
             self.__dict__["_ms_tables_cache"] = hit
         return hit[1], hit[2], hit[3], hit[4]
 
+    def _level_table(self, ddim, sampler="reference"):
+        """Known-frame conditioning: the (steps + 1, 2) fp32 host table of the level (a, s) the latent sits on - row 0: x_T's node,
+        row i + 1: after step i - so that a known frame is stored as a * known + s * known_noise.  Reference DDIM: alphas_cumprod_prev[time_next]
+        (column 0 = column 2 of `_step_tables(True)`'s rows, bit for bit), init alphas_cumprod_prev[time] of the first step; reference DDPM:
+        alphas_cumprod_prev[t] of step t, init alphas_cumprod[num_timesteps - 1] - both in the reference's fp32 tensor arithmetic; "dpmpp_*":
+        (alpha_n, sigma_n) of `_ms_step_tables` in double, rounded once, init (alpha_s, sigma_s) of the first step.  The last row is (1, 0)."""
+        if sampler != "reference":
+            pairs = self.ddim_times()
+            self._ms_step_tables(sampler)           # (its checks of the grid)
+            acp = self.alphas_cumprod.detach().double().cpu()
+            a = [float(acp[pairs[0][0]])] + [1.0 if i == len(pairs) - 1 else float(acp[tn]) for i, (_, tn) in enumerate(pairs)]
+            return torch.tensor([[math.sqrt(v), math.sqrt(1.0 - v)] for v in a], dtype=torch.float64).float().contiguous()
+        b = {k: v.detach().float().cpu() for k, v in self.named_buffers(recurse=False)}
+        if ddim:
+            pairs = self.ddim_times()
+            a = [b['alphas_cumprod_prev'][pairs[0][0]]] + [b['alphas_cumprod_prev'][tn] for _, tn in pairs]
+        else:
+            a = [b['alphas_cumprod'][self.num_timesteps - 1]] + [b['alphas_cumprod_prev'][t] for t in reversed(range(self.num_timesteps))]
+        return torch.stack([torch.stack([v.sqrt(), (1 - v).sqrt()]) for v in a]).float().contiguous()
+
+    def _level_table_on(self, ddim, sampler, dev):
+        """(host table, table on `dev`) of `_level_table`, kept per (sampler, schedule) like `_step_tables_on`."""
+        key = (bool(ddim), sampler, self.sampling_timesteps, self.num_timesteps, str(dev),
+               tuple((k, v._version, v.data_ptr()) for k, v in self.named_buffers(recurse=False)))
+        hit = self.__dict__.get("_level_cache")
+        if hit is None or hit[0] != key:
+            host = self._level_table(ddim, sampler)
+            hit = (key, host, host.to(dev))
+            self.__dict__["_level_cache"] = hit
+        return hit[1], hit[2]
+
+    def _check_known(self, shape, known, known_mask):
+        """Both or none; known (B, C, T, S, S) float32, known_mask (B, T) bool.  ValueError before anything is launched."""
+        if known is None and known_mask is None:
+            return False
+        if known is None or known_mask is None:
+            raise ValueError("sample: known and known_mask go together (both or none)")
+        if not isinstance(known, torch.Tensor) or known.dtype != torch.float32 or tuple(known.shape) != tuple(shape):
+            raise ValueError("sample: known must be a float32 tensor of shape %s, got %s %s"
+                             % (tuple(shape), getattr(known, "dtype", type(known)), tuple(getattr(known, "shape", ()))))
+        if not isinstance(known_mask, torch.Tensor) or known_mask.dtype != torch.bool or tuple(known_mask.shape) != (shape[0], shape[2]):
+            raise ValueError("sample: known_mask must be a bool tensor of shape %s, got %s %s"
+                             % ((shape[0], shape[2]), getattr(known_mask, "dtype", type(known_mask)), tuple(getattr(known_mask, "shape", ()))))
+        return True
+
     # ------------------------------------------------------------------ sampling
     @torch.no_grad()
-    def sample(self, fea, cond=None, cond_scale=1., batch_size=16):
-        """Reference :762-775.  fea: planar (B, 256, S, S); cond: (B, 768) tensor or list[str].  Runs `self.sampler`."""
+    def sample(self, fea, cond=None, cond_scale=1., batch_size=16, *, known=None, known_mask=None):
+        """Reference :762-775.  fea: planar (B, 256, S, S); cond: (B, 768) tensor or list[str].  Runs `self.sampler`.
+        known (B, C, T, S, S) float32 + known_mask (B, T) bool (keyword only, both or none): condition on known frames by the replacement
+        method - frame t of sample b is kept on the trajectory of known[b, :, t] and returned bit for bit where the mask is
+        set; values of `known` at other frames are never read into the result."""
         device = next(self.denoise_fn.parameters()).device
+        if cond is not None and not is_list_str(cond):
+            batch = cond.shape[0]
+        elif cond is not None:
+            batch = len(cond)
+        else:
+            batch = batch_size
+        shape = (batch, self.channels, self.num_frames, self.image_size, self.image_size)
+        self._check_known(shape, known, known_mask)
         if cond is not None:
             cond = self._embed(cond, device)
-        batch = cond.shape[0] if cond is not None else batch_size
-        shape = (batch, self.channels, self.num_frames, self.image_size, self.image_size)
         if self.sampler != "reference":
-            return self._sample(fea, shape, cond, cond_scale, True, sampler=self.sampler)
-        return self._sample(fea, shape, cond, cond_scale, self.is_ddim_sampling)
+            return self._sample(fea, shape, cond, cond_scale, True, sampler=self.sampler, known=known, known_mask=known_mask)
+        return self._sample(fea, shape, cond, cond_scale, self.is_ddim_sampling, known=known, known_mask=known_mask)
 
     @torch.no_grad()
-    def p_sample_loop(self, fea, shape, cond=None, cond_scale=1.):
-        return self._sample(fea, shape, cond, cond_scale, False)
+    def p_sample_loop(self, fea, shape, cond=None, cond_scale=1., *, known=None, known_mask=None):
+        return self._sample(fea, shape, cond, cond_scale, False, known=known, known_mask=known_mask)
 
     @torch.no_grad()
-    def ddim_sample(self, fea, shape, cond=None, cond_scale=1., clip_denoised=True):
-        return self._sample(fea, shape, cond, cond_scale, True)
+    def ddim_sample(self, fea, shape, cond=None, cond_scale=1., clip_denoised=True, *, known=None, known_mask=None):
+        return self._sample(fea, shape, cond, cond_scale, True, known=known, known_mask=known_mask)
 
-    def _sample(self, fea, shape, cond, cond_scale, ddim, sampler="reference"):
+    def _sample(self, fea, shape, cond, cond_scale, ddim, sampler="reference", known=None, known_mask=None):
+        conditioned = self._check_known(shape, known, known_mask)
         unet = self.denoise_fn
         pk = unet.packed()
         dev = next(unet.parameters()).device
@@ -306,6 +361,10 @@ class GaussianDiffusion(nn.Module):
         # (the convolution precision explicitly: both modes share one pack - id(pk) does not tell a graph captured in the other mode apart)
         # (... and the sampler: a graph captured for one update rule must never be replayed for another)
         key = (batch, frames, s, len(variants), float(cond_scale), bool(ddim), steps, id(pk), unet.conv_precision, sampler)
+        if conditioned:
+            # known frames: a plan (and graph) of its own, whose update kernel is the conditioned instantiation; the unconditioned key is unchanged
+            key = key + ("known",)
+            level_host, level_dev = self._level_table_on(ddim, sampler, dev)
         plan = self._plans.get(key)
         if plan is None:
             plan = {
@@ -320,7 +379,15 @@ class GaussianDiffusion(nn.Module):
                 # m_{i-1} of the multistep samplers; never cleared: the first step of a video is first order and does not read it
                 "hist": torch.empty(shape, device=dev) if multistep else None,
             }
-            self._plans = {key: plan}      # keep one plan (static buffers are large)
+            if conditioned:
+                # static operands of the conditioned update kernel, filled in place by every call (another mask / other frames: no new capture)
+                plan.update({"known": torch.empty(shape, device=dev), "known_noise": torch.empty(shape, device=dev),
+                             "kmask": torch.zeros((batch, frames), dtype=torch.bool, device=dev),
+                             "level": torch.empty((steps + 1, 2), device=dev)})
+            # keep one plan (static buffers are large) - and the one of the other kind next to it: a long video alternates a plain first
+            # chunk with conditioned ones and must not capture again for each
+            self._plans = {k: v for k, v in self._plans.items() if (k[-1] == "known") != conditioned}
+            self._plans[key] = plan
         if plan["graph"] is not None and plan.get("buf_gen") != unet._buf_gen:
             # an eager call in between (Unet3D.forward, p_losses in eval mode, a larger batch) re-allocated scratch
             # arenas whose raw pointers the captured graph holds: capture again on the current arenas
@@ -347,13 +414,23 @@ class GaussianDiffusion(nn.Module):
                 unet.run_trunk(pk, r, ss2, 2 * batch, frames, s, eps2)
                 ops.cfg_combine(eps2[:batch], eps2[batch:], b["scale"], eps)      # null + (cond - null) * scale
             quantile = self.dynamic_thres_percentile if self.use_dynamic_thres else -1.0
+            kf = {}
+            if conditioned:
+                kf = dict(known=plan["known"], known_noise=plan["known_noise"], frame_mask=plan["kmask"], level=plan["level"], frames=frames)
             if multistep:
-                ops.sampler_step_ms(x, eps, plan["hist"], b["coef"], step_dev, quantile=quantile, ws=plan["ws"])
+                ops.sampler_step_ms(x, eps, plan["hist"], b["coef"], step_dev, quantile=quantile, ws=plan["ws"], **kf)
             else:
-                ops.sampler_step(x, eps, noise, b["coef"], step_dev, quantile=quantile, ws=plan["ws"])
+                ops.sampler_step(x, eps, noise, b["coef"], step_dev, quantile=quantile, ws=plan["ws"], **kf)
 
         use_graph = (_native.library().kind == "hip" and os.environ.get("LFDM_NO_GRAPH", "0") != "1")
         self._draw(x)                                   # x_T  (:753 / :788)
+        if conditioned:
+            # one more draw directly behind x_T's (every step draw keeps its place in the order), then x_T's known frames on the init level
+            plan["known"].copy_(known)
+            plan["kmask"].copy_(known_mask)
+            plan["level"].copy_(level_dev)
+            self._draw(plan["known_noise"])
+            ops.known_blend(x, plan["known"], plan["known_noise"], plan["kmask"], float(level_host[0, 0]), float(level_host[0, 1]), frames)
         step_dev.zero_()
         if use_graph and plan["graph"] is None:
             # dry run allocates every scratch buffer outside the capture, then state is restored

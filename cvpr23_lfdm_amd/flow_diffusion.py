@@ -111,7 +111,7 @@ class FlowDiffusion(nn.Module):
             self.diffusion.text_encoder = BertTextEncoder(bert_path, use_cls=self.diffusion.text_use_bert_cls)
         for attr in ('ref_img', 'ref_img_fea', 'real_vid', 'real_out_vid', 'real_warped_vid', 'real_vid_grid',
                      'real_vid_conf', 'fake_out_vid', 'fake_warped_vid', 'fake_vid_grid', 'fake_vid_conf',
-                     'sample_out_vid', 'sample_warped_vid', 'sample_vid_grid', 'sample_vid_conf'):
+                     'sample_out_vid', 'sample_warped_vid', 'sample_vid_grid', 'sample_vid_conf', 'sample_latent'):
             setattr(self, attr, None)
         self.is_train = is_train
         if self.is_train:
@@ -136,31 +136,94 @@ class FlowDiffusion(nn.Module):
             torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count())
 
     # ------------------------------------------------------------------ sampling (a28)
-    def sample_one_video(self, cond_scale):
+    def sample_one_video(self, cond_scale, *, known_latent=None, known_mask=None):
         """Reference :190-216.  Results land in sample_vid_grid (B,2,T,S,S), sample_vid_conf (B,1,T,S,S),
-        sample_out_vid / sample_warped_vid (B,3,T,H,W)."""
+        sample_out_vid / sample_warped_vid (B,3,T,H,W), and the latent the diffusion returned (B,3,T,S,S; the residual flow when
+        use_residual_flow) in sample_latent.  known_latent (B,3,T,S,S) in that same space + known_mask (B,T) bool (keyword only, both or
+        none): GaussianDiffusion.sample's known frames."""
         gen = self.generator
         with torch.no_grad():
             img = self.sample_img.float().contiguous()
+            dm = self.diffusion                                       # (bad known frames are refused before anything is launched)
+            dm._check_known((img.shape[0], dm.channels, dm.num_frames, dm.image_size, dm.image_size), known_latent, known_mask)
             skips = gen.encode(img)                                   # encoder ONCE per video
             b, _, h, w = img.shape
             d = 2 ** gen.num_down_blocks
-            fea_cl = skips[-1]
             fea = gen.compute_fea_from_skips(skips, b, h // d, w // d)
             self.sample_img_fea = fea
-            pred = self.diffusion.sample(fea, cond=self.sample_text, batch_size=1, cond_scale=cond_scale)
-            nf, s = pred.shape[2], pred.shape[3]
-            if self.use_residual_flow:
-                grid = pred[:, :2] + self.get_grid(b, nf, s, s, normalize=True).to(pred.device)
-                maps = torch.cat((grid, pred[:, 2:3]), dim=1).contiguous()
-            else:
-                maps = pred
-            self.sample_vid_grid = maps[:, :2]
-            self.sample_vid_conf = (pred[:, 2, :, :, :].unsqueeze(dim=1) + 1) * 0.5
-            out, warped = gen.decode_video(img, skips, maps[:, 0], maps[:, 1], maps[:, 2], nf, s, s,
-                                           3 * nf * s * s, s * s, occ_scale=0.5, occ_bias=0.5)
-            self.sample_out_vid = out
-            self.sample_warped_vid = warped
+            pred = self.diffusion.sample(fea, cond=self.sample_text, batch_size=1, cond_scale=cond_scale, known=known_latent,
+                                         known_mask=known_mask)
+            self.sample_latent = pred
+            self._decode_sample(img, skips, pred)
+
+    def _maps(self, pred):
+        """(sampling grid + occlusion channel (B,3,T,S,S), confidence (B,1,T,S,S)) of a latent (:203-210)."""
+        b, nf, s = pred.shape[0], pred.shape[2], pred.shape[3]
+        if self.use_residual_flow:
+            grid = pred[:, :2] + self.get_grid(b, nf, s, s, normalize=True).to(pred.device)
+            maps = torch.cat((grid, pred[:, 2:3]), dim=1).contiguous()
+        else:
+            maps = pred
+        return maps, (pred[:, 2, :, :, :].unsqueeze(dim=1) + 1) * 0.5
+
+    def _decode_sample(self, img, skips, pred):
+        maps, conf = self._maps(pred)
+        nf, s = pred.shape[2], pred.shape[3]
+        self.sample_vid_grid = maps[:, :2]
+        self.sample_vid_conf = conf
+        out, warped = self.generator.decode_video(img, skips, maps[:, 0], maps[:, 1], maps[:, 2], nf, s, s,
+                                                  3 * nf * s * s, s * s, occ_scale=0.5, occ_bias=0.5)
+        self.sample_out_vid = out
+        self.sample_warped_vid = warped
+
+    def sample_long_video(self, cond_scale, total_frames, overlap=8):
+        """A video of `total_frames` frames, longer than the model's window of num_frames, as a chain of windows: the LFAE
+        encoder runs ONCE; chunk 0 is a plain sample; chunk j > 0 is conditioned on the last `overlap` latent frames of chunk j - 1 placed at
+        its frames 0 .. overlap-1 (same source image, features and text condition - only the latent is chained); the result keeps chunk 0 whole
+        and frames overlap.. of every later chunk, cut to total_frames, and is decoded in pieces of at most num_frames frames.  Results as
+        sample_one_video's, with T = total_frames."""
+        nf = self.diffusion.num_frames
+        total_frames, overlap = int(total_frames), int(overlap)
+        if overlap < 1 or overlap >= nf:
+            raise ValueError("sample_long_video: overlap must lie in [1, num_frames - 1 = %d], got %d" % (nf - 1, overlap))
+        if total_frames < 1:
+            raise ValueError("sample_long_video: total_frames must be at least 1, got %d" % total_frames)
+        gen = self.generator
+        with torch.no_grad():
+            img = self.sample_img.float().contiguous()
+            skips = gen.encode(img)                                   # encoder ONCE per long video
+            b, _, h, w = img.shape
+            d = 2 ** gen.num_down_blocks
+            fea = gen.compute_fea_from_skips(skips, b, h // d, w // d)
+            self.sample_img_fea = fea
+            chunk = self.diffusion.sample(fea, cond=self.sample_text, batch_size=1, cond_scale=cond_scale)
+            pieces, have = [chunk], nf
+            mask = torch.zeros((b, nf), dtype=torch.bool, device=chunk.device)
+            mask[:, :overlap] = True
+            while have < total_frames:
+                known = torch.zeros_like(chunk)
+                known[:, :, :overlap] = chunk[:, :, nf - overlap:]
+                chunk = self.diffusion.sample(fea, cond=self.sample_text, batch_size=1, cond_scale=cond_scale, known=known, known_mask=mask)
+                pieces.append(chunk[:, :, overlap:])
+                have += nf - overlap
+            latent = torch.cat(pieces, dim=2)[:, :, :total_frames].contiguous()
+            self.sample_latent = latent
+            s = latent.shape[3]
+            grids, confs, outs, warps = [], [], [], []
+            for f0 in range(0, total_frames, nf):                     # decode in pieces of at most num_frames frames
+                part = latent[:, :, f0:f0 + nf].contiguous()
+                maps, conf = self._maps(part)
+                n_part = part.shape[2]
+                out, warped = gen.decode_video(img, skips, maps[:, 0], maps[:, 1], maps[:, 2], n_part, s, s,
+                                               3 * n_part * s * s, s * s, occ_scale=0.5, occ_bias=0.5)
+                grids.append(maps[:, :2])
+                confs.append(conf)
+                outs.append(out)
+                warps.append(warped)
+            self.sample_vid_grid = torch.cat(grids, dim=2)
+            self.sample_vid_conf = torch.cat(confs, dim=2)
+            self.sample_out_vid = torch.cat(outs, dim=2)
+            self.sample_warped_vid = torch.cat(warps, dim=2)
 
     def set_sample_input(self, sample_img, sample_text):
         dev = next(self.unet.parameters()).device
@@ -388,7 +451,7 @@ class FlowDiffusionFunctional(FlowDiffusion):
         out.pop("ref_img_fea", None)
         return out
 
-    def sample_one_video(self, sample_img, sample_text, cond_scale):
+    def sample_one_video(self, sample_img, sample_text, cond_scale, *, known_latent=None, known_mask=None):
         self.set_sample_input(sample_img=sample_img, sample_text=sample_text)
-        FlowDiffusion.sample_one_video(self, cond_scale)
-        return {k: getattr(self, k) for k in ("sample_vid_grid", "sample_vid_conf", "sample_out_vid", "sample_warped_vid")}
+        FlowDiffusion.sample_one_video(self, cond_scale, known_latent=known_latent, known_mask=known_mask)
+        return {k: getattr(self, k) for k in ("sample_vid_grid", "sample_vid_conf", "sample_out_vid", "sample_warped_vid", "sample_latent")}

@@ -863,33 +863,102 @@ def sampler_ws(batch, n, device):
     return ws
 
 
-def sampler_step(x, eps, noise, coef, step_dev, *, quantile=0.9, advance=True, x0_out=None, ws=None):
+def _known_operands(what, x, known, known_noise, frame_mask, level, frames, need_level=True):
+    """The known-frame operands of sampler_step / sampler_step_ms / known_blend: all of them or none.  -> None, or (frames, frame_elems) after
+    the shape / dtype checks (frame_mask: (B, frames) bool or uint8, used as bytes)."""
+    given = [known is not None, known_noise is not None, frame_mask is not None, frames is not None]
+    if need_level:
+        given.append(level is not None)
+    if not any(given):
+        return None
+    if not all(given):
+        raise ValueError("%s: known, known_noise, frame_mask, %sframes go together (all of them or none)" % (what, "level, " if need_level else ""))
+    batch = x.shape[0]
+    n = x.numel() // batch
+    frames = int(frames)
+    if frames < 1 or n % frames != 0:
+        raise ValueError("%s: frames = %d does not divide the sample's %d elements" % (what, frames, n))
+    if x.dim() >= 4:                                     # planar (B, C, T, ...): a frame is everything behind T
+        if x.shape[2] != frames:
+            raise ValueError("%s: x has %d frames, frames = %d" % (what, x.shape[2], frames))
+        frame_elems = x[0, 0, 0].numel()
+    elif x.dim() == 3:                                   # (B, C * T, hw)
+        frame_elems = x.shape[2]
+    else:
+        raise ValueError("%s: x must be (B, C, T, ...) or (B, C * T, hw) for known frames" % what)
+    if n % (frames * frame_elems) != 0:
+        raise ValueError("%s: %d elements per sample are no multiple of %d frames x %d" % (what, n, frames, frame_elems))
+    for name, t in (("known", known), ("known_noise", known_noise)):
+        if t.dtype != torch.float32 or t.numel() != x.numel() or not t.is_contiguous() or t.device != x.device:
+            raise ValueError("%s: %s must be a contiguous float32 tensor of x's %d elements on x's device" % (what, name, x.numel()))
+    if frame_mask.dtype not in (torch.bool, torch.uint8) or tuple(frame_mask.shape) != (batch, frames) or not frame_mask.is_contiguous() \
+            or frame_mask.device != x.device:
+        raise ValueError("%s: frame_mask must be a contiguous (%d, %d) bool / uint8 tensor on x's device" % (what, batch, frames))
+    if need_level and (level.dtype != torch.float32 or level.dim() != 2 or level.shape[1] != 2 or not level.is_contiguous()
+                       or level.device != x.device):
+        raise ValueError("%s: level must be a contiguous (steps + 1, 2) float32 tensor on x's device" % what)
+    return frames, frame_elems
+
+
+def sampler_step(x, eps, noise, coef, step_dev, *, quantile=0.9, advance=True, x0_out=None, ws=None,
+                 known=None, known_noise=None, frame_mask=None, level=None, frames=None):
+    """lfdm_sampler_step_f32; with the five known-frame keywords (all or none) lfdm_sampler_step_known_f32: frames whose frame_mask[b, t] is set
+    are stored as level[step + 1] = (a, s) applied to (known, known_noise) instead of the update's result."""
     lib = _lib()
     _chk(lib, x, eps, noise, coef, step_dev, x0_out, ws)
+    kf = _known_operands("sampler_step", x, known, known_noise, frame_mask, level, frames)
     batch = x.shape[0]
     n = x.numel() // batch
     if ws is None:
         ws = sampler_ws(batch, n, x.device)
-    lib.check(lib.lfdm_sampler_step_f32(_p(x), _p(eps), _p(noise), _p(x0_out), batch, n, _p(coef),
-                                        _p(step_dev), quantile, int(advance), _p(ws), ws.numel() * 4,
-                                        _stream(lib)), "lfdm_sampler_step_f32")
+    if kf is None:
+        lib.check(lib.lfdm_sampler_step_f32(_p(x), _p(eps), _p(noise), _p(x0_out), batch, n, _p(coef),
+                                            _p(step_dev), quantile, int(advance), _p(ws), ws.numel() * 4,
+                                            _stream(lib)), "lfdm_sampler_step_f32")
+    else:
+        lib.check(lib.lfdm_sampler_step_known_f32(_p(x), _p(eps), _p(noise), _p(x0_out), batch, n, _p(coef),
+                                                  _p(step_dev), quantile, int(advance), _p(ws), ws.numel() * 4,
+                                                  _p(known), _p(known_noise), _p(frame_mask), _p(level), kf[0], kf[1],
+                                                  _stream(lib)), "lfdm_sampler_step_known_f32")
     return x
 
 
-def sampler_step_ms(x, eps, hist, coef, step_dev, *, quantile=0.9, advance=True, x0_out=None, ws=None):
+def sampler_step_ms(x, eps, hist, coef, step_dev, *, quantile=0.9, advance=True, x0_out=None, ws=None,
+                    known=None, known_noise=None, frame_mask=None, level=None, frames=None):
     """lfdm_sampler_step_ms_f32: x <- k_x*x + k_m*m + k_prev*hist, hist <- m (the thresholded data prediction of this step);
-    coef rows {c_x, c_eps, k_x, k_m, k_prev, 0} (GaussianDiffusion._ms_step_tables)."""
+    coef rows {c_x, c_eps, k_x, k_m, k_prev, 0} (GaussianDiffusion._ms_step_tables).  Known-frame keywords as sampler_step
+    (lfdm_sampler_step_ms_known_f32)."""
     lib = _lib()
     _chk(lib, x, eps, hist, coef, step_dev, x0_out, ws)
+    kf = _known_operands("sampler_step_ms", x, known, known_noise, frame_mask, level, frames)
     batch = x.shape[0]
     n = x.numel() // batch
     if hist.numel() != x.numel():
         raise ValueError("sampler_step_ms: hist must have x's %d elements, got %d" % (x.numel(), hist.numel()))
     if ws is None:
         ws = sampler_ws(batch, n, x.device)
-    lib.check(lib.lfdm_sampler_step_ms_f32(_p(x), _p(eps), _p(hist), _p(x0_out), batch, n, _p(coef),
-                                           _p(step_dev), quantile, int(advance), _p(ws), ws.numel() * 4,
-                                           _stream(lib)), "lfdm_sampler_step_ms_f32")
+    if kf is None:
+        lib.check(lib.lfdm_sampler_step_ms_f32(_p(x), _p(eps), _p(hist), _p(x0_out), batch, n, _p(coef),
+                                               _p(step_dev), quantile, int(advance), _p(ws), ws.numel() * 4,
+                                               _stream(lib)), "lfdm_sampler_step_ms_f32")
+    else:
+        lib.check(lib.lfdm_sampler_step_ms_known_f32(_p(x), _p(eps), _p(hist), _p(x0_out), batch, n, _p(coef),
+                                                     _p(step_dev), quantile, int(advance), _p(ws), ws.numel() * 4,
+                                                     _p(known), _p(known_noise), _p(frame_mask), _p(level), kf[0], kf[1],
+                                                     _stream(lib)), "lfdm_sampler_step_ms_known_f32")
+    return x
+
+
+def known_blend(x, known, known_noise, frame_mask, a, s, frames):
+    """lfdm_known_blend_f32: x[b, :, t] <- a * known + s * known_noise where frame_mask[b, t] (the x_T blend of a conditioned video)."""
+    lib = _lib()
+    _chk(lib, x, known, known_noise)
+    if known is None or known_noise is None or frame_mask is None:
+        raise ValueError("known_blend: known, known_noise and frame_mask are required")
+    fr, frame_elems = _known_operands("known_blend", x, known, known_noise, frame_mask, None, frames, need_level=False)
+    batch = x.shape[0]
+    lib.check(lib.lfdm_known_blend_f32(_p(x), _p(known), _p(known_noise), _p(frame_mask), float(a), float(s), batch, x.numel() // batch,
+                                       fr, frame_elems, _stream(lib)), "lfdm_known_blend_f32")
     return x
 
 

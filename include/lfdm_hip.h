@@ -340,6 +340,26 @@ int lfdm_sampler_step_f32(float* x, const float* eps, const float* noise, float*
 int lfdm_sampler_step_ms_f32(float* x, const float* eps, float* hist, float* x0_out, int batch, int64_t n,
                              const float* coef, int32_t* step_dev, float quantile, int advance, void* ws,
                              size_t ws_bytes, lfdm_stream_t stream);
+/* Known-frame conditioning (replacement method; additive, ABI version unchanged): the two steps above with the final store of x
+ * replaced, at the frames a byte mask marks, by the known content on the level the step ends on:
+ *   x[b, i] <- a * known[b, i] + s * known_noise[b, i]     where frame_mask[b, (i / frame_elems) % frames] != 0,   (a, s) = level[2 * (step + 1)]
+ * known, known_noise (B, n) fp32; frame_mask (B, frames) bytes; level (steps + 1, 2) fp32 on the device, row 0 = the level of x_T, row i + 1 =
+ * after step i, indexed by the same device step counter as coef (read before it is advanced).  n must be a multiple of frames * frame_elems
+ * (planar (C, T, S, S): frame_elems = S * S).  It is a select, not a blend: values of known / known_noise at unmarked frames are never read into
+ * a result and may be NaN.  x0, the threshold (quantile over the whole sample), x0_out, hist and the step counter are exactly what the plain
+ * step computes; the launch sequence is the plain step's with the update kernel's conditioned instantiation.  Null known operands or a bad
+ * frame split return LFDM_EINVAL. */
+int lfdm_sampler_step_known_f32(float* x, const float* eps, const float* noise, float* x0_out, int batch, int64_t n,
+                                const float* coef, int32_t* step_dev, float quantile, int advance, void* ws, size_t ws_bytes,
+                                const float* known, const float* known_noise, const unsigned char* frame_mask, const float* level,
+                                int frames, int64_t frame_elems, lfdm_stream_t stream);
+int lfdm_sampler_step_ms_known_f32(float* x, const float* eps, float* hist, float* x0_out, int batch, int64_t n,
+                                   const float* coef, int32_t* step_dev, float quantile, int advance, void* ws, size_t ws_bytes,
+                                   const float* known, const float* known_noise, const unsigned char* frame_mask, const float* level,
+                                   int frames, int64_t frame_elems, lfdm_stream_t stream);
+/* the same select with host scalars, for x_T (once per video, outside the replayed step): x <- a * known + s * known_noise at marked frames */
+int lfdm_known_blend_f32(float* x, const float* known, const float* known_noise, const unsigned char* frame_mask, float a, float s,
+                         int batch, int64_t n, int frames, int64_t frame_elems, lfdm_stream_t stream);
 /* classifier-free guidance combine of Unet3D.forward_with_cond_scale (:525-526):
  * out = null_eps + (cond_eps - null_eps) * scale   (out may alias an input) */
 int lfdm_cfg_combine_f32(const float* cond_eps, const float* null_eps, float scale, float* out,

@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""lfdm_sampler_step_f32 and lfdm_sampler_step_ms_f32 at the C2 latent (B=1, 3x40x32x32): us per step (graph replay), alternating."""
+"""lfdm_sampler_step_f32 and lfdm_sampler_step_ms_f32, plain and with known frames (8 of the 40, lfdm_sampler_step_*_known_f32), at the C2
+latent (B=1, 3x40x32x32): us per step (graph replay), alternating."""
 import os
 import statistics
 import sys
@@ -26,8 +27,14 @@ for b, shape in ((1, (3, 40, 32, 32)), (16, (3, 40, 32, 32)), (4, (3, 40, 64, 64
     table = torch.rand(4, 6, device="cuda")            # every coefficient non-zero: the multistep update reads its history
     step = torch.zeros(1, dtype=torch.int32, device="cuda")
     ws = ops.sampler_ws(b, n, "cuda")
+    mask = torch.zeros(b, shape[1], dtype=torch.bool, device="cuda")
+    mask[:, :8] = True
+    kf = dict(known=torch.randn(b, *shape, device="cuda"), known_noise=torch.randn(b, *shape, device="cuda"), frame_mask=mask,
+              level=torch.rand(5, 2, device="cuda"), frames=shape[1])
     fns = {"sampler_step": lambda: ops.sampler_step(x, eps, noise, table, step, ws=ws, advance=False),
-           "sampler_step_ms": lambda: ops.sampler_step_ms(x, eps, hist, table, step, ws=ws, advance=False)}
+           "sampler_step_ms": lambda: ops.sampler_step_ms(x, eps, hist, table, step, ws=ws, advance=False),
+           "sampler_step known": lambda: ops.sampler_step(x, eps, noise, table, step, ws=ws, advance=False, **kf),
+           "sampler_step_ms known": lambda: ops.sampler_step_ms(x, eps, hist, table, step, ws=ws, advance=False, **kf)}
     graphs = {}
     for name, fn in fns.items():
         for _ in range(3):

@@ -5,6 +5,7 @@ checkpoints, read one reference image, sample a 40-frame video per text prompt a
 
     python tools/demo.py --config configs/lfae_128.yaml --lfae-ckpt RegionMM.pth --dm-ckpt flowdiff.pth \
         --bert /data/bert-base-cased --image face.jpg --text happiness anger --out demo_out
+    python tools/demo.py --synthetic --total-frames 112 --overlap 4 --out demo_out      # a long video: three chained 40-frame windows
     python tools/demo.py --synthetic --out demo_out        # random-init weights, random image, fixed embedding:
                                                             # exercises the whole pipeline where no checkpoint exists
 """
@@ -21,7 +22,7 @@ sys.path.insert(0, ROOT)
 from cvpr23_lfdm_amd import FlowDiffusion, io_compat as C  # noqa: E402
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", default=os.path.join(ROOT, "configs", "lfae_128.yaml"))
     ap.add_argument("--lfae-ckpt", default="", help="RegionMM_*.pth (keys generator / region_predictor / bg_predictor)")
@@ -40,7 +41,15 @@ def main():
                     help="operands of the UNet's Winograd 3x3 convolutions: bf16 is the faster, lower-precision sampling mode (DESIGN.md)")
     ap.add_argument("--sampler", choices=("reference", "dpmpp_1", "dpmpp_2m"), default="reference",
                     help="reference: DDIM / DDPM as the reference samples; dpmpp_2m: DPM-Solver++(2M), second order, for few --steps (DESIGN.md 4.2)")
-    args = ap.parse_args()
+    ap.add_argument("--total-frames", type=int, default=0,
+                    help="a video of this many frames, longer than --frames, as a chain of overlapping windows conditioned on known frames "
+                         "(FlowDiffusion.sample_long_video, DESIGN.md 4.3); 0 (default): off, one window of --frames")
+    ap.add_argument("--overlap", type=int, default=8, help="latent frames two consecutive windows of --total-frames share")
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
     if not torch.cuda.is_available():
         sys.exit("tools/demo.py needs a GPU: the sampling path is liblfdm_hip.so only")
     os.makedirs(args.out, exist_ok=True)
@@ -72,7 +81,10 @@ def main():
     name = os.path.splitext(os.path.basename(args.image))[0] if args.image else "random"
     for i, text in enumerate(args.text):
         model.set_sample_input(sample_img=ref, sample_text=[text])
-        model.sample_one_video(cond_scale=args.cond_scale)
+        if args.total_frames > 0:
+            model.sample_long_video(args.cond_scale, args.total_frames, overlap=args.overlap)
+        else:
+            model.sample_one_video(cond_scale=args.cond_scale)
         path = os.path.join(args.out, "%04d_%s_%s_%.2f.gif" % (i, text.replace(" ", "_"), name, args.cond_scale))
         C.mimsave(path, C.video_strip(model, ref))
         print(path)
