@@ -123,6 +123,7 @@ class GridSampleParams(C.Structure):
 
 
 BN_TICKETS = 1024
+OPTIM_PLAN_BYTES = 64      # LFDM_OPTIM_PLAN_BYTES: lfdm_optim_plan = [apply i32 | - | clip_coef, total_norm, bias1, bias2_sqrt, ema_decay, 1 - ema_decay f32 | applied_steps, skipped_steps i64 | -]
 
 _SIGNATURES = {
     # name: (restype, argtypes)
@@ -211,6 +212,11 @@ _SIGNATURES = {
     "lfdm_linear_attention_bwd_ws_bytes": (sz, [i32]),
     "lfdm_linear_attention_bwd_cl_f32": (i32, [f32p, f32p, f32p, i32, i32, C.c_void_p, sz, stream_t]),
     "lfdm_adam_step_f32": (i32, [f32p, f32p, f32p, f32p, i64, f32, f32, f32, f32, f32, i32, f32, stream_t]),
+    # ---- guarded optimizer step: norm partials -> device-resident plan -> fused Adam + EMA (additive, ABI stays 12)
+    "lfdm_grad_sumsq_ws_bytes": (sz, [i64]),
+    "lfdm_grad_sumsq_f32": (i32, [f32p, i64, f32p, sz, stream_t]),
+    "lfdm_optim_plan_f32": (i32, [f32p, i32, C.c_void_p, sz, f32, f32, i32, f32, f32, C.c_double, i64, stream_t]),
+    "lfdm_adam_guarded_step_f32": (i32, [f32p, f32p, f32p, f32p, f32p, i64, f32, f32, f32, f32, f32, f32, C.c_void_p, stream_t]),
     "lfdm_depthwise_down_planar_f32": (i32, [f32p, f32p, f32p, i32, i32, i32, i32, i32, i32, i32, i32, stream_t]),
     "lfdm_upsample2_pad_cl_f32": (i32, [f32p, f32p, i32, i32, i32, i32, i32, i32, i32, stream_t]),
     "lfdm_layernorm_bwd_ws_bytes": (sz, [i64, i32]),

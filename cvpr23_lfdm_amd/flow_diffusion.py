@@ -7,6 +7,7 @@ The DM training step (a29) = frozen-LFAE pseudo ground truth batched over all fr
 diffusion loss through the native UNet forward/backward (unet_train.py, autograd.py) -> fused Adam (optim.py), with
 an optional one-process-per-GPU gradient all-reduce (`enable_data_parallel`).
 """
+import contextlib
 import os
 
 import torch
@@ -68,14 +69,18 @@ class FlowDiffusion(nn.Module):
                  ddim_sampling_eta=1., timesteps=1000, dim_mults=(1, 2, 4, 8), lr=1e-4,
                  adam_betas=(0.9, 0.99), is_train=True, only_use_flow=True, use_residual_flow=False,
                  learn_null_cond=False, use_deconv=True, padding_mode="zeros", pretrained_pth="",
-                 config_pth="", bert_path=None, *, conv_precision="fp32", sampler="reference"):
+                 config_pth="", bert_path=None, *, conv_precision="fp32", sampler="reference", ema_decay=None, ema_start_step=0,
+                 max_grad_norm=None, skip_nonfinite=False):
         """Reference signature (video_flow_diffusion_model.py:19-37) + `bert_path`: a local Hugging Face directory of
         bert-base-cased for `cond=list[str]` (the reference downloads it with torch.hub; see text.py).  LFDM_BERT_PATH in
         the environment is the default, so unchanged caller scripts pick it up.
         conv_precision (keyword only): Unet3D.conv_precision of the denoiser - "fp32" (default) or "bf16", the opt-in faster sampling mode
         whose Winograd 3x3 convolutions run on bf16 operands (sampling and the eval branch of p_losses; training stays fp32).
         sampler (keyword only): GaussianDiffusion.sampler - "reference" (default: DDIM / DDPM as the reference chooses), "dpmpp_2m"
-        (DPM-Solver++(2M): second order, deterministic, meant for few steps) or "dpmpp_1"; composes with conv_precision."""
+        (DPM-Solver++(2M): second order, deterministic, meant for few steps) or "dpmpp_1"; composes with conv_precision.
+        ema_decay / ema_start_step / max_grad_norm / skip_nonfinite (keyword only, all off by default; training only): FlatAdam's options -
+        an exponential moving average of the denoiser's weights (`ema_weights()`, `ema_state_dict()`), global-norm gradient clipping and a
+        guard that skips a step whose gradient is not finite, all decided on the device inside the optimizer step."""
         super().__init__()
         check_num_frames(num_frames)        # (before the checkpoint and the config are read)
         if sampler not in GaussianDiffusion.SAMPLERS:
@@ -122,7 +127,10 @@ class FlowDiffusion(nn.Module):
             self.rec_loss = torch.tensor(0.0)
             self.rec_warp_loss = torch.tensor(0.0)
             # a torch.optim.Optimizer (state_dict / param_groups / lr schedulers work) whose step is one fused HIP launch
-            self.optimizer_diff = FlatAdam(self.diffusion.parameters(), lr=lr, betas=adam_betas)
+            self.optimizer_diff = FlatAdam(self.diffusion.parameters(), lr=lr, betas=adam_betas, ema_decay=ema_decay,
+                                           ema_start_step=ema_start_step, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+        elif ema_decay is not None or max_grad_norm is not None or skip_nonfinite:
+            raise ValueError("ema_decay / max_grad_norm / skip_nonfinite are options of the training optimizer: they need is_train=True")
         self._dp = None
         self.lazy_real_decode = os.environ.get("LFDM_LAZY_REAL_DECODE", "0") == "1"     # see the real_out_vid property
         self._real_decode, self._real_out_vid, self._real_warped_vid = None, None, None
@@ -224,6 +232,25 @@ class FlowDiffusion(nn.Module):
             self.sample_vid_conf = torch.cat(confs, dim=2)
             self.sample_out_vid = torch.cat(outs, dim=2)
             self.sample_warped_vid = torch.cat(warps, dim=2)
+
+    # ------------------------------------------------------------------ averaged weights
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the denoiser's parameters ARE the optimizer's averaged weights (their storage is re-pointed at the `ema`
+        slices, nothing is copied) and the weights epoch is bumped, so Unet3D.packed() and the captured sampling graphs rebuild:
+        sample_one_video / sample_long_video sample from the average with every sampler and conv_precision.  optimizer_diff.step() raises
+        inside.  The raw weights come back on exit, also when the body raises."""
+        if not self.is_train:
+            raise RuntimeError("ema_weights(): only a training model (is_train=True, ema_decay=...) keeps an average; for sampling alone "
+                               "load ema_state_dict() into the model")
+        with self.optimizer_diff.ema_weights():
+            yield self
+
+    def ema_state_dict(self):
+        """A dict shaped like diffusion.state_dict() (same keys; buffers as they are) with the averaged weights in place of the raw ones,
+        detached copies: what a sampling model - this framework's or the reference's demo scripts - loads with load_state_dict."""
+        with self.ema_weights():
+            return {k: v.detach().clone() for k, v in self.diffusion.state_dict().items()}
 
     def set_sample_input(self, sample_img, sample_text):
         dev = next(self.unet.parameters()).device

@@ -7,23 +7,64 @@ live contiguously, each tensor being a view.  The same flat gradient buffer is w
 bucketed sum all-reduce over xGMI launched from autograd hooks while backward is still running; the 1/world of the
 mean is folded into the Adam kernel.  (Reference multi-GPU: nn.DataParallel threads + NCCL reduce to GPU 0,
 SURVEY.md 3.4; here: one process per GPU, every rank applies the identical update, no parameter broadcast.)
+
+Opt-in: an exponential moving average of the weights, global-norm gradient clipping and a guard that skips
+a step whose gradient is not finite.  With any of them on the step is the GUARDED one - a sum-of-squares pass over the flat
+gradient, a one-workgroup plan kernel and a fused Adam + EMA update that reads clip coefficient, skip-or-apply, bias
+corrections and EMA decay from device memory - and the authoritative step counter lives on the device: `step()` never
+synchronises.
 """
+import contextlib
+
 import torch
 
+from ._native import OPTIM_PLAN_BYTES
 from .ops import _chk, _lib, _p, _stream
 from .params import bump_weights_epoch
 
 
 class FlatAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    """torch.optim.Adam semantics over flat buffers.  Options (all off by default: the step is then the single
+    lfdm_adam_step_f32 launch):
+      ema_decay       d in [0, 1): a fifth flat buffer `ema` (same offsets as the parameters, initialised from them) takes
+                      ema = d * ema + (1 - d) * p_new in the update pass; every slice is state[p]["ema"], so state_dict() /
+                      load_state_dict() carry it (a state without "ema" loads: the average restarts from the parameters).
+      ema_start_step  applied steps 1 .. ema_start_step leave ema == p exactly (decay 0).
+      max_grad_norm   torch.nn.utils.clip_grad_norm_(params, max_grad_norm) semantics on the averaged gradient, before weight
+                      decay.  The flat gradient buffer is NOT modified: p.grad keeps showing the unclipped gradient.
+      skip_nonfinite  a step whose gradient norm is inf / nan (one such element anywhere, or a sum of squares beyond fp32)
+                      changes nothing: parameters, moments, ema and the step counter stay as they were; skipped_steps() counts it.
+    last_grad_norm() / skipped_steps() read the device plan back (a synchronisation: use them at print frequency)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, ema_decay=None, ema_start_step=0,
+                 max_grad_norm=None, skip_nonfinite=False):
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError("FlatAdam: ema_decay must lie in [0, 1), got %r" % (ema_decay,))
+        if int(ema_start_step) < 0:
+            raise ValueError("FlatAdam: ema_start_step must be >= 0, got %r" % (ema_start_step,))
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError("FlatAdam: max_grad_norm must be positive, got %r" % (max_grad_norm,))
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
-        self._flat = None            # per group: dict(params, offs, p, g, m, v, gviews)
+        self._flat = None            # per group: dict(params, offs, p, g, m, v, gviews[, ema, plan, partials])
         self._staged = False         # gradients already gathered into the flat buffer (GradAllReduce.finish)
         self.grad_scale = 1.0        # GradAllReduce sets 1/world
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_start_step = int(ema_start_step)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.guarded = self.ema_decay is not None or self.max_grad_norm is not None or self.skip_nonfinite
+        if self.guarded and len(self.param_groups) != 1:
+            raise ValueError("FlatAdam: ema_decay / max_grad_norm / skip_nonfinite need ONE parameter group (the norm is global)")
+        self._ema_live = False       # inside ema_weights(): the parameters point at the ema slices
 
     # ------------------------------------------------------------------ flat storage
     def _build(self):
+        skipped = 0
+        if self.guarded and self._flat is not None:       # a rebuild (parameters moved): the device counters move along
+            steps, skipped = self._flat[0]["plan"].view(torch.int64)[4:6].tolist()
+            for p in self._flat[0]["params"]:
+                self.state[p]["step"] = torch.tensor(float(steps))
         flats = []
         for group in self.param_groups:
             ps = [p for p in group["params"] if p.requires_grad]
@@ -56,13 +97,43 @@ class FlatAdam(torch.optim.Optimizer):
                 st.setdefault("step", torch.tensor(0.0))
                 st["exp_avg"] = fm[o:o + k].view(p.shape)
                 st["exp_avg_sq"] = fv[o:o + k].view(p.shape)
-            flats.append(dict(params=ps, offs=offs, p=fp, g=fg, m=fm, v=fv, gviews=gviews))
+            fl = dict(params=ps, offs=offs, p=fp, g=fg, m=fm, v=fv, gviews=gviews)
+            if self.guarded:
+                self._build_guarded(fl, skipped)
+            flats.append(fl)
         self._flat = flats
         self._staged = False
+
+    def _build_guarded(self, fl, skipped=0):
+        """The guarded step's device state: the plan (its counter starts at the loaded step), the norm partials, the average."""
+        lib = _lib()
+        fp, ps, offs = fl["p"], fl["params"], fl["offs"]
+        plan = torch.zeros(OPTIM_PLAN_BYTES // 4, dtype=torch.int32, device=fp.device)
+        plan.view(torch.int64)[4] = int(self.state[ps[0]]["step"])          # lfdm_optim_plan.applied_steps
+        plan.view(torch.int64)[5] = int(skipped)                            # .skipped_steps
+        fl["plan"] = plan
+        if self.max_grad_norm is not None or self.skip_nonfinite:
+            fl["partials"] = torch.zeros(lib.lfdm_grad_sumsq_ws_bytes(fp.numel()) // 4, dtype=torch.float32, device=fp.device)
+        if self.ema_decay is None:
+            for p in ps:
+                self.state[p].pop("ema", None)
+            return
+        fe = fp.clone()                                                      # no saved average: it starts from the parameters
+        for pi, (p, o) in enumerate(zip(ps, offs)):
+            k, st = p.numel(), self.state[p]
+            if "ema" in st:
+                if st["ema"].numel() != k:
+                    raise ValueError("FlatAdam.load_state_dict: the average of parameter #%d has %d elements, the parameter %s has %d"
+                                     % (pi, st["ema"].numel(), tuple(p.shape), k))
+                fe[o:o + k].copy_(st["ema"].reshape(-1))
+            st["ema"] = fe[o:o + k].view(p.shape)
+        fl["ema"] = fe
 
     def _valid(self):
         if self._flat is None:
             return False
+        if self._ema_live:               # the parameters are deliberately elsewhere (ema_weights); step() refuses to run
+            return True
         for fl in self._flat:
             base = fl["p"].data_ptr()
             for p, o in zip(fl["params"], fl["offs"]):
@@ -119,8 +190,61 @@ class FlatAdam(torch.optim.Optimizer):
             self._staged = True
 
     def load_state_dict(self, state_dict):
+        if self._ema_live:
+            raise RuntimeError("FlatAdam.load_state_dict inside ema_weights(): the parameters are the averaged ones")
         super().load_state_dict(state_dict)
-        self._flat = None             # loaded moments are folded into fresh flat buffers at the next step
+        self._flat = None             # loaded moments (and average, and step count) are folded into fresh flat buffers at the next step
+
+    def _plan(self):
+        return self.ensure_flat()[0]["plan"]
+
+    def applied_steps(self):
+        """Steps applied so far (skipped ones not counted).  Guarded: read back from the device."""
+        if self.guarded:
+            return int(self._plan().view(torch.int64)[4].item())
+        fl = self.ensure_flat()[0]
+        return int(self.state[fl["params"][0]]["step"])
+
+    def skipped_steps(self):
+        """Steps the non-finite guard dropped since this optimizer's buffers were built (read back from the device)."""
+        return int(self._plan().view(torch.int64)[5].item()) if self.guarded else 0
+
+    def last_grad_norm(self):
+        """Global norm of the averaged gradient of the latest step, before clipping (read back from the device); None when
+        neither clipping nor the guard is on - no norm pass runs then."""
+        if self.max_grad_norm is None and not self.skip_nonfinite:
+            return None
+        return float(self._plan().view(torch.float32)[3].item())
+
+    def state_dict(self):
+        if self.guarded and self._flat is not None:      # the device counter is the authoritative one: the only read-back is here
+            step = float(self.applied_steps())
+            for fl in self._flat:
+                for p in fl["params"]:
+                    self.state[p]["step"] = torch.tensor(step)
+        return super().state_dict()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside: every parameter's storage is its slice of the averaged buffer (no copy); step() raises.  The caller bumps
+        whatever caches depend on the weights (FlowDiffusion.ema_weights does).  Restored on exit, also on an exception."""
+        if self.ema_decay is None:
+            raise RuntimeError("ema_weights(): this optimizer keeps no average (ema_decay=None)")
+        if self._ema_live:
+            raise RuntimeError("ema_weights() is not re-entrant")
+        fl = self.ensure_flat()[0]
+        raw = [p.data for p in fl["params"]]
+        self._ema_live = True
+        try:
+            for p in fl["params"]:
+                p.data = self.state[p]["ema"]
+            bump_weights_epoch()
+            yield self
+        finally:
+            for p, d in zip(fl["params"], raw):
+                p.data = d
+            self._ema_live = False
+            bump_weights_epoch()
 
     # ------------------------------------------------------------------ step
     @torch.no_grad()
@@ -129,11 +253,17 @@ class FlatAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if self._ema_live:
+            raise RuntimeError("FlatAdam.step() inside ema_weights(): the parameters are the averaged ones - leave the context first")
         lib = _lib()
         self.ensure_flat()
         if not self._staged:
             self.stage_grads()
         self._staged = False
+        if self.guarded:
+            self._guarded_step(lib)
+            bump_weights_epoch()
+            return loss
         for group, fl in zip(self.param_groups, self.ensure_flat()):
             st0 = self.state[fl["params"][0]]
             step = int(st0["step"]) + 1
@@ -147,6 +277,24 @@ class FlatAdam(torch.optim.Optimizer):
                       "lfdm_adam_step_f32")
         bump_weights_epoch()      # the kernel wrote the parameters behind torch's back: packed weight caches must rebuild
         return loss
+
+    def _guarded_step(self, lib):
+        """Norm partials (only with clipping / the guard) -> plan -> fused update, all on the current stream, no read-back."""
+        group, fl = self.param_groups[0], self._flat[0]
+        n, parts, ema = fl["p"].numel(), fl.get("partials"), fl.get("ema")
+        _chk(lib, fl["p"], fl["g"], fl["m"], fl["v"], ema, parts)
+        b1, b2 = group["betas"]
+        stream = _stream(lib)
+        if parts is not None:
+            lib.check(lib.lfdm_grad_sumsq_f32(_p(fl["g"]), n, _p(parts), parts.numel() * 4, stream), "lfdm_grad_sumsq_f32")
+        lib.check(lib.lfdm_optim_plan_f32(_p(parts), 0 if parts is None else parts.numel(), _p(fl["plan"]), fl["plan"].numel() * 4,
+                                          float(self.grad_scale), -1.0 if self.max_grad_norm is None else self.max_grad_norm,
+                                          int(self.skip_nonfinite), float(b1), float(b2),
+                                          -1.0 if self.ema_decay is None else self.ema_decay, self.ema_start_step, stream),
+                  "lfdm_optim_plan_f32")
+        lib.check(lib.lfdm_adam_guarded_step_f32(_p(fl["p"]), _p(fl["g"]), _p(fl["m"]), _p(fl["v"]), _p(ema), n, float(group["lr"]),
+                                                 float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
+                                                 float(self.grad_scale), _p(fl["plan"]), stream), "lfdm_adam_guarded_step_f32")
 
 
 class GradAllReduce:
@@ -185,8 +333,10 @@ class GradAllReduce:
         if self.world <= 1:
             return
         for group, fl in zip(self.opt.param_groups, self.opt.ensure_flat()):
-            for key in ("p", "m", "v"):
+            for key in ("p", "m", "v") + (("ema",) if "ema" in fl else ()):
                 self.dist.broadcast(fl[key], src=src, group=self.group)
+            if "plan" in fl:                          # guarded: the device plan carries the counters (applied / skipped steps)
+                self.dist.broadcast(fl["plan"], src=src, group=self.group)
             step = torch.tensor([float(self.opt.state[fl["params"][0]]["step"])], device=fl["p"].device)
             self.dist.broadcast(step, src=src, group=self.group)
             for p in fl["params"]:
@@ -194,14 +344,19 @@ class GradAllReduce:
         bump_weights_epoch()
 
     def replica_checksum(self):
-        """(max - min) over ranks of the fp64 sum of the flat parameter buffer: 0.0 iff the replicas agree."""
-        tot = torch.stack([fl["p"].double().sum() for fl in self.opt.ensure_flat()]).sum().reshape(1)
+        """(max - min) over ranks of the fp64 sum of the flat parameter buffer: 0.0 iff the replicas agree.  With an average
+        (FlatAdam ema_decay) the same for the `ema` buffer, and the larger of the two is returned."""
+        flats = self.opt.ensure_flat()
+        tot = [torch.stack([fl["p"].double().sum() for fl in flats]).sum()]
+        if all("ema" in fl for fl in flats):
+            tot.append(torch.stack([fl["ema"].double().sum() for fl in flats]).sum())
+        tot = torch.stack(tot)
         if self.world <= 1:
             return 0.0
         hi, lo = tot.clone(), tot.clone()
         self.dist.all_reduce(hi, op=self.dist.ReduceOp.MAX, group=self.group)
         self.dist.all_reduce(lo, op=self.dist.ReduceOp.MIN, group=self.group)
-        return float((hi - lo).item())
+        return float((hi - lo).max().item())
 
     def _setup(self):
         flats = self.opt.ensure_flat()

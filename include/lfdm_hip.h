@@ -646,6 +646,49 @@ int lfdm_adam_step_f32(float* param, const float* grad, float* exp_avg, float* e
                        float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                        float grad_scale, lfdm_stream_t stream);
 
+/* Guarded optimizer step (additive; FlatAdam's opt-in ema_decay / max_grad_norm / skip_nonfinite).  Three launches on one
+ * stream replace, per step, torch.nn.utils.clip_grad_norm_(params, max_norm) (~300 small launches and a host read-back of the norm), the
+ * `if not torch.isfinite(norm): skip` test a training script would write around optimizer.step(), the Adam step itself and the
+ * `for e, p in zip(ema, params): e.mul_(d).add_(p, alpha=1 - d)` loop of an EMA class (video_flow_diffusion.py:116-135, never wired in by
+ * the reference).  Every decision is taken on the device; nothing here synchronises.  No floating-point atomics: all results are fixed
+ * functions of their inputs, so data-parallel ranks holding the same all-reduced gradient take bit-identical updates.
+ *
+ * The plan: LFDM_OPTIM_PLAN_BYTES of device memory, 16-byte aligned, zeroed once by the caller and then owned by these calls (the two
+ * counters persist across steps; a caller restoring a checkpoint writes applied_steps itself). */
+#define LFDM_OPTIM_PLAN_BYTES 64
+typedef struct {
+  int apply;                    /* 0: the norm was not finite and the guard is on - the update pass does nothing */
+  int reserved0;
+  float clip_coef;              /* min(1, max_grad_norm / (total_norm + 1e-6)); 1 when clipping is off */
+  float total_norm;             /* grad_scale * sqrt(sum g^2): the norm of the AVERAGED gradient; 0 when no norm pass ran */
+  float bias1;                  /* 1 - beta1^t, t = applied_steps + 1 (computed in double) */
+  float bias2_sqrt;             /* sqrt(1 - beta2^t) */
+  float ema_decay;              /* effective decay of step t: 0 while t <= ema_start_step (the average tracks the parameters exactly) */
+  float ema_one_minus_decay;    /* 1 - decay, rounded once from double */
+  int64_t applied_steps;        /* += 1 when apply */
+  int64_t skipped_steps;        /* += 1 when not */
+  int reserved1[4];
+} lfdm_optim_plan;
+
+/* Pass 1 (only when clipping or the guard is on): one fp32 partial sum of squares per workgroup of the launch, written to
+ * partials[0 .. lfdm_grad_sumsq_ws_bytes(n) / 4).  16-byte loads, four accumulators per thread, adam_step's launch geometry
+ * (min(ceil(n / 1024), 4096) workgroups of 256): each accumulator is a chain of L = ceil((n / 4) / (256 * workgroups)) (+ 1 when n % 4)
+ * fused multiply-adds, followed by 8 tree levels; the relative error of the norm is at most (L + 12) * 2^-24. */
+size_t lfdm_grad_sumsq_ws_bytes(int64_t n);
+int lfdm_grad_sumsq_f32(const float* grad, int64_t n, float* partials, size_t partials_bytes, lfdm_stream_t stream);
+/* Pass 2 (one workgroup): sums the partials in a fixed order in fp64 and writes the plan for step applied_steps + 1, then advances
+ * applied_steps or skipped_steps.  n_partials = 0 (partials may be NULL): no norm pass ran - total_norm 0, clip_coef 1, apply 1; then
+ * max_grad_norm must be negative and skip_nonfinite 0.  max_grad_norm < 0: clipping off.  ema_decay < 0: no average (decay 0). */
+int lfdm_optim_plan_f32(const float* partials, int n_partials, void* plan, size_t plan_bytes, float grad_scale, float max_grad_norm,
+                        int skip_nonfinite, float beta1, float beta2, double ema_decay, int64_t ema_start_step, lfdm_stream_t stream);
+/* Pass 3: the arithmetic of the plain Adam step above with grad = g * grad_scale * clip_coef + weight_decay * p (the clip acts on the
+ * averaged gradient, before weight decay - the torch call order) and, when ema is not NULL, ema = d * ema + (1 - d) * p_new in the same
+ * pass; clip_coef, the bias corrections, d and apply are read from the plan in device memory.  apply == 0: param, exp_avg, exp_avg_sq
+ * and ema stay bit-for-bit untouched.  grad is never written. */
+int lfdm_adam_guarded_step_f32(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, float lr,
+                               float beta1, float beta2, float eps, float weight_decay, float grad_scale, const void* plan,
+                               lfdm_stream_t stream);
+
 /* AntiAliasInterpolation2d (LFAE/modules/util.py:217-264; region / pixelwise-flow predictor inputs): planar
  * (N, C, H, W) -> zero-pad (pad_lo before, pad_hi after) -> depthwise k x k filter wgt (C, k, k) -> every
  * stride-th pixel: out (N, C, ceil((H+pad_lo+pad_hi-k+1)/stride), ...). */

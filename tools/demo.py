@@ -45,11 +45,25 @@ def build_parser():
                     help="a video of this many frames, longer than --frames, as a chain of overlapping windows conditioned on known frames "
                          "(FlowDiffusion.sample_long_video, DESIGN.md 4.3); 0 (default): off, one window of --frames")
     ap.add_argument("--overlap", type=int, default=8, help="latent frames two consecutive windows of --total-frames share")
+    ap.add_argument("--use-ema", action="store_true",
+                    help="sample from the averaged weights: the checkpoint's 'diffusion_ema' entry (tools/train_dm.py --ema-decay, DESIGN.md 4.4)")
     return ap
+
+
+def dm_state(ck, use_ema, path="the checkpoint"):
+    """The diffusion state dict to sample from: 'diffusion', or with --use-ema the averaged 'diffusion_ema' - an error when there is none."""
+    if not use_ema:
+        return ck["diffusion"]
+    if "diffusion_ema" not in ck:
+        sys.exit("--use-ema: %s has no 'diffusion_ema' entry (keys: %s) - it was trained without --ema-decay; drop --use-ema to "
+                 "sample from its raw weights" % (path, ", ".join(sorted(ck))))
+    return ck["diffusion_ema"]
 
 
 def main():
     args = build_parser().parse_args()
+    if args.use_ema and (args.synthetic or not args.dm_ckpt):
+        sys.exit("--use-ema needs --dm-ckpt: a checkpoint with a 'diffusion_ema' entry")
     if not torch.cuda.is_available():
         sys.exit("tools/demo.py needs a GPU: the sampling path is liblfdm_hip.so only")
     os.makedirs(args.out, exist_ok=True)
@@ -68,7 +82,7 @@ def main():
         emb = {t: torch.randn(1, 768, generator=torch.Generator().manual_seed(zlib.crc32(t.encode()))) for t in args.text}
         model.diffusion.text_encoder = lambda texts: torch.cat([emb[t] for t in texts])
     elif args.dm_ckpt:
-        model.diffusion.load_state_dict(torch.load(args.dm_ckpt, map_location="cpu")["diffusion"])   # demo_mug.py:93-97
+        model.diffusion.load_state_dict(dm_state(torch.load(args.dm_ckpt, map_location="cpu"), args.use_ema, args.dm_ckpt))   # demo_mug.py:93-97
     else:
         sys.exit("give --dm-ckpt (and --lfae-ckpt), or --synthetic")
     model.cuda().eval()

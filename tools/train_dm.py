@@ -6,8 +6,11 @@ restore semantics; one process per GPU under torchrun instead of nn.DataParallel
     python tools/train_dm.py --data DIR --lfae-ckpt RegionMM.pth --bert /data/bert-base-cased --out snapshots
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 tools/train_dm.py --data DIR ...
     python tools/train_dm.py --synthetic --final-step 20          # random videos / random-init LFAE: exercises the loop
+    python tools/train_dm.py --data DIR ... --ema-decay 0.9999 --ema-start-step 2000 --max-grad-norm 1.0 --skip-nonfinite
+        # averaged weights (checkpoint entry "diffusion_ema", tools/demo.py --use-ema), clipping and the non-finite guard: DESIGN.md 4.4
 """
 import argparse
+import contextlib
 import math
 import os
 import sys
@@ -47,6 +50,13 @@ def main():
     ap.add_argument("--save-img-freq", type=int, default=500)
     ap.add_argument("--num-workers", type=int, default=8)
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--ema-decay", type=float, default=None, help="keep an exponential moving average of the denoiser's weights with this "
+                    "decay; checkpoints gain a 'diffusion_ema' entry and previews are sampled from it")
+    ap.add_argument("--ema-start-step", type=int, default=0, help="the average tracks the weights exactly through this many applied steps")
+    ap.add_argument("--max-grad-norm", type=float, default=None, help="clip the global gradient norm (torch clip_grad_norm_ semantics)")
+    ap.add_argument("--skip-nonfinite", action="store_true", help="skip a step whose gradient holds an inf / nan instead of losing the run")
+    ap.add_argument("--preview-steps", type=int, default=0, help="> 0: at --save-img-freq also SAMPLE one video with this many DDIM steps "
+                    "(from the averaged weights under --ema-decay) and write it as a GIF")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("tools/train_dm.py needs a GPU: the training step is liblfdm_hip.so only")
@@ -64,8 +74,11 @@ def main():
     os.makedirs(args.out, exist_ok=True)
 
     model = FlowDiffusion(lr=args.lr, is_train=True, img_size=args.size // 4, num_frames=args.frames,
-                          null_cond_prob=args.null_cond_prob, sampling_timesteps=1000, config_pth=args.config,
-                          pretrained_pth=args.lfae_ckpt, bert_path=None if args.synthetic else args.bert)     # :153-162
+                          null_cond_prob=args.null_cond_prob, sampling_timesteps=args.preview_steps or 1000, config_pth=args.config,
+                          pretrained_pth=args.lfae_ckpt, bert_path=None if args.synthetic else args.bert,     # :153-162
+                          ema_decay=args.ema_decay, ema_start_step=args.ema_start_step, max_grad_norm=args.max_grad_norm,
+                          skip_nonfinite=args.skip_nonfinite)
+    opt = model.optimizer_diff
     model.cuda()
     if args.synthetic:
         emb = {}
@@ -111,9 +124,12 @@ def main():
             if rank == 0 and step % args.print_freq == 0:
                 dt = (timeit.default_timer() - t0) / args.print_freq
                 t0 = timeit.default_timer()
-                print("iter %d/%d  loss %.7f  loss_rec %.4f  loss_warp %.4f  lr %.2e  %.1f videos/s" % (
+                guard = ""                       # the device plan is read back HERE only (print frequency), never in the step
+                if opt.last_grad_norm() is not None:
+                    guard = "  grad_norm %.4g  skipped %d" % (opt.last_grad_norm(), opt.skipped_steps())
+                print("iter %d/%d  loss %.7f  loss_rec %.4f  loss_warp %.4f  lr %.2e  %.1f videos/s%s" % (
                     step, args.final_step, float(model.loss), float(model.rec_loss), float(model.rec_warp_loss),
-                    model.optimizer_diff.param_groups[0]["lr"], args.batch_size * world / dt), flush=True)
+                    opt.param_groups[0]["lr"], args.batch_size * world / dt, guard), flush=True)
             if rank == 0 and step % args.save_img_freq == 0:                   # the middle-frame panel of :246-275
                 mid, s = args.frames // 2, args.size
                 panel = np.zeros((2 * s, 4 * s, 3), np.uint8)
@@ -124,9 +140,19 @@ def main():
                 panel[:s, 3 * s:] = C.grid2fig(model.real_vid_grid[0, :, mid].permute(1, 2, 0).data.cpu().numpy(), grid_size=s // 4, img_size=s)
                 panel[s:, 3 * s:] = C.grid2fig(model.fake_vid_grid[0, :, mid].permute(1, 2, 0).data.cpu().numpy(), grid_size=s // 4, img_size=s)
                 C.imsave(os.path.join(args.out, "B%04d_S%06d_%s.png" % (args.batch_size, step, real_names[0])), panel)
+                if args.preview_steps > 0:                                      # a sampled preview, from the averaged weights when there are any
+                    with (model.ema_weights() if args.ema_decay is not None else contextlib.nullcontext()):
+                        model.set_sample_input(sample_img=ref_imgs[:1], sample_text=list(ref_texts)[:1])
+                        model.sample_one_video(cond_scale=1.0)
+                    C.mimsave(os.path.join(args.out, "B%04d_S%06d_%s%s.gif" % (args.batch_size, step, real_names[0],
+                                                                                "_ema" if args.ema_decay is not None else "")),
+                              C.video_strip(model, ref_imgs[:1]))
             if rank == 0 and (step % args.save_freq == 0 or step >= args.final_step):                         # :330-340
-                torch.save({"example": step * args.batch_size * world, "diffusion": model.diffusion.state_dict(),
-                            "optimizer_diff": model.optimizer_diff.state_dict()},
+                ck = {"example": step * args.batch_size * world, "diffusion": model.diffusion.state_dict(),
+                      "optimizer_diff": opt.state_dict()}
+                if args.ema_decay is not None:          # the averaged weights, shaped like "diffusion" (tools/demo.py --use-ema)
+                    ck["diffusion_ema"] = model.ema_state_dict()
+                torch.save(ck,
                            os.path.join(args.out, "flowdiff_%04d_S%06d.pth" % (args.batch_size, step)))
             if step >= args.final_step:
                 break
