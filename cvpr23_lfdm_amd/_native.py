@@ -217,6 +217,10 @@ _SIGNATURES = {
     "lfdm_grad_sumsq_f32": (i32, [f32p, i64, f32p, sz, stream_t]),
     "lfdm_optim_plan_f32": (i32, [f32p, i32, C.c_void_p, sz, f32, f32, i32, f32, f32, C.c_double, i64, stream_t]),
     "lfdm_adam_guarded_step_f32": (i32, [f32p, f32p, f32p, f32p, f32p, i64, f32, f32, f32, f32, f32, f32, C.c_void_p, stream_t]),
+    # ---- uint8 preview strips of a sampled video (additive, ABI stays 12)
+    "lfdm_flow_color_u8": (i32, [f32p, i64, f32p, C.c_void_p, i32, i32, i32, stream_t]),
+    "lfdm_render_strip_u8": (i32, [f32p, f32p, f32p, C.c_void_p, f32p, C.POINTER(C.c_double), C.POINTER(i32), i32, i32, C.c_void_p,
+                                   i32, i32, i32, i32, stream_t]),
     "lfdm_depthwise_down_planar_f32": (i32, [f32p, f32p, f32p, i32, i32, i32, i32, i32, i32, i32, i32, stream_t]),
     "lfdm_upsample2_pad_cl_f32": (i32, [f32p, f32p, i32, i32, i32, i32, i32, i32, i32, stream_t]),
     "lfdm_layernorm_bwd_ws_bytes": (sz, [i64, i32]),

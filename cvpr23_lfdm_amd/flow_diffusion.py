@@ -233,6 +233,47 @@ class FlowDiffusion(nn.Module):
             self.sample_out_vid = torch.cat(outs, dim=2)
             self.sample_warped_vid = torch.cat(warps, dim=2)
 
+    # ------------------------------------------------------------------ uint8 preview strips on the device
+    def render_sample(self, mean=(0., 0., 0.), panels=("source", "out", "warped", "flow", "conf"), indexed=False, *, source=None):
+        """The demo scripts' per-frame panel strip of the last sample_one_video / sample_long_video, rendered on the device: a uint8
+        tensor (B, T, S, P*S, 3), or (B, T, S, P*S) indices into io_compat.STRIP_PALETTE (6x6x6 cube, 8x8 ordered dither) when indexed.
+        panels: ordered subset of source / out / warped / flow / conf.  Image panels and conf are io_compat.sample_img(mean) / conf2fig to
+        the byte; flow is the colour-coded flow of misc.flow2fig (grid2fig's line drawing is not rendered on the device).  source (keyword
+        only): the (B, 3, S, S) image of the first panel, default the sample input.  Two launches (one without the flow panel)."""
+        from . import ops
+        if self.sample_out_vid is None:
+            raise RuntimeError("render_sample: nothing has been sampled yet - call sample_one_video or sample_long_video first")
+        panels = tuple(panels)
+        with torch.no_grad():
+            kw = {}
+            if "source" in panels:
+                src = self.sample_img if source is None else source
+                kw["source"] = src.to(self.sample_out_vid.device).float().contiguous()
+            if "out" in panels:
+                kw["out_vid"] = self.sample_out_vid.contiguous()
+            if "warped" in panels:
+                kw["warped_vid"] = self.sample_warped_vid.contiguous()
+            if "conf" in panels:
+                kw["conf"] = self.sample_vid_conf.contiguous()
+            if "flow" in panels:
+                kw["flow_color"] = ops.flow_to_color_u8(self.sample_vid_grid)
+                if "source" not in kw and len(kw) == 1:          # (a strip of the flow panel alone: the batch size comes from the source)
+                    kw["source"] = self.sample_img.to(self.sample_out_vid.device).float().contiguous()
+            return ops.render_strip(mean=mean, panels=panels, indexed=indexed, **kw)
+
+    def render_sample_host(self, mean=(0., 0., 0.), panels=("source", "out", "warped", "flow", "conf"), indexed=False, *, source=None):
+        """render_sample copied to the host: one asynchronous copy into a pinned buffer kept on the model (reused while the shape is
+        unchanged, so the returned numpy array is overwritten by the next call of the same shape) and ONE stream synchronisation."""
+        dev = self.render_sample(mean=mean, panels=panels, indexed=indexed, source=source)
+        buf = getattr(self, "_render_host", None)
+        if buf is None or buf.shape != dev.shape or buf.is_pinned() != dev.is_cuda:
+            buf = torch.empty(dev.shape, dtype=torch.uint8, pin_memory=dev.is_cuda)
+            self._render_host = buf
+        buf.copy_(dev, non_blocking=True)
+        if dev.is_cuda:
+            torch.cuda.current_stream(dev.device).synchronize()
+        return buf.numpy()
+
     # ------------------------------------------------------------------ averaged weights (DESIGN.md 4.4)
     @contextlib.contextmanager
     def ema_weights(self):

@@ -208,3 +208,46 @@ def video_strip(model, ref_imgs, mean=(0.0, 0.0, 0.0), grid_size=32):
         panel[:, 4 * s:5 * s] = conf2fig(model.sample_vid_conf[0, :, t], img_size=s)[..., None]
         frames.append(panel)
     return frames
+
+
+# ---------------------------------------------------------------------------------------------
+# the same strip rendered on the device (FlowDiffusion.render_sample) - opt-in; video_strip / mimsave above are unchanged
+# ---------------------------------------------------------------------------------------------
+def _strip_palette():
+    """The palette of the indexed strip: a 6x6x6 colour cube, index = 36 r + 6 g + b with level k = 51 k; entries 216 .. 255 black."""
+    pal = np.zeros((256, 3), np.uint8)
+    lv = np.arange(6, dtype=np.uint8) * 51
+    pal[:216, 0], pal[:216, 1], pal[:216, 2] = np.repeat(lv, 36), np.tile(np.repeat(lv, 6), 6), np.tile(lv, 36)
+    return pal
+
+
+STRIP_PALETTE = _strip_palette()
+STRIP_PALETTE.setflags(write=False)
+
+
+def video_strip_device(model, ref_imgs, mean=(0.0, 0.0, 0.0), indexed=False):
+    """video_strip's list of per-frame arrays (batch element 0) from ONE device rendering and one copy: [source | generated | warped |
+    colour-coded flow | occlusion], (S, 5S, 3) uint8 each - or (S, 5S) palette indices into STRIP_PALETTE when indexed (for
+    mimsave_indexed).  Panels 0, 1, 2 and 4 are video_strip's bytes; panel 3 is the reference's misc.flow2fig colour coding instead of
+    grid2fig's line drawing, which is not rendered on the device.  The arrays are views of the model's pinned host buffer: the next
+    render_sample_host call of the same shape overwrites them."""
+    host = model.render_sample_host(mean=mean, indexed=indexed, source=ref_imgs)
+    return [host[0, t] for t in range(host.shape[1])]
+
+
+def mimsave_indexed(path, index_frames, palette=STRIP_PALETTE, duration=0.1, loop=0):
+    """Animated GIF from (H, W) uint8 palette-index frames: PIL `P`-mode images with `palette` ((256, 3) uint8) attached, so PIL writes
+    the indices as they are - no per-frame median-cut quantisation as for RGB frames - and a decoder returns palette[index]."""
+    from PIL import Image
+    pal = np.ascontiguousarray(np.asarray(palette, dtype=np.uint8)).reshape(-1).tobytes()
+    ims = []
+    for f in index_frames:
+        f = np.asarray(f)
+        if f.ndim != 2 or f.dtype != np.uint8:
+            raise ValueError("mimsave_indexed: frames are (H, W) uint8 palette indices, got %s %s" % (f.dtype, f.shape))
+        im = Image.fromarray(np.ascontiguousarray(f), mode="P")
+        im.putpalette(pal)
+        ims.append(im)
+    if not ims:
+        raise ValueError("mimsave_indexed: no frames")
+    ims[0].save(path, save_all=True, append_images=ims[1:], duration=int(round(duration * 1000)), loop=loop, optimize=False)

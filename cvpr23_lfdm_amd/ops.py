@@ -1082,3 +1082,111 @@ def depthwise_down_planar(x, weight, stride, pad_lo, pad_hi):
     lib.check(lib.lfdm_depthwise_down_planar_f32(_p(x), _p(wt), _p(out), n, c, h, w, k, pad_lo, pad_hi, stride, _stream(lib)),
               "lfdm_depthwise_down_planar_f32")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# uint8 preview strips of a sampled video (csrc/render.hip)
+# ---------------------------------------------------------------------------------------------
+PANELS = ("source", "out", "warped", "flow", "conf")          # LFDM_PANEL_* = the position in this tuple
+_ident_cache = {}
+
+
+def _chk_dev(lib, *tensors):
+    """_chk's device rule for operands that are not all fp32 / int32."""
+    for t in tensors:
+        if t is None:
+            continue
+        if lib.kind == "hip" and not t.is_cuda:
+            raise RuntimeError("lfdm ops need tensors on the GPU (no CPU fallback exists)")
+        if lib.kind == "emu" and t.is_cuda:
+            raise RuntimeError("emulation library needs CPU tensors")
+
+
+def _identity_table(s, device):
+    """torch.linspace(-1, 1, s), the call io_compat.get_grid makes, on `device` (made on the host, kept per size and device)."""
+    key = (int(s), str(device))
+    if key not in _ident_cache:
+        _ident_cache[key] = torch.linspace(-1.0, 1.0, int(s)).to(device)
+    return _ident_cache[key]
+
+
+def flow_to_color_u8(grid, out=None):
+    """lfdm_flow_color_u8: grid (B, 2, T, s, s) fp32 sampling grid (x, y) -> (B * T, s, s, 3) uint8, io_compat.flow_to_color(grid -
+    identity) of every frame (what misc.flow2fig colours), the identity from torch.linspace(-1, 1, s).  grid may be the first two
+    channels of a (B, 3, T, s, s) latent: only the batch stride may differ from a contiguous tensor's."""
+    lib = _lib()
+    _chk_dev(lib, grid, out)
+    if grid.dtype != torch.float32 or grid.dim() != 5 or grid.shape[1] != 2 or grid.shape[3] != grid.shape[4]:
+        raise ValueError("flow_to_color_u8: grid must be a float32 (B, 2, T, s, s) tensor, got %s %s" % (grid.dtype, tuple(grid.shape)))
+    b, _, t, s, _ = grid.shape
+    if s % 4 != 0:
+        raise ValueError("flow_to_color_u8: s = %d is not a multiple of 4" % s)
+    if tuple(grid.stride()[1:]) != (t * s * s, s * s, s, 1) or (b > 1 and grid.stride(0) < 2 * t * s * s):
+        grid = grid.contiguous()
+    stride = grid.stride(0) if b > 1 else 2 * t * s * s
+    if out is None:
+        out = torch.empty(b * t, s, s, 3, dtype=torch.uint8, device=grid.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (b * t, s, s, 3) or not out.is_contiguous() or out.device != grid.device:
+        raise ValueError("flow_to_color_u8: out must be a contiguous uint8 (%d, %d, %d, 3) tensor on grid's device" % (b * t, s, s))
+    lib.check(lib.lfdm_flow_color_u8(_p(grid), stride, _p(_identity_table(s, grid.device)), _p(out), b, t, s, _stream(lib)),
+              "lfdm_flow_color_u8")
+    return out
+
+
+def render_strip(*, source=None, out_vid=None, warped_vid=None, flow_color=None, conf=None, mean=(0.0, 0.0, 0.0),
+                 panels=PANELS, indexed=False, out=None):
+    """lfdm_render_strip_u8: the per-frame panel strip of the demo scripts, (B, T, S, P * S, 3) uint8 RGB - or (B, T, S, P * S) uint8
+    indices into io_compat.STRIP_PALETTE when indexed - for the ordered panel names in `panels` (from ops.PANELS).  Operands (only those
+    of the listed panels are needed): source (B, 3, S, S), out_vid / warped_vid (B, 3, T, S, S), conf (B, 1, T, s, s) fp32,
+    flow_color (B * T, s, s, 3) uint8 from flow_to_color_u8; S = 4 s.  Image panels are io_compat.sample_img with `mean`, conf is
+    io_compat.conf2fig, flow is the colour image resized like io_compat.flow2fig does - to the byte."""
+    lib = _lib()
+    panels = tuple(panels)
+    for p in panels:
+        if p not in PANELS:
+            raise ValueError("render_strip: unknown panel %r (one of %s)" % (p, ", ".join(PANELS)))
+    if not 1 <= len(panels) <= 8:
+        raise ValueError("render_strip: 1 to 8 panels, got %d" % len(panels))
+    ops_by_name = dict(source=source, out=out_vid, warped=warped_vid, flow=flow_color, conf=conf)
+    used = {p: ops_by_name[p] for p in panels}
+    for p, t in used.items():
+        if t is None:
+            raise ValueError("render_strip: panel %r needs its operand" % p)
+    _chk_dev(lib, out, *used.values())
+    # batch, frame count and size: from a video operand, else conf, else flow_color + source (given ones count, listed or not)
+    vid = out_vid if out_vid is not None else warped_vid
+    if vid is not None and vid.dim() == 5:
+        b, frames, size = vid.shape[0], vid.shape[2], vid.shape[-1]
+    elif conf is not None and conf.dim() == 5:
+        b, frames, size = conf.shape[0], conf.shape[2], 4 * conf.shape[-1]
+    elif flow_color is not None and source is not None and flow_color.dim() == 4 and source.dim() == 4:
+        b, size = source.shape[0], 4 * flow_color.shape[1]
+        frames = flow_color.shape[0] // b
+    else:
+        raise ValueError("render_strip: the frame count needs out_vid, warped_vid or conf (or flow_color together with source)")
+    s = size // 4
+    want = dict(source=(b, 3, size, size), out=(b, 3, frames, size, size), warped=(b, 3, frames, size, size),
+                flow=(b * frames, s, s, 3), conf=(b, 1, frames, s, s))
+    for p, t in used.items():
+        dt = torch.uint8 if p == "flow" else torch.float32
+        if t.dtype != dt or tuple(t.shape) != want[p] or not t.is_contiguous():
+            raise ValueError("render_strip: %s must be a contiguous %s tensor of shape %s, got %s %s"
+                             % (p, dt, want[p], t.dtype, tuple(t.shape)))
+    if size != 4 * s or s % 4 != 0:
+        raise ValueError("render_strip: frame size %d must be 4 x a latent size that is a multiple of 4" % size)
+    mean = [float(m) for m in mean]
+    if len(mean) != 3:
+        raise ValueError("render_strip: mean has three channels")
+    dev = next(iter(used.values())).device
+    shape = (b, frames, size, len(panels) * size) + (() if indexed else (3,))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != dev:
+        raise ValueError("render_strip: out must be a contiguous uint8 %s tensor on the operands' device" % (shape,))
+    import numpy as np
+    add = (C.c_double * 3)(*(np.array(mean) / 255.0).tolist())          # io_compat.sample_img's `np.array(mean) / 255.0`
+    codes = (C.c_int * len(panels))(*[PANELS.index(p) for p in panels])
+    lib.check(lib.lfdm_render_strip_u8(_p(used.get("source")), _p(used.get("out")), _p(used.get("warped")), _p(used.get("flow")),
+                                       _p(used.get("conf")), add, codes, len(panels), int(bool(indexed)), _p(out), b, frames, size, s,
+                                       _stream(lib)), "lfdm_render_strip_u8")
+    return out

@@ -831,6 +831,37 @@ typedef struct lfdm_pack_wino_job {
 } lfdm_pack_wino_job;
 int lfdm_pack_wino_weights_multi_f32(const lfdm_pack_wino_job* jobs, int n_jobs, int total_blocks, lfdm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * uint8 preview strips of a sampled video (additive under ABI 12).  Replaces, on the device, what the reference's demo
+ * scripts do per frame on the host between sample_one_video and imageio.mimsave: misc.py:66-73 flow2fig (flow_vis.flow_to_color),
+ * misc.py:76-80 conf2fig, demo/demo_mug.py:26-32 sample_img and :124-143 the panel strip.  misc.py:44-63 grid2fig (a matplotlib line
+ * drawing) is not rendered here.
+ *
+ * lfdm_flow_color_u8: out (batch * frames, s, s, 3) uint8 = flow_to_color(grid - identity) per frame.  grid: planar (batch, 2, frames,
+ * s, s), channel 0 = x, contiguous within a batch element, batch elements batch_stride floats apart (so the first two channels of a
+ * (batch, 3, frames, s, s) latent can be passed as they are).  ident: s floats, torch.linspace(-1, 1, s) made by the caller - the
+ * subtraction is fp32 and must see the host's values.  Everything after the subtraction is fp64 in numpy's operation order; the maximum
+ * radius is taken per frame (wave shuffles + LDS, no atomics).  One workgroup per frame.  s % 4 == 0; out 16-byte aligned. */
+int lfdm_flow_color_u8(const float* grid, int64_t batch_stride, const float* ident, unsigned char* out, int batch, int frames, int s,
+                       lfdm_stream_t stream);
+/* lfdm_render_strip_u8: out (batch, frames, S, n_panels * S, 3) uint8 RGB, or with indexed != 0 (batch, frames, S, n_panels * S) uint8
+ * indices into the fixed 6x6x6 palette (index = 36 r + 6 g + b, level k = 51 k) under an 8x8 ordered dither:
+ *   level = (c * 320 + 255 * bayer[y & 7][x & 7] + 127) / 16320   (integer division; c the channel value 0 .. 255; x the strip column).
+ * panels: HOST array of n_panels (1 .. 8) LFDM_PANEL_* codes, left to right; only the operands of the listed panels are read, the others
+ * may be NULL.  source (batch, 3, S, S), out_vid / warped_vid (batch, 3, frames, S, S) planar fp32: byte = trunc(clamp(float(double(x) +
+ * mean_over_255[c]), 0, 1) * 255.f) (mean_over_255: HOST array of 3 doubles, mean / 255.0); flow_color: lfdm_flow_color_u8's output,
+ * resized s -> S bilinearly (align_corners = false, round half to even); conf (batch, 1, frames, s, s): nearest, trunc(conf * 255.f) on
+ * three channels.  NaN -> 0.  S == 4 * s, s % 4 == 0; out and the fp32 image operands 16-byte aligned.  Every store is a whole 16-byte
+ * segment. */
+#define LFDM_PANEL_SOURCE 0
+#define LFDM_PANEL_OUT 1
+#define LFDM_PANEL_WARPED 2
+#define LFDM_PANEL_FLOW 3
+#define LFDM_PANEL_CONF 4
+int lfdm_render_strip_u8(const float* source, const float* out_vid, const float* warped_vid, const unsigned char* flow_color,
+                         const float* conf, const double* mean_over_255, const int* panels, int n_panels, int indexed,
+                         unsigned char* out, int batch, int frames, int S, int s, lfdm_stream_t stream);
+
 /* Box calibration, not on the product path (bench.py prints it beside every timing; ABI version 7): `blocks` workgroups of four
  * wavefronts run `iters` x 4 independent v_mfma_f32_32x32x2_f32 (2 * 32 * 32 * 2 FLOP each, pseudo-random operands) and
  * record, per workgroup b, out[2b] = shader cycles and out[2b+1] = 100 MHz real-time ticks of the loop: effective clock (MHz) =

@@ -2,16 +2,20 @@
 """The reference's demo flow (demo/demo_mug.py:60-146, demo_mhad.py, demo_natops.py) on this framework: load LFAE + DM
 checkpoints, read one reference image, sample a 40-frame video per text prompt and write the five-panel GIF
 [source | generated | warped source | flow grid | occlusion].  Needs a GPU (liblfdm_hip.so; there is no CPU path).
+--render device renders that strip on the GPU (FlowDiffusion.render_sample; its fourth panel is the colour-coded flow of
+misc.flow2fig, not grid2fig's drawing) and --gif indexed writes its palette indices without PIL's per-frame quantisation.
 
     python tools/demo.py --config configs/lfae_128.yaml --lfae-ckpt RegionMM.pth --dm-ckpt flowdiff.pth \
         --bert /data/bert-base-cased --image face.jpg --text happiness anger --out demo_out
     python tools/demo.py --synthetic --total-frames 112 --overlap 4 --out demo_out      # a long video: three chained 40-frame windows
+    python tools/demo.py --synthetic --render device --gif indexed --out demo_out       # strip and palette indices made on the GPU
     python tools/demo.py --synthetic --out demo_out        # random-init weights, random image, fixed embedding:
                                                             # exercises the whole pipeline where no checkpoint exists
 """
 import argparse
 import os
 import sys
+import time
 import zlib
 
 import numpy as np
@@ -47,7 +51,20 @@ def build_parser():
     ap.add_argument("--overlap", type=int, default=8, help="latent frames two consecutive windows of --total-frames share")
     ap.add_argument("--use-ema", action="store_true",
                     help="sample from the averaged weights: the checkpoint's 'diffusion_ema' entry (tools/train_dm.py --ema-decay, DESIGN.md 4.4)")
+    ap.add_argument("--render", choices=("host", "device"), default="host",
+                    help="where the panel strip is made: host (default; io_compat.video_strip, per frame with numpy / matplotlib) or device "
+                         "(one rendering on the GPU and one copy; the fourth panel is then the colour-coded flow, DESIGN.md 4.5)")
+    ap.add_argument("--gif", choices=("rgb", "indexed"), default="rgb",
+                    help="rgb (default): RGB frames, PIL quantises each; indexed: the device's 6x6x6-palette indices (ordered dither) written "
+                         "as they are - needs --render device")
     return ap
+
+
+def check_args(args):
+    if args.gif == "indexed" and args.render != "device":
+        sys.exit("--gif indexed needs --render device: the palette indices are made by the device rendering")
+    if args.use_ema and (args.synthetic or not args.dm_ckpt):
+        sys.exit("--use-ema needs --dm-ckpt: a checkpoint with a 'diffusion_ema' entry")
 
 
 def dm_state(ck, use_ema, path="the checkpoint"):
@@ -62,8 +79,7 @@ def dm_state(ck, use_ema, path="the checkpoint"):
 
 def main():
     args = build_parser().parse_args()
-    if args.use_ema and (args.synthetic or not args.dm_ckpt):
-        sys.exit("--use-ema needs --dm-ckpt: a checkpoint with a 'diffusion_ema' entry")
+    check_args(args)
     if not torch.cuda.is_available():
         sys.exit("tools/demo.py needs a GPU: the sampling path is liblfdm_hip.so only")
     os.makedirs(args.out, exist_ok=True)
@@ -94,14 +110,29 @@ def main():
     ref = torch.from_numpy(np.asarray(img, np.float32) / 255.0).permute(2, 0, 1).unsqueeze(0).cuda()
     name = os.path.splitext(os.path.basename(args.image))[0] if args.image else "random"
     for i, text in enumerate(args.text):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
         model.set_sample_input(sample_img=ref, sample_text=[text])
         if args.total_frames > 0:
             model.sample_long_video(args.cond_scale, args.total_frames, overlap=args.overlap)
         else:
             model.sample_one_video(cond_scale=args.cond_scale)
         path = os.path.join(args.out, "%04d_%s_%s_%.2f.gif" % (i, text.replace(" ", "_"), name, args.cond_scale))
-        C.mimsave(path, C.video_strip(model, ref))
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        if args.render == "device":
+            frames = C.video_strip_device(model, ref, indexed=args.gif == "indexed")
+        else:
+            frames = C.video_strip(model, ref)
+        t2 = time.perf_counter()
+        if args.gif == "indexed":
+            C.mimsave_indexed(path, frames)
+        else:
+            C.mimsave(path, frames)
+        t3 = time.perf_counter()
         print(path)
+        print("%s: sample %.3f s, render (%s) %.3f s, write (%s) %.3f s" % (os.path.basename(path), t1 - t0, args.render, t2 - t1,
+                                                                           args.gif, t3 - t2))
 
 
 if __name__ == "__main__":
