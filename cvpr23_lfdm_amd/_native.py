@@ -221,6 +221,11 @@ _SIGNATURES = {
     "lfdm_flow_color_u8": (i32, [f32p, i64, f32p, C.c_void_p, i32, i32, i32, stream_t]),
     "lfdm_render_strip_u8": (i32, [f32p, f32p, f32p, C.c_void_p, f32p, C.POINTER(C.c_double), C.POINTER(i32), i32, i32, C.c_void_p,
                                    i32, i32, i32, i32, stream_t]),
+    # ---- paired video metrics (additive, ABI stays 12)
+    "lfdm_video_metrics_ws_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "lfdm_video_metrics": (i32, [f32p, f32p, C.POINTER(C.c_double), i32, C.c_void_p, i32, i32, i32, i32, i32, C.c_void_p, sz, stream_t]),
+    "lfdm_flow_metrics": (i32, [f32p, i64, f32p, i64, f32p, f32p, C.c_void_p, i32, i32, i32, stream_t]),
+    "lfdm_psnr_f64": (i32, [C.c_void_p, C.c_void_p, i64, stream_t]),
     "lfdm_depthwise_down_planar_f32": (i32, [f32p, f32p, f32p, i32, i32, i32, i32, i32, i32, i32, i32, stream_t]),
     "lfdm_upsample2_pad_cl_f32": (i32, [f32p, f32p, i32, i32, i32, i32, i32, i32, i32, stream_t]),
     "lfdm_layernorm_bwd_ws_bytes": (sz, [i64, i32]),

@@ -1190,3 +1190,113 @@ def render_strip(*, source=None, out_vid=None, warped_vid=None, flow_color=None,
                                        _p(used.get("conf")), add, codes, len(panels), int(bool(indexed)), _p(out), b, frames, size, s,
                                        _stream(lib)), "lfdm_render_strip_u8")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# paired video metrics
+# ---------------------------------------------------------------------------------------------
+
+METRIC_DOMAINS = ("raw", "unit", "uint8")          # LFDM_METRIC_* = the position in this tuple
+SSIM_WINDOW = 11
+
+
+def _metric_table(what, out, shape, device):
+    if out is None:
+        return torch.empty(shape, dtype=torch.float64, device=device)
+    if out.dtype != torch.float64 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != device:
+        raise ValueError("%s: out must be a contiguous float64 %s tensor on the operands' device" % (what, shape))
+    return out
+
+
+def video_metrics(a, b, *, mean=(0, 0, 0), domain="unit", out=None):
+    """lfdm_video_metrics: a, b (B, C, T, H, W) fp32 videos -> (B, T, 3) float64, [l1, mse, ssim] of every frame averaged over its
+    channels (1 <= C <= 4; H, W >= 11, any value).  domain: "raw" the values as they are; "unit" io_compat.sample_img before its
+    scaling, clamp(float32(x + mean / 255), 0, 1); "uint8" the bytes the demo writes, over 255.  SSIM is Wang et al.'s (11-tap Gaussian,
+    sigma 1.5, valid interior only) with data range 1 in every domain, "raw" included.  All arithmetic is fp64 in a fixed order: a
+    frame's numbers are bit-identical from run to run and whatever the batch around it."""
+    lib = _lib()
+    for name, t in (("a", a), ("b", b)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError("video_metrics: %s must be a float32 tensor, got %s" % (name, getattr(t, "dtype", type(t))))
+    if domain not in METRIC_DOMAINS:
+        raise ValueError("video_metrics: unknown domain %r (one of %s)" % (domain, ", ".join(METRIC_DOMAINS)))
+    if a.dim() != 5 or tuple(a.shape) != tuple(b.shape):
+        raise ValueError("video_metrics: a and b must be (B, C, T, H, W) tensors of one shape, got %s and %s"
+                         % (tuple(a.shape), tuple(b.shape)))
+    bsz, ch, frames, h, w = a.shape
+    if bsz < 1 or frames < 1 or not 1 <= ch <= 4:
+        raise ValueError("video_metrics: needs B, T >= 1 and 1 <= C <= 4, got %s" % (tuple(a.shape),))
+    if h < SSIM_WINDOW or w < SSIM_WINDOW:
+        raise ValueError("video_metrics: H, W must be at least %d (the SSIM window), got %s" % (SSIM_WINDOW, tuple(a.shape)))
+    mean = [float(m) for m in mean]
+    if len(mean) != ch:
+        raise ValueError("video_metrics: mean has %d values for %d channels (shape %s)" % (len(mean), ch, tuple(a.shape)))
+    if a.device != b.device:
+        raise ValueError("video_metrics: a is on %s, b on %s" % (a.device, b.device))
+    _chk_dev(lib, a, b, out)
+    out = _metric_table("video_metrics", out, (bsz, frames, 3), a.device)
+    a = a if a.is_contiguous() else a.contiguous()
+    b = b if b.is_contiguous() else b.contiguous()
+    ws_bytes = lib.lfdm_video_metrics_ws_bytes(bsz, ch, frames, h, w)
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=a.device)
+    import numpy as np
+    add = (C.c_double * ch)(*(np.array(mean) / 255.0).tolist())          # io_compat.sample_img's `np.array(mean) / 255.0`
+    lib.check(lib.lfdm_video_metrics(_p(a), _p(b), add, METRIC_DOMAINS.index(domain), _p(out), bsz, ch, frames, h, w, _p(ws), ws_bytes,
+                                     _stream(lib)), "lfdm_video_metrics")
+    return out
+
+
+def _flow_grid(g):
+    """(tensor, batch stride) of a (B, 2, T, s, s) grid: copied only when more than its batch stride differs from a contiguous one's."""
+    b, _, t, s, _ = g.shape
+    if tuple(g.stride()[1:]) != (t * s * s, s * s, s, 1) or (b > 1 and g.stride(0) < 2 * t * s * s):
+        g = g.contiguous()
+    return g, (g.stride(0) if b > 1 else 2 * t * s * s)
+
+
+def flow_metrics(grid_a, grid_b, conf_a=None, conf_b=None, out=None):
+    """lfdm_flow_metrics: two sampling grids (B, 2, T, s, s) fp32 (x, y) and optionally their confidences (B, 1, T, s, s) ->
+    (B, T, 2) float64: [mean end-point error sqrt(dx^2 + dy^2) in the grids' normalised units, mean |conf_a - conf_b| (0 without
+    confidences)] per frame.  A grid may be the first two channels of a (B, 3, T, s, s) latent: only the batch stride may differ
+    from a contiguous tensor's.  fp64 in a fixed order, like video_metrics."""
+    lib = _lib()
+    if (conf_a is None) != (conf_b is None):
+        raise ValueError("flow_metrics: give both confidences or neither")
+    for name, t in (("grid_a", grid_a), ("grid_b", grid_b), ("conf_a", conf_a), ("conf_b", conf_b)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32):
+            raise TypeError("flow_metrics: %s must be a float32 tensor, got %s" % (name, getattr(t, "dtype", type(t))))
+    if grid_a.dim() != 5 or grid_a.shape[1] != 2 or grid_a.shape[3] != grid_a.shape[4] or tuple(grid_a.shape) != tuple(grid_b.shape):
+        raise ValueError("flow_metrics: grids must be (B, 2, T, s, s) tensors of one shape, got %s and %s"
+                         % (tuple(grid_a.shape), tuple(grid_b.shape)))
+    b, _, t, s, _ = grid_a.shape
+    if b < 1 or t < 1 or not 1 <= s <= 4096:
+        raise ValueError("flow_metrics: needs B, T >= 1 and 1 <= s <= 4096, got %s" % (tuple(grid_a.shape),))
+    for name, c in (("conf_a", conf_a), ("conf_b", conf_b)):
+        if c is not None and tuple(c.shape) != (b, 1, t, s, s):
+            raise ValueError("flow_metrics: %s must be %s, got %s" % (name, (b, 1, t, s, s), tuple(c.shape)))
+    for x in (grid_b, conf_a, conf_b):
+        if x is not None and x.device != grid_a.device:
+            raise ValueError("flow_metrics: operands on %s and %s" % (grid_a.device, x.device))
+    _chk_dev(lib, grid_a, grid_b, conf_a, conf_b, out)
+    out = _metric_table("flow_metrics", out, (b, t, 2), grid_a.device)
+    grid_a, stride_a = _flow_grid(grid_a)
+    grid_b, stride_b = _flow_grid(grid_b)
+    if conf_a is not None:
+        conf_a = conf_a if conf_a.is_contiguous() else conf_a.contiguous()
+        conf_b = conf_b if conf_b.is_contiguous() else conf_b.contiguous()
+    lib.check(lib.lfdm_flow_metrics(_p(grid_a), stride_a, _p(grid_b), stride_b, _p(conf_a), _p(conf_b), _p(out), b, t, s, _stream(lib)),
+              "lfdm_flow_metrics")
+    return out
+
+
+def psnr(mse_table, out=None):
+    """lfdm_psnr_f64: 10 log10(1 / mse) elementwise over a float64 table (data range 1), inf where mse == 0."""
+    lib = _lib()
+    if not isinstance(mse_table, torch.Tensor) or mse_table.dtype != torch.float64:
+        raise TypeError("psnr: the table must be a float64 tensor, got %s" % getattr(mse_table, "dtype", type(mse_table)))
+    _chk_dev(lib, mse_table, out)
+    src = mse_table if mse_table.is_contiguous() else mse_table.contiguous()
+    out = _metric_table("psnr", out, tuple(src.shape), src.device)
+    if src.numel():
+        lib.check(lib.lfdm_psnr_f64(_p(src), _p(out), src.numel(), _stream(lib)), "lfdm_psnr_f64")
+    return out

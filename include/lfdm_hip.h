@@ -862,6 +862,38 @@ int lfdm_render_strip_u8(const float* source, const float* out_vid, const float*
                          const float* conf, const double* mean_over_255, const int* panels, int n_panels, int indexed,
                          unsigned char* out, int batch, int frames, int S, int s, lfdm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Paired, full-reference metrics of two videos (additive under ABI 12): per frame and on the device what an evaluation
+ * script would otherwise copy to the host for (LFAE/test_flowautoenc_*.py: the L1 behind out_loss / warp_loss).
+ *
+ * lfdm_video_metrics: a, b planar fp32 (batch, channels, frames, h, w), contiguous; out (batch, frames, 3) float64 = [l1, mse, ssim] of
+ * every frame, each the mean over the frame's channels.  1 <= channels <= 4; h, w >= 11, any value.  The value domain:
+ *   LFDM_METRIC_RAW    the operands as they are;
+ *   LFDM_METRIC_UNIT   v = clamp(float(double(x) + mean_over_255[c]), 0, 1) (io_compat.sample_img before its scaling);
+ *   LFDM_METRIC_UINT8  trunc(float(v * 255.f)) / 255: the bytes lfdm_render_strip_u8 writes, NaN -> 0.
+ * mean_over_255: HOST array of `channels` doubles, mean / 255.0 (may be NULL for RAW).  l1 = mean |a - b| and mse = mean (a - b)^2 over the
+ * whole frame.  ssim: Wang et al. 2004 - separable 11-tap Gaussian window, sigma 1.5, weights normalised to sum 1 per axis; variances and
+ * covariance E[xy] - E[x] E[y]; C1 = 0.01^2, C2 = 0.03^2 (data range 1 in EVERY domain, RAW included); the map on the valid interior
+ * (h - 10) x (w - 10) only, averaged.  Operands are converted exactly to fp64 and all arithmetic is fp64.  No atomics: per-tile sums go
+ * to ws (lfdm_video_metrics_ws_bytes bytes, 8-byte aligned, need not be zeroed) and a second launch adds them in tile order, so a
+ * frame's three numbers are bit-identical from run to run and do not depend on batch, frames or the frame's place among them. */
+#define LFDM_METRIC_RAW 0
+#define LFDM_METRIC_UNIT 1
+#define LFDM_METRIC_UINT8 2
+#define LFDM_METRIC_MAX_CHANNELS 4
+size_t lfdm_video_metrics_ws_bytes(int batch, int channels, int frames, int h, int w);
+int lfdm_video_metrics(const float* a, const float* b, const double* mean_over_255, int domain, double* out, int batch, int channels,
+                       int frames, int h, int w, void* ws, size_t ws_bytes, lfdm_stream_t stream);
+/* lfdm_flow_metrics: out (batch, frames, 2) float64 = [mean end-point error sqrt(dx^2 + dy^2) of two sampling grids in their normalised
+ * units, mean |conf_a - conf_b|] per latent frame.  grid_a / grid_b: planar (batch, 2, frames, s, s), channel 0 = x, batch elements
+ * stride_a / stride_b floats apart (as lfdm_flow_color_u8: the first two channels of a (batch, 3, frames, s, s) latent pass as they
+ * are); conf_a / conf_b (batch, 1, frames, s, s) contiguous, both or neither - without them the second number is 0.  fp64, no atomics,
+ * one workgroup per frame in a fixed order. */
+int lfdm_flow_metrics(const float* grid_a, int64_t stride_a, const float* grid_b, int64_t stride_b, const float* conf_a,
+                      const float* conf_b, double* out, int batch, int frames, int s, lfdm_stream_t stream);
+/* out[i] = 10 log10(1 / mse[i]) over n doubles (data range 1), +inf where mse[i] == 0. */
+int lfdm_psnr_f64(const double* mse, double* out, int64_t n, lfdm_stream_t stream);
+
 /* Box calibration, not on the product path (bench.py prints it beside every timing; ABI version 7): `blocks` workgroups of four
  * wavefronts run `iters` x 4 independent v_mfma_f32_32x32x2_f32 (2 * 32 * 32 * 2 FLOP each, pseudo-random operands) and
  * record, per workgroup b, out[2b] = shader cycles and out[2b+1] = 100 MHz real-time ticks of the loop: effective clock (MHz) =

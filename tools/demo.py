@@ -77,6 +77,38 @@ def dm_state(ck, use_ema, path="the checkpoint"):
     return ck["diffusion_ema"]
 
 
+def make_model(args, *, steps=None, sampler=None, conv_precision=None, use_ema=None, need_dm=True):
+    """The FlowDiffusion of the parsed options with its weights loaded, on the host (demo_mug.py:80-97); tools/eval.py builds its models
+    here too.  steps / sampler / conv_precision / use_ema override the options of the same names; need_dm=False accepts a run without
+    --dm-ckpt (an LFAE-only evaluation)."""
+    steps = args.steps if steps is None else steps
+    sampler = args.sampler if sampler is None else sampler
+    conv_precision = args.conv_precision if conv_precision is None else conv_precision
+    use_ema = args.use_ema if use_ema is None else use_ema
+    model = FlowDiffusion(is_train=False, img_size=args.size // 4, num_frames=args.frames, sampling_timesteps=steps,
+                          null_cond_prob=0.1, config_pth=args.config, pretrained_pth=args.lfae_ckpt,
+                          bert_path=None if args.synthetic else args.bert, conv_precision=conv_precision,
+                          sampler=sampler)          # demo_mug.py:80-88
+    if args.synthetic:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import synth
+        model.unet.load_state_dict(synth.unet_state())
+        model.generator.load_state_dict(synth.generator_state())
+        emb = {}
+
+        def encode(texts):          # a fixed embedding per prompt, seeded by the prompt
+            for t in texts:
+                if t not in emb:
+                    emb[t] = torch.randn(1, 768, generator=torch.Generator().manual_seed(zlib.crc32(t.encode())))
+            return torch.cat([emb[t] for t in texts])
+        model.diffusion.text_encoder = encode
+    elif args.dm_ckpt:
+        model.diffusion.load_state_dict(dm_state(torch.load(args.dm_ckpt, map_location="cpu"), use_ema, args.dm_ckpt))   # demo_mug.py:93-97
+    elif need_dm:
+        sys.exit("give --dm-ckpt (and --lfae-ckpt), or --synthetic")
+    return model
+
+
 def main():
     args = build_parser().parse_args()
     check_args(args)
@@ -86,21 +118,7 @@ def main():
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
 
-    model = FlowDiffusion(is_train=False, img_size=args.size // 4, num_frames=args.frames, sampling_timesteps=args.steps,
-                          null_cond_prob=0.1, config_pth=args.config, pretrained_pth=args.lfae_ckpt,
-                          bert_path=None if args.synthetic else args.bert, conv_precision=args.conv_precision,
-                          sampler=args.sampler)          # demo_mug.py:80-88
-    if args.synthetic:
-        sys.path.insert(0, os.path.join(ROOT, "tests"))
-        import synth
-        model.unet.load_state_dict(synth.unet_state())
-        model.generator.load_state_dict(synth.generator_state())
-        emb = {t: torch.randn(1, 768, generator=torch.Generator().manual_seed(zlib.crc32(t.encode()))) for t in args.text}
-        model.diffusion.text_encoder = lambda texts: torch.cat([emb[t] for t in texts])
-    elif args.dm_ckpt:
-        model.diffusion.load_state_dict(dm_state(torch.load(args.dm_ckpt, map_location="cpu"), args.use_ema, args.dm_ckpt))   # demo_mug.py:93-97
-    else:
-        sys.exit("give --dm-ckpt (and --lfae-ckpt), or --synthetic")
+    model = make_model(args)
     model.cuda().eval()
 
     if args.image:
