@@ -156,16 +156,17 @@ __global__ __launch_bounds__(64) void attention_kernel(const float* __restrict__
     for (int tj = 0; tj < NT; ++tj)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float e = (tj * 16 + lq * 4 + r) < L ? expf(st[ti][tj][r] - m) : 0.f;
+        const float e = (tj * 16 + lq * 4 + r) < L ? fast_exp(st[ti][tj][r] - m) : 0.f;
         st[ti][tj][r] = e;
         sum += e;
       }
     sum += __shfl_xor(sum, 16);
     sum += __shfl_xor(sum, 32);
+    const float inv = fast_rcp(sum);               // one reciprocal per query (lfdm_device.h fast_exp / fast_rcp)
 #pragma unroll
     for (int tj = 0; tj < NT; ++tj)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) st[ti][tj][r] = st[ti][tj][r] / sum;
+      for (int r = 0; r < 4; ++r) st[ti][tj][r] = st[ti][tj][r] * inv;
   }
 
   // ---- O = P V ----
@@ -259,10 +260,10 @@ __global__ __launch_bounds__(256) void linattn_context_kernel(const float* __res
     for (int u = 0; u < 2; ++u) {
       const int nl = ln + 32 * u;
       const bool ok = n0 + nl < hw;
-      ek[nl][4 * lc4 + 0] = ok ? expf(rk[u].x - kmax[4 * lc4 + 0]) : 0.f;
-      ek[nl][4 * lc4 + 1] = ok ? expf(rk[u].y - kmax[4 * lc4 + 1]) : 0.f;
-      ek[nl][4 * lc4 + 2] = ok ? expf(rk[u].z - kmax[4 * lc4 + 2]) : 0.f;
-      ek[nl][4 * lc4 + 3] = ok ? expf(rk[u].w - kmax[4 * lc4 + 3]) : 0.f;
+      ek[nl][4 * lc4 + 0] = ok ? fast_exp(rk[u].x - kmax[4 * lc4 + 0]) : 0.f;
+      ek[nl][4 * lc4 + 1] = ok ? fast_exp(rk[u].y - kmax[4 * lc4 + 1]) : 0.f;
+      ek[nl][4 * lc4 + 2] = ok ? fast_exp(rk[u].z - kmax[4 * lc4 + 2]) : 0.f;
+      ek[nl][4 * lc4 + 3] = ok ? fast_exp(rk[u].w - kmax[4 * lc4 + 3]) : 0.f;
       *reinterpret_cast<float4*>(&vv[nl][4 * lc4]) = rv[u];
     }
     __syncthreads();
@@ -280,10 +281,11 @@ __global__ __launch_bounds__(256) void linattn_context_kernel(const float* __res
     __syncthreads();
   }
   float* dst = ctx_out + ((int64_t)blockIdx.x * DH + d) * DH + e0;
-  dst[0] = acc[0] / ssum;
-  dst[1] = acc[1] / ssum;
-  dst[2] = acc[2] / ssum;
-  dst[3] = acc[3] / ssum;
+  const float inv = fast_rcp(ssum);
+  dst[0] = acc[0] * inv;
+  dst[1] = acc[1] * inv;
+  dst[2] = acc[2] * inv;
+  dst[3] = acc[3] * inv;
 }
 
 // grid (ceil(hw/32), n_frames); thread = (token, head)
@@ -315,12 +317,12 @@ __global__ __launch_bounds__(256) void linattn_output_kernel(const float* __rest
   float sum = 0.f;
 #pragma unroll
   for (int i = 0; i < DH; ++i) {
-    q[i] = expf(q[i] - m);
+    q[i] = fast_exp(q[i] - m);
     sum += q[i];
   }
-  const float scale = 0.17677669529663687f;
+  const float scale = 0.17677669529663687f * fast_rcp(sum);
 #pragma unroll
-  for (int i = 0; i < DH; ++i) q[i] = q[i] / sum * scale;
+  for (int i = 0; i < DH; ++i) q[i] = q[i] * scale;
   float* op = out + row * OUT_LD + h * DH;
   const float* ch = cs + h * CS;
 #pragma unroll

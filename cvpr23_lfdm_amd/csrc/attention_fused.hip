@@ -30,12 +30,6 @@ constexpr int HEADS = 8;
 constexpr int DH = 32;
 constexpr int OUT_LD = HEADS * DH;      // 256
 
-#if defined(LFDM_EMU_BUILD)
-static inline float fast_exp(float x) { return expf(x); }
-#else
-__device__ __forceinline__ float fast_exp(float x) { return __expf(x); }      // v_exp_f32(x * log2 e)
-#endif
-
 // Attention of one (sequence, head) from operand-layout fragments (see the header comment): scores transposed,
 // softmax in registers, P V, store.  qf/kf[ti][4*fi + r] = feature 16*fi + 4*lq + r of token 16*ti + l15 (q scaled and
 // rotated, k rotated); vf[half][4*ti + r] = v[token 16*ti + 4*lq + r][16*half + l15].
@@ -59,8 +53,8 @@ __device__ __forceinline__ void attend_store(const float (&qf)[NT][8], const flo
       st[ti][tj] = acc;
     }
   // VALU diet (round 4; the head loop spends as many issue cycles outside the matrix pipe as inside it: 39 IEEE divisions, 36 expf
-  // expansions per head): exp is the hardware exponential (v_exp_f32 on x * log2 e: the arguments are <= 0, the
-  // result within 2 ulp of expf), and the normalisation multiplies by ONE reciprocal per query instead of dividing every probability.
+  // expansions per head): exp is the hardware exponential (lfdm_device.h fast_exp: the arguments are <= 0; error figures there),
+  // and the normalisation multiplies by ONE reciprocal per query instead of dividing every probability.
 #pragma unroll
   for (int ti = 0; ti < NT; ++ti) {
     const int qt = ti * 16 + l15;                     // this lane's query token

@@ -317,7 +317,7 @@ __global__ __launch_bounds__(256) void linattn_lowres_kernel(const float* __rest
     const float mx = kmax[d];
     float s = 0.f;
     for (int n = part; n < hw; n += 8) {
-      const float e = expf(qkv[n * LDQ + DH + d] - mx);
+      const float e = fast_exp(qkv[n * LDQ + DH + d] - mx);
       qkv[n * LDQ + DH + d] = e;
       s += e;
     }
@@ -340,8 +340,8 @@ __global__ __launch_bounds__(256) void linattn_lowres_kernel(const float* __rest
       const float4 v4 = *reinterpret_cast<const float4*>(qkv + n * LDQ + 2 * DH + e0);
       a0 = fmaf(e, v4.x, a0); a1 = fmaf(e, v4.y, a1); a2 = fmaf(e, v4.z, a2); a3 = fmaf(e, v4.w, a3);
     }
-    const float ss = ksum[d];
-    *reinterpret_cast<float4*>(&ctx[d][e0]) = make_float4(a0 / ss, a1 / ss, a2 / ss, a3 / ss);
+    const float ss = fast_rcp(ksum[d]);
+    *reinterpret_cast<float4*>(&ctx[d][e0]) = make_float4(a0 * ss, a1 * ss, a2 * ss, a3 * ss);
   }
   // ---- q softmax over the 32 features of a pixel (8 lanes per pixel, four features each), in place, scaled ----
   for (int n0 = 0; n0 < hw; n0 += 32) {             // (uniform trip count: the shuffles below involve every lane of a wavefront)
@@ -350,10 +350,11 @@ __global__ __launch_bounds__(256) void linattn_lowres_kernel(const float* __rest
     float4 q4 = *reinterpret_cast<const float4*>(qkv + n * LDQ + 4 * (tid & 7));
     float m = fmaxf(fmaxf(q4.x, q4.y), fmaxf(q4.z, q4.w));
     m = fmaxf(m, __shfl_xor(m, 1)); m = fmaxf(m, __shfl_xor(m, 2)); m = fmaxf(m, __shfl_xor(m, 4));
-    q4.x = expf(q4.x - m); q4.y = expf(q4.y - m); q4.z = expf(q4.z - m); q4.w = expf(q4.w - m);
+    q4.x = fast_exp(q4.x - m); q4.y = fast_exp(q4.y - m); q4.z = fast_exp(q4.z - m); q4.w = fast_exp(q4.w - m);
     float s = (q4.x + q4.y) + (q4.z + q4.w);
     s += __shfl_xor(s, 1); s += __shfl_xor(s, 2); s += __shfl_xor(s, 4);
-    q4.x = q4.x / s * ATT_SCALE; q4.y = q4.y / s * ATT_SCALE; q4.z = q4.z / s * ATT_SCALE; q4.w = q4.w / s * ATT_SCALE;
+    s = ATT_SCALE * fast_rcp(s);
+    q4.x *= s; q4.y *= s; q4.z *= s; q4.w *= s;
     if (live) *reinterpret_cast<float4*>(qkv + n * LDQ + 4 * (tid & 7)) = q4;
   }
   __syncthreads();
@@ -473,19 +474,20 @@ __global__ __launch_bounds__(256) void attn_lowres_kernel(const float* __restric
     for (int tj = 0; tj < NT; ++tj)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float e = (tj * 16 + lq * 4 + r) < L ? expf(st[tj][r] - m) : 0.f;
+        const float e = (tj * 16 + lq * 4 + r) < L ? fast_exp(st[tj][r] - m) : 0.f;
         st[tj][r] = e;
         sum += e;
       }
     sum += __shfl_xor(sum, 16);
     sum += __shfl_xor(sum, 32);
+    const float inv = fast_rcp(sum);
     // O = P V: B operand = v[token 16*tj + 4*lq + r][16*half + l15]
     f32x4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = o0;
 #pragma unroll
     for (int tj = 0; tj < NT; ++tj)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float p = st[tj][r] / sum;
+        const float p = st[tj][r] * inv;
         const float* vr = qkv + (16 * tj + 4 * lq + r) * LDQ + 2 * DH;
         o0 = mfma_16x16x4(p, vr[l15], o0);
         o1 = mfma_16x16x4(p, vr[16 + l15], o1);

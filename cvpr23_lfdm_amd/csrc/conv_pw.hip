@@ -275,8 +275,8 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(lfdm_conv_params p, int gx
         float4 rr = pre_r[g * TN + j];
         if (p.res_gn_partial) {
           const float4 ga = *reinterpret_cast<const float4*>(s_ga + col - n0), gb = *reinterpret_cast<const float4*>(s_gb + col - n0);
-          rr.x = siluf_(fmaf(rr.x, ga.x, gb.x)); rr.y = siluf_(fmaf(rr.y, ga.y, gb.y));
-          rr.z = siluf_(fmaf(rr.z, ga.z, gb.z)); rr.w = siluf_(fmaf(rr.w, ga.w, gb.w));
+          rr.x = silu_fast_(fmaf(rr.x, ga.x, gb.x)); rr.y = silu_fast_(fmaf(rr.y, ga.y, gb.y));
+          rr.z = silu_fast_(fmaf(rr.z, ga.z, gb.z)); rr.w = silu_fast_(fmaf(rr.w, ga.w, gb.w));
         }
         v.x += bb.x + rr.x; v.y += bb.y + rr.y; v.z += bb.z + rr.z; v.w += bb.w + rr.w;
       }

@@ -293,6 +293,19 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m));
   return v;
 }
+// exp of a NON-POSITIVE argument (softmax terms exp(x - max), running-max rescales) on the hardware exponential: v_exp_f32(x * log2 e).
+// The rounding of x * log2 e grows with |x|: against expf, 1.5 ulp on [-1, 0], 8.5 ulp on [-10, -1], ~30 ulp on [-30, -10] (checked on the
+// CPU) - relative errors of 4e-6 on terms below e^-10 of their row's largest, harmless for a softmax, but NOT "within 2 ulp".  A huge
+// negative argument (-3e38 - m, the first running-max rescale) overflows to -inf in the product and gives exactly 0.  fast_rcp is
+// v_rcp_f32 (1 ulp): ONE reciprocal per softmax row, multiplied into the probabilities, instead of an IEEE division per element.
+// The emulator build keeps expf and the division.
+#if defined(LFDM_EMU_BUILD)
+static inline float fast_exp(float x) { return expf(x); }
+static inline float fast_rcp(float x) { return 1.0f / x; }
+#else
+__device__ __forceinline__ float fast_exp(float x) { return __expf(x); }
+__device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
+#endif
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 __device__ __forceinline__ float siluf_(float x) { return x / (1.0f + expf(-x)); }
 

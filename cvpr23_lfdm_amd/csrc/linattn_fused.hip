@@ -133,13 +133,13 @@ __global__ __launch_bounds__(64, 3) void linattn_fused_ctx_kernel(const float* _
     }
     m = fmaxf(m, __shfl_xor(m, 32));
     const float m_new = fmaxf(m_run, m);
-    const float alpha = expf(m_run - m_new);               // 0 for the first tile (m_run = -3e38)
+    const float alpha = fast_exp(m_run - m_new);               // 0 for the first tile (m_run = -3e38)
     float ssum = 0.f;
     float e[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int tok = t0 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-      e[r] = tok < n1 ? expf(ka[r] - m_new) : 0.f;
+      e[r] = tok < n1 ? fast_exp(ka[r] - m_new) : 0.f;
       ssum += e[r];
     }
     ssum += __shfl_xor(ssum, 32);
@@ -161,12 +161,29 @@ __global__ __launch_bounds__(64, 3) void linattn_fused_ctx_kernel(const float* _
 }
 
 // ---- B: grid (n_frames*8), 256 threads: ctx[d][e] merged over the splits ----
+// FOLD (lfdm_linear_attention_fused_out_cl_f32): the merged context stays in LDS and the kernel emits to_out folded into it,
+//   Mt_h[c][d] = sum_e Wout[c][32 h + e] ctx_h[d][e]      (64 x 32 per (frame, head); Y = (q~ ctx) Wout_h^T = q~ (ctx Wout_h^T)),
+// in the A-operand order of pass C': [frame][head][2 cb][4 quads][64 lanes = 32 kh + c_local][4] <- Mt[32 cb + c_local][8 quad + 4 kh + 0..3].
+// Thread (quad, kh, c_local) = tid owns the two float4 (cb = 0, 1) at float4 index 256 cb + tid: 256 fmaf, e ascending - a fixed order.  Its 16
+// float4 of wout (packed order, 512 contiguous bytes per instruction and half-wave) are requested before the partials.
+template <bool FOLD>
 __global__ __launch_bounds__(256) void linattn_fused_merge_kernel(const float* __restrict__ part, int nsplit,
-                                                                  float* __restrict__ ctx_out) {
+                                                                  float* __restrict__ ctx_out, const float* __restrict__ wout) {
   constexpr int MAXS = 64;
   __shared__ float s_w[MAXS][DH];                  // weight of split p for feature d: e^{m_p - M} / denominator
+  __shared__ __attribute__((aligned(16))) float s_ctx[FOLD ? DH * DH : 4];
   const int tid = threadIdx.x;
   const float* base = part + (int64_t)blockIdx.x * nsplit * PART;
+  float4 wo[2][8];                                 // FOLD: Wout[32 cb + c_local][32 h + 4 j8 .. + 3]
+  if constexpr (FOLD) {
+    const int h = blockIdx.x & 7, cl = tid & 31;
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+      for (int j8 = 0; j8 < 8; ++j8)
+        wo[cb][j8] = *reinterpret_cast<const float4*>(wout + ((int64_t)(((h * 2 + cb) * 4 + (j8 >> 1)) * 64 + 32 * (j8 & 1) + cl)) * 4);
+  }
+  float acc[4];                                    // ctx element i = tid + 256 * e: d = i >> 5, e = i & 31
   // (round 4: every loop over the splits is unrolled by four - a load per trip paid one L2 round trip per split, 16 of them in a row at
   //  32x32: 12.6 us for a kernel that moves 22 MB)
   if (nsplit <= 8) {
@@ -190,10 +207,10 @@ __global__ __launch_bounds__(256) void linattn_fused_merge_kernel(const float* _
       float den = 0.f, w[PS];
 #pragma unroll
       for (int p = 0; p < PS; ++p) {
-        w[p] = p < nsplit ? expf(pm[p] - mm) : 0.f;
+        w[p] = p < nsplit ? fast_exp(pm[p] - mm) : 0.f;
         den += w[p] * psum[p];
       }
-      const float inv = 1.0f / den;
+      const float inv = fast_rcp(den);
 #pragma unroll
       for (int p = 0; p < PS; ++p)
         if (p < nsplit) s_w[p][tid] = w[p] * inv;
@@ -201,36 +218,70 @@ __global__ __launch_bounds__(256) void linattn_fused_merge_kernel(const float* _
     __syncthreads();
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const int i = tid + 256 * e, d = i >> 5;
-      float acc = 0.f;
+      const int d = (tid + 256 * e) >> 5;
+      float a = 0.f;
 #pragma unroll
       for (int p = 0; p < PS; ++p)
-        if (p < nsplit) acc += s_w[p][d] * cv[e][p];
-      ctx_out[(int64_t)blockIdx.x * DH * DH + i] = acc;
+        if (p < nsplit) a += s_w[p][d] * cv[e][p];
+      acc[e] = a;
     }
-    return;
-  }
-  if (tid < DH) {
-    float mm = -3.0e38f;
+  } else {
+    if (tid < DH) {
+      float mm = -3.0e38f;
 #pragma unroll 4
-    for (int p = 0; p < nsplit; ++p) mm = fmaxf(mm, base[(int64_t)p * PART + DH * DH + tid]);
-    float den = 0.f;
+      for (int p = 0; p < nsplit; ++p) mm = fmaxf(mm, base[(int64_t)p * PART + DH * DH + tid]);
+      float den = 0.f;
 #pragma unroll 4
-    for (int p = 0; p < nsplit; ++p) {
-      const float w = expf(base[(int64_t)p * PART + DH * DH + tid] - mm);
-      s_w[p][tid] = w;
-      den += w * base[(int64_t)p * PART + DH * DH + DH + tid];
+      for (int p = 0; p < nsplit; ++p) {
+        const float w = fast_exp(base[(int64_t)p * PART + DH * DH + tid] - mm);
+        s_w[p][tid] = w;
+        den += w * base[(int64_t)p * PART + DH * DH + DH + tid];
+      }
+      const float inv = fast_rcp(den);
+      for (int p = 0; p < nsplit; ++p) s_w[p][tid] *= inv;
     }
-    const float inv = 1.0f / den;
-    for (int p = 0; p < nsplit; ++p) s_w[p][tid] *= inv;
-  }
-  __syncthreads();
-  for (int i = tid; i < DH * DH; i += 256) {
-    const int d = i >> 5;
-    float acc = 0.f;
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int i = tid + 256 * e, d = i >> 5;
+      float a = 0.f;
 #pragma unroll 4
-    for (int p = 0; p < nsplit; ++p) acc += s_w[p][d] * base[(int64_t)p * PART + i];
-    ctx_out[(int64_t)blockIdx.x * DH * DH + i] = acc;
+      for (int p = 0; p < nsplit; ++p) a += s_w[p][d] * base[(int64_t)p * PART + i];
+      acc[e] = a;
+    }
+  }
+  if constexpr (!FOLD) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ctx_out[(int64_t)blockIdx.x * DH * DH + tid + 256 * e] = acc[e];
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) s_ctx[tid + 256 * e] = acc[e];
+    __syncthreads();
+    const float* crow = s_ctx + 4 * (tid >> 5) * DH;       // ctx rows d = 8 quad + 4 kh + 0..3 (one address per half-wave: broadcast)
+    float mt[2][4];
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) mt[cb][j] = 0.f;
+#pragma unroll
+    for (int j8 = 0; j8 < 8; ++j8)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float4 c4 = *reinterpret_cast<const float4*>(crow + j * DH + 4 * j8);
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) {
+          float a = mt[cb][j];
+          a = fmaf(wo[cb][j8].x, c4.x, a);
+          a = fmaf(wo[cb][j8].y, c4.y, a);
+          a = fmaf(wo[cb][j8].z, c4.z, a);
+          a = fmaf(wo[cb][j8].w, c4.w, a);
+          mt[cb][j] = a;
+        }
+      }
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb)
+      *reinterpret_cast<float4*>(ctx_out + ((int64_t)blockIdx.x * 2 * DH * DH / 4 + 256 * cb + tid) * 4) =
+          make_float4(mt[cb][0], mt[cb][1], mt[cb][2], mt[cb][3]);
   }
 }
 
@@ -264,11 +315,11 @@ __global__ __launch_bounds__(64, 2) void linattn_fused_out_kernel(const float* _
     float sum = 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      q[r] = expf(q[r] - m);
+      q[r] = fast_exp(q[r] - m);
       sum += q[r];
     }
     sum += __shfl_xor(sum, 32);
-    const float inv = LA_SCALE / sum;
+    const float inv = LA_SCALE * fast_rcp(sum);
     // out[token][e] = sum_d q~[token][d] ctx[d][e]: A = q (lane = token, slot = d half), B = ctx[d(kh, r)][e = l31]
     const float* cb = ctx + ((int64_t)f * HEADS + h) * DH * DH + l31;
     f32x16 o;
@@ -289,18 +340,19 @@ __global__ __launch_bounds__(64, 2) void linattn_fused_out_kernel(const float* _
 // ---- C': output + to_out + bias + residual in one pass (round 6; lfdm_linear_attention_fused_out_cl_f32) ----
 // The separate to_out projection of a C = 64 block was a 25 us launch that re-read the 42 MB attention output pass C had just written in
 // 128-byte pieces.  Here a workgroup of four waves owns one 32-token tile of a frame; wave w runs heads 2w, 2w + 1:
-//   Q^T = Wq xhat^T as in pass C (lane = token, registers = 16 features), softmax over the features,
-//   O^T[e][tok] = sum_d ctx[d][e] q~[tok][d]  - pass C's product with the operands exchanged: the accumulator then has lane = token, registers =
-//     features e(half, r), which IS the B operand (column = token, k = e) of
-//   Y^T[c][tok] += sum_e Wout[c][32 h + e] O^T[e][tok]   (A = Wout rows in operand order, two 32-channel row blocks).
+//   Q^T = Wq xhat^T as in pass C (lane = token, registers = 16 features), softmax over the features: the accumulator (lane = token, registers =
+//     features d(half, r)) IS the B operand (column = token, k = d) of
+//   Y^T[c][tok] += sum_d Mt_h[c][d] q~[tok][d]   (A = Mt_h rows in operand order, two 32-channel row blocks),
+// where Mt_h = Wout_h ctx_h^T comes from the merge pass (to_out folded into the context: it depends on the frame, not on the token).  64 MFMAs per
+// head instead of the 80 of q~ ctx followed by Wout, 8 float4 loads instead of 16 strided dwords of ctx + 8 float4 of wout, and no dependent O^T stage.
 // The four waves' partial Y^T (their two heads each) meet in LDS ([wave][token][64 + 4] floats: a lane's registers (r & 3) are four consecutive
 // channels = one 16-byte store), and 256 threads finish out[tok][c] = x[tok][c] + bias[c] + sum of the four partials as float4 rows.
-// wout arrives packed (ops.pack_linattn_out_weight): [8 heads][2 row blocks][4 quads][64 lanes = 32 kh + c_local][4] <- Wout[32 cb + c_local][32 h + 8 quad + 4 kh + e].
+// wout arrives packed (ops.pack_linattn_out_weight): [8 heads][2 row blocks][4 quads][64 lanes = 32 kh + c_local][4] <- Wout[32 cb + c_local][32 h + 8 quad + 4 kh + e];
+// the merge pass reads it and writes mt in the same order with d in the place of e.
 constexpr int LDY = C + 4;
 __global__ __launch_bounds__(256, 2) void linattn_fused_out2_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ wqkv,
-                                                                    const float* __restrict__ wout, const float* __restrict__ bias_out,
-                                                                    const float* __restrict__ ctx, int hw, float eps, float* __restrict__ out,
-                                                                    int ldo) {
+                                                                    const float* __restrict__ bias_out, const float* __restrict__ mt, int hw,
+                                                                    float eps, float* __restrict__ out, int ldo) {
   __shared__ __attribute__((aligned(16))) float s_y[4 * 32 * LDY];
   const int tid = threadIdx.x;
   const int wave = lfdm_uniform(tid >> 6);
@@ -317,6 +369,13 @@ __global__ __launch_bounds__(256, 2) void linattn_fused_out2_kernel(const float*
     for (int r = 0; r < 16; ++r) yT[cb][r] = 0.f;
 #pragma unroll 1
   for (int h = 2 * wave; h < 2 * wave + 2; ++h) {
+    // the head's eight Mt fragments (A operand of Y^T: lane = row c_local, k = d(kh, r)) are requested in front of the Q^T products
+    const float* msrc = mt + (((int64_t)f * HEADS + h) * (2 * DH * DH / 4) + lane) * 4;
+    float4 mf[2][4];
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+      for (int qd = 0; qd < 4; ++qd) mf[cb][qd] = *reinterpret_cast<const float4*>(msrc + (cb * 4 + qd) * 256);
     float wq[CH];
     load_wfrag(wqkv, 0, h, lane, wq);                      // A operand: lane = feature d
     f32x16 q;
@@ -332,33 +391,23 @@ __global__ __launch_bounds__(256, 2) void linattn_fused_out2_kernel(const float*
     float sum = 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      q[r] = expf(q[r] - m);
+      q[r] = fast_exp(q[r] - m);
       sum += q[r];
     }
     sum += __shfl_xor(sum, 32);
-    const float inv = LA_SCALE / sum;
-    // O^T[e][tok]: A = ctx[d(kh, r)][e = l31] (lane = row e), B = q~ (lane = column tok, k = d(kh, r))
-    const float* cb_ = ctx + ((int64_t)f * HEADS + h) * DH * DH + l31;
-    f32x16 oT;
+    const float inv = LA_SCALE * fast_rcp(sum);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) oT[r] = 0.f;
+    for (int r = 0; r < 16; ++r) q[r] *= inv;
+    // Y^T[c][tok] += Mt[c][d] q~[tok][d]: A = Mt fragment (lane = row c), B = q~ (lane = column tok, k = d(kh, r), r = 4 qd + j)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) oT = mfma_32x32x2(cb_[((r & 3) + 8 * (r >> 2) + 4 * kh) * DH], q[r] * inv, oT);
-    // lane = token; oT[r] = O^T[e(kh, r)][tok].  Y^T[c][tok] += Wout[c][32 h + e] O^T[e][tok]: A = Wout fragment (lane = row c), B = oT
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb) {
-      const float* wsrc = wout + ((int64_t)((h * 2 + cb) * 4) * 64 + lane) * 4;
-      float4 wo[4];
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd) wo[qd] = *reinterpret_cast<const float4*>(wsrc + 256 * qd);
+    for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
       for (int qd = 0; qd < 4; ++qd) {
-        yT[cb] = mfma_32x32x2(wo[qd].x, oT[4 * qd + 0], yT[cb]);
-        yT[cb] = mfma_32x32x2(wo[qd].y, oT[4 * qd + 1], yT[cb]);
-        yT[cb] = mfma_32x32x2(wo[qd].z, oT[4 * qd + 2], yT[cb]);
-        yT[cb] = mfma_32x32x2(wo[qd].w, oT[4 * qd + 3], yT[cb]);
+        yT[cb] = mfma_32x32x2(mf[cb][qd].x, q[4 * qd + 0], yT[cb]);
+        yT[cb] = mfma_32x32x2(mf[cb][qd].y, q[4 * qd + 1], yT[cb]);
+        yT[cb] = mfma_32x32x2(mf[cb][qd].z, q[4 * qd + 2], yT[cb]);
+        yT[cb] = mfma_32x32x2(mf[cb][qd].w, q[4 * qd + 3], yT[cb]);
       }
-    }
   }
   // lane (tok = l31, half kh): yT[cb][r] = Y^T[c = 32 cb + (r&3) + 8 (r>>2) + 4 kh][tok] over this wave's two heads
   float* ys = s_y + (wave * 32 + l31) * LDY;
@@ -391,13 +440,15 @@ __global__ __launch_bounds__(256, 2) void linattn_fused_out2_kernel(const float*
 
 extern "C" size_t lfdm_linear_attention_fused_ws_bytes(int n_frames, int hw) {
   const int nsplit = (hw + SPLIT_TOK - 1) / SPLIT_TOK;
-  return ((size_t)n_frames * HEADS * nsplit * PART + (size_t)n_frames * HEADS * DH * DH) * sizeof(float);
+  // partials | per (frame, head): ctx[32][32] (plain entry point) or Mt[64][32] (with to_out): 8 KB
+  return ((size_t)n_frames * HEADS * nsplit * PART + (size_t)n_frames * HEADS * 2 * DH * DH) * sizeof(float);
 }
 
 namespace {
-// passes A + B: context partials and their merge; *ctx_out = the merged contexts inside the workspace
-void launch_ctx_and_merge(const float* x, int ldx, const float* wqkv, int n_frames, int hw, float ln_eps, void* ws, float** ctx_out,
-                          hipStream_t stream) {
+// passes A + B: context partials and their merge; *ctx_out = the merged contexts inside the workspace - or, with wout, the contexts with
+// to_out folded in (Mt, linattn_fused_merge_kernel<true>)
+void launch_ctx_and_merge(const float* x, int ldx, const float* wqkv, const float* wout, int n_frames, int hw, float ln_eps, void* ws,
+                          float** ctx_out, hipStream_t stream) {
   // splits of whole 32-token tiles, as many as fit ONE round of waves (3 per SIMD: 3072), at most 64 (the merge kernel's table)
   const int tiles = (hw + 31) / 32;
   // (batched shapes - more (frame, head) pairs than half a round - get at least four rounds of waves instead of one long wave per pair:
@@ -413,7 +464,8 @@ void launch_ctx_and_merge(const float* x, int ldx, const float* wqkv, int n_fram
   float* part = (float*)ws;
   float* ctx = part + (size_t)n_frames * HEADS * ((hw + SPLIT_TOK - 1) / SPLIT_TOK) * PART;
   LFDM_LAUNCH(linattn_fused_ctx_kernel, dim3(n_frames * HEADS, nsplit), dim3(64), 0, stream, x, ldx, wqkv, hw, ln_eps, part, split_tok);
-  LFDM_LAUNCH(linattn_fused_merge_kernel, dim3(n_frames * HEADS), dim3(256), 0, stream, (const float*)part, nsplit, ctx);
+  if (wout) LFDM_LAUNCH((linattn_fused_merge_kernel<true>), dim3(n_frames * HEADS), dim3(256), 0, stream, (const float*)part, nsplit, ctx, wout);
+  else LFDM_LAUNCH((linattn_fused_merge_kernel<false>), dim3(n_frames * HEADS), dim3(256), 0, stream, (const float*)part, nsplit, ctx, wout);
   *ctx_out = ctx;
 }
 }  // namespace
@@ -432,7 +484,7 @@ extern "C" int lfdm_linear_attention_fused_cl_f32(const float* x, int ldx, int c
     return LFDM_EWORKSPACE;
   }
   float* ctx = nullptr;
-  launch_ctx_and_merge(x, ldx, wqkv, n_frames, hw, ln_eps, ws, &ctx, stream);
+  launch_ctx_and_merge(x, ldx, wqkv, nullptr, n_frames, hw, ln_eps, ws, &ctx, stream);
   const int64_t otiles = (int64_t)((hw + 31) / 32) * n_frames;
   const int hgroups = otiles >= 4096 ? 1 : (otiles >= 2048 ? 2 : 4);
   LFDM_LAUNCH(linattn_fused_out_kernel, dim3((hw + 31) / 32, n_frames, hgroups), dim3(64), 0, stream, x, ldx, wqkv,
@@ -454,9 +506,9 @@ extern "C" int lfdm_linear_attention_fused_out_cl_f32(const float* x, int ldx, i
     lfdm_set_error("linear_attention_fused_out: workspace too small");
     return LFDM_EWORKSPACE;
   }
-  float* ctx = nullptr;
-  launch_ctx_and_merge(x, ldx, wqkv, n_frames, hw, ln_eps, ws, &ctx, stream);
-  LFDM_LAUNCH(linattn_fused_out2_kernel, dim3((hw + 31) / 32, n_frames), dim3(256), 0, stream, x, ldx, wqkv, wout, bias_out, (const float*)ctx, hw,
+  float* mt = nullptr;
+  launch_ctx_and_merge(x, ldx, wqkv, wout, n_frames, hw, ln_eps, ws, &mt, stream);
+  LFDM_LAUNCH(linattn_fused_out2_kernel, dim3((hw + 31) / 32, n_frames), dim3(256), 0, stream, x, ldx, wqkv, bias_out, (const float*)mt, hw,
               ln_eps, out, ldo);
   return lfdm_check_launch("linear_attention_fused_out");
 }

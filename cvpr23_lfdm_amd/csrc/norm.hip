@@ -198,10 +198,10 @@ __global__ __launch_bounds__(NT) void gn_apply_kernel(
     y.z = fmaf(v.z, a.z, d.z);
     y.w = fmaf(v.w, a.w, d.w);
     if (silu) {
-      y.x = siluf_(y.x);
-      y.y = siluf_(y.y);
-      y.z = siluf_(y.z);
-      y.w = siluf_(y.w);
+      y.x = silu_fast_(y.x);
+      y.y = silu_fast_(y.y);
+      y.z = silu_fast_(y.z);
+      y.w = silu_fast_(y.w);
     }
     if (rb) {
       const float4 r = k == 0 ? pre_r[0] : k == 1 ? pre_r[1] : rb[i];

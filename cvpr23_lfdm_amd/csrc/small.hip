@@ -340,8 +340,8 @@ __global__ __launch_bounds__(256) void heads_gn_kernel(const float* __restrict__
       float s0 = 0.f, s1 = 0.f, s2 = 0.f;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float t0 = siluf_(fmaf(v[j].x, ra[j].x, rb[j].x)), t1 = siluf_(fmaf(v[j].y, ra[j].y, rb[j].y));
-        const float t2 = siluf_(fmaf(v[j].z, ra[j].z, rb[j].z)), t3 = siluf_(fmaf(v[j].w, ra[j].w, rb[j].w));
+        const float t0 = silu_fast_(fmaf(v[j].x, ra[j].x, rb[j].x)), t1 = silu_fast_(fmaf(v[j].y, ra[j].y, rb[j].y));
+        const float t2 = silu_fast_(fmaf(v[j].z, ra[j].z, rb[j].z)), t3 = silu_fast_(fmaf(v[j].w, ra[j].w, rb[j].w));
         s0 += (t0 * w0[j].x + t1 * w0[j].y) + (t2 * w0[j].z + t3 * w0[j].w);
         s1 += (t0 * w1[j].x + t1 * w1[j].y) + (t2 * w1[j].z + t3 * w1[j].w);
         s2 += (t0 * w2[j].x + t1 * w2[j].y) + (t2 * w2[j].z + t3 * w2[j].w);
@@ -367,7 +367,7 @@ __global__ __launch_bounds__(256) void heads_gn_kernel(const float* __restrict__
       const float4 a = *reinterpret_cast<const float4*>(s_a + 4 * k), d = *reinterpret_cast<const float4*>(s_b + 4 * k);
       const float4 w0 = *reinterpret_cast<const float4*>(wl + 4 * k), w1 = *reinterpret_cast<const float4*>(wl + 512 + 4 * k);
       const float4 w2 = *reinterpret_cast<const float4*>(wl + 1024 + 4 * k);
-      const float t0 = siluf_(fmaf(v.x, a.x, d.x)), t1 = siluf_(fmaf(v.y, a.y, d.y)), t2 = siluf_(fmaf(v.z, a.z, d.z)), t3 = siluf_(fmaf(v.w, a.w, d.w));
+      const float t0 = silu_fast_(fmaf(v.x, a.x, d.x)), t1 = silu_fast_(fmaf(v.y, a.y, d.y)), t2 = silu_fast_(fmaf(v.z, a.z, d.z)), t3 = silu_fast_(fmaf(v.w, a.w, d.w));
       s0 += (t0 * w0.x + t1 * w0.y) + (t2 * w0.z + t3 * w0.w);
       s1 += (t0 * w1.x + t1 * w1.y) + (t2 * w1.z + t3 * w1.w);
       s2 += (t0 * w2.x + t1 * w2.y) + (t2 * w2.z + t3 * w2.w);

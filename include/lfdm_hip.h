@@ -440,8 +440,9 @@ int lfdm_linear_attention_fused_cl_f32(const float* x, int ldx, int channels, co
                                        lfdm_stream_t stream);
 /* ... and the WHOLE block Residual(PreNorm(SpatialLinearAttention)) at C == 64 (ABI version 12; video_flow_diffusion.py:170-189, :240-265 incl. to_out,
  * its bias and the residual add): out[row][c] = x[row][c] + bias_out[c] + sum_k attention(LayerNorm(x))[row][k] Wout[c][k], rows of 64 with stride ldo,
- * out != x.  The 256-column attention output is never written: the output pass keeps O^T in accumulator registers as the B operand of the to_out
- * product (one launch and 84 MB of traffic less than lfdm_linear_attention_fused_cl_f32 + a 1x1 convolution at 40 frames of 32x32).  wout: the
+ * out != x.  The 256-column attention output is never written: the merge pass folds to_out into the context (Mt_h = Wout_h ctx_h^T, 64 x 32 per
+ * (frame, head)) and the output pass multiplies the softmaxed q accumulator by it (one launch and 84 MB of traffic less than
+ * lfdm_linear_attention_fused_cl_f32 + a 1x1 convolution at 40 frames of 32x32).  wout: the
  * (64, 256) to_out weight in MFMA-operand order [8 heads][2 row blocks][4 quads][64 lanes = 32*kh + c_local][4] <- Wout[32*cb + c_local][32*h + 8*quad + 4*kh + e]
  * (cvpr23_lfdm_amd.ops.pack_linattn_out_weight); bias_out (64,) or NULL; same workspace as above. */
 int lfdm_linear_attention_fused_out_cl_f32(const float* x, int ldx, int channels, const float* wqkv, const float* wout, const float* bias_out,
