@@ -226,6 +226,10 @@ _SIGNATURES = {
     "lfdm_video_metrics": (i32, [f32p, f32p, C.POINTER(C.c_double), i32, C.c_void_p, i32, i32, i32, i32, i32, C.c_void_p, sz, stream_t]),
     "lfdm_flow_metrics": (i32, [f32p, i64, f32p, i64, f32p, f32p, C.c_void_p, i32, i32, i32, stream_t]),
     "lfdm_psnr_f64": (i32, [C.c_void_p, C.c_void_p, i64, stream_t]),
+    # ---- training batches from a packed uint8 frame store (additive, ABI stays 12)
+    "lfdm_video_prep_ws_bytes": (sz, [i32, i32]),
+    "lfdm_video_prep_u8": (i32, [C.c_void_p, i64, C.c_void_p, f32p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), f32p, i32, i32, i32, i32,
+                                 i32, i32, C.c_void_p, sz, stream_t]),
     "lfdm_depthwise_down_planar_f32": (i32, [f32p, f32p, f32p, i32, i32, i32, i32, i32, i32, i32, i32, stream_t]),
     "lfdm_upsample2_pad_cl_f32": (i32, [f32p, f32p, i32, i32, i32, i32, i32, i32, i32, stream_t]),
     "lfdm_layernorm_bwd_ws_bytes": (sz, [i64, i32]),

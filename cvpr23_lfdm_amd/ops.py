@@ -1300,3 +1300,85 @@ def psnr(mse_table, out=None):
     if src.numel():
         lib.check(lib.lfdm_psnr_f64(_p(src), _p(out), src.numel(), _stream(lib)), "lfdm_psnr_f64")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# training batches from a packed uint8 frame store (csrc/video_prep.hip)
+# ---------------------------------------------------------------------------------------------
+PREP_RATIOS = (1, 2, 4)
+PREP_STATS, PREP_MAIN = 1, 2          # LFDM_PREP_*
+
+
+def video_prep(store_u8, frame_index, params, hue_shift, mean, image_size, jitter, out=None, *, valid=None,
+               launches=PREP_STATS | PREP_MAIN):
+    """lfdm_video_prep_u8: gathers frames from store_u8 (N, S, S, 3) uint8 by frame_index (B, T) int32 and returns the training batch
+    (B, 3, T, H, H) float32, H = image_size, S / H in {1, 2, 4}: bit for bit what data.FrameFolderVideos makes of the same pixels -
+    data.color_jitter with the factors params (B, 3) float32 = (brightness, contrast, saturation) and hue_shift (B,) int32 = int(hf * 255)
+    when `jitter`, the area shrink, - mean (3 floats, host), / 255.  jitter=False carries no jitter arithmetic at all (params and hue_shift
+    may be None).  valid (B, 4) int32 = (y0, x0, h, w): the picture inside a zero-padded stored frame (non-square videos); jitter and the
+    contrast mean see only it.  frame_index may have repeats and any order; every entry is range-checked here, on the host.  The four
+    small tables (frame_index, params, hue_shift, valid) may be host tensors - they are checked there and uploaded - which avoids the
+    read-back that checking a device tensor costs.  launches: measurement only (tools/bench_video_prep.py)."""
+    lib = _lib()
+    if not isinstance(store_u8, torch.Tensor) or store_u8.dtype != torch.uint8 or store_u8.dim() != 4 or store_u8.shape[3] != 3 \
+            or store_u8.shape[1] != store_u8.shape[2] or not store_u8.is_contiguous():
+        raise ValueError("video_prep: store_u8 must be a contiguous uint8 (N, S, S, 3) tensor, got %s %s"
+                         % (getattr(store_u8, "dtype", type(store_u8)), tuple(getattr(store_u8, "shape", ()))))
+    _chk_dev(lib, store_u8, out)
+    n, s = int(store_u8.shape[0]), int(store_u8.shape[1])
+    h = int(image_size)
+    if s % 4 != 0 or h % 4 != 0 or h < 4:
+        raise ValueError("video_prep: store_size %d and image_size %d must be multiples of 4" % (s, h))
+    if h * (s // h) != s or s // h not in PREP_RATIOS:
+        raise ValueError("video_prep: store_size / image_size must be 1, 2 or 4, got %d / %d" % (s, h))
+    if n < 1:
+        raise ValueError("video_prep: the store is empty")
+    if not isinstance(frame_index, torch.Tensor) or frame_index.dtype != torch.int32 or frame_index.dim() != 2 or frame_index.numel() == 0:
+        raise ValueError("video_prep: frame_index must be a non-empty int32 (B, T) tensor, got %s %s"
+                         % (getattr(frame_index, "dtype", type(frame_index)), tuple(getattr(frame_index, "shape", ()))))
+    b, t = int(frame_index.shape[0]), int(frame_index.shape[1])
+    lo, hi = int(frame_index.min()), int(frame_index.max())
+    if lo < 0 or hi >= n:
+        raise IndexError("video_prep: frame_index holds %d .. %d, the store has rows 0 .. %d" % (lo, hi, n - 1))
+    dev = store_u8.device
+
+    def table(name, x):          # the small per-batch tables may come from the host: checked there, then uploaded
+        if x is None or x.device == dev:
+            return x if x is None else x.contiguous()
+        if x.is_cuda:
+            raise ValueError("video_prep: %s is on %s, the store on %s" % (name, x.device, dev))
+        return x.contiguous().to(dev, non_blocking=True)
+
+    frame_index = table("frame_index", frame_index)
+    mean = [float(m) for m in mean]
+    if len(mean) != 3:
+        raise ValueError("video_prep: mean has three channels")
+    jitter = bool(jitter)
+    ws, ws_bytes = None, 0
+    if jitter:
+        if not isinstance(params, torch.Tensor) or params.dtype != torch.float32 or tuple(params.shape) != (b, 3):
+            raise ValueError("video_prep: params must be a float32 (%d, 3) tensor" % b)
+        if not bool(torch.isfinite(params).all()):          # a NaN or inf factor would reach the kernel's float -> int conversion
+            raise ValueError("video_prep: params holds a NaN or an infinity")
+        if not isinstance(hue_shift, torch.Tensor) or hue_shift.dtype != torch.int32 or tuple(hue_shift.shape) != (b,):
+            raise ValueError("video_prep: hue_shift must be an int32 (%d,) tensor" % b)
+        if valid is not None:
+            if not isinstance(valid, torch.Tensor) or valid.dtype != torch.int32 or tuple(valid.shape) != (b, 4):
+                raise ValueError("video_prep: valid must be an int32 (%d, 4) tensor of (y0, x0, h, w)" % b)
+            vv = valid.cpu()
+            if bool((vv < 0).any()) or bool((vv[:, 2:] < 1).any()) or bool(((vv[:, :2] + vv[:, 2:]) > s).any()):
+                raise ValueError("video_prep: a valid rectangle is empty or leaves the %d x %d stored frame" % (s, s))
+        params, hue_shift, valid = table("params", params), table("hue_shift", hue_shift), table("valid", valid)
+        ws_bytes = lib.lfdm_video_prep_ws_bytes(b, t)
+        ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
+    else:
+        params = hue_shift = valid = None
+    shape = (b, 3, t, h, h)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != dev:
+        raise ValueError("video_prep: out must be a contiguous float32 %s tensor on the store's device" % (shape,))
+    lib.check(lib.lfdm_video_prep_u8(_p(store_u8), n, _p(frame_index), _p(params), _p(hue_shift), _p(valid), (C.c_float * 3)(*mean),
+                                     _p(out), b, t, s, h, int(jitter), int(launches), _p(ws), ws_bytes, _stream(lib)),
+              "lfdm_video_prep_u8")
+    return out

@@ -1,0 +1,185 @@
+"""Packed uint8 frame store and on-device batch preparation for the DM trainer - an opt-in input path beside
+data.FrameFolderVideos, which stays the definition of what a batch is.
+
+    pack_frame_folders(root, out_dir, store_size)      decode every frame of root/<label>/<video>/*.jpg|png ONCE, area-resize it to
+                                                       store_size (1, 2 or 4 x the training size) -> frames.u8 + index.json
+    PackedVideos(out_dir, image_size, ...)             Dataset over the store: an item is bytes and four jitter numbers, no arithmetic
+    DevicePrep(dataset)                                collated batch -> real_vids (B, 3, T, H, W) float32 on the device (ops.video_prep)
+
+Colour jitter, the area shrink, the mean and the / 255 run in csrc/video_prep.hip, bit for bit what FrameFolderVideos computes from the
+stored bytes.  The approximation is the store itself.  A source larger than store_size is rounded to a byte once, when packed: without
+jitter that is at most 0.5 / 255 against the host path on the original files.  With jitter the augmentation then runs at store
+resolution, not source resolution (the host jitters the full-size frames and shrinks afterwards); every jitter stage is non-linear, so on
+larger originals the two paths are neither bit- nor bound-comparable - several levels of 255 apart on the test's small noisy frames.
+"""
+import json
+import os
+import random
+
+import numpy as np
+import torch
+from torch.utils import data as tdata
+
+from . import _native, ops
+from .data import FrameFolderVideos, _rgb, sample_indices
+from .io_compat import INTER_AREA, imread, resize
+
+FRAMES_FILE, INDEX_FILE = "frames.u8", "index.json"
+STORE_VERSION = 1
+
+
+def _check_sizes(store_size, image_size=None):
+    if store_size < 4 or store_size % 4 != 0:
+        raise ValueError("store_size must be a multiple of 4, got %r" % (store_size,))
+    if image_size is not None:
+        if image_size < 4 or image_size % 4 != 0:
+            raise ValueError("image_size must be a multiple of 4, got %r" % (image_size,))
+        if store_size % image_size != 0 or store_size // image_size not in ops.PREP_RATIOS:
+            raise ValueError("store_size / image_size must be 1, 2 or 4 (the shrink factors csrc/video_prep.hip has), got %d / %d"
+                             % (store_size, image_size))
+
+
+def _picture_rect(shape, store_size):
+    """Where io_compat.resize puts a frame of `shape` inside the store_size square: (y0, x0, h, w); the rest is zero padding."""
+    ratio = float(store_size) / max(shape[:2])
+    h, w = (int(x * ratio) for x in shape[:2])
+    return [(store_size - h) // 2, (store_size - w) // 2, h, w]
+
+
+def pack_frame_folders(root, out_dir, store_size):
+    """Walks root/<label>/<video>/*.jpg|png like FrameFolderVideos and writes out_dir/frames.u8, a flat (N_frames, S, S, 3) uint8 array of
+    io_compat.resize(data._rgb(frame), store_size, INTER_AREA) (rounded to a byte, zero-padded to a square), and out_dir/index.json
+    (labels, names, first frame, frame count, picture rectangle, store_size).  Returns the index."""
+    store_size = int(store_size)
+    _check_sizes(store_size)
+    videos = FrameFolderVideos(root).videos
+    total = sum(len(paths) for _, _, paths in videos)
+    os.makedirs(out_dir, exist_ok=True)
+    # a raw file, not .npy: np.memmap reads it back with the index's shape
+    frames = np.memmap(os.path.join(out_dir, FRAMES_FILE), dtype=np.uint8, mode="w+", shape=(total, store_size, store_size, 3))
+    entries, row = [], 0
+    for label, vid, paths in videos:
+        rect = None
+        for k, p in enumerate(paths):
+            a = np.ascontiguousarray(_rgb(imread(p)), dtype=np.uint8)
+            r = _picture_rect(a.shape, store_size)
+            if rect is None:
+                rect = r
+            elif r != rect:
+                raise ValueError("%s: the frames of one video must share a size (frame 0 and frame %d differ)" % (os.path.dirname(p), k))
+            frames[row + k] = resize(a, store_size, interpolation=INTER_AREA)
+        entries.append({"label": label, "video": vid, "first": row, "count": len(paths), "valid": rect})
+        row += len(paths)
+    frames.flush()
+    del frames
+    index = {"version": STORE_VERSION, "store_size": store_size, "frames": total, "videos": entries}
+    with open(os.path.join(out_dir, INDEX_FILE), "w") as f:
+        json.dump(index, f)
+    return index
+
+
+def draw_jitter(rnd=random, bright=64. / 255, contrast=0.25, sat=0.25, hue=0.04):
+    """The four draws of data.color_jitter, same order and ranges -> ((bf, cf, sf) float32, hue shift int(hf * 255))."""
+    bf = rnd.uniform(max(0, 1 - bright), 1 + bright)
+    cf = rnd.uniform(max(0, 1 - contrast), 1 + contrast)
+    sf = rnd.uniform(max(0, 1 - sat), 1 + sat)
+    hf = rnd.uniform(-hue, hue)
+    return np.array([bf, cf, sf], np.float32), int(hf * 255)
+
+
+class PackedVideos(tdata.Dataset):
+    """Item = (frames uint8 (T, S, S, 3), params float32[3] = (bf, cf, sf), hue_shift int32, label, name, valid int32[4]); with
+    resident=True the first entry is the (T,) int32 rows of the store instead of their pixels (DevicePrep holds the store on the
+    device).  Frame sampling is data.sample_indices, the jitter draws are data.color_jitter's; jitter=False gives (1, 1, 1), 0 and
+    `self.jitter` False, which makes DevicePrep skip the jitter arithmetic altogether (PIL's HSV round trip is lossy even at shift 0)."""
+
+    def __init__(self, store_dir, image_size=128, num_frames=40, sampling="uniform", mean=(0, 0, 0), jitter=False, resident=False):
+        with open(os.path.join(store_dir, INDEX_FILE)) as f:
+            self.index = json.load(f)
+        if self.index.get("version") != STORE_VERSION:
+            raise ValueError("%s: store version %r, this code reads %d" % (store_dir, self.index.get("version"), STORE_VERSION))
+        self.store_size = int(self.index["store_size"])
+        _check_sizes(self.store_size, int(image_size))
+        self.image_size, self.num_frames, self.sampling, self.jitter, self.resident = int(image_size), num_frames, sampling, jitter, resident
+        self.mean = np.asarray(mean, np.float32)
+        self.videos = self.index["videos"]
+        if not self.videos:
+            raise FileNotFoundError("no videos in %r" % (store_dir,))
+        # the device shrinks the padded square, the host shrinks the picture and then centres it: the same thing only when the picture
+        # starts and ends on a k x k cell
+        k = self.store_size // self.image_size
+        for v in self.videos:
+            if any(x % k for x in v["valid"]):
+                raise ValueError("%s: video %s/%s has its picture at (y0, x0, h, w) = %s inside the %d x %d stored frame, not on multiples "
+                                 "of store_size / image_size = %d: a %d x %d cell would mix picture and padding; pack at store_size == "
+                                 "image_size" % (store_dir, v["label"], v["video"], tuple(v["valid"]), self.store_size, self.store_size,
+                                                 k, k, k))
+        s = self.store_size
+        self.frames = np.memmap(os.path.join(store_dir, FRAMES_FILE), dtype=np.uint8, mode="r", shape=(int(self.index["frames"]), s, s, 3))
+
+    def __len__(self):
+        return len(self.videos)
+
+    def __getitem__(self, index):
+        v = self.videos[index]
+        rows = v["first"] + sample_indices(v["count"], self.num_frames, self.sampling)
+        if self.jitter:
+            params, shift = draw_jitter()
+        else:
+            params, shift = np.ones(3, np.float32), 0
+        first = rows.astype(np.int32) if self.resident else np.stack([self.frames[i] for i in rows])
+        return first, params, np.array(shift, np.int32), v["label"], "%s_%s" % (v["label"], v["video"]), np.asarray(v["valid"], np.int32)
+
+
+class DevicePrep:
+    """Callable on a collated PackedVideos batch: returns real_vids (B, 3, T, H, W) float32 on the device; the reference frame is
+    real_vids[:, :, 0].  Staged batches cross as bytes through two reused pinned buffers (non_blocking; a buffer is refilled only after
+    its last copy has finished); a resident dataset's store is uploaded here, once, and a batch is then a table of row numbers."""
+    _CHUNK = 1 << 28
+
+    def __init__(self, dataset, device=None):
+        self.ds = dataset
+        kind = _native.library().kind
+        self.device = torch.device(device if device is not None else ("cuda" if kind == "hip" else "cpu"))
+        self.cuda = self.device.type == "cuda"
+        self._pinned, self._events, self._slot = [None, None], [None, None], 0
+        self.store = None
+        if dataset.resident:
+            n, s = dataset.frames.shape[0], dataset.store_size
+            self.store = torch.empty((n, s, s, 3), dtype=torch.uint8, device=self.device)
+            step = max(1, self._CHUNK // (s * s * 3))
+            for i in range(0, n, step):
+                self.store[i:i + step].copy_(torch.from_numpy(np.array(dataset.frames[i:i + step])))
+
+    def _stage(self, frames):
+        """(B, T, S, S, 3) uint8 host tensor -> (B * T, S, S, 3) on the device."""
+        flat = frames.reshape((-1,) + tuple(frames.shape[2:]))
+        if not self.cuda:
+            return flat.contiguous()
+        if flat.is_pinned() and flat.is_contiguous():
+            # a DataLoader with pin_memory=True has pinned the collated batch already: no second host copy.  The caching host allocator
+            # keeps the block from reuse until this copy has run.
+            return flat.to(self.device, non_blocking=True)
+        k = self._slot
+        self._slot ^= 1
+        if self._events[k] is not None:
+            self._events[k].synchronize()
+        if self._pinned[k] is None or self._pinned[k].numel() < flat.numel():
+            self._pinned[k] = torch.empty(flat.numel(), dtype=torch.uint8, pin_memory=True)
+        host = self._pinned[k][:flat.numel()].view(flat.shape)
+        host.copy_(flat)
+        dev = host.to(self.device, non_blocking=True)
+        self._events[k] = torch.cuda.Event()
+        self._events[k].record()
+        return dev
+
+    def __call__(self, batch):
+        first, params, shift, valid = batch[0], batch[1], batch[2], batch[5]
+        if self.ds.resident:
+            store, rows = self.store, first.to(torch.int32)
+        else:
+            store = self._stage(first)
+            rows = torch.arange(first.shape[0] * first.shape[1], dtype=torch.int32).view(first.shape[0], first.shape[1])
+        jitter = bool(self.ds.jitter)
+        return ops.video_prep(store, rows, params.to(torch.float32) if jitter else None, shift.to(torch.int32) if jitter else None,
+                              self.ds.mean.tolist(), self.ds.image_size, jitter, valid=valid.to(torch.int32) if jitter else None)

@@ -895,6 +895,37 @@ int lfdm_flow_metrics(const float* grid_a, int64_t stride_a, const float* grid_b
 /* out[i] = 10 log10(1 / mse[i]) over n doubles (data range 1), +inf where mse[i] == 0. */
 int lfdm_psnr_f64(const double* mse, double* out, int64_t n, lfdm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Training batches from a packed uint8 frame store (additive under ABI 12): on the device what the host loader does per
+ * frame between decode and the batch tensor - colour jitter, area shrink, mean subtraction, / 255, transpose.
+ *
+ * lfdm_video_prep_u8: out (batch, 3, frames, H, H) planar fp32, H = image_size, from store (store_frames, S, S, 3) uint8, S = store_size.
+ * frame_index: DEVICE (batch, frames) int32 rows of store - a gather, repeats and any order allowed; every entry must lie in
+ * 0 .. store_frames - 1 and THE CALLER CHECKS THAT (the entry point cannot read device memory).  S == k * H with k in {1, 2, 4};
+ * S % 4 == 0 and H % 4 == 0; store 4-byte, out 16-byte aligned.  mean: HOST array of 3 floats.
+ *   jitter == 0: out = fl32(fl32(avg - mean[c]) / 255.f), avg = the k x k byte sum / (k * k) (exact); params, hue_shift, valid and ws
+ *                are not read and may be NULL.
+ *   jitter != 0: every source pixel first goes through the colour jitter below with the factors of its batch element - params DEVICE
+ *                (batch, 3) fp32 = (brightness, contrast, saturation), hue_shift DEVICE (batch) int32 (added to the 8-bit hue, mod 256).
+ *                valid: DEVICE (batch, 4) int32 = (y0, x0, h, w), the part of a stored frame that is picture (the rest is the zero
+ *                padding of a non-square video): jitter and the contrast mean see the picture only, padding stays 0.  NULL = all of it.
+ *                Like frame_index it is device memory the entry point cannot read: THE CALLER CHECKS that every row has y0, x0 >= 0,
+ *                h, w >= 1 (h * w == 0 divides by zero in the stats launch), y0 + h <= S and x0 + w <= S (a rectangle that leaves the
+ *                frame silently changes n), and that params holds finite numbers (a NaN or inf factor reaches a float -> int cast).
+ * Jitter, per pixel on bytes, in this order (blend(d, x, a) = trunc(fl32(d) + a * fl32(x - d)) in fp32 without fma, clamped to 0 .. 255
+ * when a is outside [0, 1]; L = (19595 r + 38470 g + 7471 b + 0x8000) >> 16):
+ *   brightness blend(0, x, bf); contrast blend(m, x, cf), m = (2 sum + n) / (2 n) over the frame's n picture pixels' L after brightness
+ *   (integer); saturation blend(L, x, sf); RGB -> 8-bit HSV, hue + hue_shift, HSV -> RGB (fp32 / fp64 mix spelled out in DESIGN.md 4.7).
+ * Two launches: with jitter, one workgroup per (batch, frame) writes m to ws (integer sums: wave shuffles, then LDS; no atomics); then
+ * one thread per 4 adjacent output pixels.  launches: LFDM_PREP_STATS | LFDM_PREP_MAIN normally; one bit alone runs that launch alone
+ * (measurement; MAIN alone with jitter reads the m a STATS run left in ws).  ws: lfdm_video_prep_ws_bytes bytes, 4-byte aligned. */
+#define LFDM_PREP_STATS 1
+#define LFDM_PREP_MAIN 2
+size_t lfdm_video_prep_ws_bytes(int batch, int frames);
+int lfdm_video_prep_u8(const unsigned char* store, int64_t store_frames, const int* frame_index, const float* params,
+                       const int* hue_shift, const int* valid, const float* mean, float* out, int batch, int frames, int store_size,
+                       int image_size, int jitter, int launches, void* ws, size_t ws_bytes, lfdm_stream_t stream);
+
 /* Box calibration, not on the product path (bench.py prints it beside every timing; ABI version 7): `blocks` workgroups of four
  * wavefronts run `iters` x 4 independent v_mfma_f32_32x32x2_f32 (2 * 32 * 32 * 2 FLOP each, pseudo-random operands) and
  * record, per workgroup b, out[2b] = shader cycles and out[2b+1] = 100 MHz real-time ticks of the loop: effective clock (MHz) =

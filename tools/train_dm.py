@@ -6,6 +6,8 @@ restore semantics; one process per GPU under torchrun instead of nn.DataParallel
     python tools/train_dm.py --data DIR --lfae-ckpt RegionMM.pth --bert /data/bert-base-cased --out snapshots
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 tools/train_dm.py --data DIR ...
     python tools/train_dm.py --synthetic --final-step 20          # random videos / random-init LFAE: exercises the loop
+    python tools/pack_videos.py DIR PACKED --store-size 128 && python tools/train_dm.py --packed PACKED [--resident] ...
+        # frames decoded once into a uint8 store; jitter, shrink and normalisation on the device
     python tools/train_dm.py --data DIR ... --ema-decay 0.9999 --ema-start-step 2000 --max-grad-norm 1.0 --skip-nonfinite
         # averaged weights (checkpoint entry "diffusion_ema", tools/demo.py --use-ema), clipping and the non-finite guard: DESIGN.md 4.4
 """
@@ -28,7 +30,7 @@ from cvpr23_lfdm_amd import FlowDiffusion, io_compat as C  # noqa: E402
 from cvpr23_lfdm_amd.data import FrameFolderVideos, SyntheticVideos  # noqa: E402
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--data", default="")
     ap.add_argument("--synthetic", action="store_true")
@@ -57,7 +59,25 @@ def main():
     ap.add_argument("--skip-nonfinite", action="store_true", help="skip a step whose gradient holds an inf / nan instead of losing the run")
     ap.add_argument("--preview-steps", type=int, default=0, help="> 0: at --save-img-freq also SAMPLE one video with this many DDIM steps "
                     "(from the averaged weights under --ema-decay) and write it as a GIF")
-    args = ap.parse_args()
+    ap.add_argument("--packed", default="", help="a store written by tools/pack_videos.py (instead of --data): batches cross to the device "
+                    "as bytes and colour jitter, area shrink and normalisation run there")
+    ap.add_argument("--resident", action="store_true", help="with --packed: upload the whole store once; a batch is then frame numbers")
+    return ap.parse_args(argv)
+
+
+def make_dataset(args):
+    """(dataset, prep): prep is None for the host loaders, whose items are finished videos, and a video_store.DevicePrep for --packed."""
+    if args.packed:
+        from cvpr23_lfdm_amd.video_store import DevicePrep, PackedVideos
+        ds = PackedVideos(args.packed, image_size=args.size, num_frames=args.frames, sampling="random", jitter=True, resident=args.resident)
+        return ds, DevicePrep(ds)
+    ds = SyntheticVideos(n=256, image_size=args.size, num_frames=args.frames) if args.synthetic else \
+        FrameFolderVideos(args.data, image_size=args.size, num_frames=args.frames, sampling="random", jitter=True)
+    return ds, None
+
+
+def main():
+    args = parse_args()
     if not torch.cuda.is_available():
         sys.exit("tools/train_dm.py needs a GPU: the training step is liblfdm_hip.so only")
 
@@ -103,8 +123,7 @@ def main():
     torch.manual_seed(args.seed + 1 + rank)     # per-rank streams for t / noise / null-cond mask / data order
     np.random.seed(args.seed + 1 + rank)
 
-    ds = SyntheticVideos(n=256, image_size=args.size, num_frames=args.frames) if args.synthetic else \
-        FrameFolderVideos(args.data, image_size=args.size, num_frames=args.frames, sampling="random", jitter=True)
+    ds, prep = make_dataset(args)
     sampler = data.distributed.DistributedSampler(ds, world, rank, shuffle=True, seed=args.seed) if world > 1 else None
     loader = data.DataLoader(ds, batch_size=args.batch_size, shuffle=sampler is None, sampler=sampler,
                              num_workers=args.num_workers, pin_memory=True, drop_last=True)
@@ -115,8 +134,12 @@ def main():
     while step < args.final_step:
         if sampler is not None:
             sampler.set_epoch(epoch)
-        for real_vids, ref_texts, real_names in loader:
-            real_vids = real_vids.cuda(non_blocking=True)
+        for batch in loader:
+            if prep is None:
+                real_vids, ref_texts, real_names = batch
+                real_vids = real_vids.cuda(non_blocking=True)
+            else:
+                real_vids, ref_texts, real_names = prep(batch), batch[3], batch[4]
             ref_imgs = real_vids[:, :, 0].clone().detach()                    # first frame = reference frame (:221)
             model.set_train_input(ref_img=ref_imgs, real_vid=real_vids, ref_text=list(ref_texts))
             model.optimize_parameters()
