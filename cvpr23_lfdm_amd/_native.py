@@ -209,6 +209,11 @@ _SIGNATURES = {
     "lfdm_attention_bwd_ws_bytes": (sz, [i32, i32, i32, i32]),
     "lfdm_attention_bwd_cl_f32": (i32, [f32p, f32p, f32p, i32, i32, i32, i32, f32p, f32p, f32p, f32p, C.c_void_p, sz,
                                        stream_t]),
+    # ---- long attention, 65 .. 256 tokens (additive, ABI stays 12)
+    "lfdm_attention_long_cl_f32": (i32, [f32p, f32p, i32, i32, i32, i32, f32p, f32p, f32p, f32p, stream_t]),
+    "lfdm_attention_long_bwd_ws_bytes": (sz, [i32, i32, i32, i32]),
+    "lfdm_attention_long_bwd_cl_f32": (i32, [f32p, f32p, f32p, i32, i32, i32, i32, f32p, f32p, f32p, f32p, C.c_void_p, sz,
+                                            stream_t]),
     "lfdm_linear_attention_bwd_ws_bytes": (sz, [i32]),
     "lfdm_linear_attention_bwd_cl_f32": (i32, [f32p, f32p, f32p, i32, i32, C.c_void_p, sz, stream_t]),
     "lfdm_adam_step_f32": (i32, [f32p, f32p, f32p, f32p, i64, f32, f32, f32, f32, f32, i32, f32, stream_t]),

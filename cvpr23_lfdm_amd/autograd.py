@@ -359,7 +359,9 @@ class LayerNormCL(Function):
 
 
 class AttentionCL(Function):
-    """Attention.forward core (:303-363) on qkv rows; bias = (8, L, L) relative-position table or None."""
+    """Attention.forward core (:303-363) on qkv rows; bias = (8, L, L) relative-position table or None.  More than 64 tokens per sequence
+    run on the streaming pair (ops.attention_long_cl / train_ops.attention_long_bwd): same saved tensors, same gradients - the long
+    backward recomputes its row statistics, so the forward saves none."""
 
     @staticmethod
     def forward(ctx, qkv, bias, rot_cos, rot_sin, batch, frames, hw, mode):
@@ -367,13 +369,15 @@ class AttentionCL(Function):
         b = None if bias is None else _c(bias.detach())
         ctx.save_for_backward(q, b, rot_cos, rot_sin)
         ctx.meta = (batch, frames, hw, mode)
-        return ops.attention_cl(q, batch, frames, hw, mode, bias=b, rot_cos=rot_cos, rot_sin=rot_sin)
+        fwd = ops.attention_long_cl if (frames if mode == 0 else hw) > ops.ATTN_SHORT_MAX else ops.attention_cl
+        return fwd(q, batch, frames, hw, mode, bias=b, rot_cos=rot_cos, rot_sin=rot_sin)
 
     @staticmethod
     def backward(ctx, dout):
         q, b, rot_cos, rot_sin = ctx.saved_tensors
         batch, frames, hw, mode = ctx.meta
-        dqkv, dbias = train_ops.attention_bwd(q, _c(dout), batch, frames, hw, mode, bias=b, rot_cos=rot_cos, rot_sin=rot_sin)
+        bwd = train_ops.attention_long_bwd if (frames if mode == 0 else hw) > ops.ATTN_SHORT_MAX else train_ops.attention_bwd
+        dqkv, dbias = bwd(q, _c(dout), batch, frames, hw, mode, bias=b, rot_cos=rot_cos, rot_sin=rot_sin)
         return dqkv, dbias, None, None, None, None, None, None
 
 

@@ -15,7 +15,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _native, ops
-from .unet import check_num_frames
+from .unet import check_num_frames, frame_limit
 
 
 def cosine_beta_schedule(timesteps, s=0.008):
@@ -43,13 +43,22 @@ class GaussianDiffusion(nn.Module):
     def __init__(self, denoise_fn, *, image_size, num_frames, text_use_bert_cls=False, channels=3,
                  timesteps=1000, sampling_timesteps=250, ddim_sampling_eta=1., loss_type='l1',
                  use_dynamic_thres=False, dynamic_thres_percentile=0.9, null_cond_prob=0.1,
-                 per_element_loss=False, sampler="reference"):
+                 per_element_loss=False, sampler="reference", long_attention=False):
         """Reference signature + `sampler` (keyword): what `sample()` runs.  "reference" (default): the reference's own pair, DDIM when
         sampling_timesteps < timesteps, ancestral DDPM otherwise.  "dpmpp_2m": DPM-Solver++(2M) (Lu et al. 2022), the second-order multistep
         rule on the thresholded data prediction, one UNet evaluation per step, on the reference's DDIM time grid; "dpmpp_1": its first-order
         form on every step.  Both are deterministic: nothing is drawn after x_T and `ddim_sampling_eta` is ignored (`_ms_step_tables`)."""
         super().__init__()
-        check_num_frames(num_frames)
+        # long_attention (keyword, default False): up to 256 frames; the denoiser must have been built with the same option (Unet3D)
+        self.long_attention = bool(long_attention)
+        check_num_frames(num_frames, frame_limit(self.long_attention))
+        if self.long_attention:
+            if not getattr(denoise_fn, "long_attention", False):
+                raise ValueError("long_attention=True needs a denoiser built with long_attention=True")
+            denoise_fn.check_geometry(num_frames, image_size)
+            if use_dynamic_thres and channels * num_frames * image_size * image_size >= 1 << 24:
+                raise ValueError("%d frames of %d x %d: dynamic thresholding takes its quantile over fewer than 2^24 values per sample"
+                                 % (num_frames, image_size, image_size))
         self.sampler = sampler
         # True = the *_multiGPU.py flavour of the reference (video_flow_diffusion_multiGPU.py:857-880):
         # un-reduced loss tensor and `(loss, null_cond_mask)` as the return value of p_losses / forward
@@ -328,6 +337,8 @@ class GaussianDiffusion(nn.Module):
         pk = unet.packed()
         dev = next(unet.parameters()).device
         batch, ch, frames, s, _ = shape
+        if getattr(unet, "long_attention", False):
+            unet.check_geometry(frames, s)        # (frames / mid-block pixels the streaming kernels do not take: before the first launch)
         n = ch * frames * s * s
         multistep = sampler != "reference"
         times, coef_dev, t_table, draws = self._ms_step_tables_on(sampler, dev) if multistep else self._step_tables_on(ddim, dev)

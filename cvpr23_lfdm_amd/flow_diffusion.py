@@ -18,7 +18,7 @@ from .diffusion import GaussianDiffusion
 from .generator import Generator
 from .params import ParamTree, bg_predictor_spec, build_tree, region_predictor_spec
 from .optim import FlatAdam, GradAllReduce
-from .unet import Unet3D, check_num_frames
+from .unet import Unet3D, check_num_frames, frame_limit
 
 
 class RegionPredictor(ParamTree):
@@ -70,7 +70,7 @@ class FlowDiffusion(nn.Module):
                  adam_betas=(0.9, 0.99), is_train=True, only_use_flow=True, use_residual_flow=False,
                  learn_null_cond=False, use_deconv=True, padding_mode="zeros", pretrained_pth="",
                  config_pth="", bert_path=None, *, conv_precision="fp32", sampler="reference", ema_decay=None, ema_start_step=0,
-                 max_grad_norm=None, skip_nonfinite=False):
+                 max_grad_norm=None, skip_nonfinite=False, long_attention=False):
         """Reference signature (video_flow_diffusion_model.py:19-37) + `bert_path`: a local Hugging Face directory of
         bert-base-cased for `cond=list[str]` (the reference downloads it with torch.hub; see text.py).  LFDM_BERT_PATH in
         the environment is the default, so unchanged caller scripts pick it up.
@@ -80,9 +80,12 @@ class FlowDiffusion(nn.Module):
         (DPM-Solver++(2M): second order, deterministic, meant for few steps) or "dpmpp_1"; composes with conv_precision.
         ema_decay / ema_start_step / max_grad_norm / skip_nonfinite (keyword only, all off by default; training only): FlatAdam's options -
         an exponential moving average of the denoiser's weights (`ema_weights()`, `ema_state_dict()`), global-norm gradient clipping and a
-        guard that skips a step whose gradient is not finite, all decided on the device inside the optimizer step."""
+        guard that skips a step whose gradient is not finite, all decided on the device inside the optimizer step.
+        long_attention (keyword only, default False): Unet3D.long_attention - up to 256 frames per window (and up to 256 pixels per frame in
+        the mid block) on the streaming attention kernels, for sampling and training."""
         super().__init__()
-        check_num_frames(num_frames)        # (before the checkpoint and the config are read)
+        self.long_attention = bool(long_attention)
+        check_num_frames(num_frames, frame_limit(self.long_attention))        # (before the checkpoint and the config are read)
         if sampler not in GaussianDiffusion.SAMPLERS:
             raise ValueError("sampler must be one of %s, got %r" % (GaussianDiffusion.SAMPLERS, sampler))
         self.use_residual_flow = use_residual_flow
@@ -104,12 +107,14 @@ class FlowDiffusion(nn.Module):
                 self.set_requires_grad(net, False)
         self.unet = Unet3D(dim=64, channels=3 + 256, out_grid_dim=2, out_conf_dim=1, dim_mults=dim_mults,
                            use_bert_text_cond=True, learn_null_cond=learn_null_cond,
-                           use_final_activation=False, use_deconv=use_deconv, padding_mode=padding_mode)
+                           use_final_activation=False, use_deconv=use_deconv, padding_mode=padding_mode,
+                           long_attention=self.long_attention)
         self.unet.conv_precision = conv_precision
         self.diffusion = GaussianDiffusion(self.unet, image_size=img_size, num_frames=num_frames,
                                            sampling_timesteps=sampling_timesteps, timesteps=timesteps,
                                            loss_type='l2', use_dynamic_thres=True,
-                                           null_cond_prob=null_cond_prob, ddim_sampling_eta=ddim_sampling_eta, sampler=sampler)
+                                           null_cond_prob=null_cond_prob, ddim_sampling_eta=ddim_sampling_eta, sampler=sampler,
+                                           long_attention=self.long_attention)
         bert_path = bert_path or os.environ.get("LFDM_BERT_PATH")
         if bert_path:
             from .text import BertTextEncoder

@@ -567,6 +567,27 @@ def attention_cl(qkv, batch, frames, hw, mode, *, bias=None, rot_cos=None, rot_s
     return out
 
 
+ATTN_SHORT_MAX = 64       # tokens per sequence of attention_cl and the fused forms
+ATTN_LONG_MAX = 256       # tokens per sequence of attention_long_cl
+
+
+def attention_long_cl(qkv, batch, frames, hw, mode, *, bias=None, rot_cos=None, rot_sin=None, out=None, stats=None):
+    """attention_cl over 65 .. 256 tokens per sequence (streaming kernel; 64 and fewer are refused: attention_cl owns them).
+    stats: optional (nseq * 8, 2, L) tensor that receives the row maxima and row sums."""
+    lib = _lib()
+    _chk(lib, qkv, bias, rot_cos, rot_sin, out, stats)
+    assert qkv.shape[1] == 768 and qkv.is_contiguous()
+    if stats is not None:
+        seq = frames if mode == 0 else hw
+        nseq = batch * hw if mode == 0 else batch * frames
+        assert stats.is_contiguous() and stats.numel() == nseq * 8 * 2 * seq
+    if out is None:
+        out = torch.empty(qkv.shape[0], 256, dtype=torch.float32, device=qkv.device)
+    lib.check(lib.lfdm_attention_long_cl_f32(_p(qkv), _p(out), batch, frames, hw, mode, _p(bias),
+                                             _p(rot_cos), _p(rot_sin), _p(stats), _stream(lib)), "lfdm_attention_long_cl_f32")
+    return out
+
+
 def temporal_attention_fused_cl(x, wqkv, batch, frames, hw, *, bias=None, rot_cos=None, rot_sin=None, eps=1e-5, out=None):
     """LayerNorm + to_qkv + temporal attention in one launch (C in {64, 128}); wqkv (768, C) with gamma folded."""
     lib = _lib()

@@ -15,15 +15,23 @@ from .params import ParamTree, build_tree, unet_spec, weights_epoch
 
 BERT_MODEL_DIM = 768
 # Every temporal-attention kernel (csrc/attention*.hip, attn_lowres.hip, train_attention.hip) holds one pixel's whole sequence of
-# frames in a wavefront's registers and is built for 1 ... 64 frames.
+# frames in a wavefront's registers and is built for 1 ... 64 frames.  The same limit holds for the mid block's spatial attention (one
+# frame's pixels are the sequence).  Opt-in (`Unet3D(long_attention=True)`): sequences of 65 ... 256 tokens run on the streaming kernels of
+# csrc/attention_long.hip (ops.attention_long_cl / train_ops.attention_long_bwd) behind the unfused LayerNorm-folded to_qkv and the to_out
+# convolution; everything up to 64 tokens keeps its kernels and its launches.
 MAX_FRAMES = 64
+MAX_FRAMES_LONG = ops.ATTN_LONG_MAX       # 256
 
 
-def check_num_frames(num_frames):
+def check_num_frames(num_frames, limit=MAX_FRAMES):
     """ValueError for a frame count the temporal-attention kernels are not built for - at construction / call time, not at the
-    first temporal-attention launch in the middle of a sample or training step."""
-    if not 1 <= int(num_frames) <= MAX_FRAMES:
-        raise ValueError("num_frames = %d: the temporal-attention kernels are built for 1 ... %d frames" % (int(num_frames), MAX_FRAMES))
+    first temporal-attention launch in the middle of a sample or training step.  limit: the model's (`Unet3D.max_frames`)."""
+    if not 1 <= int(num_frames) <= limit:
+        raise ValueError("num_frames = %d: the temporal-attention kernels are built for 1 ... %d frames" % (int(num_frames), limit))
+
+
+def frame_limit(long_attention):
+    return MAX_FRAMES_LONG if long_attention else MAX_FRAMES
 
 
 # Default-on fusions keep ONE switch each for A/B profiling and for the bit-compare tests (LFDM_x=0 -> the separate launches):
@@ -81,8 +89,12 @@ class Unet3D(ParamTree):
                  channels=3, attn_heads=8, attn_dim_head=32, use_bert_text_cond=False, init_dim=None,
                  init_kernel_size=7, use_sparse_linear_attn=True, resnet_groups=8,
                  use_final_activation=False, learn_null_cond=False, use_deconv=True,
-                 padding_mode="zeros"):
+                 padding_mode="zeros", long_attention=False):
+        """Reference signature + `long_attention` (default False: nothing changes).  True: up to 256 frames, and a mid block of up to
+        256 pixels per frame, on the streaming attention kernels; sequences of up to 64 tokens run as before."""
         super().__init__()
+        self.long_attention = bool(long_attention)
+        self.max_frames = frame_limit(self.long_attention)
         if attn_heads != 8 or attn_dim_head != 32 or resnet_groups != 8 or not use_sparse_linear_attn \
                 or use_final_activation or init_dim not in (None, dim) or init_kernel_size != 7:
             raise NotImplementedError("Unet3D: only the configuration the LFDM scripts use is built "
@@ -459,6 +471,25 @@ class Unet3D(ParamTree):
         self._conv(x, pk[prefix + "qkv.w"], 768, 1, n_img, s, out=qkv, ln_wsum=pk[prefix + "qkv.wsum"])
         return qkv, self._buf("at.o", rows, 256)
 
+    def _attention(self, qkv, batch, frames, hw, mode, att, **tables):
+        """The softmax-attention core on the qkv rows: up to 64 tokens per sequence on ops.attention_cl; more on the streaming kernel
+        when the model was built with long_attention (without it attention_cl refuses them, as it always has)."""
+        if self.long_attention and (frames if mode == 0 else hw) > ops.ATTN_SHORT_MAX:
+            return ops.attention_long_cl(qkv, batch, frames, hw, mode, out=att, **tables)
+        return ops.attention_cl(qkv, batch, frames, hw, mode, out=att, **tables)
+
+    def check_geometry(self, frames, s):
+        """ValueError before the first launch for a call this model's attention kernels do not take: the frame count, and with
+        long_attention the pixels per frame of the latent and of the mid block (its spatial attention's sequence)."""
+        check_num_frames(frames, self.max_frames)
+        if self.long_attention:
+            if s * s > 64 * 64:      # (lfdm_linear_attention_fused*_cl_f32 at C = 64: the level-0 blocks of every model)
+                raise ValueError("%d x %d frames: the fused linear attention is built for at most 64 x 64 pixels per frame" % (s, s))
+            mid = (s >> (len(self.dim_mults) - 1)) ** 2
+            if mid > ops.ATTN_LONG_MAX:
+                raise ValueError("%d x %d frames: the mid block's spatial attention runs over %d pixels per frame, the attention kernels "
+                                 "are built for at most %d" % (s, s, mid, ops.ATTN_LONG_MAX))
+
     def _temporal_attn(self, pk, prefix, x, batch, frames, s, c, outname, tables, focus=None):
         bias, cos, sin = tables
         if focus is not None and any(focus):
@@ -467,7 +498,7 @@ class Unet3D(ParamTree):
             # projection for those samples, on the attention output for the others (library launches on row ranges; never captured)
             qkv, att = self._attn_common(pk, prefix, x, batch * frames, s, c)
             if not all(focus):
-                ops.attention_cl(qkv, batch, frames, s * s, 0, bias=bias, rot_cos=cos, rot_sin=sin, out=att)
+                self._attention(qkv, batch, frames, s * s, 0, att, bias=bias, rot_cos=cos, rot_sin=sin)
             out = self._buf(outname, x.shape[0], c)
             rows = frames * s * s
             for b in range(batch):
@@ -488,7 +519,7 @@ class Unet3D(ParamTree):
                                     rot_cos=cos, rot_sin=sin, out=att)
         else:
             qkv, att = self._attn_common(pk, prefix, x, batch * frames, s, c)
-            ops.attention_cl(qkv, batch, frames, s * s, 0, bias=bias, rot_cos=cos, rot_sin=sin, out=att)
+            self._attention(qkv, batch, frames, s * s, 0, att, bias=bias, rot_cos=cos, rot_sin=sin)
         out = self._buf(outname, x.shape[0], c)
         return self._conv(att, pk[prefix + "out.w"], c, 1, batch * frames, s, residual=x, out=out)
 
@@ -498,7 +529,7 @@ class Unet3D(ParamTree):
             ops.attention_lowres_cl(x, pk[prefix + "qkv.wf"], pk[prefix + "qkv.wsum"], batch, frames, s * s, 1, out=att)
         else:
             qkv, att = self._attn_common(pk, prefix, x, batch * frames, s, c)
-            ops.attention_cl(qkv, batch, frames, s * s, 1, out=att)
+            self._attention(qkv, batch, frames, s * s, 1, att)
         out = self._buf(outname, x.shape[0], c)
         return self._conv(att, pk[prefix + "out.w"], c, 1, batch * frames, s, residual=x, out=out)
 
@@ -631,7 +662,7 @@ class Unet3D(ParamTree):
         (fea may differ per frame here; the samplers use the cheaper split path where it is constant)."""
         if self.has_cond and cond is None:
             raise AssertionError("cond must be passed in if cond_dim specified")
-        check_num_frames(x.shape[2])
+        self.check_geometry(x.shape[2], x.shape[3])
         # :542-543: drawn BEFORE the null-condition mask (it consumes the RNG for 0 < prob < 1)
         if focus_present_mask is None and prob_focus_present in (0, 1):      # (no random draw, no device round trip)
             focus = [True] * x.shape[0] if prob_focus_present == 1 else None

@@ -16,7 +16,7 @@ import torch.nn.functional as F
 
 from . import autograd as A
 from . import ops, train_ops
-from .unet import check_num_frames, prob_mask_like, rel_pos_bias_table
+from .unet import prob_mask_like, rel_pos_bias_table
 
 
 def _time_embedding(unet, time):
@@ -112,7 +112,7 @@ def unet_train_forward(unet, x_dyn, fea, time, cond, null_cond_prob=0., none_con
                        prob_focus_present=0.):
     """x_dyn (B, 3, T, S, S) noisy flow/occlusion, fea (B, 256, S, S) reference-image features (constant over T),
     time (B,) long, cond (B, 768)  ->  eps_hat (B, 3, T, S, S) with grad to every UNet parameter."""
-    check_num_frames(x_dyn.shape[2])
+    unet.check_geometry(x_dyn.shape[2], x_dyn.shape[3])
     g = unet.get
     c = _Ctx()
     A.repack_stale()          # every Winograd filter the previous step used (forward + data-gradient forms): one launch

@@ -610,6 +610,27 @@ int lfdm_attention_bwd_cl_f32(const float* qkv, const float* dout, float* dqkv, 
                               const float* rot_sin, float* dbias, void* ws, size_t ws_bytes,
                               lfdm_stream_t stream);
 
+/* Long attention (additive under ABI 12; csrc/attention_long.hip): the same attention over 65 <= L <= 256 tokens per sequence, streaming
+ * key / value tiles of 16 tokens past a resident block of queries (two-sweep softmax: exact row maximum first, then exp / sum / P V).
+ * Arguments, row layouts, modes, bias (8, L, L) and rotary tables (L, 16) exactly as lfdm_attention_cl_f32 / lfdm_attention_bwd_cl_f32.
+ * L <= 64 is refused (LFDM_EINVAL: the short kernels own that range, nothing is dispatched twice), L > 256 is refused with a message
+ * naming 256; a refused call writes nothing.
+ *   forward:  stats (may be NULL) receives, per (sequence, head), the row maxima and the row sums of exp(s - max):
+ *             (nseq * 8, 2, L) floats, nseq = batch * hw (mode 0) or batch * frames (mode 1).
+ *   backward: two-phase flash form, P and dP recomputed from qkv (nothing else saved), dbias iff bias; no atomics, every output element
+ *             has one owner, bias partials summed in a fixed order: bit-identical from run to run.  ws is ALWAYS required, 16-byte
+ *             aligned, lfdm_attention_long_bwd_ws_bytes: 3 * nseq * 8 * roundup(L, 16) floats of row statistics plus
+ *             G * 8 * L * L floats of bias partials, G = min(nseq, max(1, 2048 / (8 * ceil(L / 16)))) - at most 32 MB, independent of
+ *             batch * hw.  The query returns 0 for a shape the entry point refuses. */
+int lfdm_attention_long_cl_f32(const float* qkv, float* out, int batch, int frames, int hw, int mode,
+                               const float* bias, const float* rot_cos, const float* rot_sin, float* stats,
+                               lfdm_stream_t stream);
+size_t lfdm_attention_long_bwd_ws_bytes(int batch, int frames, int hw, int mode);
+int lfdm_attention_long_bwd_cl_f32(const float* qkv, const float* dout, float* dqkv, int batch, int frames,
+                                   int hw, int mode, const float* bias, const float* rot_cos,
+                                   const float* rot_sin, float* dbias, void* ws, size_t ws_bytes,
+                                   lfdm_stream_t stream);
+
 /* Backward of lfdm_linear_attention_cl_f32 (SpatialLinearAttention core, :254-263): dqkv rows from qkv, dout. */
 size_t lfdm_linear_attention_bwd_ws_bytes(int n_frames);
 int lfdm_linear_attention_bwd_cl_f32(const float* qkv, const float* dout, float* dqkv, int n_frames,

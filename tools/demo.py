@@ -51,6 +51,7 @@ def build_parser():
     ap.add_argument("--overlap", type=int, default=8, help="latent frames two consecutive windows of --total-frames share")
     ap.add_argument("--use-ema", action="store_true",
                     help="sample from the averaged weights: the checkpoint's 'diffusion_ema' entry (tools/train_dm.py --ema-decay, DESIGN.md 4.4)")
+    ap.add_argument("--long-attention", action="store_true", help="windows of 65 ... 256 frames (and a mid block of up to 256 pixels per frame) on the streaming attention kernels (FlowDiffusion(long_attention=True), DESIGN.md 4.8)")
     ap.add_argument("--render", choices=("host", "device"), default="host",
                     help="where the panel strip is made: host (default; io_compat.video_strip, per frame with numpy / matplotlib) or device "
                          "(one rendering on the GPU and one copy; the fourth panel is then the colour-coded flow, DESIGN.md 4.5)")
@@ -88,7 +89,7 @@ def make_model(args, *, steps=None, sampler=None, conv_precision=None, use_ema=N
     model = FlowDiffusion(is_train=False, img_size=args.size // 4, num_frames=args.frames, sampling_timesteps=steps,
                           null_cond_prob=0.1, config_pth=args.config, pretrained_pth=args.lfae_ckpt,
                           bert_path=None if args.synthetic else args.bert, conv_precision=conv_precision,
-                          sampler=sampler)          # demo_mug.py:80-88
+                          sampler=sampler, long_attention=getattr(args, "long_attention", False))          # demo_mug.py:80-88
     if args.synthetic:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import synth

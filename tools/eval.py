@@ -53,6 +53,7 @@ def build_parser():
         p.add_argument("--steps", type=int, default=100)
         p.add_argument("--conv-precision", choices=("fp32", "bf16"), default="fp32")
         p.add_argument("--use-ema", action="store_true", help="sample from the checkpoint's 'diffusion_ema' entry")
+        p.add_argument("--long-attention", action="store_true", help="windows of 65 ... 256 frames (and a mid block of up to 256 pixels per frame) on the streaming attention kernels (FlowDiffusion(long_attention=True), DESIGN.md 4.8)")
         p.add_argument("--cond-scale", type=float, default=1.0)
         p.add_argument("--seed", type=int, default=1234)
         p.add_argument("--domain", choices=("raw", "unit", "uint8"), default="unit", help="value domain of L1 / PSNR / SSIM (out_loss / warp_loss are always raw)")

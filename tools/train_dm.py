@@ -62,6 +62,7 @@ def parse_args(argv=None):
     ap.add_argument("--packed", default="", help="a store written by tools/pack_videos.py (instead of --data): batches cross to the device "
                     "as bytes and colour jitter, area shrink and normalisation run there")
     ap.add_argument("--resident", action="store_true", help="with --packed: upload the whole store once; a batch is then frame numbers")
+    ap.add_argument("--long-attention", action="store_true", help="windows of 65 ... 256 frames (and a mid block of up to 256 pixels per frame) on the streaming attention kernels (FlowDiffusion(long_attention=True), DESIGN.md 4.8)")
     return ap.parse_args(argv)
 
 
@@ -97,7 +98,7 @@ def main():
                           null_cond_prob=args.null_cond_prob, sampling_timesteps=args.preview_steps or 1000, config_pth=args.config,
                           pretrained_pth=args.lfae_ckpt, bert_path=None if args.synthetic else args.bert,     # :153-162
                           ema_decay=args.ema_decay, ema_start_step=args.ema_start_step, max_grad_norm=args.max_grad_norm,
-                          skip_nonfinite=args.skip_nonfinite)
+                          skip_nonfinite=args.skip_nonfinite, long_attention=args.long_attention)
     opt = model.optimizer_diff
     model.cuda()
     if args.synthetic:
