@@ -381,7 +381,8 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(lfdm_conv_params p) {
   // transpose each 32x32 accumulator tile through a wave-private LDS scratch (aliases the A tile)
   float* scratch = smem + wave * (32 * LD);
   const bool vec_ok = (p.cout % 4 == 0) && (p.ldo % 4 == 0) && ((((uintptr_t)p.out) & 15) == 0) &&
-                      (!p.residual || ((p.ldr % 4 == 0) && ((((uintptr_t)p.residual) & 15) == 0)));
+                      (!p.residual || ((p.ldr % 4 == 0) && ((((uintptr_t)p.residual) & 15) == 0))) &&
+                      (!p.bias || (((uintptr_t)p.bias) & 15) == 0);      // (the same test as make_plan's: pre_b below is a float4 load of bias)
   const int c4 = lane & 7, rsub = lane >> 3;
   float gs[TN][4], gq[TN][4];
 #pragma unroll
@@ -463,6 +464,10 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(lfdm_conv_params p) {
             if (col < p.cout) {
               float t = vals[e];
               if (p.bias) t += p.bias[col];
+              if (p.gn_partial) {      // (a residual or bias that is not 16-byte addressable takes this branch with the statistics requested)
+                gs[j][e] += t;
+                gq[j][e] += t * t;
+              }
               if (p.residual) t += p.residual[orow * p.ldr + col];
               p.out[orow * p.ldo + col] = apply_act(t, p.act);
             }
@@ -1066,8 +1071,9 @@ int conv2d_run(const lfdm_conv_params* pp, const void* wino_bf16, hipStream_t st
   }
   if (p.ln_wsum) {
     if (!pl.fast || !pl.simple || p.kh != 1 || p.kw != 1 || p.c1 != 0 || p.stride != 1 || p.cout % 4 != 0 ||
-        p.ldo % 4 != 0 || (((uintptr_t)p.out) & 15) != 0 || (((uintptr_t)p.ln_wsum) & 15) != 0) {
-      lfdm_set_error("conv2d: fused LayerNorm needs a 1x1 convolution over one source with C % 32 == 0");
+        p.ldo % 4 != 0 || (((uintptr_t)p.out) & 15) != 0 || (((uintptr_t)p.ln_wsum) & 15) != 0 ||
+        (p.residual && (p.ldr % 4 != 0 || (((uintptr_t)p.residual) & 15) != 0)) || (p.bias && (((uintptr_t)p.bias) & 15) != 0)) {      // (float4 epilogue only)
+      lfdm_set_error("conv2d: fused LayerNorm needs a 1x1 convolution over one source with C % 32 == 0 and 16-byte addressable out / residual / bias");
       return LFDM_EINVAL;
     }
   }

@@ -465,6 +465,10 @@ extern "C" int lfdm_groupnorm_silu_cl_f32(const float* x, float* out, int batch,
     lfdm_set_error("groupnorm: unsupported shape (need C%G==0, (C/G)%4==0, 256%(C/4)==0)");
     return LFDM_EINVAL;
   }
+  if (((((uintptr_t)x) | ((uintptr_t)out) | ((uintptr_t)residual)) & 15) != 0) {      // (both kernels walk the rows as float4)
+    lfdm_set_error("groupnorm: x, out and residual must be 16-byte aligned (dense rows of C floats, read and written as float4)");
+    return LFDM_EINVAL;
+  }
   if (!ws || ws_bytes < lfdm_groupnorm_ws_bytes(batch, pixels, channels)) {
     lfdm_set_error("groupnorm: workspace too small");
     return LFDM_EWORKSPACE;
@@ -491,6 +495,10 @@ extern "C" int lfdm_groupnorm_apply_cl_f32(const float* x, float* out, int batch
     lfdm_set_error("groupnorm_apply: bad arguments");
     return LFDM_EINVAL;
   }
+  if (((((uintptr_t)x) | ((uintptr_t)out) | ((uintptr_t)residual)) & 15) != 0 || (((uintptr_t)partial) & 7) != 0) {
+    lfdm_set_error("groupnorm_apply: x, out and residual must be 16-byte aligned (dense rows of C floats, read and written as float4), partial 8-byte");
+    return LFDM_EINVAL;
+  }
   (void)ws;
   (void)ws_bytes;
   launch_gn_apply(x, out, batch, pixels, channels, groups, partial, nchunk, gamma, beta, scale_shift,
@@ -508,7 +516,11 @@ extern "C" int lfdm_layernorm_cl_f32(const float* x, float* out, int64_t rows, i
   int64_t nb = (rows + 3) / 4;
   if (nb > 16384) nb = 16384;
   const bool al16 = ((((uintptr_t)x) | ((uintptr_t)out) | ((uintptr_t)gamma)) & 15) == 0;
-  if ((channels == 64 || channels == 128) && al16 && rows >= 4096) {
+  if (!al16) {      // (every kernel below reads x / gamma and writes out as float4: there is no scalar form)
+    lfdm_set_error("layernorm: x, out and gamma must be 16-byte aligned");
+    return LFDM_EINVAL;
+  }
+  if ((channels == 64 || channels == 128) && rows >= 4096) {
     int64_t nbs = (rows + 4 * (256 / channels) * 2 * 4 - 1) / (4 * (256 / channels) * 2 * 4);      // ~4 trips per wavefront
     if (nbs > 8192) nbs = 8192;
     if (nbs < 1) nbs = 1;
@@ -529,6 +541,10 @@ extern "C" int lfdm_affine_act_cl_f32(const float* x, float* out, int64_t rows, 
     lfdm_set_error("affine_act: unsupported shape");
     return LFDM_EINVAL;
   }
+  if (((((uintptr_t)x) | ((uintptr_t)out) | ((uintptr_t)a) | ((uintptr_t)b)) & 15) != 0) {
+    lfdm_set_error("affine_act: x, out, a and b must be 16-byte aligned (float4 accesses)");
+    return LFDM_EINVAL;
+  }
   LFDM_LAUNCH(affine_act_kernel, dim3(grid_for(rows * (channels / 4))), dim3(256), 0, stream, x, out,
               rows, channels, ldx, ldo, a, b, act);
   return lfdm_check_launch("affine_act");
@@ -539,6 +555,10 @@ extern "C" int lfdm_avgpool2_cl_f32(const float* x, float* out, int n_img, int h
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !out || n_img <= 0 || (h & 1) || (w & 1) || channels % 4 != 0) {
     lfdm_set_error("avgpool2: unsupported shape");
+    return LFDM_EINVAL;
+  }
+  if (((((uintptr_t)x) | ((uintptr_t)out)) & 15) != 0) {
+    lfdm_set_error("avgpool2: x and out must be 16-byte aligned (float4 accesses)");
     return LFDM_EINVAL;
   }
   const int64_t total = (int64_t)n_img * (h / 2) * (w / 2) * (channels / 4);

@@ -636,8 +636,9 @@ extern "C" int lfdm_heads_cl_to_planar_f32(const float* y_flow, const float* y_o
                                            int batch, int frames, int hw, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!y_flow || !y_occ || !w_flow || !b_flow || !w_occ || !b_occ || !out || channels <= 0 ||
-      channels > 256 || channels % 4 != 0 || ld < channels || ld % 4 != 0 || batch <= 0 || frames <= 0 || hw <= 0) {
-    lfdm_set_error("heads: bad arguments");
+      channels > 256 || channels % 4 != 0 || ld < channels || ld % 4 != 0 || batch <= 0 || frames <= 0 || hw <= 0 ||
+      (((uintptr_t)y_flow | (uintptr_t)y_occ) & 15) != 0) {
+    lfdm_set_error("heads: bad arguments (C % 4 == 0, C <= 256, ld % 4 == 0, 16-byte aligned rows)");
     return LFDM_EINVAL;
   }
   const int64_t total = (int64_t)batch * frames * hw;

@@ -435,6 +435,10 @@ extern "C" int lfdm_groupnorm_silu_bwd_cl_f32(const float* x, const float* dy, f
     lfdm_set_error("groupnorm_bwd: bad arguments (C%4==0, C<=1024, C/4 divides 256)");
     return LFDM_EINVAL;
   }
+  if (((((uintptr_t)x) | ((uintptr_t)dy) | ((uintptr_t)dx)) & 15) != 0 || (((uintptr_t)partial) & 7) != 0) {      // (the reduce and dx kernels walk the rows as float4)
+    lfdm_set_error("groupnorm_bwd: x, dy and dx must be 16-byte aligned (dense rows of C floats, read and written as float4), partial 8-byte");
+    return LFDM_EINVAL;
+  }
   if (!ws || ws_bytes < lfdm_groupnorm_bwd_ws_bytes(batch, pixels, channels)) {
     lfdm_set_error("groupnorm_bwd: workspace too small");
     return LFDM_EWORKSPACE;
@@ -484,6 +488,10 @@ extern "C" int lfdm_layernorm_bwd_add_cl_f32(const float* x, const float* dy, co
   }
   const int nb = ln_bwd_blocks(rows);
   const bool al16 = ((((uintptr_t)x) | ((uintptr_t)dy) | ((uintptr_t)dx) | ((uintptr_t)gamma) | ((uintptr_t)dx_add)) & 15) == 0;
+  if (!al16) {      // (all three kernels read x / dy / gamma / dx_add and write dx as float4: there is no scalar form)
+    lfdm_set_error("layernorm_bwd: x, dy, dx, gamma and dx_add must be 16-byte aligned");
+    return LFDM_EINVAL;
+  }
   if (channels == 64 && al16) LFDM_LAUNCH((layernorm_bwd_small_kernel<16>), dim3(nb), dim3(256), 0, stream, x, dy, dx, rows, gamma, eps, (float*)ws, dx_add);
   else if (channels == 128 && al16) LFDM_LAUNCH((layernorm_bwd_small_kernel<32>), dim3(nb), dim3(256), 0, stream, x, dy, dx, rows, gamma, eps, (float*)ws, dx_add);
   else LFDM_LAUNCH(layernorm_bwd_kernel, dim3(nb), dim3(256), 0, stream, x, dy, dx, rows, channels, gamma, eps, (float*)ws, dx_add);

@@ -267,8 +267,8 @@ extern "C" int lfdm_warp_cl_f32(const lfdm_warp_params* pp, lfdm_stream_t stream
   if (rc) return rc;
   lfdm_warp_params p = *pp;
   if (p.c % 4 != 0 || p.ld_src % 4 != 0 || p.ld_out % 4 != 0 || (p.prev && p.ld_prev % 4 != 0) ||
-      p.ld_src < p.c || p.ld_out < p.c) {
-    lfdm_set_error("warp_cl: channels and row strides must be multiples of 4");
+      p.ld_src < p.c || p.ld_out < p.c || (((uintptr_t)p.src | (uintptr_t)p.out | (uintptr_t)p.prev) & 15) != 0) {
+    lfdm_set_error("warp_cl: channels and row strides must be multiples of 4, src / out / prev 16-byte aligned (float4 accesses)");
     return LFDM_EINVAL;
   }
   int r = (p.c % 16 == 0) ? 4 : (p.c % 8 == 0 ? 2 : 1);

@@ -13,7 +13,7 @@ from torch.autograd import Function
 from . import ops, train_ops
 from ._native import BN_TICKETS, BlurParams, GridSampleParams, WarpBwdParams
 from .autograd import grad_out_pair
-from .ops import _chk, _lib, _p, _stream
+from .ops import _chk, _ld, _lib, _p, _stream
 
 _STATE = {}
 
@@ -77,7 +77,7 @@ def batchnorm_train_fwd(x, gamma, beta, running_mean, running_var, momentum, eps
     stat = torch.empty(segments, 2, c, dtype=torch.float32, device=x.device)
     nbytes = lib.lfdm_batchnorm_train_ws_bytes(seg_rows, c, segments)
     ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
-    lib.check(lib.lfdm_batchnorm_train_fwd_cl_f32(_p(x), _p(y), seg_rows, c, segments, x.stride(0), c, _p(gamma), _p(beta), _p(running_mean), _p(running_var),
+    lib.check(lib.lfdm_batchnorm_train_fwd_cl_f32(_p(x), _p(y), seg_rows, c, segments, _ld(x), c, _p(gamma), _p(beta), _p(running_mean), _p(running_var),
                                                   float(momentum), float(eps), int(relu), _p(stat), _p(ws), nbytes, _p(_state(x.device)["tickets"]),
                                                   _stream(lib)), "lfdm_batchnorm_train_fwd_cl_f32")
     return y, stat
@@ -93,8 +93,8 @@ def batchnorm_train_bwd(x, dy, gamma, beta, stat, relu, dgamma=None, dbeta=None,
     dx = torch.empty(rows, c, dtype=torch.float32, device=x.device)
     nbytes = lib.lfdm_batchnorm_train_ws_bytes(seg_rows, c, segments)
     ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
-    lib.check(lib.lfdm_batchnorm_train_bwd_cl_f32(_p(x), _p(dy), _p(dx), seg_rows, c, segments, x.stride(0), dy.stride(0), c, _p(dx_add),
-                                                  0 if dx_add is None else dx_add.stride(0), _p(gamma), _p(beta), _p(stat),
+    lib.check(lib.lfdm_batchnorm_train_bwd_cl_f32(_p(x), _p(dy), _p(dx), seg_rows, c, segments, _ld(x), _ld(dy), c, _p(dx_add),
+                                                  0 if dx_add is None else _ld(dx_add), _p(gamma), _p(beta), _p(stat),
                                                   int(relu), _p(dgamma), _p(dbeta), _p(ws), nbytes, _p(_state(x.device)["tickets"]), _stream(lib)),
               "lfdm_batchnorm_train_bwd_cl_f32")
     return dx
@@ -259,10 +259,10 @@ class ApplyOpticalCL(Function):
         p = WarpBwdParams()
         fh, fw = _warp_bwd_common(p, m, n, h, w, c)
         p.layout_cl, p.n_div = 1, 1
-        p.src, p.ld_src, p.dout, p.ld_dout = sr.data_ptr(), sr.stride(0), dr.data_ptr(), dr.stride(0)
+        p.src, p.ld_src, p.dout, p.ld_dout = sr.data_ptr(), _ld(sr), dr.data_ptr(), _ld(dr)
         dprev = None
         if pr is not None:
-            p.prev, p.ld_prev = pr.data_ptr(), pr.stride(0)
+            p.prev, p.ld_prev = pr.data_ptr(), _ld(pr)
             if need[1]:
                 dprev = torch.empty(n * h * w, c, dtype=torch.float32, device=dev)
                 p.dprev, p.ld_dprev = dprev.data_ptr(), c
@@ -272,7 +272,7 @@ class ApplyOpticalCL(Function):
         if need[0]:
             acc = _fix_acc(dev, n * h * w * c)
             p.dsrc_fix, p.amax_bits = acc.data_ptr(), st["amax"].data_ptr()
-            lib.check(lib.lfdm_absmax_f32(_p(dr), n * h * w, c, dr.stride(0), _p(st["amax"]), _stream(lib)), "lfdm_absmax_f32")
+            lib.check(lib.lfdm_absmax_f32(_p(dr), n * h * w, c, _ld(dr), _p(st["amax"]), _stream(lib)), "lfdm_absmax_f32")
         lib.check(lib.lfdm_warp_bwd_f32(C.byref(p), _stream(lib)), "lfdm_warp_bwd_f32")
         dsrc = None
         if need[0]:

@@ -40,6 +40,23 @@ def _chk(lib, *tensors):
             raise RuntimeError("emulation library needs CPU tensors")
 
 
+def _ld(t):
+    """Row stride of a row operand that goes to the library as a leading dimension (ld0, ldo, ldx, ss_ld, ...): the library walks a row
+    with stride 1, so a transposed or column-strided view is refused here instead of being read as something else."""
+    if t.dim() < 1 or t.stride(-1) != 1:
+        raise ValueError("lfdm ops take row operands with adjacent columns (stride(-1) == 1) and a row stride, got strides %s"
+                         % (tuple(t.stride()),))
+    return t.stride(0)
+
+
+def _dense(*tensors):
+    """Operands whose entry point takes no leading dimension: the library addresses them as one dense block."""
+    for t in tensors:
+        if t is not None and not t.is_contiguous():
+            raise ValueError("this lfdm op takes no row stride for this operand: a contiguous tensor is needed, got strides %s"
+                             % (tuple(t.stride()),))
+
+
 def empty(shape, like=None, device=None, dtype=torch.float32):
     dev = device if device is not None else like.device
     return torch.empty(shape, dtype=dtype, device=dev)
@@ -139,7 +156,7 @@ def lfae_region_stats(logits, n, k, h, w, temperature):
     dev = logits.device
     e = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
     heat, shift, covar, affine, u, d = e(n, k, h, w), e(n, k, 2), e(n, k, 2, 2), e(n, k, 2, 2), e(n * k, 2, 2), e(n * k, 2, 2)
-    lib.check(lib.lfdm_lfae_region_stats_f32(_p(logits), logits.stride(0), n, k, h, w, float(temperature), _p(heat), _p(shift),
+    lib.check(lib.lfdm_lfae_region_stats_f32(_p(logits), _ld(logits), n, k, h, w, float(temperature), _p(heat), _p(shift),
                                              _p(covar), _p(affine), _p(u), _p(d), _stream(lib)), "lfdm_lfae_region_stats_f32")
     return {"shift": shift, "heatmap": heat, "covar": covar, "affine": affine, "u": u, "d": d}
 
@@ -176,7 +193,7 @@ def lfae_motion_combine(heads, sparse, has_occ):
     n, k1, h, w, _ = sparse.shape
     flow = torch.empty(n, h, w, 2, dtype=torch.float32, device=sparse.device)
     occ = torch.empty(n, 1, h, w, dtype=torch.float32, device=sparse.device) if has_occ else None
-    lib.check(lib.lfdm_lfae_motion_combine_f32(_p(heads), heads.stride(0), _p(sparse), n, k1 - 1, h * w, _p(flow), _p(occ),
+    lib.check(lib.lfdm_lfae_motion_combine_f32(_p(heads), _ld(heads), _p(sparse), n, k1 - 1, h * w, _p(flow), _p(occ),
                                                _stream(lib)), "lfdm_lfae_motion_combine_f32")
     return flow, occ
 
@@ -334,14 +351,14 @@ def conv_params(src0, weight, cout, kh, kw, n_img, hi, wi, *, src1=None, bias=No
     p = ConvParams()
     p.src0, p.src1 = _p(src0), _p(src1)
     p.c0, p.c1 = src0.shape[1], (src1.shape[1] if src1 is not None else 0)
-    p.ld0, p.ld1 = src0.stride(0), (src1.stride(0) if src1 is not None else 0)
+    p.ld0, p.ld1 = _ld(src0), (_ld(src1) if src1 is not None else 0)
     p.n_img, p.hi, p.wi, p.hq, p.wq = n_img, hi, wi, hq, wq
     p.stride, p.upsample, p.pad_mode = stride, int(upsample), int(reflect)
     p.kh, p.kw, p.pad_y, p.pad_x = kh, kw, pad_y, pad_x
     p.weight, p.cout, p.coutp, p.bias = _p(weight), cout, coutp, _p(bias)
-    p.out, p.ldo, p.ho, p.wo = _p(out), out.stride(0), ho, wo
+    p.out, p.ldo, p.ho, p.wo = _p(out), _ld(out), ho, wo
     p.out_scale, p.out_off_y, p.out_off_x = out_scale, out_off[0], out_off[1]
-    p.residual, p.ldr = _p(residual), (residual.stride(0) if residual is not None else 0)
+    p.residual, p.ldr = _p(residual), (_ld(residual) if residual is not None else 0)
     p.act, p.ksplit, p.partial = act, ksplit, None
     p.gn_partial, p.gn_groups, p.gn_pixels = None, 0, 0
     p.ln_wsum, p.ln_eps = _p(ln_wsum), ln_eps
@@ -489,8 +506,8 @@ def conv2d_smalln_cl(x, wpacked, bias4, cout, k, n_img, h, w, *, act=ACT_NONE, o
     _chk(lib, x, wpacked, bias4, out)
     if out is None:
         out = torch.empty(n_img * h * w, 4, dtype=torch.float32, device=x.device)
-    lib.check(lib.lfdm_conv2d_smalln_cl_f32(_p(x), x.stride(0), x.shape[1], n_img, h, w, _p(wpacked), _p(bias4), _p(out),
-                                            out.stride(0), cout, k, act, _stream(lib)), "lfdm_conv2d_smalln_cl_f32")
+    lib.check(lib.lfdm_conv2d_smalln_cl_f32(_p(x), _ld(x), x.shape[1], n_img, h, w, _p(wpacked), _p(bias4), _p(out),
+                                            _ld(out), cout, k, act, _stream(lib)), "lfdm_conv2d_smalln_cl_f32")
     return out
 
 
@@ -515,6 +532,7 @@ def groupnorm_silu_cl(x, batch, gamma, beta, *, groups=8, scale_shift=None, resi
     rows, ch = x.shape
     pixels = rows // batch
     _chk(lib, x, gamma, beta, scale_shift, residual, out, ws)
+    _dense(x, residual, out)
     if out is None:
         out = torch.empty_like(x)
     need = lib.lfdm_groupnorm_ws_bytes(batch, pixels, ch)
@@ -522,7 +540,7 @@ def groupnorm_silu_cl(x, batch, gamma, beta, *, groups=8, scale_shift=None, resi
         ws = torch.empty(need // 4, dtype=torch.float32, device=x.device)
     lib.check(lib.lfdm_groupnorm_silu_cl_f32(_p(x), _p(out), batch, pixels, ch, groups, _p(gamma),
                                              _p(beta), _p(scale_shift),
-                                             scale_shift.stride(0) if scale_shift is not None else 0,
+                                             _ld(scale_shift) if scale_shift is not None else 0,
                                              _p(residual), eps, int(silu), _p(ws),
                                              ws.numel() * 4, _stream(lib)), "lfdm_groupnorm_silu_cl_f32")
     return out
@@ -534,13 +552,14 @@ def groupnorm_apply_cl(x, batch, gamma, beta, partial, nchunk, *, groups=8, scal
     lib = _lib()
     rows, ch = x.shape
     _chk(lib, x, gamma, beta, partial, scale_shift, residual, out, ws)
+    _dense(x, residual, out, partial)
     if out is None:
         out = torch.empty_like(x)
     if ws is None:
         ws = torch.empty(batch * 2 * ch, dtype=torch.float32, device=x.device)
     lib.check(lib.lfdm_groupnorm_apply_cl_f32(_p(x), _p(out), batch, rows // batch, ch, groups, _p(gamma), _p(beta),
                                               _p(scale_shift),
-                                              scale_shift.stride(0) if scale_shift is not None else 0,
+                                              _ld(scale_shift) if scale_shift is not None else 0,
                                               _p(residual), eps, int(silu), _p(partial), nchunk, _p(ws),
                                               ws.numel() * 4, _stream(lib)), "lfdm_groupnorm_apply_cl_f32")
     return out
@@ -549,6 +568,7 @@ def groupnorm_apply_cl(x, batch, gamma, beta, partial, nchunk, *, groups=8, scal
 def layernorm_cl(x, gamma, eps=1e-5, out=None):
     lib = _lib()
     _chk(lib, x, gamma, out)
+    _dense(x, out)
     if out is None:
         out = torch.empty_like(x)
     lib.check(lib.lfdm_layernorm_cl_f32(_p(x), _p(out), x.shape[0], x.shape[1], _p(gamma), eps,
@@ -596,7 +616,7 @@ def temporal_attention_fused_cl(x, wqkv, batch, frames, hw, *, bias=None, rot_co
     assert wqkv.shape == (768, c) and wqkv.is_contiguous()
     if out is None:
         out = torch.empty(x.shape[0], 256, dtype=torch.float32, device=x.device)
-    lib.check(lib.lfdm_temporal_attention_fused_cl_f32(_p(x), x.stride(0), c, _p(wqkv), _p(out), batch, frames, hw, _p(bias),
+    lib.check(lib.lfdm_temporal_attention_fused_cl_f32(_p(x), _ld(x), c, _p(wqkv), _p(out), batch, frames, hw, _p(bias),
                                                        _p(rot_cos), _p(rot_sin), eps, _stream(lib)),
               "lfdm_temporal_attention_fused_cl_f32")
     return out
@@ -632,7 +652,7 @@ def temporal_attention_fused_out_cl(x, wqkv, wout, batch, frames, hw, *, bias=No
     if out is None:
         out = torch.empty(x.shape[0], c, dtype=torch.float32, device=x.device)
     assert out.data_ptr() != x.data_ptr()
-    lib.check(lib.lfdm_temporal_attention_fused_out_cl_f32(_p(x), x.stride(0), c, _p(wqkv), _p(wout), _p(out), out.stride(0), batch, frames, hw,
+    lib.check(lib.lfdm_temporal_attention_fused_out_cl_f32(_p(x), _ld(x), c, _p(wqkv), _p(wout), _p(out), _ld(out), batch, frames, hw,
                                                            _p(bias), _p(rot_cos), _p(rot_sin), eps, _stream(lib)),
               "lfdm_temporal_attention_fused_out_cl_f32")
     return out
@@ -662,7 +682,7 @@ def linear_attention_fused_cl(x, wqkv, n_frames, hw, *, eps=1e-5, out=None, ws=N
         ws = ws.reshape(-1)
     if ws is None or ws.numel() * 4 < need:
         ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=x.device)
-    lib.check(lib.lfdm_linear_attention_fused_cl_f32(_p(x), x.stride(0), x.shape[1], _p(wqkv), _p(out), n_frames, hw, eps,
+    lib.check(lib.lfdm_linear_attention_fused_cl_f32(_p(x), _ld(x), x.shape[1], _p(wqkv), _p(out), n_frames, hw, eps,
                                                      _p(ws), ws.numel() * 4, _stream(lib)),
               "lfdm_linear_attention_fused_cl_f32")
     return out
@@ -690,7 +710,7 @@ def linear_attention_fused_out_cl(x, wqkv, wout, bias_out, n_frames, hw, *, eps=
         ws = ws.reshape(-1)
     if ws is None or ws.numel() * 4 < need:
         ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=x.device)
-    lib.check(lib.lfdm_linear_attention_fused_out_cl_f32(_p(x), x.stride(0), x.shape[1], _p(wqkv), _p(wout), _p(bias_out), _p(out), out.stride(0),
+    lib.check(lib.lfdm_linear_attention_fused_out_cl_f32(_p(x), _ld(x), x.shape[1], _p(wqkv), _p(wout), _p(bias_out), _p(out), _ld(out),
                                                          n_frames, hw, eps, _p(ws), ws.numel() * 4, _stream(lib)),
               "lfdm_linear_attention_fused_out_cl_f32")
     return out
@@ -704,7 +724,7 @@ def linear_attention_lowres_cl(x, wqkv, wsum, n_frames, hw, *, eps=1e-5, out=Non
     assert wqkv.shape == (768, x.shape[1]) and wqkv.is_contiguous() and wsum.numel() >= 768
     if out is None:
         out = torch.empty(x.shape[0], 256, dtype=torch.float32, device=x.device)
-    lib.check(lib.lfdm_linear_attention_lowres_cl_f32(_p(x), x.stride(0), x.shape[1], _p(wqkv), _p(wsum), _p(out), n_frames, hw, eps,
+    lib.check(lib.lfdm_linear_attention_lowres_cl_f32(_p(x), _ld(x), x.shape[1], _p(wqkv), _p(wsum), _p(out), n_frames, hw, eps,
                                                       _stream(lib)), "lfdm_linear_attention_lowres_cl_f32")
     return out
 
@@ -721,7 +741,7 @@ def attention_lowres_cl(x, wqkv, wsum, batch, frames, hw, mode, *, bias=None, ro
     assert wqkv.shape == (768, x.shape[1]) and wqkv.is_contiguous() and wsum.numel() >= 768
     if out is None:
         out = torch.empty(x.shape[0], 256, dtype=torch.float32, device=x.device)
-    lib.check(lib.lfdm_attention_lowres_cl_f32(_p(x), x.stride(0), x.shape[1], _p(wqkv), _p(wsum), _p(out), batch, frames, hw, mode,
+    lib.check(lib.lfdm_attention_lowres_cl_f32(_p(x), _ld(x), x.shape[1], _p(wqkv), _p(wsum), _p(out), batch, frames, hw, mode,
                                                _p(bias), _p(rot_cos), _p(rot_sin), eps, _stream(lib)), "lfdm_attention_lowres_cl_f32")
     return out
 
@@ -748,7 +768,7 @@ def linear_small(x, w, bias=None, *, act_in=ACT_NONE, act_out=ACT_NONE, out=None
     assert w.shape[1] == k and w.stride(1) == 1
     if out is None:
         out = torch.empty(batch, n, dtype=torch.float32, device=x.device)
-    lib.check(lib.lfdm_linear_small_f32(_p(x), _p(w), _p(bias), _p(out), batch, k, n, x.stride(0),
+    lib.check(lib.lfdm_linear_small_f32(_p(x), _p(w), _p(bias), _p(out), batch, k, n, _ld(x),
                                         w.stride(0), out.stride(0), act_in, act_out, _stream(lib)),
               "lfdm_linear_small_f32")
     return out
@@ -809,7 +829,7 @@ def sinusoidal(t_dev, freqs, batch, dim, *, t_stride=1, out=None):
     assert t_dev.dtype == torch.int32
     if out is None:
         out = torch.empty(batch, dim, dtype=torch.float32, device=t_dev.device)
-    lib.check(lib.lfdm_sinusoidal_f32(_p(t_dev), t_stride, _p(freqs), _p(out), batch, dim, out.stride(0),
+    lib.check(lib.lfdm_sinusoidal_f32(_p(t_dev), t_stride, _p(freqs), _p(out), batch, dim, _ld(out),
                                       _stream(lib)), "lfdm_sinusoidal_f32")
     return out
 
@@ -821,7 +841,7 @@ def conv_planar_in_cl(x, batch, cin, cin_total, frames, h, w, wgt, kh, kw, cout,
     if out is None:
         out = torch.empty(batch * frames * h * w, cout, dtype=torch.float32, device=x.device)
     lib.check(lib.lfdm_conv_planar_in_cl_f32(_p(x), batch, cin, cin_total, frames, h, w, _p(wgt), kh, kw,
-                                             cout, _p(bias), _p(add_term), _p(out), out.stride(0), act,
+                                             cout, _p(bias), _p(add_term), _p(out), _ld(out), act,
                                              _stream(lib)), "lfdm_conv_planar_in_cl_f32")
     return out
 
@@ -834,7 +854,7 @@ def heads_cl_to_planar(y_flow, y_occ, w_flow, b_flow, w_occ, b_occ, batch, frame
     assert y_flow.stride(0) == y_occ.stride(0) and y_flow.stride(1) == 1 and y_occ.stride(1) == 1
     if out is None:
         out = torch.empty(batch, 3, frames, hw, dtype=torch.float32, device=y_flow.device)
-    lib.check(lib.lfdm_heads_cl_to_planar_f32(_p(y_flow), _p(y_occ), ch, y_flow.stride(0), _p(w_flow), _p(b_flow),
+    lib.check(lib.lfdm_heads_cl_to_planar_f32(_p(y_flow), _p(y_occ), ch, _ld(y_flow), _p(w_flow), _p(b_flow),
                                               _p(w_occ), _p(b_occ), _p(out), batch, frames, hw,
                                               _stream(lib)), "lfdm_heads_cl_to_planar_f32")
     return out
@@ -851,8 +871,8 @@ def heads_res_cl_to_planar(y_flow, y_occ, w_flow, b_flow, w_occ, b_occ, x0, x1, 
     assert w_extra.shape == (3, c0 + c1) and w_extra.is_contiguous() and x0.stride(1) == 1
     if out is None:
         out = torch.empty(batch, 3, frames, hw, dtype=torch.float32, device=y_flow.device)
-    lib.check(lib.lfdm_heads_res_cl_to_planar_f32(_p(y_flow), _p(y_occ), ch, y_flow.stride(0), _p(w_flow), _p(b_flow), _p(w_occ), _p(b_occ),
-                                                  _p(x0), x0.stride(0), c0, _p(x1), x1.stride(0) if x1 is not None else 0, c1, _p(w_extra),
+    lib.check(lib.lfdm_heads_res_cl_to_planar_f32(_p(y_flow), _p(y_occ), ch, _ld(y_flow), _p(w_flow), _p(b_flow), _p(w_occ), _p(b_occ),
+                                                  _p(x0), _ld(x0), c0, _p(x1), _ld(x1) if x1 is not None else 0, c1, _p(w_extra),
                                                   _p(out), batch, frames, hw, _stream(lib)), "lfdm_heads_res_cl_to_planar_f32")
     return out
 
@@ -865,12 +885,13 @@ def heads_gn_res_cl_to_planar(y, partial, nchunk, gamma, beta, w_flow, b_flow, w
     _chk(lib, y, partial, gamma, beta, w_flow, b_flow, w_occ, b_occ, x0, x1, w_extra, out)
     ch = y.shape[1] // 2
     c0, c1 = x0.shape[1], (x1.shape[1] if x1 is not None else 0)
+    _ld(y)
     assert y.stride(1) == 1 and y.shape[1] == 2 * ch and gamma.numel() == 2 * ch == beta.numel() and partial.is_contiguous()
     assert w_extra.shape == (3, c0 + c1) and w_extra.is_contiguous() and x0.stride(1) == 1 and w_flow.numel() == 2 * ch and w_occ.numel() == ch
     if out is None:
         out = torch.empty(batch, 3, frames, hw, dtype=torch.float32, device=y.device)
-    lib.check(lib.lfdm_heads_gn_res_cl_to_planar_f32(_p(y), y.stride(0), ch, _p(partial), nchunk, groups, _p(gamma), _p(beta), eps, _p(w_flow), _p(b_flow),
-                                                     _p(w_occ), _p(b_occ), _p(x0), x0.stride(0), c0, _p(x1), x1.stride(0) if x1 is not None else 0, c1,
+    lib.check(lib.lfdm_heads_gn_res_cl_to_planar_f32(_p(y), _ld(y), ch, _p(partial), nchunk, groups, _p(gamma), _p(beta), eps, _p(w_flow), _p(b_flow),
+                                                     _p(w_occ), _p(b_occ), _p(x0), _ld(x0), c0, _p(x1), _ld(x1) if x1 is not None else 0, c1,
                                                      _p(w_extra), _p(out), batch, frames, hw, _stream(lib)), "lfdm_heads_gn_res_cl_to_planar_f32")
     return out
 
@@ -1026,8 +1047,8 @@ def warp_cl(src, batch, frames, h, w, flow_x, flow_y, occ, fh, fw, fsb, fst, *, 
     if out is None:
         out = torch.empty(batch * frames * h * w, c, dtype=torch.float32, device=src.device)
     p = _warp_params(src, out, batch, frames, h, w, c, flow_x, flow_y, occ, fh, fw, fsb, fst, prev,
-                     occ_scale, occ_bias, src.stride(0), prev.stride(0) if prev is not None else 0,
-                     out.stride(0), True)
+                     occ_scale, occ_bias, _ld(src), _ld(prev) if prev is not None else 0,
+                     _ld(out), True)
     lib.check(lib.lfdm_warp_cl_f32(C.byref(p), _stream(lib)), "lfdm_warp_cl_f32")
     return out
 
@@ -1041,7 +1062,7 @@ def warp_planar(src, frames, flow_x, flow_y, occ, fh, fw, fsb, fst, *, prev=None
     assert src.is_contiguous()
     if out is None:
         out = torch.empty(b, c, frames, h, w, dtype=torch.float32, device=src.device)
-    ld_prev = prev.stride(0) if (prev is not None and prev_is_cl) else 0
+    ld_prev = _ld(prev) if (prev is not None and prev_is_cl) else 0
     p = _warp_params(src, out, b, frames, h, w, c, flow_x, flow_y, occ, fh, fw, fsb, fst, prev,
                      occ_scale, occ_bias, 0, ld_prev, 0, prev_is_cl)
     lib.check(lib.lfdm_warp_planar_f32(C.byref(p), _stream(lib)), "lfdm_warp_planar_f32")
@@ -1053,8 +1074,8 @@ def affine_act_cl(x, a, b, act=ACT_RELU, out=None):
     _chk(lib, x, a, b, out)
     if out is None:
         out = torch.empty(x.shape[0], x.shape[1], dtype=torch.float32, device=x.device)
-    lib.check(lib.lfdm_affine_act_cl_f32(_p(x), _p(out), x.shape[0], x.shape[1], x.stride(0),
-                                         out.stride(0), _p(a), _p(b), act, _stream(lib)), "lfdm_affine_act_cl_f32")
+    lib.check(lib.lfdm_affine_act_cl_f32(_p(x), _p(out), x.shape[0], x.shape[1], _ld(x),
+                                         _ld(out), _p(a), _p(b), act, _stream(lib)), "lfdm_affine_act_cl_f32")
     return out
 
 
@@ -1074,7 +1095,7 @@ def planar_to_cl(x, n_img, channels, hw, out=None):
     _chk(lib, x, out)
     if out is None:
         out = torch.empty(n_img * hw, channels, dtype=torch.float32, device=x.device)
-    lib.check(lib.lfdm_planar_to_cl_f32(_p(x), _p(out), n_img, channels, hw, out.stride(0), _stream(lib)),
+    lib.check(lib.lfdm_planar_to_cl_f32(_p(x), _p(out), n_img, channels, hw, _ld(out), _stream(lib)),
               "lfdm_planar_to_cl_f32")
     return out
 
@@ -1084,7 +1105,7 @@ def cl_to_planar(x, n_img, channels, hw, out=None):
     _chk(lib, x, out)
     if out is None:
         out = torch.empty(n_img, channels, hw, dtype=torch.float32, device=x.device)
-    lib.check(lib.lfdm_cl_to_planar_f32(_p(x), _p(out), n_img, channels, hw, x.stride(0), _stream(lib)),
+    lib.check(lib.lfdm_cl_to_planar_f32(_p(x), _p(out), n_img, channels, hw, _ld(x), _stream(lib)),
               "lfdm_cl_to_planar_f32")
     return out
 

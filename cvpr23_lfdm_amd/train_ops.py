@@ -8,7 +8,7 @@ import ctypes as C
 import torch
 
 from ._native import ML_MAX, MultiLinearParams, WgradParams
-from .ops import _chk, _lib, _p, _stream
+from .ops import _chk, _ld, _lib, _p, _stream
 
 
 def _ws(lib_bytes, like):
@@ -30,12 +30,12 @@ def colsum(x, out=None):
     lib = _lib()
     _chk(lib, x, out)
     rows, c = x.shape
-    assert x.stride(1) == 1
+    _ld(x)
     if out is None:
         out = torch.empty(c, dtype=torch.float32, device=x.device)
     nbytes = lib.lfdm_colsum_ws_bytes(rows, c)
     ws = _ws(nbytes, x)
-    lib.check(lib.lfdm_colsum_f32(_p(x), rows, c, x.stride(0), _p(out), _p(ws), nbytes, _stream(lib)), "lfdm_colsum_f32")
+    lib.check(lib.lfdm_colsum_f32(_p(x), rows, c, _ld(x), _p(out), _p(ws), nbytes, _stream(lib)), "lfdm_colsum_f32")
     return out
 
 
@@ -59,10 +59,10 @@ def conv_wgrad(x, dy, n_img, hi, wi, hq, wq, kh, kw, stride=1, pad=None, out=Non
         dw = out
         assert out.is_contiguous() and out.dtype == torch.float32 and out.shape[0] == cout and out.numel() % (cout * kh * kw) == 0
         p.dw_layout, p.dw_cin_total, p.dw_ci_off = 1, out.numel() // (cout * kh * kw), ci_off
-    p.x, p.cin, p.ldx = x.data_ptr(), cin, x.stride(0)
+    p.x, p.cin, p.ldx = x.data_ptr(), cin, _ld(x)
     p.n_img, p.hi, p.wi, p.hq, p.wq = n_img, hi, wi, hq, wq
     p.stride, p.kh, p.kw, p.pad_y, p.pad_x = stride, kh, kw, pad[0], pad[1]
-    p.dy, p.cout, p.lddy = dy.data_ptr(), cout, dy.stride(0)
+    p.dy, p.cout, p.lddy = dy.data_ptr(), cout, _ld(dy)
     p.dw = dw.data_ptr()
     if dbias is not None:
         assert dbias.is_contiguous() and dbias.numel() == cout
@@ -109,7 +109,7 @@ def groupnorm_silu_bwd(x, dy, batch, gamma, beta, partial, nchunk, scale_shift=N
     ws = _ws(nbytes, x)
     lib.check(lib.lfdm_groupnorm_silu_bwd_cl_f32(
         _p(x), _p(dy), _p(dx), batch, pixels, c, groups, _p(gamma), _p(beta), _p(scale_shift),
-        scale_shift.stride(0) if scale_shift is not None else 0, eps, 1 if silu else 0, _p(partial), nchunk, _p(dgb),
+        _ld(scale_shift) if scale_shift is not None else 0, eps, 1 if silu else 0, _p(partial), nchunk, _p(dgb),
         _p(dss), 2 * c, _p(ws), nbytes, _stream(lib)), "lfdm_groupnorm_silu_bwd_cl_f32")
     return dx, dgb[0], dgb[1], dss
 
@@ -286,5 +286,5 @@ def im2col_cl(x, n_img, h, w, k, pad):
     c = x.shape[1]
     hq, wq = h + 2 * pad - k + 1, w + 2 * pad - k + 1
     out = torch.empty(n_img * hq * wq, k * k * c, dtype=torch.float32, device=x.device)
-    lib.check(lib.lfdm_im2col_cl_f32(_p(x), _p(out), n_img, h, w, c, x.stride(0), k, pad, _stream(lib)), "lfdm_im2col_cl_f32")
+    lib.check(lib.lfdm_im2col_cl_f32(_p(x), _p(out), n_img, h, w, c, _ld(x), k, pad, _stream(lib)), "lfdm_im2col_cl_f32")
     return out

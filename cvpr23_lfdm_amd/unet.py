@@ -362,11 +362,13 @@ class Unet3D(ParamTree):
 
     # ------------------------------------------------------------------ building blocks
     def _conv(self, src0, w, cout, k, n_img, s, *, src1=None, bias=None, residual=None, out=None, gn=None,
-              scratch="splitk", ww=None, **kw):
+              scratch="splitk", ww=None, only_schedule=None, **kw):
         # (measured and removed: res_conv on a second stream - slower; split-K slabs reduced inside the launch with a release / acquire
         #  fence pair, KSW schedule - neutral; the fence-free form on the Winograd schedule is `_WINO_FUSE_REDUCE` below)
         """One lfdm_conv2d_cl_f32 launch; tile shape / split-K come from the library's plan.
-        gn = (batch,) asks for fused GroupNorm statistics; then returns (out, (partial, nchunk) or None)."""
+        gn = (batch,) asks for fused GroupNorm statistics; then returns (out, (partial, nchunk) or None).
+        only_schedule = k: launch only if the library plans schedule k for these parameters (lfdm_conv2d_schedule), else return None with
+        nothing enqueued - the caller decides up front instead of catching the library's refusal."""
         if ((k == 1 or (k == 4 and kw.get("stride") == 2)) and self._pk is not None and w.dim() == 3 and w.shape[1] % 32 == 0 and
                 not kw.get("deconv4")):
             # 1x1 projections: the operand-order pack for the pointwise schedule, built once per weight pack
@@ -378,7 +380,9 @@ class Unet3D(ParamTree):
         p, y = ops.conv_params(src0, w, cout, k, k, n_img, s, s, src1=src1, bias=bias, residual=residual,
                                out=out, weight_wino=ww if (src1 is None or src0.shape[1] % 16 == 0) else None, **kw)
         coutp = p.coutp
-        sched = ops.conv_schedule(p) if (_WINO_FUSE_REDUCE and kw.get("deconv4") is None) else -1
+        sched = ops.conv_schedule(p) if ((_WINO_FUSE_REDUCE and kw.get("deconv4") is None) or only_schedule is not None) else -1
+        if only_schedule is not None and sched != only_schedule:
+            return None
         # (KSW: fused statistics need the group inside a 32-column tile - wider groups keep the reduce pass, whose statistics take any width)
         if sched == 2:
             counters = self._tile_counters(src0.device)
@@ -451,11 +455,12 @@ class Unet3D(ParamTree):
             # h + res_conv(x) with block2's GroupNorm + SiLU applied to the RAW `out` in the res_conv launch's epilogue (pointwise schedule;
             # lfdm_conv_params.res_gn_*): no GroupNorm launch for the blocks that change their channel count
             res_gn = dict(partial=st[0], nchunk=st[1], pixels=rows // batch, gamma=pk[prefix + "block2.norm.w"], beta=pk[prefix + "block2.norm.b"], groups=8)
-            try:
-                return self._conv(x, pk[prefix + "res.w"], cout, 1, n_img, s, src1=skip, bias=pk[prefix + "res.b"], residual=out, out=out,
-                                  res_gn=res_gn)
-            except RuntimeError:
-                pass          # (a geometry the pointwise schedule does not take - M > 16 384 rows: the separate GroupNorm launch below)
+            # (asked up front: a geometry the pointwise schedule does not take - more than _RES_GN_MAX_ROWS = 65 536 rows, LFDM_PW=0 - gets the
+            #  separate GroupNorm launch below; an error of the launch itself propagates)
+            fused = self._conv(x, pk[prefix + "res.w"], cout, 1, n_img, s, src1=skip, bias=pk[prefix + "res.b"], residual=out, out=out,
+                               res_gn=res_gn, only_schedule=3)
+            if fused is not None:
+                return fused
         self._gn(out, batch, pk[prefix + "block2.norm.w"], pk[prefix + "block2.norm.b"], st,
                  residual=None if has_res else x)
         if has_res:

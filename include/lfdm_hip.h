@@ -15,6 +15,16 @@
  *  - no allocation, no synchronisation, no hidden state: every call only enqueues kernels on
  *    `stream` (hipGraph-capturable); scratch memory is passed in by the caller;
  *  - return value 0 on success, negative LFDM_E* otherwise; lfdm_last_error() describes it.
+ *
+ * Layouts (the "Layout:" line of each entry point; tests/test_operand_layouts.py asserts them)
+ *  - a row operand with a leading dimension (ld0, ldo, ldx, ss_ld, ...) is a window of a wider buffer: row r starts at base + r*ld,
+ *    columns are adjacent, ld >= its column count.  The floats of a row beyond its columns ("gap columns"), and everything else
+ *    outside the window, are never read into a result and never written - they may hold NaN.  An operand without a leading
+ *    dimension is dense;
+ *  - "any" = every 4-byte aligned pointer and every ld is taken (the library picks a scalar form where a vector form does not
+ *    apply); "16 B" = the pointer must be 16-byte aligned and "ld % 4" the stride a multiple of 4 floats, LFDM_EINVAL otherwise -
+ *    a refused call enqueues nothing and writes nothing;
+ *  - operands must not overlap unless the line says "may alias".
  */
 #ifndef LFDM_HIP_H
 #define LFDM_HIP_H
@@ -171,6 +181,11 @@ typedef struct lfdm_conv_params {
   float res_gn_eps;
 } lfdm_conv_params;
 
+/* Layout: src0 / src1 (ld0, ld1), out (ldo), residual (ldr), bias: any.  All 16 B with ld % 4 and cout % 4 == 0: every schedule; otherwise schedule 0
+ * only (scalar epilogue / reduce pass for out, residual, bias; generic loads for src0 / src1) - ask lfdm_conv2d_schedule.  Forms that exist in the
+ * float4 epilogues only are refused there: gn_partial (needs out 16 B, ldo % 4), ln_wsum (out, residual, bias 16 B, ld % 4), res_gn_*, groups, pool2,
+ * lfdm_conv2d_cl_wino_bf16.  out may alias residual (same pointer and ldr == ldo) on every schedule, reduce pass and in-launch reduction:
+ * each element is read by the thread that writes it.  out must not overlap src0 / src1.  partial, tile_counters, gn_partial: dense. */
 int lfdm_conv2d_cl_f32(const lfdm_conv_params* p, lfdm_stream_t stream);
 /* Opt-in lower-precision form of the Winograd F(2x2,3x3) schedule: runs exactly the launch lfdm_conv2d_cl_f32 would run for `p` (same plan:
  * tile_rows, ksplit, slabs, GroupNorm partial layout, tile counters - every buffer sized for p stays valid) with the transform-domain GEMM on
@@ -206,6 +221,8 @@ int lfdm_conv2d_plan_slabs(const lfdm_conv_params* p);
  * ws: caller scratch of lfdm_groupnorm_ws_bytes(B, P, C) bytes.
  */
 size_t lfdm_groupnorm_ws_bytes(int batch, int pixels, int channels);
+/* Layout (both entry points): x, out, residual dense rows of C floats, 16 B; out may alias x (in place), residual may alias neither.
+ * scale_shift (ss_ld >= 2C): any - a column window of a wider table. */
 int lfdm_groupnorm_silu_cl_f32(const float* x, float* out, int batch, int pixels, int channels,
                                int groups, const float* gamma, const float* beta,
                                const float* scale_shift, int ss_ld, const float* residual,
@@ -222,6 +239,7 @@ int lfdm_groupnorm_apply_cl_f32(const float* x, float* out, int batch, int pixel
                                 void* ws, size_t ws_bytes, lfdm_stream_t stream);
 
 /* Channel LayerNorm (gamma only, biased variance): video_flow_diffusion.py:170-179. */
+/* Layout: x, out dense rows, gamma: 16 B. */
 int lfdm_layernorm_cl_f32(const float* x, float* out, int64_t rows, int channels,
                           const float* gamma, float eps, lfdm_stream_t stream);
 
@@ -249,6 +267,7 @@ int lfdm_linear_attention_cl_f32(const float* qkv, float* out, int n_frames, int
 /* ------------------------------------------------------------------------------------------
  * Small dense layers of the conditioning path (time_mlp :423-428, ResnetBlock.mlp :217-220).
  * y[b][n] = act_out( sum_k act_in(x[b][k]) * w[n][k] + bias[n] ),  w rows of stride ldw. */
+/* Layout: x (ldx), w (ldw), y (ldy), bias: any. */
 int lfdm_linear_small_f32(const float* x, const float* w, const float* bias, float* y,
                           int batch, int k, int n, int ldx, int ldw, int ldy, int act_in,
                           int act_out, lfdm_stream_t stream);
@@ -263,6 +282,7 @@ int lfdm_step_cond_f32(const float* step_table, const float* batch_base, const i
  * is a (dim/2) table prepared once by the host (a 1-ulp difference in exp is amplified ~1000x by
  * t, so the table is computed with the same fp32 expression the reference uses).
  * The timestep is read from DEVICE memory (int32) so a captured graph can be replayed per step. */
+/* Layout: out (ldo): any. */
 int lfdm_sinusoidal_f32(const int32_t* t_dev, int t_stride, const float* freqs, float* out,
                         int batch, int dim, int ldo, lfdm_stream_t stream);
 
@@ -274,6 +294,7 @@ int lfdm_sinusoidal_f32(const int32_t* t_dev, int t_stride, const float* freqs, 
  * x: (B, cin_total, T, H, W) planar, only channels [0, cin) are read; w: [kh*kw*cin][cout]
  * (tap-major, then channel); add_term: NULL or (B, H, W, cout) CL broadcast over T.
  */
+/* Layout: x dense planar; out (ldo), bias, add_term (dense rows of cout): any (float4 epilogue when all are 16 B with ldo % 4, scalar otherwise). */
 int lfdm_conv_planar_in_cl_f32(const float* x, int batch, int cin, int cin_total, int frames,
                                int h, int w, const float* wgt, int kh, int kw, int cout,
                                const float* bias, const float* add_term, float* out, int ldo,
@@ -283,6 +304,7 @@ int lfdm_conv_planar_in_cl_f32(const float* x, int batch, int cin, int cin_total
  * PLANAR 3-channel prediction (B, 3, T, H, W): ch 0,1 from y_flow (w_flow (2,C)), ch 2 from y_occ.
  * ld = row stride (floats) of both feature tensors: the two heads' ResnetBlocks run as one 2C-channel block, their outputs
  * are the two column halves of one (rows, 2C) buffer. */
+/* Layout (the three heads forms): y_flow / y_occ resp. y (ld), x0 (ld0), x1 (ld1): 16 B, ld % 4, C % 4; out dense planar. */
 int lfdm_heads_cl_to_planar_f32(const float* y_flow, const float* y_occ, int channels, int ld,
                                 const float* w_flow, const float* b_flow, const float* w_occ,
                                 const float* b_occ, float* out, int batch, int frames, int hw,
@@ -362,6 +384,7 @@ int lfdm_known_blend_f32(float* x, const float* known, const float* known_noise,
                          int batch, int64_t n, int frames, int64_t frame_elems, lfdm_stream_t stream);
 /* classifier-free guidance combine of Unet3D.forward_with_cond_scale (:525-526):
  * out = null_eps + (cond_eps - null_eps) * scale   (out may alias an input) */
+/* Layout: dense, any; out may alias cond_eps or null_eps. */
 int lfdm_cfg_combine_f32(const float* cond_eps, const float* null_eps, float scale, float* out,
                          int64_t n, lfdm_stream_t stream);
 /* stand-alone |x| quantile (torch.quantile semantics, :722-726) for tests: q_out[b] */
@@ -392,6 +415,8 @@ typedef struct lfdm_warp_params {
   int prev_is_cl;        /* planar kernel only: prev given as CL rows (ld_prev) */
 } lfdm_warp_params;
 
+/* Layout: warp_cl: src (ld_src), prev (ld_prev), out (ld_out): 16 B, ld % 4, C % 4.  warp_planar: src, out dense planar (src any: the plane kernel
+ * stages 16 B planes with float4 and others with scalar loads), prev as CL rows (ld_prev): any.  flow_x / flow_y / occ: any (fsb, fst in floats). */
 int lfdm_warp_cl_f32(const lfdm_warp_params* p, lfdm_stream_t stream);
 int lfdm_warp_planar_f32(const lfdm_warp_params* p, lfdm_stream_t stream);
 
@@ -400,6 +425,8 @@ int lfdm_warp_planar_f32(const lfdm_warp_params* p, lfdm_stream_t stream);
  * affine_act: y = act(x*a[c] + b[c])  (eval BatchNorm + ReLU of ResBlock2d, util.py:84-90)
  * avgpool2:   2x2 average pool (DownBlock2d, util.py:124)
  */
+/* Layout: affine_act: x (ldx), out (ldo), a, b: 16 B, ld % 4, C % 4; out may alias x.  avgpool2: x, out dense, 16 B.  planar_to_cl: out (ldo) any.
+ * cl_to_planar: x (ldx) any. */
 int lfdm_affine_act_cl_f32(const float* x, float* out, int64_t rows, int channels, int ldx,
                            int ldo, const float* a, const float* b, int act,
                            lfdm_stream_t stream);
@@ -415,6 +442,7 @@ int lfdm_cl_to_planar_f32(const float* x, float* out, int n_img, int channels, i
  * rotary :329-331 and relative position bias :339-340).  x: CL rows (B*T*HW, C) stride ldx; wqkv: the to_qkv weight
  * (768, C) row-major with the LayerNorm gamma folded in (w[n][c] * gamma[c]); out: rows of 256 (heads merged).
  * The 768-wide qkv tensor is never materialised. */
+/* Layout: x (ldx), wqkv: 16 B, ldx % 4; out dense rows of 256; bias any (float4 loads when 16 B and frames % 4 == 0, scalar otherwise). */
 int lfdm_temporal_attention_fused_cl_f32(const float* x, int ldx, int channels, const float* wqkv, float* out,
                                          int batch, int frames, int hw, const float* bias,
                                          const float* rot_cos, const float* rot_sin, float ln_eps,
@@ -425,6 +453,7 @@ int lfdm_temporal_attention_fused_cl_f32(const float* x, int ldx, int channels, 
  *   wqkv [3 = q|k|v][8 heads][2 feature halves][4 quads][64 lanes][4]  <-  (W_qkv * gamma)[which*256 + head*32 + 16*half + l15][16*lq + 4*quad + e]
  *   wout [4 column tiles][16 steps S][64 lanes][4]                      <-  W_out[16*ct + l15][16*S + 4*lq + e]
  * out (rows, C) with row stride ldo, out != x.  C == 64 only (the finest UNet levels). */
+/* Layout: x (ldx), wqkv, wout: 16 B, ldx % 4; out (ldo): any, out != x; bias as above. */
 int lfdm_temporal_attention_fused_out_cl_f32(const float* x, int ldx, int channels, const float* wqkv, const float* wout, float* out,
                                              int ldo, int batch, int frames, int hw, const float* bias, const float* rot_cos,
                                              const float* rot_sin, float ln_eps, lfdm_stream_t stream);
@@ -434,6 +463,7 @@ int lfdm_temporal_attention_fused_out_cl_f32(const float* x, int ldx, int channe
  * LayerNorm gamma folded in; out rows of 256.  qkv is never materialised (every pass recomputes its projection). 
  * wqkv (ABI version 8): the LayerNorm-folded (768, 64) weight in MFMA-operand order [3 = q|k|v][8 heads][8 quads][64 lanes = 32*kh + l31][4]
  * <- W[which*256 + head*32 + l31][32*kh + 4*quad + e] (cvpr23_lfdm_amd.ops.pack_linattn_weights): every fragment load = one contiguous 1 KB. */
+/* Layout: x (ldx), wqkv: 16 B, ldx % 4; out dense rows of 256. */
 size_t lfdm_linear_attention_fused_ws_bytes(int n_frames, int hw);
 int lfdm_linear_attention_fused_cl_f32(const float* x, int ldx, int channels, const float* wqkv, float* out,
                                        int n_frames, int hw, float ln_eps, void* ws, size_t ws_bytes,
@@ -445,6 +475,7 @@ int lfdm_linear_attention_fused_cl_f32(const float* x, int ldx, int channels, co
  * lfdm_linear_attention_fused_cl_f32 + a 1x1 convolution at 40 frames of 32x32).  wout: the
  * (64, 256) to_out weight in MFMA-operand order [8 heads][2 row blocks][4 quads][64 lanes = 32*kh + c_local][4] <- Wout[32*cb + c_local][32*h + 8*quad + 4*kh + e]
  * (cvpr23_lfdm_amd.ops.pack_linattn_out_weight); bias_out (64,) or NULL; same workspace as above. */
+/* Layout: x (ldx), out (ldo), wqkv, wout, bias_out: 16 B, ld % 4; out != x. */
 int lfdm_linear_attention_fused_out_cl_f32(const float* x, int ldx, int channels, const float* wqkv, const float* wout, const float* bias_out,
                                            float* out, int ldo, int n_frames, int hw, float ln_eps, void* ws, size_t ws_bytes,
                                            lfdm_stream_t stream);
@@ -458,6 +489,7 @@ int lfdm_linear_attention_fused_out_cl_f32(const float* x, int ldx, int channels
  * lfdm_linear_attention_lowres_cl_f32: SpatialLinearAttention (video_flow_diffusion.py:240-265), hw <= 64 or 192 < hw <= 256 pixels
  * per frame.  lfdm_attention_lowres_cl_f32: Attention (:286-363); mode 0 = over the frames of a pixel (rot_cos / rot_sin (T,16), bias
  * (8,T,T) as in lfdm_attention_cl_f32), mode 1 = over the pixels of a frame (mid block); at most 64 tokens per sequence. */
+/* Layout (both): x (ldx), wqkv, out (dense rows of 256): 16 B, ldx % 4. */
 int lfdm_linear_attention_lowres_cl_f32(const float* x, int ldx, int channels, const float* wqkv, const float* wsum, float* out,
                                         int n_frames, int hw, float ln_eps, lfdm_stream_t stream);
 int lfdm_attention_lowres_cl_f32(const float* x, int ldx, int channels, const float* wqkv, const float* wsum, float* out, int batch,
@@ -471,6 +503,8 @@ int lfdm_attention_lowres_cl_f32(const float* x, int ldx, int channels, const fl
  * dgrad != 0 builds the filters of the data-gradient convolution instead (roles of the channel axes exchanged, taps
  * flipped): the result convolves dY (cout channels) into dX (cin channels); then cout % 16 == 0 is required and
  * coutp >= cin.  dgrad == 0 requires cin % 16 == 0 and coutp >= cout; coutp % 32 == 0. */
+/* Layout (the four Winograd packers, the per-job ld_o of lfdm_pack_wino_weights_multi_f32 included): w (ld_o >= cin*9 floats between output channels): any -
+ * an input-channel slice of a wider filter is read where it lies, nothing of the filter outside the slice is read; out dense (bf16: 16 B). */
 int lfdm_pack_wino_weight_f32(const float* w, int ld_o, int cout, int cin, int coutp, int dgrad, float* out,
                               lfdm_stream_t stream);
 /* the F(4x4,3x3) filters of lfdm_conv_params.weight_wino4: out[36][cin/8][coutp][8] (zero for output channels >= cout), same `w`
@@ -493,6 +527,8 @@ int lfdm_pack_wino_weight_bf16(const float* w, int ld_o, int cout, int cin, int 
  * lfdm_lfae_motion_combine_f32: (:112-128) heads = channels-last rows (N*hw, ldh) of the mask (columns 0..K) and occlusion
  * (column K+1, read iff occ != NULL) convolutions: flow (N, h, w, 2) = sum_k softmax_k(mask) * sparse_k,
  * occ (N, 1, h, w) = sigmoid. */
+/* Layout: motion_inputs: rows (ld): 16 B, ld % 4, ld >= 4*(regions+1); DELIBERATE EXCEPTION to the gap rule: the columns 4*(regions+1) ... ld-1 of every row are
+ * WRITTEN as zero (ld is the consumer's channel count); sparse 8 B; the inputs dense.  region_stats: logits (ldh): any.  motion_combine: heads (ldh): any; sparse, flow 8 B. */
 int lfdm_lfae_motion_inputs_f32(const float* src_img, const float* drv_shift, const float* drv_covar, const float* drv_affine,
                                 const float* src_shift, const float* src_covar, const float* src_affine, const float* bg,
                                 float region_var, int revert_axis_swap, int batch, int frames, int regions, int h, int w,
@@ -529,6 +565,7 @@ int lfdm_pack_conv_weight_f32(const float* w, int n_o, int n_i, int taps, int64_
  * x: CL rows (n_img*h*w, cin) stride ldx; wgt: [k*k][cin][4] (tap-major, filters innermost, zero padded to 4);
  * bias: 4 floats or NULL; out: CL rows stride ldo (only `cout` columns are written); stride 1, zero padding k/2.
  * x and wgt 16-byte aligned, ldx % 4 == 0, cin % 16 == 0, odd k <= 7 (LFDM_EINVAL otherwise). */
+/* Layout: x (ldx), wgt: 16 B, ldx % 4; out (ldo >= cout): any - exactly `cout` columns of a row are written, the rest of a 4-wide row is a gap. */
 int lfdm_conv2d_smalln_cl_f32(const float* x, int ldx, int cin, int n_img, int h, int w, const float* wgt,
                               const float* bias, float* out, int ldo, int cout, int k, int act,
                               lfdm_stream_t stream);
@@ -565,13 +602,16 @@ typedef struct lfdm_wgrad_params {
   int dw_ci_off;          /* (layout 1) this call's first input channel */
   float* dbias;           /* optional (cout): sum over rows of dy */
 } lfdm_wgrad_params;
+/* Layout: x (ldx), dy (lddy): 16 B, ld % 4, cin % 4, cout % 4 (a channel slice of a wider activation is a pointer offset); dw, dbias dense. */
 size_t lfdm_conv2d_wgrad_ws_bytes(const lfdm_wgrad_params* p);
 int lfdm_conv2d_wgrad_cl_f32(const lfdm_wgrad_params* p, void* ws, size_t ws_bytes, lfdm_stream_t stream);
 
 /* out[i] = sum_s in[s*n + i], s in fixed order (second stage of every deterministic split reduction) */
+/* Layout: dense, any (float4 form when n % 4 == 0 and both pointers 16 B, scalar otherwise). */
 int lfdm_sum_leading_f32(const float* in, float* out, int64_t n, int s, lfdm_stream_t stream);
 
 /* Bias gradient: out[c] = sum_r x[r][c] over CL rows (stride ld). */
+/* Layout: x (ld): any. */
 size_t lfdm_colsum_ws_bytes(int64_t rows, int c);
 int lfdm_colsum_f32(const float* x, int64_t rows, int c, int ld, float* out, void* ws, size_t ws_bytes,
                     lfdm_stream_t stream);
@@ -581,6 +621,7 @@ int lfdm_colsum_f32(const float* x, int64_t rows, int c, int ld, float* out, voi
  * (sum, sumsq) partials the forward pass used (first batch*nchunk*groups*2 floats of its workspace, or the
  * convolution's gn_partial).  Outputs: dx rows; dgamma_dbeta = [dgamma(C) | dbeta(C)];
  * dscale_shift (when scale_shift != NULL) = B rows [dscale(C) | dshift(C)] with stride dss_ld. */
+/* Layout: x, dy, dx dense rows of C floats, 16 B; partial 8 B; scale_shift (ss_ld), dscale_shift (dss_ld): any. */
 size_t lfdm_groupnorm_bwd_ws_bytes(int batch, int pixels, int channels);
 int lfdm_groupnorm_silu_bwd_cl_f32(const float* x, const float* dy, float* dx, int batch, int pixels,
                                    int channels, int groups, const float* gamma, const float* beta,
@@ -590,6 +631,7 @@ int lfdm_groupnorm_silu_bwd_cl_f32(const float* x, const float* dy, float* dx, i
                                    lfdm_stream_t stream);
 
 /* Backward of lfdm_layernorm_cl_f32 (LayerNorm, video_flow_diffusion.py:170-179): dx rows and dgamma (C). */
+/* Layout (both forms): x, dy, dx, dx_add dense rows, gamma: 16 B. */
 size_t lfdm_layernorm_bwd_ws_bytes(int64_t rows, int channels);
 int lfdm_layernorm_bwd_cl_f32(const float* x, const float* dy, float* dx, int64_t rows, int channels,
                               const float* gamma, float eps, float* dgamma, void* ws, size_t ws_bytes,
@@ -657,6 +699,7 @@ typedef struct lfdm_multi_linear_params {
   float* dbias[LFDM_MULTI_LINEAR_MAX];
   float* dx;                                   /* (rows, k) or NULL */
 } lfdm_multi_linear_params;
+/* Layout (forward and backward): dense; x, every w, every dw, dx and ws 16 B, k % 4 == 0. */
 int lfdm_multi_linear_f32(const lfdm_multi_linear_params* p, lfdm_stream_t stream);
 size_t lfdm_multi_linear_bwd_ws_bytes(const lfdm_multi_linear_params* p);
 int lfdm_multi_linear_bwd_f32(const lfdm_multi_linear_params* p, void* ws, size_t ws_bytes, lfdm_stream_t stream);
@@ -664,6 +707,8 @@ int lfdm_multi_linear_bwd_f32(const lfdm_multi_linear_params* p, void* ws, size_
 /* Fused Adam over one flat parameter buffer: torch.optim.Adam(betas, eps, weight_decay) semantics (no amsgrad),
  * video_flow_diffusion_model.py:113-114,188.  grad is multiplied by grad_scale first (1/world for the
  * data-parallel mean).  step = 1-based step count (bias correction). */
+/* Layout (lfdm_adam_step_f32, lfdm_adam_guarded_step_f32, lfdm_grad_sumsq_f32, lfdm_optim_plan_f32): flat dense buffers; param, grad, exp_avg, exp_avg_sq, ema
+ * and the plan record 16 B. */
 int lfdm_adam_step_f32(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                        float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                        float grad_scale, lfdm_stream_t stream);
@@ -741,6 +786,7 @@ int lfdm_upsample2_pad_cl_f32(const float* x, float* out, int n_img, int h, int 
  * order and dgamma / dbeta are summed over the segments - exactly `segments` calls of the module on the separate batches (the region
  * predictor on source, driving and transformed frames, model.py:157-160, :190-191), as one launch pair. */
 size_t lfdm_batchnorm_train_ws_bytes(int64_t rows, int channels, int segments);
+/* Layout (forward and backward): x (ldx), y (ldy), dy (lddy), dx (lddx), dx_add (ldadd): 16 B, ld % 4, C % 4 - channel slices of wider channels-last tensors; stat 16 B. */
 int lfdm_batchnorm_train_fwd_cl_f32(const float* x, float* y, int64_t rows, int channels, int segments, int ldx, int ldy,
                                     const float* gamma, const float* beta, float* running_mean, float* running_var, float momentum,
                                     float eps, int relu, float* stat, void* ws, size_t ws_bytes, unsigned* tickets, lfdm_stream_t stream);
@@ -796,6 +842,8 @@ typedef struct lfdm_warp_bwd_params {
   int ld_src, ld_dout, ld_prev, ld_dprev;
   int64_t ss_n, ss_c, ss_h, ss_w, ds_n, ds_c, ds_h, ds_w, ps_n, ps_c, ps_h, ps_w, dps_n, dps_c, dps_h, dps_w;
 } lfdm_warp_bwd_params;
+/* Layout: warp_bwd, channels-last form: src (ld_src), dout (ld_dout), prev (ld_prev), dprev (ld_dprev): 16 B, ld % 4; dsrc_fix 8 B, dense; the strided form takes any
+ * element strides.  absmax: x (ld): any (float4 walk when 16 B, ld % 4 and C % 4, scalar otherwise).  fix_finalize: out (ld): any; acc dense. */
 int lfdm_warp_bwd_f32(const lfdm_warp_bwd_params* p, lfdm_stream_t stream);
 /* *out_bits = max(*out_bits, bit pattern of max |x|) over a (rows, channels) matrix with leading dimension ld (integer max). */
 int lfdm_absmax_f32(const float* x, int64_t rows, int channels, int64_t ld, unsigned* out_bits, lfdm_stream_t stream);
@@ -841,6 +889,7 @@ int lfdm_l1_mean_bwd_f32(const float* x, const float* y, int64_t n, float weight
 /* im2col of channels-last rows with few channels (channels % 4 == 0, <= 16; stride 1, zero padding): out (n_img*hq*wq, k*k*channels),
  * column tap * channels + ch.  Lets the weight gradient of the generator's 7x7 RGB convolutions (LFAE/modules/generator.py:37,56: 3 -> 64
  * and 64 -> 3 channels) run as ONE 1x1 weight-gradient GEMM instead of 49 per-tap GEMMs that pad 4 channels to a 64-wide tile. */
+/* Layout: x (ldx): 16 B, ldx % 4, C % 4; out dense, 16 B. */
 int lfdm_im2col_cl_f32(const float* x, float* out, int n_img, int h, int w, int channels, int ldx, int k, int pad, lfdm_stream_t stream);
 
 /* lfdm_pack_wino_weight_f32 for MANY filters in one launch: `jobs` is a table of n_jobs records IN DEVICE MEMORY, sorted by block0 = the first
@@ -864,6 +913,7 @@ int lfdm_pack_wino_weights_multi_f32(const lfdm_pack_wino_job* jobs, int n_jobs,
  * (batch, 3, frames, s, s) latent can be passed as they are).  ident: s floats, torch.linspace(-1, 1, s) made by the caller - the
  * subtraction is fp32 and must see the host's values.  Everything after the subtraction is fp64 in numpy's operation order; the maximum
  * radius is taken per frame (wave shuffles + LDS, no atomics).  One workgroup per frame.  s % 4 == 0; out 16-byte aligned. */
+/* Layout: grid: any, batch item b at grid + b*batch_stride (>= 2*frames*s*s floats: the first two channels of a 3-channel latent are read in place); out dense, 16 B. */
 int lfdm_flow_color_u8(const float* grid, int64_t batch_stride, const float* ident, unsigned char* out, int batch, int frames, int s,
                        lfdm_stream_t stream);
 /* lfdm_render_strip_u8: out (batch, frames, S, n_panels * S, 3) uint8 RGB, or with indexed != 0 (batch, frames, S, n_panels * S) uint8
@@ -911,6 +961,7 @@ int lfdm_video_metrics(const float* a, const float* b, const double* mean_over_2
  * stride_a / stride_b floats apart (as lfdm_flow_color_u8: the first two channels of a (batch, 3, frames, s, s) latent pass as they
  * are); conf_a / conf_b (batch, 1, frames, s, s) contiguous, both or neither - without them the second number is 0.  fp64, no atomics,
  * one workgroup per frame in a fixed order. */
+/* Layout: grid_a (stride_a), grid_b (stride_b): any, each with its own batch stride; confidences dense; out 8 B. */
 int lfdm_flow_metrics(const float* grid_a, int64_t stride_a, const float* grid_b, int64_t stride_b, const float* conf_a,
                       const float* conf_b, double* out, int batch, int frames, int s, lfdm_stream_t stream);
 /* out[i] = 10 log10(1 / mse[i]) over n doubles (data range 1), +inf where mse[i] == 0. */

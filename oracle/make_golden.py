@@ -399,12 +399,19 @@ def main():
     args = ap.parse_args()
     torch.manual_seed(0)
     if args.full:
-        {"c3": lambda: c3_steps_case("c3_ddpm_steps_b16"),
-         "c3full": lambda: c3_full_schedule_case("sample_ddpm1000_c3_b2"),      # configs[2]'s whole 1000-step schedule, ~1 h here "c4": lambda: train_full_case("train_step_c4_b4_t40"),
-         "c4b8": lambda: train_full_case("train_step_c4_b8_t40", b=8),
-         "c5": lambda: c5_case("sample_ddim10_c5_256"),
-         "c5b4": lambda: c5_case("sample_ddim50_c5_256_b4", b=4, steps=50, stride=4),      # configs[4] at its per-GPU batch (32 videos over 8 GPUs), ~35 min here
-         "c5d50": lambda: c5_case("sample_ddim50_c5_256", steps=50)}[args.full]()      # the configuration's real step count (~8 min here)
+        full = {
+            "c3": lambda: c3_steps_case("c3_ddpm_steps_b16"),
+            # configs[2]'s whole 1000-step schedule, ~1 h here
+            "c3full": lambda: c3_full_schedule_case("sample_ddpm1000_c3_b2"),
+            "c4": lambda: train_full_case("train_step_c4_b4_t40"),
+            "c4b8": lambda: train_full_case("train_step_c4_b8_t40", b=8),
+            "c5": lambda: c5_case("sample_ddim10_c5_256"),
+            # configs[4] at its per-GPU batch (32 videos over 8 GPUs), ~35 min here
+            "c5b4": lambda: c5_case("sample_ddim50_c5_256_b4", b=4, steps=50, stride=4),
+            # the configuration's real step count (~8 min here)
+            "c5d50": lambda: c5_case("sample_ddim50_c5_256", steps=50),
+        }
+        full[args.full]()
         return
     if args.lfae_train:
         for kind in (("tiny", "mug128") if args.lfae_train == "both" else (args.lfae_train,)):
