@@ -18,7 +18,7 @@ import torch
 from . import ops
 
 __all__ = ["MetricAccumulator", "FlowAccumulator", "compare_videos", "compare_flows", "reference_loss", "lfae_reconstruction", "sample_against_real",
-           "ab_compare"]
+           "ab_compare", "interpolation_error"]
 
 
 class _Result(dict):
@@ -185,3 +185,47 @@ def ab_compare(model_a, model_b, sample_img, sample_text, cond_scale=1.0, seed=0
     b = _sample(model_b, sample_img, sample_text, cond_scale, seed, total_frames, overlap)
     return {"video": compare_videos(b["sample_out_vid"], a["sample_out_vid"], mean, domain),
             "flow": compare_flows(b["sample_vid_grid"], a["sample_vid_grid"], b["sample_vid_conf"], a["sample_vid_conf"])}
+
+
+_SAMPLE_ATTRS = ("sample_img", "sample_text", "sample_latent", "sample_vid_grid", "sample_vid_conf", "sample_out_vid", "sample_warped_vid")
+
+
+def interpolation_error(model, real_vid, ref_img, factor=2, mode="linear", mean=(0, 0, 0), domain="unit"):
+    """What temporal interpolation of the latent (FlowDiffusion.decode_at) costs on real motion, on an is_train=False
+    model: the frozen LFAE's pseudo-ground-truth latent of all T frames of real_vid (the grid, minus the identity under residual flow,
+    and conf * 2 - 1, as the training step builds it) is thinned to frames 0, f, 2f, ... (f = factor; (T - 1) % f == 0, else ValueError),
+    resampled back to the T original instants in `mode`, and both latents are decoded from ref_img.
+    -> {"flow": compare_flows of the interpolated against the true maps, "video": compare_videos of the two decodes, "interp_vs_real" /
+    "lfae_vs_real": compare_videos of each decode against real_vid (the second is the LFAE's own reconstruction error, the floor the
+    first is read against), "held_out": (T,) bool, True where a frame was interpolated}.  Kept frames are exact copies of the latent: their
+    rows of the flow table are exactly 0.  The model's sample_* attributes are left as they were."""
+    f = int(factor)
+    if real_vid.dim() != 5:
+        raise ValueError("interpolation_error: real_vid must be (B, 3, T, H, W), got %s" % (tuple(real_vid.shape),))
+    t = int(real_vid.shape[2])
+    if f < 1 or f != factor or (t - 1) % f != 0:
+        raise ValueError("interpolation_error: factor must be an integer >= 1 that divides T - 1 = %d, got %r" % (t - 1, factor))
+    real = _frozen_lfae(model, real_vid, ref_img)
+    saved = {k: getattr(model, k, None) for k in _SAMPLE_ATTRS}
+    try:
+        with torch.no_grad():
+            grid, conf = model.real_vid_grid, model.real_vid_conf
+            if model.use_residual_flow:
+                b, _, _, h, w = grid.shape
+                grid = grid - model.get_grid(b, t, h, w, normalize=True).to(grid.device)
+            latent = torch.cat((grid, conf * 2 - 1), dim=1).contiguous()
+            kept = latent[:, :, ::f].contiguous()
+        model.set_sample_input(sample_img=model.ref_img, sample_text=None)
+        model.decode_at(range(t), latent=latent)
+        true = {k: getattr(model, k) for k in _SAMPLE_ATTRS[3:]}
+        model.decode_at([j / f for j in range(t)], mode, latent=kept)
+        got = {k: getattr(model, k) for k in _SAMPLE_ATTRS[3:]}
+    finally:
+        for k, v in saved.items():
+            setattr(model, k, v)
+    held_out = torch.tensor([j % f != 0 for j in range(t)], dtype=torch.bool)
+    return {"flow": compare_flows(got["sample_vid_grid"], true["sample_vid_grid"], got["sample_vid_conf"], true["sample_vid_conf"]),
+            "video": compare_videos(got["sample_out_vid"], true["sample_out_vid"], mean, domain),
+            "interp_vs_real": compare_videos(got["sample_out_vid"], real, mean, domain),
+            "lfae_vs_real": compare_videos(true["sample_out_vid"], real, mean, domain),
+            "held_out": held_out}

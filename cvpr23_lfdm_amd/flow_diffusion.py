@@ -149,11 +149,14 @@ class FlowDiffusion(nn.Module):
             torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count())
 
     # ------------------------------------------------------------------ sampling (a28)
-    def sample_one_video(self, cond_scale, *, known_latent=None, known_mask=None):
+    def sample_one_video(self, cond_scale, *, known_latent=None, known_mask=None, frame_times=None, interp="linear"):
         """Reference :190-216.  Results land in sample_vid_grid (B,2,T,S,S), sample_vid_conf (B,1,T,S,S),
         sample_out_vid / sample_warped_vid (B,3,T,H,W), and the latent the diffusion returned (B,3,T,S,S; the residual flow when
         use_residual_flow) in sample_latent.  known_latent (B,3,T,S,S) in that same space + known_mask (B,T) bool (keyword only, both or
-        none): GaussianDiffusion.sample's known frames."""
+        none): GaussianDiffusion.sample's known frames.  frame_times (keyword only; default None: off) + interp: after
+        sampling, decode_at(frame_times, interp) - the four result tensors then hold len(frame_times) frames."""
+        if frame_times is not None:
+            frame_times = self._check_frame_times(frame_times, interp, self.diffusion.num_frames)
         gen = self.generator
         with torch.no_grad():
             img = self.sample_img.float().contiguous()
@@ -168,6 +171,8 @@ class FlowDiffusion(nn.Module):
                                          known_mask=known_mask)
             self.sample_latent = pred
             self._decode_sample(img, skips, pred)
+        if frame_times is not None:
+            self.decode_at(frame_times, interp)
 
     def _maps(self, pred):
         """(sampling grid + occlusion channel (B,3,T,S,S), confidence (B,1,T,S,S)) of a latent (:203-210)."""
@@ -189,18 +194,21 @@ class FlowDiffusion(nn.Module):
         self.sample_out_vid = out
         self.sample_warped_vid = warped
 
-    def sample_long_video(self, cond_scale, total_frames, overlap=8):
+    def sample_long_video(self, cond_scale, total_frames, overlap=8, *, frame_times=None, interp="linear"):
         """A video of `total_frames` frames, longer than the model's window of num_frames, as a chain of windows: the LFAE
         encoder runs ONCE; chunk 0 is a plain sample; chunk j > 0 is conditioned on the last `overlap` latent frames of chunk j - 1 placed at
         its frames 0 .. overlap-1 (same source image, features and text condition - only the latent is chained); the result keeps chunk 0 whole
         and frames overlap.. of every later chunk, cut to total_frames, and is decoded in pieces of at most num_frames frames.  Results as
-        sample_one_video's, with T = total_frames."""
+        sample_one_video's, with T = total_frames.  frame_times / interp (keyword only): as sample_one_video's, times in
+        [0, total_frames - 1]."""
         nf = self.diffusion.num_frames
         total_frames, overlap = int(total_frames), int(overlap)
         if overlap < 1 or overlap >= nf:
             raise ValueError("sample_long_video: overlap must lie in [1, num_frames - 1 = %d], got %d" % (nf - 1, overlap))
         if total_frames < 1:
             raise ValueError("sample_long_video: total_frames must be at least 1, got %d" % total_frames)
+        if frame_times is not None:
+            frame_times = self._check_frame_times(frame_times, interp, total_frames)
         gen = self.generator
         with torch.no_grad():
             img = self.sample_img.float().contiguous()
@@ -237,6 +245,57 @@ class FlowDiffusion(nn.Module):
             self.sample_vid_conf = torch.cat(confs, dim=2)
             self.sample_out_vid = torch.cat(outs, dim=2)
             self.sample_warped_vid = torch.cat(warps, dim=2)
+        if frame_times is not None:
+            self.decode_at(frame_times, interp)
+
+    # ------------------------------------------------------------------ other frame times from the sampled latent
+    @staticmethod
+    def _check_frame_times(times, mode, frames):
+        """The list of `times`, refused (ValueError / IndexError) before anything is launched when a time or the mode is bad."""
+        from . import ops
+        if mode not in ops.RESAMPLE_MODES:
+            raise ValueError("unknown interpolation mode %r (one of %s)" % (mode, ", ".join(ops.RESAMPLE_MODES)))
+        times = times.tolist() if isinstance(times, torch.Tensor) else list(times)
+        ops.resample_tables(times, frames)
+        return times
+
+    def decode_at(self, times, mode="linear", *, latent=None):
+        """Decodes `latent` (keyword only; default: sample_latent, what the last sample_one_video / sample_long_video left) from
+        sample_img at `times`: floats in [0, T - 1] in any order, repeats allowed (retime.frame_times makes the usual lists).  An integer
+        time is that sampled frame; a time between two integers is a frame whose warp field and occlusion map are interpolated between
+        theirs - mode "linear", or "cubic" (Catmull-Rom; the occlusion channel is then clamped to [-1, 1]).  One launch per piece
+        resamples the latent and builds the generator's maps (ops.latent_resample_maps), the batched decode runs in pieces of at most
+        num_frames frames like sample_long_video's.  Results land in sample_vid_grid, sample_vid_conf, sample_out_vid and
+        sample_warped_vid with len(times) frames; sample_latent is left as sampled.  decode_at(range(T)) reproduces the sampled video
+        bit for bit."""
+        from . import ops
+        latent = self.sample_latent if latent is None else latent
+        if latent is None or getattr(self, "sample_img", None) is None:
+            raise RuntimeError("decode_at: nothing has been sampled yet - call sample_one_video or sample_long_video first")
+        times = self._check_frame_times(times, mode, latent.shape[2])
+        gen, nf = self.generator, self.diffusion.num_frames
+        clamp_from = 2 if mode == "cubic" else None
+        with torch.no_grad():
+            img = self.sample_img.float().contiguous()
+            latent = latent.to(img.device).float().contiguous()
+            skips = gen.encode(img)
+            s = latent.shape[3]
+            grids, confs, outs, warps = [], [], [], []
+            for f0 in range(0, len(times), nf):                       # decode in pieces of at most num_frames frames
+                part = times[f0:f0 + nf]
+                maps, conf = ops.latent_resample_maps(latent, part, mode, residual=self.use_residual_flow, clamp_from=clamp_from)
+                n_part = len(part)
+                out, warped = gen.decode_video(img, skips, maps[:, 0], maps[:, 1], maps[:, 2], n_part, s, s,
+                                               3 * n_part * s * s, s * s, occ_scale=0.5, occ_bias=0.5)
+                grids.append(maps[:, :2])
+                confs.append(conf)
+                outs.append(out)
+                warps.append(warped)
+            one = len(grids) == 1
+            self.sample_vid_grid = grids[0] if one else torch.cat(grids, dim=2)
+            self.sample_vid_conf = confs[0] if one else torch.cat(confs, dim=2)
+            self.sample_out_vid = outs[0] if one else torch.cat(outs, dim=2)
+            self.sample_warped_vid = warps[0] if one else torch.cat(warps, dim=2)
 
     # ------------------------------------------------------------------ uint8 preview strips on the device (DESIGN.md 4.5)
     def render_sample(self, mean=(0., 0., 0.), panels=("source", "out", "warped", "flow", "conf"), indexed=False, *, source=None):
@@ -524,7 +583,8 @@ class FlowDiffusionFunctional(FlowDiffusion):
         out.pop("ref_img_fea", None)
         return out
 
-    def sample_one_video(self, sample_img, sample_text, cond_scale, *, known_latent=None, known_mask=None):
+    def sample_one_video(self, sample_img, sample_text, cond_scale, *, known_latent=None, known_mask=None, frame_times=None, interp="linear"):
         self.set_sample_input(sample_img=sample_img, sample_text=sample_text)
-        FlowDiffusion.sample_one_video(self, cond_scale, known_latent=known_latent, known_mask=known_mask)
+        FlowDiffusion.sample_one_video(self, cond_scale, known_latent=known_latent, known_mask=known_mask, frame_times=frame_times,
+                                       interp=interp)
         return {k: getattr(self, k) for k in ("sample_vid_grid", "sample_vid_conf", "sample_out_vid", "sample_warped_vid", "sample_latent")}

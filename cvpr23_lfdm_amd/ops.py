@@ -1424,3 +1424,101 @@ def video_prep(store_u8, frame_index, params, hue_shift, mean, image_size, jitte
                                      _p(out), b, t, s, h, int(jitter), int(launches), _p(ws), ws_bytes, _stream(lib)),
               "lfdm_video_prep_u8")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# temporal resampling of a sampled latent (csrc/latent_resample.hip)
+# ---------------------------------------------------------------------------------------------
+RESAMPLE_MODES = ("linear", "cubic")          # LFDM_RESAMPLE_* = the position in this tuple
+
+
+def resample_tables(times, frames):
+    """The host side of lfdm_latent_resample_f32's time tables: times (a sequence or host tensor of floats in [0, frames - 1], any order,
+    repeats allowed, at least one) -> (idx int32 array, frac float32 array), time = idx + frac with frac in [0, 1).  i = floor(t) and
+    a = t - i are taken in float64, a is rounded to fp32, and an a that rounds to 1.0f becomes (i + 1, 0): the kernel converts no time."""
+    import numpy as np
+    if isinstance(times, torch.Tensor):
+        if times.is_cuda:
+            raise ValueError("latent_resample: times is a host sequence or host tensor (it is checked on the host), got a tensor on %s"
+                             % times.device)
+        times = times.detach().reshape(-1).to(torch.float64).numpy()
+    try:
+        t = np.asarray(list(times) if not isinstance(times, np.ndarray) else times, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError("latent_resample: times must be a sequence of numbers")
+    if t.size == 0:
+        raise ValueError("latent_resample: times is empty (at least one output frame)")
+    if not np.isfinite(t).all():
+        raise ValueError("latent_resample: times holds a NaN or an infinity")
+    if t.min() < 0.0 or t.max() > frames - 1:
+        raise IndexError("latent_resample: times span %g .. %g, the latent has frames 0 .. %d (no extrapolation)"
+                         % (t.min(), t.max(), frames - 1))
+    i = np.floor(t)
+    a = (t - i).astype(np.float32)
+    up = a >= np.float32(1.0)
+    i = i.astype(np.int64) + up
+    a[up] = 0.0
+    assert i.min() >= 0 and i.max() <= frames - 1 and not (a[i == frames - 1] != 0).any()
+    return i.astype(np.int32), a
+
+
+def _resample_call(what, latent, times, mode, clamp_from, maps, residual, out, conf):
+    lib = _lib()
+    if not isinstance(latent, torch.Tensor) or latent.dtype != torch.float32 or latent.dim() != 5:
+        raise ValueError("%s: latent must be a float32 (B, C, T, H, W) tensor, got %s %s"
+                         % (what, getattr(latent, "dtype", type(latent)), tuple(getattr(latent, "shape", ()))))
+    _chk_dev(lib, latent, out, conf)
+    b, c, t, h, w = (int(v) for v in latent.shape)
+    if min(b, c, t, h, w) < 1:
+        raise ValueError("%s: the latent is empty, shape %s" % (what, tuple(latent.shape)))
+    if not latent.is_contiguous():
+        raise ValueError("%s: the latent must be contiguous, got strides %s" % (what, tuple(latent.stride())))
+    if (h * w) % 4 != 0:
+        raise ValueError("%s: H * W = %d is not a multiple of 4" % (what, h * w))
+    if mode not in RESAMPLE_MODES:
+        raise ValueError("%s: unknown mode %r (one of %s)" % (what, mode, ", ".join(RESAMPLE_MODES)))
+    if maps and c != 3:
+        raise ValueError("%s: the maps form needs a latent of C == 3 channels (x, y, occlusion), got %d" % (what, c))
+    clamp_from = c if clamp_from is None else int(clamp_from)
+    if clamp_from < 0:
+        raise ValueError("%s: clamp_from must be a channel index >= 0 (None: no clamp), got %d" % (what, clamp_from))
+    idx, frac = resample_tables(times, t)
+    n = int(idx.shape[0])
+    if n > 65535 or b > 65535:
+        raise ValueError("%s: at most 65535 output frames and batch elements per call, got %d and %d" % (what, n, b))
+    dev = latent.device
+
+    def result(name, x, shape):
+        if x is None:
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or tuple(x.shape) != shape or not x.is_contiguous() or x.device != dev:
+            raise ValueError("%s: %s must be a contiguous float32 %s tensor on the latent's device" % (what, name, shape))
+        return x
+
+    out = result("out", out, (b, c, n, h, w))
+    conf = result("conf", conf, (b, 1, n, h, w)) if maps else None
+    for name, x in (("latent", latent), ("out", out), ("conf", conf)):
+        if x is not None and x.data_ptr() % 16 != 0:
+            raise ValueError("%s: %s is not 16-byte aligned" % (what, name))
+    ident_x = _identity_table(w, dev) if maps and residual else None
+    ident_y = _identity_table(h, dev) if maps and residual else None
+    idx_d = torch.from_numpy(idx).to(dev, non_blocking=True)
+    frac_d = torch.from_numpy(frac).to(dev, non_blocking=True)
+    lib.check(lib.lfdm_latent_resample_f32(_p(latent), _p(idx_d), _p(frac_d), _p(ident_x), _p(ident_y), _p(out), _p(conf), b, c, t, n, h, w,
+                                           RESAMPLE_MODES.index(mode), clamp_from, _stream(lib)), "lfdm_latent_resample_f32")
+    return out, conf
+
+
+def latent_resample(latent, times, mode="linear", clamp_from=None, out=None):
+    """lfdm_latent_resample_f32: latent (B, C, T, H, W) fp32, contiguous -> (B, C, T', H, W), frame j taken at times[j] (resample_tables:
+    floats in [0, T - 1], any order, repeats allowed).  mode "linear": x[i] + a (x[i+1] - x[i]); "cubic": Catmull-Rom with the end frames
+    duplicated.  An integer time gives that frame bit for bit in both modes (selected: no other frame is read).  clamp_from: interpolated
+    values of channels >= clamp_from are clamped to [-1, 1] (None: no clamp).  H * W % 4 == 0.  Everything is checked before the launch."""
+    return _resample_call("latent_resample", latent, times, mode, clamp_from, False, False, out, None)[0]
+
+
+def latent_resample_maps(latent, times, mode="linear", residual=False, clamp_from=None, out=None, conf=None):
+    """latent_resample of a (B, 3, T, H, W) latent and FlowDiffusion._maps of the result in one launch -> (maps (B, 3, T', H, W), conf
+    (B, 1, T', H, W)): maps = the resampled latent, with torch.linspace(-1, 1, .) added to channels 0 (x) and 1 (y) when `residual`
+    (use_residual_flow); conf = (ch2 + 1) * 0.5.  At an integer time both are _maps(latent[:, :, i]) bit for bit."""
+    return _resample_call("latent_resample_maps", latent, times, mode, clamp_from, True, bool(residual), out, conf)

@@ -998,6 +998,36 @@ int lfdm_video_prep_u8(const unsigned char* store, int64_t store_frames, const i
                        const int* hue_shift, const int* valid, const float* mean, float* out, int batch, int frames, int store_size,
                        int image_size, int jitter, int launches, void* ws, size_t ws_bytes, lfdm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Temporal resampling of a sampled flow latent (additive under ABI 12): frames at other instants than the sampled ones -
+ * a higher frame rate, slow motion, reverse, ping-pong - from the latent, without sampling more frames.  Every frame's warp field refers
+ * to the same source image, so a field between two frames is a weighted mix of its neighbours.
+ *
+ * lfdm_latent_resample_f32: out (batch, channels, out_frames, h, w) from latent (batch, channels, frames, h, w), planar fp32.  Output
+ * frame j is taken at time idx[j] + frac[j]: idx DEVICE (out_frames) int32 in 0 .. frames - 1, frac DEVICE (out_frames) fp32 in [0, 1),
+ * any order, repeats allowed.  The tables are device memory the entry point cannot read: THE CALLER CHECKS them (and that frac == 0 where
+ * idx == frames - 1); the kernel clamps idx and its neighbours into 0 .. frames - 1, so a bad table never reads outside latent.
+ *   frac[j] == 0           frame idx[j] bit for bit, in both modes: selected, not multiplied - no other frame is read, so a NaN or an
+ *                          infinity elsewhere cannot reach it, and frames == 1 is legal.  Not clamped.
+ *   LFDM_RESAMPLE_LINEAR   x[i] + a * (x[i+1] - x[i]), a = frac[j]: three fp32 roundings, no fma.
+ *   LFDM_RESAMPLE_CUBIC    Catmull-Rom over x0 .. x3 = frames max(i-1, 0), i, i+1, min(i+2, frames-1) (the end frames duplicated):
+ *                          ((w0 x0 + w1 x1) + w2 x2) + w3 x3 in fp32 without fma, w0 = ((2 - a) a - 1) a / 2, w1 = ((3a - 5) a^2 + 2) / 2,
+ *                          w2 = ((4 - 3a) a + 1) a / 2, w3 = (a - 1) a^2 / 2, each evaluated in fp64 and rounded once to fp32.
+ * clamp_from: interpolated values of channels >= clamp_from are clamped to [-1, 1] (cubic weights overshoot, the occlusion channel
+ * lives in [-1, 1]); clamp_from >= channels: no clamp.
+ * The maps form (conf != NULL; channels == 3): the launch also does what FlowDiffusion._maps does behind it - conf (batch, 1,
+ * out_frames, h, w) = (ch2 + 1) * 0.5 (two fp32 operations), and with ident_x (w floats) / ident_y (h floats) - DEVICE,
+ * torch.linspace(-1, 1, .) made by the caller, both or neither - out channel 0 += ident_x[x], channel 1 += ident_y[y] (one fp32 add:
+ * the residual-flow case).  At frac == 0 that is _maps of the selected frame bit for bit.
+ * h * w % 4 == 0.  One thread per 4 adjacent values: 16-byte loads and stores; grid (plane chunks, out_frames, batch), out_frames and
+ * batch <= 65535; no atomics, nothing depends on launch order: results are bit-identical from run to run. */
+/* Layout: all operands dense; latent, out, conf 16 B; out / conf may not alias latent or each other. */
+#define LFDM_RESAMPLE_LINEAR 0
+#define LFDM_RESAMPLE_CUBIC 1
+int lfdm_latent_resample_f32(const float* latent, const int* idx, const float* frac, const float* ident_x, const float* ident_y,
+                             float* out, float* conf, int batch, int channels, int frames, int out_frames, int h, int w, int mode,
+                             int clamp_from, lfdm_stream_t stream);
+
 /* Box calibration, not on the product path (bench.py prints it beside every timing; ABI version 7): `blocks` workgroups of four
  * wavefronts run `iters` x 4 independent v_mfma_f32_32x32x2_f32 (2 * 32 * 32 * 2 FLOP each, pseudo-random operands) and
  * record, per workgroup b, out[2b] = shader cycles and out[2b+1] = 100 MHz real-time ticks of the loop: effective clock (MHz) =

@@ -9,6 +9,7 @@ misc.flow2fig, not grid2fig's drawing) and --gif indexed writes its palette indi
         --bert /data/bert-base-cased --image face.jpg --text happiness anger --out demo_out
     python tools/demo.py --synthetic --total-frames 112 --overlap 4 --out demo_out      # a long video: three chained 40-frame windows
     python tools/demo.py --synthetic --render device --gif indexed --out demo_out       # strip and palette indices made on the GPU
+    python tools/demo.py --synthetic --fps-factor 4 --render device --gif indexed      # 157 frames decoded from the 40 sampled ones
     python tools/demo.py --synthetic --out demo_out        # random-init weights, random image, fixed embedding:
                                                             # exercises the whole pipeline where no checkpoint exists
 """
@@ -58,10 +59,26 @@ def build_parser():
     ap.add_argument("--gif", choices=("rgb", "indexed"), default="rgb",
                     help="rgb (default): RGB frames, PIL quantises each; indexed: the device's 6x6x6-palette indices (ordered dither) written "
                          "as they are - needs --render device")
+    ap.add_argument("--fps-factor", type=int, default=1,
+                    help="K output frames per sampled interval, decoded from the sampled latent at the times j / K (FlowDiffusion.decode_at, "
+                         "DESIGN.md 4.9): (frames - 1) * K + 1 frames for the sampling cost of --frames; 1 (default): off")
+    ap.add_argument("--interp", choices=("linear", "cubic"), default="linear", help="how the latent is interpolated between sampled frames")
+    ap.add_argument("--reverse", action="store_true", help="play the sampled motion backwards")
+    ap.add_argument("--pingpong", action="store_true", help="forward, then back: a GIF that loops seamlessly")
     return ap
 
 
+def retime(args, frames):
+    """The frame times of --fps-factor / --reverse / --pingpong for a sample of `frames` frames, or None when none of them is given."""
+    if args.fps_factor == 1 and not args.reverse and not args.pingpong:
+        return None
+    from cvpr23_lfdm_amd.retime import frame_times
+    return frame_times(frames, args.fps_factor, reverse=args.reverse, pingpong=args.pingpong)
+
+
 def check_args(args):
+    if args.fps_factor < 1:
+        sys.exit("--fps-factor must be at least 1")
     if args.gif == "indexed" and args.render != "device":
         sys.exit("--gif indexed needs --render device: the palette indices are made by the device rendering")
     if args.use_ema and (args.synthetic or not args.dm_ckpt):
@@ -136,6 +153,9 @@ def main():
             model.sample_long_video(args.cond_scale, args.total_frames, overlap=args.overlap)
         else:
             model.sample_one_video(cond_scale=args.cond_scale)
+        times = retime(args, args.total_frames if args.total_frames > 0 else args.frames)
+        if times is not None:
+            model.decode_at(times, args.interp)
         path = os.path.join(args.out, "%04d_%s_%s_%.2f.gif" % (i, text.replace(" ", "_"), name, args.cond_scale))
         torch.cuda.synchronize()
         t1 = time.perf_counter()

@@ -1,17 +1,20 @@
 #!/usr/bin/env python
 """Paired, full-reference evaluation of checkpoints on the device (cvpr23_lfdm_amd.evaluate): per-frame L1, MSE / PSNR and
-SSIM in image space, end-point and occlusion error in latent-flow space.  Three subcommands share tools/demo.py's model options:
+SSIM in image space, end-point and occlusion error in latent-flow space.  Four subcommands share tools/demo.py's model options:
 
   lfae   the reference's LFAE/test_flowautoenc_*.py loop: every test video reconstructed from its first frame through the frozen LFAE;
          the JSON carries the reference's keys out_loss / warp_loss (same normalisation) plus L1 / PSNR / SSIM of both outputs
   dm     DM/test_video_flow_diffusion_*.py's sampling loop with a measurement: a video sampled from each test video's first frame and
          label, against the real video, against the LFAE's own reconstruction and, in flow space, against the pseudo ground truth
   ab     two sampling configurations on one input, B against A per frame and in summary (what is paired: DESIGN.md 4.6)
+  interp what temporal interpolation of the latent costs on real motion: every test video's pseudo-ground-truth latent
+         thinned to every --factor-th frame, resampled back (--interp linear | cubic) and decoded, against the full latent's decode
 
     python tools/eval.py lfae --lfae-ckpt RegionMM.pth --dataset mug --data-dir /data/MUG --out lfae.json
     python tools/eval.py dm --lfae-ckpt RegionMM.pth --dm-ckpt flowdiff.pth --bert /data/bert-base-cased --dataset mug --data-dir /data/MUG
     python tools/eval.py ab --lfae-ckpt RegionMM.pth --dm-ckpt flowdiff.pth --bert /data/bert-base-cased --image face.jpg --text anger \
         --a sampler=reference,steps=100 --b sampler=dpmpp_2m,steps=20,conv_precision=bf16
+    python tools/eval.py interp --lfae-ckpt RegionMM.pth --dataset mug --data-dir /data/MUG --factor 2 --interp cubic
     python tools/eval.py ab --synthetic --a steps=10 --b steps=10,conv_precision=bf16      # random-init weights: exercises the path
 
 FVD is not computed: it needs an I3D network this repository does not ship.  Non-finite numbers (the PSNR of equal frames) are written
@@ -72,6 +75,12 @@ def build_parser():
         p = sub.add_parser(name)
         common(p)
         data(p)
+    p = sub.add_parser("interp")
+    common(p)
+    data(p)
+    p.add_argument("--factor", type=int, default=2, help="keep every FACTOR-th latent frame and interpolate the others back; of each video the "
+                                                          "first 1 + FACTOR * ((frames - 1) // FACTOR) frames are used")
+    p.add_argument("--interp", choices=("linear", "cubic"), default="linear")
     p = sub.add_parser("ab")
     common(p)
     p.add_argument("--a", default="", help="configuration A as key=value[,key=value...] over sampler, steps, conv_precision, use_ema")
@@ -115,7 +124,7 @@ def build_model(args, overrides=None):
     cfg.update(overrides or {})
     if cfg["use_ema"] and (args.synthetic or not args.dm_ckpt):
         sys.exit("use_ema needs --dm-ckpt: a checkpoint with a 'diffusion_ema' entry")
-    model = _demo().make_model(args, need_dm=args.command != "lfae", **cfg)
+    model = _demo().make_model(args, need_dm=args.command not in ("lfae", "interp"), **cfg)
     if args.synthetic:          # the frozen-LFAE pass also runs the two predictors, which the demo never does
         import synth
         model.region_predictor.load_state_dict(synth.region_state())
@@ -186,6 +195,36 @@ def run_dm(args):
     return out
 
 
+def run_interp(args):
+    if args.factor < 1:
+        sys.exit("--factor must be at least 1")
+    model, _ = build_model(args)
+    mean, it = batches(args)
+    names = ("video", "interp_vs_real", "lfae_vs_real")
+    acc = {k: E.MetricAccumulator() for k in names}
+    held = {k: E.MetricAccumulator() for k in names}
+    flow, flow_held = E.FlowAccumulator(), E.FlowAccumulator()
+    used = 0
+    for real_vid, _, _ in it:
+        used = 1 + args.factor * ((real_vid.shape[2] - 1) // args.factor)
+        real_vid = real_vid[:, :, :used]
+        res = E.interpolation_error(model, real_vid, real_vid[:, :, 0], factor=args.factor, mode=args.interp, mean=mean, domain=args.domain)
+        mask = res["held_out"]
+        for k in names:
+            acc[k].update(res[k]["table"])
+            if bool(mask.any()):
+                held[k].update(res[k]["table"][:, mask.to(res[k]["table"].device)].contiguous())
+        flow.update(res["flow"]["table"])
+        if bool(mask.any()):
+            flow_held.update(res["flow"]["table"][:, mask.to(res["flow"]["table"].device)].contiguous())
+    out = {k: a.result() for k, a in acc.items()}
+    out["flow"] = flow.result()
+    if flow_held.frames:
+        out["held_out"] = dict({k: a.result() for k, a in held.items()}, flow=flow_held.result())
+    out.update(factor=args.factor, interp=args.interp, frames_used=used, domain=args.domain, mean=list(mean))
+    return out
+
+
 def run_ab(args):
     model_a, cfg_a = build_model(args, parse_overrides(args.a))
     model_b, cfg_b = build_model(args, parse_overrides(args.b))
@@ -209,7 +248,7 @@ def run_ab(args):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    out = jsonable({"lfae": run_lfae, "dm": run_dm, "ab": run_ab}[args.command](args))
+    out = jsonable({"lfae": run_lfae, "dm": run_dm, "ab": run_ab, "interp": run_interp}[args.command](args))
     out["command"] = args.command
     path = args.out or "eval_%s.json" % args.command
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
