@@ -10,6 +10,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include "lfdm_device.h"
+#include "lfdm_philox.h"
 #include "../../include/lfdm_hip.h"
 
 namespace {
@@ -277,14 +278,53 @@ struct KnownPre<true, PRE> {
   }
 };
 
+// Counter-based step noise (lfdm_sampler_step_counter_f32): the operands of the update kernel's GENERATING variant, which
+// computes noise[b, i] = lfdm_noise_element(seeds[b], i, step, 2, *window) in registers instead of loading it.  Empty for the loading variants.
+template <bool GEN>
+struct GenOps {};
+template <>
+struct GenOps<true> {
+  const uint64_t* seeds;     // (B): the videos' seeds
+  const uint32_t* window;    // one device word: the window number (0 for one video)
+};
+// The generating variant's registers: the video's key and the two uniform counter words.  The three words are wave-uniform loads; nothing
+// per element is requested from memory, and the Philox rounds of the PRE prefetched elements are issued next to the prefetch loads, in front
+// of the five histogram scans, whose barriers and round trips they run under.  Each thread evaluates the quad of its own element (four
+// neighbouring threads share one: the element mapping is the loading variant's, one element per thread and trip, so that the update
+// expression below is one source expression for both).
+template <bool GEN>
+struct GenPre {
+  __device__ __forceinline__ void head(const GenOps<GEN>&, const int32_t*, int) {}
+  __device__ __forceinline__ float draw(bool, int64_t) const { return 0.f; }
+};
+template <>
+struct GenPre<true> {
+  uint64_t seed;
+  uint32_t window, step;
+  __device__ __forceinline__ void head(const GenOps<true>& g, const int32_t* step_dev, int b) {
+    seed = g.seeds[b];
+    window = *g.window;
+    step = (uint32_t)(*step_dev);
+  }
+  __device__ __forceinline__ float draw(bool in, int64_t i) const {          // (i < n < 2^24)
+    return in ? lfdm_noise_element(seed, (uint32_t)i, step, (uint32_t)LFDM_NOISE_STREAM_STEP, window) : 0.f;
+  }
+};
+
+// Both optional operand sets as ONE trailing kernel argument: empty (one byte, like KnownOps<false> alone before) for the plain instantiation,
+// so the kernel-argument layout of the loading instantiations is what it was.
+template <bool KNOWN, bool GEN>
+struct StepOps : KnownOps<KNOWN>, GenOps<GEN> {};
+
 // KNOWN: the final store of x selects a * known + s * known_noise at the frames the byte mask marks; x0_out, the threshold, the housekeeping and
 // every other frame are the plain variant's.  What was chosen for the loads: the step counter and, behind it, the level pair are requested first
 // (that two-trip chain runs under the five histogram scans, like the operands); the mask byte, known and known_noise of the PRE prefetched
 // elements are loaded UNCONDITIONALLY in the same batch as today's prefetch (no round trip in front of the search; values at unmasked frames
 // are loaded but only ever pass through a select, so they may be NaN); the loop behind the prefetched elements branches on the mask byte.
 // The frame index of an element is carried along, not divided out (KnownPre).
+// GEN: `noise` is not an operand (null); the step noise is computed where it is loaded otherwise (GenPre).
 // grid (nblk, B)
-template <bool KNOWN>
+template <bool KNOWN, bool GEN>
 __global__ __launch_bounds__(256) void sampler_update_kernel(float* __restrict__ x,
                                                              const float* __restrict__ eps,
                                                              const float* __restrict__ noise,
@@ -293,8 +333,10 @@ __global__ __launch_bounds__(256) void sampler_update_kernel(float* __restrict__
                                                              const float* __restrict__ coef,
                                                              const int32_t* step_dev,      // (no __restrict__: advance_dev is the same word)
                                                              Ranks rk, unsigned* __restrict__ hists, int hist_samples,
-                                                             unsigned* __restrict__ ticket, int32_t* advance_dev, KnownOps<KNOWN> kf) {
+                                                             unsigned* __restrict__ ticket, int32_t* advance_dev, StepOps<KNOWN, GEN> so) {
   __shared__ unsigned s_part[256], s_res[4];
+  const KnownOps<KNOWN>& kf = so;
+  const GenOps<GEN>& gen = so;
   const int b = blockIdx.y;
   float* xb = x + (int64_t)b * n;
   const float* eb = eps + (int64_t)b * n;
@@ -308,6 +350,8 @@ __global__ __launch_bounds__(256) void sampler_update_kernel(float* __restrict__
   float p_x0[PRE], p_e[PRE], p_x[PRE], p_n[PRE];
   KnownPre<KNOWN, PRE> kp;
   kp.head(kf, step_dev, b, n);
+  GenPre<GEN> gp;
+  gp.head(gen, step_dev, b);
 #pragma unroll
   for (int k = 0; k < PRE; ++k) {
     const int64_t i = i0 + k * stride;
@@ -315,7 +359,10 @@ __global__ __launch_bounds__(256) void sampler_update_kernel(float* __restrict__
     p_x0[k] = in ? x0b[i] : 0.f;
     p_e[k] = in ? eb[i] : 0.f;
     p_x[k] = in ? xb[i] : 0.f;
-    p_n[k] = (in && nb) ? nb[i] : 0.f;
+    if constexpr (GEN)
+      p_n[k] = gp.draw(in, i);
+    else
+      p_n[k] = (in && nb) ? nb[i] : 0.f;
     kp.load(kf, k, in, i);
   }
   float s = 1.0f;                       // rk.frac < 0: static clipping, x0.clamp(-1, 1) (use_dynamic_thres=False, :729-732)
@@ -333,7 +380,7 @@ __global__ __launch_bounds__(256) void sampler_update_kernel(float* __restrict__
       if (x0o) x0o[i] = x0;
       float v = k_x0 * x0 + k_eps * p_e[k];
       if (k_x != 0.f) v += k_x * p_x[k];
-      if (k_noise != 0.f && nb) v += k_noise * p_n[k];
+      if (k_noise != 0.f && (GEN || nb)) v += k_noise * p_n[k];
       v = kp.pick(k, v);
       xb[i] = v;
     }
@@ -344,7 +391,11 @@ __global__ __launch_bounds__(256) void sampler_update_kernel(float* __restrict__
     if (x0o) x0o[i] = x0;
     float v = k_x0 * x0 + k_eps * eb[i];
     if (k_x != 0.f) v += k_x * xb[i];
-    if (k_noise != 0.f && nb) v += k_noise * nb[i];
+    if constexpr (GEN) {
+      if (k_noise != 0.f) v += k_noise * gp.draw(true, i);
+    } else {
+      if (k_noise != 0.f && nb) v += k_noise * nb[i];
+    }
     v = kp.tail(kf, i, v);
     xb[i] = v;
   }
@@ -470,6 +521,53 @@ __global__ void advance_step_kernel(int32_t* step_dev) {
   if (threadIdx.x == 0 && blockIdx.x == 0) *step_dev += 1;
 }
 
+// Counter-based noise written to memory (lfdm_philox_normal_f32 / lfdm_philox_bits_u32): out[b * row_stride + i], i < n, of video seeds[b].
+// One thread owns quad q = i >> 2 (no output is computed twice) and stores it as ONE 16-byte word where the row's base is 16-byte aligned
+// and the quad lies inside the row; the ragged last quad and rows on other alignments are stored element by element.  BITS: the raw
+// Philox words instead of the normals (tests).  grid (nblk, B)
+template <bool BITS>
+__global__ __launch_bounds__(256) void philox_fill_kernel(uint32_t* __restrict__ out, const uint64_t* __restrict__ seeds, uint32_t n,
+                                                          int64_t row_stride, uint32_t stream_id, uint32_t step, uint32_t window) {
+  const int b = blockIdx.y;
+  const uint64_t seed = seeds[b];
+  uint32_t* ob = out + (int64_t)b * row_stride;
+  const bool wide = (reinterpret_cast<uintptr_t>(ob) & 15u) == 0;
+  const uint32_t quads = (n + 3u) >> 2;
+  for (uint32_t q = blockIdx.x * 256u + threadIdx.x; q < quads; q += gridDim.x * 256u) {
+    const lfdm_philox_quad o = lfdm_noise_bits(seed, q, step, stream_id, window);
+    uint32_t v[4];
+#pragma unroll
+    for (unsigned j = 0; j < 4; ++j) v[j] = BITS ? o.r[j] : __float_as_uint(lfdm_noise_normal(o, j));
+    const uint32_t i = 4u * q;
+    if (wide && i + 4u <= n) {
+      uint4 w;
+      w.x = v[0]; w.y = v[1]; w.z = v[2]; w.w = v[3];
+      *reinterpret_cast<uint4*>(ob + i) = w;
+    } else {
+#pragma unroll
+      for (unsigned j = 0; j < 4; ++j)
+        if (i + j < n) ob[i + j] = v[j];
+    }
+  }
+}
+
+template <bool BITS>
+int run_philox_fill(const char* what, void* out, const uint64_t* seeds, int batch, int64_t n, int64_t row_stride, unsigned stream_id,
+                    unsigned step, unsigned window, hipStream_t stream) {
+  char msg[160];
+  if (!out || !seeds || batch <= 0 || n <= 0 || n >= (1 << 24) || row_stride < n || stream_id > 2u) {
+    snprintf(msg, sizeof msg, "%s: bad arguments (0 < n < 2^24, row_stride >= n, stream_id 0 .. 2)", what);
+    lfdm_set_error(msg);
+    return LFDM_EINVAL;
+  }
+  const int64_t quads = (n + 3) / 4;
+  int64_t nb = (quads + 255) / 256;
+  if (nb > 1024) nb = 1024;
+  LFDM_LAUNCH((philox_fill_kernel<BITS>), dim3((unsigned)nb, batch), dim3(256), 0, stream, reinterpret_cast<uint32_t*>(out), seeds, (uint32_t)n,
+              row_stride, (uint32_t)stream_id, (uint32_t)step, (uint32_t)window);
+  return lfdm_check_launch(what);
+}
+
 Ranks make_ranks(int64_t n, float quantile) {
   // torch.quantile: rank = q * (n - 1) evaluated in the input dtype (fp32), then floor / lerp
   const float pos = quantile * (float)(n - 1);
@@ -587,9 +685,11 @@ int make_known(const char* what, const float* known, const float* known_noise, c
 
 // The one launch sequence of every sampler step: [histogram clear for batch > 2] pass 0, two select passes, update.  MS: the multistep update
 // (second = hist) instead of the DDIM / DDPM one (second = noise); KNOWN: the update kernel's known-frame instantiation.
-template <bool MS, bool KNOWN>
+template <bool MS, bool KNOWN, bool GEN = false>
 int run_step(const char* what, float* x, const float* eps, float* second, float* x0_out, int batch, int64_t n, const float* coef,
-             int32_t* step_dev, float quantile, int advance, void* ws, size_t ws_bytes, KnownOps<KNOWN> kf, hipStream_t stream) {
+             int32_t* step_dev, float quantile, int advance, void* ws, size_t ws_bytes, KnownOps<KNOWN> kf, hipStream_t stream,
+             GenOps<GEN> gen = GenOps<GEN>{}) {
+  static_assert(!(MS && GEN), "the multistep update draws nothing");
   char msg[160];
   if (!x || !eps || (MS && !second) || !coef || !step_dev || batch <= 0 || n <= 0 || n >= (1 << 24)) {
     snprintf(msg, sizeof msg, "%s: bad arguments (n < 2^24)", what);
@@ -623,12 +723,13 @@ int run_step(const char* what, float* x, const float* eps, float* second, float*
   LFDM_LAUNCH(quantile_pass0_kernel, grid, block, 0, stream, (const float*)x, eps, x0buf, n, coef,
               (const int32_t*)step_dev, hists);         // (also the x0 = c_x*x - c_eps*eps pass: columns 0-1 of either table)
   if (dynamic) run_select(x0buf, batch, n, rk, hists, stream);
-  if (MS)
+  if constexpr (MS)
     LFDM_LAUNCH((sampler_update_ms_kernel<KNOWN>), grid, block, 0, stream, x, second, (const float*)x0buf, x0_out, n, coef,
                 (const int32_t*)step_dev, rk, hists, fold_clear ? batch : 0, ticket, advance ? step_dev : (int32_t*)nullptr, kf);
-  else
-    LFDM_LAUNCH((sampler_update_kernel<KNOWN>), grid, block, 0, stream, x, eps, (const float*)second, x0buf, x0_out, n, coef,
-                (const int32_t*)step_dev, rk, hists, fold_clear ? batch : 0, ticket, advance ? step_dev : (int32_t*)nullptr, kf);
+  else if constexpr (!MS)
+    LFDM_LAUNCH((sampler_update_kernel<KNOWN, GEN>), grid, block, 0, stream, x, eps, (const float*)second, x0buf, x0_out, n, coef,
+                (const int32_t*)step_dev, rk, hists, fold_clear ? batch : 0, ticket, advance ? step_dev : (int32_t*)nullptr,
+                StepOps<KNOWN, GEN>{kf, gen});
   return lfdm_check_launch(what);
 }
 
@@ -683,4 +784,50 @@ extern "C" int lfdm_known_blend_f32(float* x, const float* known, const float* k
   LFDM_LAUNCH(known_blend_kernel, dim3(blocks_for(n), batch), dim3(256), 0, stream, x, known, known_noise, frame_mask, a, s, (unsigned)n,
               kf.frames, kf.frame_elems);
   return lfdm_check_launch("known_blend");
+}
+
+extern "C" int lfdm_philox_normal_f32(float* out, const uint64_t* seeds, int batch, int64_t n, int64_t row_stride, unsigned stream_id,
+                                      unsigned step, unsigned window, lfdm_stream_t stream_) {
+  return run_philox_fill<false>("philox_normal", out, seeds, batch, n, row_stride, stream_id, step, window, (hipStream_t)stream_);
+}
+
+extern "C" int lfdm_philox_bits_u32(uint32_t* out, const uint64_t* seeds, int batch, int64_t n, int64_t row_stride, unsigned stream_id,
+                                    unsigned step, unsigned window, lfdm_stream_t stream_) {
+  return run_philox_fill<true>("philox_bits", out, seeds, batch, n, row_stride, stream_id, step, window, (hipStream_t)stream_);
+}
+
+namespace {
+int make_gen(const char* what, const uint64_t* seeds, const uint32_t* window, GenOps<true>* gen) {
+  if (!seeds || !window) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "%s: seeds (batch 64-bit words) and window (one 32-bit word) must both be given, on the device", what);
+    lfdm_set_error(msg);
+    return LFDM_EINVAL;
+  }
+  gen->seeds = seeds;
+  gen->window = window;
+  return 0;
+}
+}  // namespace
+
+extern "C" int lfdm_sampler_step_counter_f32(float* x, const float* eps, const uint64_t* seeds, const uint32_t* window, float* x0_out,
+                                             int batch, int64_t n, const float* coef, int32_t* step_dev, float quantile, int advance,
+                                             void* ws, size_t ws_bytes, lfdm_stream_t stream_) {
+  GenOps<true> gen;
+  if (int rc = make_gen("sampler_step_counter", seeds, window, &gen)) return rc;
+  return run_step<false, false, true>("sampler_step_counter", x, eps, nullptr, x0_out, batch, n, coef, step_dev, quantile, advance, ws,
+                                      ws_bytes, KnownOps<false>{}, (hipStream_t)stream_, gen);
+}
+
+extern "C" int lfdm_sampler_step_counter_known_f32(float* x, const float* eps, const uint64_t* seeds, const uint32_t* window, float* x0_out,
+                                                   int batch, int64_t n, const float* coef, int32_t* step_dev, float quantile,
+                                                   int advance, void* ws, size_t ws_bytes, const float* known, const float* known_noise,
+                                                   const unsigned char* frame_mask, const float* level, int frames, int64_t frame_elems,
+                                                   lfdm_stream_t stream_) {
+  GenOps<true> gen;
+  if (int rc = make_gen("sampler_step_counter_known", seeds, window, &gen)) return rc;
+  KnownOps<true> kf;
+  if (int rc = make_known("sampler_step_counter_known", known, known_noise, frame_mask, level, n, frames, frame_elems, &kf)) return rc;
+  return run_step<false, true, true>("sampler_step_counter_known", x, eps, nullptr, x0_out, batch, n, coef, step_dev, quantile, advance,
+                                     ws, ws_bytes, kf, (hipStream_t)stream_, gen);
 }

@@ -5,7 +5,9 @@ select] -> Unet3D trunk (HIP kernels) -> fused x0 / radix-select quantile / upda
 whole step is captured once as a hipGraph and replayed for every timestep (all step-dependent
 scalars live in device tables indexed by a device step counter, the reference's per-step host
 syncs are gone).  Noise comes from torch's generator in the reference's order
-(SURVEY.md Appendix D), so a fixed seed reproduces.
+(SURVEY.md Appendix D), so a fixed seed reproduces.  Opt-in `noise="counter"`: per-video seeds, every
+normal a function of (seed, window, stream, step, element), the step noise computed inside the update
+kernel.
 """
 import math
 import os
@@ -43,12 +45,16 @@ class GaussianDiffusion(nn.Module):
     def __init__(self, denoise_fn, *, image_size, num_frames, text_use_bert_cls=False, channels=3,
                  timesteps=1000, sampling_timesteps=250, ddim_sampling_eta=1., loss_type='l1',
                  use_dynamic_thres=False, dynamic_thres_percentile=0.9, null_cond_prob=0.1,
-                 per_element_loss=False, sampler="reference", long_attention=False):
+                 per_element_loss=False, sampler="reference", long_attention=False, noise="torch"):
         """Reference signature + `sampler` (keyword): what `sample()` runs.  "reference" (default): the reference's own pair, DDIM when
         sampling_timesteps < timesteps, ancestral DDPM otherwise.  "dpmpp_2m": DPM-Solver++(2M) (Lu et al. 2022), the second-order multistep
         rule on the thresholded data prediction, one UNet evaluation per step, on the reference's DDIM time grid; "dpmpp_1": its first-order
         form on every step.  Both are deterministic: nothing is drawn after x_T and `ddim_sampling_eta` is ignored (`_ms_step_tables`)."""
         super().__init__()
+        # noise (keyword, default "torch"): where sampling noise comes from.  "torch": torch's default generator in the reference's draw order.
+        # "counter": per-video seeds - every normal is a function of (video seed, window, stream, step, element) (DESIGN.md 4.10); `sample`
+        # then needs `seeds`.  Training draws (t, masks, q_sample's noise) stay on torch's generator in both modes.
+        self.noise = noise
         # long_attention (keyword, default False): up to 256 frames; the denoiser must have been built with the same option (Unet3D)
         self.long_attention = bool(long_attention)
         check_num_frames(num_frames, frame_limit(self.long_attention))
@@ -107,6 +113,17 @@ class GaussianDiffusion(nn.Module):
         self.rank_shard = None
 
     SAMPLERS = ("reference", "dpmpp_1", "dpmpp_2m")
+    NOISE_MODES = ("torch", "counter")
+
+    @property
+    def noise(self):
+        return self._noise
+
+    @noise.setter
+    def noise(self, value):
+        if value not in self.NOISE_MODES:
+            raise ValueError("noise must be one of %s, got %r" % (self.NOISE_MODES, value))
+        self.__dict__["_noise"] = value
 
     @property
     def sampler(self):
@@ -301,13 +318,57 @@ class GaussianDiffusion(nn.Module):
                              % ((shape[0], shape[2]), getattr(known_mask, "dtype", type(known_mask)), tuple(getattr(known_mask, "shape", ()))))
         return True
 
+    def _check_seeds(self, batch, seeds, window=0):
+        """noise="counter": the list of `batch` seeds (Python ints in [0, 2^64)); noise="torch": None.  ValueError before anything is launched
+        when the seeds do not fit the mode, their number is not the batch, one is out of range, or a noise tape is installed next to them."""
+        if self.noise != "counter":
+            if seeds is not None:
+                raise ValueError("sample: seeds need noise='counter' (this model draws from torch's generator: noise=%r)" % (self.noise,))
+            if window != 0:
+                raise ValueError("sample: window needs noise='counter'")
+            return None
+        if seeds is None:
+            raise ValueError("sample: noise='counter' needs seeds (one integer in [0, 2^64) per video)")
+        if self.noise_source is not None:
+            raise ValueError("sample: a noise_source (tape) and noise='counter' exclude each other - replay counter_tape(...) under noise='torch'")
+        if isinstance(window, bool) or not isinstance(window, int) or not 0 <= window < (1 << 32):
+            raise ValueError("sample: window must be an integer in [0, 2^32), got %r" % (window,))
+        return ops.check_seeds(seeds, batch, "sample: seeds")
+
+    def counter_tape(self, seeds, shape, ddim, window=0, known=False):
+        """The counter-based draws of one `sample` call as a noise tape: a callable with the `noise_source` signature that returns, in the
+        default path's draw order, the tensors ops.philox_normal writes for `seeds` - x_T (stream 0), then the known-frame noise (stream 1) if
+        `known`, then one tensor per drawing step of the schedule (stream 2, step = the step's index; none under the multistep samplers).
+        Installed as `noise_source` of a noise="torch" model - or handed to the oracle - it reproduces the noise="counter" sample."""
+        shape = tuple(shape)
+        seeds = ops.check_seeds(seeds, shape[0], "counter_tape: seeds")
+        dev = "cuda" if _native.library().kind == "hip" else "cpu"
+        draws = [] if self.sampler != "reference" else self._step_tables(ddim)[2]
+        plan = [(ops.NOISE_STREAM_XT, 0)] + ([(ops.NOISE_STREAM_KNOWN, 0)] if known else [])
+        plan += [(ops.NOISE_STREAM_STEP, i) for i, d in enumerate(draws) if d]
+        seeds_dev = ops.seeds_tensor(seeds, dev)
+        state = {"next": 0}
+
+        def tape(want_shape):
+            if tuple(want_shape) != shape:
+                raise ValueError("counter_tape: made for draws of shape %s, asked for %s" % (shape, tuple(want_shape)))
+            if state["next"] >= len(plan):
+                raise IndexError("counter_tape: the schedule makes %d draws, one more was asked for" % len(plan))
+            stream, step = plan[state["next"]]
+            state["next"] += 1
+            return ops.philox_normal(torch.empty(shape, device=dev), seeds_dev, stream=stream, step=step, window=window)
+
+        return tape
+
     # ------------------------------------------------------------------ sampling
     @torch.no_grad()
-    def sample(self, fea, cond=None, cond_scale=1., batch_size=16, *, known=None, known_mask=None):
+    def sample(self, fea, cond=None, cond_scale=1., batch_size=16, *, known=None, known_mask=None, seeds=None, window=0):
         """Reference :762-775.  fea: planar (B, 256, S, S); cond: (B, 768) tensor or list[str].  Runs `self.sampler`.
         known (B, C, T, S, S) float32 + known_mask (B, T) bool (keyword only, both or none): condition on known frames by the replacement
         method - frame t of sample b is kept on the trajectory of known[b, :, t] and returned bit for bit where the mask is
-        set; values of `known` at other frames are never read into the result."""
+        set; values of `known` at other frames are never read into the result.
+        seeds (keyword only; needed by, and only allowed under, noise="counter"): one Python int in [0, 2^64) per video - video b is then a
+        function of seeds[b] (and of `window`, the window number of a long video) wherever it sits in the batch."""
         device = next(self.denoise_fn.parameters()).device
         if cond is not None and not is_list_str(cond):
             batch = cond.shape[0]
@@ -317,22 +378,26 @@ class GaussianDiffusion(nn.Module):
             batch = batch_size
         shape = (batch, self.channels, self.num_frames, self.image_size, self.image_size)
         self._check_known(shape, known, known_mask)
+        self._check_seeds(batch, seeds, window)
         if cond is not None:
             cond = self._embed(cond, device)
+        kw = dict(known=known, known_mask=known_mask, seeds=seeds, window=window)
         if self.sampler != "reference":
-            return self._sample(fea, shape, cond, cond_scale, True, sampler=self.sampler, known=known, known_mask=known_mask)
-        return self._sample(fea, shape, cond, cond_scale, self.is_ddim_sampling, known=known, known_mask=known_mask)
+            return self._sample(fea, shape, cond, cond_scale, True, sampler=self.sampler, **kw)
+        return self._sample(fea, shape, cond, cond_scale, self.is_ddim_sampling, **kw)
 
     @torch.no_grad()
-    def p_sample_loop(self, fea, shape, cond=None, cond_scale=1., *, known=None, known_mask=None):
-        return self._sample(fea, shape, cond, cond_scale, False, known=known, known_mask=known_mask)
+    def p_sample_loop(self, fea, shape, cond=None, cond_scale=1., *, known=None, known_mask=None, seeds=None, window=0):
+        return self._sample(fea, shape, cond, cond_scale, False, known=known, known_mask=known_mask, seeds=seeds, window=window)
 
     @torch.no_grad()
-    def ddim_sample(self, fea, shape, cond=None, cond_scale=1., clip_denoised=True, *, known=None, known_mask=None):
-        return self._sample(fea, shape, cond, cond_scale, True, known=known, known_mask=known_mask)
+    def ddim_sample(self, fea, shape, cond=None, cond_scale=1., clip_denoised=True, *, known=None, known_mask=None, seeds=None, window=0):
+        return self._sample(fea, shape, cond, cond_scale, True, known=known, known_mask=known_mask, seeds=seeds, window=window)
 
-    def _sample(self, fea, shape, cond, cond_scale, ddim, sampler="reference", known=None, known_mask=None):
+    def _sample(self, fea, shape, cond, cond_scale, ddim, sampler="reference", known=None, known_mask=None, seeds=None, window=0):
         conditioned = self._check_known(shape, known, known_mask)
+        seeds = self._check_seeds(shape[0], seeds, window)
+        counter = seeds is not None
         unet = self.denoise_fn
         pk = unet.packed()
         dev = next(unet.parameters()).device
@@ -371,7 +436,8 @@ class GaussianDiffusion(nn.Module):
         # ---- static step state ----------------------------------------------------------------
         # (the convolution precision explicitly: both modes share one pack - id(pk) does not tell a graph captured in the other mode apart)
         # (... and the sampler: a graph captured for one update rule must never be replayed for another)
-        key = (batch, frames, s, len(variants), float(cond_scale), bool(ddim), steps, id(pk), unet.conv_precision, sampler)
+        # (... and the noise mode: the counter mode's update kernel is the generating instantiation)
+        key = (batch, frames, s, len(variants), float(cond_scale), bool(ddim), steps, id(pk), unet.conv_precision, sampler, self.noise)
         if conditioned:
             # known frames: a plan (and graph) of its own, whose update kernel is the conditioned instantiation; the unconditioned key is unchanged
             key = key + ("known",)
@@ -390,6 +456,9 @@ class GaussianDiffusion(nn.Module):
                 # m_{i-1} of the multistep samplers; never cleared: the first step of a video is first order and does not read it
                 "hist": torch.empty(shape, device=dev) if multistep else None,
             }
+            if counter:
+                # static operands of the generating update kernel, refilled in place by every call: one captured graph serves every seed
+                plan.update({"seeds": torch.zeros(batch, dtype=torch.int64, device=dev), "window": torch.zeros(1, dtype=torch.int32, device=dev)})
             if conditioned:
                 # static operands of the conditioned update kernel, filled in place by every call (another mask / other frames: no new capture)
                 plan.update({"known": torch.empty(shape, device=dev), "known_noise": torch.empty(shape, device=dev),
@@ -430,20 +499,34 @@ class GaussianDiffusion(nn.Module):
                 kf = dict(known=plan["known"], known_noise=plan["known_noise"], frame_mask=plan["kmask"], level=plan["level"], frames=frames)
             if multistep:
                 ops.sampler_step_ms(x, eps, plan["hist"], b["coef"], step_dev, quantile=quantile, ws=plan["ws"], **kf)
+            elif counter:
+                ops.sampler_step(x, eps, None, b["coef"], step_dev, quantile=quantile, ws=plan["ws"], seeds=plan["seeds"], window=plan["window"],
+                                 **kf)
             else:
                 ops.sampler_step(x, eps, noise, b["coef"], step_dev, quantile=quantile, ws=plan["ws"], **kf)
 
         use_graph = (_native.library().kind == "hip" and os.environ.get("LFDM_NO_GRAPH", "0") != "1")
-        self._draw(x)                                   # x_T  (:753 / :788)
+        if counter:
+            ops.seeds_tensor(seeds, dev, out=plan["seeds"])
+            plan["window"].fill_(window)
+            ops.philox_normal(x, plan["seeds"], stream=ops.NOISE_STREAM_XT, window=window)
+        else:
+            self._draw(x)                               # x_T  (:753 / :788)
         if conditioned:
             # one more draw directly behind x_T's (every step draw keeps its place in the order), then x_T's known frames on the init level
             plan["known"].copy_(known)
             plan["kmask"].copy_(known_mask)
             plan["level"].copy_(level_dev)
-            self._draw(plan["known_noise"])
+            if counter:
+                ops.philox_normal(plan["known_noise"], plan["seeds"], stream=ops.NOISE_STREAM_KNOWN, window=window)
+            else:
+                self._draw(plan["known_noise"])
             ops.known_blend(x, plan["known"], plan["known_noise"], plan["kmask"], float(level_host[0, 0]), float(level_host[0, 1]), frames)
         step_dev.zero_()
         if use_graph and plan["graph"] is None:
+            # the captured kernels bind the coefficient table by pointer and later calls copy theirs into it: a copy of the capture's own,
+            # never the tensor `_step_tables_on` keeps (an in-place write would change the kept table under its still valid key)
+            bind["coef"] = bind["coef"].clone()
             # dry run allocates every scratch buffer outside the capture, then state is restored
             x_saved = x.clone()
             noise.zero_()
@@ -476,10 +559,12 @@ class GaussianDiffusion(nn.Module):
         # eager loop makes, tests/test_end_to_end.py); a replayed noise tape (`noise_source`, the parity tests) cannot be captured
         # and keeps one step per replay.
         # (the multistep samplers draw nothing after x_T: a noise tape does not stand in their way)
-        chunk = int(os.environ.get("LFDM_GRAPH_STEPS", "10")) if (use_graph and (self.noise_source is None or multistep)) else 1
+        # (counter mode: the step noise is computed inside the update kernel - nothing to capture or launch in front of a step, no draw flags:
+        #  one chunk graph per chunk length)
+        chunk = int(os.environ.get("LFDM_GRAPH_STEPS", "10")) if (use_graph and (self.noise_source is None or multistep or counter)) else 1
         if chunk <= 1:
             for i in range(steps):
-                if draws[i]:
+                if draws[i] and not counter:
                     self._draw(noise)
                 if use_graph:
                     plan["graph"].replay()
@@ -491,7 +576,7 @@ class GaussianDiffusion(nn.Module):
             graphs.clear()
             plan["chunk_buf_gen"] = unet._buf_gen
         for i0 in range(0, steps, chunk):
-            flags = tuple(bool(d) for d in draws[i0:i0 + chunk])
+            flags = tuple(bool(d) and not counter for d in draws[i0:i0 + chunk])
             g = graphs.get(flags)
             if g is None:
                 g = torch.cuda.CUDAGraph()

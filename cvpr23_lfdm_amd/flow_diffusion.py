@@ -70,7 +70,7 @@ class FlowDiffusion(nn.Module):
                  adam_betas=(0.9, 0.99), is_train=True, only_use_flow=True, use_residual_flow=False,
                  learn_null_cond=False, use_deconv=True, padding_mode="zeros", pretrained_pth="",
                  config_pth="", bert_path=None, *, conv_precision="fp32", sampler="reference", ema_decay=None, ema_start_step=0,
-                 max_grad_norm=None, skip_nonfinite=False, long_attention=False):
+                 max_grad_norm=None, skip_nonfinite=False, long_attention=False, noise="torch"):
         """Reference signature (video_flow_diffusion_model.py:19-37) + `bert_path`: a local Hugging Face directory of
         bert-base-cased for `cond=list[str]` (the reference downloads it with torch.hub; see text.py).  LFDM_BERT_PATH in
         the environment is the default, so unchanged caller scripts pick it up.
@@ -82,8 +82,12 @@ class FlowDiffusion(nn.Module):
         an exponential moving average of the denoiser's weights (`ema_weights()`, `ema_state_dict()`), global-norm gradient clipping and a
         guard that skips a step whose gradient is not finite, all decided on the device inside the optimizer step.
         long_attention (keyword only, default False): Unet3D.long_attention - up to 256 frames per window (and up to 256 pixels per frame in
-        the mid block) on the streaming attention kernels, for sampling and training."""
+        the mid block) on the streaming attention kernels, for sampling and training.
+        noise (keyword only, default "torch"): GaussianDiffusion.noise - "counter" gives every sampled video a seed of its own
+        (sample_one_video(seeds=...), sample_long_video(seed=...)).  Training draws stay on torch's generator."""
         super().__init__()
+        if noise not in GaussianDiffusion.NOISE_MODES:
+            raise ValueError("noise must be one of %s, got %r" % (GaussianDiffusion.NOISE_MODES, noise))
         self.long_attention = bool(long_attention)
         check_num_frames(num_frames, frame_limit(self.long_attention))        # (before the checkpoint and the config are read)
         if sampler not in GaussianDiffusion.SAMPLERS:
@@ -114,7 +118,7 @@ class FlowDiffusion(nn.Module):
                                            sampling_timesteps=sampling_timesteps, timesteps=timesteps,
                                            loss_type='l2', use_dynamic_thres=True,
                                            null_cond_prob=null_cond_prob, ddim_sampling_eta=ddim_sampling_eta, sampler=sampler,
-                                           long_attention=self.long_attention)
+                                           long_attention=self.long_attention, noise=noise)
         bert_path = bert_path or os.environ.get("LFDM_BERT_PATH")
         if bert_path:
             from .text import BertTextEncoder
@@ -149,8 +153,8 @@ class FlowDiffusion(nn.Module):
             torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count())
 
     # ------------------------------------------------------------------ sampling (a28)
-    def sample_one_video(self, cond_scale, *, known_latent=None, known_mask=None, frame_times=None, interp="linear"):
-        """Reference :190-216.  Results land in sample_vid_grid (B,2,T,S,S), sample_vid_conf (B,1,T,S,S),
+    def sample_one_video(self, cond_scale, *, known_latent=None, known_mask=None, frame_times=None, interp="linear", seeds=None):
+        """Reference :190-216.  seeds (keyword only; noise="counter"): one integer in [0, 2^64) per video of the batch (GaussianDiffusion.sample).  Results land in sample_vid_grid (B,2,T,S,S), sample_vid_conf (B,1,T,S,S),
         sample_out_vid / sample_warped_vid (B,3,T,H,W), and the latent the diffusion returned (B,3,T,S,S; the residual flow when
         use_residual_flow) in sample_latent.  known_latent (B,3,T,S,S) in that same space + known_mask (B,T) bool (keyword only, both or
         none): GaussianDiffusion.sample's known frames.  frame_times (keyword only; default None: off) + interp: after
@@ -162,13 +166,14 @@ class FlowDiffusion(nn.Module):
             img = self.sample_img.float().contiguous()
             dm = self.diffusion                                       # (bad known frames are refused before anything is launched)
             dm._check_known((img.shape[0], dm.channels, dm.num_frames, dm.image_size, dm.image_size), known_latent, known_mask)
+            dm._check_seeds(img.shape[0], seeds)
             skips = gen.encode(img)                                   # encoder ONCE per video
             b, _, h, w = img.shape
             d = 2 ** gen.num_down_blocks
             fea = gen.compute_fea_from_skips(skips, b, h // d, w // d)
             self.sample_img_fea = fea
             pred = self.diffusion.sample(fea, cond=self.sample_text, batch_size=1, cond_scale=cond_scale, known=known_latent,
-                                         known_mask=known_mask)
+                                         known_mask=known_mask, seeds=seeds)
             self.sample_latent = pred
             self._decode_sample(img, skips, pred)
         if frame_times is not None:
@@ -194,13 +199,14 @@ class FlowDiffusion(nn.Module):
         self.sample_out_vid = out
         self.sample_warped_vid = warped
 
-    def sample_long_video(self, cond_scale, total_frames, overlap=8, *, frame_times=None, interp="linear"):
+    def sample_long_video(self, cond_scale, total_frames, overlap=8, *, frame_times=None, interp="linear", seed=None):
         """A video of `total_frames` frames, longer than the model's window of num_frames, as a chain of windows: the LFAE
         encoder runs ONCE; chunk 0 is a plain sample; chunk j > 0 is conditioned on the last `overlap` latent frames of chunk j - 1 placed at
         its frames 0 .. overlap-1 (same source image, features and text condition - only the latent is chained); the result keeps chunk 0 whole
         and frames overlap.. of every later chunk, cut to total_frames, and is decoded in pieces of at most num_frames frames.  Results as
         sample_one_video's, with T = total_frames.  frame_times / interp (keyword only): as sample_one_video's, times in
-        [0, total_frames - 1]."""
+        [0, total_frames - 1].  seed (keyword only; noise="counter"): the long video's ONE seed - an integer in [0, 2^64), or one per video
+        of the batch; window w draws with counter word `window` = w, so a window can be made again without the ones before it."""
         nf = self.diffusion.num_frames
         total_frames, overlap = int(total_frames), int(overlap)
         if overlap < 1 or overlap >= nf:
@@ -212,19 +218,27 @@ class FlowDiffusion(nn.Module):
         gen = self.generator
         with torch.no_grad():
             img = self.sample_img.float().contiguous()
+            seeds = seed
+            if isinstance(seed, int) and not isinstance(seed, bool):
+                if img.shape[0] != 1:
+                    raise ValueError("sample_long_video: a batch of %d videos needs a sequence of %d seeds" % (img.shape[0], img.shape[0]))
+                seeds = [seed]
+            self.diffusion._check_seeds(img.shape[0], seeds)
+            skw = (lambda w: {}) if seeds is None else (lambda w: dict(seeds=seeds, window=w))
             skips = gen.encode(img)                                   # encoder ONCE per long video
             b, _, h, w = img.shape
             d = 2 ** gen.num_down_blocks
             fea = gen.compute_fea_from_skips(skips, b, h // d, w // d)
             self.sample_img_fea = fea
-            chunk = self.diffusion.sample(fea, cond=self.sample_text, batch_size=1, cond_scale=cond_scale)
+            chunk = self.diffusion.sample(fea, cond=self.sample_text, batch_size=1, cond_scale=cond_scale, **skw(0))
             pieces, have = [chunk], nf
             mask = torch.zeros((b, nf), dtype=torch.bool, device=chunk.device)
             mask[:, :overlap] = True
             while have < total_frames:
                 known = torch.zeros_like(chunk)
                 known[:, :, :overlap] = chunk[:, :, nf - overlap:]
-                chunk = self.diffusion.sample(fea, cond=self.sample_text, batch_size=1, cond_scale=cond_scale, known=known, known_mask=mask)
+                chunk = self.diffusion.sample(fea, cond=self.sample_text, batch_size=1, cond_scale=cond_scale, known=known, known_mask=mask,
+                                              **skw(len(pieces)))
                 pieces.append(chunk[:, :, overlap:])
                 have += nf - overlap
             latent = torch.cat(pieces, dim=2)[:, :, :total_frames].contiguous()
@@ -583,8 +597,9 @@ class FlowDiffusionFunctional(FlowDiffusion):
         out.pop("ref_img_fea", None)
         return out
 
-    def sample_one_video(self, sample_img, sample_text, cond_scale, *, known_latent=None, known_mask=None, frame_times=None, interp="linear"):
+    def sample_one_video(self, sample_img, sample_text, cond_scale, *, known_latent=None, known_mask=None, frame_times=None, interp="linear",
+                         seeds=None):
         self.set_sample_input(sample_img=sample_img, sample_text=sample_text)
         FlowDiffusion.sample_one_video(self, cond_scale, known_latent=known_latent, known_mask=known_mask, frame_times=frame_times,
-                                       interp=interp)
+                                       interp=interp, seeds=seeds)
         return {k: getattr(self, k) for k in ("sample_vid_grid", "sample_vid_conf", "sample_out_vid", "sample_warped_vid", "sample_latent")}

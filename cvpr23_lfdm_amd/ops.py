@@ -942,18 +942,112 @@ def _known_operands(what, x, known, known_noise, frame_mask, level, frames, need
     return frames, frame_elems
 
 
+NOISE_STREAM_XT, NOISE_STREAM_KNOWN, NOISE_STREAM_STEP = 0, 1, 2       # counter word `stream` of the counter-based noise (csrc/lfdm_philox.h)
+
+
+def check_seeds(seeds, batch, what="seeds"):
+    """The list of `batch` Python ints in [0, 2^64) that `seeds` holds; ValueError otherwise (before anything is launched)."""
+    try:
+        seeds = list(seeds)
+    except TypeError:
+        raise ValueError("%s: a sequence of %d integers in [0, 2^64) is needed, got %r" % (what, batch, seeds))
+    if len(seeds) != batch:
+        raise ValueError("%s: %d seeds for %d videos (one per video)" % (what, len(seeds), batch))
+    for v in seeds:
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < (1 << 64):
+            raise ValueError("%s: every seed must be an integer in [0, 2^64), got %r" % (what, v))
+    return seeds
+
+
+def seeds_tensor(seeds, device, out=None):
+    """Unsigned 64-bit seeds as the int64 device tensor the kernels read (two's complement: the same 64 bits).  out: refilled in place."""
+    t = torch.tensor([v - (1 << 64) if v >= (1 << 63) else v for v in check_seeds(seeds, len(seeds))], dtype=torch.int64)
+    if out is None:
+        return t.to(device)
+    return out.copy_(t)
+
+
+def _seed_operand(what, lib, seeds, batch, device):
+    if not torch.is_tensor(seeds):
+        seeds = seeds_tensor(check_seeds(seeds, batch, what), device)
+    if seeds.dtype != torch.int64 or tuple(seeds.shape) != (batch,) or not seeds.is_contiguous() or seeds.device != torch.device(device):
+        raise ValueError("%s: seeds must be %d Python ints or a contiguous int64 tensor of %d words on the operands' device" % (what, batch, batch))
+    if (lib.kind == "hip") != seeds.is_cuda:
+        raise RuntimeError("%s: seeds on the wrong device for the %s library" % (what, lib.kind))
+    return seeds
+
+
+def _philox_fill(name, out, seeds, stream, step, window):
+    lib = _lib()
+    if out.dim() < 1 or out.numel() == 0:
+        raise ValueError("%s: out must be (B, ...)" % name)
+    batch = out.shape[0]
+    n = out.numel() // batch
+    item = out[0]
+    if not item.is_contiguous() or (batch > 1 and out.stride(0) < n):
+        raise ValueError("%s: every row of out must be dense and rows must not overlap, got strides %s" % (name, tuple(out.stride())))
+    if (lib.kind == "hip") != out.is_cuda:
+        raise RuntimeError("%s: out on the wrong device for the %s library (no CPU fallback exists)" % (name, lib.kind))
+    if stream not in (NOISE_STREAM_XT, NOISE_STREAM_KNOWN, NOISE_STREAM_STEP):
+        raise ValueError("%s: stream must be 0 (x_T), 1 (known-frame noise) or 2 (step noise), got %r" % (name, stream))
+    if not (0 <= int(step) < 1 << 32 and 0 <= int(window) < 1 << 32):
+        raise ValueError("%s: step and window are 32-bit counter words" % name)
+    seeds = _seed_operand(name, lib, seeds, batch, out.device)
+    fn = lib.lfdm_philox_normal_f32 if name == "philox_normal" else lib.lfdm_philox_bits_u32
+    lib.check(fn(_p(out), _p(seeds), batch, n, out.stride(0) if batch > 1 else n, int(stream), int(step), int(window), _stream(lib)),
+              "lfdm_" + name)
+    return out
+
+
+def philox_normal(out, seeds, *, stream, step=0, window=0):
+    """lfdm_philox_normal_f32: fills the float32 tensor out (B, ...) - dense rows, any row stride - with the counter-based standard normals
+    of the videos `seeds` (B Python ints in [0, 2^64), or an int64 device tensor of the same bits): row b is a function of
+    (seeds[b], window, stream, step) alone."""
+    if out.dtype != torch.float32:
+        raise TypeError("philox_normal: out must be float32, got %s" % out.dtype)
+    return _philox_fill("philox_normal", out, seeds, stream, step, window)
+
+
+def philox_bits(out, seeds, *, stream, step=0, window=0):
+    """lfdm_philox_bits_u32: the raw Philox4x32-10 words behind philox_normal, as the bits of the int32 tensor out (B, ...): element i of a row
+    is output i & 3 of the counter (i >> 2, step, stream, window) under the key of the row's seed."""
+    if out.dtype != torch.int32:
+        raise TypeError("philox_bits: out must be int32 (the raw 32-bit words), got %s" % out.dtype)
+    return _philox_fill("philox_bits", out, seeds, stream, step, window)
+
+
 def sampler_step(x, eps, noise, coef, step_dev, *, quantile=0.9, advance=True, x0_out=None, ws=None,
-                 known=None, known_noise=None, frame_mask=None, level=None, frames=None):
+                 known=None, known_noise=None, frame_mask=None, level=None, frames=None, seeds=None, window=None):
     """lfdm_sampler_step_f32; with the five known-frame keywords (all or none) lfdm_sampler_step_known_f32: frames whose frame_mask[b, t] is set
-    are stored as level[step + 1] = (a, s) applied to (known, known_noise) instead of the update's result."""
+    are stored as level[step + 1] = (a, s) applied to (known, known_noise) instead of the update's result.
+    seeds (int64 device tensor (B), ops.seeds_tensor) + window (int32 device tensor of one word), both or none, with noise=None:
+    lfdm_sampler_step_counter_f32 / _known_f32 - the step noise is computed inside the update kernel from (seeds[b], window, step) and is
+    bit for bit what philox_normal(stream=2, step=the step counter's value, window=window) writes."""
     lib = _lib()
     _chk(lib, x, eps, noise, coef, step_dev, x0_out, ws)
     kf = _known_operands("sampler_step", x, known, known_noise, frame_mask, level, frames)
     batch = x.shape[0]
     n = x.numel() // batch
+    if (seeds is None) != (window is None):
+        raise ValueError("sampler_step: seeds and window go together (both or none)")
+    if seeds is not None and noise is not None:
+        raise ValueError("sampler_step: seeds (noise computed in the kernel) and a noise tensor exclude each other")
+    if seeds is not None:
+        seeds = _seed_operand("sampler_step", lib, seeds, batch, x.device)
+        if not torch.is_tensor(window) or window.dtype != torch.int32 or window.numel() != 1 or window.device != x.device:
+            raise ValueError("sampler_step: window must be an int32 tensor of one word on x's device")
     if ws is None:
         ws = sampler_ws(batch, n, x.device)
-    if kf is None:
+    if seeds is not None and kf is None:
+        lib.check(lib.lfdm_sampler_step_counter_f32(_p(x), _p(eps), _p(seeds), _p(window), _p(x0_out), batch, n, _p(coef),
+                                                    _p(step_dev), quantile, int(advance), _p(ws), ws.numel() * 4,
+                                                    _stream(lib)), "lfdm_sampler_step_counter_f32")
+    elif seeds is not None:
+        lib.check(lib.lfdm_sampler_step_counter_known_f32(_p(x), _p(eps), _p(seeds), _p(window), _p(x0_out), batch, n, _p(coef),
+                                                          _p(step_dev), quantile, int(advance), _p(ws), ws.numel() * 4,
+                                                          _p(known), _p(known_noise), _p(frame_mask), _p(level), kf[0], kf[1],
+                                                          _stream(lib)), "lfdm_sampler_step_counter_known_f32")
+    elif kf is None:
         lib.check(lib.lfdm_sampler_step_f32(_p(x), _p(eps), _p(noise), _p(x0_out), batch, n, _p(coef),
                                             _p(step_dev), quantile, int(advance), _p(ws), ws.numel() * 4,
                                             _stream(lib)), "lfdm_sampler_step_f32")

@@ -382,6 +382,36 @@ int lfdm_sampler_step_ms_known_f32(float* x, const float* eps, float* hist, floa
 /* the same select with host scalars, for x_T (once per video, outside the replayed step): x <- a * known + s * known_noise at marked frames */
 int lfdm_known_blend_f32(float* x, const float* known, const float* known_noise, const unsigned char* frame_mask, float a, float s,
                          int batch, int64_t n, int frames, int64_t frame_elems, lfdm_stream_t stream);
+/* Counter-based noise (additive, ABI version unchanged; DESIGN.md 4.10, csrc/lfdm_philox.h): every normal is a pure function of
+ * (video seed, window, stream, step, element).  Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85,
+ * ten rounds) with key = (seed & 0xffffffff, seed >> 32) and counter = (i >> 2, step, stream_id, window) gives four words r0..r3 for the quad
+ * of element i of one video's flat latent; u(r) = ((r >> 8) + 0.5) * 2^-24 in fp32 arithmetic;  R(r) = sqrt(-2 ln u(r));
+ *   z[4q] = R(r0) cos(2 pi u(r1)), z[4q+1] = R(r0) sin(2 pi u(r1)), z[4q+2] = R(r2) cos(2 pi u(r3)), z[4q+3] = R(r2) sin(2 pi u(r3)),  |z| <= 5.89.
+ * stream_id: 0 = x_T, 1 = known-frame noise, 2 = step noise.  step: the sampler step index (0 for the two per-video draws).  window: 0 for one
+ * video, the window number in a long video.  seeds: `batch` unsigned 64-bit words ON THE DEVICE.  0 < n < 2^24, row_stride >= n.
+ * lfdm_philox_normal_f32 writes z, lfdm_philox_bits_u32 the raw words (out[b * row_stride + i] = r_{i & 3} of quad i >> 2; for tests). */
+/* Layout: out is `batch` rows of n adjacent values, row b at out + b * row_stride (any row_stride >= n, any 4-byte aligned base: rows whose
+ * base is 16-byte aligned are stored in 16-byte words, other rows and the ragged last quad element by element); nothing outside the rows is
+ * written.  seeds dense. */
+int lfdm_philox_normal_f32(float* out, const uint64_t* seeds, int batch, int64_t n, int64_t row_stride, unsigned stream_id, unsigned step,
+                           unsigned window, lfdm_stream_t stream);
+/* Layout: as lfdm_philox_normal_f32. */
+int lfdm_philox_bits_u32(uint32_t* out, const uint64_t* seeds, int batch, int64_t n, int64_t row_stride, unsigned stream_id, unsigned step,
+                         unsigned window, lfdm_stream_t stream);
+/* lfdm_sampler_step_f32 / lfdm_sampler_step_known_f32 with the step noise COMPUTED inside the update kernel instead of read:
+ *   noise[b, i] = z of (seeds[b], counter (i >> 2, *step_dev, 2, *window)), element i & 3 of its quad
+ * - bit for bit the tensor lfdm_philox_normal_f32(stream_id 2, step = *step_dev, window = *window) writes, used in the same update expression.
+ * seeds (batch 64-bit words) and window (one 32-bit word) live on the device, so that one captured graph serves every seed.  Everything else
+ * (x0, threshold, x0_out, known frames, workspace, step counter, launch sequence) is the loading entry point's. */
+/* Layout: x, eps, x0_out, known, known_noise dense (B, n); seeds, window, coef, step_dev, frame_mask, level dense. */
+int lfdm_sampler_step_counter_f32(float* x, const float* eps, const uint64_t* seeds, const uint32_t* window, float* x0_out, int batch,
+                                  int64_t n, const float* coef, int32_t* step_dev, float quantile, int advance, void* ws, size_t ws_bytes,
+                                  lfdm_stream_t stream);
+/* Layout: as lfdm_sampler_step_counter_f32. */
+int lfdm_sampler_step_counter_known_f32(float* x, const float* eps, const uint64_t* seeds, const uint32_t* window, float* x0_out, int batch,
+                                        int64_t n, const float* coef, int32_t* step_dev, float quantile, int advance, void* ws,
+                                        size_t ws_bytes, const float* known, const float* known_noise, const unsigned char* frame_mask,
+                                        const float* level, int frames, int64_t frame_elems, lfdm_stream_t stream);
 /* classifier-free guidance combine of Unet3D.forward_with_cond_scale (:525-526):
  * out = null_eps + (cond_eps - null_eps) * scale   (out may alias an input) */
 /* Layout: dense, any; out may alias cond_eps or null_eps. */

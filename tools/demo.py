@@ -10,6 +10,7 @@ misc.flow2fig, not grid2fig's drawing) and --gif indexed writes its palette indi
     python tools/demo.py --synthetic --total-frames 112 --overlap 4 --out demo_out      # a long video: three chained 40-frame windows
     python tools/demo.py --synthetic --render device --gif indexed --out demo_out       # strip and palette indices made on the GPU
     python tools/demo.py --synthetic --fps-factor 4 --render device --gif indexed      # 157 frames decoded from the 40 sampled ones
+    python tools/demo.py --synthetic --noise counter --video-seeds 7,8,9 --batch 3   # three videos, each a function of its own seed
     python tools/demo.py --synthetic --out demo_out        # random-init weights, random image, fixed embedding:
                                                             # exercises the whole pipeline where no checkpoint exists
 """
@@ -63,6 +64,14 @@ def build_parser():
                     help="K output frames per sampled interval, decoded from the sampled latent at the times j / K (FlowDiffusion.decode_at, "
                          "DESIGN.md 4.9): (frames - 1) * K + 1 frames for the sampling cost of --frames; 1 (default): off")
     ap.add_argument("--interp", choices=("linear", "cubic"), default="linear", help="how the latent is interpolated between sampled frames")
+    ap.add_argument("--noise", choices=("torch", "counter"), default="torch",
+                    help="torch (default): sampling noise from torch's generator under --seed; counter: every video has a seed of its own and "
+                         "is the same video alone, in any batch and at any place in it (--video-seeds, DESIGN.md 4.10)")
+    ap.add_argument("--video-seeds", default="", help="--noise counter: comma-separated integers in [0, 2^64), one per video of --batch "
+                                                      "(default: --seed, --seed + 1, ...)")
+    ap.add_argument("--save-latents", action="store_true",
+                    help="--noise counter: also write every video's sampled latent to OUT/latent_<prompt index>_seed<seed>.npy")
+    ap.add_argument("--batch", type=int, default=1, help="videos sampled at once per text prompt (same image and prompt; they differ in their noise)")
     ap.add_argument("--reverse", action="store_true", help="play the sampled motion backwards")
     ap.add_argument("--pingpong", action="store_true", help="forward, then back: a GIF that loops seamlessly")
     return ap
@@ -83,6 +92,25 @@ def check_args(args):
         sys.exit("--gif indexed needs --render device: the palette indices are made by the device rendering")
     if args.use_ema and (args.synthetic or not args.dm_ckpt):
         sys.exit("--use-ema needs --dm-ckpt: a checkpoint with a 'diffusion_ema' entry")
+    if args.batch < 1:
+        sys.exit("--batch must be at least 1")
+    if (args.video_seeds or args.save_latents) and args.noise != "counter":
+        sys.exit("--video-seeds / --save-latents need --noise counter")
+
+
+def video_seeds(args):
+    """--noise counter: the list of --batch seeds (--video-seeds, or --seed, --seed + 1, ...); None under --noise torch."""
+    if args.noise != "counter":
+        return None
+    if not args.video_seeds:
+        return [(args.seed + j) % (1 << 64) for j in range(args.batch)]
+    try:
+        seeds = [int(v, 0) for v in args.video_seeds.split(",")]
+    except ValueError:
+        sys.exit("--video-seeds takes comma-separated integers, got %r" % args.video_seeds)
+    if len(seeds) != args.batch or not all(0 <= v < (1 << 64) for v in seeds):
+        sys.exit("--video-seeds: %d integers in [0, 2^64) are needed (--batch), got %r" % (args.batch, args.video_seeds))
+    return seeds
 
 
 def dm_state(ck, use_ema, path="the checkpoint"):
@@ -106,7 +134,8 @@ def make_model(args, *, steps=None, sampler=None, conv_precision=None, use_ema=N
     model = FlowDiffusion(is_train=False, img_size=args.size // 4, num_frames=args.frames, sampling_timesteps=steps,
                           null_cond_prob=0.1, config_pth=args.config, pretrained_pth=args.lfae_ckpt,
                           bert_path=None if args.synthetic else args.bert, conv_precision=conv_precision,
-                          sampler=sampler, long_attention=getattr(args, "long_attention", False))          # demo_mug.py:80-88
+                          sampler=sampler, long_attention=getattr(args, "long_attention", False),
+                          noise=getattr(args, "noise", "torch"))                                            # demo_mug.py:80-88
     if args.synthetic:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import synth
@@ -144,15 +173,28 @@ def main():
     else:
         img = np.random.default_rng(args.seed).integers(0, 256, size=(args.size, args.size, 3), dtype=np.uint8)
     ref = torch.from_numpy(np.asarray(img, np.float32) / 255.0).permute(2, 0, 1).unsqueeze(0).cuda()
+    seeds = video_seeds(args)
+    skw = {} if seeds is None else dict(seeds=seeds)
     name = os.path.splitext(os.path.basename(args.image))[0] if args.image else "random"
     for i, text in enumerate(args.text):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        model.set_sample_input(sample_img=ref, sample_text=[text])
+        ref_b = ref.expand(args.batch, -1, -1, -1).contiguous()
+        model.set_sample_input(sample_img=ref_b, sample_text=[text] * args.batch)
         if args.total_frames > 0:
-            model.sample_long_video(args.cond_scale, args.total_frames, overlap=args.overlap)
+            model.sample_long_video(args.cond_scale, args.total_frames, overlap=args.overlap, **({} if seeds is None else dict(seed=seeds)))
         else:
-            model.sample_one_video(cond_scale=args.cond_scale)
+            model.sample_one_video(cond_scale=args.cond_scale, **skw)
+        if seeds is not None:           # a video's identity: its seed, a checksum of its x_T (window 0) and of the latent it gave
+            from cvpr23_lfdm_amd import ops
+            x_t = ops.philox_normal(torch.empty((len(seeds), 3, args.frames, args.size // 4, args.size // 4), device="cuda"), seeds,
+                                    stream=ops.NOISE_STREAM_XT).cpu().numpy()
+            for j, sd in enumerate(seeds):
+                lat = model.sample_latent[j].float().cpu().numpy()
+                print("video seed %d: x_T crc32 %08x, latent crc32 %08x, mean |latent| %.6f"
+                      % (sd, zlib.crc32(x_t[j].tobytes()), zlib.crc32(lat.tobytes()), float(np.abs(lat).mean())))
+                if args.save_latents:
+                    np.save(os.path.join(args.out, "latent_%04d_seed%d.npy" % (i, sd)), lat)
         times = retime(args, args.total_frames if args.total_frames > 0 else args.frames)
         if times is not None:
             model.decode_at(times, args.interp)
@@ -160,7 +202,7 @@ def main():
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         if args.render == "device":
-            frames = C.video_strip_device(model, ref, indexed=args.gif == "indexed")
+            frames = C.video_strip_device(model, ref_b, indexed=args.gif == "indexed")
         else:
             frames = C.video_strip(model, ref)
         t2 = time.perf_counter()

@@ -36,6 +36,9 @@ from cvpr23_lfdm_amd import _native, datasets, evaluate as E, io_compat as C  # 
 
 DATASETS = {"mug": datasets.MUG_test, "mhad": datasets.MHAD_test, "natops": datasets.NATOPS_test}
 AB_KEYS = {"sampler": str, "steps": int, "conv_precision": str, "use_ema": lambda v: v.lower() in ("1", "true", "yes")}
+HELD_FIXED_COUNTER = ["source image", "text condition", "cond_scale",
+                      "the video's seed (--noise counter): the same x_T, the same known-frame noise, and the same step noise at every step index "
+                      "both configurations draw at"]
 HELD_FIXED = ["source image", "text condition", "cond_scale", "torch.manual_seed before each run: the same x_T (every sampler's first draw)",
               "per-step noise only where both configurations use the reference sampler with equal step counts"]
 
@@ -59,6 +62,8 @@ def build_parser():
         p.add_argument("--long-attention", action="store_true", help="windows of 65 ... 256 frames (and a mid block of up to 256 pixels per frame) on the streaming attention kernels (FlowDiffusion(long_attention=True), DESIGN.md 4.8)")
         p.add_argument("--cond-scale", type=float, default=1.0)
         p.add_argument("--seed", type=int, default=1234)
+        p.add_argument("--noise", choices=("torch", "counter"), default="torch",
+                       help="counter: sampled videos take their noise from per-video seeds (ab: both sides get --seed as the video's seed)")
         p.add_argument("--domain", choices=("raw", "unit", "uint8"), default="unit", help="value domain of L1 / PSNR / SSIM (out_loss / warp_loss are always raw)")
         p.add_argument("--out", default="", help="JSON file to write (default: eval_<command>.json)")
 
@@ -233,7 +238,9 @@ def run_ab(args):
     else:
         img = np.random.default_rng(args.seed).integers(0, 256, size=(args.size, args.size, 3), dtype=np.uint8)
     ref = torch.from_numpy(np.asarray(img, np.float32) / 255.0).permute(2, 0, 1).unsqueeze(0)
-    res = E.ab_compare(model_a, model_b, ref, [args.text], cond_scale=args.cond_scale, seed=args.seed, domain=args.domain)
+    counter = args.noise == "counter"
+    res = E.ab_compare(model_a, model_b, ref, [args.text], cond_scale=args.cond_scale, seed=args.seed, domain=args.domain,
+                       seeds=[args.seed % (1 << 64)] if counter else None)
     video, flow = res["video"]["table"][0].cpu(), res["flow"]["table"][0].cpu()
     psnr = res["video"]["psnr"][0].cpu().tolist()
     print("B against A per frame:  frame        l1       mse      psnr      ssim       epe  occl.err")
@@ -243,7 +250,7 @@ def run_ab(args):
     return {"a": cfg_a, "b": cfg_b, "video": res["video"]["summary"], "flow": res["flow"]["summary"],
             "per_frame": dict(l1=video[:, 0].tolist(), mse=video[:, 1].tolist(), psnr=psnr, ssim=video[:, 2].tolist(),
                               epe=flow[:, 0].tolist(), occlusion_error=flow[:, 1].tolist()),
-            "held_fixed": HELD_FIXED, "text": args.text, "cond_scale": args.cond_scale, "seed": args.seed, "domain": args.domain}
+            "held_fixed": HELD_FIXED_COUNTER if counter else HELD_FIXED, "text": args.text, "cond_scale": args.cond_scale, "seed": args.seed, "domain": args.domain}
 
 
 def main(argv=None):
