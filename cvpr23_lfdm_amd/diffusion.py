@@ -11,6 +11,7 @@ kernel.
 """
 import math
 import os
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn.functional as F
@@ -39,6 +40,87 @@ def shard_bounds(rank_shard, b_local):
         return rank_shard
     rank, world = rank_shard
     return rank * b_local, (rank + 1) * b_local, b_local * world
+
+
+class Schedule:
+    """One sampling schedule on one device (GaussianDiffusion._schedule): the timesteps, the (steps, 6) coefficient table and the int32
+    timestep table on the device, one draw flag per step, and - once a conditioned call has asked - the level table on host and device."""
+    __slots__ = ("times", "coef", "t_table", "draws", "level_host", "level")
+
+    def __init__(self, times, coef, t_table, draws):
+        self.times, self.coef, self.t_table, self.draws, self.level_host, self.level = times, coef, t_table, draws, None, None
+
+
+class Request(NamedTuple):
+    """A validated sampling call (GaussianDiffusion.check_request): seeds is the list of ints under noise="counter", else None."""
+    shape: tuple
+    known: Optional[torch.Tensor]
+    known_mask: Optional[torch.Tensor]
+    seeds: Optional[list]
+    window: int
+
+
+class SampleMode(NamedTuple):
+    """Everything a sampler step branches on, and so the key of its plan and captured graphs: `sampler_step` sees the plan and this and
+    nothing of the model.  conv_precision by name (both modes share one weight pack - `pack`, its id, does not tell them apart); quantile
+    -1.0 is the static clamp; known: the conditioned update kernel on the plan's known-frame operands."""
+    batch: int
+    frames: int
+    size: int
+    passes: int
+    cond_scale: float
+    ddim: bool
+    steps: int
+    pack: int
+    conv_precision: str
+    sampler: str
+    noise: str
+    quantile: float
+    known: bool
+
+
+def sampler_step(unet, plan, mode):
+    """One sampler step on the plan's operands: [per-step cond select] -> UNet -> fused x0 / quantile / update.  This is what is captured."""
+    pk, x, eps, step = plan["pk"], plan["x"], plan["eps"], plan["step"]
+    b, frames, s = mode.batch, mode.frames, mode.size
+    if mode.passes == 1:
+        ops.step_cond(plan["step_part"], plan["parts"][0], step, plan["ss"])
+        r = unet.stem(pk, x, plan["fea_term"], b, frames, s)
+        unet.run_trunk(pk, r, plan["ss"], b, frames, s, eps)
+    else:       # forward_with_cond_scale (:511-526): logits and null_logits in ONE 2B batch, rows of samples [cond | null]
+        x2, eps2, ss2 = plan["x2"], plan["eps2"], plan["ss2"]
+        for i, part in enumerate(plan["parts"]):
+            ops.step_cond(plan["step_part"], part, step, ss2[i * b:(i + 1) * b])
+            x2[i * b:(i + 1) * b].copy_(x)
+        r = unet.stem(pk, x2, plan["fea_term"], 2 * b, frames, s)
+        unet.run_trunk(pk, r, ss2, 2 * b, frames, s, eps2)
+        ops.cfg_combine(eps2[:b], eps2[b:], mode.cond_scale, eps)      # null + (cond - null) * scale
+    kw = dict(quantile=mode.quantile, ws=plan["ws"])
+    if mode.known:
+        kw.update(known=plan["known"], known_noise=plan["known_noise"], frame_mask=plan["kmask"], level=plan["level"], frames=frames)
+    if mode.sampler != "reference":
+        ops.sampler_step_ms(x, eps, plan["hist"], plan["coef"], step, **kw)
+    elif mode.noise == "counter":
+        ops.sampler_step(x, eps, None, plan["coef"], step, seeds=plan["seeds"], window=plan["window"], **kw)
+    else:
+        ops.sampler_step(x, eps, plan["noise"], plan["coef"], step, **kw)
+
+
+def capture_step(unet, plan, mode):
+    """The plan's single-step graph on the current scratch arenas; the chunk graphs of the old arenas go with the old one."""
+    x, step = plan["x"], plan["step"]
+    x_saved = x.clone()
+    plan["noise"].zero_()
+    sampler_step(unet, plan, mode)          # dry run: allocates every scratch buffer outside the capture, then state is restored
+    torch.cuda.synchronize()
+    x.copy_(x_saved)
+    step.zero_()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        sampler_step(unet, plan, mode)
+    x.copy_(x_saved)
+    step.zero_()
+    plan.update(graph=graph, chunk_graphs={}, buf_gen=unet._buf_gen)
 
 
 class GaussianDiffusion(nn.Module):
@@ -107,7 +189,8 @@ class GaussianDiffusion(nn.Module):
         self.text_encoder = None
         self.noise_source = None
         self.pred_x0 = None
-        self._plans = {}
+        self._plans = {}            # SampleMode -> plan: at most one plain and one known-frame plan
+        self._schedules = {}        # `_schedule_key` -> Schedule
         # (rank, world) under sharded data parallelism (FlowDiffusion.enable_data_parallel): the training step's random
         # draws are made for the GLOBAL batch on every rank (identical generators) and sliced
         self.rank_shard = None
@@ -197,25 +280,6 @@ class GaussianDiffusion(nn.Module):
                 draws.append(True)      # p_sample draws on every step, also at t == 0 (:743)
         return times, torch.stack(rows).float().contiguous(), draws
 
-    def _step_tables_on(self, ddim, dev):
-        """(times, coefficient table on `dev`, timestep table on `dev`, draws) of `_step_tables`, kept per schedule.  The tables are functions of
-        the registered buffers only, but building them reads every buffer back to the host - a device-to-host copy, i.e. a host synchronisation
-        at the start of EVERY video: the host could never run ahead of the GPU, and its own work between two videos (these 100 iterations of
-        scalar tensor arithmetic, the next video's launches) ran with the GPU idle - 2.3-3.8 ms of a 258 ms video in the kernel trace
-        (profiles/r06_af_video_gaps.txt).  Cached on (schedule, every buffer's version counter and address); an instance-level replacement of
-        `_step_tables` (the teacher-forced tests) is never cached."""
-        if "_step_tables" in self.__dict__:
-            times, coef, draws = self._step_tables(ddim)
-            return times, coef.to(dev), torch.tensor(times, dtype=torch.int32, device=dev), draws
-        key = (bool(ddim), self.sampling_timesteps, float(self.ddim_sampling_eta), self.num_timesteps, str(dev),
-               tuple((k, v._version, v.data_ptr()) for k, v in self.named_buffers(recurse=False)))
-        hit = self.__dict__.get("_tables_cache")
-        if hit is None or hit[0] != key:
-            times, coef, draws = self._step_tables(ddim)
-            hit = (key, times, coef.to(dev), torch.tensor(times, dtype=torch.int32, device=dev), draws)
-            self.__dict__["_tables_cache"] = hit
-        return hit[1], hit[2], hit[3], hit[4]
-
     def _ms_step_tables(self, sampler):
         """Timestep list and the (steps, 6) table {c_x, c_eps, k_x, k_m, k_prev, 0} of lfdm_sampler_step_ms_f32 for "dpmpp_2m" / "dpmpp_1":
             m_i = threshold(c_x x - c_eps eps);   x <- k_x x + k_m m_i + k_prev m_{i-1}
@@ -262,17 +326,6 @@ class GaussianDiffusion(nn.Module):
             times.append(time)
         return times, torch.tensor(rows, dtype=torch.float64).float().contiguous()
 
-    def _ms_step_tables_on(self, sampler, dev):
-        """`_ms_step_tables` on `dev` in the shape `_step_tables_on` returns (no step draws), kept per (sampler, schedule) like it."""
-        key = (sampler, self.sampling_timesteps, self.num_timesteps, str(dev),
-               tuple((k, v._version, v.data_ptr()) for k, v in self.named_buffers(recurse=False)))
-        hit = self.__dict__.get("_ms_tables_cache")
-        if hit is None or hit[0] != key:
-            times, coef = self._ms_step_tables(sampler)
-            hit = (key, times, coef.to(dev), torch.tensor(times, dtype=torch.int32, device=dev), [False] * len(times))
-            self.__dict__["_ms_tables_cache"] = hit
-        return hit[1], hit[2], hit[3], hit[4]
-
     def _level_table(self, ddim, sampler="reference"):
         """Known-frame conditioning: the (steps + 1, 2) fp32 host table of the level (a, s) the latent sits on - row 0: x_T's node,
         row i + 1: after step i - so that a known frame is stored as a * known + s * known_noise.  Reference DDIM: alphas_cumprod_prev[time_next]
@@ -293,47 +346,65 @@ class GaussianDiffusion(nn.Module):
             a = [b['alphas_cumprod'][self.num_timesteps - 1]] + [b['alphas_cumprod_prev'][t] for t in reversed(range(self.num_timesteps))]
         return torch.stack([torch.stack([v.sqrt(), (1 - v).sqrt()]) for v in a]).float().contiguous()
 
-    def _level_table_on(self, ddim, sampler, dev):
-        """(host table, table on `dev`) of `_level_table`, kept per (sampler, schedule) like `_step_tables_on`."""
-        key = (bool(ddim), sampler, self.sampling_timesteps, self.num_timesteps, str(dev),
-               tuple((k, v._version, v.data_ptr()) for k, v in self.named_buffers(recurse=False)))
-        hit = self.__dict__.get("_level_cache")
-        if hit is None or hit[0] != key:
-            host = self._level_table(ddim, sampler)
-            hit = (key, host, host.to(dev))
-            self.__dict__["_level_cache"] = hit
-        return hit[1], hit[2]
+    def _schedule_key(self, ddim, sampler, dev):
+        """Everything a schedule's tables are a function of; the buffers' stamps come last."""
+        return (bool(ddim), sampler, float(self.ddim_sampling_eta), self.sampling_timesteps, self.num_timesteps, str(dev),
+                tuple((k, v._version, v.data_ptr()) for k, v in self.named_buffers(recurse=False)))
 
-    def _check_known(self, shape, known, known_mask):
-        """Both or none; known (B, C, T, S, S) float32, known_mask (B, T) bool.  ValueError before anything is launched."""
-        if known is None and known_mask is None:
-            return False
-        if known is None or known_mask is None:
+    def _schedule(self, ddim, sampler, dev, level=False):
+        """The `Schedule` of (ddim, sampler) on `dev`: `_step_tables` / `_ms_step_tables` (whose grid checks raise from here) and, once a
+        conditioned call has asked with level=True, `_level_table`; kept per `_schedule_key`, a hit returns the same tensors.  The tables
+        are functions of the registered buffers only, but building them reads every buffer back to the host - a host synchronisation at the
+        start of EVERY video, 2.3-3.8 ms of a 258 ms video in the kernel trace (profiles/r06_af_video_gaps.txt).  A buffer written in
+        place or replaced makes new entries (the old ones are dropped); an instance-level replacement of `_step_tables` (the teacher-forced
+        tests) is never kept.  Nobody writes these tensors and no graph binds them: a plan copies them into operands of its own."""
+        multistep = sampler != "reference"
+        ddim = bool(ddim) or multistep
+        key = None if (not multistep and "_step_tables" in self.__dict__) else self._schedule_key(ddim, sampler, dev)
+        sch = self._schedules.get(key)
+        if sch is None:
+            if multistep:
+                times, coef = self._ms_step_tables(sampler)
+                draws = [False] * len(times)
+            else:
+                times, coef, draws = self._step_tables(ddim)
+            sch = Schedule(times, coef.to(dev), torch.tensor(times, dtype=torch.int32, device=dev), draws)
+            if key is not None:
+                self._schedules = {k: v for k, v in self._schedules.items() if k[-1] == key[-1]}
+                self._schedules[key] = sch
+        if level and sch.level is None:
+            sch.level_host = self._level_table(ddim, sampler)
+            sch.level = sch.level_host.to(dev)
+        return sch
+
+    def check_request(self, shape, known=None, known_mask=None, seeds=None, window=0):
+        """The validated `Request` of one sampling call; ValueError before anything is launched (and before the text encoder runs).  known
+        (B, C, T, S, S) float32 and known_mask (B, T) bool: both or none.  seeds: noise="counter" needs one Python int in [0, 2^64) per video
+        and no noise tape next to them; noise="torch" takes neither seeds nor a window.  The outermost entry (FlowDiffusion.sample_one_video
+        / sample_long_video; sample / p_sample_loop / ddim_sample called directly) checks once, everything below takes the Request on trust."""
+        shape = tuple(shape)
+        if (known is None) != (known_mask is None):
             raise ValueError("sample: known and known_mask go together (both or none)")
-        if not isinstance(known, torch.Tensor) or known.dtype != torch.float32 or tuple(known.shape) != tuple(shape):
-            raise ValueError("sample: known must be a float32 tensor of shape %s, got %s %s"
-                             % (tuple(shape), getattr(known, "dtype", type(known)), tuple(getattr(known, "shape", ()))))
-        if not isinstance(known_mask, torch.Tensor) or known_mask.dtype != torch.bool or tuple(known_mask.shape) != (shape[0], shape[2]):
-            raise ValueError("sample: known_mask must be a bool tensor of shape %s, got %s %s"
-                             % ((shape[0], shape[2]), getattr(known_mask, "dtype", type(known_mask)), tuple(getattr(known_mask, "shape", ()))))
-        return True
-
-    def _check_seeds(self, batch, seeds, window=0):
-        """noise="counter": the list of `batch` seeds (Python ints in [0, 2^64)); noise="torch": None.  ValueError before anything is launched
-        when the seeds do not fit the mode, their number is not the batch, one is out of range, or a noise tape is installed next to them."""
+        if known is not None:
+            if not isinstance(known, torch.Tensor) or known.dtype != torch.float32 or tuple(known.shape) != shape:
+                raise ValueError("sample: known must be a float32 tensor of shape %s, got %s %s"
+                                 % (shape, getattr(known, "dtype", type(known)), tuple(getattr(known, "shape", ()))))
+            if not isinstance(known_mask, torch.Tensor) or known_mask.dtype != torch.bool or tuple(known_mask.shape) != (shape[0], shape[2]):
+                raise ValueError("sample: known_mask must be a bool tensor of shape %s, got %s %s"
+                                 % ((shape[0], shape[2]), getattr(known_mask, "dtype", type(known_mask)), tuple(getattr(known_mask, "shape", ()))))
         if self.noise != "counter":
             if seeds is not None:
                 raise ValueError("sample: seeds need noise='counter' (this model draws from torch's generator: noise=%r)" % (self.noise,))
             if window != 0:
                 raise ValueError("sample: window needs noise='counter'")
-            return None
+            return Request(shape, known, known_mask, None, 0)
         if seeds is None:
             raise ValueError("sample: noise='counter' needs seeds (one integer in [0, 2^64) per video)")
         if self.noise_source is not None:
             raise ValueError("sample: a noise_source (tape) and noise='counter' exclude each other - replay counter_tape(...) under noise='torch'")
         if isinstance(window, bool) or not isinstance(window, int) or not 0 <= window < (1 << 32):
             raise ValueError("sample: window must be an integer in [0, 2^32), got %r" % (window,))
-        return ops.check_seeds(seeds, batch, "sample: seeds")
+        return Request(shape, known, known_mask, ops.check_seeds(seeds, shape[0], "sample: seeds"), window)
 
     def counter_tape(self, seeds, shape, ddim, window=0, known=False):
         """The counter-based draws of one `sample` call as a noise tape: a callable with the `noise_source` signature that returns, in the
@@ -343,7 +414,7 @@ class GaussianDiffusion(nn.Module):
         shape = tuple(shape)
         seeds = ops.check_seeds(seeds, shape[0], "counter_tape: seeds")
         dev = "cuda" if _native.library().kind == "hip" else "cpu"
-        draws = [] if self.sampler != "reference" else self._step_tables(ddim)[2]
+        draws = self._schedule(ddim, self.sampler, dev).draws
         plan = [(ops.NOISE_STREAM_XT, 0)] + ([(ops.NOISE_STREAM_KNOWN, 0)] if known else [])
         plan += [(ops.NOISE_STREAM_STEP, i) for i, d in enumerate(draws) if d]
         seeds_dev = ops.seeds_tensor(seeds, dev)
@@ -369,223 +440,153 @@ class GaussianDiffusion(nn.Module):
         set; values of `known` at other frames are never read into the result.
         seeds (keyword only; needed by, and only allowed under, noise="counter"): one Python int in [0, 2^64) per video - video b is then a
         function of seeds[b] (and of `window`, the window number of a long video) wherever it sits in the batch."""
-        device = next(self.denoise_fn.parameters()).device
-        if cond is not None and not is_list_str(cond):
-            batch = cond.shape[0]
-        elif cond is not None:
-            batch = len(cond)
-        else:
-            batch = batch_size
+        batch = batch_size if cond is None else len(cond)
         shape = (batch, self.channels, self.num_frames, self.image_size, self.image_size)
-        self._check_known(shape, known, known_mask)
-        self._check_seeds(batch, seeds, window)
+        return self.sample_checked(fea, cond, cond_scale, self.check_request(shape, known, known_mask, seeds, window))
+
+    @torch.no_grad()
+    def sample_checked(self, fea, cond, cond_scale, req):
+        """`sample` of a Request that `check_request` has returned (FlowDiffusion checks before the LFAE encoder runs)."""
+        if cond is not None and len(cond) != req.shape[0]:
+            raise ValueError("fea batch %d != cond batch %d" % (req.shape[0], len(cond)))
         if cond is not None:
-            cond = self._embed(cond, device)
-        kw = dict(known=known, known_mask=known_mask, seeds=seeds, window=window)
-        if self.sampler != "reference":
-            return self._sample(fea, shape, cond, cond_scale, True, sampler=self.sampler, **kw)
-        return self._sample(fea, shape, cond, cond_scale, self.is_ddim_sampling, **kw)
+            cond = self._embed(cond, next(self.denoise_fn.parameters()).device)
+        return self._sample(fea, cond, cond_scale, self.is_ddim_sampling or self.sampler != "reference", self.sampler, req)
 
     @torch.no_grad()
     def p_sample_loop(self, fea, shape, cond=None, cond_scale=1., *, known=None, known_mask=None, seeds=None, window=0):
-        return self._sample(fea, shape, cond, cond_scale, False, known=known, known_mask=known_mask, seeds=seeds, window=window)
+        return self._sample(fea, cond, cond_scale, False, "reference", self.check_request(shape, known, known_mask, seeds, window))
 
     @torch.no_grad()
     def ddim_sample(self, fea, shape, cond=None, cond_scale=1., clip_denoised=True, *, known=None, known_mask=None, seeds=None, window=0):
-        return self._sample(fea, shape, cond, cond_scale, True, known=known, known_mask=known_mask, seeds=seeds, window=window)
+        return self._sample(fea, cond, cond_scale, True, "reference", self.check_request(shape, known, known_mask, seeds, window))
 
-    def _sample(self, fea, shape, cond, cond_scale, ddim, sampler="reference", known=None, known_mask=None, seeds=None, window=0):
-        conditioned = self._check_known(shape, known, known_mask)
-        seeds = self._check_seeds(shape[0], seeds, window)
-        counter = seeds is not None
+    def _sample(self, fea, cond, cond_scale, ddim, sampler, req):
+        """One video batch: schedule -> this call's operand values -> the plan of its mode, refilled -> x_T -> the steps."""
         unet = self.denoise_fn
-        pk = unet.packed()
         dev = next(unet.parameters()).device
-        batch, ch, frames, s, _ = shape
+        batch, _, frames, s, _ = req.shape
         if getattr(unet, "long_attention", False):
             unet.check_geometry(frames, s)        # (frames / mid-block pixels the streaming kernels do not take: before the first launch)
-        n = ch * frames * s * s
-        multistep = sampler != "reference"
-        times, coef_dev, t_table, draws = self._ms_step_tables_on(sampler, dev) if multistep else self._step_tables_on(ddim, dev)
-        steps = len(times)
+        sch = self._schedule(ddim, sampler, dev, level=req.known is not None)
+        pk = unet.packed()
+        values = self._step_operands(unet, pk, sch, fea, cond, cond_scale, batch, s)
+        mode = SampleMode(batch, frames, s, len(values["parts"]), float(cond_scale), bool(ddim), len(sch.times), id(pk), unet.conv_precision,
+                          sampler, self.noise, float(self.dynamic_thres_percentile) if self.use_dynamic_thres else -1.0, req.known is not None)
+        plan = self._plans.get(mode) or self._new_plan(mode, pk, req.shape, values)
+        # the plan owns every operand a captured kernel binds: each call, eager or replayed, copies its values into them
+        plan["step_part"].copy_(values["step_part"])
+        for dst, src in zip(plan["parts"], values["parts"]):
+            dst.copy_(src)
+        for rows in plan["fea_term"].chunk(mode.passes):        # (two passes: rows of samples [cond | null])
+            rows.copy_(values["fea_term"])
+        plan["coef"].copy_(sch.coef)
+        if mode.known:
+            plan["level"].copy_(sch.level)
+        self._draw_start(plan, mode, req, sch.level_host)
+        return self._run_steps(unet, plan, mode, sch.draws)
 
-        # ---- per-call constants -------------------------------------------------------------
+    @staticmethod
+    def _step_operands(unet, pk, sch, fea, cond, cond_scale, batch, s):
+        """What this call feeds the step: the per-step part of the scale / shift rows, the per-sample part of each UNet pass, fea's term."""
+        dev = sch.coef.device
         fea = fea.to(dev).float().contiguous()
         if fea.shape[0] != batch:
             raise ValueError("fea batch %d != cond batch %d" % (fea.shape[0], batch))
         fea_cl = ops.planar_to_cl(fea.reshape(batch, fea.shape[1], s * s), batch, fea.shape[1], s * s)
         fea_term = unet.fea_term(pk, fea_cl, batch, s)
-        temb_steps = unet.time_embedding(pk, t_table, steps)
-        variants = []           # (per-sample cond part) for each UNet pass of a step
+        temb_steps = unet.time_embedding(pk, sch.t_table, len(sch.times))
+        parts = []
         if unet.has_cond:
             ones = torch.ones(batch, dtype=torch.bool, device=dev)
-            if cond_scale == 0:
-                masks = [ones]
-            elif cond_scale == 1:
-                masks = [~ones]
-            else:
-                masks = [~ones, ones]
+            masks = [ones] if cond_scale == 0 else [~ones] if cond_scale == 1 else [~ones, ones]
             for m in masks:
                 step_part, sample_part = unet.cond_tables(pk, temb_steps, unet.merge_cond(cond, m))
-                variants.append(sample_part)
+                parts.append(sample_part)
             unet.null_cond_mask = masks[-1]
         else:
             step_part = ops.linear_small(temb_steps, pk["cond.w"], pk["cond.b"], act_in=ops.ACT_SILU)
-            variants.append(torch.zeros(batch, pk["cond.n"], device=dev))
+            parts.append(torch.zeros(batch, pk["cond.n"], device=dev))
+        return {"step_part": step_part, "parts": parts, "fea_term": fea_term}
 
-        # ---- static step state ----------------------------------------------------------------
-        # (the convolution precision explicitly: both modes share one pack - id(pk) does not tell a graph captured in the other mode apart)
-        # (... and the sampler: a graph captured for one update rule must never be replayed for another)
-        # (... and the noise mode: the counter mode's update kernel is the generating instantiation)
-        key = (batch, frames, s, len(variants), float(cond_scale), bool(ddim), steps, id(pk), unet.conv_precision, sampler, self.noise)
-        if conditioned:
-            # known frames: a plan (and graph) of its own, whose update kernel is the conditioned instantiation; the unconditioned key is unchanged
-            key = key + ("known",)
-            level_host, level_dev = self._level_table_on(ddim, sampler, dev)
-        plan = self._plans.get(key)
-        if plan is None:
-            plan = {
-                "x": torch.empty(shape, device=dev), "eps": torch.empty(shape, device=dev),
-                # classifier-free guidance with cond_scale not in {0, 1}: cond and null passes run as ONE 2B batch
-                "x2": torch.empty((2 * batch,) + tuple(shape[1:]), device=dev) if len(variants) > 1 else None,
-                "eps2": torch.empty((2 * batch,) + tuple(shape[1:]), device=dev) if len(variants) > 1 else None,
-                "ss2": torch.empty(2 * batch, pk["cond.n"], device=dev) if len(variants) > 1 else None,
-                "noise": torch.empty(shape, device=dev), "step": torch.zeros(1, dtype=torch.int32, device=dev),
-                "ss": torch.empty(batch, pk["cond.n"], device=dev),
-                "ws": ops.sampler_ws(batch, n, dev), "graph": None, "pk": pk,
-                # m_{i-1} of the multistep samplers; never cleared: the first step of a video is first order and does not read it
-                "hist": torch.empty(shape, device=dev) if multistep else None,
-            }
-            if counter:
-                # static operands of the generating update kernel, refilled in place by every call: one captured graph serves every seed
-                plan.update({"seeds": torch.zeros(batch, dtype=torch.int64, device=dev), "window": torch.zeros(1, dtype=torch.int32, device=dev)})
-            if conditioned:
-                # static operands of the conditioned update kernel, filled in place by every call (another mask / other frames: no new capture)
-                plan.update({"known": torch.empty(shape, device=dev), "known_noise": torch.empty(shape, device=dev),
-                             "kmask": torch.zeros((batch, frames), dtype=torch.bool, device=dev),
-                             "level": torch.empty((steps + 1, 2), device=dev)})
-            # keep one plan (static buffers are large) - and the one of the other kind next to it: a long video alternates a plain first
-            # chunk with conditioned ones and must not capture again for each
-            self._plans = {k: v for k, v in self._plans.items() if (k[-1] == "known") != conditioned}
-            self._plans[key] = plan
-        if plan["graph"] is not None and plan.get("buf_gen") != unet._buf_gen:
-            # an eager call in between (Unet3D.forward, p_losses in eval mode, a larger batch) re-allocated scratch
-            # arenas whose raw pointers the captured graph holds: capture again on the current arenas
-            plan["graph"] = None
-        x, eps, noise, step_dev, ss = plan["x"], plan["eps"], plan["noise"], plan["step"], plan["ss"]
-        if len(variants) > 1:
-            fea_term = torch.cat((fea_term, fea_term), dim=0).contiguous()       # rows of samples [cond | null]
-        bind = {"step_part": step_part, "variants": variants, "coef": coef_dev, "fea_term": fea_term,
-                "scale": float(cond_scale)}
-        plan["bind"] = bind
+    def _new_plan(self, mode, pk, shape, values):
+        """The static state of one mode: x, eps, the kernels' operands and workspace, later its graphs.  One plan is kept (the buffers are
+        large) - and the one of the other kind next to it: a long video alternates a plain first window with conditioned ones and must not
+        capture again for each."""
+        dev, batch, steps = values["step_part"].device, mode.batch, mode.steps
+        new = lambda *size, **kw: torch.empty(size, device=dev, **kw)
+        plan = {"x": new(*shape), "eps": new(*shape), "noise": new(*shape), "step": torch.zeros(1, dtype=torch.int32, device=dev),
+                "ss": new(batch, pk["cond.n"]), "ws": ops.sampler_ws(batch, math.prod(shape[1:]), dev), "pk": pk,
+                "step_part": torch.empty_like(values["step_part"]), "parts": [torch.empty_like(v) for v in values["parts"]],
+                "fea_term": values["fea_term"].new_empty((mode.passes * values["fea_term"].shape[0],) + tuple(values["fea_term"].shape[1:])),
+                "coef": new(steps, 6), "graph": None, "chunk_graphs": {}, "buf_gen": None}
+        if mode.passes > 1:
+            plan.update(x2=new(2 * batch, *shape[1:]), eps2=new(2 * batch, *shape[1:]), ss2=new(2 * batch, pk["cond.n"]))
+        if mode.sampler != "reference":
+            plan["hist"] = new(*shape)       # m_{i-1}; never cleared: the first step of a video is first order and does not read it
+        if mode.noise == "counter":         # one captured graph serves every seed
+            plan.update(seeds=torch.zeros(batch, dtype=torch.int64, device=dev), window=torch.zeros(1, dtype=torch.int32, device=dev))
+        if mode.known:                      # another mask / other frames: no new capture
+            plan.update(known=new(*shape), known_noise=new(*shape), kmask=torch.zeros((batch, mode.frames), dtype=torch.bool, device=dev),
+                        level=new(steps + 1, 2))
+        self._plans = {k: v for k, v in self._plans.items() if k.known != mode.known}
+        self._plans[mode] = plan
+        return plan
 
-        def one_step():
-            b = plan["bind"]
-            if len(b["variants"]) == 1:
-                ops.step_cond(b["step_part"], b["variants"][0], step_dev, ss)
-                r = unet.stem(pk, x, b["fea_term"], batch, frames, s)
-                unet.run_trunk(pk, r, ss, batch, frames, s, eps)
-            else:       # forward_with_cond_scale (:511-526): logits and null_logits in one batched pass
-                x2, eps2, ss2 = plan["x2"], plan["eps2"], plan["ss2"]
-                for i, sample_part in enumerate(b["variants"]):
-                    ops.step_cond(b["step_part"], sample_part, step_dev, ss2[i * batch:(i + 1) * batch])
-                    x2[i * batch:(i + 1) * batch].copy_(x)
-                r = unet.stem(pk, x2, b["fea_term"], 2 * batch, frames, s)
-                unet.run_trunk(pk, r, ss2, 2 * batch, frames, s, eps2)
-                ops.cfg_combine(eps2[:batch], eps2[batch:], b["scale"], eps)      # null + (cond - null) * scale
-            quantile = self.dynamic_thres_percentile if self.use_dynamic_thres else -1.0
-            kf = {}
-            if conditioned:
-                kf = dict(known=plan["known"], known_noise=plan["known_noise"], frame_mask=plan["kmask"], level=plan["level"], frames=frames)
-            if multistep:
-                ops.sampler_step_ms(x, eps, plan["hist"], b["coef"], step_dev, quantile=quantile, ws=plan["ws"], **kf)
-            elif counter:
-                ops.sampler_step(x, eps, None, b["coef"], step_dev, quantile=quantile, ws=plan["ws"], seeds=plan["seeds"], window=plan["window"],
-                                 **kf)
-            else:
-                ops.sampler_step(x, eps, noise, b["coef"], step_dev, quantile=quantile, ws=plan["ws"], **kf)
-
-        use_graph = (_native.library().kind == "hip" and os.environ.get("LFDM_NO_GRAPH", "0") != "1")
+    def _draw_start(self, plan, mode, req, level_host):
+        """x_T into plan["x"] (:753 / :788); conditioned: one more draw directly behind it (every step draw keeps its place in the order),
+        then x_T's known frames on the init level.  The step counter starts at 0."""
+        x, counter = plan["x"], mode.noise == "counter"
         if counter:
-            ops.seeds_tensor(seeds, dev, out=plan["seeds"])
-            plan["window"].fill_(window)
-            ops.philox_normal(x, plan["seeds"], stream=ops.NOISE_STREAM_XT, window=window)
+            ops.seeds_tensor(req.seeds, x.device, out=plan["seeds"])
+            plan["window"].fill_(req.window)
+            ops.philox_normal(x, plan["seeds"], stream=ops.NOISE_STREAM_XT, window=req.window)
         else:
-            self._draw(x)                               # x_T  (:753 / :788)
-        if conditioned:
-            # one more draw directly behind x_T's (every step draw keeps its place in the order), then x_T's known frames on the init level
-            plan["known"].copy_(known)
-            plan["kmask"].copy_(known_mask)
-            plan["level"].copy_(level_dev)
+            self._draw(x)
+        if mode.known:
+            plan["known"].copy_(req.known)
+            plan["kmask"].copy_(req.known_mask)
             if counter:
-                ops.philox_normal(plan["known_noise"], plan["seeds"], stream=ops.NOISE_STREAM_KNOWN, window=window)
+                ops.philox_normal(plan["known_noise"], plan["seeds"], stream=ops.NOISE_STREAM_KNOWN, window=req.window)
             else:
                 self._draw(plan["known_noise"])
-            ops.known_blend(x, plan["known"], plan["known_noise"], plan["kmask"], float(level_host[0, 0]), float(level_host[0, 1]), frames)
-        step_dev.zero_()
-        if use_graph and plan["graph"] is None:
-            # the captured kernels bind the coefficient table by pointer and later calls copy theirs into it: a copy of the capture's own,
-            # never the tensor `_step_tables_on` keeps (an in-place write would change the kept table under its still valid key)
-            bind["coef"] = bind["coef"].clone()
-            # dry run allocates every scratch buffer outside the capture, then state is restored
-            x_saved = x.clone()
-            noise.zero_()
-            one_step()
-            torch.cuda.synchronize()
-            x.copy_(x_saved)
-            step_dev.zero_()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                one_step()
-            x.copy_(x_saved)
-            step_dev.zero_()
-            plan["graph"] = graph
-            plan["buf_gen"] = unet._buf_gen
-            plan["static_bind"] = bind
-        if use_graph:
-            # the captured kernels hold the pointers of the first call's tables: refresh them in place
-            sb = plan["static_bind"]
-            if sb is not bind:
-                sb["step_part"].copy_(bind["step_part"])
-                for dst, src in zip(sb["variants"], bind["variants"]):
-                    dst.copy_(src)
-                sb["coef"].copy_(bind["coef"])
-                if sb["fea_term"].data_ptr() != bind["fea_term"].data_ptr():
-                    sb["fea_term"].copy_(bind["fea_term"])
-                plan["bind"] = sb
+            ops.known_blend(x, plan["known"], plan["known_noise"], plan["kmask"], float(level_host[0, 0]), float(level_host[0, 1]), mode.frames)
+        plan["step"].zero_()
+
+    def _run_steps(self, unet, plan, mode, draws):
+        """Every step of the schedule on the plan, eagerly (emulator, LFDM_NO_GRAPH=1) or by graph replay; -> a copy of the final x.
+        The graphs hold raw pointers into the UNet's scratch arenas: when an eager call in between (Unet3D.forward, p_losses in eval mode,
+        a larger batch) has re-allocated one (`unet._buf_gen` moved), all of the plan's graphs are captured again."""
+        x, noise = plan["x"], plan["noise"]
+        use_graph = _native.library().kind == "hip" and os.environ.get("LFDM_NO_GRAPH", "0") != "1"
+        draws = [bool(d) and mode.noise != "counter" for d in draws]        # (counter mode: the update kernel computes the step noise)
+        if use_graph and (plan["graph"] is None or plan["buf_gen"] != unet._buf_gen):
+            capture_step(unet, plan, mode)
         # Several sampler steps per graph launch (LFDM_GRAPH_STEPS, default 10): between two replays the GPU sits through the graph
-        # launch and the host-launched noise kernel (~40 us per step of the 3 ms, measured as video time - 100 x the profiled step
-        # span).  The step's noise draw is captured with the step (torch's graph-safe philox state: the draws are the ones the
-        # eager loop makes, tests/test_end_to_end.py); a replayed noise tape (`noise_source`, the parity tests) cannot be captured
-        # and keeps one step per replay.
-        # (the multistep samplers draw nothing after x_T: a noise tape does not stand in their way)
-        # (counter mode: the step noise is computed inside the update kernel - nothing to capture or launch in front of a step, no draw flags:
-        #  one chunk graph per chunk length)
-        chunk = int(os.environ.get("LFDM_GRAPH_STEPS", "10")) if (use_graph and (self.noise_source is None or multistep or counter)) else 1
+        # launch and the host-launched noise kernel (~40 us per step of the 3 ms).  The step's noise draw is captured with the step
+        # (torch's graph-safe philox state: the draws are the ones the eager loop makes, tests/test_end_to_end.py); a replayed noise
+        # tape (`noise_source`, the parity tests) cannot be captured and keeps one step per replay - unless the mode draws nothing after x_T.
+        taped = self.noise_source is not None and mode.sampler == "reference" and mode.noise != "counter"
+        chunk = int(os.environ.get("LFDM_GRAPH_STEPS", "10")) if use_graph and not taped else 1
         if chunk <= 1:
-            for i in range(steps):
-                if draws[i] and not counter:
+            for draw in draws:
+                if draw:
                     self._draw(noise)
                 if use_graph:
                     plan["graph"].replay()
                 else:
-                    one_step()
+                    sampler_step(unet, plan, mode)
             return x.clone()
-        graphs = plan.setdefault("chunk_graphs", {})
-        if plan.get("chunk_buf_gen") != unet._buf_gen:        # an arena moved since these were captured
-            graphs.clear()
-            plan["chunk_buf_gen"] = unet._buf_gen
-        for i0 in range(0, steps, chunk):
-            flags = tuple(bool(d) and not counter for d in draws[i0:i0 + chunk])
-            g = graphs.get(flags)
+        for i0 in range(0, len(draws), chunk):
+            flags = tuple(draws[i0:i0 + chunk])       # one chunk graph per pattern of draws
+            g = plan["chunk_graphs"].get(flags)
             if g is None:
-                g = torch.cuda.CUDAGraph()
+                g = plan["chunk_graphs"][flags] = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
-                    for f in flags:
-                        if f:
-                            self._draw(noise)
-                        one_step()
-                graphs[flags] = g
+                    for draw in flags:
+                        if draw:
+                            noise.normal_()
+                        sampler_step(unet, plan, mode)
             g.replay()
         return x.clone()
 

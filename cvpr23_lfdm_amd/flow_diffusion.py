@@ -161,20 +161,12 @@ class FlowDiffusion(nn.Module):
         sampling, decode_at(frame_times, interp) - the four result tensors then hold len(frame_times) frames."""
         if frame_times is not None:
             frame_times = self._check_frame_times(frame_times, interp, self.diffusion.num_frames)
-        gen = self.generator
-        with torch.no_grad():
-            img = self.sample_img.float().contiguous()
-            dm = self.diffusion                                       # (bad known frames are refused before anything is launched)
-            dm._check_known((img.shape[0], dm.channels, dm.num_frames, dm.image_size, dm.image_size), known_latent, known_mask)
-            dm._check_seeds(img.shape[0], seeds)
-            skips = gen.encode(img)                                   # encoder ONCE per video
-            b, _, h, w = img.shape
-            d = 2 ** gen.num_down_blocks
-            fea = gen.compute_fea_from_skips(skips, b, h // d, w // d)
-            self.sample_img_fea = fea
-            pred = self.diffusion.sample(fea, cond=self.sample_text, batch_size=1, cond_scale=cond_scale, known=known_latent,
-                                         known_mask=known_mask, seeds=seeds)
-            self.sample_latent = pred
+        dm = self.diffusion
+        with torch.no_grad():                 # (bad known frames / seeds are refused before anything is launched)
+            req = dm.check_request((self.sample_img.shape[0], dm.channels, dm.num_frames, dm.image_size, dm.image_size), known_latent, known_mask,
+                                   seeds)
+            img, skips, fea = self._source()
+            self.sample_latent = pred = dm.sample_checked(fea, self.sample_text, cond_scale, req)
             self._decode_sample(img, skips, pred)
         if frame_times is not None:
             self.decode_at(frame_times, interp)
@@ -189,15 +181,33 @@ class FlowDiffusion(nn.Module):
             maps = pred
         return maps, (pred[:, 2, :, :, :].unsqueeze(dim=1) + 1) * 0.5
 
+    def _encode_source(self):
+        """(img, skips) of the source image: the LFAE encoder, ONCE per (long) video."""
+        img = self.sample_img.float().contiguous()
+        return img, self.generator.encode(img)
+
+    def _source(self):
+        """Source image -> (img, skips, fea): the encoding and the feature map the diffusion is conditioned on (kept in sample_img_fea)."""
+        img, skips = self._encode_source()
+        d = 2 ** self.generator.num_down_blocks
+        self.sample_img_fea = fea = self.generator.compute_fea_from_skips(skips, img.shape[0], img.shape[2] // d, img.shape[3] // d)
+        return img, skips, fea
+
+    def _decode_pieces(self, img, skips, pieces):
+        """Decodes a sequence of pieces (maps (B,3,n,S,S), conf (B,1,n,S,S), n <= num_frames) - of `_maps` or ops.latent_resample_maps - into
+        sample_vid_grid / sample_vid_conf / sample_out_vid / sample_warped_vid: one piece is stored as it is, several are concatenated along T."""
+        cols = {"sample_vid_grid": [], "sample_vid_conf": [], "sample_out_vid": [], "sample_warped_vid": []}
+        for maps, conf, n in pieces:
+            s = maps.shape[3]
+            out, warped = self.generator.decode_video(img, skips, maps[:, 0], maps[:, 1], maps[:, 2], n, s, s, 3 * n * s * s, s * s,
+                                                      occ_scale=0.5, occ_bias=0.5)
+            for col, v in zip(cols.values(), (maps[:, :2], conf, out, warped)):
+                col.append(v)
+        for name, col in cols.items():
+            setattr(self, name, col[0] if len(col) == 1 else torch.cat(col, dim=2))
+
     def _decode_sample(self, img, skips, pred):
-        maps, conf = self._maps(pred)
-        nf, s = pred.shape[2], pred.shape[3]
-        self.sample_vid_grid = maps[:, :2]
-        self.sample_vid_conf = conf
-        out, warped = self.generator.decode_video(img, skips, maps[:, 0], maps[:, 1], maps[:, 2], nf, s, s,
-                                                  3 * nf * s * s, s * s, occ_scale=0.5, occ_bias=0.5)
-        self.sample_out_vid = out
-        self.sample_warped_vid = warped
+        self._decode_pieces(img, skips, [self._maps(pred) + (pred.shape[2],)])
 
     def sample_long_video(self, cond_scale, total_frames, overlap=8, *, frame_times=None, interp="linear", seed=None):
         """A video of `total_frames` frames, longer than the model's window of num_frames, as a chain of windows: the LFAE
@@ -215,50 +225,29 @@ class FlowDiffusion(nn.Module):
             raise ValueError("sample_long_video: total_frames must be at least 1, got %d" % total_frames)
         if frame_times is not None:
             frame_times = self._check_frame_times(frame_times, interp, total_frames)
-        gen = self.generator
+        dm = self.diffusion
         with torch.no_grad():
-            img = self.sample_img.float().contiguous()
-            seeds = seed
+            b, seeds = self.sample_img.shape[0], seed
             if isinstance(seed, int) and not isinstance(seed, bool):
-                if img.shape[0] != 1:
-                    raise ValueError("sample_long_video: a batch of %d videos needs a sequence of %d seeds" % (img.shape[0], img.shape[0]))
+                if b != 1:
+                    raise ValueError("sample_long_video: a batch of %d videos needs a sequence of %d seeds" % (b, b))
                 seeds = [seed]
-            self.diffusion._check_seeds(img.shape[0], seeds)
-            skw = (lambda w: {}) if seeds is None else (lambda w: dict(seeds=seeds, window=w))
-            skips = gen.encode(img)                                   # encoder ONCE per long video
-            b, _, h, w = img.shape
-            d = 2 ** gen.num_down_blocks
-            fea = gen.compute_fea_from_skips(skips, b, h // d, w // d)
-            self.sample_img_fea = fea
-            chunk = self.diffusion.sample(fea, cond=self.sample_text, batch_size=1, cond_scale=cond_scale, **skw(0))
+            req = dm.check_request((b, dm.channels, nf, dm.image_size, dm.image_size), seeds=seeds)
+            img, skips, fea = self._source()
+            chunk = dm.sample_checked(fea, self.sample_text, cond_scale, req)
             pieces, have = [chunk], nf
             mask = torch.zeros((b, nf), dtype=torch.bool, device=chunk.device)
             mask[:, :overlap] = True
-            while have < total_frames:
+            while have < total_frames:                                # (window w of a seeded video draws with counter word `window` = w)
                 known = torch.zeros_like(chunk)
                 known[:, :, :overlap] = chunk[:, :, nf - overlap:]
-                chunk = self.diffusion.sample(fea, cond=self.sample_text, batch_size=1, cond_scale=cond_scale, known=known, known_mask=mask,
-                                              **skw(len(pieces)))
+                window = len(pieces) if req.seeds is not None else 0
+                chunk = dm.sample_checked(fea, self.sample_text, cond_scale, req._replace(known=known, known_mask=mask, window=window))
                 pieces.append(chunk[:, :, overlap:])
                 have += nf - overlap
-            latent = torch.cat(pieces, dim=2)[:, :, :total_frames].contiguous()
-            self.sample_latent = latent
-            s = latent.shape[3]
-            grids, confs, outs, warps = [], [], [], []
-            for f0 in range(0, total_frames, nf):                     # decode in pieces of at most num_frames frames
-                part = latent[:, :, f0:f0 + nf].contiguous()
-                maps, conf = self._maps(part)
-                n_part = part.shape[2]
-                out, warped = gen.decode_video(img, skips, maps[:, 0], maps[:, 1], maps[:, 2], n_part, s, s,
-                                               3 * n_part * s * s, s * s, occ_scale=0.5, occ_bias=0.5)
-                grids.append(maps[:, :2])
-                confs.append(conf)
-                outs.append(out)
-                warps.append(warped)
-            self.sample_vid_grid = torch.cat(grids, dim=2)
-            self.sample_vid_conf = torch.cat(confs, dim=2)
-            self.sample_out_vid = torch.cat(outs, dim=2)
-            self.sample_warped_vid = torch.cat(warps, dim=2)
+            self.sample_latent = latent = torch.cat(pieces, dim=2)[:, :, :total_frames].contiguous()
+            self._decode_pieces(img, skips, (self._maps(latent[:, :, f0:f0 + nf].contiguous()) + (min(nf, total_frames - f0),)
+                                             for f0 in range(0, total_frames, nf)))     # in pieces of at most num_frames frames
         if frame_times is not None:
             self.decode_at(frame_times, interp)
 
@@ -287,29 +276,14 @@ class FlowDiffusion(nn.Module):
         if latent is None or getattr(self, "sample_img", None) is None:
             raise RuntimeError("decode_at: nothing has been sampled yet - call sample_one_video or sample_long_video first")
         times = self._check_frame_times(times, mode, latent.shape[2])
-        gen, nf = self.generator, self.diffusion.num_frames
+        nf = self.diffusion.num_frames
         clamp_from = 2 if mode == "cubic" else None
         with torch.no_grad():
-            img = self.sample_img.float().contiguous()
+            img, skips = self._encode_source()
             latent = latent.to(img.device).float().contiguous()
-            skips = gen.encode(img)
-            s = latent.shape[3]
-            grids, confs, outs, warps = [], [], [], []
-            for f0 in range(0, len(times), nf):                       # decode in pieces of at most num_frames frames
-                part = times[f0:f0 + nf]
-                maps, conf = ops.latent_resample_maps(latent, part, mode, residual=self.use_residual_flow, clamp_from=clamp_from)
-                n_part = len(part)
-                out, warped = gen.decode_video(img, skips, maps[:, 0], maps[:, 1], maps[:, 2], n_part, s, s,
-                                               3 * n_part * s * s, s * s, occ_scale=0.5, occ_bias=0.5)
-                grids.append(maps[:, :2])
-                confs.append(conf)
-                outs.append(out)
-                warps.append(warped)
-            one = len(grids) == 1
-            self.sample_vid_grid = grids[0] if one else torch.cat(grids, dim=2)
-            self.sample_vid_conf = confs[0] if one else torch.cat(confs, dim=2)
-            self.sample_out_vid = outs[0] if one else torch.cat(outs, dim=2)
-            self.sample_warped_vid = warps[0] if one else torch.cat(warps, dim=2)
+            self._decode_pieces(img, skips, (ops.latent_resample_maps(latent, times[f0:f0 + nf], mode, residual=self.use_residual_flow,
+                                                                       clamp_from=clamp_from) + (len(times[f0:f0 + nf]),)
+                                             for f0 in range(0, len(times), nf)))       # in pieces of at most num_frames frames
 
     # ------------------------------------------------------------------ uint8 preview strips on the device
     def render_sample(self, mean=(0., 0., 0.), panels=("source", "out", "warped", "flow", "conf"), indexed=False, *, source=None):

@@ -1016,6 +1016,27 @@ def philox_bits(out, seeds, *, stream, step=0, window=0):
     return _philox_fill("philox_bits", out, seeds, stream, step, window)
 
 
+_SAMPLER_STEP = {      # (multistep, counter noise, known frames) -> C entry point
+    (False, False, False): "lfdm_sampler_step_f32", (False, False, True): "lfdm_sampler_step_known_f32",
+    (False, True, False): "lfdm_sampler_step_counter_f32", (False, True, True): "lfdm_sampler_step_counter_known_f32",
+    (True, False, False): "lfdm_sampler_step_ms_f32", (True, False, True): "lfdm_sampler_step_ms_known_f32"}
+
+
+def _sampler_step(lib, multistep, x, eps, third, coef, step_dev, quantile, advance, x0_out, ws, kf, known_operands, seeds=None, window=None):
+    """The one call behind sampler_step / sampler_step_ms (operands already checked): the common argument list, with (seeds, window) in
+    place of the third tensor (noise / hist) in counter mode and the known-frame tail when kf = (frames, frame_elems) is given."""
+    batch = x.shape[0]
+    if ws is None:
+        ws = sampler_ws(batch, x.numel() // batch, x.device)
+    name = _SAMPLER_STEP[(multistep, seeds is not None, kf is not None)]
+    args = [_p(x), _p(eps)] + ([_p(third)] if seeds is None else [_p(seeds), _p(window)])
+    args += [_p(x0_out), batch, x.numel() // batch, _p(coef), _p(step_dev), quantile, int(advance), _p(ws), ws.numel() * 4]
+    if kf is not None:
+        args += [_p(t) for t in known_operands] + [kf[0], kf[1]]
+    lib.check(getattr(lib, name)(*args, _stream(lib)), name)
+    return x
+
+
 def sampler_step(x, eps, noise, coef, step_dev, *, quantile=0.9, advance=True, x0_out=None, ws=None,
                  known=None, known_noise=None, frame_mask=None, level=None, frames=None, seeds=None, window=None):
     """lfdm_sampler_step_f32; with the five known-frame keywords (all or none) lfdm_sampler_step_known_f32: frames whose frame_mask[b, t] is set
@@ -1027,7 +1048,6 @@ def sampler_step(x, eps, noise, coef, step_dev, *, quantile=0.9, advance=True, x
     _chk(lib, x, eps, noise, coef, step_dev, x0_out, ws)
     kf = _known_operands("sampler_step", x, known, known_noise, frame_mask, level, frames)
     batch = x.shape[0]
-    n = x.numel() // batch
     if (seeds is None) != (window is None):
         raise ValueError("sampler_step: seeds and window go together (both or none)")
     if seeds is not None and noise is not None:
@@ -1036,27 +1056,7 @@ def sampler_step(x, eps, noise, coef, step_dev, *, quantile=0.9, advance=True, x
         seeds = _seed_operand("sampler_step", lib, seeds, batch, x.device)
         if not torch.is_tensor(window) or window.dtype != torch.int32 or window.numel() != 1 or window.device != x.device:
             raise ValueError("sampler_step: window must be an int32 tensor of one word on x's device")
-    if ws is None:
-        ws = sampler_ws(batch, n, x.device)
-    if seeds is not None and kf is None:
-        lib.check(lib.lfdm_sampler_step_counter_f32(_p(x), _p(eps), _p(seeds), _p(window), _p(x0_out), batch, n, _p(coef),
-                                                    _p(step_dev), quantile, int(advance), _p(ws), ws.numel() * 4,
-                                                    _stream(lib)), "lfdm_sampler_step_counter_f32")
-    elif seeds is not None:
-        lib.check(lib.lfdm_sampler_step_counter_known_f32(_p(x), _p(eps), _p(seeds), _p(window), _p(x0_out), batch, n, _p(coef),
-                                                          _p(step_dev), quantile, int(advance), _p(ws), ws.numel() * 4,
-                                                          _p(known), _p(known_noise), _p(frame_mask), _p(level), kf[0], kf[1],
-                                                          _stream(lib)), "lfdm_sampler_step_counter_known_f32")
-    elif kf is None:
-        lib.check(lib.lfdm_sampler_step_f32(_p(x), _p(eps), _p(noise), _p(x0_out), batch, n, _p(coef),
-                                            _p(step_dev), quantile, int(advance), _p(ws), ws.numel() * 4,
-                                            _stream(lib)), "lfdm_sampler_step_f32")
-    else:
-        lib.check(lib.lfdm_sampler_step_known_f32(_p(x), _p(eps), _p(noise), _p(x0_out), batch, n, _p(coef),
-                                                  _p(step_dev), quantile, int(advance), _p(ws), ws.numel() * 4,
-                                                  _p(known), _p(known_noise), _p(frame_mask), _p(level), kf[0], kf[1],
-                                                  _stream(lib)), "lfdm_sampler_step_known_f32")
-    return x
+    return _sampler_step(lib, False, x, eps, noise, coef, step_dev, quantile, advance, x0_out, ws, kf, (known, known_noise, frame_mask, level), seeds, window)
 
 
 def sampler_step_ms(x, eps, hist, coef, step_dev, *, quantile=0.9, advance=True, x0_out=None, ws=None,
@@ -1068,21 +1068,9 @@ def sampler_step_ms(x, eps, hist, coef, step_dev, *, quantile=0.9, advance=True,
     _chk(lib, x, eps, hist, coef, step_dev, x0_out, ws)
     kf = _known_operands("sampler_step_ms", x, known, known_noise, frame_mask, level, frames)
     batch = x.shape[0]
-    n = x.numel() // batch
     if hist.numel() != x.numel():
         raise ValueError("sampler_step_ms: hist must have x's %d elements, got %d" % (x.numel(), hist.numel()))
-    if ws is None:
-        ws = sampler_ws(batch, n, x.device)
-    if kf is None:
-        lib.check(lib.lfdm_sampler_step_ms_f32(_p(x), _p(eps), _p(hist), _p(x0_out), batch, n, _p(coef),
-                                               _p(step_dev), quantile, int(advance), _p(ws), ws.numel() * 4,
-                                               _stream(lib)), "lfdm_sampler_step_ms_f32")
-    else:
-        lib.check(lib.lfdm_sampler_step_ms_known_f32(_p(x), _p(eps), _p(hist), _p(x0_out), batch, n, _p(coef),
-                                                     _p(step_dev), quantile, int(advance), _p(ws), ws.numel() * 4,
-                                                     _p(known), _p(known_noise), _p(frame_mask), _p(level), kf[0], kf[1],
-                                                     _stream(lib)), "lfdm_sampler_step_ms_known_f32")
-    return x
+    return _sampler_step(lib, True, x, eps, hist, coef, step_dev, quantile, advance, x0_out, ws, kf, (known, known_noise, frame_mask, level))
 
 
 def known_blend(x, known, known_noise, frame_mask, a, s, frames):

@@ -62,24 +62,28 @@ def test_sampler_tables_match_oracle():
 
 
 def test_sampler_tables_are_kept_per_schedule_and_follow_the_buffers():
-    """`_step_tables_on` (the tables of `_step_tables` on the sampling device, kept between videos so that no per-video host read-back synchronises with
+    """`_schedule` (the tables of `_step_tables` on the sampling device, kept between videos so that no per-video host read-back synchronises with
     the GPU): the same objects for the same schedule, rebuilt when a registered buffer is written (load_state_dict, an edited schedule), when the
     schedule changes, and never cached for an instance-level replacement of `_step_tables` (the teacher-forced tests)."""
     from cvpr23_lfdm_amd import GaussianDiffusion
     d = GaussianDiffusion(torch.nn.Identity(), image_size=8, num_frames=4, timesteps=50, sampling_timesteps=10, loss_type="l2")
-    t1, c1, tt1, dr1 = d._step_tables_on(True, torch.device("cpu"))
-    t2, c2, tt2, dr2 = d._step_tables_on(True, torch.device("cpu"))
+    tables = lambda ddim: (lambda s: (s.times, s.coef, s.t_table, s.draws))(d._schedule(ddim, "reference", torch.device("cpu")))
+    t1, c1, tt1, dr1 = tables(True)
+    t2, c2, tt2, dr2 = tables(True)
     assert c1 is c2 and tt1 is tt2 and t1 == t2 and tt1.tolist() == t1
     ref_t, ref_c, _ = d._step_tables(True)
     assert torch.equal(c1, ref_c) and t1 == ref_t
     d.sqrt_recip_alphas_cumprod.mul_(2.0)                    # an in-place write bumps the buffer's version counter
-    t3, c3, _, _ = d._step_tables_on(True, torch.device("cpu"))
+    t3, c3, _, _ = tables(True)
     assert c3 is not c1 and torch.equal(c3, d._step_tables(True)[1]) and not torch.equal(c3, c1)
-    t4, c4, _, _ = d._step_tables_on(False, torch.device("cpu"))
+    t4, c4, _, _ = tables(False)
     assert len(t4) == 50 and c4 is not c3
+    kept = dict(d._schedules)
     d._step_tables = lambda ddim: ([7], torch.zeros(1, 6), [True])
-    t5, c5, tt5, _ = d._step_tables_on(True, torch.device("cpu"))
-    assert t5 == [7] and tt5.tolist() == [7] and "_tables_cache" in d.__dict__ and d.__dict__["_tables_cache"][1] != [7]
+    t5, c5, tt5, _ = tables(True)
+    assert t5 == [7] and tt5.tolist() == [7] and d._schedules == kept and len(kept) == 2 and all(s.times != [7] for s in kept.values())
+    del d._step_tables
+    assert tables(True)[1] is c3 and tables(False)[1] is c4
 
 
 def test_state_dict_layout_and_roundtrip():

@@ -85,16 +85,16 @@ def test_level_table_ddpm():
 
 def test_level_tables_are_kept_per_sampler_and_schedule():
     d = diffusion("dpmpp_2m", 10, 50)
-    cpu = torch.device("cpu")
-    h1, d1 = d._level_table_on(True, "dpmpp_2m", cpu)
-    h2, d2 = d._level_table_on(True, "dpmpp_2m", cpu)
+    levels = lambda sampler: (lambda s: (s.level_host, s.level))(d._schedule(True, sampler, torch.device("cpu"), level=True))
+    h1, d1 = levels("dpmpp_2m")
+    h2, d2 = levels("dpmpp_2m")
     assert h1 is h2 and d1 is d2 and torch.equal(h1, d1)
-    h3, _ = d._level_table_on(True, "reference", cpu)
+    h3, _ = levels("reference")
     assert h3 is not h1 and not torch.equal(h3, h1)
-    h4, _ = d._level_table_on(True, "dpmpp_2m", cpu)
+    h4, _ = levels("dpmpp_2m")
     assert torch.equal(h4, h1)
     d.alphas_cumprod.mul_(0.5)                                      # an in-place write bumps the buffer's version counter
-    h5, _ = d._level_table_on(True, "dpmpp_2m", cpu)
+    h5, _ = levels("dpmpp_2m")
     assert not torch.equal(h5, h1)
 
 
@@ -538,7 +538,7 @@ def test_other_mask_and_frames_need_no_new_plan(sampler, extra):
     m = _model(sampler, **extra)
     cases = [(5, (0, 1)), (6, (0, 3)), (5, (2,))]
     got = [_video(m, seed, *_known(seed, fr)) for seed, fr in cases]
-    plans = [p for key, p in m.diffusion._plans.items() if key[-1] == "known"]
+    plans = [p for key, p in m.diffusion._plans.items() if key.known]
     assert len(plans) == 1
     for (seed, fr), g in zip(cases, got):
         k, mask = _known(seed, fr)
@@ -576,6 +576,29 @@ def test_all_false_mask_is_the_unconditioned_video():
     k, mask = _known(5, ())
     assert not mask.any() and torch.isnan(k).all()
     assert torch.equal(_video(m, 5, k, mask), _video(_model("dpmpp_2m"), 5))
+
+
+@pytest.mark.gpu
+def test_threshold_mode_is_part_of_the_plan():
+    """use_dynamic_thres goes into the update kernel's arguments at capture time: changing it between two videos of one model must not
+    replay a graph captured under the other mode.  T = 4, S = 8, 5 DDIM steps on tape 5, where the CPU oracle's 0.9 quantile of |x0| is
+    6.92, 2.82, 1.79, 1.28, 1.01 over the steps (above 1 on every one: the two modes clamp differently, max difference 0.91 in the latent)."""
+    _gpu()
+    kw = dict(sampling_timesteps=5)
+    m = _model("reference", **kw)
+    assert m.diffusion.use_dynamic_thres and m.diffusion.dynamic_thres_percentile == 0.9
+    first = _video(m, 5)
+    m.diffusion.use_dynamic_thres = False
+    second = _video(m, 5)
+    plans = m.diffusion._plans
+    assert 1 <= len(plans) <= 2 and {key.quantile for key in plans} in ({-1.0}, {-1.0, 0.9})      # two plans or one replaced, never a stale graph
+    m.diffusion.use_dynamic_thres = True
+    third = _video(m, 5)
+    static = _model("reference", **kw)
+    static.diffusion.use_dynamic_thres = False
+    assert torch.equal(second, _video(static, 5))
+    assert torch.equal(first, third)
+    assert not torch.equal(second, first) and torch.isfinite(second).all()
 
 
 @pytest.mark.gpu

@@ -101,7 +101,7 @@ def test_tables_refuse_repeated_nodes_and_bad_names():
     with pytest.raises(ValueError, match="strictly decreasing"):
         d._ms_step_tables("dpmpp_2m")
     with pytest.raises(ValueError, match="strictly decreasing"):
-        d._ms_step_tables_on("dpmpp_1", torch.device("cpu"))
+        d._schedule(True, "dpmpp_1", torch.device("cpu"))
     diffusion("dpmpp_2m", 999, 1000)._ms_step_tables("dpmpp_2m")     # every timestep once: fine
     with pytest.raises(ValueError, match="sampler"):
         GaussianDiffusion(torch.nn.Identity(), image_size=8, num_frames=4, sampler="dpm")
@@ -118,14 +118,14 @@ def test_tables_refuse_repeated_nodes_and_bad_names():
 
 def test_tables_are_kept_per_sampler_and_schedule():
     d = diffusion("dpmpp_2m", 10, 50)
-    cpu = torch.device("cpu")
-    t1, c1, tt1, dr1 = d._ms_step_tables_on("dpmpp_2m", cpu)
-    t2, c2, tt2, _ = d._ms_step_tables_on("dpmpp_2m", cpu)
+    tables = lambda sampler: (lambda s: (s.times, s.coef, s.t_table, s.draws))(d._schedule(True, sampler, torch.device("cpu")))
+    t1, c1, tt1, dr1 = tables("dpmpp_2m")
+    t2, c2, tt2, _ = tables("dpmpp_2m")
     assert c1 is c2 and tt1 is tt2 and tt1.tolist() == t1 and dr1 == [False] * 10
-    _, c3, _, _ = d._ms_step_tables_on("dpmpp_1", cpu)
+    _, c3, _, _ = tables("dpmpp_1")
     assert c3 is not c1 and not torch.equal(c3, c1)
     d.alphas_cumprod.mul_(0.5)                                      # an in-place write bumps the buffer's version counter
-    _, c4, _, _ = d._ms_step_tables_on("dpmpp_1", cpu)
+    _, c4, _, _ = tables("dpmpp_1")
     assert not torch.equal(c4, c3)
     # the reference tables are what they were
     ref = diffusion("reference", 10, 50)
