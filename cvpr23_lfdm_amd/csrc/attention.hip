@@ -11,15 +11,10 @@
 //    tokens + context = k v^T (two-pass column reduction), then q-softmax over the 32-dim axis
 //    and out = context^T q.
 #include <stdlib.h>
-#include "lfdm_device.h"
+#include "attn_core.h"
 #include "../../include/lfdm_hip.h"
 
 namespace {
-
-constexpr int HEADS = 8;
-constexpr int DH = 32;
-constexpr int QKV_LD = 3 * HEADS * DH;  // 768
-constexpr int OUT_LD = HEADS * DH;      // 256
 
 // One wavefront (= one 64-thread workgroup) per (sequence, head).  Nothing but P goes through LDS:
 //  * the sum over the 32 head features is order independent, so MFMA k-slot `lq` of step s is given feature
@@ -29,10 +24,10 @@ constexpr int OUT_LD = HEADS * DH;      // 256
 //  * V is consumed as the B operand of P*V in its natural row layout (lane = feature, k-slot = tokens 16*t + 4*lq + r):
 //    scalar loads, each element read exactly once;
 //  * the scores are computed transposed (S^T = K Q^T), which makes the softmax a register reduction + two shuffles and
-//    leaves P^T directly in the A-operand layout of P V: NO LDS and no barrier anywhere in the kernel.
+//    leaves P^T directly in the A-operand layout of P V: NO LDS and no barrier anywhere in the kernel (attn_core.h attend_store).
 // The first version staged Q, K, V and P in LDS (20 KB per wave, 8 waves per CU, 60 % of the wave cycles in s_waitcnt).
 template <int LP>
-__global__ __launch_bounds__(64) void attention_kernel(const float* __restrict__ qkv, float* __restrict__ out, int batch,
+__global__ __launch_bounds__(64) void attention_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                        int frames, int hw, int mode, const float* __restrict__ bias,
                                                        const float* __restrict__ rot_cos,
                                                        const float* __restrict__ rot_sin) {
@@ -44,6 +39,8 @@ __global__ __launch_bounds__(64) void attention_kernel(const float* __restrict__
   const int64_t unit = blockIdx.x;
   const int64_t seq = unit / HEADS;
   const int head = (int)(unit - seq * HEADS);
+  // seq_rows (attn_core.h), open-coded: through the helper hipcc (ROCm 7.2) associates b * frames * hw the other way round and
+  // attention_kernel<32> ends at 82 instead of 80 registers - five waves per SIMD instead of six
   int64_t row0, tstride;
   if (mode == 0) {
     const int64_t b = seq / hw, pix = seq - b * hw;
@@ -53,7 +50,6 @@ __global__ __launch_bounds__(64) void attention_kernel(const float* __restrict__
     row0 = seq * hw;
     tstride = 1;
   }
-  const float scale = 0.17677669529663687f;  // 32^-0.5
   const float* base = qkv + head * DH;
 
   // ---- Q / K fragments: token tile*16 + l15, features 8*lq .. 8*lq+7 ----
@@ -69,8 +65,8 @@ __global__ __launch_bounds__(64) void attention_kernel(const float* __restrict__
       k0 = *reinterpret_cast<const float4*>(src + OUT_LD);
       k1 = *reinterpret_cast<const float4*>(src + OUT_LD + 4);
     }
-    qf[ti][0] = q0.x * scale; qf[ti][1] = q0.y * scale; qf[ti][2] = q0.z * scale; qf[ti][3] = q0.w * scale;
-    qf[ti][4] = q1.x * scale; qf[ti][5] = q1.y * scale; qf[ti][6] = q1.z * scale; qf[ti][7] = q1.w * scale;
+    qf[ti][0] = q0.x * ATT_SCALE; qf[ti][1] = q0.y * ATT_SCALE; qf[ti][2] = q0.z * ATT_SCALE; qf[ti][3] = q0.w * ATT_SCALE;
+    qf[ti][4] = q1.x * ATT_SCALE; qf[ti][5] = q1.y * ATT_SCALE; qf[ti][6] = q1.z * ATT_SCALE; qf[ti][7] = q1.w * ATT_SCALE;
     kf[ti][0] = k0.x; kf[ti][1] = k0.y; kf[ti][2] = k0.z; kf[ti][3] = k0.w;
     kf[ti][4] = k1.x; kf[ti][5] = k1.y; kf[ti][6] = k1.z; kf[ti][7] = k1.w;
   }
@@ -97,101 +93,14 @@ __global__ __launch_bounds__(64) void attention_kernel(const float* __restrict__
 #pragma unroll
         for (int pr = 0; pr < 4; ++pr) {
           const float c = rot_cos[t * 16 + 4 * lq + pr], sn = rot_sin[t * 16 + 4 * lq + pr];
-          const float qx = qf[ti][2 * pr], qy = qf[ti][2 * pr + 1];
-          const float kx = kf[ti][2 * pr], ky = kf[ti][2 * pr + 1];
-          qf[ti][2 * pr] = qx * c - qy * sn;
-          qf[ti][2 * pr + 1] = qy * c + qx * sn;
-          kf[ti][2 * pr] = kx * c - ky * sn;
-          kf[ti][2 * pr + 1] = ky * c + kx * sn;
+          rot_pair(qf[ti][2 * pr], qf[ti][2 * pr + 1], c, sn);
+          rot_pair(kf[ti][2 * pr], kf[ti][2 * pr + 1], c, sn);
         }
       }
     }
   }
-
-  // ---- S^T = K Q^T: lane = query token 16*ti + l15, registers = key tokens 16*tj + 4*lq + r.  The softmax over the keys
-  // of a query is then a reduction over the lane's registers plus two shuffles (the four k-slots), and the result is
-  // already the A operand of P V in the token order above: the scores never touch LDS. ----
-  f32x4 st[NT][NT];
-#pragma unroll
-  for (int ti = 0; ti < NT; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < NT; ++tj) {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < 8; ++s) acc = mfma_16x16x4(kf[tj][s], qf[ti][s], acc);
-      st[ti][tj] = acc;
-    }
   const bool bias_vec = bias && (L % 4 == 0) && ((((uintptr_t)bias) & 15) == 0);
-#pragma unroll
-  for (int ti = 0; ti < NT; ++ti) {
-    const int qt = ti * 16 + l15;
-    float m = -3.0e38f;
-#pragma unroll
-    for (int tj = 0; tj < NT; ++tj) {
-      float bv[4] = {0.f, 0.f, 0.f, 0.f};
-      const int key0 = tj * 16 + lq * 4;
-      if (bias && qt < L && key0 < L) {
-        const float* bp = bias + ((int64_t)head * L + qt) * L + key0;
-        if (bias_vec) {
-          const float4 b4 = *reinterpret_cast<const float4*>(bp);
-          bv[0] = b4.x; bv[1] = b4.y; bv[2] = b4.z; bv[3] = b4.w;
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) bv[r] = (key0 + r < L) ? bp[r] : 0.f;
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float v = st[ti][tj][r];
-        if (key0 + r >= L) v = -3.0e38f;
-        else v += bv[r];
-        st[ti][tj][r] = v;
-        m = fmaxf(m, v);
-      }
-    }
-    m = fmaxf(m, __shfl_xor(m, 16));
-    m = fmaxf(m, __shfl_xor(m, 32));
-    float sum = 0.f;
-#pragma unroll
-    for (int tj = 0; tj < NT; ++tj)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float e = (tj * 16 + lq * 4 + r) < L ? fast_exp(st[ti][tj][r] - m) : 0.f;
-        st[ti][tj][r] = e;
-        sum += e;
-      }
-    sum += __shfl_xor(sum, 16);
-    sum += __shfl_xor(sum, 32);
-    const float inv = fast_rcp(sum);               // one reciprocal per query (lfdm_device.h fast_exp / fast_rcp)
-#pragma unroll
-    for (int tj = 0; tj < NT; ++tj)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) st[ti][tj][r] = st[ti][tj][r] * inv;
-  }
-
-  // ---- O = P V ----
-#pragma unroll
-  for (int ti = 0; ti < NT; ++ti) {
-    f32x4 o[2];
-    o[0] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    o[1] = o[0];
-#pragma unroll
-    for (int tj = 0; tj < NT; ++tj)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        o[0] = mfma_16x16x4(st[ti][tj][r], vf[0][4 * tj + r], o[0]);
-        o[1] = mfma_16x16x4(st[ti][tj][r], vf[1][4 * tj + r], o[1]);
-      }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int t = ti * 16 + lq * 4 + r;
-      if (t < L) {
-        float* dst = out + (row0 + (int64_t)t * tstride) * OUT_LD + head * DH;
-        dst[l15] = o[0][r];
-        dst[16 + l15] = o[1][r];
-      }
-    }
-  }
+  attend_store<NT, true>(qf, kf, vf, head, L, l15, lq, bias, bias_vec, out, row0, tstride);
 }
 
 // ---------------- linear attention ----------------
@@ -320,7 +229,7 @@ __global__ __launch_bounds__(256) void linattn_output_kernel(const float* __rest
     q[i] = fast_exp(q[i] - m);
     sum += q[i];
   }
-  const float scale = 0.17677669529663687f * fast_rcp(sum);
+  const float scale = ATT_SCALE * fast_rcp(sum);
 #pragma unroll
   for (int i = 0; i < DH; ++i) q[i] = q[i] * scale;
   float* op = out + row * OUT_LD + h * DH;
@@ -355,10 +264,9 @@ extern "C" int lfdm_attention_cl_f32(const float* qkv, float* out, int batch, in
   const int64_t nseq = mode == 0 ? (int64_t)batch * hw : (int64_t)batch * frames;
   const int64_t units = nseq * HEADS;
   const dim3 grid((unsigned)units), block(64);
-  if (L <= 16) LFDM_LAUNCH((attention_kernel<16>), grid, block, 0, stream, qkv, out, batch, frames, hw, mode, bias, rot_cos, rot_sin);
-  else if (L <= 32) LFDM_LAUNCH((attention_kernel<32>), grid, block, 0, stream, qkv, out, batch, frames, hw, mode, bias, rot_cos, rot_sin);
-  else if (L <= 48) LFDM_LAUNCH((attention_kernel<48>), grid, block, 0, stream, qkv, out, batch, frames, hw, mode, bias, rot_cos, rot_sin);
-  else LFDM_LAUNCH((attention_kernel<64>), grid, block, 0, stream, qkv, out, batch, frames, hw, mode, bias, rot_cos, rot_sin);
+  lp_ladder(L, [&](auto lp) {
+    LFDM_LAUNCH((attention_kernel<decltype(lp)::value>), grid, block, 0, stream, qkv, out, frames, hw, mode, bias, rot_cos, rot_sin);
+  });
   return lfdm_check_launch("attention");
 }
 

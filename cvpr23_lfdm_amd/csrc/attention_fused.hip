@@ -17,122 +17,15 @@
 //  * V = x W_v^T is computed untransposed: lane = feature, registers = tokens 16*t + 4*slot + r, exactly the
 //    B operand of P V with the token order t(slot, s) = 16*(s>>2) + 4*slot + (s&3);
 //  * the scores are computed TRANSPOSED too (S^T = K Q^T): lane = query token, registers = key tokens, so the softmax
-//    over the keys is a register reduction + two shuffles and P^T is already the A operand of P V: no LDS at all.
+//    over the keys is a register reduction + two shuffles and P^T is already the A operand of P V: no LDS at all
+//    (attn_core.h attend_store; the fused kernels normalise with the IEEE division, attention_kernel with v_rcp_f32).
 // Weight fragments (rows of W, contiguous over channels) come from L2 as float4.
 #include <stdlib.h>
 
-#include "lfdm_device.h"
+#include "attn_core.h"
 #include "../../include/lfdm_hip.h"
 
 namespace {
-
-constexpr int HEADS = 8;
-constexpr int DH = 32;
-constexpr int OUT_LD = HEADS * DH;      // 256
-
-// Attention of one (sequence, head) from operand-layout fragments (see the header comment): scores transposed,
-// softmax in registers, P V, store.  qf/kf[ti][4*fi + r] = feature 16*fi + 4*lq + r of token 16*ti + l15 (q scaled and
-// rotated, k rotated); vf[half][4*ti + r] = v[token 16*ti + 4*lq + r][16*half + l15].
-// o_lds != nullptr: the attention output goes to the workgroup's LDS tile [token][256] (16-byte quads XOR-swizzled by the token, see
-// temporal_attn_fused_out_kernel) instead of global memory.
-template <int NT>
-__device__ __forceinline__ void attend_store(const float (&qf)[NT][8], const float (&kf)[NT][8], const float (&vf)[2][4 * NT],
-                                             int head, int L, int l15, int lq, const float* __restrict__ bias, bool bias_vec,
-                                             float* __restrict__ out, int64_t row0, int hw, float* o_lds = nullptr) {
-  // ---- S^T = K Q^T: lane = query token 16*ti + l15, registers = key tokens 16*tj + 4*lq + r.  In this orientation the
-  // softmax over the keys of a query is a reduction over the lane's registers plus two shuffles (the four k-slots),
-  // and the result is ALREADY the A operand of P V for the token order t(lq, s) = 16*(s>>2) + 4*lq + (s&3): no LDS. ----
-  f32x4 st[NT][NT];                                   // [ti (query tile)][tj (key tile)]
-#pragma unroll
-  for (int ti = 0; ti < NT; ++ti)
-#pragma unroll
-    for (int tj = 0; tj < NT; ++tj) {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < 8; ++s) acc = mfma_16x16x4(kf[tj][s], qf[ti][s], acc);
-      st[ti][tj] = acc;
-    }
-  // VALU diet (round 4; the head loop spends as many issue cycles outside the matrix pipe as inside it: 39 IEEE divisions, 36 expf
-  // expansions per head): exp is the hardware exponential (lfdm_device.h fast_exp: the arguments are <= 0; error figures there),
-  // and the normalisation multiplies by ONE reciprocal per query instead of dividing every probability.
-#pragma unroll
-  for (int ti = 0; ti < NT; ++ti) {
-    const int qt = ti * 16 + l15;                     // this lane's query token
-    float m = -3.0e38f;
-#pragma unroll
-    for (int tj = 0; tj < NT; ++tj) {
-      float bv[4] = {0.f, 0.f, 0.f, 0.f};
-      const int key0 = tj * 16 + lq * 4;
-      if (bias && qt < L && key0 < L) {                 // (guarded: unconditional loads of all nine fragments spill 84 registers)
-        const float* bp = bias + ((int64_t)head * L + qt) * L + key0;
-        if (bias_vec) {                                 // four consecutive keys of one query row: one 16-byte load
-          const float4 b4 = *reinterpret_cast<const float4*>(bp);
-          bv[0] = b4.x; bv[1] = b4.y; bv[2] = b4.z; bv[3] = b4.w;
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) bv[r] = (key0 + r < L) ? bp[r] : 0.f;
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float v = (key0 + r >= L) ? -3.0e38f : st[ti][tj][r] + bv[r];
-        st[ti][tj][r] = v;
-        m = fmaxf(m, v);
-      }
-    }
-    m = fmaxf(m, __shfl_xor(m, 16));
-    m = fmaxf(m, __shfl_xor(m, 32));
-    float sum = 0.f;
-#pragma unroll
-    for (int tj = 0; tj < NT; ++tj)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int key = tj * 16 + lq * 4 + r;
-        const float e = key < L ? fast_exp(st[ti][tj][r] - m) : 0.f;
-        st[ti][tj][r] = e;
-        sum += e;
-      }
-    sum += __shfl_xor(sum, 16);
-    sum += __shfl_xor(sum, 32);
-    const float inv = 1.0f / sum;
-#pragma unroll
-    for (int tj = 0; tj < NT; ++tj)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) st[ti][tj][r] = st[ti][tj][r] * inv;
-  }
-
-  // ---- O = P V ----
-#pragma unroll
-  for (int ti = 0; ti < NT; ++ti) {
-    f32x4 o[2];
-    o[0] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    o[1] = o[0];
-#pragma unroll
-    for (int tj = 0; tj < NT; ++tj)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        o[0] = mfma_16x16x4(st[ti][tj][r], vf[0][4 * tj + r], o[0]);
-        o[1] = mfma_16x16x4(st[ti][tj][r], vf[1][4 * tj + r], o[1]);
-      }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int t = ti * 16 + lq * 4 + r;
-      if (t < L) {
-        if (o_lds) {      // column c = head*32 + 16*half + l15 -> quad c >> 2, swizzled by the row
-#pragma unroll
-          for (int half = 0; half < 2; ++half) {
-            const int c = head * DH + 16 * half + l15;
-            o_lds[t * OUT_LD + ((((c >> 2) ^ (t & 15)) << 2) | (c & 3))] = o[half][r];
-          }
-        } else {
-          float* dst = out + (row0 + (int64_t)t * hw) * OUT_LD + head * DH;
-          dst[l15] = o[0][r];
-          dst[16 + l15] = o[1][r];
-        }
-      }
-    }
-  }
-}
 
 // The body of one wavefront: heads [head_begin, head_begin + heads_per_block) of sequence `seq`; results to global `out` or to `o_lds`.
 // ROT_RELOAD: the rotary factors are re-read from their (L1-resident, 2.5 KB) tables per head instead of living in 24 registers across the
@@ -153,7 +46,6 @@ __device__ __forceinline__ void tattn_heads(const float* __restrict__ x, int ldx
   const int L = frames;
   const int64_t b = seq / hw, pix = seq - b * hw;
   const int64_t row0 = b * frames * hw + pix;
-  const float scale = 0.17677669529663687f;  // 32^-0.5
 
   // ---- the sequence's rows, normalised, as MFMA fragments: xf[ti][s] = xhat[token 16*ti + l15][CQ*lq + s] ----
   float xf[NT][CQ];
@@ -167,19 +59,14 @@ __device__ __forceinline__ void tattn_heads(const float* __restrict__ x, int ldx
       for (int q = 0; q < CQ / 4; ++q) {
         const float4 v = *reinterpret_cast<const float4*>(src + 4 * q);
         xf[ti][4 * q] = v.x; xf[ti][4 * q + 1] = v.y; xf[ti][4 * q + 2] = v.z; xf[ti][4 * q + 3] = v.w;
-        s1 += (v.x + v.y) + (v.z + v.w);
-        s2 += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+        ln_accum(v, s1, s2);
       }
     } else {
 #pragma unroll
       for (int s = 0; s < CQ; ++s) xf[ti][s] = 0.f;
     }
-    s1 += __shfl_xor(s1, 16); s2 += __shfl_xor(s2, 16);
-    s1 += __shfl_xor(s1, 32); s2 += __shfl_xor(s2, 32);
-    const float mean = s1 * (1.0f / (float)C);
-    float var = s2 * (1.0f / (float)C) - mean * mean;
-    if (var < 0.f) var = 0.f;
-    const float rstd = 1.0f / sqrtf(var + eps);
+    float mean, rstd;
+    ln_stats_slots4<false>(s1, s2, C, eps, mean, rstd);
     if (t < L) {
 #pragma unroll
       for (int s = 0; s < CQ; ++s) xf[ti][s] = (xf[ti][s] - mean) * rstd;
@@ -240,7 +127,7 @@ __device__ __forceinline__ void tattn_heads(const float* __restrict__ x, int ldx
         for (int ti = 0; ti < NT; ++ti)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            if ((g >> 1) == 0) qf[ti][4 * (g & 1) + r] = acc[ti][r] * scale;
+            if ((g >> 1) == 0) qf[ti][4 * (g & 1) + r] = acc[ti][r] * ATT_SCALE;
             else kf[ti][4 * (g & 1) + r] = acc[ti][r];
           }
       }
@@ -261,12 +148,8 @@ __device__ __forceinline__ void tattn_heads(const float* __restrict__ x, int ldx
               c = rc[ti][2 * fi + pr];
               sn = rs[ti][2 * fi + pr];
             }
-            const float qx = qf[ti][4 * fi + 2 * pr], qy = qf[ti][4 * fi + 2 * pr + 1];
-            const float kx = kf[ti][4 * fi + 2 * pr], ky = kf[ti][4 * fi + 2 * pr + 1];
-            qf[ti][4 * fi + 2 * pr] = qx * c - qy * sn;
-            qf[ti][4 * fi + 2 * pr + 1] = qy * c + qx * sn;
-            kf[ti][4 * fi + 2 * pr] = kx * c - ky * sn;
-            kf[ti][4 * fi + 2 * pr + 1] = ky * c + kx * sn;
+            rot_pair(qf[ti][4 * fi + 2 * pr], qf[ti][4 * fi + 2 * pr + 1], c, sn);
+            rot_pair(kf[ti][4 * fi + 2 * pr], kf[ti][4 * fi + 2 * pr + 1], c, sn);
           }
       }
     }
@@ -300,14 +183,14 @@ __device__ __forceinline__ void tattn_heads(const float* __restrict__ x, int ldx
       }
     }
 
-    attend_store<NT>(qf, kf, vf, head, L, l15, lq, bias, bias_vec, out, row0, hw, o_lds);
+    attend_store<NT, false>(qf, kf, vf, head, L, l15, lq, bias, bias_vec, out, row0, hw, o_lds);
   }
 }
 
 template <int LP, int C>
 __global__ __launch_bounds__(64, 2) void temporal_attn_fused_kernel(const float* __restrict__ x, int ldx, int heads_per_block,
                                                                  const float* __restrict__ wqkv,   // (768, C), gamma folded
-                                                                 float* __restrict__ out, int batch, int frames, int hw,
+                                                                 float* __restrict__ out, int frames, int hw,
                                                                  const float* __restrict__ bias,
                                                                  const float* __restrict__ rot_cos,
                                                                  const float* __restrict__ rot_sin, float eps) {
@@ -392,7 +275,7 @@ __global__ __launch_bounds__(64 * NW, 2) void temporal_attn_fused_out_kernel(con
 template <int LP>
 __global__ __launch_bounds__(64, 1) void temporal_attn_fused_wide_kernel(const float* __restrict__ x, int ldx, int channels,
                                                                       int heads_per_block, const float* __restrict__ wqkv,
-                                                                      float* __restrict__ out, int batch, int frames, int hw,
+                                                                      float* __restrict__ out, int frames, int hw,
                                                                       const float* __restrict__ bias,
                                                                       const float* __restrict__ rot_cos,
                                                                       const float* __restrict__ rot_sin, float eps) {
@@ -403,7 +286,6 @@ __global__ __launch_bounds__(64, 1) void temporal_attn_fused_wide_kernel(const f
   const int64_t seq = blockIdx.x;
   const int64_t b = seq / hw, pix = seq - b * hw;
   const int64_t row0 = b * frames * hw + pix;
-  const float scale = 0.17677669529663687f;
   const int ncb = channels / 64;
 
   float mean[NT], rstd[NT];
@@ -415,19 +297,9 @@ __global__ __launch_bounds__(64, 1) void temporal_attn_fused_wide_kernel(const f
       const float* src = x + (row0 + (int64_t)t * hw) * ldx + 16 * lq;
       for (int cb = 0; cb < ncb; ++cb)
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float4 v = *reinterpret_cast<const float4*>(src + 64 * cb + 4 * q);
-          s1 += (v.x + v.y) + (v.z + v.w);
-          s2 += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-        }
+        for (int q = 0; q < 4; ++q) ln_accum(*reinterpret_cast<const float4*>(src + 64 * cb + 4 * q), s1, s2);
     }
-    s1 += __shfl_xor(s1, 16); s2 += __shfl_xor(s2, 16);
-    s1 += __shfl_xor(s1, 32); s2 += __shfl_xor(s2, 32);
-    const float m = s1 / (float)channels;
-    float var = s2 / (float)channels - m * m;
-    if (var < 0.f) var = 0.f;
-    mean[ti] = m;
-    rstd[ti] = 1.0f / sqrtf(var + eps);
+    ln_stats_slots4<true>(s1, s2, channels, eps, mean[ti], rstd[ti]);
   }
   const bool bias_vec = bias && (L % 4 == 0) && ((((uintptr_t)bias) & 15) == 0);
 
@@ -486,7 +358,7 @@ __global__ __launch_bounds__(64, 1) void temporal_attn_fused_wide_kernel(const f
       for (int fi = 0; fi < 2; ++fi)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          qf[ti][4 * fi + r] = aq[fi][ti][r] * scale;
+          qf[ti][4 * fi + r] = aq[fi][ti][r] * ATT_SCALE;
           kf[ti][4 * fi + r] = ak[fi][ti][r];
           vf[fi][4 * ti + r] = av[fi][ti][r];
         }
@@ -500,16 +372,12 @@ __global__ __launch_bounds__(64, 1) void temporal_attn_fused_wide_kernel(const f
 #pragma unroll
           for (int pr = 0; pr < 2; ++pr) {
             const float c = rot_cos[tt * 16 + 8 * fi + 2 * lq + pr], sn = rot_sin[tt * 16 + 8 * fi + 2 * lq + pr];
-            const float qx = qf[ti][4 * fi + 2 * pr], qy = qf[ti][4 * fi + 2 * pr + 1];
-            const float kx = kf[ti][4 * fi + 2 * pr], ky = kf[ti][4 * fi + 2 * pr + 1];
-            qf[ti][4 * fi + 2 * pr] = qx * c - qy * sn;
-            qf[ti][4 * fi + 2 * pr + 1] = qy * c + qx * sn;
-            kf[ti][4 * fi + 2 * pr] = kx * c - ky * sn;
-            kf[ti][4 * fi + 2 * pr + 1] = ky * c + kx * sn;
+            rot_pair(qf[ti][4 * fi + 2 * pr], qf[ti][4 * fi + 2 * pr + 1], c, sn);
+            rot_pair(kf[ti][4 * fi + 2 * pr], kf[ti][4 * fi + 2 * pr + 1], c, sn);
           }
       }
     }
-    attend_store<NT>(qf, kf, vf, head, L, l15, lq, bias, bias_vec, out, row0, hw);
+    attend_store<NT, false>(qf, kf, vf, head, L, l15, lq, bias, bias_vec, out, row0, hw);
   }
 }
 
@@ -519,10 +387,9 @@ int launch_fused_wide(const float* x, int ldx, int channels, const float* wqkv, 
   int hpb = 8;
   while (hpb > 1 && nseq * (HEADS / hpb) < 2048) hpb >>= 1;
   const dim3 grid((unsigned)nseq, (unsigned)(HEADS / hpb)), block(64);
-  if (frames <= 16) LFDM_LAUNCH((temporal_attn_fused_wide_kernel<16>), grid, block, 0, stream, x, ldx, channels, hpb, wqkv, out, batch, frames, hw, bias, rot_cos, rot_sin, eps);
-  else if (frames <= 32) LFDM_LAUNCH((temporal_attn_fused_wide_kernel<32>), grid, block, 0, stream, x, ldx, channels, hpb, wqkv, out, batch, frames, hw, bias, rot_cos, rot_sin, eps);
-  else if (frames <= 48) LFDM_LAUNCH((temporal_attn_fused_wide_kernel<48>), grid, block, 0, stream, x, ldx, channels, hpb, wqkv, out, batch, frames, hw, bias, rot_cos, rot_sin, eps);
-  else LFDM_LAUNCH((temporal_attn_fused_wide_kernel<64>), grid, block, 0, stream, x, ldx, channels, hpb, wqkv, out, batch, frames, hw, bias, rot_cos, rot_sin, eps);
+  lp_ladder(frames, [&](auto lp) {
+    LFDM_LAUNCH((temporal_attn_fused_wide_kernel<decltype(lp)::value>), grid, block, 0, stream, x, ldx, channels, hpb, wqkv, out, frames, hw, bias, rot_cos, rot_sin, eps);
+  });
   return lfdm_check_launch("temporal_attention_fused_wide");
 }
 
@@ -537,10 +404,9 @@ int launch_fused(const float* x, int ldx, const float* wqkv, float* out, int bat
     if (v == 1 || v == 2 || v == 4 || v == 8) hpb = v;
   }
   const dim3 grid((unsigned)nseq, (unsigned)(HEADS / hpb)), block(64);
-  if (frames <= 16) LFDM_LAUNCH((temporal_attn_fused_kernel<16, C>), grid, block, 0, stream, x, ldx, hpb, wqkv, out, batch, frames, hw, bias, rot_cos, rot_sin, eps);
-  else if (frames <= 32) LFDM_LAUNCH((temporal_attn_fused_kernel<32, C>), grid, block, 0, stream, x, ldx, hpb, wqkv, out, batch, frames, hw, bias, rot_cos, rot_sin, eps);
-  else if (frames <= 48) LFDM_LAUNCH((temporal_attn_fused_kernel<48, C>), grid, block, 0, stream, x, ldx, hpb, wqkv, out, batch, frames, hw, bias, rot_cos, rot_sin, eps);
-  else LFDM_LAUNCH((temporal_attn_fused_kernel<64, C>), grid, block, 0, stream, x, ldx, hpb, wqkv, out, batch, frames, hw, bias, rot_cos, rot_sin, eps);
+  lp_ladder(frames, [&](auto lp) {
+    LFDM_LAUNCH((temporal_attn_fused_kernel<decltype(lp)::value, C>), grid, block, 0, stream, x, ldx, hpb, wqkv, out, frames, hw, bias, rot_cos, rot_sin, eps);
+  });
   return lfdm_check_launch("temporal_attention_fused");
 }
 
@@ -557,10 +423,10 @@ int launch_fused_out_lp(const float* x, int ldx, const float* wqkv, const float*
     if (v == 1 || v == 2 || v == 4 || v == 8) nw = v;
   }
   const dim3 grid((unsigned)nseq);
-  if (nw == 1) LFDM_LAUNCH((temporal_attn_fused_out_kernel<LP, LROWS, 1>), grid, dim3(64), 0, stream, x, ldx, wqkv, wout, out, ldo, frames, hw, bias, rot_cos, rot_sin, eps);
-  else if (nw == 2) LFDM_LAUNCH((temporal_attn_fused_out_kernel<LP, LROWS, 2>), grid, dim3(128), 0, stream, x, ldx, wqkv, wout, out, ldo, frames, hw, bias, rot_cos, rot_sin, eps);
-  else if (nw == 4) LFDM_LAUNCH((temporal_attn_fused_out_kernel<LP, LROWS, 4>), grid, dim3(256), 0, stream, x, ldx, wqkv, wout, out, ldo, frames, hw, bias, rot_cos, rot_sin, eps);
-  else LFDM_LAUNCH((temporal_attn_fused_out_kernel<LP, LROWS, 8>), grid, dim3(512), 0, stream, x, ldx, wqkv, wout, out, ldo, frames, hw, bias, rot_cos, rot_sin, eps);
+  lfdm_ladder<1, 2, 4, 8>(nw, [&](auto nwc) {
+    constexpr int NW = decltype(nwc)::value;
+    LFDM_LAUNCH((temporal_attn_fused_out_kernel<LP, LROWS, NW>), grid, dim3(64 * NW), 0, stream, x, ldx, wqkv, wout, out, ldo, frames, hw, bias, rot_cos, rot_sin, eps);
+  });
   return lfdm_check_launch("temporal_attention_fused_out");
 }
 
@@ -575,11 +441,12 @@ extern "C" int lfdm_temporal_attention_fused_out_cl_f32(const float* x, int ldx,
     lfdm_set_error("temporal_attention_fused_out: needs C == 64, frames <= 64, 16-byte aligned rows, out != x");
     return LFDM_EINVAL;
   }
-  if (frames <= 16) return launch_fused_out_lp<16, 16>(x, ldx, wqkv, wout, out, ldo, batch, frames, hw, bias, rot_cos, rot_sin, ln_eps, stream);
-  if (frames <= 32) return launch_fused_out_lp<32, 32>(x, ldx, wqkv, wout, out, ldo, batch, frames, hw, bias, rot_cos, rot_sin, ln_eps, stream);
-  if (frames <= 40) return launch_fused_out_lp<48, 40>(x, ldx, wqkv, wout, out, ldo, batch, frames, hw, bias, rot_cos, rot_sin, ln_eps, stream);
-  if (frames <= 48) return launch_fused_out_lp<48, 48>(x, ldx, wqkv, wout, out, ldo, batch, frames, hw, bias, rot_cos, rot_sin, ln_eps, stream);
-  return launch_fused_out_lp<64, 64>(x, ldx, wqkv, wout, out, ldo, batch, frames, hw, bias, rot_cos, rot_sin, ln_eps, stream);
+  return lp_ladder(frames, [&](auto lp) {
+    constexpr int LP = decltype(lp)::value;
+    if (LP == 48 && frames <= 40)      // the 40-frame videos: a 40-row LDS tile
+      return launch_fused_out_lp<48, 40>(x, ldx, wqkv, wout, out, ldo, batch, frames, hw, bias, rot_cos, rot_sin, ln_eps, stream);
+    return launch_fused_out_lp<LP, LP>(x, ldx, wqkv, wout, out, ldo, batch, frames, hw, bias, rot_cos, rot_sin, ln_eps, stream);
+  });
 }
 
 extern "C" int lfdm_temporal_attention_fused_cl_f32(const float* x, int ldx, int channels, const float* wqkv, float* out,

@@ -34,30 +34,14 @@
 // tile) = 2 with one (10 waves per CU by LDS).  No spills, no AGPRs - against the one wave per SIMD on 512 VGPRs of attention_bwd_kernel.
 // No inline-assembly load pipeline in this version: the other waves of the SIMD hide the streamed loads.
 #include <stdlib.h>
-#include "lfdm_device.h"
+#include "attn_core.h"
 #include "../../include/lfdm_hip.h"
 
 namespace {
 
-constexpr int HEADS = 8;
-constexpr int DH = 32;
-constexpr int QKV_LD = 3 * HEADS * DH;  // 768
-constexpr int OUT_LD = HEADS * DH;      // 256
-constexpr float ATT_SCALE = 0.17677669529663687f;  // 32^-0.5
 constexpr int L_MIN = 65, L_MAX = 256;
 constexpr int NQ = 2;                   // query tiles of 16 per wave (forward, phase Q)
 constexpr int MAX_WAVES_KV = 2048;      // launch-size cap of phase KV
-
-__device__ __forceinline__ void seq_rows(int64_t seq, int mode, int frames, int hw, int64_t& row0, int64_t& tstride) {
-  if (mode == 0) {
-    const int64_t b = seq / hw, pix = seq - b * hw;
-    row0 = b * frames * hw + pix;
-    tstride = hw;
-  } else {
-    row0 = seq * hw;
-    tstride = 1;
-  }
-}
 
 // f[s] = src[token t][8*lq + s] * scale (zeros for t >= L), rotated by the token's rotary factors if rot_cos: the A / B operand of a
 // contraction over the 32 features for the token of lane & 15.  src points at column 0 of the head's q, k, v or dout block of row 0.
@@ -75,9 +59,7 @@ __device__ __forceinline__ void load_frag(float f[8], const float* src, int ld, 
 #pragma unroll
     for (int pr = 0; pr < 4; ++pr) {
       const float c = rot_cos[t * 16 + 4 * lq + pr], sn = rot_sin[t * 16 + 4 * lq + pr];
-      const float x = f[2 * pr], y = f[2 * pr + 1];
-      f[2 * pr] = x * c - y * sn;
-      f[2 * pr + 1] = y * c + x * sn;
+      rot_pair(f[2 * pr], f[2 * pr + 1], c, sn);
     }
   }
 }

@@ -17,17 +17,13 @@
 //    columns of the head are written.
 #include <stdlib.h>
 
-#include "lfdm_device.h"
+#include "attn_core.h"
 #include "../../include/lfdm_hip.h"
 
 namespace {
 
-constexpr int HEADS = 8;
-constexpr int DH = 32;
-constexpr int OUT_LD = HEADS * DH;      // 256
 constexpr int NQ = 3 * DH;              // q | k | v columns of one head
 constexpr int LDQ = NQ + 4;             // LDS row stride (16-byte aligned rows)
-constexpr float ATT_SCALE = 0.17677669529663687f;   // 32^-0.5
 
 // One wavefront's share of the projection: rows r = 0 .. 16*NT-1 of the unit (global row row0 + r * rstride, rows >= nrows are
 // clamped duplicates that nobody reads), channels [c_begin, c_end) in steps of 16.  acc[ti][nj]: D layout of v_mfma_f32_16x16x4
@@ -395,14 +391,7 @@ __global__ __launch_bounds__(256) void attn_lowres_kernel(const float* __restric
   const int64_t seq = unit >> 3;
   const int head = (int)(unit & 7);
   int64_t row0, tstride;
-  if (mode == 0) {
-    const int64_t b = seq / hw, pix = seq - b * hw;
-    row0 = b * frames * hw + pix;
-    tstride = hw;
-  } else {
-    row0 = seq * hw;
-    tstride = 1;
-  }
+  seq_rows(seq, mode, frames, hw, row0, tstride);
   const int L = mode == 0 ? frames : hw;
   const float wsum_val = load_wsum(wsum, head);
   // (49 ... 64 tokens: with 96 accumulator registers, the ring and the attention's own fragments the asm pipeline does not fit the
@@ -422,9 +411,7 @@ __global__ __launch_bounds__(256) void attn_lowres_kernel(const float* __restric
 #pragma unroll
         for (int pr = 0; pr < 4; ++pr) {
           const float c = rot_cos[t * 16 + 4 * lq + pr], sn = rot_sin[t * 16 + 4 * lq + pr];
-          const float qx = qf[2 * pr], qy = qf[2 * pr + 1];
-          qf[2 * pr] = qx * c - qy * sn;
-          qf[2 * pr + 1] = qy * c + qx * sn;
+          rot_pair(qf[2 * pr], qf[2 * pr + 1], c, sn);
         }
       }
     }
@@ -439,9 +426,7 @@ __global__ __launch_bounds__(256) void attn_lowres_kernel(const float* __restric
 #pragma unroll
         for (int pr = 0; pr < 4; ++pr) {
           const float c = rot_cos[t * 16 + 4 * lq + pr], sn = rot_sin[t * 16 + 4 * lq + pr];
-          const float kx = kf[tj][2 * pr], ky = kf[tj][2 * pr + 1];
-          kf[tj][2 * pr] = kx * c - ky * sn;
-          kf[tj][2 * pr + 1] = ky * c + kx * sn;
+          rot_pair(kf[tj][2 * pr], kf[tj][2 * pr + 1], c, sn);
         }
       }
     }
@@ -454,33 +439,8 @@ __global__ __launch_bounds__(256) void attn_lowres_kernel(const float* __restric
       for (int s = 0; s < 8; ++s) a = mfma_16x16x4(kf[tj][s], qf[s], a);
       st[tj] = a;
     }
-    const int qt = ti * 16 + l15;
-    float m = -3.0e38f;
-#pragma unroll
-    for (int tj = 0; tj < NT; ++tj)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int key = tj * 16 + lq * 4 + r;
-        float v = st[tj][r];
-        if (key >= L) v = -3.0e38f;
-        else if (bias && qt < L) v += bias[((int64_t)head * L + qt) * L + key];
-        st[tj][r] = v;
-        m = fmaxf(m, v);
-      }
-    m = fmaxf(m, __shfl_xor(m, 16));
-    m = fmaxf(m, __shfl_xor(m, 32));
-    float sum = 0.f;
-#pragma unroll
-    for (int tj = 0; tj < NT; ++tj)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float e = (tj * 16 + lq * 4 + r) < L ? fast_exp(st[tj][r] - m) : 0.f;
-        st[tj][r] = e;
-        sum += e;
-      }
-    sum += __shfl_xor(sum, 16);
-    sum += __shfl_xor(sum, 32);
-    const float inv = fast_rcp(sum);
+    // softmax over the keys (attn_core.h; the bias is read element by element: its rows have no alignment here)
+    const float inv = softmax_tile<NT, true>(st, head, L, ti * 16 + l15, lq, bias, false);
     // O = P V: B operand = v[token 16*tj + 4*lq + r][16*half + l15]
     f32x4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = o0;
 #pragma unroll
@@ -519,14 +479,14 @@ extern "C" int lfdm_linear_attention_lowres_cl_f32(const float* x, int ldx, int 
     return LFDM_EINVAL;
   }
   const dim3 grid((unsigned)(n_frames * HEADS)), block(256);
-  if (hw <= 16) LFDM_LAUNCH((linattn_lowres_kernel<1, false>), grid, block, 0, stream, x, ldx, channels, wqkv, wsum, out, hw, ln_eps);
-  else if (hw <= 32) LFDM_LAUNCH((linattn_lowres_kernel<2, false>), grid, block, 0, stream, x, ldx, channels, wqkv, wsum, out, hw, ln_eps);
-  else if (hw <= 64) LFDM_LAUNCH((linattn_lowres_kernel<4, false>), grid, block, 0, stream, x, ldx, channels, wqkv, wsum, out, hw, ln_eps);
-  else if (hw > 192) LFDM_LAUNCH((linattn_lowres_kernel<4, true>), grid, block, 0, stream, x, ldx, channels, wqkv, wsum, out, hw, ln_eps);
-  else {
+  if (hw > 192) LFDM_LAUNCH((linattn_lowres_kernel<4, true>), grid, block, 0, stream, x, ldx, channels, wqkv, wsum, out, hw, ln_eps);
+  else if (hw > 64) {
     lfdm_set_error("linear_attention_lowres: 64 < hw <= 192 pixels per frame is not built (use the unfused entry points)");
     return LFDM_EINVAL;
-  }
+  } else
+    lfdm_ladder<16, 32, 64>(hw, [&](auto rows) {
+      LFDM_LAUNCH((linattn_lowres_kernel<decltype(rows)::value / 16, false>), grid, block, 0, stream, x, ldx, channels, wqkv, wsum, out, hw, ln_eps);
+    });
   return lfdm_check_launch("linear_attention_lowres");
 }
 
@@ -542,9 +502,8 @@ extern "C" int lfdm_attention_lowres_cl_f32(const float* x, int ldx, int channel
     return LFDM_EINVAL;
   }
   const dim3 grid((unsigned)(nseq * HEADS)), block(256);
-  if (L <= 16) LFDM_LAUNCH((attn_lowres_kernel<1>), grid, block, 0, stream, x, ldx, channels, wqkv, wsum, out, frames, hw, mode, bias, rot_cos, rot_sin, ln_eps);
-  else if (L <= 32) LFDM_LAUNCH((attn_lowres_kernel<2>), grid, block, 0, stream, x, ldx, channels, wqkv, wsum, out, frames, hw, mode, bias, rot_cos, rot_sin, ln_eps);
-  else if (L <= 48) LFDM_LAUNCH((attn_lowres_kernel<3>), grid, block, 0, stream, x, ldx, channels, wqkv, wsum, out, frames, hw, mode, bias, rot_cos, rot_sin, ln_eps);
-  else LFDM_LAUNCH((attn_lowres_kernel<4>), grid, block, 0, stream, x, ldx, channels, wqkv, wsum, out, frames, hw, mode, bias, rot_cos, rot_sin, ln_eps);
+  lp_ladder(L, [&](auto lp) {
+    LFDM_LAUNCH((attn_lowres_kernel<decltype(lp)::value / 16>), grid, block, 0, stream, x, ldx, channels, wqkv, wsum, out, frames, hw, mode, bias, rot_cos, rot_sin, ln_eps);
+  });
   return lfdm_check_launch("attention_lowres");
 }

@@ -17,19 +17,15 @@
 // into the weights by the host.
 #include <stdlib.h>
 
-#include "lfdm_device.h"
+#include "attn_core.h"
 #include "../../include/lfdm_hip.h"
 
 namespace {
 
-constexpr int HEADS = 8;
-constexpr int DH = 32;
-constexpr int OUT_LD = HEADS * DH;      // 256
 constexpr int C = 64;                   // input channels (finest level)
 constexpr int CH = C / 2;               // channels per k-slot
 constexpr int SPLIT_TOK = 32;           // smallest context split (one token tile): sizes the workspace
 constexpr int PART = DH * DH + 2 * DH;  // floats per partial: ctx[32][32] | m[32] | s[32]
-constexpr float LA_SCALE = 0.17677669529663687f;
 
 // xhat fragment of one token: lane (token l31 of the tile, half kh) holds channels CH*kh .. CH*kh + CH-1, normalised.  `xrow` is ALWAYS a valid
 // row (the callers clamp the token index) and is loaded unconditionally; !ok only zeroes the result.  (Round 6: behind `if (ok)` every one of the
@@ -319,7 +315,7 @@ __global__ __launch_bounds__(64, 2) void linattn_fused_out_kernel(const float* _
       sum += q[r];
     }
     sum += __shfl_xor(sum, 32);
-    const float inv = LA_SCALE * fast_rcp(sum);
+    const float inv = ATT_SCALE * fast_rcp(sum);
     // out[token][e] = sum_d q~[token][d] ctx[d][e]: A = q (lane = token, slot = d half), B = ctx[d(kh, r)][e = l31]
     const float* cb = ctx + ((int64_t)f * HEADS + h) * DH * DH + l31;
     f32x16 o;
@@ -395,7 +391,7 @@ __global__ __launch_bounds__(256, 2) void linattn_fused_out2_kernel(const float*
       sum += q[r];
     }
     sum += __shfl_xor(sum, 32);
-    const float inv = LA_SCALE * fast_rcp(sum);
+    const float inv = ATT_SCALE * fast_rcp(sum);
 #pragma unroll
     for (int r = 0; r < 16; ++r) q[r] *= inv;
     // Y^T[c][tok] += Mt[c][d] q~[tok][d]: A = Mt fragment (lane = row c), B = q~ (lane = column tok, k = d(kh, r), r = 4 qd + j)

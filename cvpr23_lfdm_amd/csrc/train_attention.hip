@@ -16,18 +16,13 @@
 //    A per-(frame, head) reduction kernel (k-softmax statistics, ctx, dctx) and a per-token apply kernel.
 #include <stdlib.h>
 
-#include "lfdm_device.h"
+#include "attn_core.h"
 #include "../../include/lfdm_hip.h"
 
 namespace {
 
-constexpr int HEADS = 8;
-constexpr int DH = 32;
-constexpr int QKV_LD = 3 * HEADS * DH;  // 768
-constexpr int OUT_LD = HEADS * DH;      // 256
 constexpr int SQ = 34;                  // LDS row stride of Q, K
 constexpr int SV = 36;                  // LDS row stride of V, dO
-constexpr float ATT_SCALE = 0.17677669529663687f;  // 32^-0.5
 
 // LROWS (>= the sequence length, <= LP): rows of the wave's LDS tiles.  The 40-frame videos use 40 of the 48 padded rows: the three GEMMs that
 // contract over tokens run 10 instead of 12 k-steps.  (Five waves per CU would fit the 160 KB with 30.4 KB tiles, but the kernel lives on the
@@ -75,14 +70,7 @@ __global__ __launch_bounds__(64 * WPB) void attention_bwd_kernel(
     valid = unit < units;
     const int64_t seq = valid ? unit / HEADS : 0;
     head = valid ? (int)(unit - seq * HEADS) : 0;
-    if (mode == 0) {
-      const int64_t b = seq / hw, pix = seq - b * hw;
-      row0 = b * frames * hw + pix;
-      tstride = hw;
-    } else {
-      row0 = seq * hw;
-      tstride = 1;
-    }
+    seq_rows(seq, mode, frames, hw, row0, tstride);
   };
   auto fetch = [&](int64_t unit) {
     bool valid;
@@ -138,12 +126,10 @@ __global__ __launch_bounds__(64 * WPB) void attention_bwd_kernel(
         if (rot_cos && t < L) {
           const float c0 = BATCH ? rcos[i].x : rot_cos[t * 16 + 2 * c4], s0 = BATCH ? rsin[i].x : rot_sin[t * 16 + 2 * c4];
           const float c1 = BATCH ? rcos[i].y : rot_cos[t * 16 + 2 * c4 + 1], s1 = BATCH ? rsin[i].y : rot_sin[t * 16 + 2 * c4 + 1];
-          float4 qr, kr;
-          qr.x = q.x * c0 - q.y * s0; qr.y = q.y * c0 + q.x * s0;
-          qr.z = q.z * c1 - q.w * s1; qr.w = q.w * c1 + q.z * s1;
-          kr.x = k.x * c0 - k.y * s0; kr.y = k.y * c0 + k.x * s0;
-          kr.z = k.z * c1 - k.w * s1; kr.w = k.w * c1 + k.z * s1;
-          q = qr; k = kr;
+          rot_pair(q.x, q.y, c0, s0);
+          rot_pair(q.z, q.w, c1, s1);
+          rot_pair(k.x, k.y, c0, s0);
+          rot_pair(k.z, k.w, c1, s1);
         }
         if (LROWS < LP && t >= LROWS) continue;
         float* dq = Qs + t * SQ + 4 * c4;
@@ -599,11 +585,11 @@ extern "C" int lfdm_attention_bwd_cl_f32(const float* qkv, const float* dout, fl
     part = (float*)ws;
   }
   const dim3 grid(nb), block(64 * wpb);
-  if (L <= 16) LFDM_LAUNCH((attention_bwd_kernel<16, 4>), grid, block, 0, stream, qkv, dout, dqkv, batch, frames, hw, mode, bias, rot_cos, rot_sin, part);
-  else if (L <= 32) LFDM_LAUNCH((attention_bwd_kernel<32, 4>), grid, block, 0, stream, qkv, dout, dqkv, batch, frames, hw, mode, bias, rot_cos, rot_sin, part);
-  else if (rows40) LFDM_LAUNCH((attention_bwd_kernel<48, 4, 40>), grid, block, 0, stream, qkv, dout, dqkv, batch, frames, hw, mode, bias, rot_cos, rot_sin, part);
-  else if (L <= 48) LFDM_LAUNCH((attention_bwd_kernel<48, 4>), grid, block, 0, stream, qkv, dout, dqkv, batch, frames, hw, mode, bias, rot_cos, rot_sin, part);
-  else LFDM_LAUNCH((attention_bwd_kernel<64, 2>), grid, block, 0, stream, qkv, dout, dqkv, batch, frames, hw, mode, bias, rot_cos, rot_sin, part);
+  lp_ladder(L, [&](auto lp) {
+    constexpr int LP = decltype(lp)::value, WPB = LP > 48 ? 2 : 4;
+    if (LP == 48 && rows40) LFDM_LAUNCH((attention_bwd_kernel<48, 4, 40>), grid, block, 0, stream, qkv, dout, dqkv, batch, frames, hw, mode, bias, rot_cos, rot_sin, part);
+    else LFDM_LAUNCH((attention_bwd_kernel<LP, WPB>), grid, block, 0, stream, qkv, dout, dqkv, batch, frames, hw, mode, bias, rot_cos, rot_sin, part);
+  });
   int rc = lfdm_check_launch("attention_bwd");
   if (rc) return rc;
   if (dbias) {
