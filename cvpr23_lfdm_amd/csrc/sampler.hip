@@ -190,7 +190,10 @@ __device__ float resolve_quantile(const unsigned* hs, Ranks rk, unsigned* s_part
   find_bins<1>(h2b, rb, b2, t, s_part, s_res);
   const float lo = __uint_as_float((bin0[0] << 21) | (a1[0] << 10) | a2[0]);
   const float hi = __uint_as_float((bin0[1] << 21) | (b1[0] << 10) | b2[0]);
-  return lo + rk.frac * (hi - lo);  // aten lerp form for weight < 0.5
+  // ATen's lerp, both branches, each ONE fused multiply-add (what its vectorised CPU kernel evaluates and torch.quantile returns):
+  // weight < 0.5: lo + w d, otherwise hi - (1 - w) d.  Explicit fmaf: the bits do not depend on the compiler's contraction setting.
+  const float d = hi - lo;
+  return rk.frac < 0.5f ? fmaf(rk.frac, d, lo) : fmaf(-d, 1.0f - rk.frac, hi);
 }
 
 __global__ __launch_bounds__(256) void quantile_out_kernel(Ranks rk, const unsigned* __restrict__ hists,

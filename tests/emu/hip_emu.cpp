@@ -37,7 +37,15 @@ thread_local State g;
 
 static const size_t kStackBytes = 256 * 1024;
 static thread_local std::vector<Fiber> fibers;
-static thread_local std::vector<char*> stacks;
+// The fiber stacks of one OS thread, freed when the thread ends: launch() starts fresh workers for every multi-workgroup grid, and stacks
+// that outlived them cost 64 MiB of address space and 256 mappings per worker and launch - a few thousand launches in one process
+// ran into the kernel's limit on mappings.
+struct FiberStacks : std::vector<char*> {
+  ~FiberStacks() {
+    for (char* p : *this) free(p);
+  }
+};
+static thread_local FiberStacks stacks;
 static thread_local const std::function<void()>* cur_body = nullptr;
 static thread_local unsigned live_threads = 0;
 

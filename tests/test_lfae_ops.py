@@ -236,6 +236,85 @@ def test_apply_optical_image(backend):
         assert_close(got.cpu() / s, want / s, TOL, "apply_optical_image " + name)
 
 
+def _point_flow(n, h, w, ix, iy):
+    """Every output pixel samples the source position (ix, iy) (pixel units, align_corners=False)."""
+    flow = torch.empty(n, h, w, 2)
+    flow[..., 0] = (2.0 * ix + 1.0) / w - 1.0
+    flow[..., 1] = (2.0 * iy + 1.0) / h - 1.0
+    return flow
+
+
+def _spiked(shape):
+    dy = 1e-3 * rnd(*shape, seed=5)
+    dy.view(-1)[1234] = 1e6
+    return dy
+
+
+SCATTER_CASES = {    # name -> (flow, dout) builders for (n, h, w) and the output's shape
+    "one_point_dout_1": (lambda n, h, w: _point_flow(n, h, w, 6.3, 9.6), lambda s: torch.ones(s)),
+    "one_point_dout_3e4": (lambda n, h, w: _point_flow(n, h, w, 6.3, 9.6), lambda s: torch.full(s, 3e4)),
+    "one_pixel_centre": (lambda n, h, w: _point_flow(n, h, w, 5.0, 11.0), lambda s: torch.ones(s)),
+    "dout_zero": (lambda n, h, w: _flow(n, h, w, 3, amp=0.6), lambda s: torch.zeros(s)),
+    "dout_one_large_element": (lambda n, h, w: _flow(n, h, w, 3, amp=0.6), _spiked),
+    "dout_1e-30": (lambda n, h, w: _flow(n, h, w, 3, amp=0.6), lambda s: 1e-30 * rnd(*s, seed=5)),
+    "dout_1e30": (lambda n, h, w: _flow(n, h, w, 3, amp=0.6), lambda s: 1e30 * rnd(*s, seed=5)),
+    "flow_beyond_the_clamp": (lambda n, h, w: _flow(n, h, w, 3, amp=0.6) + 1e8, lambda s: rnd(*s, seed=5)),
+}
+
+
+def _scaled_close(got, want, what):
+    s = float(want.abs().max()) or 1.0                      # an all-zero reference is compared as it stands
+    assert_close(got.cpu() / s, want / s, TOL, what)
+
+
+@pytest.mark.parametrize("case", sorted(SCATTER_CASES))
+def test_apply_optical_scatter_extremes(backend, case):
+    """The fixed-point scatter of the warp backward picks its scale 2^k from absmax(dout) and a bound of 4 h w terms per address.  Random
+    flows spread the terms evenly; here every output pixel scatters into the same four (or one) source pixels, dout is zero (k = 0),
+    tiny, huge, or dominated by one element, and the flow lies beyond the kernels' +-1e6 clamp (output and gradients are zero).
+    Reference: F.grid_sample(align_corners=False) times occ (ApplyOpticalImage: blended with prev) under float64 autograd."""
+    dev = backend
+    n, c, h, w = 2, 8, 16, 16
+    make_flow, make_dout = SCATTER_CASES[case]
+    src, prev = rnd(n, c, h, w, seed=1), rnd(n, c, h, w, seed=2)
+    flow, occ = make_flow(n, h, w).contiguous(), torch.sigmoid(rnd(n, 1, h, w, seed=4))
+    dy = make_dout((n, c, h, w))
+    s64, p64, f64, o64 = (t.double().requires_grad_(True) for t in (src, prev, flow, occ))
+    ref = _apply_optical_ref(s64, None, f64, o64)
+    ref.backward(dy.double())
+    if case == "flow_beyond_the_clamp":
+        assert float(ref.detach().abs().max()) == 0.0 and float(s64.grad.abs().max()) == 0.0 and float(f64.grad.abs().max()) == 0.0
+
+    def run_cl():
+        sd = _cl(src.to(dev)).requires_grad_(True)
+        fd, od = flow.clone().to(dev).requires_grad_(True), occ.clone().to(dev).requires_grad_(True)
+        out = L.ApplyOpticalCL.apply(sd, None, L._maps_planar(fd, od))
+        out.backward(_cl(dy.to(dev)))
+        st = L._state(sd.device)
+        assert int(st["fix"].abs().max()) == 0 and int(st["amax"].abs().max()) == 0, "workspace not handed back zeroed"
+        return out.detach(), sd.grad, fd.grad, od.grad
+
+    out, dsrc, dflow, docc = run_cl()
+    assert_close(out.cpu(), ref.detach(), TOL, case + " out")
+    for name, got, want in (("dsrc", dsrc, s64.grad), ("dflow", dflow, f64.grad), ("docc", docc, o64.grad)):
+        assert torch.isfinite(got).all(), case + " " + name
+        _scaled_close(got, want, "%s %s" % (case, name))
+    for a, b in zip((out, dsrc, dflow, docc), run_cl()):
+        assert torch.equal(a, b), case + ": not the same bits from run to run"
+    # the per-pixel backward of the image blend (no d_src, no scatter): the same maps, dout and extremes
+    for t in (f64, o64):
+        t.grad = None
+    ref = _apply_optical_ref(s64.detach(), p64, f64, o64)
+    ref.backward(dy.double())
+    pd, fd, od = (t.clone().to(dev).requires_grad_(True) for t in (prev, flow, occ))
+    out = L.ApplyOpticalImage.apply(src.to(dev), pd, L._maps_planar(fd, od))
+    assert_close(out.detach().cpu(), ref.detach(), TOL, case + " image out")
+    out.backward(dy.to(dev))
+    for name, got, want in (("dprev", pd.grad, p64.grad), ("dflow", fd.grad, f64.grad), ("docc", od.grad, o64.grad)):
+        assert torch.isfinite(got).all(), case + " image " + name
+        _scaled_close(got, want, "%s image %s" % (case, name))
+
+
 @pytest.mark.parametrize("reflection,n_div", [(False, 1), (False, 3), (True, 1)])
 def test_grid_sample(backend, reflection, n_div):
     dev = backend

@@ -669,7 +669,7 @@ def test_heads_with_groupnorm_folded(backend, case):
 
 
 # ------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n", [97, 3 * 4 * 8 * 8, 122880])
+@pytest.mark.parametrize("n", [97, 192, 3 * 4 * 8 * 8, 3 * 1 * 32 * 32, 122880])
 def test_abs_quantile(backend, n):
     dev = backend
     if n > 10000 and not big(dev):
