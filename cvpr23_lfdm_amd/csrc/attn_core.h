@@ -162,13 +162,6 @@ __device__ __forceinline__ void ln_stats_slots4(float s1, float s2, int channels
   rstd = 1.0f / sqrtf(var + eps);
 }
 
-// Host-side ladder: f(std::integral_constant<int, R>) for the first rung R >= v; the last rung takes everything above it.  A launch
-// site names its kernel and argument list once, inside f.
-template <int R, int... REST, class F>
-inline auto lfdm_ladder(int v, F&& f) {
-  if constexpr (sizeof...(REST) == 0) return f(std::integral_constant<int, R>{});
-  else return v <= R ? f(std::integral_constant<int, R>{}) : lfdm_ladder<REST...>(v, f);
-}
-// ... over the padded length of a sequence of L <= 64 tokens
+// lfdm_ladder (lfdm_device.h) over the padded length of a sequence of L <= 64 tokens
 template <class F>
 inline auto lp_ladder(int L, F&& f) { return lfdm_ladder<16, 32, 48, 64>(L, f); }

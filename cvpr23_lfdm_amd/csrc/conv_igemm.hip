@@ -20,8 +20,7 @@
 //    (sum, sum of squares per group) so the following GroupNorm needs no statistics pass.
 #include <stdlib.h>
 
-#include "lfdm_device.h"
-#include "../../include/lfdm_hip.h"
+#include "conv_core.h"
 
 namespace {
 
@@ -380,9 +379,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(lfdm_conv_params p) {
 
   // transpose each 32x32 accumulator tile through a wave-private LDS scratch (aliases the A tile)
   float* scratch = smem + wave * (32 * LD);
-  const bool vec_ok = (p.cout % 4 == 0) && (p.ldo % 4 == 0) && ((((uintptr_t)p.out) & 15) == 0) &&
-                      (!p.residual || ((p.ldr % 4 == 0) && ((((uintptr_t)p.residual) & 15) == 0))) &&
-                      (!p.bias || (((uintptr_t)p.bias) & 15) == 0);      // (the same test as make_plan's: pre_b below is a float4 load of bias)
+  const bool vec_ok = (p.cout % 4 == 0) && conv_epilogue_vec4_ok(p);      // (make_plan's test: pre_b below is a float4 load of bias)
   const int c4 = lane & 7, rsub = lane >> 3;
   float gs[TN][4], gq[TN][4];
 #pragma unroll
@@ -412,8 +409,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(lfdm_conv_params p) {
         const int colbase = n0 + wn * WN + 32 * j + 4 * c4;
         pre_r[j][it] = z4;
         if (vec_ok && p.residual && colbase < p.cout && s_img[row] >= 0) {
-          const int64_t orow = ((int64_t)s_img[row] * p.ho + s_qy[row] * p.out_scale + p.out_off_y) * p.wo + s_qx[row] * p.out_scale + p.out_off_x;
-          pre_r[j][it] = *reinterpret_cast<const float4*>(p.residual + orow * p.ldr + colbase);
+          pre_r[j][it] = *reinterpret_cast<const float4*>(p.residual + conv_out_row(p, s_img[row], s_qy[row], s_qx[row]) * p.ldr + colbase);
         }
       }
 #pragma unroll
@@ -431,9 +427,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(lfdm_conv_params p) {
         const int img = s_img[row];
         if (img < 0 || colbase >= p.cout) continue;
         float4 v = *reinterpret_cast<const float4*>(scratch + trow * LD + 4 * c4);
-        const int oy = s_qy[row] * p.out_scale + p.out_off_y;
-        const int ox = s_qx[row] * p.out_scale + p.out_off_x;
-        const int64_t orow = ((int64_t)img * p.ho + oy) * p.wo + ox;
+        const int64_t orow = conv_out_row(p, img, s_qy[row], s_qx[row]);
         if (vec_ok) {
           if (FAST && LN) {      // y = rstd * (x.W' - mean * sum_c W')
             const float4 ws = pre_w[j];
@@ -441,75 +435,29 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(lfdm_conv_params p) {
             v.x = rs * (v.x - mu * ws.x); v.y = rs * (v.y - mu * ws.y);
             v.z = rs * (v.z - mu * ws.z); v.w = rs * (v.w - mu * ws.w);
           }
-          {
-            const float4 bb = pre_b[j];
-            v.x += bb.x; v.y += bb.y; v.z += bb.z; v.w += bb.w;
-          }
-          if (p.gn_partial) {
-            gs[j][0] += v.x; gs[j][1] += v.y; gs[j][2] += v.z; gs[j][3] += v.w;
-            gq[j][0] += v.x * v.x; gq[j][1] += v.y * v.y; gq[j][2] += v.z * v.z; gq[j][3] += v.w * v.w;
-          }
-          {
-            const float4 rr = pre_r[j][it];
-            v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w;
-          }
-          v.x = apply_act(v.x, p.act); v.y = apply_act(v.y, p.act);
-          v.z = apply_act(v.z, p.act); v.w = apply_act(v.w, p.act);
-          *reinterpret_cast<float4*>(p.out + orow * p.ldo + colbase) = v;
+          conv_finish4<true>(v, pre_b[j], pre_r[j][it], p.act, p.out + orow * p.ldo + colbase, [&](const float4& t) {
+            if (p.gn_partial) gn_accum4(t, gs[j], gq[j]);
+          });
         } else {
           const float vals[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int col = colbase + e;
-            if (col < p.cout) {
-              float t = vals[e];
-              if (p.bias) t += p.bias[col];
-              if (p.gn_partial) {      // (a residual or bias that is not 16-byte addressable takes this branch with the statistics requested)
-                gs[j][e] += t;
-                gq[j][e] += t * t;
-              }
-              if (p.residual) t += p.residual[orow * p.ldr + col];
-              p.out[orow * p.ldo + col] = apply_act(t, p.act);
-            }
-          }
+          for (int e = 0; e < 4; ++e)
+            if (colbase + e < p.cout)
+              conv_finish1(p, vals[e], orow, colbase + e, [&](float t) {
+                if (p.gn_partial) {      // (a residual or bias that is not 16-byte addressable takes this branch with the statistics requested)
+                  gs[j][e] += t;
+                  gq[j][e] += t * t;
+                }
+              });
         }
       }
     }
   }
 
   if (p.gn_partial) {
-    // per-tile GroupNorm partial sums: lanes with equal c4 hold the same 4 columns
+    // per-tile GroupNorm partial sums (gn_pixels % BM == 0: one sample per tile)
     __syncthreads();
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float s = gs[j][e], q = gq[j][e];
-#pragma unroll
-        for (int m = 8; m <= 32; m <<= 1) {
-          s += __shfl_xor(s, m);
-          q += __shfl_xor(q, m);
-        }
-        if (lane < 8) {
-          const int col = wn * WN + 32 * j + 4 * c4 + e;
-          s_gn[0][wm][col] = s;
-          s_gn[1][wm][col] = q;
-        }
-      }
-    __syncthreads();
-    const int cg = p.cout / p.gn_groups;              // channels per group
-    const int gpt = BN / cg;                          // groups covered by this N tile (BN % cg == 0)
-    if (tid < gpt && n0 + tid * cg < p.cout) {
-      float s = 0.f, q = 0.f;
-      for (int c = 0; c < cg; ++c) {
-        s += s_gn[0][0][tid * cg + c] + s_gn[0][1][tid * cg + c];
-        q += s_gn[1][0][tid * cg + c] + s_gn[1][1][tid * cg + c];
-      }
-      const int64_t tile = m0 / BM;                   // gn_pixels % BM == 0: one sample per tile
-      float* dst = p.gn_partial + (tile * p.gn_groups + (n0 / cg + tid)) * 2;
-      dst[0] = s;
-      dst[1] = q;
-    }
+    gn_fold_tile<2, TN, BN>(p, gs, gq, s_gn, wm, wn * WN, n0, m0 / BM);
   }
 }
 
@@ -564,8 +512,7 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(lfdm_conv_param
     const int img = m / hqwq;
     const int rem = m - img * hqwq;
     const int qy = rem / p.wq, qx = rem - qy * p.wq;
-    const int64_t orow = ((int64_t)img * p.ho + qy * p.out_scale + p.out_off_y) * p.wo +
-                         qx * p.out_scale + p.out_off_x;
+    const int64_t orow = conv_out_row(p, img, qy, qx);
     float vals[4] = {s.x, s.y, s.z, s.w};
     if (p.ln_wsum) {                                 // fused channel LayerNorm: y = rstd * (x.W' - mean * sum_c W')
       const float* st = p.partial + (int64_t)p.ksplit * zs + (int64_t)m * 2;
@@ -583,37 +530,14 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(lfdm_conv_param
       for (int e = 0; e < 4; ++e) vals[e] = rs * (vals[e] - mean * (col + e < p.coutp ? p.ln_wsum[col + e] : 0.f));
     }
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int c = col + e;
-      if (c < p.cout) {
-        float v = vals[e];
-        if (p.bias) v += p.bias[c];
-        gs += v;
-        gq += v * v;
-        if (p.residual) v += p.residual[orow * p.ldr + c];
-        p.out[orow * p.ldo + c] = apply_act(v, p.act);
-      }
-    }
+    for (int e = 0; e < 4; ++e)
+      if (col + e < p.cout)
+        conv_finish1(p, vals[e], orow, col + e, [&](float t) {
+          gs += t;
+          gq += t * t;
+        });
   }
-  if (p.gn_partial) {
-    red_s[tid] = gs;
-    red_q[tid] = gq;
-    __syncthreads();
-    const int cg4 = (p.cout / p.gn_groups) / 4;      // float4 columns per group
-    const int gpb = cw / cg4;                        // groups owned by this block (cw % cg4 == 0)
-    if (tid < gpb) {
-      float ts = 0.f, tq = 0.f;
-      // thread t touched local column quad t % cw (256 % cw == 0): local group tid owns [tid*cg4, +cg4)
-      for (int rep = 0; rep < 256; rep += cw)
-        for (int k = 0; k < cg4; ++k) {
-          ts += red_s[rep + tid * cg4 + k];
-          tq += red_q[rep + tid * cg4 + k];
-        }
-      float* dst = p.gn_partial + ((int64_t)blockIdx.x * p.gn_groups + cq0 / cg4 + tid) * 2;
-      dst[0] = ts;
-      dst[1] = tq;
-    }
-  }
+  if (p.gn_partial) splitk_gn_tail(p, red_s, red_q, gs, gq, cw, cq0);
 }
 
 // The same pass for the shapes the sampler produces (round 4): KS slabs known at compile time, all KS 16-byte loads of an item in flight
@@ -647,31 +571,12 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_vec_kernel(lfdm_conv_p
     float4 s = v[0];
 #pragma unroll
     for (int z = 1; z < KS; ++z) { s.x += v[z].x; s.y += v[z].y; s.z += v[z].z; s.w += v[z].w; }
-    s.x += bb.x; s.y += bb.y; s.z += bb.z; s.w += bb.w;
-    gs += (s.x + s.y) + (s.z + s.w);
-    gq += (s.x * s.x + s.y * s.y) + (s.z * s.z + s.w * s.w);
-    s.x = apply_act(s.x + rr.x, p.act); s.y = apply_act(s.y + rr.y, p.act);
-    s.z = apply_act(s.z + rr.z, p.act); s.w = apply_act(s.w + rr.w, p.act);
-    *reinterpret_cast<float4*>(p.out + (int64_t)m * p.ldo + col) = s;
+    conv_finish4<true>(s, bb, rr, p.act, p.out + (int64_t)m * p.ldo + col, [&](const float4& t) {      // (one accumulator per thread, not per column)
+      gs += (t.x + t.y) + (t.z + t.w);
+      gq += (t.x * t.x + t.y * t.y) + (t.z * t.z + t.w * t.w);
+    });
   }
-  if (p.gn_partial) {
-    red_s[tid] = gs;
-    red_q[tid] = gq;
-    __syncthreads();
-    const int cg4 = (p.cout / p.gn_groups) / 4;
-    const int gpb = cw / cg4;
-    if (tid < gpb) {
-      float ts = 0.f, tq = 0.f;
-      for (int rep = 0; rep < 256; rep += cw)
-        for (int k = 0; k < cg4; ++k) {
-          ts += red_s[rep + tid * cg4 + k];
-          tq += red_q[rep + tid * cg4 + k];
-        }
-      float* dst = p.gn_partial + ((int64_t)blockIdx.x * p.gn_groups + cq0 / cg4 + tid) * 2;
-      dst[0] = ts;
-      dst[1] = tq;
-    }
-  }
+  if (p.gn_partial) splitk_gn_tail(p, red_s, red_q, gs, gq, cw, cq0);
 }
 
 // column chunks for the reduce grid: enough workgroups to cover the chip, chunks of >= 16 float4 that
@@ -760,9 +665,7 @@ ConvPlan make_plan(const lfdm_conv_params& p) {
   const int64_t in_rows = (int64_t)p.n_img * p.hi * p.wi;
   const bool fits32 = in_rows * p.ld0 * 4 < (1ll << 32) - 64 && in_rows * (p.c1 ? p.ld1 : 1) * 4 < (1ll << 32) - 64 &&
                       (int64_t)nchunks * p.coutp * 128 < (1ll << 32) - 64;      // buffer descriptors: 32-bit offsets
-  const bool vec_ok = (p.cout % 4 == 0) && (p.ldo % 4 == 0) && ((((uintptr_t)p.out) & 15) == 0) &&
-                      (!p.residual || ((p.ldr % 4 == 0) && ((((uintptr_t)p.residual) & 15) == 0))) &&
-                      (!p.bias || (((uintptr_t)p.bias) & 15) == 0);
+  const bool vec_ok = (p.cout % 4 == 0) && conv_epilogue_vec4_ok(p);
   pl.simple = pl.simple && fits32;      // the mask/buffer-descriptor path uses 32-bit byte offsets
   bool ksw = pl.fast && pl.simple && nchunks >= 8 && M >= 160 && !p.ln_wsum && fits32 && vec_ok;
   if (conv_force() == 0) ksw = false;
@@ -915,11 +818,7 @@ ConvPlan make_plan(const lfdm_conv_params& p) {
 // in-launch reduction (advisor, round 5: ticket words handed in for a launch the fused path then refuses bought extra slabs and a reduce launch).
 bool wino_fuse_geometry_ok(const lfdm_conv_params& p, int bn) {
   static const bool on = [] { const char* e = getenv("LFDM_WINO_FUSE_REDUCE"); return !(e && e[0] == '0'); }();      // (A/B and bit-compare switch: tests)
-  if (!on || !p.tile_counters || p.deconv4 || bn != 32 || p.groups > 1 || p.pool2 || p.cout != p.coutp || p.ldo % 4 != 0 ||
-      (((uintptr_t)p.out) & 15) != 0 ||
-      (p.bias && (((uintptr_t)p.bias) & 15) != 0) ||
-      (p.residual && (p.ldr % 4 != 0 || (((uintptr_t)p.residual) & 15) != 0)))
-    return false;
+  if (!on || !p.tile_counters || p.deconv4 || bn != 32 || p.groups > 1 || p.pool2 || p.cout != p.coutp || !conv_epilogue_vec4_ok(p)) return false;
   const int64_t ntiles = (int64_t)p.n_img * (p.hq / 2) * (p.wq / 2);
   return (int64_t)p.tile_counters_len >= ((ntiles + 31) / 32) * (p.coutp / 32);
 }
@@ -940,9 +839,8 @@ int wino_balance(const ConvPlan& pl, const lfdm_conv_params& p, int* extra_slabs
   if (extra_slabs) *extra_slabs = 0;
   static const bool on = [] { const char* e = getenv("LFDM_WINO_BALANCE"); return !(e && e[0] == '0'); }();      // (A/B and bit-compare switch)
   static const bool fuse_on = [] { const char* e = getenv("LFDM_WINO_FUSE_REDUCE"); return !(e && e[0] == '0'); }();
-  if (!on || !fuse_on || pl.kind != 2 || pl.bn != 32 || !p.tile_counters || p.deconv4 || p.groups > 1 || p.pool2 || p.cout != p.coutp || p.ldo % 4 != 0 ||
-      (((uintptr_t)p.out) & 15) != 0 || (p.bias && (((uintptr_t)p.bias) & 15) != 0) ||
-      (p.residual && (p.ldr % 4 != 0 || (((uintptr_t)p.residual) & 15) != 0)))
+  if (!on || !fuse_on || pl.kind != 2 || pl.bn != 32 || !p.tile_counters || p.deconv4 || p.groups > 1 || p.pool2 || p.cout != p.coutp ||
+      !conv_epilogue_vec4_ok(p))
     return 0;
   if (pl.ksplit > 1 && !splitk_fused(pl, p)) return 0;
   const int64_t ntiles = (int64_t)p.n_img * (p.hq / 2) * (p.wq / 2);
@@ -1071,8 +969,7 @@ int conv2d_run(const lfdm_conv_params* pp, const void* wino_bf16, hipStream_t st
   }
   if (p.ln_wsum) {
     if (!pl.fast || !pl.simple || p.kh != 1 || p.kw != 1 || p.c1 != 0 || p.stride != 1 || p.cout % 4 != 0 ||
-        p.ldo % 4 != 0 || (((uintptr_t)p.out) & 15) != 0 || (((uintptr_t)p.ln_wsum) & 15) != 0 ||
-        (p.residual && (p.ldr % 4 != 0 || (((uintptr_t)p.residual) & 15) != 0)) || (p.bias && (((uintptr_t)p.bias) & 15) != 0)) {      // (float4 epilogue only)
+        (((uintptr_t)p.ln_wsum) & 15) != 0 || !conv_epilogue_vec4_ok(p)) {      // (float4 epilogue only)
       lfdm_set_error("conv2d: fused LayerNorm needs a 1x1 convolution over one source with C % 32 == 0 and 16-byte addressable out / residual / bias");
       return LFDM_EINVAL;
     }
@@ -1099,10 +996,8 @@ int conv2d_run(const lfdm_conv_params* pp, const void* wino_bf16, hipStream_t st
   if (p.ksplit > 1 && !splitk_fused(pl, p)) {
     const dim3 rgrid((unsigned)((M + SPLITK_ROWS - 1) / SPLITK_ROWS), (unsigned)splitk_col_chunks(p, M), p.deconv4 ? 4 : 1);
     static const bool vec_on = [] { const char* e = lfdm_knob("LFDM_REDUCE_VEC"); return !(e && e[0] == '0'); }();      // (A/B knob)
-    const bool vec = vec_on && p.ksplit <= 8 && !p.deconv4 && !p.ln_wsum && p.cout == p.coutp && p.ldo % 4 == 0 && (((uintptr_t)p.out) & 15) == 0 &&
-                     p.out_scale == 1 && p.out_off_y == 0 && p.out_off_x == 0 && p.ho == p.hq && p.wo == p.wq &&
-                     (!p.bias || (((uintptr_t)p.bias) & 15) == 0) && (!p.residual || (p.ldr % 4 == 0 && (((uintptr_t)p.residual) & 15) == 0)) &&
-                     (((uintptr_t)p.partial) & 15) == 0;
+    const bool vec = vec_on && p.ksplit <= 8 && !p.deconv4 && !p.ln_wsum && p.cout == p.coutp && conv_epilogue_vec4_ok(p) &&
+                     p.out_scale == 1 && p.out_off_y == 0 && p.out_off_x == 0 && p.ho == p.hq && p.wo == p.wq && (((uintptr_t)p.partial) & 15) == 0;
     if (vec) {
       switch (p.ksplit) {
         case 2: LFDM_LAUNCH(conv_splitk_reduce_vec_kernel<2>, rgrid, dim3(256), 0, stream, p); break;

@@ -12,8 +12,7 @@
 // (LDS double buffer).  The four partial tiles are summed through LDS once at the end, which also
 // gives every thread a float4 of one output row -> coalesced epilogue with bias / residual /
 // activation / GroupNorm partial sums, or a split-K partial write.
-#include "lfdm_device.h"
-#include "../../include/lfdm_hip.h"
+#include "conv_core.h"
 
 namespace {
 
@@ -228,9 +227,7 @@ __global__ __launch_bounds__(256) void conv_ksw_kernel(lfdm_conv_params p) {
   }
   auto out_row = [&](int i) -> int64_t {
     const int row = 32 * i + trow;
-    const int oy = s_qy[row] * p.out_scale + p.out_off_y;
-    const int ox = s_qx[row] * p.out_scale + p.out_off_x;
-    return ((int64_t)s_img[row] * p.ho + oy) * p.wo + ox;
+    return conv_out_row(p, s_img[row], s_qy[row], s_qx[row]);
   };
   auto load_res = [&](int i, int j) -> float4 {
     const int colbase = n0 + 32 * j + 4 * c4;
@@ -267,6 +264,7 @@ __global__ __launch_bounds__(256) void conv_ksw_kernel(lfdm_conv_params p) {
             *reinterpret_cast<float4*>(p.partial + ((int64_t)blockIdx.z * M + (m0 + row)) * p.coutp + colbase) = v;
           }
         } else if (colbase < p.cout) {
+          // (written out, not conv_finish4: through the helper the 160x64 instantiations grow by 0.5 - 0.6 KB of code and measured slower - DESIGN.md section 3)
           const int64_t orow = out_row(i);
           v.x += bias4[j].x; v.y += bias4[j].y; v.z += bias4[j].z; v.w += bias4[j].w;
           if (p.gn_partial) {
@@ -296,38 +294,7 @@ __global__ __launch_bounds__(256) void conv_ksw_kernel(lfdm_conv_params p) {
     for (int i = 0; i < 5; ++i) dst[i] = tstamp[i];
   }
 #endif
-  if (p.gn_partial && ksplit == 1) {
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float s = gs[j][e], q = gq[j][e];
-#pragma unroll
-        for (int m = 8; m <= 32; m <<= 1) {
-          s += __shfl_xor(s, m);
-          q += __shfl_xor(q, m);
-        }
-        if (lane < 8) {
-          s_gn[0][wave][32 * j + 4 * c4 + e] = s;
-          s_gn[1][wave][32 * j + 4 * c4 + e] = q;
-        }
-      }
-    __syncthreads();
-    const int cg = p.cout / p.gn_groups;
-    const int gpt = BN / cg;
-    if (tid < gpt && n0 + tid * cg < p.cout) {
-      float s = 0.f, q = 0.f;
-      for (int c = 0; c < cg; ++c)
-        for (int w = 0; w < 4; ++w) {
-          s += s_gn[0][w][tid * cg + c];
-          q += s_gn[1][w][tid * cg + c];
-        }
-      const int64_t tile = m0 / BM;
-      float* dst = p.gn_partial + (tile * p.gn_groups + (n0 / cg + tid)) * 2;
-      dst[0] = s;
-      dst[1] = q;
-    }
-  }
+  if (p.gn_partial && ksplit == 1) gn_fold_tile<4, TN, BN>(p, gs, gq, s_gn, wave, 0, n0, m0 / BM);
 }
 
 }  // namespace

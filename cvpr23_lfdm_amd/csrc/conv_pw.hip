@@ -14,8 +14,7 @@
 // Workgroups are dealt so that the column tiles of one row tile share an XCD (x is read into ONE L2).
 #include <stdlib.h>
 
-#include "lfdm_device.h"
-#include "../../include/lfdm_hip.h"
+#include "conv_core.h"
 
 namespace {
 
@@ -117,51 +116,18 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(lfdm_conv_params p, int gx
   fetch(0);
   if (p.res_gn_partial) {
     // (round 6) the residual is a RAW convolution output: its GroupNorm + SiLU is applied in the epilogue.  Statistics of this row tile's sample,
-    // merged as gn_apply_kernel does (32 lanes walk one group's chunks, k ascending, double) while the first operand group is in flight; only the
-    // groups that cover this workgroup's columns are merged.
+    // merged by gn_apply_kernel's own walk (gn_stats.h) while the first operand group is in flight; only the groups that cover this workgroup's
+    // columns are merged.
     const int groups = p.res_gn_groups, nchunk = p.res_gn_nchunk, cg = p.cout / groups;
     const int b = m0 / p.res_gn_pixels;
     const int g_lo = n0 / cg;
     const int g_hi = (((n0 + BN < p.cout ? n0 + BN : p.cout) - 1) / cg);
-    const int sub = tid & 31;
     // (this thread's gamma / beta of the first 256 columns are requested before the merge, not behind its barrier; a 384-column
     // tile (TN = 3, KW = 1) fills its remaining columns after it)
     const int pcol = n0 + tid;
     const bool pcol_ok = tid < BN && pcol < p.cout;
     const float pre_gamma = p.res_gn_gamma[pcol_ok ? pcol : 0], pre_beta = p.res_gn_beta[pcol_ok ? pcol : 0];
-    for (int g0 = g_lo; g0 <= g_hi; g0 += 8) {
-      const int g = g0 + (tid >> 5);
-      double sm = 0.0, sq = 0.0;
-      if (g <= g_hi) {
-        const float2* src = reinterpret_cast<const float2*>(p.res_gn_partial) + ((int64_t)b * nchunk) * groups + g;
-        int k = sub;
-        for (; k + 96 < nchunk; k += 128) {
-          const float2 v0 = src[(int64_t)k * groups], v1 = src[(int64_t)(k + 32) * groups];
-          const float2 v2 = src[(int64_t)(k + 64) * groups], v3 = src[(int64_t)(k + 96) * groups];
-          sm += (double)v0.x; sq += (double)v0.y;
-          sm += (double)v1.x; sq += (double)v1.y;
-          sm += (double)v2.x; sq += (double)v2.y;
-          sm += (double)v3.x; sq += (double)v3.y;
-        }
-        for (; k < nchunk; k += 32) {
-          const float2 v = src[(int64_t)k * groups];
-          sm += (double)v.x;
-          sq += (double)v.y;
-        }
-      }
-      for (int msk = 16; msk >= 1; msk >>= 1) {
-        sm += __shfl_xor(sm, msk);
-        sq += __shfl_xor(sq, msk);
-      }
-      if (g <= g_hi && sub == 0) {
-        const double n = (double)p.res_gn_pixels * (double)cg;
-        const double mean = sm / n;
-        double var = sq / n - mean * mean;
-        if (var < 0.0) var = 0.0;
-        s_gstat[0][g - g_lo] = (float)mean;
-        s_gstat[1][g - g_lo] = (float)(1.0 / sqrt(var + (double)p.res_gn_eps));
-      }
-    }
+    gn_merge_stats<4>(p.res_gn_partial, b, nchunk, groups, g_lo, g_hi, 256, 32, (double)p.res_gn_pixels * (double)cg, p.res_gn_eps, s_gstat[0], s_gstat[1]);
     __syncthreads();
     if (pcol_ok) {
       const int g = pcol / cg - g_lo;
@@ -270,21 +236,13 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(lfdm_conv_params p, int gx
         v.x = rstd * (v.x - mean * ws.x); v.y = rstd * (v.y - mean * ws.y);
         v.z = rstd * (v.z - mean * ws.z); v.w = rstd * (v.w - mean * ws.w);
       }
-      {
-        const float4 bb = pre_b[g * TN + j];
-        float4 rr = pre_r[g * TN + j];
-        if (p.res_gn_partial) {
-          const float4 ga = *reinterpret_cast<const float4*>(s_ga + col - n0), gb = *reinterpret_cast<const float4*>(s_gb + col - n0);
-          rr.x = silu_fast_(fmaf(rr.x, ga.x, gb.x)); rr.y = silu_fast_(fmaf(rr.y, ga.y, gb.y));
-          rr.z = silu_fast_(fmaf(rr.z, ga.z, gb.z)); rr.w = silu_fast_(fmaf(rr.w, ga.w, gb.w));
-        }
-        v.x += bb.x + rr.x; v.y += bb.y + rr.y; v.z += bb.z + rr.z; v.w += bb.w + rr.w;
+      float4 rr = pre_r[g * TN + j];
+      if (p.res_gn_partial) {
+        const float4 ga = *reinterpret_cast<const float4*>(s_ga + col - n0), gb = *reinterpret_cast<const float4*>(s_gb + col - n0);
+        rr.x = silu_fast_(fmaf(rr.x, ga.x, gb.x)); rr.y = silu_fast_(fmaf(rr.y, ga.y, gb.y));
+        rr.z = silu_fast_(fmaf(rr.z, ga.z, gb.z)); rr.w = silu_fast_(fmaf(rr.w, ga.w, gb.w));
       }
-      if (p.act) {
-        v.x = apply_act(v.x, p.act); v.y = apply_act(v.y, p.act);
-        v.z = apply_act(v.z, p.act); v.w = apply_act(v.w, p.act);
-      }
-      *reinterpret_cast<float4*>(p.out + (int64_t)orow * p.ldo + col) = v;
+      conv_finish4<true, true>(v, pre_b[g * TN + j], rr, p.act, p.out + (int64_t)orow * p.ldo + col);      // v + (bias + residual): this schedule alone
     }
   }
 }

@@ -15,8 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "lfdm_device.h"
-#include "../../include/lfdm_hip.h"
+#include "conv_core.h"
 
 namespace {
 
@@ -418,15 +417,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv_wino_kernel(lfdm_co
             *reinterpret_cast<float4*>(p.partial + ((int64_t)bz * M + orow) * p.coutp + co) = y[q];
           }
         } else if (co < p.cout) {
-          float4 v = make_float4(y[q].x + bb.x, y[q].y + bb.y, y[q].z + bb.z, y[q].w + bb.w);
-          gs[ct][0] += v.x; gs[ct][1] += v.y; gs[ct][2] += v.z; gs[ct][3] += v.w;
-          gq[ct][0] += v.x * v.x; gq[ct][1] += v.y * v.y; gq[ct][2] += v.z * v.z; gq[ct][3] += v.w * v.w;
-          v.x += res[q].x; v.y += res[q].y; v.z += res[q].z; v.w += res[q].w;
-          if (ACT) {
-            v.x = apply_act(v.x, p.act); v.y = apply_act(v.y, p.act);
-            v.z = apply_act(v.z, p.act); v.w = apply_act(v.w, p.act);
-          }
-          *reinterpret_cast<float4*>(p.out + orow * p.ldo + co) = v;
+          conv_finish4<ACT>(y[q], bb, res[q], p.act, p.out + orow * p.ldo + co, [&](const float4& t) { gn_accum4(t, gs[ct], gq[ct]); });
         }
       }
     }
@@ -506,65 +497,16 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv_wino_kernel(lfdm_co
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int64_t orow = orow0 + (q >> 1) * p.wq + (q & 1);
-        float4 t = v[q];
-        t.x += bb.x; t.y += bb.y; t.z += bb.z; t.w += bb.w;
-        gs[0][0] += t.x; gs[0][1] += t.y; gs[0][2] += t.z; gs[0][3] += t.w;
-        gq[0][0] += t.x * t.x; gq[0][1] += t.y * t.y; gq[0][2] += t.z * t.z; gq[0][3] += t.w * t.w;
-        t.x = apply_act(t.x + res[q].x, p.act); t.y = apply_act(t.y + res[q].y, p.act);
-        t.z = apply_act(t.z + res[q].z, p.act); t.w = apply_act(t.w + res[q].w, p.act);
-        *reinterpret_cast<float4*>(p.out + orow * p.ldo + co) = t;
+        conv_finish4<true>(v[q], bb, res[q], p.act, p.out + orow * p.ldo + co, [&](const float4& t) { gn_accum4(t, gs[0], gq[0]); });      // (any activation at run time)
       }
     }
   }
   if (p.gn_partial && (nslab == 1 || reduced_here)) {
-    // per-channel sums over the workgroup's 32 tiles: lanes with equal e_c4 (stride 8) inside the wave, then the four waves
-#pragma unroll
-    for (int ct = 0; ct < NT; ++ct)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float sv = gs[ct][e], qv = gq[ct][e];
-#pragma unroll
-        for (int msk = 8; msk <= 32; msk <<= 1) {
-          sv += __shfl_xor(sv, msk);
-          qv += __shfl_xor(qv, msk);
-        }
-        if (lane < 8) {
-          s_gn[0][wave][WN * ct + 4 * e_c4 + e] = sv;
-          s_gn[1][wave][WN * ct + 4 * e_c4 + e] = qv;
-        }
-      }
-    __syncthreads();
-    const int cg = p.cout / p.gn_groups;
-    if (cg > WNB) {
-      // a group wider than the workgroup's columns (512 channels / 8 groups at the 4x4 level): the workgroup's sums are ONE of the
-      // cg / WNB column parts of its group and go to their own chunk slot - chunk = tile block * parts + part; the consumer merges
-      // (pixels / tile rows) * parts chunks per sample (host: lfdm_conv2d_plan's tile_rows, unet.py)
-      if (tid == 0) {
-        float sv = 0.f, qv = 0.f;
-        for (int c = 0; c < WNB; ++c)
-          for (int w4 = 0; w4 < 4; ++w4) {
-            sv += s_gn[0][w4][c];
-            qv += s_gn[1][w4][c];
-          }
-        const int parts = cg / WNB;
-        float* dst = p.gn_partial + (((int64_t)bx * parts + (n0 % cg) / WNB) * p.gn_groups + n0 / cg) * 2;
-        dst[0] = sv;
-        dst[1] = qv;
-      }
-      return;
-    }
-    const int gpt = WNB / cg;                     // groups inside this workgroup's columns (cg divides 32 or is a multiple of it: host check)
-    if (tid < gpt && n0 + tid * cg < p.cout) {
-      float sv = 0.f, qv = 0.f;
-      for (int c = 0; c < cg; ++c)
-        for (int w4 = 0; w4 < 4; ++w4) {
-          sv += s_gn[0][w4][tid * cg + c];
-          qv += s_gn[1][w4][tid * cg + c];
-        }
-      float* dst = p.gn_partial + ((int64_t)bx * p.gn_groups + (n0 / cg + tid)) * 2;
-      dst[0] = sv;
-      dst[1] = qv;
-    }
+    // per-channel sums over the workgroup's 32 tiles; a group either lies inside the workgroup's columns or spans several column tiles
+    // (cg divides 32 or is a multiple of it: host check)
+    gn_fold_lds<4, NT, WNB>(gs, gq, s_gn, wave, 0);
+    if (p.cout / p.gn_groups > WNB) gn_fold_part<4, WNB>(p, s_gn, n0, bx);
+    else gn_fold_groups<4, WNB>(p, s_gn, n0, bx);
   }
 }
 
@@ -702,22 +644,24 @@ extern "C" int lfdm_pack_wino_weights_multi_f32(const lfdm_pack_wino_job* jobs, 
 
 namespace {
 
-// the bf16-operand instantiations: every (ACT, NT, FUSE) the fp32 dispatch below can pick, not the pooled form (lfdm_conv2d_cl_wino_bf16 refuses it).
-// The layout of V in LDS is BF_VB16 (HISTORY.md: the A/B against BF_VF32); --knobs builds also carry BF_VF32 (LFDM_WINO_BF16_VF32=1).
+// The unpooled (ACT, NT, FUSE) instantiations of one operand form behind one dispatch: fp32 (BF_NONE) and the bf16 layouts - BF_VB16 is the
+// shipped one (HISTORY.md: the A/B against BF_VF32), --knobs builds also carry BF_VF32 (LFDM_WINO_BF16_VF32=1).
+// grid = (tile blocks, column tiles, ksplit); bn = 32 or 64 columns per workgroup.
 template <int BF>
-void launch_wino_bf16(const lfdm_conv_params& p, int bn, bool fuse_reduce, int bal_whole, dim3 grid, hipStream_t stream) {
-  const bool act = p.act != LFDM_ACT_NONE;
-  if (fuse_reduce) {
-    if (bal_whole > 0) {
+void launch_wino(const lfdm_conv_params& p, int bn, bool fuse_reduce, int bal_whole, dim3 grid, hipStream_t stream) {
+  if (fuse_reduce) {                      // (splitk_fused / wino_balance, conv_igemm.hip: 32-column tiles; any activation at run time)
+    if (bal_whole > 0) {                  // balanced: whole jobs first, then the two halves of each remaining job (see the kernel)
       const unsigned jobs = grid.x * grid.y * grid.z;
-      LFDM_LAUNCH((conv_wino_kernel<false, 1, false, true, BF>), dim3((unsigned)bal_whole + 2u * (jobs - (unsigned)bal_whole)), dim3(256), 0, stream, p, bal_whole);
-    } else {
-      LFDM_LAUNCH((conv_wino_kernel<false, 1, false, true, BF>), grid, dim3(256), 0, stream, p, 0);
+      grid = dim3((unsigned)bal_whole + 2u * (jobs - (unsigned)bal_whole));
     }
-  } else if (bn == 64 && act) LFDM_LAUNCH((conv_wino_kernel<true, 2, false, false, BF>), grid, dim3(256), 0, stream, p, 0);
-  else if (bn == 64) LFDM_LAUNCH((conv_wino_kernel<false, 2, false, false, BF>), grid, dim3(256), 0, stream, p, 0);
-  else if (act) LFDM_LAUNCH((conv_wino_kernel<true, 1, false, false, BF>), grid, dim3(256), 0, stream, p, 0);
-  else LFDM_LAUNCH((conv_wino_kernel<false, 1, false, false, BF>), grid, dim3(256), 0, stream, p, 0);
+    LFDM_LAUNCH((conv_wino_kernel<false, 1, false, true, BF>), grid, dim3(256), 0, stream, p, bal_whole > 0 ? bal_whole : 0);
+    return;
+  }
+  lfdm_ladder<32, 64>(bn, [&](auto rung) {
+    constexpr int NT = decltype(rung)::value / WN;
+    if (p.act != LFDM_ACT_NONE) LFDM_LAUNCH((conv_wino_kernel<true, NT, false, false, BF>), grid, dim3(256), 0, stream, p, 0);
+    else LFDM_LAUNCH((conv_wino_kernel<false, NT, false, false, BF>), grid, dim3(256), 0, stream, p, 0);
+  });
 }
 
 }  // namespace
@@ -731,10 +675,10 @@ int lfdm_conv_wino_bf16_launch(const lfdm_conv_params& p_, const void* weight_bf
   const dim3 grid((unsigned)((ntiles + WT - 1) / WT), (unsigned)((p.coutp + bn - 1) / bn), p.ksplit > 1 ? p.ksplit : 1);
 #if defined(LFDM_TUNING_KNOBS) || defined(LFDM_EMU_BUILD)
   const char* e = lfdm_knob("LFDM_WINO_BF16_VF32");      // (read per call: tools/bench_wino_bf16.py --vlds alternates the layouts in one process)
-  if (e && e[0] == '1') launch_wino_bf16<BF_VF32>(p, bn, fuse_reduce, bal_whole, grid, stream);
+  if (e && e[0] == '1') launch_wino<BF_VF32>(p, bn, fuse_reduce, bal_whole, grid, stream);
   else
 #endif
-    launch_wino_bf16<BF_VB16>(p, bn, fuse_reduce, bal_whole, grid, stream);
+    launch_wino<BF_VB16>(p, bn, fuse_reduce, bal_whole, grid, stream);
   return lfdm_check_launch("conv_wino_bf16");
 }
 
@@ -742,22 +686,11 @@ int lfdm_conv_wino_bf16_launch(const lfdm_conv_params& p_, const void* weight_bf
 int lfdm_conv_wino_launch(const lfdm_conv_params& p, int bn, bool fuse_reduce, int bal_whole, hipStream_t stream) {
   const int64_t ntiles = (int64_t)p.n_img * (p.hq / 2) * (p.wq / 2);
   const dim3 grid((unsigned)((ntiles + WT - 1) / WT), (unsigned)((p.coutp + bn - 1) / bn), p.ksplit > 1 ? p.ksplit : 1);
-  const bool act = p.act != LFDM_ACT_NONE;
-  if (fuse_reduce) {                      // (splitk_fused / wino_balance, conv_igemm.hip: 32-column tiles; any activation at run time)
-    if (bal_whole > 0) {                  // balanced: whole jobs first, then the two halves of each remaining job (see the kernel)
-      const unsigned jobs = grid.x * grid.y * grid.z;
-      LFDM_LAUNCH((conv_wino_kernel<false, 1, false, true>), dim3((unsigned)bal_whole + 2u * (jobs - (unsigned)bal_whole)), dim3(256), 0, stream, p, bal_whole);
-    } else {
-      LFDM_LAUNCH((conv_wino_kernel<false, 1, false, true>), grid, dim3(256), 0, stream, p, 0);
-    }
-    return lfdm_check_launch("conv_wino");
-  }
-  if (p.pool2 && act) {                   // (the pooled form follows an output activation in every caller: lfdm_conv2d_cl_f32 checks)
+  if (!fuse_reduce && p.pool2 && p.act != LFDM_ACT_NONE) {      // (the pooled form follows an output activation in every caller: lfdm_conv2d_cl_f32 checks; fp32 only)
     if (bn == 64) LFDM_LAUNCH((conv_wino_kernel<true, 2, true>), grid, dim3(256), 0, stream, p, 0);
     else LFDM_LAUNCH((conv_wino_kernel<true, 1, true>), grid, dim3(256), 0, stream, p, 0);
-  } else if (bn == 64 && act) LFDM_LAUNCH((conv_wino_kernel<true, 2>), grid, dim3(256), 0, stream, p, 0);
-  else if (bn == 64) LFDM_LAUNCH((conv_wino_kernel<false, 2>), grid, dim3(256), 0, stream, p, 0);
-  else if (act) LFDM_LAUNCH((conv_wino_kernel<true, 1>), grid, dim3(256), 0, stream, p, 0);
-  else LFDM_LAUNCH((conv_wino_kernel<false, 1>), grid, dim3(256), 0, stream, p, 0);
+  } else {
+    launch_wino<BF_NONE>(p, bn, fuse_reduce, bal_whole, grid, stream);
+  }
   return lfdm_check_launch("conv_wino");
 }

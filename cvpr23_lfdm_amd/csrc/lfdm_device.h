@@ -120,6 +120,14 @@ __device__ __forceinline__ void lfdm_static_for(F&& f) {
   }
 }
 
+// Host-side ladder: f(std::integral_constant<int, R>) for the first rung R >= v; the last rung takes everything above it.  A launch
+// site names its kernel and argument list once, inside f.
+template <int R, int... REST, class F>
+inline auto lfdm_ladder(int v, F&& f) {
+  if constexpr (sizeof...(REST) == 0) return f(std::integral_constant<int, R>{});
+  else return v <= R ? f(std::integral_constant<int, R>{}) : lfdm_ladder<REST...>(v, f);
+}
+
 // Buffer-descriptor loads: an out-of-range byte offset returns zeros, which turns "is this filter tap
 // inside the image" into one v_cndmask on the offset instead of a divergent branch around the load
 // (branches inside the MFMA loop also made hipcc copy all accumulator registers every iteration).

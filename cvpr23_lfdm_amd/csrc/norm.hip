@@ -7,8 +7,7 @@
 // partials in double and folds mean/rstd/gamma/beta/scale/shift into one per-(b,c) FMA ->
 // a streaming apply pass.  Reduction order is fixed (no float atomics): bit-reproducible.
 #include <stdlib.h>
-#include "lfdm_device.h"
-#include "../../include/lfdm_hip.h"
+#include "gn_stats.h"
 
 namespace {
 
@@ -124,47 +123,13 @@ __global__ __launch_bounds__(NT) void gn_apply_kernel(
   // (a coalesced float2 walk with one thread per (chunk, group) item + an LDS tree was measured: 9.2 vs 9.1 us at 320 chunks and
   // 8.0 vs 6.8 us at 32 - the extra barrier costs more than the strided loads; removed)
   // LPG lanes walk one group's chunks: a whole wavefront per group once the workgroup has 64 threads per group
-  const int lpg = (NT >= 64 * groups) ? 64 : 32;
-  const int gpp = NT / lpg;           // groups per pass
-  const int sub = tid & (lpg - 1);
-  for (int g0 = 0; g0 < groups; g0 += gpp) {
-    const int g = g0 + tid / lpg;
-    double s = 0.0, q = 0.0;
-    if (g < groups) {
-      // four chunk loads in flight per lane (round 4: the one-load-per-trip walk paid an L2 round trip per chunk - 2.4 us of the launch
-      // at 320 chunks, tools/ubench/launch_floor.py); same summation order as before: k ascending per lane.
-      // Round 6, measured and NOT kept: all of a lane's loads in flight at once (sixteen 64-bit-addressed loads: 56 -> 135 VGPRs = three
-      // waves per SIMD, +3.6 ms per video, profiles/r06_b_gn_merge_ab.txt) and eight per trip through a buffer descriptor with no single-
-      // load tail (64 VGPRs, still +1.4 ms per video, profiles/r06_c_gn_merge8_ab.txt): in situ the walk is not what the launch waits for.
-      const float2* src = reinterpret_cast<const float2*>(partial) + ((int64_t)b * nchunk) * groups + g;
-      int k = sub;
-      for (; k + 3 * lpg < nchunk; k += 4 * lpg) {
-        const float2 v0 = src[(int64_t)k * groups], v1 = src[(int64_t)(k + lpg) * groups];
-        const float2 v2 = src[(int64_t)(k + 2 * lpg) * groups], v3 = src[(int64_t)(k + 3 * lpg) * groups];
-        s += (double)v0.x; q += (double)v0.y;
-        s += (double)v1.x; q += (double)v1.y;
-        s += (double)v2.x; q += (double)v2.y;
-        s += (double)v3.x; q += (double)v3.y;
-      }
-      for (; k < nchunk; k += lpg) {
-        const float2 v = src[(int64_t)k * groups];
-        s += (double)v.x;
-        q += (double)v.y;
-      }
-    }
-    for (int m = lpg >> 1; m >= 1; m >>= 1) {
-      s += __shfl_xor(s, m);
-      q += __shfl_xor(q, m);
-    }
-    if (g < groups && sub == 0) {
-      const double n = (double)pixels * (double)(channels / groups);
-      const double mean = s / n;
-      double var = q / n - mean * mean;
-      if (var < 0.0) var = 0.0;
-      s_mean[g] = (float)mean;
-      s_rstd[g] = (float)(1.0 / sqrt(var + (double)eps));
-    }
-  }
+  // The walk (gn_stats.h) keeps four chunk loads in flight per lane (round 4: the one-load-per-trip walk paid an L2 round trip per chunk - 2.4 us
+  // of the launch at 320 chunks, tools/ubench/launch_floor.py); same summation order as before: k ascending per lane.
+  // Round 6, measured and NOT kept: all of a lane's loads in flight at once (sixteen 64-bit-addressed loads: 56 -> 135 VGPRs = three
+  // waves per SIMD, +3.6 ms per video, profiles/r06_b_gn_merge_ab.txt) and eight per trip through a buffer descriptor with no single-
+  // load tail (64 VGPRs, still +1.4 ms per video, profiles/r06_c_gn_merge8_ab.txt): in situ the walk is not what the launch waits for.
+  gn_merge_stats<4>(partial, b, nchunk, groups, 0, groups - 1, NT, (NT >= 64 * groups) ? 64 : 32, (double)pixels * (double)(channels / groups), eps,
+                    s_mean, s_rstd);
   __syncthreads();
   const int cg = channels / groups;
   {

@@ -3,8 +3,7 @@
 // small-C_in direct convolution (UNet init conv's step-dependent 3 channels, LFAE first conv) and
 // the two 1x1x1 output heads writing the planar (B,3,T,H,W) prediction.
 #include <stdlib.h>
-#include "lfdm_device.h"
-#include "../../include/lfdm_hip.h"
+#include "gn_stats.h"
 
 namespace {
 
@@ -237,43 +236,8 @@ __global__ __launch_bounds__(256) void heads_gn_kernel(const float* __restrict__
   const float pw_oc = (pi_ok && tid >= channels) ? w_occ[tid - channels] : 0.f;
   const float pe0 = tid < 3 * ce ? w_extra[tid] : 0.f, pe1 = tid + 256 < 3 * ce ? w_extra[tid + 256] : 0.f;
   const float pre_gamma = gamma[pi_ok ? tid : 0], pre_beta = beta[pi_ok ? tid : 0];
-  // ---- statistics of this sample: gn_apply_kernel's merge (32 lanes walk one group's chunks, four loads in flight, k ascending) ----
-  {
-    const int lpg = 32, gpp = 256 / lpg, sub = tid & (lpg - 1);
-    for (int g0 = 0; g0 < groups; g0 += gpp) {
-      const int g = g0 + tid / lpg;
-      double sm = 0.0, sq = 0.0;
-      if (g < groups) {
-        const float2* src = reinterpret_cast<const float2*>(partial) + ((int64_t)b * nchunk) * groups + g;
-        int k = sub;
-        for (; k + 3 * lpg < nchunk; k += 4 * lpg) {
-          const float2 v0 = src[(int64_t)k * groups], v1 = src[(int64_t)(k + lpg) * groups];
-          const float2 v2 = src[(int64_t)(k + 2 * lpg) * groups], v3 = src[(int64_t)(k + 3 * lpg) * groups];
-          sm += (double)v0.x; sq += (double)v0.y;
-          sm += (double)v1.x; sq += (double)v1.y;
-          sm += (double)v2.x; sq += (double)v2.y;
-          sm += (double)v3.x; sq += (double)v3.y;
-        }
-        for (; k < nchunk; k += lpg) {
-          const float2 v = src[(int64_t)k * groups];
-          sm += (double)v.x;
-          sq += (double)v.y;
-        }
-      }
-      for (int m = lpg >> 1; m >= 1; m >>= 1) {
-        sm += __shfl_xor(sm, m);
-        sq += __shfl_xor(sq, m);
-      }
-      if (g < groups && sub == 0) {
-        const double n = (double)pixels * (double)(c2 / groups);
-        const double mean = sm / n;
-        double var = sq / n - mean * mean;
-        if (var < 0.0) var = 0.0;
-        s_mean[g] = (float)mean;
-        s_rstd[g] = (float)(1.0 / sqrt(var + (double)eps));
-      }
-    }
-  }
+  // ---- statistics of this sample: gn_apply_kernel's merge (gn_stats.h; 32 lanes walk one group's chunks) ----
+  gn_merge_stats<4>(partial, b, nchunk, groups, 0, groups - 1, 256, 32, (double)pixels * (double)(c2 / groups), eps, s_mean, s_rstd);
   for (int i = tid; i < c2; i += 256) {                                       // head weights per y channel
     const bool pre = i == tid;
     wl[i] = pre ? pw_f0 : (i < channels ? w_flow[i] : 0.f);

@@ -13,8 +13,7 @@
 // (no float atomics), a tiny per-sample finalize, and the dx pass.  mean/rstd are re-derived from the
 // forward's (sum, sumsq) partials exactly as the forward kernel does (double merge), so forward and
 // backward see the same statistics.
-#include "lfdm_device.h"
-#include "../../include/lfdm_hip.h"
+#include "gn_stats.h"
 
 namespace {
 
@@ -28,34 +27,10 @@ __host__ __device__ inline int gnb_num_chunks(int pixels) {
   return n;
 }
 
-// group statistics from the forward partials -> s_mean / s_rstd (same arithmetic as gn_apply_kernel)
+// group statistics from the forward partials -> s_mean / s_rstd: gn_apply_kernel's merge (gn_stats.h), one chunk load per trip
 __device__ __forceinline__ void group_stats(const float* partial, int nchunk, int b, int groups, int pixels,
                                             int channels, float eps, float* s_mean, float* s_rstd) {
-  const int tid = threadIdx.x, sub = tid & 31;
-  for (int g0 = 0; g0 < groups; g0 += 8) {
-    const int g = g0 + (tid >> 5);
-    double s = 0.0, q = 0.0;
-    if (g < groups) {
-      for (int k = sub; k < nchunk; k += 32) {
-        const float* src = partial + (((int64_t)b * nchunk + k) * groups + g) * 2;
-        s += (double)src[0];
-        q += (double)src[1];
-      }
-    }
-#pragma unroll
-    for (int m = 16; m >= 1; m >>= 1) {
-      s += __shfl_xor(s, m);
-      q += __shfl_xor(q, m);
-    }
-    if (g < groups && sub == 0) {
-      const double n = (double)pixels * (double)(channels / groups);
-      const double mean = s / n;
-      double var = q / n - mean * mean;
-      if (var < 0.0) var = 0.0;
-      s_mean[g] = (float)mean;
-      s_rstd[g] = (float)(1.0 / sqrt(var + (double)eps));
-    }
-  }
+  gn_merge_stats<1>(partial, b, nchunk, groups, 0, groups - 1, 256, 32, (double)pixels * (double)(channels / groups), eps, s_mean, s_rstd);
 }
 
 __device__ __forceinline__ float dact(float z, int silu) {

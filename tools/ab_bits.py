@@ -1,0 +1,217 @@
+#!/usr/bin/env python
+"""Same bits?  Runs a fixed list of calls on seeded inputs under ONE build of the kernels and writes one line per output tensor -
+name, shape, SHA-256 of its bytes - so that two builds (a refactor and its parent commit) can be compared line by line.
+
+    tools/ab_bits.py run OUT.txt [--emu [LIB]]           this process, the library LFDM_HIP_LIB names (default: the in-tree one) on the GPU,
+                                                         or an emulator library on the CPU (default: the in-tree one)
+    tools/ab_bits.py diff A.txt B.txt                    exit status 1 when any line differs or is missing
+    tools/ab_bits.py ab BASE_LIB OUT_DIR [--emu] [--new LIB] [--timeout S]
+                                                         `run` under BASE_LIB, then under the in-tree library (or --new), each in a fresh child
+                                                         process with its own time limit, one after the other; stops at the first non-zero
+                                                         exit status; then `diff`
+
+The calls are the suite's own: the listed tests of tests/ run in-process (their case lists cannot go stale here) with every function of
+cvpr23_lfdm_amd.ops / train_ops wrapped - each tensor a call returns, and the gn_partial buffer it was handed, becomes a line.  `extra` below adds
+the few cells no test reaches.  Nothing but tensor bytes is looked at."""
+import argparse
+import hashlib
+import os
+import subprocess
+import sys
+
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# (file, -k expression): the smallest shapes that reach every epilogue / GroupNorm hand-off of the convolution family
+TESTS = [
+    ("tests/test_ops_parity.py",
+     "test_conv2d or test_deconv_one_launch or test_conv_fused_groupnorm_stats or test_conv_fused_layernorm or test_conv_pointwise or "
+     "test_conv_downsample_gather or test_winograd_pooled_epilogue or test_conv_winograd_splitk_reduced_in_launch or "
+     "test_conv_winograd_balanced_launch or test_groupnorm_apply_many_partials or test_heads_with_groupnorm_folded"),
+    ("tests/test_conv_wino_bf16.py", "test_conv2d_winograd_bf16"),
+    ("tests/test_train_ops.py", "test_groupnorm_bwd"),
+]
+DESELECT = "not gpu_only and not bigTrue and not random_geometries and not plan and not refuses and not smalln"
+
+
+class Recorder:
+    """pytest plugin: wraps the ops layer for the session, names every recorded tensor test-id#call.function#index"""
+
+    def __init__(self, out_path, emu_lib):
+        self.lines, self.out_path, self.emu_lib, self.test, self.ncall, self.depth = [], out_path, emu_lib, "setup", 0, 0
+
+    def record(self, name, t):
+        b = t.detach().cpu().contiguous().view(-1).view(dtype=__import__("torch").uint8).numpy().tobytes()
+        self.lines.append("%s %s %s" % (name, "x".join(str(d) for d in t.shape) or "scalar", hashlib.sha256(b).hexdigest()))
+
+    def wrap(self, mod):
+        import torch
+
+        def tensors(v):
+            if isinstance(v, torch.Tensor):
+                yield v
+            elif isinstance(v, (tuple, list)):
+                for e in v:
+                    yield from tensors(e)
+
+        def make(fname, f):
+            def g(*a, **kw):
+                self.depth += 1
+                try:
+                    r = f(*a, **kw)
+                finally:
+                    self.depth -= 1
+                if self.depth > 0:      # only what the caller of the ops layer sees
+                    return r
+                self.ncall += 1
+                outs = list(tensors(r)) + ([kw["gn_partial"]] if isinstance(kw.get("gn_partial"), torch.Tensor) else [])
+                for i, t in enumerate(outs):
+                    self.record("%s#%d.%s#%d" % (self.test, self.ncall, fname, i), t)
+                return r
+            g.__wrapped__ = f
+            return g
+
+        for fname, f in list(vars(mod).items()):
+            if (callable(f) and not fname.startswith("_") and getattr(f, "__module__", None) == mod.__name__ and not isinstance(f, type)
+                    and fname not in ("empty", "conv_params", "sampler_ws")):      # (uninitialised buffers, argument records)
+                setattr(mod, fname, make(fname, f))
+
+    def pytest_sessionstart(self, session):
+        sys.path.insert(0, R)
+        from cvpr23_lfdm_amd import _build, ops, train_ops
+        if self.emu_lib:
+            _build.build_emu = lambda force=False: self.emu_lib      # (the suite's `backend` fixture asks the build for the emulator library)
+        self.wrap(ops)
+        self.wrap(train_ops)
+
+    def pytest_runtest_setup(self, item):
+        self.test, self.ncall = item.nodeid.split("::", 1)[1], 0
+
+
+def extra(dev, rec):
+    """Cells no test reaches.  Same conventions as the suite (tests/util.py layouts, seeded randn)."""
+    import math
+    import torch
+    sys.path.insert(0, os.path.join(R, "tests"))
+    from cvpr23_lfdm_amd import ops
+    from util import rnd, to_cl
+
+    # 2x2-wave schedule, scalar epilogue WITH statistics: the bias pointer is offset by one float (not 16-byte addressable)
+    rec.test, rec.ncall = "extra_igemm_scalar_tail_with_gn_partial", 0
+    n, cin, cout, h, w = 2, 32, 64, 8, 8
+    x, wt = rnd(n, cin, h, w, seed=1), rnd(cout, cin, 3, 3, seed=2, scale=1.0 / math.sqrt(cin * 9))
+    bias = torch.zeros(cout + 1, device=dev)
+    bias[1:] = rnd(cout, seed=3).to(dev)
+    xs, wd = to_cl(x).to(dev), ops.pack_conv_weight(wt).to(dev)
+    pp, _ = ops.conv_params(xs, wd, cout, 3, 3, n, h, w, bias=bias[1:], ksplit=1)
+    assert ops.conv_schedule(pp) == 0, "the 2x2-wave schedule was not selected"
+    rows, _ = ops.conv_plan(pp)
+    partial = torch.zeros(n * (h * w // rows), 16, device=dev)
+    ops.conv2d_cl(xs, wd, cout, 3, 3, n, h, w, bias=bias[1:], ksplit=1, gn_partial=partial, gn_groups=8, gn_pixels=h * w)
+
+    # Winograd, a group wider than the workgroup's columns: 512 channels in 8 groups at 4x4 (32-column workgroups: two part slots per group)
+    for bn in ("32", "64"):
+        rec.test, rec.ncall = "extra_wino_group_spans_column_tiles_bn" + bn, 0
+        os.environ.update(LFDM_WINO="1", LFDM_WINO_BN=bn)
+        n, cin, cout, h, w = 16, 32, 512, 4, 4
+        x, wt = rnd(n, cin, h, w, seed=1), rnd(cout, cin, 3, 3, seed=2, scale=1.0 / math.sqrt(cin * 9))
+        xs, wd, ww = to_cl(x).to(dev), ops.pack_conv_weight(wt).to(dev), ops.pack_wino_weight(wt.to(dev))
+        kw = dict(bias=rnd(cout, seed=3).to(dev), weight_wino=ww, ksplit=1)
+        pp, _ = ops.conv_params(xs, wd, cout, 3, 3, n, h, w, **kw)
+        assert ops.conv_schedule(pp) == 2, "the Winograd schedule was not selected"
+        pixels = n // 2 * h * w                                            # two samples of 128 pixels = one tile block each
+        partial = torch.zeros(2 * (pixels // 128) * 2, 16, device=dev)     # (room for two column parts per group)
+        ops.conv2d_cl(xs, wd, cout, 3, 3, n, h, w, gn_partial=partial, gn_groups=8, gn_pixels=pixels, **kw)
+
+
+def run(out_path, emu):
+    import pytest
+    emu_lib = None
+    if emu is not None:
+        emu_lib = os.path.abspath(emu) if emu else os.path.join(R, "tests", "emu", "liblfdm_emu.so")
+    rec = Recorder(out_path, emu_lib)
+    os.chdir(R)
+    # (the F(2x2) Winograd cases run at both workgroup widths: LFDM_WINO_BN is a parameter of the suite's own tests)
+    args = ["-q", "-p", "no:cacheprovider", "-x", "-m", "emu" if emu is not None else "gpu"]
+    kexpr = "(" + " or ".join("(%s)" % k for _, k in TESTS) + ") and " + DESELECT
+    rc = pytest.main(args + [f for f, _ in TESTS] + ["-k", kexpr], plugins=[rec])
+    if rc != 0:
+        return int(rc)
+    # extra cells: drive the same wrapped ops under the same library
+    import torch
+    from cvpr23_lfdm_amd import _native
+    if emu_lib:
+        _native._set_library_for_tests(_native.NativeLibrary(emu_lib, "emu"))
+    dev = "cpu" if emu_lib else "cuda"
+    extra(dev, rec)
+    if dev == "cuda":
+        torch.cuda.synchronize()
+    with open(out_path, "w") as fh:
+        fh.write("\n".join(rec.lines) + "\n")
+    print("%d tensors -> %s" % (len(rec.lines), out_path))
+    return 0
+
+
+def diff(a, b):
+    def load(p):
+        d = {}
+        for line in open(p):
+            if line.strip():
+                name, shape, h = line.rsplit(None, 2)
+                d[name] = (shape, h)
+        return d
+    A, B = load(a), load(b)
+    bad = 0
+    for name in sorted(set(A) | set(B)):
+        if A.get(name) != B.get(name):
+            bad += 1
+            print("DIFFERS %s: %s | %s" % (name, A.get(name, "missing"), B.get(name, "missing")))
+    print("%d tensors compared, %d not bit-equal" % (len(set(A) | set(B)), bad))
+    return 1 if bad else 0
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    sub = ap.add_subparsers(dest="mode", required=True)
+    r = sub.add_parser("run")
+    r.add_argument("out")
+    r.add_argument("--emu", nargs="?", const="", default=None)
+    d = sub.add_parser("diff")
+    d.add_argument("a")
+    d.add_argument("b")
+    c = sub.add_parser("ab")
+    c.add_argument("base")
+    c.add_argument("out_dir")
+    c.add_argument("--new", default=None)
+    c.add_argument("--emu", action="store_true")
+    c.add_argument("--timeout", type=int, default=240)
+    a = ap.parse_args()
+    if a.mode == "run":
+        return run(a.out, a.emu)
+    if a.mode == "diff":
+        return diff(a.a, a.b)
+    os.makedirs(a.out_dir, exist_ok=True)
+    outs = []
+    for tag, lib in (("base", os.path.abspath(a.base)), ("new", os.path.abspath(a.new) if a.new else None)):
+        out = os.path.join(a.out_dir, "bits_%s%s.txt" % ("emu_" if a.emu else "", tag))
+        env = dict(os.environ)
+        cmd = [sys.executable, os.path.abspath(__file__), "run", out]
+        if a.emu:
+            cmd += ["--emu"] + ([lib] if lib else [])
+        elif lib:
+            env["LFDM_HIP_LIB"] = lib
+        else:
+            env.pop("LFDM_HIP_LIB", None)
+        try:
+            rc = subprocess.run(cmd, env=env, cwd=R, timeout=a.timeout).returncode
+        except subprocess.TimeoutExpired:
+            print("%s: time limit of %d s" % (tag, a.timeout))
+            return 124
+        if rc != 0:
+            print("%s: exit status %d" % (tag, rc))
+            return rc
+        outs.append(out)
+    return diff(*outs)
+
+
+if __name__ == "__main__":
+    sys.exit(main())
