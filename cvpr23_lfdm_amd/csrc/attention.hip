@@ -26,7 +26,7 @@ namespace {
 //  * the scores are computed transposed (S^T = K Q^T), which makes the softmax a register reduction + two shuffles and
 //    leaves P^T directly in the A-operand layout of P V: NO LDS and no barrier anywhere in the kernel (attn_core.h attend_store).
 // The first version staged Q, K, V and P in LDS (20 KB per wave, 8 waves per CU, 60 % of the wave cycles in s_waitcnt).
-template <int LP>
+template <int LP, bool PIPE>
 __global__ __launch_bounds__(64) void attention_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                        int frames, int hw, int mode, const float* __restrict__ bias,
                                                        const float* __restrict__ rot_cos,
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(64) void attention_kernel(const float* __restrict__
     }
   }
   const bool bias_vec = bias && (L % 4 == 0) && ((((uintptr_t)bias) & 15) == 0);
-  attend_store<NT, true>(qf, kf, vf, head, L, l15, lq, bias, bias_vec, out, row0, tstride);
+  attend_store<NT, true, PIPE>(qf, kf, vf, head, L, l15, lq, bias, bias_vec, out, row0, tstride);
 }
 
 // ---------------- linear attention ----------------
@@ -265,7 +265,12 @@ extern "C" int lfdm_attention_cl_f32(const float* qkv, float* out, int batch, in
   const int64_t units = nseq * HEADS;
   const dim3 grid((unsigned)units), block(64);
   lp_ladder(L, [&](auto lp) {
-    LFDM_LAUNCH((attention_kernel<decltype(lp)::value>), grid, block, 0, stream, qkv, out, frames, hw, mode, bias, rot_cos, rot_sin);
+    constexpr int LP = decltype(lp)::value;
+    constexpr bool CAN_PIPE = LP != 32;      // (at 32 the pipelined order takes 82 registers instead of 80: five waves per SIMD instead of six)
+    if (CAN_PIPE && bias_by_quads(bias, L))
+      LFDM_LAUNCH((attention_kernel<LP, CAN_PIPE>), grid, block, 0, stream, qkv, out, frames, hw, mode, bias, rot_cos, rot_sin);
+    else
+      LFDM_LAUNCH((attention_kernel<LP, false>), grid, block, 0, stream, qkv, out, frames, hw, mode, bias, rot_cos, rot_sin);
   });
   return lfdm_check_launch("attention");
 }

@@ -27,17 +27,46 @@
 
 namespace {
 
-// The body of one wavefront: heads [head_begin, head_begin + heads_per_block) of sequence `seq`; results to global `out` or to `o_lds`.
+// Probe build (-DLFDM_TATTN_STAMP, tools/probe_tattn_phases.py; =2: every launch on the whole order of attend_store): the waves of
+// temporal_attn_fused_out_kernel add up s_memtime cycles per phase and leave them in the buffer lfdm_tattn_stamp_buffer names.  A stamp
+// is fenced on both sides, so the phases of a probe build do not overlap as the library's do: read its shares, not its length.
+#ifdef LFDM_TATTN_STAMP
+struct CycleProbe {
+  long long t, acc[8];
+  __device__ __forceinline__ void start() {
+    for (int i = 0; i < 8; ++i) acc[i] = 0;
+    t = clock64();
+  }
+  __device__ __forceinline__ void lap(int i) {
+    LFDM_SCHED_FENCE();
+    const long long now = clock64();
+    acc[i] += now - t;
+    t = now;
+    LFDM_SCHED_FENCE();
+  }
+};
+long long* tattn_stamps = nullptr;
+#define TATTN_STAMP_PARAM , long long* stamps
+#define TATTN_STAMP_ARG , tattn_stamps
+#else
+#define TATTN_STAMP_PARAM
+#define TATTN_STAMP_ARG
+#endif
+
+// The body of one wavefront: heads [head_begin, head_begin + heads_per_block) of sequence `seq`; results to the global rows `out` or,
+// with TO_LDS, to the workgroup's LDS tile `out`.
 // ROT_RELOAD: the rotary factors are re-read from their (L1-resident, 2.5 KB) tables per head instead of living in 24 registers across the
 // head loop - the one-launch block needs the registers (27 spills otherwise).
 // WPACK: wqkv is in MFMA-operand order [q|k|v][head][feature half][quad q][lane][4] (lane (l15, lq) <- W[row 16*half + l15][C/4*lq + 4q ..]):
 // every fragment load instruction then reads ONE contiguous 1 KB instead of a 16-byte piece of each of its 64 lanes' 64-byte segments
 // (four times the L1 line look-ups per byte in the row-major layout).
-template <int LP, int C, bool ROT_RELOAD = false, bool WPACK = false>
+// PIPE: the pipelined order of attend_store (attn_core.h).  TO_LDS: `out` is the workgroup's LDS tile.
+// probe: lap(4) closes the prologue, lap(0) a head's projections, attend_store the rest.
+template <int LP, int C, bool ROT_RELOAD = false, bool WPACK = false, bool PIPE = false, bool TO_LDS = false, class PROBE = NoProbe>
 __device__ __forceinline__ void tattn_heads(const float* __restrict__ x, int ldx, int head_begin, int heads_per_block,
                                             const float* __restrict__ wqkv, float* __restrict__ out, int frames, int hw, int64_t seq,
                                             const float* __restrict__ bias, const float* __restrict__ rot_cos,
-                                            const float* __restrict__ rot_sin, float eps, float* o_lds) {
+                                            const float* __restrict__ rot_sin, float eps, PROBE&& probe = NoProbe{}) {
   constexpr int NT = LP / 16;
   constexpr int CQ = C / 4;                        // channels per k-slot
 
@@ -90,6 +119,7 @@ __device__ __forceinline__ void tattn_heads(const float* __restrict__ x, int ldx
     }
   }
   const bool bias_vec = bias && (L % 4 == 0) && ((((uintptr_t)bias) & 15) == 0);
+  probe.lap(4);
 
 #pragma unroll 1
   for (int head = head_begin; head < head_begin + heads_per_block; ++head) {
@@ -183,11 +213,12 @@ __device__ __forceinline__ void tattn_heads(const float* __restrict__ x, int ldx
       }
     }
 
-    attend_store<NT, false>(qf, kf, vf, head, L, l15, lq, bias, bias_vec, out, row0, hw, o_lds);
+    probe.lap(0);
+    attend_store<NT, false, PIPE, TO_LDS>(qf, kf, vf, head, L, l15, lq, bias, bias_vec, out, row0, hw, probe);
   }
 }
 
-template <int LP, int C>
+template <int LP, int C, bool PIPE>
 __global__ __launch_bounds__(64, 2) void temporal_attn_fused_kernel(const float* __restrict__ x, int ldx, int heads_per_block,
                                                                  const float* __restrict__ wqkv,   // (768, C), gamma folded
                                                                  float* __restrict__ out, int frames, int hw,
@@ -195,7 +226,7 @@ __global__ __launch_bounds__(64, 2) void temporal_attn_fused_kernel(const float*
                                                                  const float* __restrict__ rot_cos,
                                                                  const float* __restrict__ rot_sin, float eps) {
   // grid.y splits the 8 heads over workgroups when there are few sequences (x is re-read per workgroup: 10-20 KB)
-  tattn_heads<LP, C>(x, ldx, blockIdx.y * heads_per_block, heads_per_block, wqkv, out, frames, hw, blockIdx.x, bias, rot_cos, rot_sin, eps, nullptr);
+  tattn_heads<LP, C, false, false, PIPE>(x, ldx, blockIdx.y * heads_per_block, heads_per_block, wqkv, out, frames, hw, blockIdx.x, bias, rot_cos, rot_sin, eps);
 }
 
 // ... + to_out + residual in the same launch (round 4; lfdm_temporal_attention_fused_out_cl_f32): Residual(PreNorm(Attention)) complete,
@@ -208,20 +239,28 @@ __global__ __launch_bounds__(64, 2) void temporal_attn_fused_kernel(const float*
 // four k-steps: k-slot lq of step (S, j) takes k = 16 S + 4 lq + j for BOTH operands), B = Wout straight from L2 in the same order.
 // Both weight tensors arrive PACKED in operand order (ops.pack_tattn_weights): wqkv [3][8][2][4][64 lanes][4], wout [4 ct][16 S][64 lanes][4].
 // LROWS = rows of the LDS tile (>= frames): 40 for the 40-frame videos (40 KB: four workgroups per CU), LP otherwise.
-template <int LP, int LROWS, int NW>
+// PIPE: the pipelined attention core (attn_core.h attend_tiles); the launcher asks for it only with a bias that is read by quads.
+template <int LP, int LROWS, int NW, bool PIPE>
 __global__ __launch_bounds__(64 * NW, 2) void temporal_attn_fused_out_kernel(const float* __restrict__ x, int ldx,
                                                                           const float* __restrict__ wqkv, const float* __restrict__ wout,
                                                                           float* __restrict__ out, int ldo, int frames, int hw,
                                                                           const float* __restrict__ bias, const float* __restrict__ rot_cos,
-                                                                          const float* __restrict__ rot_sin, float eps) {
+                                                                          const float* __restrict__ rot_sin, float eps TATTN_STAMP_PARAM) {
   constexpr int C = 64, NT = LP / 16, CT = C / 16;
   __shared__ __attribute__((aligned(16))) float o_lds[LROWS * OUT_LD];
   const int wave = lfdm_uniform((int)(threadIdx.x >> 6));
   const int lane = threadIdx.x & 63, l15 = lane & 15, lq = lane >> 4;
   const int L = frames;
   const int64_t seq = blockIdx.x;
-  tattn_heads<LP, C, (NW < 8), true>(x, ldx, wave * (HEADS / NW), HEADS / NW, wqkv, nullptr, frames, hw, seq, bias, rot_cos, rot_sin, eps, o_lds);
+#ifdef LFDM_TATTN_STAMP
+  CycleProbe probe;
+  probe.start();
+#else
+  NoProbe probe;
+#endif
+  tattn_heads<LP, C, (NW < 8), true, PIPE, true>(x, ldx, wave * (HEADS / NW), HEADS / NW, wqkv, o_lds, frames, hw, seq, bias, rot_cos, rot_sin, eps, probe);
   __syncthreads();
+  probe.lap(5);
   const int64_t b = seq / hw, pix = seq - b * hw;
   const int64_t row0 = b * frames * hw + pix;
   // output tiles (ti, ct), ti-major, dealt to the waves
@@ -267,12 +306,17 @@ __global__ __launch_bounds__(64 * NW, 2) void temporal_attn_fused_out_kernel(con
       }
     }
   }
+#ifdef LFDM_TATTN_STAMP
+  probe.lap(6);
+  if (stamps && lane == 0 && blockIdx.x < 256)
+    for (int i = 0; i < 8; ++i) stamps[((int64_t)blockIdx.x * 8 + wave) * 8 + i] = probe.acc[i];
+#endif
 }
 
 // Wide variant (C = 128, 256, ...): the channels are streamed in blocks of 64 with persistent Q^T / K^T / V
 // accumulators, so the register budget does not grow with C; the sequence's rows are re-read from L1/L2 for every head
 // and channel block (10-40 KB) and normalised on the fly with the token's mean / rstd computed once up front.
-template <int LP>
+template <int LP, bool PIPE>
 __global__ __launch_bounds__(64, 1) void temporal_attn_fused_wide_kernel(const float* __restrict__ x, int ldx, int channels,
                                                                       int heads_per_block, const float* __restrict__ wqkv,
                                                                       float* __restrict__ out, int frames, int hw,
@@ -377,7 +421,7 @@ __global__ __launch_bounds__(64, 1) void temporal_attn_fused_wide_kernel(const f
           }
       }
     }
-    attend_store<NT, false>(qf, kf, vf, head, L, l15, lq, bias, bias_vec, out, row0, hw);
+    attend_store<NT, false, PIPE>(qf, kf, vf, head, L, l15, lq, bias, bias_vec, out, row0, hw);
   }
 }
 
@@ -388,7 +432,11 @@ int launch_fused_wide(const float* x, int ldx, int channels, const float* wqkv, 
   while (hpb > 1 && nseq * (HEADS / hpb) < 2048) hpb >>= 1;
   const dim3 grid((unsigned)nseq, (unsigned)(HEADS / hpb)), block(64);
   lp_ladder(frames, [&](auto lp) {
-    LFDM_LAUNCH((temporal_attn_fused_wide_kernel<decltype(lp)::value>), grid, block, 0, stream, x, ldx, channels, hpb, wqkv, out, frames, hw, bias, rot_cos, rot_sin, eps);
+    constexpr int LP = decltype(lp)::value;
+    if (bias_by_quads(bias, frames))
+      LFDM_LAUNCH((temporal_attn_fused_wide_kernel<LP, true>), grid, block, 0, stream, x, ldx, channels, hpb, wqkv, out, frames, hw, bias, rot_cos, rot_sin, eps);
+    else
+      LFDM_LAUNCH((temporal_attn_fused_wide_kernel<LP, false>), grid, block, 0, stream, x, ldx, channels, hpb, wqkv, out, frames, hw, bias, rot_cos, rot_sin, eps);
   });
   return lfdm_check_launch("temporal_attention_fused_wide");
 }
@@ -405,7 +453,12 @@ int launch_fused(const float* x, int ldx, const float* wqkv, float* out, int bat
   }
   const dim3 grid((unsigned)nseq, (unsigned)(HEADS / hpb)), block(64);
   lp_ladder(frames, [&](auto lp) {
-    LFDM_LAUNCH((temporal_attn_fused_kernel<decltype(lp)::value, C>), grid, block, 0, stream, x, ldx, hpb, wqkv, out, frames, hw, bias, rot_cos, rot_sin, eps);
+    constexpr int LP = decltype(lp)::value;
+    constexpr bool CAN_PIPE = LP <= 32;      // (at 48 and 64 the pipelined order spills more: profiles/attend_pipeline_ab.txt section 1)
+    if (CAN_PIPE && bias_by_quads(bias, frames))
+      LFDM_LAUNCH((temporal_attn_fused_kernel<LP, C, CAN_PIPE>), grid, block, 0, stream, x, ldx, hpb, wqkv, out, frames, hw, bias, rot_cos, rot_sin, eps);
+    else
+      LFDM_LAUNCH((temporal_attn_fused_kernel<LP, C, false>), grid, block, 0, stream, x, ldx, hpb, wqkv, out, frames, hw, bias, rot_cos, rot_sin, eps);
   });
   return lfdm_check_launch("temporal_attention_fused");
 }
@@ -425,12 +478,27 @@ int launch_fused_out_lp(const float* x, int ldx, const float* wqkv, const float*
   const dim3 grid((unsigned)nseq);
   lfdm_ladder<1, 2, 4, 8>(nw, [&](auto nwc) {
     constexpr int NW = decltype(nwc)::value;
-    LFDM_LAUNCH((temporal_attn_fused_out_kernel<LP, LROWS, NW>), grid, dim3(64 * NW), 0, stream, x, ldx, wqkv, wout, out, ldo, frames, hw, bias, rot_cos, rot_sin, eps);
+    // The pipelined attention core wherever it costs neither scratch nor a wave per SIMD (profiles/attend_pipeline_ab.txt section 1: at 64 rows
+    // and four waves it spills 184 bytes instead of 168).  It reads the bias by quads: any other bias, or none, stays on the whole order.
+#if defined(LFDM_TATTN_STAMP) && LFDM_TATTN_STAMP == 2
+    constexpr bool CAN_PIPE = false;
+#else
+    constexpr bool CAN_PIPE = !(LP == 64 && NW == 4);
+#endif
+    if (CAN_PIPE && bias_by_quads(bias, frames))
+      LFDM_LAUNCH((temporal_attn_fused_out_kernel<LP, LROWS, NW, CAN_PIPE>), grid, dim3(64 * NW), 0, stream, x, ldx, wqkv, wout, out, ldo, frames, hw, bias, rot_cos, rot_sin, eps TATTN_STAMP_ARG);
+    else
+      LFDM_LAUNCH((temporal_attn_fused_out_kernel<LP, LROWS, NW, false>), grid, dim3(64 * NW), 0, stream, x, ldx, wqkv, wout, out, ldo, frames, hw, bias, rot_cos, rot_sin, eps TATTN_STAMP_ARG);
   });
   return lfdm_check_launch("temporal_attention_fused_out");
 }
 
 }  // namespace
+
+#ifdef LFDM_TATTN_STAMP
+// 256 workgroups x 8 waves x 8 phases of 64-bit cycle sums (device memory), or nullptr
+extern "C" void lfdm_tattn_stamp_buffer(void* p) { tattn_stamps = (long long*)p; }
+#endif
 
 extern "C" int lfdm_temporal_attention_fused_out_cl_f32(const float* x, int ldx, int channels, const float* wqkv, const float* wout,
                                                         float* out, int ldo, int batch, int frames, int hw, const float* bias,

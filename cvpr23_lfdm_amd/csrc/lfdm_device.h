@@ -278,6 +278,20 @@ __device__ __forceinline__ unsigned lfdm_agent_load_u32(const unsigned* p) { ret
 __device__ __forceinline__ void lfdm_sleep() { __builtin_amdgcn_s_sleep(2); }
 #endif
 
+// A line the instruction scheduler moves nothing across (no instruction of its own): bounds how far ahead a software pipeline written in
+// source order may be pulled - past it, hipcc requests every later stage's operands at once and pays for them in registers.
+// LFDM_SCHED_GROUP(mask, n): the next n instructions of class `mask` (LFDM_SG_MFMA, LFDM_SG_VALU: vector ALU other than MFMA and
+// transcendentals) of the region between two fences form a group; successive groups are issued in the order they are written.
+#if defined(LFDM_EMU_BUILD)
+#define LFDM_SCHED_FENCE() ((void)0)
+#define LFDM_SCHED_GROUP(mask, n) ((void)0)
+#else
+#define LFDM_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
+#define LFDM_SCHED_GROUP(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
+#endif
+#define LFDM_SG_VALU 0x002
+#define LFDM_SG_MFMA 0x008
+
 // Ordering point for LDS traffic that stays INSIDE one wavefront (a wave-private LDS region written by some lanes and read by others): the
 // LDS unit executes a wave's operations in order, so all that is needed is that the compiler keeps them in program order and that every
 // lane has issued its writes - no workgroup barrier, the other waves of the workgroup are not involved.

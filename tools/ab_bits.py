@@ -2,10 +2,11 @@
 """Same bits?  Runs a fixed list of calls on seeded inputs under ONE build of the kernels and writes one line per output tensor -
 name, shape, SHA-256 of its bytes - so that two builds (a refactor and its parent commit) can be compared line by line.
 
-    tools/ab_bits.py run OUT.txt [--emu [LIB]]           this process, the library LFDM_HIP_LIB names (default: the in-tree one) on the GPU,
+    tools/ab_bits.py run OUT.txt [--emu [LIB]] [--set conv|attention]
+                                                         this process, the library LFDM_HIP_LIB names (default: the in-tree one) on the GPU,
                                                          or an emulator library on the CPU (default: the in-tree one)
     tools/ab_bits.py diff A.txt B.txt                    exit status 1 when any line differs or is missing
-    tools/ab_bits.py ab BASE_LIB OUT_DIR [--emu] [--new LIB] [--timeout S]
+    tools/ab_bits.py ab BASE_LIB OUT_DIR [--emu] [--new LIB] [--timeout S] [--set conv|attention]
                                                          `run` under BASE_LIB, then under the in-tree library (or --new), each in a fresh child
                                                          process with its own time limit, one after the other; stops at the first non-zero
                                                          exit status; then `diff`
@@ -21,16 +22,28 @@ import sys
 
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# (file, -k expression): the smallest shapes that reach every epilogue / GroupNorm hand-off of the convolution family
-TESTS = [
-    ("tests/test_ops_parity.py",
-     "test_conv2d or test_deconv_one_launch or test_conv_fused_groupnorm_stats or test_conv_fused_layernorm or test_conv_pointwise or "
-     "test_conv_downsample_gather or test_winograd_pooled_epilogue or test_conv_winograd_splitk_reduced_in_launch or "
-     "test_conv_winograd_balanced_launch or test_groupnorm_apply_many_partials or test_heads_with_groupnorm_folded"),
-    ("tests/test_conv_wino_bf16.py", "test_conv2d_winograd_bf16"),
-    ("tests/test_train_ops.py", "test_groupnorm_bwd"),
-]
-DESELECT = "not gpu_only and not bigTrue and not random_geometries and not plan and not refuses and not smalln"
+# (file, -k expression) per --set.  conv: the smallest shapes that reach every epilogue / GroupNorm hand-off of the convolution family;
+# attention: every entry point that goes through csrc/attn_core.h (the short-sequence core, the fused temporal kernels, the low-resolution
+# kernel), the long-sequence kernels beside them, the fast-math cases and the per-tile-order cases.
+SETS = {
+    "conv": ([
+        ("tests/test_ops_parity.py",
+         "test_conv2d or test_deconv_one_launch or test_conv_fused_groupnorm_stats or test_conv_fused_layernorm or test_conv_pointwise or "
+         "test_conv_downsample_gather or test_winograd_pooled_epilogue or test_conv_winograd_splitk_reduced_in_launch or "
+         "test_conv_winograd_balanced_launch or test_groupnorm_apply_many_partials or test_heads_with_groupnorm_folded"),
+        ("tests/test_conv_wino_bf16.py", "test_conv2d_winograd_bf16"),
+        ("tests/test_train_ops.py", "test_groupnorm_bwd"),
+    ], "not gpu_only and not bigTrue and not random_geometries and not plan and not refuses and not smalln"),
+    "attention": ([
+        ("tests/test_ops_parity.py",
+         "test_attention_temporal or test_attention_spatial or test_temporal_attention_fused or test_attention_lowres or "
+         "test_temporal_attention_block_frame_edges or test_temporal_attention_fused_frame_edges or test_attention_frame_edges or "
+         "test_spatial_attention_token_edges"),
+        ("tests/test_attention_fast_math.py", "attention"),
+        ("tests/test_attention_long.py", "test_forward or test_backward"),
+        ("tests/test_attend_pipeline.py", "test_block or test_core"),
+    ], "not refuses"),
+}
 
 
 class Recorder:
@@ -123,8 +136,9 @@ def extra(dev, rec):
         ops.conv2d_cl(xs, wd, cout, 3, 3, n, h, w, gn_partial=partial, gn_groups=8, gn_pixels=pixels, **kw)
 
 
-def run(out_path, emu):
+def run(out_path, emu, which="conv"):
     import pytest
+    tests, deselect = SETS[which]
     emu_lib = None
     if emu is not None:
         emu_lib = os.path.abspath(emu) if emu else os.path.join(R, "tests", "emu", "liblfdm_emu.so")
@@ -132,8 +146,8 @@ def run(out_path, emu):
     os.chdir(R)
     # (the F(2x2) Winograd cases run at both workgroup widths: LFDM_WINO_BN is a parameter of the suite's own tests)
     args = ["-q", "-p", "no:cacheprovider", "-x", "-m", "emu" if emu is not None else "gpu"]
-    kexpr = "(" + " or ".join("(%s)" % k for _, k in TESTS) + ") and " + DESELECT
-    rc = pytest.main(args + [f for f, _ in TESTS] + ["-k", kexpr], plugins=[rec])
+    kexpr = "(" + " or ".join("(%s)" % k for _, k in tests) + ") and " + deselect
+    rc = pytest.main(args + [f for f, _ in tests] + ["-k", kexpr], plugins=[rec])
     if rc != 0:
         return int(rc)
     # extra cells: drive the same wrapped ops under the same library
@@ -142,7 +156,8 @@ def run(out_path, emu):
     if emu_lib:
         _native._set_library_for_tests(_native.NativeLibrary(emu_lib, "emu"))
     dev = "cpu" if emu_lib else "cuda"
-    extra(dev, rec)
+    if which == "conv":
+        extra(dev, rec)
     if dev == "cuda":
         torch.cuda.synchronize()
     with open(out_path, "w") as fh:
@@ -175,6 +190,7 @@ def main():
     r = sub.add_parser("run")
     r.add_argument("out")
     r.add_argument("--emu", nargs="?", const="", default=None)
+    r.add_argument("--set", choices=sorted(SETS), default="conv")
     d = sub.add_parser("diff")
     d.add_argument("a")
     d.add_argument("b")
@@ -184,9 +200,10 @@ def main():
     c.add_argument("--new", default=None)
     c.add_argument("--emu", action="store_true")
     c.add_argument("--timeout", type=int, default=240)
+    c.add_argument("--set", choices=sorted(SETS), default="conv")
     a = ap.parse_args()
     if a.mode == "run":
-        return run(a.out, a.emu)
+        return run(a.out, a.emu, a.set)
     if a.mode == "diff":
         return diff(a.a, a.b)
     os.makedirs(a.out_dir, exist_ok=True)
@@ -194,7 +211,7 @@ def main():
     for tag, lib in (("base", os.path.abspath(a.base)), ("new", os.path.abspath(a.new) if a.new else None)):
         out = os.path.join(a.out_dir, "bits_%s%s.txt" % ("emu_" if a.emu else "", tag))
         env = dict(os.environ)
-        cmd = [sys.executable, os.path.abspath(__file__), "run", out]
+        cmd = [sys.executable, os.path.abspath(__file__), "run", out, "--set", a.set]
         if a.emu:
             cmd += ["--emu"] + ([lib] if lib else [])
         elif lib:
