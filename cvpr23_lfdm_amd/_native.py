@@ -186,6 +186,14 @@ _SIGNATURES = {
     "lfdm_sampler_step_ms_known_f32": (i32, [f32p, f32p, f32p, f32p, i32, i64, f32p, C.c_void_p, f32, i32,
                                             C.c_void_p, sz, f32p, f32p, C.c_void_p, f32p, i32, i64, stream_t]),
     "lfdm_known_blend_f32": (i32, [f32p, f32p, f32p, C.c_void_p, f32, f32, i32, i64, i32, i64, stream_t]),
+    # ---- per-element known masks (additive, ABI stays 12)
+    "lfdm_sampler_step_elem_f32": (i32, [f32p, f32p, f32p, f32p, i32, i64, f32p, C.c_void_p, f32, i32,
+                                        C.c_void_p, sz, f32p, f32p, C.c_void_p, f32p, stream_t]),
+    "lfdm_sampler_step_ms_elem_f32": (i32, [f32p, f32p, f32p, f32p, i32, i64, f32p, C.c_void_p, f32, i32,
+                                           C.c_void_p, sz, f32p, f32p, C.c_void_p, f32p, stream_t]),
+    "lfdm_sampler_step_counter_elem_f32": (i32, [f32p, f32p, C.c_void_p, C.c_void_p, f32p, i32, i64, f32p, C.c_void_p, f32, i32,
+                                                C.c_void_p, sz, f32p, f32p, C.c_void_p, f32p, stream_t]),
+    "lfdm_known_blend_elem_f32": (i32, [f32p, f32p, f32p, C.c_void_p, f32, f32, i32, i64, stream_t]),
     # ---- counter-based noise: fill kernels and the generating sampler step (additive, ABI stays 12)
     "lfdm_philox_normal_f32": (i32, [f32p, C.c_void_p, i32, i64, i64, C.c_uint, C.c_uint, C.c_uint, stream_t]),
     "lfdm_philox_bits_u32": (i32, [C.c_void_p, C.c_void_p, i32, i64, i64, C.c_uint, C.c_uint, C.c_uint, stream_t]),

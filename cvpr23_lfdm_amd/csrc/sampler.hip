@@ -206,15 +206,23 @@ __global__ __launch_bounds__(256) void quantile_out_kernel(Ranks rk, const unsig
 
 // Known-frame conditioning (replacement method; lfdm_sampler_step_known_f32): the operands of the update kernels' KNOWN variant.
 // The plain instantiations carry the empty form as their last argument, so everything in front of it sits where it sat.
-template <bool KNOWN>
+// ELEM (lfdm_sampler_step_elem_f32): one mask byte per ELEMENT instead of one per frame - no frames, no frame_elems, no division.
+template <bool KNOWN, bool ELEM = false>
 struct KnownOps {};
 template <>
-struct KnownOps<true> {
+struct KnownOps<true, false> {
   const float* known;          // (B, n)
   const float* known_noise;    // (B, n)
   const unsigned char* mask;   // (B, frames), non-zero = known
   const float* level;          // (steps + 1, 2): row step + 1 = (a, s) after this step
   unsigned frames, frame_elems;
+};
+template <>
+struct KnownOps<true, true> {
+  const float* known;          // (B, n)
+  const float* known_noise;    // (B, n)
+  const unsigned char* mask;   // (B, n), non-zero = known
+  const float* level;          // (steps + 1, 2): row step + 1 = (a, s) after this step
 };
 
 // x[b, i] <- a * known + s * known_noise where the frame (i / frame_elems) % frames of sample b is known (x_T, once per video).  grid (nblk, B)
@@ -229,16 +237,25 @@ __global__ __launch_bounds__(256) void known_blend_kernel(float* __restrict__ x,
     if (mb[(i / frame_elems) % frames]) x[off + i] = a * known[off + i] + s * known_noise[off + i];
 }
 
+// the element-mask form of known_blend_kernel: mask (B, n).  grid (nblk, B)
+__global__ __launch_bounds__(256) void known_blend_elem_kernel(float* __restrict__ x, const float* __restrict__ known,
+                                                               const float* __restrict__ known_noise,
+                                                               const unsigned char* __restrict__ mask, float a, float s, unsigned n) {
+  const int64_t off = (int64_t)blockIdx.y * n;
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u)
+    if (mask[off + i]) x[off + i] = a * known[off + i] + s * known_noise[off + i];
+}
+
 // The KNOWN variant's registers: level pair, and mask byte / known / known_noise of the PRE prefetched elements.  Empty for the plain variant.
-template <bool KNOWN, int PRE>
+template <bool KNOWN, bool ELEM, int PRE>
 struct KnownPre {
-  __device__ __forceinline__ void head(const KnownOps<KNOWN>&, const int32_t*, int, int64_t) {}
-  __device__ __forceinline__ void load(const KnownOps<KNOWN>&, int, bool, int64_t) {}
+  __device__ __forceinline__ void head(const KnownOps<KNOWN, ELEM>&, const int32_t*, int, int64_t) {}
+  __device__ __forceinline__ void load(const KnownOps<KNOWN, ELEM>&, int, bool, int64_t) {}
   __device__ __forceinline__ float pick(int, float v) const { return v; }
-  __device__ __forceinline__ float tail(const KnownOps<KNOWN>&, int64_t, float v) { return v; }
+  __device__ __forceinline__ float tail(const KnownOps<KNOWN, ELEM>&, int64_t, float v) { return v; }
 };
 template <int PRE>
-struct KnownPre<true, PRE> {
+struct KnownPre<true, false, PRE> {
   float a, s, kn[PRE], kz[PRE];
   unsigned mk[PRE];
   int64_t off;
@@ -281,6 +298,32 @@ struct KnownPre<true, PRE> {
   }
 };
 
+// ELEM: the mask byte sits where the element sits - the frame variant's walk (fr, rem, next) has no counterpart, the byte is one more load of
+// the prefetch batch at the element's own index.
+template <int PRE>
+struct KnownPre<true, true, PRE> {
+  float a, s, kn[PRE], kz[PRE];
+  unsigned mk[PRE];
+  int64_t off;
+  __device__ __forceinline__ void head(const KnownOps<true, true>& kf, const int32_t* step_dev, int b, int64_t n) {
+    const float* lv = kf.level + 2 * ((int64_t)(*step_dev) + 1);
+    a = lv[0];
+    s = lv[1];
+    off = (int64_t)b * n;
+  }
+  __device__ __forceinline__ void load(const KnownOps<true, true>& kf, int k, bool in, int64_t i) {
+    const unsigned u = in ? (unsigned)i : 0u;
+    mk[k] = in ? kf.mask[off + u] : 0u;
+    kn[k] = in ? kf.known[off + u] : 0.f;
+    kz[k] = in ? kf.known_noise[off + u] : 0.f;
+  }
+  __device__ __forceinline__ float pick(int k, float v) const { return mk[k] ? a * kn[k] + s * kz[k] : v; }
+  __device__ __forceinline__ float tail(const KnownOps<true, true>& kf, int64_t i, float v) {
+    if (kf.mask[off + i]) v = a * kf.known[off + i] + s * kf.known_noise[off + i];
+    return v;
+  }
+};
+
 // Counter-based step noise (lfdm_sampler_step_counter_f32): the operands of the update kernel's GENERATING variant, which
 // computes noise[b, i] = lfdm_noise_element(seeds[b], i, step, 2, *window) in registers instead of loading it.  Empty for the loading variants.
 template <bool GEN>
@@ -316,8 +359,8 @@ struct GenPre<true> {
 
 // Both optional operand sets as ONE trailing kernel argument: empty (one byte, like KnownOps<false> alone before) for the plain instantiation,
 // so the kernel-argument layout of the loading instantiations is what it was.
-template <bool KNOWN, bool GEN>
-struct StepOps : KnownOps<KNOWN>, GenOps<GEN> {};
+template <bool KNOWN, bool GEN, bool ELEM = false>
+struct StepOps : KnownOps<KNOWN, ELEM>, GenOps<GEN> {};
 
 // KNOWN: the final store of x selects a * known + s * known_noise at the frames the byte mask marks; x0_out, the threshold, the housekeeping and
 // every other frame are the plain variant's.  What was chosen for the loads: the step counter and, behind it, the level pair are requested first
@@ -325,9 +368,10 @@ struct StepOps : KnownOps<KNOWN>, GenOps<GEN> {};
 // elements are loaded UNCONDITIONALLY in the same batch as today's prefetch (no round trip in front of the search; values at unmasked frames
 // are loaded but only ever pass through a select, so they may be NaN); the loop behind the prefetched elements branches on the mask byte.
 // The frame index of an element is carried along, not divided out (KnownPre).
+// ELEM: the mask holds one byte per element (KnownOps<true, true>); same load order, the byte is requested at the element's own index.
 // GEN: `noise` is not an operand (null); the step noise is computed where it is loaded otherwise (GenPre).
 // grid (nblk, B)
-template <bool KNOWN, bool GEN>
+template <bool KNOWN, bool GEN, bool ELEM>
 __global__ __launch_bounds__(256) void sampler_update_kernel(float* __restrict__ x,
                                                              const float* __restrict__ eps,
                                                              const float* __restrict__ noise,
@@ -336,9 +380,9 @@ __global__ __launch_bounds__(256) void sampler_update_kernel(float* __restrict__
                                                              const float* __restrict__ coef,
                                                              const int32_t* step_dev,      // (no __restrict__: advance_dev is the same word)
                                                              Ranks rk, unsigned* __restrict__ hists, int hist_samples,
-                                                             unsigned* __restrict__ ticket, int32_t* advance_dev, StepOps<KNOWN, GEN> so) {
+                                                             unsigned* __restrict__ ticket, int32_t* advance_dev, StepOps<KNOWN, GEN, ELEM> so) {
   __shared__ unsigned s_part[256], s_res[4];
-  const KnownOps<KNOWN>& kf = so;
+  const KnownOps<KNOWN, ELEM>& kf = so;
   const GenOps<GEN>& gen = so;
   const int b = blockIdx.y;
   float* xb = x + (int64_t)b * n;
@@ -351,7 +395,7 @@ __global__ __launch_bounds__(256) void sampler_update_kernel(float* __restrict__
   constexpr int PRE = 8;
   const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
   float p_x0[PRE], p_e[PRE], p_x[PRE], p_n[PRE];
-  KnownPre<KNOWN, PRE> kp;
+  KnownPre<KNOWN, ELEM, PRE> kp;
   kp.head(kf, step_dev, b, n);
   GenPre<GEN> gp;
   gp.head(gen, step_dev, b);
@@ -426,7 +470,7 @@ __global__ __launch_bounds__(256) void sampler_update_kernel(float* __restrict__
 // operand any more (pass 0 consumed it).  k_prev == 0 / k_x == 0 skip their operand: on a first-order step hist may be uninitialised
 // memory.  Prefetch, end-of-step housekeeping and the KNOWN variant (only the store of x differs: hist and x0_out receive m at every frame)
 // as in sampler_update_kernel.  grid (nblk, B)
-template <bool KNOWN>
+template <bool KNOWN, bool ELEM>
 __global__ __launch_bounds__(256) void sampler_update_ms_kernel(float* __restrict__ x,
                                                                 float* __restrict__ hist,
                                                                 const float* __restrict__ x0buf,
@@ -434,7 +478,7 @@ __global__ __launch_bounds__(256) void sampler_update_ms_kernel(float* __restric
                                                                 const float* __restrict__ coef,
                                                                 const int32_t* step_dev,      // (no __restrict__: advance_dev is the same word)
                                                                 Ranks rk, unsigned* __restrict__ hists, int hist_samples,
-                                                                unsigned* __restrict__ ticket, int32_t* advance_dev, KnownOps<KNOWN> kf) {
+                                                                unsigned* __restrict__ ticket, int32_t* advance_dev, KnownOps<KNOWN, ELEM> kf) {
   __shared__ unsigned s_part[256], s_res[4];
   const int b = blockIdx.y;
   float* xb = x + (int64_t)b * n;
@@ -444,7 +488,7 @@ __global__ __launch_bounds__(256) void sampler_update_ms_kernel(float* __restric
   constexpr int PRE = 8;               // requested before the five histogram scans, like sampler_update_kernel's
   const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
   float p_x0[PRE], p_x[PRE], p_m[PRE];
-  KnownPre<KNOWN, PRE> kp;
+  KnownPre<KNOWN, ELEM, PRE> kp;
   kp.head(kf, step_dev, b, n);
 #pragma unroll
   for (int k = 0; k < PRE; ++k) {
@@ -686,11 +730,32 @@ int make_known(const char* what, const float* known, const float* known_noise, c
   return 0;
 }
 
+// argument check of the element-mask operands (no frame split: the mask has n bytes per sample); on success fills kf
+int make_known_elem(const char* what, const float* known, const float* known_noise, const unsigned char* elem_mask, const float* level,
+                    int64_t n, KnownOps<true, true>* kf) {
+  char msg[160];
+  if (!known || !known_noise || !elem_mask || !level) {
+    snprintf(msg, sizeof msg, "%s: known, known_noise, elem_mask and level must all be given", what);
+    lfdm_set_error(msg);
+    return LFDM_EINVAL;
+  }
+  if (n <= 0 || n >= (1 << 24)) {
+    snprintf(msg, sizeof msg, "%s: n = %lld must lie in (0, 2^24)", what, (long long)n);
+    lfdm_set_error(msg);
+    return LFDM_EINVAL;
+  }
+  kf->known = known;
+  kf->known_noise = known_noise;
+  kf->mask = elem_mask;
+  kf->level = level;
+  return 0;
+}
+
 // The one launch sequence of every sampler step: [histogram clear for batch > 2] pass 0, two select passes, update.  MS: the multistep update
-// (second = hist) instead of the DDIM / DDPM one (second = noise); KNOWN: the update kernel's known-frame instantiation.
-template <bool MS, bool KNOWN, bool GEN = false>
+// (second = hist) instead of the DDIM / DDPM one (second = noise); KNOWN: the update kernel's known-frame instantiation, ELEM: its element-mask one.
+template <bool MS, bool KNOWN, bool GEN = false, bool ELEM = false>
 int run_step(const char* what, float* x, const float* eps, float* second, float* x0_out, int batch, int64_t n, const float* coef,
-             int32_t* step_dev, float quantile, int advance, void* ws, size_t ws_bytes, KnownOps<KNOWN> kf, hipStream_t stream,
+             int32_t* step_dev, float quantile, int advance, void* ws, size_t ws_bytes, KnownOps<KNOWN, ELEM> kf, hipStream_t stream,
              GenOps<GEN> gen = GenOps<GEN>{}) {
   static_assert(!(MS && GEN), "the multistep update draws nothing");
   char msg[160];
@@ -727,12 +792,12 @@ int run_step(const char* what, float* x, const float* eps, float* second, float*
               (const int32_t*)step_dev, hists);         // (also the x0 = c_x*x - c_eps*eps pass: columns 0-1 of either table)
   if (dynamic) run_select(x0buf, batch, n, rk, hists, stream);
   if constexpr (MS)
-    LFDM_LAUNCH((sampler_update_ms_kernel<KNOWN>), grid, block, 0, stream, x, second, (const float*)x0buf, x0_out, n, coef,
+    LFDM_LAUNCH((sampler_update_ms_kernel<KNOWN, ELEM>), grid, block, 0, stream, x, second, (const float*)x0buf, x0_out, n, coef,
                 (const int32_t*)step_dev, rk, hists, fold_clear ? batch : 0, ticket, advance ? step_dev : (int32_t*)nullptr, kf);
   else if constexpr (!MS)
-    LFDM_LAUNCH((sampler_update_kernel<KNOWN, GEN>), grid, block, 0, stream, x, eps, (const float*)second, x0buf, x0_out, n, coef,
+    LFDM_LAUNCH((sampler_update_kernel<KNOWN, GEN, ELEM>), grid, block, 0, stream, x, eps, (const float*)second, x0buf, x0_out, n, coef,
                 (const int32_t*)step_dev, rk, hists, fold_clear ? batch : 0, ticket, advance ? step_dev : (int32_t*)nullptr,
-                StepOps<KNOWN, GEN>{kf, gen});
+                StepOps<KNOWN, GEN, ELEM>{kf, gen});
   return lfdm_check_launch(what);
 }
 
@@ -789,6 +854,39 @@ extern "C" int lfdm_known_blend_f32(float* x, const float* known, const float* k
   return lfdm_check_launch("known_blend");
 }
 
+extern "C" int lfdm_sampler_step_elem_f32(float* x, const float* eps, const float* noise, float* x0_out, int batch, int64_t n,
+                                          const float* coef, int32_t* step_dev, float quantile, int advance, void* ws, size_t ws_bytes,
+                                          const float* known, const float* known_noise, const unsigned char* elem_mask, const float* level,
+                                          lfdm_stream_t stream_) {
+  KnownOps<true, true> kf;
+  if (int rc = make_known_elem("sampler_step_elem", known, known_noise, elem_mask, level, n, &kf)) return rc;
+  return run_step<false, true, false, true>("sampler_step_elem", x, eps, const_cast<float*>(noise), x0_out, batch, n, coef, step_dev, quantile,
+                                            advance, ws, ws_bytes, kf, (hipStream_t)stream_);
+}
+
+extern "C" int lfdm_sampler_step_ms_elem_f32(float* x, const float* eps, float* hist, float* x0_out, int batch, int64_t n, const float* coef,
+                                             int32_t* step_dev, float quantile, int advance, void* ws, size_t ws_bytes, const float* known,
+                                             const float* known_noise, const unsigned char* elem_mask, const float* level,
+                                             lfdm_stream_t stream_) {
+  KnownOps<true, true> kf;
+  if (int rc = make_known_elem("sampler_step_ms_elem", known, known_noise, elem_mask, level, n, &kf)) return rc;
+  return run_step<true, true, false, true>("sampler_step_ms_elem", x, eps, hist, x0_out, batch, n, coef, step_dev, quantile, advance, ws,
+                                           ws_bytes, kf, (hipStream_t)stream_);
+}
+
+extern "C" int lfdm_known_blend_elem_f32(float* x, const float* known, const float* known_noise, const unsigned char* elem_mask, float a,
+                                         float s, int batch, int64_t n, lfdm_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  KnownOps<true, true> kf;
+  if (!x || batch <= 0) {
+    lfdm_set_error("known_blend_elem: bad arguments");
+    return LFDM_EINVAL;
+  }
+  if (int rc = make_known_elem("known_blend_elem", known, known_noise, elem_mask, /*level: not an operand*/ known, n, &kf)) return rc;
+  LFDM_LAUNCH(known_blend_elem_kernel, dim3(blocks_for(n), batch), dim3(256), 0, stream, x, known, known_noise, elem_mask, a, s, (unsigned)n);
+  return lfdm_check_launch("known_blend_elem");
+}
+
 extern "C" int lfdm_philox_normal_f32(float* out, const uint64_t* seeds, int batch, int64_t n, int64_t row_stride, unsigned stream_id,
                                       unsigned step, unsigned window, lfdm_stream_t stream_) {
   return run_philox_fill<false>("philox_normal", out, seeds, batch, n, row_stride, stream_id, step, window, (hipStream_t)stream_);
@@ -833,4 +931,16 @@ extern "C" int lfdm_sampler_step_counter_known_f32(float* x, const float* eps, c
   if (int rc = make_known("sampler_step_counter_known", known, known_noise, frame_mask, level, n, frames, frame_elems, &kf)) return rc;
   return run_step<false, true, true>("sampler_step_counter_known", x, eps, nullptr, x0_out, batch, n, coef, step_dev, quantile, advance,
                                      ws, ws_bytes, kf, (hipStream_t)stream_, gen);
+}
+
+extern "C" int lfdm_sampler_step_counter_elem_f32(float* x, const float* eps, const uint64_t* seeds, const uint32_t* window, float* x0_out,
+                                                  int batch, int64_t n, const float* coef, int32_t* step_dev, float quantile, int advance,
+                                                  void* ws, size_t ws_bytes, const float* known, const float* known_noise,
+                                                  const unsigned char* elem_mask, const float* level, lfdm_stream_t stream_) {
+  GenOps<true> gen;
+  if (int rc = make_gen("sampler_step_counter_elem", seeds, window, &gen)) return rc;
+  KnownOps<true, true> kf;
+  if (int rc = make_known_elem("sampler_step_counter_elem", known, known_noise, elem_mask, level, n, &kf)) return rc;
+  return run_step<false, true, true, true>("sampler_step_counter_elem", x, eps, nullptr, x0_out, batch, n, coef, step_dev, quantile, advance,
+                                           ws, ws_bytes, kf, (hipStream_t)stream_, gen);
 }

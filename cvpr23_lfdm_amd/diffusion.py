@@ -52,18 +52,23 @@ class Schedule:
 
 
 class Request(NamedTuple):
-    """A validated sampling call (GaussianDiffusion.check_request): seeds is the list of ints under noise="counter", else None."""
+    """A validated sampling call (GaussianDiffusion.check_request): seeds is the list of ints under noise="counter", else None.  known_mask:
+    (B, T) bool - known frames - or 5-D bool (B, C | 1, T, S, S) - known elements.  start / start_step: the latent the
+    schedule is entered on in front of step start_step (None: pure noise in front of step 0)."""
     shape: tuple
     known: Optional[torch.Tensor]
     known_mask: Optional[torch.Tensor]
     seeds: Optional[list]
     window: int
+    start: Optional[torch.Tensor] = None
+    start_step: int = 0
 
 
 class SampleMode(NamedTuple):
     """Everything a sampler step branches on, and so the key of its plan and captured graphs: `sampler_step` sees the plan and this and
     nothing of the model.  conv_precision by name (both modes share one weight pack - `pack`, its id, does not tell them apart); quantile
-    -1.0 is the static clamp; known: the conditioned update kernel on the plan's known-frame operands."""
+    -1.0 is the static clamp; known: the conditioned update kernel on the plan's known operands - elem: its element-mask instantiation, the
+    plan's mask then has the latent's shape.  (Where a video starts is no part of the key: the step counter's first value is an operand.)"""
     batch: int
     frames: int
     size: int
@@ -77,6 +82,7 @@ class SampleMode(NamedTuple):
     noise: str
     quantile: float
     known: bool
+    elem: bool = False
 
 
 def sampler_step(unet, plan, mode):
@@ -97,7 +103,8 @@ def sampler_step(unet, plan, mode):
         ops.cfg_combine(eps2[:b], eps2[b:], mode.cond_scale, eps)      # null + (cond - null) * scale
     kw = dict(quantile=mode.quantile, ws=plan["ws"])
     if mode.known:
-        kw.update(known=plan["known"], known_noise=plan["known_noise"], frame_mask=plan["kmask"], level=plan["level"], frames=frames)
+        kw.update(known=plan["known"], known_noise=plan["known_noise"], level=plan["level"])
+        kw.update(dict(elem_mask=plan["kmask"]) if mode.elem else dict(frame_mask=plan["kmask"], frames=frames))
     if mode.sampler != "reference":
         ops.sampler_step_ms(x, eps, plan["hist"], plan["coef"], step, **kw)
     elif mode.noise == "counter":
@@ -109,17 +116,17 @@ def sampler_step(unet, plan, mode):
 def capture_step(unet, plan, mode):
     """The plan's single-step graph on the current scratch arenas; the chunk graphs of the old arenas go with the old one."""
     x, step = plan["x"], plan["step"]
-    x_saved = x.clone()
+    x_saved, step_saved = x.clone(), step.clone()       # (the counter holds the first step of this video: not 0 when it starts on a latent)
     plan["noise"].zero_()
     sampler_step(unet, plan, mode)          # dry run: allocates every scratch buffer outside the capture, then state is restored
     torch.cuda.synchronize()
     x.copy_(x_saved)
-    step.zero_()
+    step.copy_(step_saved)
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
         sampler_step(unet, plan, mode)
     x.copy_(x_saved)
-    step.zero_()
+    step.copy_(step_saved)
     plan.update(graph=graph, chunk_graphs={}, buf_gen=unet._buf_gen)
 
 
@@ -377,10 +384,13 @@ class GaussianDiffusion(nn.Module):
             sch.level = sch.level_host.to(dev)
         return sch
 
-    def check_request(self, shape, known=None, known_mask=None, seeds=None, window=0):
+    def check_request(self, shape, known=None, known_mask=None, seeds=None, window=0, start=None, start_step=0, steps=None):
         """The validated `Request` of one sampling call; ValueError before anything is launched (and before the text encoder runs).  known
         (B, C, T, S, S) float32 and known_mask (B, T) bool: both or none.  seeds: noise="counter" needs one Python int in [0, 2^64) per video
-        and no noise tape next to them; noise="torch" takes neither seeds nor a window.  The outermost entry (FlowDiffusion.sample_one_video
+        and no noise tape next to them; noise="torch" takes neither seeds nor a window.  known_mask may also be a 5-D bool of shape
+        (B, C, T, S, S) or (B, 1, T, S, S) (broadcast over the channels): known ELEMENTS.  start (B, C, T, S, S) float32 with
+        0 <= start_step < steps (`steps`: of the schedule the caller runs, default `sample`'s): the latent the schedule is entered on; a
+        start_step without start is refused.  The outermost entry (FlowDiffusion.sample_one_video
         / sample_long_video; sample / p_sample_loop / ddim_sample called directly) checks once, everything below takes the Request on trust."""
         shape = tuple(shape)
         if (known is None) != (known_mask is None):
@@ -389,34 +399,47 @@ class GaussianDiffusion(nn.Module):
             if not isinstance(known, torch.Tensor) or known.dtype != torch.float32 or tuple(known.shape) != shape:
                 raise ValueError("sample: known must be a float32 tensor of shape %s, got %s %s"
                                  % (shape, getattr(known, "dtype", type(known)), tuple(getattr(known, "shape", ()))))
-            if not isinstance(known_mask, torch.Tensor) or known_mask.dtype != torch.bool or tuple(known_mask.shape) != (shape[0], shape[2]):
-                raise ValueError("sample: known_mask must be a bool tensor of shape %s, got %s %s"
-                                 % ((shape[0], shape[2]), getattr(known_mask, "dtype", type(known_mask)), tuple(getattr(known_mask, "shape", ()))))
+            forms = ((shape[0], shape[2]), shape, (shape[0], 1) + shape[2:])
+            if not isinstance(known_mask, torch.Tensor) or known_mask.dtype != torch.bool or tuple(known_mask.shape) not in forms:
+                raise ValueError("sample: known_mask must be a bool tensor of shape %s (frames) or %s / %s (elements), got %s %s"
+                                 % (forms + (getattr(known_mask, "dtype", type(known_mask)), tuple(getattr(known_mask, "shape", ())))))
+        if start is None:
+            if start_step != 0:
+                raise ValueError("sample: start_step = %r needs start (the latent to enter the schedule on)" % (start_step,))
+        else:
+            if not isinstance(start, torch.Tensor) or start.dtype != torch.float32 or tuple(start.shape) != shape:
+                raise ValueError("sample: start must be a float32 tensor of shape %s, got %s %s"
+                                 % (shape, getattr(start, "dtype", type(start)), tuple(getattr(start, "shape", ()))))
+            if steps is None:
+                steps = self.sampling_timesteps if self.is_ddim_sampling or self.sampler != "reference" else self.num_timesteps
+            if isinstance(start_step, bool) or not isinstance(start_step, int) or not 0 <= start_step < steps:
+                raise ValueError("sample: start_step must be an integer in [0, %d), got %r" % (steps, start_step))
         if self.noise != "counter":
             if seeds is not None:
                 raise ValueError("sample: seeds need noise='counter' (this model draws from torch's generator: noise=%r)" % (self.noise,))
             if window != 0:
                 raise ValueError("sample: window needs noise='counter'")
-            return Request(shape, known, known_mask, None, 0)
+            return Request(shape, known, known_mask, None, 0, start, start_step)
         if seeds is None:
             raise ValueError("sample: noise='counter' needs seeds (one integer in [0, 2^64) per video)")
         if self.noise_source is not None:
             raise ValueError("sample: a noise_source (tape) and noise='counter' exclude each other - replay counter_tape(...) under noise='torch'")
         if isinstance(window, bool) or not isinstance(window, int) or not 0 <= window < (1 << 32):
             raise ValueError("sample: window must be an integer in [0, 2^32), got %r" % (window,))
-        return Request(shape, known, known_mask, ops.check_seeds(seeds, shape[0], "sample: seeds"), window)
+        return Request(shape, known, known_mask, ops.check_seeds(seeds, shape[0], "sample: seeds"), window, start, start_step)
 
-    def counter_tape(self, seeds, shape, ddim, window=0, known=False):
+    def counter_tape(self, seeds, shape, ddim, window=0, known=False, start_step=0):
         """The counter-based draws of one `sample` call as a noise tape: a callable with the `noise_source` signature that returns, in the
         default path's draw order, the tensors ops.philox_normal writes for `seeds` - x_T (stream 0), then the known-frame noise (stream 1) if
-        `known`, then one tensor per drawing step of the schedule (stream 2, step = the step's index; none under the multistep samplers).
+        `known`, then one tensor per drawing step of the schedule (stream 2, step = the step's index; none under the multistep samplers)
+        from step `start_step` on (a video entered at that step draws nothing for the steps in front of it).
         Installed as `noise_source` of a noise="torch" model - or handed to the oracle - it reproduces the noise="counter" sample."""
         shape = tuple(shape)
         seeds = ops.check_seeds(seeds, shape[0], "counter_tape: seeds")
         dev = "cuda" if _native.library().kind == "hip" else "cpu"
         draws = self._schedule(ddim, self.sampler, dev).draws
         plan = [(ops.NOISE_STREAM_XT, 0)] + ([(ops.NOISE_STREAM_KNOWN, 0)] if known else [])
-        plan += [(ops.NOISE_STREAM_STEP, i) for i, d in enumerate(draws) if d]
+        plan += [(ops.NOISE_STREAM_STEP, i) for i, d in enumerate(draws) if d and i >= start_step]
         seeds_dev = ops.seeds_tensor(seeds, dev)
         state = {"next": 0}
 
@@ -433,16 +456,21 @@ class GaussianDiffusion(nn.Module):
 
     # ------------------------------------------------------------------ sampling
     @torch.no_grad()
-    def sample(self, fea, cond=None, cond_scale=1., batch_size=16, *, known=None, known_mask=None, seeds=None, window=0):
+    def sample(self, fea, cond=None, cond_scale=1., batch_size=16, *, known=None, known_mask=None, seeds=None, window=0, start=None,
+               start_step=0):
         """Reference :762-775.  fea: planar (B, 256, S, S); cond: (B, 768) tensor or list[str].  Runs `self.sampler`.
         known (B, C, T, S, S) float32 + known_mask (B, T) bool (keyword only, both or none): condition on known frames by the replacement
         method - frame t of sample b is kept on the trajectory of known[b, :, t] and returned bit for bit where the mask is
         set; values of `known` at other frames are never read into the result.
         seeds (keyword only; needed by, and only allowed under, noise="counter"): one Python int in [0, 2^64) per video - video b is then a
-        function of seeds[b] (and of `window`, the window number of a long video) wherever it sits in the batch."""
+        function of seeds[b] (and of `window`, the window number of a long video) wherever it sits in the batch.
+        known_mask may instead be 5-D, (B, C, T, S, S) or (B, 1, T, S, S) bool: known ELEMENTS - a region of every frame, one channel
+        (DESIGN.md 4.11).  start (B, C, T, S, S) float32 + start_step k in [0, steps): the schedule is entered in front of step k on
+        x = a_k start + s_k z (z: the x_T draw, (a_k, s_k): row k of the level table) and steps k .. steps - 1 run - an edit of an existing
+        video, the closer to it the later it starts.  Known content is then placed on row k."""
         batch = batch_size if cond is None else len(cond)
         shape = (batch, self.channels, self.num_frames, self.image_size, self.image_size)
-        return self.sample_checked(fea, cond, cond_scale, self.check_request(shape, known, known_mask, seeds, window))
+        return self.sample_checked(fea, cond, cond_scale, self.check_request(shape, known, known_mask, seeds, window, start, start_step))
 
     @torch.no_grad()
     def sample_checked(self, fea, cond, cond_scale, req):
@@ -454,12 +482,16 @@ class GaussianDiffusion(nn.Module):
         return self._sample(fea, cond, cond_scale, self.is_ddim_sampling or self.sampler != "reference", self.sampler, req)
 
     @torch.no_grad()
-    def p_sample_loop(self, fea, shape, cond=None, cond_scale=1., *, known=None, known_mask=None, seeds=None, window=0):
-        return self._sample(fea, cond, cond_scale, False, "reference", self.check_request(shape, known, known_mask, seeds, window))
+    def p_sample_loop(self, fea, shape, cond=None, cond_scale=1., *, known=None, known_mask=None, seeds=None, window=0, start=None,
+                      start_step=0):
+        return self._sample(fea, cond, cond_scale, False, "reference",
+                            self.check_request(shape, known, known_mask, seeds, window, start, start_step, steps=self.num_timesteps))
 
     @torch.no_grad()
-    def ddim_sample(self, fea, shape, cond=None, cond_scale=1., clip_denoised=True, *, known=None, known_mask=None, seeds=None, window=0):
-        return self._sample(fea, cond, cond_scale, True, "reference", self.check_request(shape, known, known_mask, seeds, window))
+    def ddim_sample(self, fea, shape, cond=None, cond_scale=1., clip_denoised=True, *, known=None, known_mask=None, seeds=None, window=0,
+                    start=None, start_step=0):
+        return self._sample(fea, cond, cond_scale, True, "reference",
+                            self.check_request(shape, known, known_mask, seeds, window, start, start_step, steps=self.sampling_timesteps))
 
     def _sample(self, fea, cond, cond_scale, ddim, sampler, req):
         """One video batch: schedule -> this call's operand values -> the plan of its mode, refilled -> x_T -> the steps."""
@@ -468,11 +500,12 @@ class GaussianDiffusion(nn.Module):
         batch, _, frames, s, _ = req.shape
         if getattr(unet, "long_attention", False):
             unet.check_geometry(frames, s)        # (frames / mid-block pixels the streaming kernels do not take: before the first launch)
-        sch = self._schedule(ddim, sampler, dev, level=req.known is not None)
+        sch = self._schedule(ddim, sampler, dev, level=req.known is not None or req.start is not None)
         pk = unet.packed()
         values = self._step_operands(unet, pk, sch, fea, cond, cond_scale, batch, s)
         mode = SampleMode(batch, frames, s, len(values["parts"]), float(cond_scale), bool(ddim), len(sch.times), id(pk), unet.conv_precision,
-                          sampler, self.noise, float(self.dynamic_thres_percentile) if self.use_dynamic_thres else -1.0, req.known is not None)
+                          sampler, self.noise, float(self.dynamic_thres_percentile) if self.use_dynamic_thres else -1.0, req.known is not None,
+                          req.known is not None and req.known_mask.dim() == 5)
         plan = self._plans.get(mode) or self._new_plan(mode, pk, req.shape, values)
         # the plan owns every operand a captured kernel binds: each call, eager or replayed, copies its values into them
         plan["step_part"].copy_(values["step_part"])
@@ -481,10 +514,13 @@ class GaussianDiffusion(nn.Module):
         for rows in plan["fea_term"].chunk(mode.passes):        # (two passes: rows of samples [cond | null])
             rows.copy_(values["fea_term"])
         plan["coef"].copy_(sch.coef)
+        first = req.start_step if req.start is not None else 0
+        if first > 0 and sampler == "dpmpp_2m":         # no history in front of the first step run: first order, in the plan's own copy
+            plan["coef"][first].copy_(self._schedule(ddim, "dpmpp_1", dev).coef[first])
         if mode.known:
             plan["level"].copy_(sch.level)
-        self._draw_start(plan, mode, req, sch.level_host)
-        return self._run_steps(unet, plan, mode, sch.draws)
+        self._draw_start(plan, mode, req, sch.level_host, first)
+        return self._run_steps(unet, plan, mode, sch.draws, first)
 
     @staticmethod
     def _step_operands(unet, pk, sch, fea, cond, cond_scale, batch, s):
@@ -526,23 +562,32 @@ class GaussianDiffusion(nn.Module):
             plan["hist"] = new(*shape)       # m_{i-1}; never cleared: the first step of a video is first order and does not read it
         if mode.noise == "counter":         # one captured graph serves every seed
             plan.update(seeds=torch.zeros(batch, dtype=torch.int64, device=dev), window=torch.zeros(1, dtype=torch.int32, device=dev))
-        if mode.known:                      # another mask / other frames: no new capture
-            plan.update(known=new(*shape), known_noise=new(*shape), kmask=torch.zeros((batch, mode.frames), dtype=torch.bool, device=dev),
-                        level=new(steps + 1, 2))
-        self._plans = {k: v for k, v in self._plans.items() if k.known != mode.known}
+        if mode.known:                      # another mask / other frames or elements: no new capture
+            plan.update(known=new(*shape), known_noise=new(*shape), level=new(steps + 1, 2),
+                        kmask=torch.zeros(tuple(shape) if mode.elem else (batch, mode.frames), dtype=torch.bool, device=dev))
+        self._plans = {k: v for k, v in self._plans.items() if (k.known, k.elem) != (mode.known, mode.elem)}
         self._plans[mode] = plan
         return plan
 
-    def _draw_start(self, plan, mode, req, level_host):
+    def _draw_start(self, plan, mode, req, level_host, first=0):
         """x_T into plan["x"] (:753 / :788); conditioned: one more draw directly behind it (every step draw keeps its place in the order),
-        then x_T's known frames on the init level.  The step counter starts at 0."""
+        then x_T's known frames / elements on the init level.  The step counter starts at 0.  With req.start: the x_T draw z goes to the
+        noise buffer and x <- a start + s z on row `first` of the level table (one blend launch, all-True mask), the known content is placed
+        on that row and the step counter starts at `first`."""
         x, counter = plan["x"], mode.noise == "counter"
+        z = x if req.start is None else plan["noise"]
         if counter:
             ops.seeds_tensor(req.seeds, x.device, out=plan["seeds"])
             plan["window"].fill_(req.window)
-            ops.philox_normal(x, plan["seeds"], stream=ops.NOISE_STREAM_XT, window=req.window)
+            ops.philox_normal(z, plan["seeds"], stream=ops.NOISE_STREAM_XT, window=req.window)
         else:
-            self._draw(x)
+            self._draw(z)
+        if req.start is not None or mode.known:             # (a plain video has asked for no level table)
+            a, s = float(level_host[first, 0]), float(level_host[first, 1])
+        if req.start is not None:
+            if "all" not in plan:
+                plan["all"] = torch.ones(tuple(x.shape), dtype=torch.bool, device=x.device)
+            ops.known_blend_elem(x, req.start.to(x.device).contiguous(), z, plan["all"], a, s)
         if mode.known:
             plan["known"].copy_(req.known)
             plan["kmask"].copy_(req.known_mask)
@@ -550,13 +595,17 @@ class GaussianDiffusion(nn.Module):
                 ops.philox_normal(plan["known_noise"], plan["seeds"], stream=ops.NOISE_STREAM_KNOWN, window=req.window)
             else:
                 self._draw(plan["known_noise"])
-            ops.known_blend(x, plan["known"], plan["known_noise"], plan["kmask"], float(level_host[0, 0]), float(level_host[0, 1]), mode.frames)
-        plan["step"].zero_()
+            if mode.elem:
+                ops.known_blend_elem(x, plan["known"], plan["known_noise"], plan["kmask"], a, s)
+            else:
+                ops.known_blend(x, plan["known"], plan["known_noise"], plan["kmask"], a, s, mode.frames)
+        plan["step"].fill_(first)
 
-    def _run_steps(self, unet, plan, mode, draws):
-        """Every step of the schedule on the plan, eagerly (emulator, LFDM_NO_GRAPH=1) or by graph replay; -> a copy of the final x.
+    def _run_steps(self, unet, plan, mode, draws, first=0):
+        """Steps first .. of the schedule on the plan (the step counter already holds `first`), eagerly (emulator, LFDM_NO_GRAPH=1) or by graph replay; -> a copy of the final x.
         The graphs hold raw pointers into the UNet's scratch arenas: when an eager call in between (Unet3D.forward, p_losses in eval mode,
-        a larger batch) has re-allocated one (`unet._buf_gen` moved), all of the plan's graphs are captured again."""
+        a larger batch) has re-allocated one (`unet._buf_gen` moved), all of the plan's graphs are captured again.  A video that starts
+        at a later step replays the single-step graph up to the next chunk boundary and then the chunk graphs of the full run: no capture."""
         x, noise = plan["x"], plan["noise"]
         use_graph = _native.library().kind == "hip" and os.environ.get("LFDM_NO_GRAPH", "0") != "1"
         draws = [bool(d) and mode.noise != "counter" for d in draws]        # (counter mode: the update kernel computes the step noise)
@@ -569,7 +618,7 @@ class GaussianDiffusion(nn.Module):
         taped = self.noise_source is not None and mode.sampler == "reference" and mode.noise != "counter"
         chunk = int(os.environ.get("LFDM_GRAPH_STEPS", "10")) if use_graph and not taped else 1
         if chunk <= 1:
-            for draw in draws:
+            for draw in draws[first:]:
                 if draw:
                     self._draw(noise)
                 if use_graph:
@@ -577,7 +626,11 @@ class GaussianDiffusion(nn.Module):
                 else:
                     sampler_step(unet, plan, mode)
             return x.clone()
-        for i0 in range(0, len(draws), chunk):
+        for i0 in range(first, min(len(draws), -(-first // chunk) * chunk)):       # up to the chunk grid of the full run, step by step
+            if draws[i0]:
+                self._draw(noise)
+            plan["graph"].replay()
+        for i0 in range(-(-first // chunk) * chunk, len(draws), chunk):
             flags = tuple(draws[i0:i0 + chunk])       # one chunk graph per pattern of draws
             g = plan["chunk_graphs"].get(flags)
             if g is None:

@@ -8,6 +8,7 @@ diffusion loss through the native UNet forward/backward (unet_train.py, autograd
 an optional one-process-per-GPU gradient all-reduce (`enable_data_parallel`).
 """
 import contextlib
+import math
 import os
 
 import torch
@@ -153,18 +154,31 @@ class FlowDiffusion(nn.Module):
             torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count())
 
     # ------------------------------------------------------------------ sampling (a28)
-    def sample_one_video(self, cond_scale, *, known_latent=None, known_mask=None, frame_times=None, interp="linear", seeds=None):
+    def sample_one_video(self, cond_scale, *, known_latent=None, known_mask=None, frame_times=None, interp="linear", seeds=None,
+                         start_latent=None, strength=None):
         """Reference :190-216.  seeds (keyword only; noise="counter"): one integer in [0, 2^64) per video of the batch (GaussianDiffusion.sample).  Results land in sample_vid_grid (B,2,T,S,S), sample_vid_conf (B,1,T,S,S),
         sample_out_vid / sample_warped_vid (B,3,T,H,W), and the latent the diffusion returned (B,3,T,S,S; the residual flow when
         use_residual_flow) in sample_latent.  known_latent (B,3,T,S,S) in that same space + known_mask (B,T) bool (keyword only, both or
         none): GaussianDiffusion.sample's known frames.  frame_times (keyword only; default None: off) + interp: after
-        sampling, decode_at(frame_times, interp) - the four result tensors then hold len(frame_times) frames."""
+        sampling, decode_at(frame_times, interp) - the four result tensors then hold len(frame_times) frames.
+        known_mask may also be 5-D, (B,3,T,S,S) or (B,1,T,S,S) bool: known ELEMENTS of the latent.  start_latent
+        (B,3,T,S,S; e.g. `encode_video` of a real video, or an earlier sample_latent) + strength in (0, 1] (keyword only, both or none): the
+        video is an edit of that latent - the schedule is entered at start_step = steps - ceil(strength * steps) on the latent noised to
+        that level, so strength 1 runs every step and a small strength stays close to the start."""
         if frame_times is not None:
             frame_times = self._check_frame_times(frame_times, interp, self.diffusion.num_frames)
         dm = self.diffusion
+        if (start_latent is None) != (strength is None):
+            raise ValueError("sample_one_video: start_latent and strength go together (both or none)")
+        start_step = 0
+        if strength is not None:
+            if isinstance(strength, bool) or not isinstance(strength, (int, float)) or not 0.0 < strength <= 1.0:
+                raise ValueError("sample_one_video: strength must lie in (0, 1], got %r" % (strength,))
+            steps = dm.sampling_timesteps if dm.is_ddim_sampling or dm.sampler != "reference" else dm.num_timesteps
+            start_step = steps - int(math.ceil(strength * steps - 1e-9))        # (0.3 * 10 = 3.0000000000000004 is three steps)
         with torch.no_grad():                 # (bad known frames / seeds are refused before anything is launched)
             req = dm.check_request((self.sample_img.shape[0], dm.channels, dm.num_frames, dm.image_size, dm.image_size), known_latent, known_mask,
-                                   seeds)
+                                   seeds, 0, start_latent, start_step)
             img, skips, fea = self._source()
             self.sample_latent = pred = dm.sample_checked(fea, self.sample_text, cond_scale, req)
             self._decode_sample(img, skips, pred)
@@ -373,6 +387,37 @@ class FlowDiffusion(nn.Module):
         self.real_vid = real_vid.to(dev)
         self.ref_text = ref_text
 
+    def _lfae_pass(self, real_vid, ref_img, decode):
+        """The frozen LFAE on every frame of real_vid against ref_img, all B*T frames in one batched pass -> Generator.forward_frames' dict
+        (optical_flow (B,2,T,S,S), occlusion_map (B,1,T,S,S), bottle_neck_feat; decode: as forward_frames' - True: prediction / deformed, False: the callable
+        that makes them)."""
+        b, _, nf, H, W = real_vid.shape
+        with torch.no_grad():
+            ref = ref_img.float().contiguous()
+            frames = real_vid.float().permute(0, 2, 1, 3, 4).reshape(b * nf, -1, H, W).contiguous()
+            source_region_params = self.region_predictor(ref)
+            driving_region_params = self.region_predictor(frames)
+            ref_rep = ref.unsqueeze(1).expand(b, nf, *ref.shape[1:]).reshape(b * nf, *ref.shape[1:])
+            bg_params = self.bg_predictor(ref_rep, frames)
+            return self.generator.forward_frames(ref, nf, driving_region_params, source_region_params, bg_params, decode=decode)
+
+    def _latent_of(self, grid, conf):
+        """The latent the diffusion denoises from the LFAE's sampling grid and occlusion map: grid minus identity under use_residual_flow,
+        occlusion * 2 - 1."""
+        if self.use_residual_flow:
+            b, _, nf, h, w = grid.shape
+            grid = grid - self.get_grid(b, nf, h, w, normalize=True).to(grid.device)
+        return torch.cat((grid, conf * 2 - 1), dim=1)
+
+    def encode_video(self, real_vid, ref_img):
+        """The latent (B, 3, T, S, S) of a real video (B, 3, T, H, W) relative to ref_img (B, 3, H, W), in the space the diffusion denoises
+        and sample_one_video(known_latent= / start_latent=) takes: the LFAE pass of the training step without the decode and without the
+        diffusion.  Independent of is_train."""
+        dev = next(self.unet.parameters()).device
+        generated = self._lfae_pass(real_vid.to(dev), ref_img.to(dev), False)
+        with torch.no_grad():
+            return self._latent_of(generated["optical_flow"], generated["occlusion_map"]).contiguous()
+
     def _train_forward(self, real_vid, ref_img, ref_text, lazy_real=False):
         """Shared body of `forward` (reference :116-179) and of the functional *_multiGPU flavour
         (video_flow_diffusion_model_multiGPU.py:89-157): pseudo ground-truth flow / occlusion of every frame from
@@ -381,14 +426,8 @@ class FlowDiffusion(nn.Module):
         b, _, nf, H, W = real_vid.shape
         gen = self.generator
         out = {}
-        with torch.no_grad():
-            ref = ref_img.float().contiguous()
-            frames = real_vid.float().permute(0, 2, 1, 3, 4).reshape(b * nf, -1, H, W).contiguous()
-            source_region_params = self.region_predictor(ref)
-            driving_region_params = self.region_predictor(frames)
-            ref_rep = ref.unsqueeze(1).expand(b, nf, *ref.shape[1:]).reshape(b * nf, *ref.shape[1:])
-            bg_params = self.bg_predictor(ref_rep, frames)
-            generated = gen.forward_frames(ref, nf, driving_region_params, source_region_params, bg_params, decode=not lazy_real)
+        ref = ref_img.float().contiguous()
+        generated = self._lfae_pass(real_vid, ref_img, not lazy_real)
         out["real_vid_grid"] = generated["optical_flow"]
         out["real_vid_conf"] = generated["occlusion_map"]
         if lazy_real:
@@ -572,8 +611,8 @@ class FlowDiffusionFunctional(FlowDiffusion):
         return out
 
     def sample_one_video(self, sample_img, sample_text, cond_scale, *, known_latent=None, known_mask=None, frame_times=None, interp="linear",
-                         seeds=None):
+                         seeds=None, start_latent=None, strength=None):
         self.set_sample_input(sample_img=sample_img, sample_text=sample_text)
         FlowDiffusion.sample_one_video(self, cond_scale, known_latent=known_latent, known_mask=known_mask, frame_times=frame_times,
-                                       interp=interp, seeds=seeds)
+                                       interp=interp, seeds=seeds, start_latent=start_latent, strength=strength)
         return {k: getattr(self, k) for k in ("sample_vid_grid", "sample_vid_conf", "sample_out_vid", "sample_warped_vid", "sample_latent")}

@@ -942,6 +942,33 @@ def _known_operands(what, x, known, known_noise, frame_mask, level, frames, need
     return frames, frame_elems
 
 
+def _known_elem_operands(what, x, known, known_noise, elem_mask, level, need_level=True):
+    """The element-mask form of the known operands: known, known_noise, elem_mask [, level], all of them.  elem_mask: bool /
+    uint8 with x's shape (one byte per element).  -> the marker "elem" that `_sampler_step` takes in place of (frames, frame_elems)."""
+    given = [known is not None, known_noise is not None] + ([level is not None] if need_level else [])
+    if not all(given):
+        raise ValueError("%s: known, known_noise, elem_mask%s go together (all of them or none)" % (what, ", level" if need_level else ""))
+    for name, t in (("known", known), ("known_noise", known_noise)):
+        if t.dtype != torch.float32 or t.numel() != x.numel() or not t.is_contiguous() or t.device != x.device:
+            raise ValueError("%s: %s must be a contiguous float32 tensor of x's %d elements on x's device" % (what, name, x.numel()))
+    if elem_mask.dtype not in (torch.bool, torch.uint8) or tuple(elem_mask.shape) != tuple(x.shape) or not elem_mask.is_contiguous() \
+            or elem_mask.device != x.device:
+        raise ValueError("%s: elem_mask must be a contiguous bool / uint8 tensor of x's shape %s on x's device" % (what, tuple(x.shape)))
+    if need_level and (level.dtype != torch.float32 or level.dim() != 2 or level.shape[1] != 2 or not level.is_contiguous()
+                       or level.device != x.device):
+        raise ValueError("%s: level must be a contiguous (steps + 1, 2) float32 tensor on x's device" % what)
+    return "elem"
+
+
+def _known_either(what, x, known, known_noise, frame_mask, level, frames, elem_mask):
+    """frame_mask= / frames= or elem_mask=: one of the two forms, never both."""
+    if elem_mask is None:
+        return _known_operands(what, x, known, known_noise, frame_mask, level, frames), frame_mask
+    if frame_mask is not None or frames is not None:
+        raise ValueError("%s: elem_mask and frame_mask / frames exclude each other" % what)
+    return _known_elem_operands(what, x, known, known_noise, elem_mask, level), elem_mask
+
+
 NOISE_STREAM_XT, NOISE_STREAM_KNOWN, NOISE_STREAM_STEP = 0, 1, 2       # counter word `stream` of the counter-based noise (csrc/lfdm_philox.h)
 
 
@@ -1019,34 +1046,39 @@ def philox_bits(out, seeds, *, stream, step=0, window=0):
 _SAMPLER_STEP = {      # (multistep, counter noise, known frames) -> C entry point
     (False, False, False): "lfdm_sampler_step_f32", (False, False, True): "lfdm_sampler_step_known_f32",
     (False, True, False): "lfdm_sampler_step_counter_f32", (False, True, True): "lfdm_sampler_step_counter_known_f32",
-    (True, False, False): "lfdm_sampler_step_ms_f32", (True, False, True): "lfdm_sampler_step_ms_known_f32"}
+    (True, False, False): "lfdm_sampler_step_ms_f32", (True, False, True): "lfdm_sampler_step_ms_known_f32",
+    (False, False, "elem"): "lfdm_sampler_step_elem_f32", (False, True, "elem"): "lfdm_sampler_step_counter_elem_f32",
+    (True, False, "elem"): "lfdm_sampler_step_ms_elem_f32"}
 
 
 def _sampler_step(lib, multistep, x, eps, third, coef, step_dev, quantile, advance, x0_out, ws, kf, known_operands, seeds=None, window=None):
     """The one call behind sampler_step / sampler_step_ms (operands already checked): the common argument list, with (seeds, window) in
-    place of the third tensor (noise / hist) in counter mode and the known-frame tail when kf = (frames, frame_elems) is given."""
+    place of the third tensor (noise / hist) in counter mode and the known-frame tail when kf = (frames, frame_elems) is given - or the
+    element-mask tail (no frame split) when kf = "elem"."""
     batch = x.shape[0]
     if ws is None:
         ws = sampler_ws(batch, x.numel() // batch, x.device)
-    name = _SAMPLER_STEP[(multistep, seeds is not None, kf is not None)]
+    name = _SAMPLER_STEP[(multistep, seeds is not None, "elem" if kf == "elem" else kf is not None)]
     args = [_p(x), _p(eps)] + ([_p(third)] if seeds is None else [_p(seeds), _p(window)])
     args += [_p(x0_out), batch, x.numel() // batch, _p(coef), _p(step_dev), quantile, int(advance), _p(ws), ws.numel() * 4]
     if kf is not None:
-        args += [_p(t) for t in known_operands] + [kf[0], kf[1]]
+        args += [_p(t) for t in known_operands] + ([] if kf == "elem" else [kf[0], kf[1]])
     lib.check(getattr(lib, name)(*args, _stream(lib)), name)
     return x
 
 
 def sampler_step(x, eps, noise, coef, step_dev, *, quantile=0.9, advance=True, x0_out=None, ws=None,
-                 known=None, known_noise=None, frame_mask=None, level=None, frames=None, seeds=None, window=None):
+                 known=None, known_noise=None, frame_mask=None, level=None, frames=None, seeds=None, window=None, elem_mask=None):
     """lfdm_sampler_step_f32; with the five known-frame keywords (all or none) lfdm_sampler_step_known_f32: frames whose frame_mask[b, t] is set
     are stored as level[step + 1] = (a, s) applied to (known, known_noise) instead of the update's result.
     seeds (int64 device tensor (B), ops.seeds_tensor) + window (int32 device tensor of one word), both or none, with noise=None:
     lfdm_sampler_step_counter_f32 / _known_f32 - the step noise is computed inside the update kernel from (seeds[b], window, step) and is
-    bit for bit what philox_normal(stream=2, step=the step counter's value, window=window) writes."""
+    bit for bit what philox_normal(stream=2, step=the step counter's value, window=window) writes.
+    elem_mask (bool / uint8 of x's shape) in place of frame_mask / frames: lfdm_sampler_step_elem_f32 / _counter_elem_f32 - one mask byte per
+    element; passing both forms is refused."""
     lib = _lib()
     _chk(lib, x, eps, noise, coef, step_dev, x0_out, ws)
-    kf = _known_operands("sampler_step", x, known, known_noise, frame_mask, level, frames)
+    kf, mask = _known_either("sampler_step", x, known, known_noise, frame_mask, level, frames, elem_mask)
     batch = x.shape[0]
     if (seeds is None) != (window is None):
         raise ValueError("sampler_step: seeds and window go together (both or none)")
@@ -1056,21 +1088,21 @@ def sampler_step(x, eps, noise, coef, step_dev, *, quantile=0.9, advance=True, x
         seeds = _seed_operand("sampler_step", lib, seeds, batch, x.device)
         if not torch.is_tensor(window) or window.dtype != torch.int32 or window.numel() != 1 or window.device != x.device:
             raise ValueError("sampler_step: window must be an int32 tensor of one word on x's device")
-    return _sampler_step(lib, False, x, eps, noise, coef, step_dev, quantile, advance, x0_out, ws, kf, (known, known_noise, frame_mask, level), seeds, window)
+    return _sampler_step(lib, False, x, eps, noise, coef, step_dev, quantile, advance, x0_out, ws, kf, (known, known_noise, mask, level), seeds, window)
 
 
 def sampler_step_ms(x, eps, hist, coef, step_dev, *, quantile=0.9, advance=True, x0_out=None, ws=None,
-                    known=None, known_noise=None, frame_mask=None, level=None, frames=None):
+                    known=None, known_noise=None, frame_mask=None, level=None, frames=None, elem_mask=None):
     """lfdm_sampler_step_ms_f32: x <- k_x*x + k_m*m + k_prev*hist, hist <- m (the thresholded data prediction of this step);
     coef rows {c_x, c_eps, k_x, k_m, k_prev, 0} (GaussianDiffusion._ms_step_tables).  Known-frame keywords as sampler_step
-    (lfdm_sampler_step_ms_known_f32)."""
+    (lfdm_sampler_step_ms_known_f32; elem_mask=: lfdm_sampler_step_ms_elem_f32)."""
     lib = _lib()
     _chk(lib, x, eps, hist, coef, step_dev, x0_out, ws)
-    kf = _known_operands("sampler_step_ms", x, known, known_noise, frame_mask, level, frames)
+    kf, mask = _known_either("sampler_step_ms", x, known, known_noise, frame_mask, level, frames, elem_mask)
     batch = x.shape[0]
     if hist.numel() != x.numel():
         raise ValueError("sampler_step_ms: hist must have x's %d elements, got %d" % (x.numel(), hist.numel()))
-    return _sampler_step(lib, True, x, eps, hist, coef, step_dev, quantile, advance, x0_out, ws, kf, (known, known_noise, frame_mask, level))
+    return _sampler_step(lib, True, x, eps, hist, coef, step_dev, quantile, advance, x0_out, ws, kf, (known, known_noise, mask, level))
 
 
 def known_blend(x, known, known_noise, frame_mask, a, s, frames):
@@ -1083,6 +1115,23 @@ def known_blend(x, known, known_noise, frame_mask, a, s, frames):
     batch = x.shape[0]
     lib.check(lib.lfdm_known_blend_f32(_p(x), _p(known), _p(known_noise), _p(frame_mask), float(a), float(s), batch, x.numel() // batch,
                                        fr, frame_elems, _stream(lib)), "lfdm_known_blend_f32")
+    return x
+
+
+def known_blend_elem(x, known, known_noise, elem_mask, a, s):
+    """lfdm_known_blend_elem_f32: x[e] <- a * known[e] + s * known_noise[e] where elem_mask[e] (bool / uint8 of x's shape): the x_T blend of an
+    element-conditioned video and, with an all-True mask, the entry of a schedule on a given latent."""
+    lib = _lib()
+    _chk(lib, x, known, known_noise)
+    if known is None or known_noise is None or elem_mask is None:
+        raise ValueError("known_blend_elem: known, known_noise and elem_mask are required")
+    _known_elem_operands("known_blend_elem", x, known, known_noise, elem_mask, None, need_level=False)
+    for t in (known, known_noise):
+        if t.data_ptr() == x.data_ptr():
+            raise ValueError("known_blend_elem: x must not alias known or known_noise")
+    batch = x.shape[0]
+    lib.check(lib.lfdm_known_blend_elem_f32(_p(x), _p(known), _p(known_noise), _p(elem_mask), float(a), float(s), batch, x.numel() // batch,
+                                            _stream(lib)), "lfdm_known_blend_elem_f32")
     return x
 
 

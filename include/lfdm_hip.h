@@ -382,6 +382,25 @@ int lfdm_sampler_step_ms_known_f32(float* x, const float* eps, float* hist, floa
 /* the same select with host scalars, for x_T (once per video, outside the replayed step): x <- a * known + s * known_noise at marked frames */
 int lfdm_known_blend_f32(float* x, const float* known, const float* known_noise, const unsigned char* frame_mask, float a, float s,
                          int batch, int64_t n, int frames, int64_t frame_elems, lfdm_stream_t stream);
+/* Per-element known masks (additive, ABI version unchanged): the known select above with one mask byte per ELEMENT:
+ *   x[b, i] <- a * known[b, i] + s * known_noise[b, i]     where elem_mask[b * n + i] != 0,   (a, s) = level[2 * (step + 1)]
+ * There is no frame split: any subset of a sample's n elements can be marked (a region of every frame, one channel, one pixel).  Everything
+ * else is lfdm_sampler_step_known_f32's: a select, never a blend (known / known_noise at unmarked elements may be NaN or uninitialised), and
+ * x0, the threshold over the whole sample, x0_out, hist, the step counter and the launch sequence are the plain step's.  Null known operands
+ * or n outside (0, 2^24) return LFDM_EINVAL. */
+/* Layout: x, eps, noise, x0_out, known, known_noise dense (B, n) fp32; elem_mask dense (B, n) bytes; coef, step_dev, level dense. */
+int lfdm_sampler_step_elem_f32(float* x, const float* eps, const float* noise, float* x0_out, int batch, int64_t n, const float* coef,
+                               int32_t* step_dev, float quantile, int advance, void* ws, size_t ws_bytes, const float* known,
+                               const float* known_noise, const unsigned char* elem_mask, const float* level, lfdm_stream_t stream);
+/* Layout: as lfdm_sampler_step_elem_f32, hist dense (B, n) in place of noise. */
+int lfdm_sampler_step_ms_elem_f32(float* x, const float* eps, float* hist, float* x0_out, int batch, int64_t n, const float* coef,
+                                  int32_t* step_dev, float quantile, int advance, void* ws, size_t ws_bytes, const float* known,
+                                  const float* known_noise, const unsigned char* elem_mask, const float* level, lfdm_stream_t stream);
+/* the element-mask select with host scalars (x_T of a conditioned video; with an all-set mask: x <- a * known + s * known_noise everywhere,
+ * the entry of a schedule on a given latent) */
+/* Layout: x, known, known_noise dense (B, n) fp32; elem_mask dense (B, n) bytes.  x must not alias known or known_noise. */
+int lfdm_known_blend_elem_f32(float* x, const float* known, const float* known_noise, const unsigned char* elem_mask, float a, float s,
+                              int batch, int64_t n, lfdm_stream_t stream);
 /* Counter-based noise (additive, ABI version unchanged; DESIGN.md 4.10, csrc/lfdm_philox.h): every normal is a pure function of
  * (video seed, window, stream, step, element).  Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85,
  * ten rounds) with key = (seed & 0xffffffff, seed >> 32) and counter = (i >> 2, step, stream_id, window) gives four words r0..r3 for the quad
@@ -412,6 +431,11 @@ int lfdm_sampler_step_counter_known_f32(float* x, const float* eps, const uint64
                                         int64_t n, const float* coef, int32_t* step_dev, float quantile, int advance, void* ws,
                                         size_t ws_bytes, const float* known, const float* known_noise, const unsigned char* frame_mask,
                                         const float* level, int frames, int64_t frame_elems, lfdm_stream_t stream);
+/* Layout: as lfdm_sampler_step_counter_f32, elem_mask dense (B, n) bytes (lfdm_sampler_step_elem_f32 with the step noise computed). */
+int lfdm_sampler_step_counter_elem_f32(float* x, const float* eps, const uint64_t* seeds, const uint32_t* window, float* x0_out, int batch,
+                                       int64_t n, const float* coef, int32_t* step_dev, float quantile, int advance, void* ws,
+                                       size_t ws_bytes, const float* known, const float* known_noise, const unsigned char* elem_mask,
+                                       const float* level, lfdm_stream_t stream);
 /* classifier-free guidance combine of Unet3D.forward_with_cond_scale (:525-526):
  * out = null_eps + (cond_eps - null_eps) * scale   (out may alias an input) */
 /* Layout: dense, any; out may alias cond_eps or null_eps. */

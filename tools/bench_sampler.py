@@ -1,6 +1,7 @@
 #!/usr/bin/env python
-"""lfdm_sampler_step_f32 and lfdm_sampler_step_ms_f32, plain and with known frames (8 of the 40, lfdm_sampler_step_*_known_f32), at the C2
-latent (B=1, 3x40x32x32): us per step (graph replay), alternating."""
+"""lfdm_sampler_step_f32 and lfdm_sampler_step_ms_f32, plain, with known frames (8 of the 40, lfdm_sampler_step_*_known_f32) and with known
+elements (the same 8 frames as an element mask, and a box of a quarter of every frame; lfdm_sampler_step_*_elem_f32), at the C2 latent
+(B=1, 3x40x32x32): us per step (graph replay), alternating."""
 import os
 import statistics
 import sys
@@ -31,10 +32,19 @@ for b, shape in ((1, (3, 40, 32, 32)), (16, (3, 40, 32, 32)), (4, (3, 40, 64, 64
     mask[:, :8] = True
     kf = dict(known=torch.randn(b, *shape, device="cuda"), known_noise=torch.randn(b, *shape, device="cuda"), frame_mask=mask,
               level=torch.rand(5, 2, device="cuda"), frames=shape[1])
+    common = {k: v for k, v in kf.items() if k not in ("frame_mask", "frames")}
+    emask = mask[:, None, :, None, None].expand(b, *shape).contiguous()          # the frame mask, one byte per element
+    box = torch.zeros(b, *shape, dtype=torch.bool, device="cuda")
+    box[..., :shape[2] // 2, :shape[3] // 2] = True                               # a quarter of every frame
+    ke, kb = dict(common, elem_mask=emask), dict(common, elem_mask=box)
     fns = {"sampler_step": lambda: ops.sampler_step(x, eps, noise, table, step, ws=ws, advance=False),
            "sampler_step_ms": lambda: ops.sampler_step_ms(x, eps, hist, table, step, ws=ws, advance=False),
            "sampler_step known": lambda: ops.sampler_step(x, eps, noise, table, step, ws=ws, advance=False, **kf),
-           "sampler_step_ms known": lambda: ops.sampler_step_ms(x, eps, hist, table, step, ws=ws, advance=False, **kf)}
+           "sampler_step_ms known": lambda: ops.sampler_step_ms(x, eps, hist, table, step, ws=ws, advance=False, **kf),
+           "sampler_step elem": lambda: ops.sampler_step(x, eps, noise, table, step, ws=ws, advance=False, **ke),
+           "sampler_step_ms elem": lambda: ops.sampler_step_ms(x, eps, hist, table, step, ws=ws, advance=False, **ke),
+           "sampler_step elem box": lambda: ops.sampler_step(x, eps, noise, table, step, ws=ws, advance=False, **kb),
+           "sampler_step_ms elem box": lambda: ops.sampler_step_ms(x, eps, hist, table, step, ws=ws, advance=False, **kb)}
     graphs = {}
     for name, fn in fns.items():
         for _ in range(3):
@@ -49,5 +59,5 @@ for b, shape in ((1, (3, 40, 32, 32)), (16, (3, 40, 32, 32)), (4, (3, 40, 64, 64
     for _ in range(5):
         for name, g in graphs.items():
             times[name].append(replay_us(g))
-    print("B=%2d n=%7d: %s" % (b, n, ",  ".join("%s %.1f us per step (min %.1f, max %.1f)" % (k, statistics.median(t), min(t), max(t))
+    print("B=%2d n=%7d:\n  %s" % (b, n, "\n  ".join("%s %.1f us per step (min %.1f, max %.1f)" % (k, statistics.median(t), min(t), max(t))
                                                   for k, t in times.items())))

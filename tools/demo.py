@@ -11,6 +11,7 @@ misc.flow2fig, not grid2fig's drawing) and --gif indexed writes its palette indi
     python tools/demo.py --synthetic --render device --gif indexed --out demo_out       # strip and palette indices made on the GPU
     python tools/demo.py --synthetic --fps-factor 4 --render device --gif indexed      # 157 frames decoded from the 40 sampled ones
     python tools/demo.py --synthetic --noise counter --video-seeds 7,8,9 --batch 3   # three videos, each a function of its own seed
+    python tools/demo.py --synthetic --from-video DIR --strength 0.5 --keep-box 0,0,16,32    # edit a video: keep the upper half of its latent
     python tools/demo.py --synthetic --out demo_out        # random-init weights, random image, fixed embedding:
                                                             # exercises the whole pipeline where no checkpoint exists
 """
@@ -74,7 +75,66 @@ def build_parser():
     ap.add_argument("--batch", type=int, default=1, help="videos sampled at once per text prompt (same image and prompt; they differ in their noise)")
     ap.add_argument("--reverse", action="store_true", help="play the sampled motion backwards")
     ap.add_argument("--pingpong", action="store_true", help="forward, then back: a GIF that loops seamlessly")
+    ap.add_argument("--from-video", default="",
+                    help="edit an existing video (DESIGN.md 4.11): a folder of frames (sorted by name; the first --frames are read, the first "
+                         "one is the source image unless --image is given), encoded to a latent by the LFAE (FlowDiffusion.encode_video); "
+                         "with --synthetic and no readable folder a synthetic video is used")
+    ap.add_argument("--strength", type=float, default=None,
+                    help="--from-video: in (0, 1] - how far the video is noised before it is denoised again; the last ceil(strength * steps) "
+                         "steps run (1: all of them, only the known box then ties the result to the video)")
+    ap.add_argument("--keep-box", default="", help="--from-video: y0,x0,y1,x1 in latent pixels (size / 4) - kept from the encoded video in "
+                                                   "every frame, the rest is regenerated")
+    ap.add_argument("--regen-box", default="", help="--from-video: y0,x0,y1,x1 in latent pixels - regenerated, everything else is kept")
     return ap
+
+
+def parse_box(text, size):
+    """'y0,x0,y1,x1' -> the four integers, 0 <= y0 < y1 <= size and 0 <= x0 < x1 <= size; ValueError otherwise."""
+    try:
+        y0, x0, y1, x1 = (int(v) for v in text.split(","))
+    except ValueError:
+        raise ValueError("a box is four comma-separated integers y0,x0,y1,x1, got %r" % (text,))
+    if not (0 <= y0 < y1 <= size and 0 <= x0 < x1 <= size):
+        raise ValueError("box %r does not lie inside the %d x %d latent (0 <= y0 < y1 <= %d, 0 <= x0 < x1 <= %d)" % (text, size, size, size, size))
+    return y0, x0, y1, x1
+
+
+def box_mask(shape, box, keep):
+    """The (B, 1, T, S, S) bool known-element mask of a latent of `shape`: True inside `box` (keep) or outside it (keep=False), every frame."""
+    b, _, t, s, _ = shape
+    y0, x0, y1, x1 = box
+    mask = torch.zeros((b, 1, t, s, s), dtype=torch.bool)
+    mask[:, :, :, y0:y1, x0:x1] = True
+    return mask if keep else ~mask
+
+
+def read_video(args, ref):
+    """(B = 1, 3, --frames, size, size) in [0, 1] on the GPU: the frames of --from-video, or the synthetic stand-in (a slow drift of `ref`)."""
+    names = sorted(os.listdir(args.from_video)) if os.path.isdir(args.from_video) else []
+    if names:
+        if len(names) < args.frames:
+            sys.exit("--from-video: %s holds %d frames, --frames %d are needed" % (args.from_video, len(names), args.frames))
+        frames = [C.resize(C.imread(os.path.join(args.from_video, n))[:, :, :3], args.size, interpolation=C.INTER_AREA) for n in names[:args.frames]]
+        vid = torch.from_numpy(np.stack([np.asarray(f, np.float32) / 255.0 for f in frames])).permute(3, 0, 1, 2).unsqueeze(0)
+        return vid.cuda().contiguous()
+    if not args.synthetic:
+        sys.exit("--from-video: %r is no folder of frames" % args.from_video)
+    shifts = [int(round(3 * np.sin(2 * np.pi * f / args.frames))) for f in range(args.frames)]
+    return torch.stack([torch.roll(ref[0], shifts=(sh, -sh), dims=(1, 2)) for sh in shifts], dim=1).unsqueeze(0).contiguous()
+
+
+def edit_arguments(args, model, ref):
+    """The sample_one_video keywords of --from-video / --strength / --keep-box / --regen-box (empty without --from-video)."""
+    if not args.from_video:
+        return {}
+    latent = model.encode_video(read_video(args, ref), ref)
+    latent = latent.expand(args.batch, -1, -1, -1, -1).contiguous()
+    kw = dict(start_latent=latent, strength=1.0 if args.strength is None else args.strength)
+    box = args.keep_box or args.regen_box
+    if box:
+        mask = box_mask(tuple(latent.shape), parse_box(box, args.size // 4), keep=bool(args.keep_box))
+        kw.update(known_latent=latent, known_mask=mask.cuda())
+    return kw
 
 
 def retime(args, frames):
@@ -96,6 +156,20 @@ def check_args(args):
         sys.exit("--batch must be at least 1")
     if (args.video_seeds or args.save_latents) and args.noise != "counter":
         sys.exit("--video-seeds / --save-latents need --noise counter")
+    if (args.strength is not None or args.keep_box or args.regen_box) and not args.from_video:
+        sys.exit("--strength / --keep-box / --regen-box need --from-video")
+    if args.keep_box and args.regen_box:
+        sys.exit("--keep-box and --regen-box exclude each other (one is the complement of the other)")
+    if args.strength is not None and not 0.0 < args.strength <= 1.0:
+        sys.exit("--strength must lie in (0, 1]")
+    if args.from_video and args.total_frames > 0:
+        sys.exit("--from-video edits one window of --frames: it does not combine with --total-frames")
+    for box in (args.keep_box, args.regen_box):
+        if box:
+            try:
+                parse_box(box, args.size // 4)
+            except ValueError as e:
+                sys.exit(str(e))
 
 
 def video_seeds(args):
@@ -166,6 +240,10 @@ def main():
     np.random.seed(args.seed)
 
     model = make_model(args)
+    if args.synthetic and args.from_video:          # the LFAE's two predictors encode the video: synthetic weights for them too
+        import synth
+        model.region_predictor.load_state_dict(synth.region_state())
+        model.bg_predictor.load_state_dict(synth.bg_state())
     model.cuda().eval()
 
     if args.image:
@@ -175,6 +253,7 @@ def main():
     ref = torch.from_numpy(np.asarray(img, np.float32) / 255.0).permute(2, 0, 1).unsqueeze(0).cuda()
     seeds = video_seeds(args)
     skw = {} if seeds is None else dict(seeds=seeds)
+    skw.update(edit_arguments(args, model, ref))
     name = os.path.splitext(os.path.basename(args.image))[0] if args.image else "random"
     for i, text in enumerate(args.text):
         torch.cuda.synchronize()

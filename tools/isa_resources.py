@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""Kernel resources from the gfx950 ISA hipcc emits (no GPU needed): registers, scratch, LDS, occupancy, code length and the counts of
-MFMA, s_nop and branch instructions of every kernel of the given csrc/*.hip files, for this tree or for another checkout of it.
+"""Kernel resources from the gfx950 ISA hipcc emits (no GPU needed): registers, scratch, LDS, occupancy, code length, the instruction count
+and the counts of MFMA, s_nop and branch instructions of every kernel of the given csrc/*.hip files, for this tree or for another checkout of it.
 LFDM_ISA_FLAGS in the environment adds compiler flags (a probe build's -D switch).
 
     tools/isa_resources.py scan OUT.json [--root DIR] file.hip ...     DIR: the checkout whose cvpr23_lfdm_amd/csrc holds the files (default: this tree)
@@ -17,7 +17,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-mllvm", "-amdgpu-mfma-vgpr-form", "-S", "--cuda-device-only"]
-FIELDS = ["VGPRs", "scratch", "LDS", "occ", "codeLen", "MFMA", "s_nop", "branch"]
+FIELDS = ["VGPRs", "scratch", "LDS", "occ", "codeLen", "insts", "MFMA", "s_nop", "branch"]
 
 
 def demangle(name):
@@ -45,7 +45,7 @@ def scan(root, files):
                 return int(mm.group(1)) if mm else -1
             res["%s %s" % (os.path.basename(f)[:-4], demangle(name))] = {
                 "VGPRs": note("NumVgprs") if note("TotalNumVgprs") < 0 else note("TotalNumVgprs"), "scratch": note("ScratchSize"),
-                "LDS": note("LDSByteSize"), "occ": note(r"Occupancy"), "codeLen": note("codeLenInByte"),
+                "LDS": note("LDSByteSize"), "occ": note(r"Occupancy"), "codeLen": note("codeLenInByte"), "insts": len(insts),
                 "MFMA": sum(i.startswith("v_mfma") for i in insts), "s_nop": sum(i.startswith("s_nop") for i in insts),
                 "branch": sum(i.startswith(("s_cbranch", "s_branch")) for i in insts)}
     return res
