@@ -16,6 +16,14 @@ def _ws(lib_bytes, like):
     return torch.empty(max(n, 1), dtype=torch.float32, device=like.device)
 
 
+def _dest(t, shape, like):
+    """A result tensor: the caller's destination (dense float32 of `shape` on the operands' device), or a new one."""
+    if t is None:
+        return torch.empty(tuple(shape), dtype=torch.float32, device=like.device)
+    assert t.is_contiguous() and t.dtype == torch.float32 and t.device == like.device and tuple(t.shape) == tuple(shape)
+    return t
+
+
 def sum_leading(x, s, n, out=None):
     lib = _lib()
     _chk(lib, x, out)
@@ -78,33 +86,36 @@ def gn_forward_chunks(pixels):
     return min(max((pixels + 15) // 16, 1), 256)
 
 
-def groupnorm_silu_train(x, batch, gamma, beta, scale_shift=None, residual=None, groups=8, eps=1e-5, silu=True):
-    """Forward for training: out-of-place, returns (y, partial) with partial = the statistics the backward needs."""
+def groupnorm_silu_train(x, batch, gamma, beta, scale_shift=None, residual=None, groups=8, eps=1e-5, silu=True, out=None):
+    """Forward for training: out-of-place, returns (y, partial, nchunk) with partial = the statistics the backward needs.
+    out: optional destination for y (nothing is written to it when the shape is refused)."""
     from . import ops
     lib = _lib()
     rows, c = x.shape
     pixels = rows // batch
     nbytes = lib.lfdm_groupnorm_ws_bytes(batch, pixels, c)
     ws = _ws(nbytes, x)
-    y = torch.empty_like(x)
+    y = _dest(out, x.shape, x)
     ops.groupnorm_silu_cl(x, batch, gamma, beta, scale_shift=scale_shift, residual=residual, groups=groups, eps=eps,
                           silu=silu, out=y, ws=ws)
     nchunk = gn_forward_chunks(pixels)
     return y, ws[: batch * nchunk * groups * 2], nchunk
 
 
-def groupnorm_silu_bwd(x, dy, batch, gamma, beta, partial, nchunk, scale_shift=None, groups=8, eps=1e-5, silu=True, dgb=None):
-    """-> (dx, dgamma, dbeta, dscale_shift or None).  dgb: optional contiguous (2, C) tensor that receives [dgamma | dbeta]."""
+def groupnorm_silu_bwd(x, dy, batch, gamma, beta, partial, nchunk, scale_shift=None, groups=8, eps=1e-5, silu=True, dgb=None,
+                       dx=None, dss=None):
+    """-> (dx, dgamma, dbeta, dscale_shift or None).  dgb: optional contiguous (2, C) tensor that receives [dgamma | dbeta]; dx, dss: optional
+    destinations (x's shape; (batch, 2 C) with scale_shift).  Nothing is written to any of them when the shape is refused."""
     lib = _lib()
-    _chk(lib, x, dy, gamma, beta, partial, scale_shift, dgb)
+    _chk(lib, x, dy, gamma, beta, partial, scale_shift, dgb, dx, dss)
     rows, c = x.shape
     pixels = rows // batch
     assert x.is_contiguous() and dy.is_contiguous()
-    dx = torch.empty_like(x)
+    dx = _dest(dx, x.shape, x)
     if dgb is None:
         dgb = torch.empty(2, c, dtype=torch.float32, device=x.device)
     assert dgb.is_contiguous() and dgb.numel() == 2 * c
-    dss = torch.empty(batch, 2 * c, dtype=torch.float32, device=x.device) if scale_shift is not None else None
+    dss = _dest(dss, (batch, 2 * c), x) if scale_shift is not None else None
     nbytes = lib.lfdm_groupnorm_bwd_ws_bytes(batch, pixels, c)
     ws = _ws(nbytes, x)
     lib.check(lib.lfdm_groupnorm_silu_bwd_cl_f32(
@@ -114,14 +125,14 @@ def groupnorm_silu_bwd(x, dy, batch, gamma, beta, partial, nchunk, scale_shift=N
     return dx, dgb[0], dgb[1], dss
 
 
-def layernorm_bwd(x, dy, gamma, eps=1e-5, dgamma=None, dx_add=None):
+def layernorm_bwd(x, dy, gamma, eps=1e-5, dgamma=None, dx_add=None, dx=None):
     """-> (dx, dgamma).  dgamma: optional contiguous tensor of C elements that receives the gamma gradient; dx_add: optional second
-    gradient of x (same shape) summed into dx by the kernel."""
+    gradient of x (same shape) summed into dx by the kernel; dx: optional destination of x's shape."""
     lib = _lib()
-    _chk(lib, x, dy, gamma, dgamma, dx_add)
+    _chk(lib, x, dy, gamma, dgamma, dx_add, dx)
     rows, c = x.shape
     assert x.is_contiguous() and dy.is_contiguous() and (dx_add is None or (dx_add.is_contiguous() and dx_add.shape == x.shape))
-    dx = torch.empty_like(x)
+    dx = _dest(dx, x.shape, x)
     if dgamma is None:
         dgamma = torch.empty(c, dtype=torch.float32, device=x.device)
     assert dgamma.is_contiguous() and dgamma.numel() == c
@@ -132,16 +143,18 @@ def layernorm_bwd(x, dy, gamma, eps=1e-5, dgamma=None, dx_add=None):
     return dx, dgamma
 
 
-def attention_bwd(qkv, dout, batch, frames, hw, mode, bias=None, rot_cos=None, rot_sin=None):
-    """-> (dqkv rows of 768, dbias (8, L, L) or None)."""
+def attention_bwd(qkv, dout, batch, frames, hw, mode, bias=None, rot_cos=None, rot_sin=None, dqkv=None, dbias=None):
+    """-> (dqkv rows of 768, dbias (8, L, L) or None).  dqkv, dbias: optional destinations (dbias only with a bias)."""
     lib = _lib()
-    _chk(lib, qkv, dout, bias, rot_cos, rot_sin)
+    _chk(lib, qkv, dout, bias, rot_cos, rot_sin, dqkv, dbias)
     assert qkv.is_contiguous() and dout.is_contiguous() and qkv.shape[1] == 768 and dout.shape[1] == 256
-    dqkv = torch.empty_like(qkv)
-    dbias, ws, nbytes = None, None, 0
-    if bias is not None:
+    dqkv = _dest(dqkv, qkv.shape, qkv)
+    ws, nbytes = None, 0
+    if bias is None:
+        assert dbias is None
+    else:
         seq = frames if mode == 0 else hw
-        dbias = torch.empty(8, seq, seq, dtype=torch.float32, device=qkv.device)
+        dbias = _dest(dbias, (8, seq, seq), qkv)
         nbytes = lib.lfdm_attention_bwd_ws_bytes(batch, frames, hw, mode)
         ws = _ws(nbytes, qkv)
     lib.check(lib.lfdm_attention_bwd_cl_f32(_p(qkv), _p(dout), _p(dqkv), batch, frames, hw, mode, _p(bias), _p(rot_cos),
@@ -169,11 +182,12 @@ def attention_long_bwd(qkv, dout, batch, frames, hw, mode, bias=None, rot_cos=No
     return dqkv, dbias
 
 
-def linear_attention_bwd(qkv, dout, n_frames, hw):
+def linear_attention_bwd(qkv, dout, n_frames, hw, dqkv=None):
+    """-> dqkv rows of 768.  dqkv: optional destination."""
     lib = _lib()
-    _chk(lib, qkv, dout)
+    _chk(lib, qkv, dout, dqkv)
     assert qkv.is_contiguous() and dout.is_contiguous()
-    dqkv = torch.empty_like(qkv)
+    dqkv = _dest(dqkv, qkv.shape, qkv)
     nbytes = lib.lfdm_linear_attention_bwd_ws_bytes(n_frames)
     ws = _ws(nbytes, qkv)
     lib.check(lib.lfdm_linear_attention_bwd_cl_f32(_p(qkv), _p(dout), _p(dqkv), n_frames, hw, _p(ws), nbytes, _stream(lib)),
@@ -237,15 +251,15 @@ def multi_linear_bwd(x, weights, dys, act=ACT_NONE, dws=None, dbs=None, want_dx=
     return dx
 
 
-def upsample2_pad(x, n_img, h, w, pad, reflect, backward=False):
-    """forward: (n*h*w, C) -> (n*(2h+2pad)*(2w+2pad), C); backward: the adjoint."""
+def upsample2_pad(x, n_img, h, w, pad, reflect, backward=False, out=None):
+    """forward: (n*h*w, C) -> (n*(2h+2pad)*(2w+2pad), C); backward: the adjoint.  out: optional destination."""
     lib = _lib()
-    _chk(lib, x)
+    _chk(lib, x, out)
     assert x.is_contiguous()
     c = x.shape[1]
     rows = n_img * h * w if backward else n_img * (2 * h + 2 * pad) * (2 * w + 2 * pad)
     assert x.shape[0] == (n_img * (2 * h + 2 * pad) * (2 * w + 2 * pad) if backward else n_img * h * w)
-    out = torch.empty(rows, c, dtype=torch.float32, device=x.device)
+    out = _dest(out, (rows, c), x)
     lib.check(lib.lfdm_upsample2_pad_cl_f32(_p(x), _p(out), n_img, h, w, c, pad, int(reflect), int(backward), _stream(lib)),
               "lfdm_upsample2_pad_cl_f32")
     return out

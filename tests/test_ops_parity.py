@@ -982,6 +982,39 @@ def test_attention_lowres(backend, c, frames, s, mode):
 #   lfdm_attention_bwd_cl_f32  attention_bwd_kernel<16,4> 1, 4 | <32,4> 17, 32 | <48,4,40> 36, 40 | <48,4> 44 | <64,2> 64
 #                                                        tests/test_train_ops.py::test_attention_temporal_bwd[<frames>]
 #     mode 1: <16,4> 1, 16 | <32,4> 17, 32 | <64,2> 64   tests/test_train_ops.py::test_attention_spatial_bwd[<hw>]
+#     beyond one trip of the grid-stride loop (attn_bwd_blocks: 2048 wavefronts; the prefetch, the dbias carried across trips, invalid units):
+#     258 sequences, <16,4> 4, 16 | <32,4> 17, 32 | <48,4,40> 33, 40 | <48,4> 41, 48 | <64,2> 49, 64; 771 sequences of 40 frames (four trips,
+#     run twice: same bits); 300 of 1     tests/test_train_edges.py::test_attention_temporal_bwd_trips[<frames>-<hw>-<twice>]
+#     mode 1: <32,4> 260 sequences of 17 | <64,2> 257 of 64 (no prefetch)
+#                                                        tests/test_train_edges.py::test_attention_spatial_bwd_trips[<b>-<frames>-<hw>]
+#
+# The other training entry points (tests/test_train_edges.py, float64 references, NaN-filled destinations; ids without the backend):
+#   lfdm_linear_attention_bwd_cl_f32  linattn_bwd_context_kernel / linattn_bwd_apply_kernel, token blocks of LA_TOK = 64, four tokens per trip:
+#     1, 2, 3 | 63, 64, 65 | 127, 130 pixels             test_linear_attention_bwd_token_edges[<hw>]
+#   lfdm_groupnorm_silu_bwd_cl_f32 and the training forward lfdm_groupnorm_silu_cl_f32 (scale_shift + SiLU | neither, with `residual`)
+#     gn_bwd_reduce_kernel: C = 4 (one float4 column) ... 1024 (one sweep of 256); 256-chunk cap with empty (8193) and ragged (9000) chunks
+#     gn_bwd_finalize_kernel: nchunk2 = 1, 2, 4, 5, 7, 13, 14, 16, 17, 66, 256 (the 16-unroll `k + 12 < nchunk2`, then the tail loop)
+#     gn_bwd_apply_kernel: grid below the caps | `batch >= 8`: 128 (8, 128, 2100, 8) | 1024 / batch (2, 256, 2100, 8)
+#     gn_merge_stats in several passes: 16 and 64 groups; sum_leading over batch 1, 2, 3, 8, 9
+#                                                        test_groupnorm_bwd_edges[<with_ss>-<silu>-<with_res>-<b>-<c>-<pixels>-<groups>]
+#     C = 96 refused by both, destinations untouched     test_groupnorm_refuses_96_channels
+#   lfdm_layernorm_bwd_add_cl_f32, with and without dx_add
+#     layernorm_bwd_kernel C / 4 = 1, 63, 64, 65, 129, 256 | layernorm_bwd_small_kernel<16> (C = 64) | <32> (C = 128); the 512-block cap with
+#     a ragged last trip in each: 4101 x 8, 2049 x 516 | 16395 x 64 | 8195 x 128
+#                                                        test_layernorm_bwd_edges[<add>-<rows>-<c>-<twice>]
+#   lfdm_conv2d_wgrad_cl_f32 on non-square images (tap-major, and the reference layout + dbias up to 16 taps)
+#     conv_wgrad3_kernel<8> | <4> (two images per tile; ragged splits, partial channel tiles), each also through LFDM_WGRAD3=0
+#     conv_wgrad_kernel<1,1> (odd image, stride 2 on even and odd inputs, 3x3 stride 2, padding in y only, 1x3 and 5x5 filters) | <1,2>
+#     (cout 100, 1024) | <2,2> (256 -> 256); wgrad_reduce_ref_kernel<1> | <4> (ceil(cin / 4) * ceil(cout / 64) = 256)
+#                                                        test_conv_wgrad_edges[<cin>-<cout>-<k>-<stride>-<pad>-<n>-<hi>-<wi>-<route>]
+#     (<2,1>, wgrad_reduce_ref_kernel<16>: tests/test_train_ops.py::test_conv_wgrad[132-8-1-1-4])
+#   lfdm_colsum_f32  colsum4_kernel: the 512-block cap (rows > 524 288), ragged and exact; two blocks at C = 68
+#                                                        test_colsum_block_cap[<rows>-<c>-<twice>]
+#   lfdm_upsample2_pad_cl_f32  upsample_pad_fwd_kernel / upsample_pad_bwd_kernel: 1x1, 1x5, 5x1, 2x3, 4x7; pad 0 / 1; reflect / zero
+#                                                        test_upsample2_pad_edges[<n>-<c>-<h>-<w>-<pad>-<reflect>]
+#   autograd.ConvCL, y and every gradient: Winograd and direct 3x3 over cat(x0, x1) + residual, Winograd fork (against the unforked ATen graph),
+#     1x1, 4x4 stride 2, deconv, 7x7 thin input / thin output, fused ReLU, 5x5
+#                                                        test_conv_function_routes[<case>]
 #   conv_pw_kernel<TN, KW> with the residual-GroupNorm epilogue, BN = 32 ... 384 columns
 #                                                        test_conv_pointwise_residual_groupnorm (the table above it)
 #   whole model: tests/test_end_to_end.py::test_unet_forward_frames[1|17|64], ::test_sample_one_video_single_frame (BASELINE configs[0]),
