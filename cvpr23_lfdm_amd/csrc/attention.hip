@@ -257,10 +257,8 @@ extern "C" int lfdm_attention_cl_f32(const float* qkv, float* out, int batch, in
   hipStream_t stream = (hipStream_t)stream_;
   const int L = mode == 0 ? frames : hw;
   if (!qkv || !out || batch <= 0 || frames <= 0 || hw <= 0 || (mode != 0 && mode != 1) ||
-      L > 64 || ((rot_cos == nullptr) != (rot_sin == nullptr))) {
-    lfdm_set_error("attention: unsupported shape (sequence length must be <= 64)");
-    return LFDM_EINVAL;
-  }
+      L > 64 || ((rot_cos == nullptr) != (rot_sin == nullptr)))
+    return lfdm_fail(LFDM_EINVAL, "attention: unsupported shape (sequence length must be <= 64)");
   const int64_t nseq = mode == 0 ? (int64_t)batch * hw : (int64_t)batch * frames;
   const int64_t units = nseq * HEADS;
   const dim3 grid((unsigned)units), block(64);
@@ -282,14 +280,10 @@ extern "C" size_t lfdm_linear_attention_ws_bytes(int n_frames) {
 extern "C" int lfdm_linear_attention_cl_f32(const float* qkv, float* out, int n_frames, int hw,
                                             void* ws, size_t ws_bytes, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!qkv || !out || n_frames <= 0 || hw <= 0) {
-    lfdm_set_error("linear_attention: bad arguments");
-    return LFDM_EINVAL;
-  }
-  if (!ws || ws_bytes < lfdm_linear_attention_ws_bytes(n_frames)) {
-    lfdm_set_error("linear_attention: workspace too small");
-    return LFDM_EWORKSPACE;
-  }
+  if (!qkv || !out || n_frames <= 0 || hw <= 0)
+    return lfdm_fail(LFDM_EINVAL, "linear_attention: bad arguments");
+  if (!ws || ws_bytes < lfdm_linear_attention_ws_bytes(n_frames))
+    return lfdm_fail(LFDM_EWORKSPACE, "linear_attention: workspace too small");
   float* ctx = reinterpret_cast<float*>(ws);
   LFDM_LAUNCH(linattn_context_kernel, dim3(n_frames * HEADS), dim3(256), 0, stream, qkv, hw, ctx);
   LFDM_LAUNCH(linattn_output_kernel, dim3((hw + 31) / 32, n_frames), dim3(256), 0, stream, qkv,

@@ -505,10 +505,8 @@ extern "C" int lfdm_temporal_attention_fused_out_cl_f32(const float* x, int ldx,
                                                         const float* rot_cos, const float* rot_sin, float ln_eps, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !wqkv || !wout || !out || batch <= 0 || frames <= 0 || frames > 64 || hw <= 0 || channels != 64 || ldx < 64 || ldx % 4 != 0 ||
-      ldo < 64 || (((uintptr_t)x | (uintptr_t)wqkv | (uintptr_t)wout) & 15) || ((rot_cos == nullptr) != (rot_sin == nullptr)) || out == x) {
-    lfdm_set_error("temporal_attention_fused_out: needs C == 64, frames <= 64, 16-byte aligned rows, out != x");
-    return LFDM_EINVAL;
-  }
+      ldo < 64 || !lfdm_aligned16(x, wqkv, wout) || ((rot_cos == nullptr) != (rot_sin == nullptr)) || out == x)
+    return lfdm_fail(LFDM_EINVAL, "temporal_attention_fused_out: needs C == 64, frames <= 64, 16-byte aligned rows, out != x");
   return lp_ladder(frames, [&](auto lp) {
     constexpr int LP = decltype(lp)::value;
     if (LP == 48 && frames <= 40)      // the 40-frame videos: a 40-row LDS tile
@@ -523,11 +521,9 @@ extern "C" int lfdm_temporal_attention_fused_cl_f32(const float* x, int ldx, int
                                                     lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !wqkv || !out || batch <= 0 || frames <= 0 || frames > 64 || hw <= 0 || ldx < channels || ldx % 4 != 0 ||
-      (((uintptr_t)x | (uintptr_t)wqkv) & 15) || ((rot_cos == nullptr) != (rot_sin == nullptr)) ||
-      channels < 64 || channels % 64 != 0) {
-    lfdm_set_error("temporal_attention_fused: needs C % 64 == 0, frames <= 64, 16-byte aligned rows");
-    return LFDM_EINVAL;
-  }
+      !lfdm_aligned16(x, wqkv) || ((rot_cos == nullptr) != (rot_sin == nullptr)) ||
+      channels < 64 || channels % 64 != 0)
+    return lfdm_fail(LFDM_EINVAL, "%s", "temporal_attention_fused: needs C % 64 == 0, frames <= 64, 16-byte aligned rows");
   if (channels == 64) return launch_fused<64>(x, ldx, wqkv, out, batch, frames, hw, bias, rot_cos, rot_sin, ln_eps, stream);
   return launch_fused_wide(x, ldx, channels, wqkv, out, batch, frames, hw, bias, rot_cos, rot_sin, ln_eps, stream);
 }

@@ -485,8 +485,7 @@ extern "C" int lfdm_attention_long_cl_f32(const float* qkv, float* out, int batc
                                           const float* rot_cos, const float* rot_sin, float* stats, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!qkv || !out || !long_shape_ok(batch, frames, hw, mode) || ((rot_cos == nullptr) != (rot_sin == nullptr))) {
-    lfdm_set_error("attention_long: unsupported shape (sequence length must be 65 .. 256; up to 64 tokens belong to lfdm_attention_cl_f32)");
-    return LFDM_EINVAL;
+    return lfdm_fail(LFDM_EINVAL, "attention_long: unsupported shape (sequence length must be 65 .. 256; up to 64 tokens belong to lfdm_attention_cl_f32)");
   }
   const int L = mode == 0 ? frames : hw;
   const int64_t nseq = mode == 0 ? (int64_t)batch * hw : (int64_t)batch * frames;
@@ -509,13 +508,10 @@ extern "C" int lfdm_attention_long_bwd_cl_f32(const float* qkv, const float* dou
   hipStream_t stream = (hipStream_t)stream_;
   if (!qkv || !dout || !dqkv || !long_shape_ok(batch, frames, hw, mode) || ((rot_cos == nullptr) != (rot_sin == nullptr)) ||
       ((bias == nullptr) != (dbias == nullptr))) {
-    lfdm_set_error("attention_long_bwd: unsupported arguments (sequence length must be 65 .. 256; dbias iff bias)");
-    return LFDM_EINVAL;
+    return lfdm_fail(LFDM_EINVAL, "attention_long_bwd: unsupported arguments (sequence length must be 65 .. 256; dbias iff bias)");
   }
-  if (!ws || (((uintptr_t)ws) & 15) != 0 || ws_bytes < lfdm_attention_long_bwd_ws_bytes(batch, frames, hw, mode)) {
-    lfdm_set_error("attention_long_bwd: workspace too small or not 16-byte aligned");
-    return LFDM_EWORKSPACE;
-  }
+  if (!ws || !lfdm_aligned16(ws) || ws_bytes < lfdm_attention_long_bwd_ws_bytes(batch, frames, hw, mode))
+    return lfdm_fail(LFDM_EWORKSPACE, "attention_long_bwd: workspace too small or not 16-byte aligned");
   const int L = mode == 0 ? frames : hw;
   const int64_t nseq = mode == 0 ? (int64_t)batch * hw : (int64_t)batch * frames;
   const int nqb = (L + 16 * NQ - 1) / (16 * NQ), nkt = (L + 15) / 16;

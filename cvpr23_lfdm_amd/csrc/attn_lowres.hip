@@ -466,7 +466,7 @@ __global__ __launch_bounds__(256) void attn_lowres_kernel(const float* __restric
 
 bool lowres_args_ok(const float* x, int ldx, int channels, const float* wqkv, const float* wsum, const float* out) {
   return x && wqkv && wsum && out && channels >= 64 && channels % 64 == 0 && ldx >= channels && ldx % 4 == 0 &&
-         ((((uintptr_t)x) | ((uintptr_t)wqkv) | ((uintptr_t)out)) & 15) == 0;
+         lfdm_aligned16(x, wqkv, out);
 }
 
 }  // namespace
@@ -474,15 +474,12 @@ bool lowres_args_ok(const float* x, int ldx, int channels, const float* wqkv, co
 extern "C" int lfdm_linear_attention_lowres_cl_f32(const float* x, int ldx, int channels, const float* wqkv, const float* wsum,
                                                    float* out, int n_frames, int hw, float ln_eps, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!lowres_args_ok(x, ldx, channels, wqkv, wsum, out) || n_frames <= 0 || hw <= 0 || hw > 256 || (int64_t)n_frames * HEADS > 0x7fffffff) {
-    lfdm_set_error("linear_attention_lowres: needs C % 64 == 0, 1 <= hw <= 256 pixels per frame, 16-byte aligned rows");
-    return LFDM_EINVAL;
-  }
+  if (!lowres_args_ok(x, ldx, channels, wqkv, wsum, out) || n_frames <= 0 || hw <= 0 || hw > 256 || (int64_t)n_frames * HEADS > 0x7fffffff)
+    return lfdm_fail(LFDM_EINVAL, "%s", "linear_attention_lowres: needs C % 64 == 0, 1 <= hw <= 256 pixels per frame, 16-byte aligned rows");
   const dim3 grid((unsigned)(n_frames * HEADS)), block(256);
   if (hw > 192) LFDM_LAUNCH((linattn_lowres_kernel<4, true>), grid, block, 0, stream, x, ldx, channels, wqkv, wsum, out, hw, ln_eps);
   else if (hw > 64) {
-    lfdm_set_error("linear_attention_lowres: 64 < hw <= 192 pixels per frame is not built (use the unfused entry points)");
-    return LFDM_EINVAL;
+    return lfdm_fail(LFDM_EINVAL, "linear_attention_lowres: 64 < hw <= 192 pixels per frame is not built (use the unfused entry points)");
   } else
     lfdm_ladder<16, 32, 64>(hw, [&](auto rows) {
       LFDM_LAUNCH((linattn_lowres_kernel<decltype(rows)::value / 16, false>), grid, block, 0, stream, x, ldx, channels, wqkv, wsum, out, hw, ln_eps);
@@ -497,10 +494,8 @@ extern "C" int lfdm_attention_lowres_cl_f32(const float* x, int ldx, int channel
   const int L = mode == 0 ? frames : hw;
   const int64_t nseq = mode == 0 ? (int64_t)batch * hw : (int64_t)batch * frames;
   if (!lowres_args_ok(x, ldx, channels, wqkv, wsum, out) || batch <= 0 || frames <= 0 || hw <= 0 || (mode != 0 && mode != 1) || L > 64 ||
-      ((rot_cos == nullptr) != (rot_sin == nullptr)) || nseq * HEADS > 0x7fffffff) {
-    lfdm_set_error("attention_lowres: needs C % 64 == 0, <= 64 tokens per sequence, 16-byte aligned rows");
-    return LFDM_EINVAL;
-  }
+      ((rot_cos == nullptr) != (rot_sin == nullptr)) || nseq * HEADS > 0x7fffffff)
+    return lfdm_fail(LFDM_EINVAL, "%s", "attention_lowres: needs C % 64 == 0, <= 64 tokens per sequence, 16-byte aligned rows");
   const dim3 grid((unsigned)(nseq * HEADS)), block(256);
   lp_ladder(L, [&](auto lp) {
     LFDM_LAUNCH((attn_lowres_kernel<decltype(lp)::value / 16>), grid, block, 0, stream, x, ldx, channels, wqkv, wsum, out, frames, hw, mode, bias, rot_cos, rot_sin, ln_eps);

@@ -60,8 +60,7 @@ __global__ __launch_bounds__(256) void calib_mfma_kernel(float* __restrict__ out
 extern "C" int lfdm_calib_mfma_f32(float* out, int blocks, int iters, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!out || blocks <= 0 || iters <= 0) {
-    lfdm_set_error("calib_mfma: out must hold 2 * blocks + 256 floats; blocks, iters > 0");
-    return LFDM_EINVAL;
+    return lfdm_fail(LFDM_EINVAL, "calib_mfma: out must hold 2 * blocks + 256 floats; blocks, iters > 0");
   }
   LFDM_LAUNCH(calib_mfma_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, out, iters, 1.0f, 0.5f);
   return lfdm_check_launch("calib_mfma");

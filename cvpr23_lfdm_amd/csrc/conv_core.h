@@ -6,6 +6,7 @@
 // GroupNorm hand-off itself is gn_stats.h.
 #pragma once
 #include "gn_stats.h"
+#include "norm_core.h"
 
 // out, bias and residual are 16-byte addressable at every column that is a multiple of 4.  Each caller adds its own condition on the
 // channel count (cout % 4 == 0, or cout == coutp).
@@ -21,10 +22,6 @@ __device__ __forceinline__ int64_t conv_out_row(const lfdm_conv_params& p, int i
   const int oy = qy * p.out_scale + p.out_off_y;      // (the pixel coordinates in 32 bits, only the row index in 64)
   const int ox = qx * p.out_scale + p.out_off_x;
   return ((int64_t)img * p.ho + oy) * p.wo + ox;
-}
-
-__device__ __forceinline__ void add4(float4& v, const float4& a) {
-  v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
 }
 
 // out4 = act((v + bias) + residual), with stats(v + bias) in between: the value GroupNorm statistics are taken of.  `stats` is the
@@ -43,8 +40,7 @@ __device__ __forceinline__ void conv_finish4(float4 v, const float4& bias, const
     add4(v, residual);
   }
   if (ACT) {
-    v.x = apply_act(v.x, act); v.y = apply_act(v.y, act);
-    v.z = apply_act(v.z, act); v.w = apply_act(v.w, act);
+    v = map4([act](float e) { return apply_act(e, act); }, v);
   }
 #ifdef LFDM_PROBE_NOSTORE      // probe build only: everything but the store
   if (v.x == 123456.789f)

@@ -537,7 +537,7 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(lfdm_conv_param
           gq += t * t;
         });
   }
-  if (p.gn_partial) splitk_gn_tail(p, red_s, red_q, gs, gq, cw, cq0);
+  if (p.gn_partial) splitk_gn_tail(p.gn_partial, (int64_t)blockIdx.x, p.gn_groups, (p.cout / p.gn_groups) / 4, cw, cq0, red_s, red_q, gs, gq);
 }
 
 // The same pass for the shapes the sampler produces (round 4): KS slabs known at compile time, all KS 16-byte loads of an item in flight
@@ -576,7 +576,7 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_vec_kernel(lfdm_conv_p
       gq += (t.x * t.x + t.y * t.y) + (t.z * t.z + t.w * t.w);
     });
   }
-  if (p.gn_partial) splitk_gn_tail(p, red_s, red_q, gs, gq, cw, cq0);
+  if (p.gn_partial) splitk_gn_tail(p.gn_partial, (int64_t)blockIdx.x, p.gn_groups, (p.cout / p.gn_groups) / 4, cw, cq0, red_s, red_q, gs, gq);
 }
 
 // column chunks for the reduce grid: enough workgroups to cover the chip, chunks of >= 16 float4 that
@@ -658,7 +658,7 @@ ConvPlan make_plan(const lfdm_conv_params& p) {
   const int64_t M = (int64_t)p.n_img * p.hq * p.wq;
   const int nchunks = (p.kh * p.kw * cin + 31) / 32;
   pl.fast = (p.c0 % 32 == 0) && (p.c1 % 32 == 0) && (p.ld0 % 4 == 0) && (p.c1 == 0 || p.ld1 % 4 == 0) &&
-            (((uintptr_t)p.src0 & 15) == 0) && (p.c1 == 0 || ((uintptr_t)p.src1 & 15) == 0);
+            lfdm_aligned16(p.src0) && (p.c1 == 0 || lfdm_aligned16(p.src1));
   pl.simple = !p.upsample && p.pad_mode == 0 && p.kh * p.kw <= 64 &&
               (int64_t)p.n_img * p.hi * p.wi < (1ll << 31) - (1 << 20);
   const int user_k = p.ksplit;                       // 0 = choose
@@ -674,8 +674,8 @@ ConvPlan make_plan(const lfdm_conv_params& p) {
   const bool wino = p.weight_wino && wino_enabled() && p.kh == 3 && p.kw == 3 && p.stride == 1 && p.pad_y == 1 && p.pad_x == 1 &&
                     p.pad_mode == 0 && fits32 && (int64_t)p.n_img * p.hq * p.wq < (1ll << 31) - (1 << 20) &&
                     p.hq == up * p.hi && p.wq == up * p.wi && p.hq % 2 == 0 && p.wq % 2 == 0 && p.c0 % 16 == 0 &&
-                    p.c1 % 16 == 0 && p.ld0 % 4 == 0 && (p.c1 == 0 || p.ld1 % 4 == 0) && (((uintptr_t)p.src0 & 15) == 0) &&
-                    (p.c1 == 0 || ((uintptr_t)p.src1 & 15) == 0) && (((uintptr_t)p.weight_wino) & 15) == 0 && !p.ln_wsum &&
+                    p.c1 % 16 == 0 && p.ld0 % 4 == 0 && (p.c1 == 0 || p.ld1 % 4 == 0) && lfdm_aligned16(p.src0) &&
+                    (p.c1 == 0 || lfdm_aligned16(p.src1)) && lfdm_aligned16(p.weight_wino) && !p.ln_wsum &&
                     p.out_scale == 1 && p.out_off_y == 0 && p.out_off_x == 0 && (p.pool2 ? (2 * p.ho == p.hq && 2 * p.wo == p.wq) : (p.ho == p.hq && p.wo == p.wq)) && (int64_t)16 * (cin / 16) * p.coutp * 64 < (1ll << 32) - 64 &&
                     !p.deconv4 && vec_ok;      // (float4 epilogue)
   // 1x1 / stride 1 projections (to_qkv with the LayerNorm fold, to_out, res_conv): the register-operand GEMM of conv_pw.hip has no
@@ -690,12 +690,12 @@ ConvPlan make_plan(const lfdm_conv_params& p) {
   const bool pw_ok = pw_mode != 0 && conv_force() < 0 && p.kh == 1 && p.kw == 1 && p.stride == 1 && !p.upsample && p.pad_y == 0 &&
                      p.pad_x == 0 && pl.fast && fits32 && vec_ok && user_k <= 1 && !p.gn_partial && !p.deconv4 && !(p.groups > 1) && !p.pool2 &&
                      p.out_scale == 1 && p.out_off_y == 0 && p.out_off_x == 0 && p.ho == p.hq && p.wo == p.wq && p.hq == p.hi && p.wq == p.wi &&
-                     (M <= pw_max_m || (p.res_gn_partial && M <= 65536)) && (!p.ln_wsum || (p.c1 == 0 && (((uintptr_t)p.ln_wsum) & 15) == 0)) && !p.tile_counters;
+                     (M <= pw_max_m || (p.res_gn_partial && M <= 65536)) && (!p.ln_wsum || (p.c1 == 0 && lfdm_aligned16(p.ln_wsum))) && !p.tile_counters;
   // ... and its gather form (round 6) for the Downsample convolutions: 4x4 / stride 2 / zero pad over one source, K = 16 C a multiple of 128,
   // K <= 2048, M <= 16 384 output rows (the KSW schedule + its reduce launch: 28 us for 1.3 GFLOP at every level of a B = 1 step; measured in the
   // step: 19.9 / 22.2 us at the first two levels, but 34.0 us for the 256-channel one - 160 workgroups walking K = 4096 - which stays on KSW)
   const bool pwg_ok = pw_mode != 0 && conv_force() < 0 && p.kh == 4 && p.kw == 4 && p.stride == 2 && !p.upsample && p.pad_mode == 0 && p.c1 == 0 &&
-                      p.c0 % 32 == 0 && (16 * p.c0) % 128 == 0 && 16 * p.c0 <= 2048 && p.ld0 % 4 == 0 && (((uintptr_t)p.src0) & 15) == 0 && fits32 && vec_ok && user_k <= 1 &&
+                      p.c0 % 32 == 0 && (16 * p.c0) % 128 == 0 && 16 * p.c0 <= 2048 && p.ld0 % 4 == 0 && lfdm_aligned16(p.src0) && fits32 && vec_ok && user_k <= 1 &&
                       !p.gn_partial && !p.deconv4 && !(p.groups > 1) && !p.pool2 && p.out_scale == 1 && p.out_off_y == 0 && p.out_off_x == 0 &&
                       p.ho == p.hq && p.wo == p.wq && !p.ln_wsum && !p.res_gn_partial && M <= pw_max_m && !p.tile_counters &&
                       (int64_t)p.n_img * p.hi * p.wi < (1ll << 31) - (1 << 20);
@@ -703,7 +703,7 @@ ConvPlan make_plan(const lfdm_conv_params& p) {
   // ~1e-6 for F(2x2)) and only where every CU gets several of its one-per-CU workgroups - the batched shapes of training / throughput
   // mode.  LFDM_WINO4=0 disables it, LFDM_WINO4_MIN overrides the workgroup-count threshold.
   if (wino && p.weight_wino4 && p.c1 == 0 && p.c0 % 32 == 0 && p.hq % 4 == 0 && p.wq % 4 == 0 && !(p.groups > 1) && !p.pool2 &&
-      !p.gn_partial && user_k <= 1 && p.coutp % 32 == 0 && (((uintptr_t)p.weight_wino4) & 15) == 0 &&
+      !p.gn_partial && user_k <= 1 && p.coutp % 32 == 0 && lfdm_aligned16(p.weight_wino4) &&
       (int64_t)36 * (cin / 8) * p.coutp * 32 < (1ll << 32) - 64) {
     const char* em = getenv("LFDM_WINO4_MIN");      // (read per call: tests and tools toggle it at run time)
     const long min_blocks4 = em ? atol(em) : 2048l;
@@ -898,58 +898,42 @@ namespace {
 
 // lfdm_conv2d_cl_f32, and with wino_bf16 != NULL lfdm_conv2d_cl_wino_bf16: the same checks and the same plan, the Winograd launch on bf16 operands
 int conv2d_run(const lfdm_conv_params* pp, const void* wino_bf16, hipStream_t stream) {
-  if (!pp) { lfdm_set_error("conv2d: null params"); return LFDM_EINVAL; }
+  if (!pp) return lfdm_fail(LFDM_EINVAL, "conv2d: null params");
   lfdm_conv_params p = *pp;
   if (!p.src0 || !p.weight || !p.out || p.c0 <= 0 || p.c1 < 0 || (p.c1 > 0 && !p.src1) ||
       p.n_img <= 0 || p.hq <= 0 || p.wq <= 0 || p.kh <= 0 || p.kw <= 0 || p.cout <= 0 ||
       (int64_t)p.n_img * p.hq * p.wq >= (1ll << 31) || p.coutp < p.cout || (p.coutp % 32) != 0 || p.stride <= 0 || p.out_scale <= 0 || p.ksplit < 0 ||
-      p.ld0 < p.c0 || (p.c1 > 0 && p.ld1 < p.c1) || p.ldo < p.cout) {
-    lfdm_set_error("conv2d: invalid geometry");
-    return LFDM_EINVAL;
-  }
+      p.ld0 < p.c0 || (p.c1 > 0 && p.ld1 < p.c1) || p.ldo < p.cout)
+    return lfdm_fail(LFDM_EINVAL, "conv2d: invalid geometry");
   if (p.pad_mode == 1) {
     const int H = p.upsample ? 2 * p.hi : p.hi, W = p.upsample ? 2 * p.wi : p.wi;
-    if (p.pad_y >= H || p.pad_x >= W || p.kh - 1 - p.pad_y >= H || p.kw - 1 - p.pad_x >= W) {
-      lfdm_set_error("conv2d: reflect padding larger than the input");
-      return LFDM_EINVAL;
-    }
+    if (p.pad_y >= H || p.pad_x >= W || p.kh - 1 - p.pad_y >= H || p.kw - 1 - p.pad_x >= W)
+      return lfdm_fail(LFDM_EINVAL, "conv2d: reflect padding larger than the input");
   }
   if (p.deconv4 && (p.kh != 2 || p.kw != 2 || p.stride != 1 || p.out_scale != 2 || p.upsample || p.pad_mode != 0 || p.ln_wsum ||
-                    p.gn_partial || p.hq != p.hi || p.wq != p.wi || p.ho != 2 * p.hi || p.wo != 2 * p.wi)) {
-    lfdm_set_error("conv2d: deconv4 = the four 2x2 parity convolutions of a ConvTranspose k4 s2 p1 (kh = kw = 2, out_scale 2, no fused norms)");
-    return LFDM_EINVAL;
-  }
-  if (p.groups > 1 && !(p.weight_wino && p.c1 == 0 && p.c0 % (16 * p.groups) == 0 && p.cout % (32 * p.groups) == 0 && p.cout == p.coutp)) {
-    lfdm_set_error("conv2d: groups > 1 needs the Winograd form, one source, c0/groups % 16 == 0 and cout/groups % 32 == 0");
-    return LFDM_EINVAL;
-  }
+                    p.gn_partial || p.hq != p.hi || p.wq != p.wi || p.ho != 2 * p.hi || p.wo != 2 * p.wi))
+    return lfdm_fail(LFDM_EINVAL, "conv2d: deconv4 = the four 2x2 parity convolutions of a ConvTranspose k4 s2 p1 (kh = kw = 2, out_scale 2, no fused norms)");
+  if (p.groups > 1 && !(p.weight_wino && p.c1 == 0 && p.c0 % (16 * p.groups) == 0 && p.cout % (32 * p.groups) == 0 && p.cout == p.coutp))
+    return lfdm_fail(LFDM_EINVAL, "%s", "conv2d: groups > 1 needs the Winograd form, one source, c0/groups % 16 == 0 and cout/groups % 32 == 0");
   const ConvPlan pl = make_plan(p);
-  if (wino_bf16 && (pl.kind != 2 || p.pool2 || (((uintptr_t)wino_bf16) & 15) != 0)) {
-    lfdm_set_error("conv2d_cl_wino_bf16: only where lfdm_conv2d_schedule picks the Winograd F(2x2,3x3) schedule (2), without pool2, with a 16-byte "
+  if (wino_bf16 && (pl.kind != 2 || p.pool2 || !lfdm_aligned16(wino_bf16)))
+    return lfdm_fail(LFDM_EINVAL, "conv2d_cl_wino_bf16: only where lfdm_conv2d_schedule picks the Winograd F(2x2,3x3) schedule (2), without pool2, with a 16-byte "
                    "aligned bf16 pack (lfdm_pack_wino_weight_bf16)");
-    return LFDM_EINVAL;
-  }
-  if (p.groups > 1 && pl.kind != 2) { lfdm_set_error("conv2d: groups > 1 is only built for the Winograd schedule (3x3, stride 1, zero pad)"); return LFDM_EINVAL; }
-  if (p.pool2 && (pl.kind != 2 || p.residual || p.gn_partial || pp->ksplit > 1 || p.act == LFDM_ACT_NONE)) {
-    lfdm_set_error("conv2d: pool2 exists on the Winograd schedule only (3x3, stride 1, zero pad 1, even size, C % 16 == 0): out = (hq/2, wq/2), "
+  if (p.groups > 1 && pl.kind != 2) return lfdm_fail(LFDM_EINVAL, "conv2d: groups > 1 is only built for the Winograd schedule (3x3, stride 1, zero pad)");
+  if (p.pool2 && (pl.kind != 2 || p.residual || p.gn_partial || pp->ksplit > 1 || p.act == LFDM_ACT_NONE))
+    return lfdm_fail(LFDM_EINVAL, "%s", "conv2d: pool2 exists on the Winograd schedule only (3x3, stride 1, zero pad 1, even size, C % 16 == 0): out = (hq/2, wq/2), "
                    "an output activation, no residual / fused GroupNorm / split-K - see lfdm_conv2d_schedule");
-    return LFDM_EINVAL;
-  }
   if (p.res_gn_partial) {
     const int g = p.res_gn_groups;
     if (pl.kind != 3 || !p.residual || g <= 0 || g > 64 || p.cout % g != 0 || (p.cout / g) % 4 != 0 || p.res_gn_pixels <= 0 || p.res_gn_pixels % 32 != 0 ||
-        ((int64_t)p.n_img * p.hq * p.wq) % p.res_gn_pixels != 0 || p.res_gn_nchunk <= 0 || !p.res_gn_gamma || !p.res_gn_beta) {
-      lfdm_set_error("conv2d: res_gn_* (GroupNorm + SiLU of the residual in the epilogue) needs the pointwise schedule (see lfdm_conv2d_schedule), a residual, "
+        ((int64_t)p.n_img * p.hq * p.wq) % p.res_gn_pixels != 0 || p.res_gn_nchunk <= 0 || !p.res_gn_gamma || !p.res_gn_beta)
+      return lfdm_fail(LFDM_EINVAL, "%s", "conv2d: res_gn_* (GroupNorm + SiLU of the residual in the epilogue) needs the pointwise schedule (see lfdm_conv2d_schedule), a residual, "
                      "cout % groups == 0 with groups of a multiple of 4 channels, pixels per sample % 32 == 0");
-      return LFDM_EINVAL;
-    }
   }
-  if (p.gn_in_partial || p.defer_reduce) {
-    lfdm_set_error("conv2d: gn_in_* / defer_reduce are reserved since ABI 12 (the variants were measured slower and removed): pass NULL / 0");
-    return LFDM_EINVAL;
-  }
+  if (p.gn_in_partial || p.defer_reduce)
+    return lfdm_fail(LFDM_EINVAL, "conv2d: gn_in_* / defer_reduce are reserved since ABI 12 (the variants were measured slower and removed): pass NULL / 0");
   p.ksplit = pl.ksplit;
-  if (p.ksplit > 1 && !p.partial) { lfdm_set_error("conv2d: split-K needs the partial buffer (lfdm_conv2d_partial_bytes)"); return LFDM_EWORKSPACE; }
+  if (p.ksplit > 1 && !p.partial) return lfdm_fail(LFDM_EWORKSPACE, "conv2d: split-K needs the partial buffer (lfdm_conv2d_partial_bytes)");
   if (p.partial) p.partial = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(p.partial) + 127) & ~(uintptr_t)127);   // (slack: partial_bytes)
   const int64_t M = (int64_t)p.n_img * p.hq * p.wq;
   if (p.gn_partial) {
@@ -958,21 +942,17 @@ int conv2d_run(const lfdm_conv_params* pp, const void* wino_bf16, hipStream_t st
     const int rows = (p.ksplit > 1 && !fused) ? SPLITK_ROWS : pl.bm;
     const bool ok = p.gn_groups > 0 && p.cout % p.gn_groups == 0 && cg % 4 == 0 && p.gn_pixels > 0 &&
                     p.gn_pixels % rows == 0 && p.cout % 4 == 0 && p.ldo % 4 == 0 &&
-                    (((uintptr_t)p.out) & 15) == 0 &&
+                    lfdm_aligned16(p.out) &&
                     ((p.ksplit > 1 && !fused) ? (256 % (p.coutp / 4) == 0 && p.cout == p.coutp)
                                               : (pl.bn % cg == 0 || (pl.kind == 2 && cg % pl.bn == 0)));      // (Winograd: a group may span column tiles)
-    if (!ok) {
-      lfdm_set_error("conv2d: fused GroupNorm statistics need pixels % tile_rows == 0 and a group size dividing "
+    if (!ok)
+      return lfdm_fail(LFDM_EINVAL, "%s", "conv2d: fused GroupNorm statistics need pixels % tile_rows == 0 and a group size dividing "
                      "the column tile (see lfdm_conv2d_plan)");
-      return LFDM_EINVAL;
-    }
   }
   if (p.ln_wsum) {
     if (!pl.fast || !pl.simple || p.kh != 1 || p.kw != 1 || p.c1 != 0 || p.stride != 1 || p.cout % 4 != 0 ||
-        (((uintptr_t)p.ln_wsum) & 15) != 0 || !conv_epilogue_vec4_ok(p)) {      // (float4 epilogue only)
-      lfdm_set_error("conv2d: fused LayerNorm needs a 1x1 convolution over one source with C % 32 == 0 and 16-byte addressable out / residual / bias");
-      return LFDM_EINVAL;
-    }
+        !lfdm_aligned16(p.ln_wsum) || !conv_epilogue_vec4_ok(p))      // (float4 epilogue only)
+      return lfdm_fail(LFDM_EINVAL, "%s", "conv2d: fused LayerNorm needs a 1x1 convolution over one source with C % 32 == 0 and 16-byte addressable out / residual / bias");
   }
   int rc;
   if (pl.kind == 1) {
@@ -997,7 +977,7 @@ int conv2d_run(const lfdm_conv_params* pp, const void* wino_bf16, hipStream_t st
     const dim3 rgrid((unsigned)((M + SPLITK_ROWS - 1) / SPLITK_ROWS), (unsigned)splitk_col_chunks(p, M), p.deconv4 ? 4 : 1);
     static const bool vec_on = [] { const char* e = lfdm_knob("LFDM_REDUCE_VEC"); return !(e && e[0] == '0'); }();      // (A/B knob)
     const bool vec = vec_on && p.ksplit <= 8 && !p.deconv4 && !p.ln_wsum && p.cout == p.coutp && conv_epilogue_vec4_ok(p) &&
-                     p.out_scale == 1 && p.out_off_y == 0 && p.out_off_x == 0 && p.ho == p.hq && p.wo == p.wq && (((uintptr_t)p.partial) & 15) == 0;
+                     p.out_scale == 1 && p.out_off_y == 0 && p.out_off_x == 0 && p.ho == p.hq && p.wo == p.wq && lfdm_aligned16(p.partial);
     if (vec) {
       switch (p.ksplit) {
         case 2: LFDM_LAUNCH(conv_splitk_reduce_vec_kernel<2>, rgrid, dim3(256), 0, stream, p); break;
@@ -1021,6 +1001,6 @@ int conv2d_run(const lfdm_conv_params* pp, const void* wino_bf16, hipStream_t st
 extern "C" int lfdm_conv2d_cl_f32(const lfdm_conv_params* p, lfdm_stream_t stream) { return conv2d_run(p, nullptr, (hipStream_t)stream); }
 
 extern "C" int lfdm_conv2d_cl_wino_bf16(const lfdm_conv_params* p, const void* weight_wino_bf16, lfdm_stream_t stream) {
-  if (!weight_wino_bf16) { lfdm_set_error("conv2d_cl_wino_bf16: null bf16 pack"); return LFDM_EINVAL; }
+  if (!weight_wino_bf16) return lfdm_fail(LFDM_EINVAL, "conv2d_cl_wino_bf16: null bf16 pack");
   return conv2d_run(p, weight_wino_bf16, (hipStream_t)stream);
 }

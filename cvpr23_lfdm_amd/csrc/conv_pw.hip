@@ -131,18 +131,20 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(lfdm_conv_params p, int gx
     __syncthreads();
     if (pcol_ok) {
       const int g = pcol / cg - g_lo;
-      const float a = s_gstat[1][g] * pre_gamma;
-      s_ga[tid] = a;
-      s_gb[tid] = pre_beta - s_gstat[0][g] * a;
+      float ga, gb;
+      gn_affine(s_gstat[0][g], s_gstat[1][g], pre_gamma, pre_beta, ga, gb);
+      s_ga[tid] = ga;
+      s_gb[tid] = gb;
     }
     if constexpr (BN > 256) {
       for (int c = tid + 256; c < BN; c += 256) {
         const int col = n0 + c;
         if (col >= p.cout) break;
         const int g = col / cg - g_lo;
-        const float a = s_gstat[1][g] * p.res_gn_gamma[col];
-        s_ga[c] = a;
-        s_gb[c] = p.res_gn_beta[col] - s_gstat[0][g] * a;
+        float ga, gb;
+        gn_affine(s_gstat[0][g], s_gstat[1][g], p.res_gn_gamma[col], p.res_gn_beta[col], ga, gb);
+        s_ga[c] = ga;
+        s_gb[c] = gb;
       }
     }
     // (the table is read after the epilogue's first barrier)

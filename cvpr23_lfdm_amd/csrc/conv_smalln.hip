@@ -124,13 +124,11 @@ extern "C" int lfdm_conv2d_smalln_cl_f32(const float* x, int ldx, int cin, int n
                                          const float* bias, float* out, int ldo, int cout, int k, int act,
                                          lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!x || !wgt || !out || cin <= 0 || cin % 16 != 0 || ldx < cin || ldx % 4 != 0 || (((uintptr_t)x) & 15) || (((uintptr_t)wgt) & 15) || n_img <= 0 ||
-      h <= 0 || w <= 0 || cout < 1 || cout > 4 || ldo < cout || k < 1 || k > MAXK || (k & 1) == 0) {
-    lfdm_set_error("conv2d_smalln: needs cout <= 4, odd k <= 7, C_in % 16 == 0, 16-byte aligned rows and filters");
-    return LFDM_EINVAL;
-  }
+  if (!x || !wgt || !out || cin <= 0 || cin % 16 != 0 || ldx < cin || ldx % 4 != 0 || !lfdm_aligned16(x) || !lfdm_aligned16(wgt) || n_img <= 0 ||
+      h <= 0 || w <= 0 || cout < 1 || cout > 4 || ldo < cout || k < 1 || k > MAXK || (k & 1) == 0)
+    return lfdm_fail(LFDM_EINVAL, "%s", "conv2d_smalln: needs cout <= 4, odd k <= 7, C_in % 16 == 0, 16-byte aligned rows and filters");
   const int64_t tiles = (int64_t)n_img * ((h + TS - 1) / TS) * ((w + TS - 1) / TS);
-  if (tiles >= (1ll << 31)) { lfdm_set_error("conv2d_smalln: too many tiles"); return LFDM_EINVAL; }
+  if (tiles >= (1ll << 31)) return lfdm_fail(LFDM_EINVAL, "conv2d_smalln: too many tiles");
   LFDM_LAUNCH(conv_smalln_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, x, ldx, cin, n_img, h, w, wgt, bias, out, ldo, cout,
               k, act);
   return lfdm_check_launch("conv2d_smalln");

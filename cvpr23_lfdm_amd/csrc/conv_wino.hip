@@ -614,10 +614,8 @@ extern "C" int lfdm_pack_wino_weight_f32(const float* w, int ld_o, int cout, int
                                          lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const int K = dgrad ? cout : cin, N = dgrad ? cin : cout;
-  if (!w || !out || cout <= 0 || cin <= 0 || K % WKC != 0 || coutp < N || coutp % 32 != 0 || ld_o < cin * 9) {
-    lfdm_set_error("pack_wino_weight: reduction channels must be a multiple of 16 and coutp a multiple of 32 >= the output channels");
-    return LFDM_EINVAL;
-  }
+  if (!w || !out || cout <= 0 || cin <= 0 || K % WKC != 0 || coutp < N || coutp % 32 != 0 || ld_o < cin * 9)
+    return lfdm_fail(LFDM_EINVAL, "pack_wino_weight: reduction channels must be a multiple of 16 and coutp a multiple of 32 >= the output channels");
   const int64_t total = (int64_t)(K / 4) * coutp;
   LFDM_LAUNCH(pack_wino_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, w, ld_o, cout, cin, coutp, dgrad, out);
   return lfdm_check_launch("pack_wino_weight");
@@ -625,10 +623,8 @@ extern "C" int lfdm_pack_wino_weight_f32(const float* w, int ld_o, int cout, int
 
 extern "C" int lfdm_pack_wino_weight_bf16(const float* w, int ld_o, int cout, int cin, int coutp, void* out, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!w || !out || cout <= 0 || cin <= 0 || cin % WKC != 0 || coutp < cout || coutp % 32 != 0 || ld_o < cin * 9 || (((uintptr_t)out) & 15) != 0) {
-    lfdm_set_error("pack_wino_weight_bf16: input channels must be a multiple of 16, coutp a multiple of 32 >= the output channels, out 16-byte aligned");
-    return LFDM_EINVAL;
-  }
+  if (!w || !out || cout <= 0 || cin <= 0 || cin % WKC != 0 || coutp < cout || coutp % 32 != 0 || ld_o < cin * 9 || !lfdm_aligned16(out))
+    return lfdm_fail(LFDM_EINVAL, "pack_wino_weight_bf16: input channels must be a multiple of 16, coutp a multiple of 32 >= the output channels, out 16-byte aligned");
   const int64_t total = (int64_t)(cin / 8) * coutp;
   LFDM_LAUNCH(pack_wino_bf16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, w, ld_o, cout, cin, coutp,
               static_cast<lfdm_bf16x8*>(out));
@@ -637,7 +633,7 @@ extern "C" int lfdm_pack_wino_weight_bf16(const float* w, int ld_o, int cout, in
 
 extern "C" int lfdm_pack_wino_weights_multi_f32(const lfdm_pack_wino_job* jobs, int n_jobs, int total_blocks, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!jobs || n_jobs <= 0 || total_blocks <= 0) { lfdm_set_error("pack_wino_weights_multi: needs a device job table and its workgroup count"); return LFDM_EINVAL; }
+  if (!jobs || n_jobs <= 0 || total_blocks <= 0) return lfdm_fail(LFDM_EINVAL, "pack_wino_weights_multi: needs a device job table and its workgroup count");
   LFDM_LAUNCH(pack_wino_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, stream, jobs, n_jobs);
   return lfdm_check_launch("pack_wino_weights_multi");
 }

@@ -709,10 +709,8 @@ __global__ __launch_bounds__(256) void pack_wino4_kernel(const float* __restrict
 
 extern "C" int lfdm_pack_wino4_weight_f32(const float* w, int ld_o, int cout, int cin, int coutp, float* out, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!w || !out || cout <= 0 || cin <= 0 || cin % W4K != 0 || coutp < cout || coutp % 32 != 0 || ld_o < cin * 9) {
-    lfdm_set_error("pack_wino4_weight: input channels must be a multiple of 8 and coutp a multiple of 32 >= the output channels");
-    return LFDM_EINVAL;
-  }
+  if (!w || !out || cout <= 0 || cin <= 0 || cin % W4K != 0 || coutp < cout || coutp % 32 != 0 || ld_o < cin * 9)
+    return lfdm_fail(LFDM_EINVAL, "pack_wino4_weight: input channels must be a multiple of 8 and coutp a multiple of 32 >= the output channels");
   const int64_t total = (int64_t)cin * coutp;
   LFDM_LAUNCH(pack_wino4_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, w, ld_o, cout, cin, coutp, out);
   return lfdm_check_launch("pack_wino4_weight");

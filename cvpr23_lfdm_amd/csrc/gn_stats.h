@@ -5,8 +5,12 @@
 // below is part of the result: where two callers associate differently (the table under "Convolution forward") the
 // difference is a template parameter, nothing here unifies arithmetic.
 #pragma once
-#include "lfdm_device.h"
+#include "norm_core.h"
 #include "../../include/lfdm_hip.h"
+
+// Most channels a GroupNorm consumer keeps per-channel tables for in LDS (gn_apply_kernel's s_a / s_b, the backward's five tables); the
+// LayerNorm backward sizes its dgamma staging by it too.  One bound, forward and backward: the launchers of both refuse more.
+constexpr int GN_MAX_C = 1024;
 
 // ---- producer side ----
 // one float4 of finished values into the lane's four per-column accumulators
@@ -91,15 +95,16 @@ __device__ __forceinline__ void gn_fold_tile(const lfdm_conv_params& p, const fl
   gn_fold_groups<NW, BN>(p, s_gn, n0, chunk);
 }
 
-// Tail of the two split-K reduce kernels (grid (row blocks, column chunks), 256 threads): a thread always sees the same column quad
-// (256 % cw == 0), gs / gq = its sum over that quad's values; local group t owns the float4 columns [t * cg4, +cg4) of the block's cw.
-__device__ __forceinline__ void splitk_gn_tail(const lfdm_conv_params& p, float (&red_s)[256], float (&red_q)[256], float gs, float gq, int cw, int cq0) {
+// Tail of the two split-K reduce kernels (grid (row blocks, column chunks), 256 threads) and of gn_partial_kernel (norm.hip: cw = C / 4,
+// cq0 = 0): a thread always sees the same column quad (256 % cw == 0), gs / gq = its sum over that quad's values; local group t owns the
+// float4 columns [t * cg4, +cg4) of the block's cw (cg4 = float4 columns per group, cw % cg4 == 0).  Writes partial[row][cq0 / cg4 + t].
+__device__ __forceinline__ void splitk_gn_tail(float* partial, int64_t row, int groups, int cg4, int cw, int cq0, float (&red_s)[256],
+                                               float (&red_q)[256], float gs, float gq) {
   const int tid = threadIdx.x;
   red_s[tid] = gs;
   red_q[tid] = gq;
   __syncthreads();
-  const int cg4 = (p.cout / p.gn_groups) / 4;      // float4 columns per group
-  const int gpb = cw / cg4;                        // groups owned by this block (cw % cg4 == 0)
+  const int gpb = cw / cg4;                        // groups owned by this block
   if (tid < gpb) {
     float ts = 0.f, tq = 0.f;
     for (int rep = 0; rep < 256; rep += cw)
@@ -107,7 +112,7 @@ __device__ __forceinline__ void splitk_gn_tail(const lfdm_conv_params& p, float 
         ts += red_s[rep + tid * cg4 + k];
         tq += red_q[rep + tid * cg4 + k];
       }
-    float* dst = p.gn_partial + ((int64_t)blockIdx.x * p.gn_groups + cq0 / cg4 + tid) * 2;
+    float* dst = partial + (row * groups + cq0 / cg4 + tid) * 2;
     dst[0] = ts;
     dst[1] = tq;
   }
@@ -160,4 +165,16 @@ __device__ __forceinline__ void gn_merge_stats(const float* __restrict__ partial
       s_rstd[g - g_lo] = (float)(1.0 / sqrt(var + (double)eps));
     }
   }
+}
+
+// The per-channel table a consumer makes of the statistics: normalised-and-affine value = x * a + b.  Sampling-path association (rstd * gamma
+// first); the training backward's channel_coeffs (train_norm.hip) forms gamma * (scale + 1) first and keeps its own.
+__device__ __forceinline__ void gn_affine(float mean, float rstd, float gamma, float beta, float& a, float& b) {
+  a = rstd * gamma;
+  b = beta - mean * a;
+}
+// ... followed by the block's conditioning: (x * a + b) * sc + sh, sc = scale + 1
+__device__ __forceinline__ void gn_affine_ss(float& a, float& b, float sc, float sh) {
+  a = a * sc;
+  b = b * sc + sh;
 }

@@ -128,41 +128,27 @@ extern "C" int lfdm_latent_resample_f32(const float* latent, const int* idx, con
                                         float* out, float* conf, int batch, int channels, int frames, int out_frames, int h, int w,
                                         int mode, int clamp_from, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!latent || !idx || !frac || !out || ((uintptr_t)latent & 15) || ((uintptr_t)out & 15) || ((uintptr_t)conf & 15) ||
-      ((uintptr_t)idx & 3) || ((uintptr_t)frac & 3)) {
-    lfdm_set_error("latent_resample: null latent / idx / frac / out, or latent / out / conf not 16-byte aligned");
-    return LFDM_EINVAL;
-  }
-  if (mode != LFDM_RESAMPLE_LINEAR && mode != LFDM_RESAMPLE_CUBIC) {
-    lfdm_set_error("latent_resample: mode is LFDM_RESAMPLE_LINEAR or LFDM_RESAMPLE_CUBIC");
-    return LFDM_EINVAL;
-  }
+  if (!latent || !idx || !frac || !out || !lfdm_aligned16(latent) || !lfdm_aligned16(out) || !lfdm_aligned16(conf) ||
+      !lfdm_aligned<4>(idx) || !lfdm_aligned<4>(frac))
+    return lfdm_fail(LFDM_EINVAL, "latent_resample: null latent / idx / frac / out, or latent / out / conf not 16-byte aligned");
+  if (mode != LFDM_RESAMPLE_LINEAR && mode != LFDM_RESAMPLE_CUBIC)
+    return lfdm_fail(LFDM_EINVAL, "latent_resample: mode is LFDM_RESAMPLE_LINEAR or LFDM_RESAMPLE_CUBIC");
   if (batch < 1 || channels < 1 || frames < 1 || out_frames < 1 || h < 1 || w < 1 || batch > 65535 || out_frames > 65535 ||
-      clamp_from < 0) {
-    lfdm_set_error("latent_resample: batch, channels, frames, out_frames, h, w >= 1, batch and out_frames <= 65535, clamp_from >= 0");
-    return LFDM_EINVAL;
-  }
+      clamp_from < 0)
+    return lfdm_fail(LFDM_EINVAL, "latent_resample: batch, channels, frames, out_frames, h, w >= 1, batch and out_frames <= 65535, clamp_from >= 0");
   const int64_t plane = (int64_t)h * w;
-  if ((plane & 3) || plane > 0x7fffffff) {
-    lfdm_set_error("latent_resample: h * w must be a multiple of 4 (below 2^31)");
-    return LFDM_EINVAL;
-  }
+  if ((plane & 3) || plane > 0x7fffffff)
+    return lfdm_fail(LFDM_EINVAL, "latent_resample: h * w must be a multiple of 4 (below 2^31)");
   const bool maps = conf != nullptr;
-  if ((ident_x == nullptr) != (ident_y == nullptr) || (ident_x && !maps)) {
-    lfdm_set_error("latent_resample: ident_x and ident_y come together, and only with conf (the maps form)");
-    return LFDM_EINVAL;
-  }
-  if (maps && channels != 3) {
-    lfdm_set_error("latent_resample: the maps form (conf given) needs channels == 3");
-    return LFDM_EINVAL;
-  }
+  if ((ident_x == nullptr) != (ident_y == nullptr) || (ident_x && !maps))
+    return lfdm_fail(LFDM_EINVAL, "latent_resample: ident_x and ident_y come together, and only with conf (the maps form)");
+  if (maps && channels != 3)
+    return lfdm_fail(LFDM_EINVAL, "latent_resample: the maps form (conf given) needs channels == 3");
   const int64_t in_floats = (int64_t)batch * channels * frames * plane, out_floats = (int64_t)batch * channels * out_frames * plane;
   const int64_t conf_floats = (int64_t)batch * out_frames * plane;
   if (overlaps(latent, in_floats, out, out_floats) || (maps && (overlaps(latent, in_floats, conf, conf_floats) ||
-                                                                overlaps(out, out_floats, conf, conf_floats)))) {
-    lfdm_set_error("latent_resample: out / conf may not alias latent or each other");
-    return LFDM_EINVAL;
-  }
+                                                                overlaps(out, out_floats, conf, conf_floats))))
+    return lfdm_fail(LFDM_EINVAL, "latent_resample: out / conf may not alias latent or each other");
   ResampleArgs a;
   a.latent = latent;
   a.idx = idx;

@@ -360,13 +360,11 @@ extern "C" int lfdm_depthwise_down_planar_f32(const float* x, const float* wgt, 
                                               lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !wgt || !out || n_img <= 0 || channels <= 0 || h <= 0 || w <= 0 || k <= 0 || k * k > DW_MAX_TAPS || stride <= 0 ||
-      pad_lo < 0 || pad_hi < 0 || n_img > 65535 || channels > 65535) {
-    lfdm_set_error("depthwise_down: bad arguments");
-    return LFDM_EINVAL;
-  }
+      pad_lo < 0 || pad_hi < 0 || n_img > 65535 || channels > 65535)
+    return lfdm_fail(LFDM_EINVAL, "depthwise_down: bad arguments");
   // full-resolution output of the padded convolution has (h + pad_lo + pad_hi - k + 1) rows; keep every stride-th
   const int hf = h + pad_lo + pad_hi - k + 1, wf = w + pad_lo + pad_hi - k + 1;
-  if (hf <= 0 || wf <= 0) { lfdm_set_error("depthwise_down: kernel larger than the padded input"); return LFDM_EINVAL; }
+  if (hf <= 0 || wf <= 0) return lfdm_fail(LFDM_EINVAL, "depthwise_down: kernel larger than the padded input");
   const int ho = (hf + stride - 1) / stride, wo = (wf + stride - 1) / stride;
   LFDM_LAUNCH(depthwise_down_kernel, dim3((unsigned)((ho * wo + 255) / 256), (unsigned)channels, (unsigned)n_img), dim3(256), 0,
               stream, x, wgt, out, channels, h, w, k, pad_lo, stride, ho, wo);
@@ -383,10 +381,8 @@ extern "C" int lfdm_lfae_motion_inputs_f32(const float* src_img, const float* dr
   if (!src_img || !drv_shift || !src_shift || !rows || !sparse || batch <= 0 || frames <= 0 || regions <= 0 ||
       regions > MOT_MAX_K || h < 2 || w < 2 || n > 65535 || ld % 4 != 0 || ld < 4 * (regions + 1) ||
       ((drv_covar == nullptr) != (src_covar == nullptr)) || ((drv_affine == nullptr) != (src_affine == nullptr)) ||
-      (!drv_covar && !(region_var > 0.f)) || (((uintptr_t)rows) & 15) != 0 || (((uintptr_t)sparse) & 7) != 0) {
-    lfdm_set_error("lfae_motion_inputs: bad arguments (3-channel source, <= 32 regions, ld % 4 == 0 and >= 4*(regions+1))");
-    return LFDM_EINVAL;
-  }
+      (!drv_covar && !(region_var > 0.f)) || !lfdm_aligned16(rows) || !lfdm_aligned<8>(sparse))
+    return lfdm_fail(LFDM_EINVAL, "%s", "lfae_motion_inputs: bad arguments (3-channel source, <= 32 regions, ld % 4 == 0 and >= 4*(regions+1))");
   LFDM_LAUNCH(lfae_motion_inputs_kernel, dim3((unsigned)((h * w + 255) / 256), (unsigned)n), dim3(256), 0, stream, src_img,
               drv_shift, drv_covar, drv_affine, src_shift, src_covar, src_affine, bg, region_var, revert_axis_swap, frames, regions,
               h, w, rows, ld, sparse);
@@ -397,10 +393,8 @@ extern "C" int lfdm_lfae_motion_combine_f32(const float* heads, int ldh, const f
                                             float* flow, float* occ, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!heads || !sparse || !flow || n_img <= 0 || regions <= 0 || hw <= 0 || ldh < regions + 1 + (occ ? 1 : 0) ||
-      (((uintptr_t)sparse) & 7) != 0 || (((uintptr_t)flow) & 7) != 0) {
-    lfdm_set_error("lfae_motion_combine: bad arguments");
-    return LFDM_EINVAL;
-  }
+      !lfdm_aligned<8>(sparse) || !lfdm_aligned<8>(flow))
+    return lfdm_fail(LFDM_EINVAL, "lfae_motion_combine: bad arguments");
   const int64_t total = (int64_t)n_img * hw;
   LFDM_LAUNCH(lfae_motion_combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, heads, ldh, sparse, regions,
               hw, total, flow, occ);
@@ -412,10 +406,8 @@ extern "C" int lfdm_lfae_region_stats_f32(const float* logits, int ldh, int n_im
                                           lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!logits || !heatmap || !shift || !covar || !affine || !u || !d || n_img <= 0 || n_img > 65535 || regions <= 0 ||
-      ldh < regions || h < 2 || w < 2 || h * w > 256 * RS_PER || !(temperature > 0.f)) {
-    lfdm_set_error("lfae_region_stats: bad arguments (h*w <= 4096)");
-    return LFDM_EINVAL;
-  }
+      ldh < regions || h < 2 || w < 2 || h * w > 256 * RS_PER || !(temperature > 0.f))
+    return lfdm_fail(LFDM_EINVAL, "lfae_region_stats: bad arguments (h*w <= 4096)");
   LFDM_LAUNCH(lfae_region_stats_kernel, dim3((unsigned)regions, (unsigned)n_img), dim3(256), 0, stream, logits, ldh, regions, h, w,
               temperature, heatmap, shift, covar, affine, u, d);
   return lfdm_check_launch("lfae_region_stats");
@@ -423,7 +415,7 @@ extern "C" int lfdm_lfae_region_stats_f32(const float* logits, int ldh, int n_im
 
 extern "C" int lfdm_svd2x2_sym_f32(const float* abc, int64_t n, float* u, float* s, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!abc || !u || !s || n <= 0) { lfdm_set_error("svd2x2_sym: bad arguments"); return LFDM_EINVAL; }
+  if (!abc || !u || !s || n <= 0) return lfdm_fail(LFDM_EINVAL, "svd2x2_sym: bad arguments");
   LFDM_LAUNCH(svd2x2_sym_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, abc, n, u, s);
   return lfdm_check_launch("svd2x2_sym");
 }

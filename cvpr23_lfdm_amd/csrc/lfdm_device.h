@@ -357,6 +357,39 @@ __device__ __forceinline__ float apply_act(float v, int act) {
   return v;
 }
 
-// host-side error plumbing (lfdm_capi.cpp)
+// host-side error plumbing (lfdm_capi.hip)
 extern "C" void lfdm_set_error(const char* msg);
 int lfdm_check_launch(const char* what);
+// the one way to refuse: sets the error text (printf-style) and returns `code`
+int lfdm_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+
+// every pointer is a multiple of N bytes (a null pointer passes: optional operands)
+template <unsigned N = 16, class... P>
+inline bool lfdm_aligned(const P*... p) {
+  return ((0 | ... | (uintptr_t)p) & (N - 1)) == 0;
+}
+template <class... P>
+inline bool lfdm_aligned16(const P*... p) {
+  return lfdm_aligned<16>(p...);
+}
+
+// workgroups of a grid-stride launch: ceil(items / per_block) clamped to [1, cap]
+inline unsigned lfdm_blocks(int64_t items, int64_t per_block, int64_t cap) {
+  const int64_t nb = (items + per_block - 1) / per_block;
+  return (unsigned)(nb < 1 ? 1 : nb > cap ? cap : nb);
+}
+
+// Cuts a workspace into its parts, in order: the *_ws_bytes query and the launcher run the same carve function, once over a null base
+// for the size and once over the caller's buffer, so the two cannot drift apart.  Every part starts where the previous one ended (the
+// parts are sized in whole floats / words: no padding, today's offsets).
+struct lfdm_carver {
+  char* base;
+  size_t bytes = 0;
+  explicit lfdm_carver(void* ws) : base((char*)ws) {}
+  template <class T>
+  T* take(size_t count) {
+    T* p = base ? (T*)(base + bytes) : nullptr;
+    bytes += count * sizeof(T);
+    return p;
+  }
+};

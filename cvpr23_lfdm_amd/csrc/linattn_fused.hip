@@ -471,14 +471,10 @@ extern "C" int lfdm_linear_attention_fused_cl_f32(const float* x, int ldx, int c
                                                   lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !wqkv || !out || n_frames <= 0 || hw <= 0 || hw > 64 * 64 || channels != C || ldx < C || ldx % 4 != 0 ||
-      (((uintptr_t)x | (uintptr_t)wqkv) & 15) || (int64_t)n_frames * HEADS > 0x7fffffff) {
-    lfdm_set_error("linear_attention_fused: needs C == 64 and 16-byte aligned rows");
-    return LFDM_EINVAL;
-  }
-  if (!ws || ws_bytes < lfdm_linear_attention_fused_ws_bytes(n_frames, hw)) {
-    lfdm_set_error("linear_attention_fused: workspace too small");
-    return LFDM_EWORKSPACE;
-  }
+      !lfdm_aligned16(x, wqkv) || (int64_t)n_frames * HEADS > 0x7fffffff)
+    return lfdm_fail(LFDM_EINVAL, "linear_attention_fused: needs C == 64 and 16-byte aligned rows");
+  if (!ws || ws_bytes < lfdm_linear_attention_fused_ws_bytes(n_frames, hw))
+    return lfdm_fail(LFDM_EWORKSPACE, "linear_attention_fused: workspace too small");
   float* ctx = nullptr;
   launch_ctx_and_merge(x, ldx, wqkv, nullptr, n_frames, hw, ln_eps, ws, &ctx, stream);
   const int64_t otiles = (int64_t)((hw + 31) / 32) * n_frames;
@@ -493,15 +489,11 @@ extern "C" int lfdm_linear_attention_fused_out_cl_f32(const float* x, int ldx, i
                                                       void* ws, size_t ws_bytes, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !wqkv || !wout || !out || out == x || n_frames <= 0 || hw <= 0 || hw > 64 * 64 || channels != C || ldx < C || ldx % 4 != 0 || ldo < C ||
-      ldo % 4 != 0 || (((uintptr_t)x | (uintptr_t)wqkv | (uintptr_t)wout | (uintptr_t)out | (uintptr_t)bias_out) & 15) ||
-      (int64_t)n_frames * HEADS > 0x7fffffff || n_frames > 65535) {
-    lfdm_set_error("linear_attention_fused_out: needs C == 64, 16-byte aligned rows, out != x, <= 65535 frames");
-    return LFDM_EINVAL;
-  }
-  if (!ws || ws_bytes < lfdm_linear_attention_fused_ws_bytes(n_frames, hw)) {
-    lfdm_set_error("linear_attention_fused_out: workspace too small");
-    return LFDM_EWORKSPACE;
-  }
+      ldo % 4 != 0 || !lfdm_aligned16(x, wqkv, wout, out, bias_out) ||
+      (int64_t)n_frames * HEADS > 0x7fffffff || n_frames > 65535)
+    return lfdm_fail(LFDM_EINVAL, "linear_attention_fused_out: needs C == 64, 16-byte aligned rows, out != x, <= 65535 frames");
+  if (!ws || ws_bytes < lfdm_linear_attention_fused_ws_bytes(n_frames, hw))
+    return lfdm_fail(LFDM_EWORKSPACE, "linear_attention_fused_out: workspace too small");
   float* mt = nullptr;
   launch_ctx_and_merge(x, ldx, wqkv, wout, n_frames, hw, ln_eps, ws, &mt, stream);
   LFDM_LAUNCH(linattn_fused_out2_kernel, dim3((hw + 31) / 32, n_frames), dim3(256), 0, stream, x, ldx, wqkv, bias_out, (const float*)mt, hw,

@@ -231,31 +231,21 @@ extern "C" size_t lfdm_video_metrics_ws_bytes(int batch, int channels, int frame
 extern "C" int lfdm_video_metrics(const float* a, const float* b, const double* mean_over_255, int domain, double* out, int batch,
                                   int channels, int frames, int h, int w, void* ws, size_t ws_bytes, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!a || !b || !out || !ws || ((uintptr_t)out & 7) || ((uintptr_t)ws & 7) || !video_shape_ok(batch, channels, frames, h, w)) {
-    lfdm_set_error("video_metrics: bad arguments (non-null a / b / out / ws, out and ws 8-byte aligned, batch, frames >= 1, "
+  if (!a || !b || !out || !ws || !lfdm_aligned<8>(out) || !lfdm_aligned<8>(ws) || !video_shape_ok(batch, channels, frames, h, w))
+    return lfdm_fail(LFDM_EINVAL, "video_metrics: bad arguments (non-null a / b / out / ws, out and ws 8-byte aligned, batch, frames >= 1, "
                    "1 <= channels <= 4, 11 <= h, w <= 32768)");
-    return LFDM_EINVAL;
-  }
-  if (domain != LFDM_METRIC_RAW && domain != LFDM_METRIC_UNIT && domain != LFDM_METRIC_UINT8) {
-    lfdm_set_error("video_metrics: domain is not one of LFDM_METRIC_RAW / _UNIT / _UINT8");
-    return LFDM_EINVAL;
-  }
-  if (domain != LFDM_METRIC_RAW && !mean_over_255) {
-    lfdm_set_error("video_metrics: the unit and uint8 domains need mean_over_255 (channels doubles)");
-    return LFDM_EINVAL;
-  }
+  if (domain != LFDM_METRIC_RAW && domain != LFDM_METRIC_UNIT && domain != LFDM_METRIC_UINT8)
+    return lfdm_fail(LFDM_EINVAL, "video_metrics: domain is not one of LFDM_METRIC_RAW / _UNIT / _UINT8");
+  if (domain != LFDM_METRIC_RAW && !mean_over_255)
+    return lfdm_fail(LFDM_EINVAL, "video_metrics: the unit and uint8 domains need mean_over_255 (channels doubles)");
   VideoMetricArgs g;
   const int tiles = metric_tiles(h, w, &g.tiles_x, &g.tiles_y);
   const int64_t n_frames = (int64_t)batch * frames;
   const int64_t blocks = n_frames * channels * tiles;
-  if (blocks > 0x7fffffff || n_frames * 3 > 0x7fffffff) {
-    lfdm_set_error("video_metrics: batch * frames * channels * tiles exceeds 2^31 - 1");
-    return LFDM_EINVAL;
-  }
-  if (ws_bytes < (size_t)blocks * 3 * sizeof(double)) {
-    lfdm_set_error("video_metrics: workspace smaller than lfdm_video_metrics_ws_bytes");
-    return LFDM_EINVAL;
-  }
+  if (blocks > 0x7fffffff || n_frames * 3 > 0x7fffffff)
+    return lfdm_fail(LFDM_EINVAL, "video_metrics: batch * frames * channels * tiles exceeds 2^31 - 1");
+  if (ws_bytes < (size_t)blocks * 3 * sizeof(double))
+    return lfdm_fail(LFDM_EINVAL, "video_metrics: workspace smaller than lfdm_video_metrics_ws_bytes");
   g.a = a;
   g.b = b;
   g.partial = (double*)ws;
@@ -285,12 +275,10 @@ extern "C" int lfdm_flow_metrics(const float* grid_a, int64_t stride_a, const fl
                                  const float* conf_b, double* out, int batch, int frames, int s, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   const int64_t need = (int64_t)2 * frames * s * s;
-  if (!grid_a || !grid_b || !out || ((uintptr_t)out & 7) || batch < 1 || frames < 1 || s < 1 || s > 4096 || stride_a < need ||
-      stride_b < need || (int64_t)batch * frames > 0x7fffffff || (conf_a == nullptr) != (conf_b == nullptr)) {
-    lfdm_set_error("flow_metrics: bad arguments (non-null grids and out, out 8-byte aligned, batch, frames >= 1, 1 <= s <= 4096, "
+  if (!grid_a || !grid_b || !out || !lfdm_aligned<8>(out) || batch < 1 || frames < 1 || s < 1 || s > 4096 || stride_a < need ||
+      stride_b < need || (int64_t)batch * frames > 0x7fffffff || (conf_a == nullptr) != (conf_b == nullptr))
+    return lfdm_fail(LFDM_EINVAL, "flow_metrics: bad arguments (non-null grids and out, out 8-byte aligned, batch, frames >= 1, 1 <= s <= 4096, "
                    "batch strides >= 2 * frames * s * s, both confidences or neither)");
-    return LFDM_EINVAL;
-  }
   LFDM_LAUNCH(flow_metrics_kernel, dim3((unsigned)(batch * frames)), dim3(kMetricBlock), 0, stream, grid_a, stride_a, grid_b, stride_b,
               conf_a, conf_b, out, frames, s);
   return lfdm_check_launch("flow_metrics");
@@ -298,10 +286,8 @@ extern "C" int lfdm_flow_metrics(const float* grid_a, int64_t stride_a, const fl
 
 extern "C" int lfdm_psnr_f64(const double* mse, double* out, int64_t n, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!mse || !out || n < 1 || (n + kMetricBlock - 1) / kMetricBlock > 0x7fffffff) {
-    lfdm_set_error("psnr: bad arguments (non-null mse / out, 1 <= n < 2^39)");
-    return LFDM_EINVAL;
-  }
+  if (!mse || !out || n < 1 || (n + kMetricBlock - 1) / kMetricBlock > 0x7fffffff)
+    return lfdm_fail(LFDM_EINVAL, "psnr: bad arguments (non-null mse / out, 1 <= n < 2^39)");
   LFDM_LAUNCH(psnr_kernel, dim3((unsigned)((n + kMetricBlock - 1) / kMetricBlock)), dim3(kMetricBlock), 0, stream, mse, out, n);
   return lfdm_check_launch("psnr");
 }

@@ -40,33 +40,18 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict
   if (prow < rows_per_iter) {
     for (int p = p0 + prow; p < p1; p += rows_per_iter) {
       const float4 v = *reinterpret_cast<const float4*>(xb + (int64_t)p * channels + 4 * c4);
-      s += (v.x + v.y) + (v.z + v.w);
-      q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+      s += hsum4(v);
+      q += sq4(v);
     }
   }
-  red_s[tid] = s;
-  red_q[tid] = q;
-  __syncthreads();
-  if (tid < groups) {
-    const int cg4 = c4n / groups;  // float4 per group per pixel
-    float ts = 0.f, tq = 0.f;
-    for (int r = 0; r < rows_per_iter; ++r)
-      for (int k = 0; k < cg4; ++k) {
-        const int t = r * c4n + tid * cg4 + k;
-        ts += red_s[t];
-        tq += red_q[t];
-      }
-    float* dst = partial + (((int64_t)b * nchunk + chunk) * groups + tid) * 2;
-    dst[0] = ts;
-    dst[1] = tq;
-  }
+  // thread g sums the rows_per_iter x (c4n / groups) slots of group g: the split-K reduce kernels' fold with one block owning every column
+  splitk_gn_tail(partial, (int64_t)b * nchunk + chunk, groups, c4n / groups, c4n, 0, red_s, red_q, s, q);
 }
 
 // Finalize + apply in one launch.  grid (blocks_per_sample, B).  Every workgroup first merges the
 // (sum, sumsq) partials of its sample in double (fixed order -> bit reproducible) and folds
 // mean / rstd / gamma / beta / (scale+1, shift) into one FMA per channel kept in LDS, then streams its
 // slice:  y = silu(x * A[c] + Bc[c]) (+ residual).
-constexpr int GN_MAX_C = 1024;
 // NT threads per workgroup (256 / 512 / 1024).  Every workgroup repeats the merge of the partials, so fewer, larger workgroups
 // (LFDM_GN_BLOCK, LFDM_GN_F4) trade memory-level parallelism for less redundant L2 traffic: with 320 partial chunks x 16
 // groups (the merged output heads) the 2560 256-thread workgroups of round 2 read 100 MB of partials for a 21 MB tensor.
@@ -137,14 +122,12 @@ __global__ __launch_bounds__(NT) void gn_apply_kernel(
     for (int c = tid; c < channels; c += NT, ++j) {
       const int g = c / cg;
       const bool pre = j < PREC;
-      const float a = s_rstd[g] * (pre ? (j == 0 ? p_g[0] : p_g[1]) : gamma[c]);
-      float bb = (pre ? (j == 0 ? p_b[0] : p_b[1]) : beta[c]) - s_mean[g] * a;
-      float aa = a;
+      float aa, bb;
+      gn_affine(s_mean[g], s_rstd[g], pre ? (j == 0 ? p_g[0] : p_g[1]) : gamma[c], pre ? (j == 0 ? p_b[0] : p_b[1]) : beta[c], aa, bb);
       if (scale_shift) {
         const float sc = (pre ? (j == 0 ? p_sc[0] : p_sc[1]) : scale_shift[(int64_t)b * ss_ld + c]) + 1.0f;
         const float sh = pre ? (j == 0 ? p_sh[0] : p_sh[1]) : scale_shift[(int64_t)b * ss_ld + channels + c];
-        aa = a * sc;
-        bb = bb * sc + sh;
+        gn_affine_ss(aa, bb, sc, sh);
       }
       s_a[c] = aa;
       s_b[c] = bb;
@@ -157,24 +140,9 @@ __global__ __launch_bounds__(NT) void gn_apply_kernel(
     const float4 v = k == 0 ? pre_v[0] : k == 1 ? pre_v[1] : xb[i];
     const float4 a = *reinterpret_cast<const float4*>(s_a + 4 * c4);
     const float4 d = *reinterpret_cast<const float4*>(s_b + 4 * c4);
-    float4 y;
-    y.x = fmaf(v.x, a.x, d.x);
-    y.y = fmaf(v.y, a.y, d.y);
-    y.z = fmaf(v.z, a.z, d.z);
-    y.w = fmaf(v.w, a.w, d.w);
-    if (silu) {
-      y.x = silu_fast_(y.x);
-      y.y = silu_fast_(y.y);
-      y.z = silu_fast_(y.z);
-      y.w = silu_fast_(y.w);
-    }
-    if (rb) {
-      const float4 r = k == 0 ? pre_r[0] : k == 1 ? pre_r[1] : rb[i];
-      y.x += r.x;
-      y.y += r.y;
-      y.z += r.z;
-      y.w += r.w;
-    }
+    float4 y = fma4(v, a, d);
+    if (silu) y = map4([](float e) { return silu_fast_(e); }, y);
+    if (rb) add4(y, k == 0 ? pre_r[0] : k == 1 ? pre_r[1] : rb[i]);
     ob[i] = y;
   }
 }
@@ -189,11 +157,6 @@ __global__ __launch_bounds__(256) void layernorm_small_kernel(const float* __res
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int sub = lane / C4N, f = lane % C4N;
   const float4 g = reinterpret_cast<const float4*>(gamma)[f];
-  auto group_sum = [&](float v) {
-#pragma unroll
-    for (int m = 1; m < C4N; m <<= 1) v += __shfl_xor(v, m);
-    return v;
-  };
   const int64_t stride = (int64_t)gridDim.x * 4 * RPW * 2;
   for (int64_t row0 = ((int64_t)blockIdx.x * 4 + wave) * RPW * 2; row0 < rows; row0 += stride) {
     float4 v[2];
@@ -206,18 +169,10 @@ __global__ __launch_bounds__(256) void layernorm_small_kernel(const float* __res
     }
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-      const float mean = group_sum((v[u].x + v[u].y) + (v[u].z + v[u].w)) / (float)C;
-      const float a = v[u].x - mean, b = v[u].y - mean, c = v[u].z - mean, d = v[u].w - mean;
-      const float var = group_sum((a * a + b * b) + (c * c + d * d)) / (float)C;
-      const float denom = sqrtf(var + eps);
-      if (live[u]) {
-        float4 y;
-        y.x = a / denom * g.x;
-        y.y = b / denom * g.y;
-        y.z = c / denom * g.z;
-        y.w = d / denom * g.w;
-        reinterpret_cast<float4*>(out + (row0 + u * RPW + sub) * C)[f] = y;
-      }
+      float4 d;
+      const float denom = sqrtf(ln_row_stats_group<C4N>(v[u], d).var + eps);      // (the forward divides, the backward multiplies by 1 / denom)
+      if (live[u])
+        reinterpret_cast<float4*>(out + (row0 + u * RPW + sub) * C)[f] = map4([denom](float e, float ge) { return e / denom * ge; }, d, g);
     }
   }
 }
@@ -232,40 +187,20 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
   for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < rows; row += (int64_t)gridDim.x * 4) {
     const float4* xr = reinterpret_cast<const float4*>(x + row * channels);
     float4 v[4];
-    float s = 0.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int f = lane + 64 * i;
-      v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (f < c4n) {
-        v[i] = xr[f];
-        s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-      }
+      v[i] = f < c4n ? xr[f] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    const float mean = wave_sum(s) / (float)channels;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int f = lane + 64 * i;
-      if (f < c4n) {
-        const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
-        q += (a * a + b * b) + (c * c + d * d);
-      }
-    }
-    const float var = wave_sum(q) / (float)channels;
-    const float denom = sqrtf(var + eps);
+    const ln_stats st = ln_row_stats_wave(v, lane, c4n, channels);
+    const float mean = st.mean, denom = sqrtf(st.var + eps);      // (the forward divides, the backward multiplies by 1 / denom)
     float4* orow = reinterpret_cast<float4*>(out + row * channels);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int f = lane + 64 * i;
       if (f < c4n) {
         const float4 g = reinterpret_cast<const float4*>(gamma)[f];
-        float4 y;
-        y.x = (v[i].x - mean) / denom * g.x;
-        y.y = (v[i].y - mean) / denom * g.y;
-        y.z = (v[i].z - mean) / denom * g.z;
-        y.w = (v[i].w - mean) / denom * g.w;
-        orow[f] = y;
+        orow[f] = map4([=](float e, float ge) { return (e - mean) / denom * ge; }, v[i], g);
       }
     }
   }
@@ -284,12 +219,7 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const float* __restrict
     const float4 v = *reinterpret_cast<const float4*>(x + r * ldx + c);
     const float4 aa = *reinterpret_cast<const float4*>(a + c);
     const float4 bb = *reinterpret_cast<const float4*>(b + c);
-    float4 y;
-    y.x = apply_act(fmaf(v.x, aa.x, bb.x), act);
-    y.y = apply_act(fmaf(v.y, aa.y, bb.y), act);
-    y.z = apply_act(fmaf(v.z, aa.z, bb.z), act);
-    y.w = apply_act(fmaf(v.w, aa.w, bb.w), act);
-    *reinterpret_cast<float4*>(out + r * ldo + c) = y;
+    *reinterpret_cast<float4*>(out + r * ldo + c) = map4([act](float e) { return apply_act(e, act); }, fma4(v, aa, bb));
   }
 }
 
@@ -311,12 +241,8 @@ __global__ __launch_bounds__(256) void avgpool2_kernel(const float* __restrict__
     const float4 v01 = *reinterpret_cast<const float4*>(base + channels);
     const float4 v10 = *reinterpret_cast<const float4*>(base + (int64_t)w * channels);
     const float4 v11 = *reinterpret_cast<const float4*>(base + (int64_t)w * channels + channels);
-    float4 y;
-    y.x = ((v00.x + v01.x) + (v10.x + v11.x)) * 0.25f;
-    y.y = ((v00.y + v01.y) + (v10.y + v11.y)) * 0.25f;
-    y.z = ((v00.z + v01.z) + (v10.z + v11.z)) * 0.25f;
-    y.w = ((v00.w + v01.w) + (v10.w + v11.w)) * 0.25f;
-    *reinterpret_cast<float4*>(out + (((int64_t)n * ho + oy) * wo + ox) * channels + c) = y;
+    *reinterpret_cast<float4*>(out + (((int64_t)n * ho + oy) * wo + ox) * channels + c) =
+        map4([](float a, float b, float c, float d) { return ((a + b) + (c + d)) * 0.25f; }, v00, v01, v10, v11);
   }
 }
 
@@ -355,13 +281,6 @@ __global__ __launch_bounds__(256) void cl_to_planar_kernel(const float* __restri
   }
 }
 
-inline unsigned grid_for(int64_t work_items, unsigned cap = 8192) {
-  int64_t nb = (work_items + 255) / 256;
-  if (nb < 1) nb = 1;
-  if (nb > cap) nb = cap;
-  return (unsigned)nb;
-}
-
 void launch_gn_apply(const float* x, float* out, int batch, int pixels, int channels, int groups,
                      const float* partial, int nchunk, const float* gamma, const float* beta,
                      const float* scale_shift, int ss_ld, float eps, int silu, const float* residual,
@@ -380,9 +299,7 @@ void launch_gn_apply(const float* x, float* out, int batch, int pixels, int chan
   }
   if (env_f4 > 0) f4 = env_f4;
   if (env_nt == 256 || env_nt == 512 || env_nt == 1024) nt = env_nt;
-  int64_t nb = (per_b + (int64_t)nt * f4 - 1) / ((int64_t)nt * f4);
-  if (nb < 1) nb = 1;
-  if (nb > 8192) nb = 8192;        // per sample (grid y = batch); the 2C-channel output heads need 5120 at 32x32 x 40 frames
+  const int64_t nb = lfdm_blocks(per_b, (int64_t)nt * f4, 8192);        // per sample (grid y = batch); the 2C-channel output heads need 5120 at 32x32 x 40 frames
   const dim3 grid((unsigned)nb, batch);
   // XCD-affine run order (see the kernel): R = runs of nt float4 per 128-pixel tile block, a power of two; whole groups of 8R runs only
   int xcd_r = 0;
@@ -412,11 +329,24 @@ void launch_gn_apply(const float* x, float* out, int batch, int pixels, int chan
 
 }  // namespace
 
-extern "C" size_t lfdm_groupnorm_ws_bytes(int batch, int pixels, int channels) {
-  const size_t partial = (size_t)batch * gn_num_chunks(pixels) * 64 * 2;
-  const size_t ab = (size_t)batch * 2 * channels;
-  return (partial + ab) * sizeof(float);
+namespace {
+// The GroupNorm forward workspace: partial[b][chunk][64 group slots][2], then 2 * C floats per sample that older callers size for and no
+// kernel uses any more (the per-channel table lives in LDS) - kept so that lfdm_groupnorm_ws_bytes answers what it always did.
+struct GnWs {
+  float* partial;
+  size_t bytes;
+};
+GnWs carve_gn_ws(void* ws, int batch, int pixels, int channels) {
+  lfdm_carver c(ws);
+  GnWs w;
+  w.partial = c.take<float>((size_t)batch * gn_num_chunks(pixels) * 64 * 2);
+  c.take<float>((size_t)batch * 2 * channels);
+  w.bytes = c.bytes;
+  return w;
 }
+}  // namespace
+
+extern "C" size_t lfdm_groupnorm_ws_bytes(int batch, int pixels, int channels) { return carve_gn_ws(nullptr, batch, pixels, channels).bytes; }
 
 extern "C" int lfdm_groupnorm_silu_cl_f32(const float* x, float* out, int batch, int pixels,
                                           int channels, int groups, const float* gamma,
@@ -426,20 +356,15 @@ extern "C" int lfdm_groupnorm_silu_cl_f32(const float* x, float* out, int batch,
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !out || !gamma || !beta || batch <= 0 || pixels <= 0 || channels <= 0 || groups <= 0 ||
       groups > 64 || (scale_shift && ss_ld < 2 * channels) || channels % groups != 0 || (channels / groups) % 4 != 0 ||
-      256 % (channels / 4) != 0) {
-    lfdm_set_error("groupnorm: unsupported shape (need C%G==0, (C/G)%4==0, 256%(C/4)==0)");
-    return LFDM_EINVAL;
-  }
-  if (((((uintptr_t)x) | ((uintptr_t)out) | ((uintptr_t)residual)) & 15) != 0) {      // (both kernels walk the rows as float4)
-    lfdm_set_error("groupnorm: x, out and residual must be 16-byte aligned (dense rows of C floats, read and written as float4)");
-    return LFDM_EINVAL;
-  }
-  if (!ws || ws_bytes < lfdm_groupnorm_ws_bytes(batch, pixels, channels)) {
-    lfdm_set_error("groupnorm: workspace too small");
-    return LFDM_EWORKSPACE;
-  }
+      256 % (channels / 4) != 0)
+    return lfdm_fail(LFDM_EINVAL, "%s", "groupnorm: unsupported shape (need C%G==0, (C/G)%4==0, 256%(C/4)==0)");
+  if (!lfdm_aligned16(x, out, residual))      // (both kernels walk the rows as float4)
+    return lfdm_fail(LFDM_EINVAL, "groupnorm: x, out and residual must be 16-byte aligned (dense rows of C floats, read and written as float4)");
+  const GnWs w = carve_gn_ws(ws, batch, pixels, channels);
+  if (!ws || ws_bytes < w.bytes)
+    return lfdm_fail(LFDM_EWORKSPACE, "groupnorm: workspace too small");
   const int nchunk = gn_num_chunks(pixels);
-  float* partial = reinterpret_cast<float*>(ws);
+  float* partial = w.partial;
   LFDM_LAUNCH(gn_partial_kernel, dim3(nchunk, batch), dim3(256), 0, stream, x, pixels, channels,
               groups, partial);
   launch_gn_apply(x, out, batch, pixels, channels, groups, (const float*)partial, nchunk, gamma, beta,
@@ -456,14 +381,10 @@ extern "C" int lfdm_groupnorm_apply_cl_f32(const float* x, float* out, int batch
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !out || !gamma || !beta || !partial || nchunk <= 0 || batch <= 0 || pixels <= 0 ||
       channels <= 0 || channels > GN_MAX_C || groups <= 0 || groups > 64 || channels % groups != 0 ||
-      channels % 4 != 0 || (scale_shift && ss_ld < 2 * channels)) {
-    lfdm_set_error("groupnorm_apply: bad arguments");
-    return LFDM_EINVAL;
-  }
-  if (((((uintptr_t)x) | ((uintptr_t)out) | ((uintptr_t)residual)) & 15) != 0 || (((uintptr_t)partial) & 7) != 0) {
-    lfdm_set_error("groupnorm_apply: x, out and residual must be 16-byte aligned (dense rows of C floats, read and written as float4), partial 8-byte");
-    return LFDM_EINVAL;
-  }
+      channels % 4 != 0 || (scale_shift && ss_ld < 2 * channels))
+    return lfdm_fail(LFDM_EINVAL, "groupnorm_apply: bad arguments");
+  if (!lfdm_aligned16(x, out, residual) || !lfdm_aligned<8>(partial))
+    return lfdm_fail(LFDM_EINVAL, "groupnorm_apply: x, out and residual must be 16-byte aligned (dense rows of C floats, read and written as float4), partial 8-byte");
   (void)ws;
   (void)ws_bytes;
   launch_gn_apply(x, out, batch, pixels, channels, groups, partial, nchunk, gamma, beta, scale_shift,
@@ -474,26 +395,17 @@ extern "C" int lfdm_groupnorm_apply_cl_f32(const float* x, float* out, int batch
 extern "C" int lfdm_layernorm_cl_f32(const float* x, float* out, int64_t rows, int channels,
                                      const float* gamma, float eps, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!x || !out || !gamma || rows <= 0 || channels <= 0 || channels % 4 != 0 || channels > 1024) {
-    lfdm_set_error("layernorm: unsupported shape (C%4==0, C<=1024)");
-    return LFDM_EINVAL;
-  }
-  int64_t nb = (rows + 3) / 4;
-  if (nb > 16384) nb = 16384;
-  const bool al16 = ((((uintptr_t)x) | ((uintptr_t)out) | ((uintptr_t)gamma)) & 15) == 0;
-  if (!al16) {      // (every kernel below reads x / gamma and writes out as float4: there is no scalar form)
-    lfdm_set_error("layernorm: x, out and gamma must be 16-byte aligned");
-    return LFDM_EINVAL;
-  }
+  if (!x || !out || !gamma || rows <= 0 || channels <= 0 || channels % 4 != 0 || channels > 1024)
+    return lfdm_fail(LFDM_EINVAL, "%s", "layernorm: unsupported shape (C%4==0, C<=1024)");
+  if (!lfdm_aligned16(x, out, gamma))      // (every kernel below reads x / gamma and writes out as float4: there is no scalar form)
+    return lfdm_fail(LFDM_EINVAL, "layernorm: x, out and gamma must be 16-byte aligned");
   if ((channels == 64 || channels == 128) && rows >= 4096) {
-    int64_t nbs = (rows + 4 * (256 / channels) * 2 * 4 - 1) / (4 * (256 / channels) * 2 * 4);      // ~4 trips per wavefront
-    if (nbs > 8192) nbs = 8192;
-    if (nbs < 1) nbs = 1;
-    if (channels == 64) LFDM_LAUNCH((layernorm_small_kernel<16>), dim3((unsigned)nbs), dim3(256), 0, stream, x, out, rows, gamma, eps);
-    else LFDM_LAUNCH((layernorm_small_kernel<32>), dim3((unsigned)nbs), dim3(256), 0, stream, x, out, rows, gamma, eps);
+    const unsigned nbs = lfdm_blocks(rows, 4 * (256 / channels) * 2 * 4, 8192);      // ~4 trips per wavefront
+    if (channels == 64) LFDM_LAUNCH((layernorm_small_kernel<16>), dim3(nbs), dim3(256), 0, stream, x, out, rows, gamma, eps);
+    else LFDM_LAUNCH((layernorm_small_kernel<32>), dim3(nbs), dim3(256), 0, stream, x, out, rows, gamma, eps);
     return lfdm_check_launch("layernorm");
   }
-  LFDM_LAUNCH(layernorm_kernel, dim3((unsigned)nb), dim3(256), 0, stream, x, out, rows, channels,
+  LFDM_LAUNCH(layernorm_kernel, dim3(lfdm_blocks(rows, 4, 16384)), dim3(256), 0, stream, x, out, rows, channels,
               gamma, eps);
   return lfdm_check_launch("layernorm");
 }
@@ -502,15 +414,11 @@ extern "C" int lfdm_affine_act_cl_f32(const float* x, float* out, int64_t rows, 
                                       int ldx, int ldo, const float* a, const float* b, int act,
                                       lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!x || !out || !a || !b || rows <= 0 || channels % 4 != 0 || ldx % 4 != 0 || ldo % 4 != 0) {
-    lfdm_set_error("affine_act: unsupported shape");
-    return LFDM_EINVAL;
-  }
-  if (((((uintptr_t)x) | ((uintptr_t)out) | ((uintptr_t)a) | ((uintptr_t)b)) & 15) != 0) {
-    lfdm_set_error("affine_act: x, out, a and b must be 16-byte aligned (float4 accesses)");
-    return LFDM_EINVAL;
-  }
-  LFDM_LAUNCH(affine_act_kernel, dim3(grid_for(rows * (channels / 4))), dim3(256), 0, stream, x, out,
+  if (!x || !out || !a || !b || rows <= 0 || channels % 4 != 0 || ldx % 4 != 0 || ldo % 4 != 0)
+    return lfdm_fail(LFDM_EINVAL, "affine_act: unsupported shape");
+  if (!lfdm_aligned16(x, out, a, b))
+    return lfdm_fail(LFDM_EINVAL, "affine_act: x, out, a and b must be 16-byte aligned (float4 accesses)");
+  LFDM_LAUNCH(affine_act_kernel, dim3(lfdm_blocks(rows * (channels / 4), 256, 8192)), dim3(256), 0, stream, x, out,
               rows, channels, ldx, ldo, a, b, act);
   return lfdm_check_launch("affine_act");
 }
@@ -518,16 +426,12 @@ extern "C" int lfdm_affine_act_cl_f32(const float* x, float* out, int64_t rows, 
 extern "C" int lfdm_avgpool2_cl_f32(const float* x, float* out, int n_img, int h, int w,
                                     int channels, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!x || !out || n_img <= 0 || (h & 1) || (w & 1) || channels % 4 != 0) {
-    lfdm_set_error("avgpool2: unsupported shape");
-    return LFDM_EINVAL;
-  }
-  if (((((uintptr_t)x) | ((uintptr_t)out)) & 15) != 0) {
-    lfdm_set_error("avgpool2: x and out must be 16-byte aligned (float4 accesses)");
-    return LFDM_EINVAL;
-  }
+  if (!x || !out || n_img <= 0 || (h & 1) || (w & 1) || channels % 4 != 0)
+    return lfdm_fail(LFDM_EINVAL, "avgpool2: unsupported shape");
+  if (!lfdm_aligned16(x, out))
+    return lfdm_fail(LFDM_EINVAL, "avgpool2: x and out must be 16-byte aligned (float4 accesses)");
   const int64_t total = (int64_t)n_img * (h / 2) * (w / 2) * (channels / 4);
-  LFDM_LAUNCH(avgpool2_kernel, dim3(grid_for(total)), dim3(256), 0, stream, x, out, n_img, h, w,
+  LFDM_LAUNCH(avgpool2_kernel, dim3(lfdm_blocks(total, 256, 8192)), dim3(256), 0, stream, x, out, n_img, h, w,
               channels);
   return lfdm_check_launch("avgpool2");
 }
@@ -535,10 +439,8 @@ extern "C" int lfdm_avgpool2_cl_f32(const float* x, float* out, int n_img, int h
 extern "C" int lfdm_planar_to_cl_f32(const float* x, float* out, int n_img, int channels, int hw,
                                      int ldo, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!x || !out || n_img <= 0 || channels <= 0 || hw <= 0 || ldo < channels) {
-    lfdm_set_error("planar_to_cl: bad arguments");
-    return LFDM_EINVAL;
-  }
+  if (!x || !out || n_img <= 0 || channels <= 0 || hw <= 0 || ldo < channels)
+    return lfdm_fail(LFDM_EINVAL, "planar_to_cl: bad arguments");
   LFDM_LAUNCH(planar_to_cl_kernel, dim3((hw + 31) / 32, (channels + 31) / 32, n_img), dim3(256), 0,
               stream, x, out, channels, hw, ldo);
   return lfdm_check_launch("planar_to_cl");
@@ -547,10 +449,8 @@ extern "C" int lfdm_planar_to_cl_f32(const float* x, float* out, int n_img, int 
 extern "C" int lfdm_cl_to_planar_f32(const float* x, float* out, int n_img, int channels, int hw,
                                      int ldx, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!x || !out || n_img <= 0 || channels <= 0 || hw <= 0 || ldx < channels) {
-    lfdm_set_error("cl_to_planar: bad arguments");
-    return LFDM_EINVAL;
-  }
+  if (!x || !out || n_img <= 0 || channels <= 0 || hw <= 0 || ldx < channels)
+    return lfdm_fail(LFDM_EINVAL, "cl_to_planar: bad arguments");
   LFDM_LAUNCH(cl_to_planar_kernel, dim3((hw + 31) / 32, (channels + 31) / 32, n_img), dim3(256), 0,
               stream, x, out, channels, hw, ldx);
   return lfdm_check_launch("cl_to_planar");

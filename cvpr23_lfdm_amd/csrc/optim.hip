@@ -58,12 +58,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 constexpr int kOptBlock = 256;
 constexpr int64_t kOptMaxBlocks = 4096;      // adam_kernel's launch geometry
 
-inline int64_t opt_blocks(int64_t n) {
-  int64_t nb = ((n >> 2) + kOptBlock - 1) / kOptBlock;
-  if (nb < 1) nb = 1;
-  if (nb > kOptMaxBlocks) nb = kOptMaxBlocks;
-  return nb;
-}
+inline int64_t opt_blocks(int64_t n) { return lfdm_blocks(n >> 2, kOptBlock, kOptMaxBlocks); }
 
 // Four accumulators per thread, one per component of the 16-byte load; thread t of workgroup b adds the float4s t + 256 b + k * 256 * grid
 // in order of k, so each accumulator is a chain of L = ceil((n / 4) / (256 * grid)) fused multiply-adds (+ 1 in workgroup 0's first lanes
@@ -199,11 +194,9 @@ extern "C" size_t lfdm_grad_sumsq_ws_bytes(int64_t n) { return n > 0 ? (size_t)o
 
 extern "C" int lfdm_grad_sumsq_f32(const float* grad, int64_t n, float* partials, size_t partials_bytes, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!grad || !partials || n <= 0 || ((uintptr_t)grad & 15) || ((uintptr_t)partials & 3) ||
-      partials_bytes < lfdm_grad_sumsq_ws_bytes(n)) {
-    lfdm_set_error("grad_sumsq: bad arguments (16-byte aligned gradient, n > 0, partials of lfdm_grad_sumsq_ws_bytes(n))");
-    return LFDM_EINVAL;
-  }
+  if (!grad || !partials || n <= 0 || !lfdm_aligned16(grad) || !lfdm_aligned<4>(partials) ||
+      partials_bytes < lfdm_grad_sumsq_ws_bytes(n))
+    return lfdm_fail(LFDM_EINVAL, "grad_sumsq: bad arguments (16-byte aligned gradient, n > 0, partials of lfdm_grad_sumsq_ws_bytes(n))");
   LFDM_LAUNCH(sumsq_kernel, dim3((unsigned)opt_blocks(n)), dim3(kOptBlock), 0, stream, grad, n, partials);
   return lfdm_check_launch("grad_sumsq");
 }
@@ -212,15 +205,11 @@ extern "C" int lfdm_optim_plan_f32(const float* partials, int n_partials, void* 
                                    float max_grad_norm, int skip_nonfinite, float beta1, float beta2, double ema_decay,
                                    int64_t ema_start_step, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!plan || ((uintptr_t)plan & 15) || plan_bytes < LFDM_OPTIM_PLAN_BYTES || n_partials < 0 || n_partials > kOptMaxBlocks ||
-      (n_partials > 0 && !partials) || ema_decay > 1.0 || ema_start_step < 0) {
-    lfdm_set_error("optim_plan: bad arguments (16-byte aligned plan of LFDM_OPTIM_PLAN_BYTES, 0 <= n_partials <= 4096, ema_decay <= 1)");
-    return LFDM_EINVAL;
-  }
-  if (n_partials == 0 && (max_grad_norm >= 0.f || skip_nonfinite)) {
-    lfdm_set_error("optim_plan: clipping and the non-finite guard need the partials of lfdm_grad_sumsq_f32");
-    return LFDM_EINVAL;
-  }
+  if (!plan || !lfdm_aligned16(plan) || plan_bytes < LFDM_OPTIM_PLAN_BYTES || n_partials < 0 || n_partials > kOptMaxBlocks ||
+      (n_partials > 0 && !partials) || ema_decay > 1.0 || ema_start_step < 0)
+    return lfdm_fail(LFDM_EINVAL, "optim_plan: bad arguments (16-byte aligned plan of LFDM_OPTIM_PLAN_BYTES, 0 <= n_partials <= 4096, ema_decay <= 1)");
+  if (n_partials == 0 && (max_grad_norm >= 0.f || skip_nonfinite))
+    return lfdm_fail(LFDM_EINVAL, "optim_plan: clipping and the non-finite guard need the partials of lfdm_grad_sumsq_f32");
   LFDM_LAUNCH(plan_kernel, dim3(1), dim3(kOptBlock), 0, stream, partials, n_partials, (OptimPlan*)plan, grad_scale, max_grad_norm,
               skip_nonfinite, beta1, beta2, ema_decay, ema_start_step);
   return lfdm_check_launch("optim_plan");
@@ -230,11 +219,9 @@ extern "C" int lfdm_adam_guarded_step_f32(float* param, const float* grad, float
                                           float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                                           const void* plan, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!param || !grad || !exp_avg || !exp_avg_sq || !plan || n <= 0 || (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg |
-      (uintptr_t)exp_avg_sq | (uintptr_t)ema | (uintptr_t)plan) & 15)) {
-    lfdm_set_error("adam_guarded: bad arguments (16-byte aligned flat buffers and plan, n > 0)");
-    return LFDM_EINVAL;
-  }
+  if (!param || !grad || !exp_avg || !exp_avg_sq || !plan || n <= 0 ||
+      !lfdm_aligned16(param, grad, exp_avg, exp_avg_sq, ema, plan))
+    return lfdm_fail(LFDM_EINVAL, "adam_guarded: bad arguments (16-byte aligned flat buffers and plan, n > 0)");
   const dim3 grid((unsigned)opt_blocks(n));
   const OptimPlan* pl = (const OptimPlan*)plan;
   if (ema)
@@ -250,18 +237,13 @@ extern "C" int lfdm_adam_step_f32(float* param, const float* grad, float* exp_av
                                   float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                                   float grad_scale, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!param || !grad || !exp_avg || !exp_avg_sq || n <= 0 || step < 1 || (((uintptr_t)param | (uintptr_t)grad |
-      (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15)) {
-    lfdm_set_error("adam: bad arguments (16-byte aligned flat buffers, step >= 1)");
-    return LFDM_EINVAL;
-  }
+  if (!param || !grad || !exp_avg || !exp_avg_sq || n <= 0 || step < 1 ||
+      !lfdm_aligned16(param, grad, exp_avg, exp_avg_sq))
+    return lfdm_fail(LFDM_EINVAL, "adam: bad arguments (16-byte aligned flat buffers, step >= 1)");
   // bias corrections in double on the host, like torch.optim.Adam's scalar path
   const double b1 = 1.0 - pow((double)beta1, (double)step);
   const double b2 = sqrt(1.0 - pow((double)beta2, (double)step));
-  int64_t nb = ((n >> 2) + 255) / 256;
-  if (nb < 1) nb = 1;
-  if (nb > 4096) nb = 4096;
-  LFDM_LAUNCH(adam_kernel, dim3((unsigned)nb), dim3(256), 0, stream, param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2,
+  LFDM_LAUNCH(adam_kernel, dim3(lfdm_blocks(n >> 2, 256, 4096)), dim3(256), 0, stream, param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2,
               eps, weight_decay, (float)b1, (float)b2, grad_scale);
   return lfdm_check_launch("adam");
 }

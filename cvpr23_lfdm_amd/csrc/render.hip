@@ -273,11 +273,9 @@ extern "C" int lfdm_flow_color_u8(const float* grid, int64_t batch_stride, const
                                   int s, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!grid || !ident || !out || batch < 1 || frames < 1 || s < 4 || (s & 3) || s > 4096 ||
-      batch_stride < (int64_t)2 * frames * s * s || (int64_t)batch * frames > 0x7fffffff || ((uintptr_t)out & 15)) {
-    lfdm_set_error("flow_color: bad arguments (non-null grid / ident / out, out 16-byte aligned, batch, frames >= 1, s a multiple of 4, "
+      batch_stride < (int64_t)2 * frames * s * s || (int64_t)batch * frames > 0x7fffffff || !lfdm_aligned16(out))
+    return lfdm_fail(LFDM_EINVAL, "flow_color: bad arguments (non-null grid / ident / out, out 16-byte aligned, batch, frames >= 1, s a multiple of 4, "
                    "batch_stride >= 2 * frames * s * s)");
-    return LFDM_EINVAL;
-  }
   LFDM_LAUNCH(flow_color_kernel, dim3((unsigned)(batch * frames)), dim3(kRenderBlock), 0, stream, grid, batch_stride, ident, out, frames,
               s);
   return lfdm_check_launch("flow_color");
@@ -287,17 +285,12 @@ extern "C" int lfdm_render_strip_u8(const float* source, const float* out_vid, c
                                     const float* conf, const double* mean_over_255, const int* panels, int n_panels, int indexed,
                                     unsigned char* out, int batch, int frames, int S, int s, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!panels || n_panels < 1 || n_panels > kMaxPanels) {
-    lfdm_set_error("render_strip: the panel list is empty (1 .. 8 panels of LFDM_PANEL_*)");
-    return LFDM_EINVAL;
-  }
-  if (!out || !mean_over_255 || batch < 1 || frames < 1 || s < 4 || (s & 3) || ((uintptr_t)out & 15)) {
-    lfdm_set_error("render_strip: bad arguments (non-null out (16-byte aligned) and mean, batch, frames >= 1, s a multiple of 4)");
-    return LFDM_EINVAL;
-  }
+  if (!panels || n_panels < 1 || n_panels > kMaxPanels)
+    return lfdm_fail(LFDM_EINVAL, "render_strip: the panel list is empty (1 .. 8 panels of LFDM_PANEL_*)");
+  if (!out || !mean_over_255 || batch < 1 || frames < 1 || s < 4 || (s & 3) || !lfdm_aligned16(out))
+    return lfdm_fail(LFDM_EINVAL, "render_strip: bad arguments (non-null out (16-byte aligned) and mean, batch, frames >= 1, s a multiple of 4)");
   if (S != 4 * s || S > 8192) {
-    lfdm_set_error("render_strip: S must be 4 * s (the LFAE's factor between frame and latent; at most 8192)");
-    return LFDM_EINVAL;
+    return lfdm_fail(LFDM_EINVAL, "render_strip: S must be 4 * s (the LFAE's factor between frame and latent; at most 8192)");
   }
   StripArgs a;
   for (int i = 0; i < kMaxPanels; ++i) a.panels[i] = 0;
@@ -306,17 +299,13 @@ extern "C" int lfdm_render_strip_u8(const float* source, const float* out_vid, c
     const void* need = k == LFDM_PANEL_SOURCE ? (const void*)source : k == LFDM_PANEL_OUT ? (const void*)out_vid
                        : k == LFDM_PANEL_WARPED ? (const void*)warped_vid : k == LFDM_PANEL_FLOW ? (const void*)flow_color
                        : k == LFDM_PANEL_CONF ? (const void*)conf : nullptr;
-    if (k < LFDM_PANEL_SOURCE || k > LFDM_PANEL_CONF || !need || (k <= LFDM_PANEL_WARPED && ((uintptr_t)need & 15))) {
-      lfdm_set_error("render_strip: a panel is not one of LFDM_PANEL_*, or its operand is null (image operands 16-byte aligned)");
-      return LFDM_EINVAL;
-    }
+    if (k < LFDM_PANEL_SOURCE || k > LFDM_PANEL_CONF || !need || (k <= LFDM_PANEL_WARPED && !lfdm_aligned16(need)))
+      return lfdm_fail(LFDM_EINVAL, "render_strip: a panel is not one of LFDM_PANEL_*, or its operand is null (image operands 16-byte aligned)");
     a.panels[i] = k;
   }
   const int64_t rows = (int64_t)batch * frames * S;
-  if (rows > 0x7fffffff) {
-    lfdm_set_error("render_strip: batch * frames * S exceeds 2^31 - 1");
-    return LFDM_EINVAL;
-  }
+  if (rows > 0x7fffffff)
+    return lfdm_fail(LFDM_EINVAL, "render_strip: batch * frames * S exceeds 2^31 - 1");
   a.source = source;
   a.out_vid = out_vid;
   a.warped_vid = warped_vid;
@@ -330,10 +319,8 @@ extern "C" int lfdm_render_strip_u8(const float* source, const float* out_vid, c
   a.s = s;
   a.n_groups = rows * n_panels * S / kGroup;
   const int64_t blocks = (a.n_groups + kRenderBlock - 1) / kRenderBlock;
-  if (blocks > 0x7fffffff) {
-    lfdm_set_error("render_strip: the strip has more than 2^41 pixels");
-    return LFDM_EINVAL;
-  }
+  if (blocks > 0x7fffffff)
+    return lfdm_fail(LFDM_EINVAL, "render_strip: the strip has more than 2^41 pixels");
   if (indexed)
     LFDM_LAUNCH(strip_kernel<1>, dim3((unsigned)blocks), dim3(kRenderBlock), 0, stream, a);
   else

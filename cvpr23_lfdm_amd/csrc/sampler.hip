@@ -601,16 +601,10 @@ __global__ __launch_bounds__(256) void philox_fill_kernel(uint32_t* __restrict__
 template <bool BITS>
 int run_philox_fill(const char* what, void* out, const uint64_t* seeds, int batch, int64_t n, int64_t row_stride, unsigned stream_id,
                     unsigned step, unsigned window, hipStream_t stream) {
-  char msg[160];
-  if (!out || !seeds || batch <= 0 || n <= 0 || n >= (1 << 24) || row_stride < n || stream_id > 2u) {
-    snprintf(msg, sizeof msg, "%s: bad arguments (0 < n < 2^24, row_stride >= n, stream_id 0 .. 2)", what);
-    lfdm_set_error(msg);
-    return LFDM_EINVAL;
-  }
+  if (!out || !seeds || batch <= 0 || n <= 0 || n >= (1 << 24) || row_stride < n || stream_id > 2u)
+    return lfdm_fail(LFDM_EINVAL, "%s: bad arguments (0 < n < 2^24, row_stride >= n, stream_id 0 .. 2)", what);
   const int64_t quads = (n + 3) / 4;
-  int64_t nb = (quads + 255) / 256;
-  if (nb > 1024) nb = 1024;
-  LFDM_LAUNCH((philox_fill_kernel<BITS>), dim3((unsigned)nb, batch), dim3(256), 0, stream, reinterpret_cast<uint32_t*>(out), seeds, (uint32_t)n,
+  LFDM_LAUNCH((philox_fill_kernel<BITS>), dim3(lfdm_blocks(quads, 256, 1024), batch), dim3(256), 0, stream, reinterpret_cast<uint32_t*>(out), seeds, (uint32_t)n,
               row_stride, (uint32_t)stream_id, (uint32_t)step, (uint32_t)window);
   return lfdm_check_launch(what);
 }
@@ -626,11 +620,30 @@ Ranks make_ranks(int64_t n, float quantile) {
   return r;
 }
 
-unsigned blocks_for(int64_t n) {
-  int64_t nb = (n + 256 * 8 - 1) / (256 * 8);
-  if (nb < 1) nb = 1;
-  if (nb > 512) nb = 512;
-  return (unsigned)nb;
+unsigned blocks_for(int64_t n) { return lfdm_blocks(n, 256 * 8, 512); }
+
+// The sampler workspace: per-sample histograms | the x0 prediction of every sample | the ticket word (64 bytes).  lfdm_sampler_ws_bytes and
+// every entry point that is handed the workspace cut it here; lfdm_abs_quantile_f32 is handed the histograms alone and takes only them.
+unsigned* carve_hists(lfdm_carver& c, int batch) { return c.take<unsigned>((size_t)batch * HIST_PER_SAMPLE); }
+struct SamplerWs {
+  unsigned* hists;
+  float* x0buf;
+  unsigned* ticket;
+  size_t bytes;
+};
+SamplerWs carve_sampler_ws(void* ws, int batch, int64_t n) {
+  lfdm_carver c(ws);
+  SamplerWs w;
+  w.hists = carve_hists(c, batch);
+  w.x0buf = c.take<float>((size_t)batch * (size_t)n);
+  w.ticket = c.take<unsigned>(16);
+  w.bytes = c.bytes;
+  return w;
+}
+
+void clear_hists(unsigned* hists, int batch, hipStream_t stream) {
+  const int64_t nz = (int64_t)batch * HIST_PER_SAMPLE;
+  LFDM_LAUNCH(zero_u32_kernel, dim3(lfdm_blocks(nz, 256, 64)), dim3(256), 0, stream, hists, nz);
 }
 
 int run_select(const float* v, int batch, int64_t n, Ranks rk, unsigned* hists, hipStream_t stream) {
@@ -645,62 +658,44 @@ int run_select(const float* v, int batch, int64_t n, Ranks rk, unsigned* hists, 
 extern "C" int lfdm_cfg_combine_f32(const float* cond_eps, const float* null_eps, float scale,
                                     float* out, int64_t n, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!cond_eps || !null_eps || !out || n <= 0) {
-    lfdm_set_error("cfg_combine: bad arguments");
-    return LFDM_EINVAL;
-  }
-  int64_t nb = (n + 255) / 256;
-  if (nb > 2048) nb = 2048;
-  LFDM_LAUNCH(cfg_combine_kernel, dim3((unsigned)nb), dim3(256), 0, stream, cond_eps, null_eps, scale,
+  if (!cond_eps || !null_eps || !out || n <= 0)
+    return lfdm_fail(LFDM_EINVAL, "cfg_combine: bad arguments");
+  LFDM_LAUNCH(cfg_combine_kernel, dim3(lfdm_blocks(n, 256, 2048)), dim3(256), 0, stream, cond_eps, null_eps, scale,
               out, n);
   return lfdm_check_launch("cfg_combine");
 }
 
 extern "C" size_t lfdm_sampler_ws_bytes(int batch, int64_t n) {
-  return (size_t)batch * HIST_PER_SAMPLE * sizeof(unsigned) + (size_t)batch * (size_t)n * sizeof(float) + 64;     // + the ticket word
+  return carve_sampler_ws(nullptr, batch, n).bytes;
 }
 
 extern "C" int lfdm_sampler_ws_init(void* ws, size_t ws_bytes, int batch, int64_t n, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!ws || batch <= 0 || n <= 0 || ws_bytes < lfdm_sampler_ws_bytes(batch, n)) {
-    lfdm_set_error("sampler_ws_init: workspace too small");
-    return LFDM_EWORKSPACE;
-  }
-  unsigned* hists = reinterpret_cast<unsigned*>(ws);
-  const int64_t nz = (int64_t)batch * HIST_PER_SAMPLE;
-  LFDM_LAUNCH(zero_u32_kernel, dim3((unsigned)((nz + 255) / 256 > 64 ? 64 : (nz + 255) / 256)), dim3(256), 0, stream, hists, nz);
-  unsigned* ticket = reinterpret_cast<unsigned*>(reinterpret_cast<float*>(hists + (size_t)batch * HIST_PER_SAMPLE) + (size_t)batch * n);
-  LFDM_LAUNCH(zero_u32_kernel, dim3(1), dim3(256), 0, stream, ticket, (int64_t)16);
+  if (!ws || batch <= 0 || n <= 0 || ws_bytes < lfdm_sampler_ws_bytes(batch, n))
+    return lfdm_fail(LFDM_EWORKSPACE, "sampler_ws_init: workspace too small");
+  const SamplerWs w = carve_sampler_ws(ws, batch, n);
+  clear_hists(w.hists, batch, stream);
+  LFDM_LAUNCH(zero_u32_kernel, dim3(1), dim3(256), 0, stream, w.ticket, (int64_t)16);
   return lfdm_check_launch("sampler_ws_init");
 }
 
 extern "C" int lfdm_abs_quantile_f32(const float* x, int batch, int64_t n, float quantile,
                                      float* q_out, void* ws, size_t ws_bytes, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!x || !q_out || batch <= 0 || n <= 0 || n >= (1 << 24) || quantile < 0.f || quantile > 1.f) {
-    lfdm_set_error("abs_quantile: bad arguments (n < 2^24)");
-    return LFDM_EINVAL;
-  }
-  if (!ws || ws_bytes < (size_t)batch * HIST_PER_SAMPLE * sizeof(unsigned)) {
-    lfdm_set_error("abs_quantile: workspace too small");
-    return LFDM_EWORKSPACE;
-  }
-  unsigned* hists = reinterpret_cast<unsigned*>(ws);
-  {
-    const int64_t nz = (int64_t)batch * HIST_PER_SAMPLE;
-    LFDM_LAUNCH(zero_u32_kernel, dim3((unsigned)((nz + 255) / 256 > 64 ? 64 : (nz + 255) / 256)), dim3(256), 0, stream,
-                hists, nz);
-  }
+  if (!x || !q_out || batch <= 0 || n <= 0 || n >= (1 << 24) || quantile < 0.f || quantile > 1.f)
+    return lfdm_fail(LFDM_EINVAL, "abs_quantile: bad arguments (n < 2^24)");
+  lfdm_carver c(ws);
+  unsigned* hists = carve_hists(c, batch);
+  if (!ws || ws_bytes < c.bytes)
+    return lfdm_fail(LFDM_EWORKSPACE, "abs_quantile: workspace too small");
+  clear_hists(hists, batch, stream);
   const Ranks rk = make_ranks(n, quantile);
   LFDM_LAUNCH(quantile_pass0_kernel, dim3(blocks_for(n), batch), dim3(256), 0, stream, x,
               (const float*)nullptr, (float*)nullptr, n, (const float*)nullptr,
               (const int32_t*)nullptr, hists);
   run_select(x, batch, n, rk, hists, stream);
   LFDM_LAUNCH(quantile_out_kernel, dim3(batch), dim3(256), 0, stream, rk, (const unsigned*)hists, q_out);
-  {   // leave the histograms cleared: lfdm_sampler_step_f32 relies on that when it is handed the same workspace
-    const int64_t nz = (int64_t)batch * HIST_PER_SAMPLE;
-    LFDM_LAUNCH(zero_u32_kernel, dim3((unsigned)((nz + 255) / 256 > 64 ? 64 : (nz + 255) / 256)), dim3(256), 0, stream, hists, nz);
-  }
+  clear_hists(hists, batch, stream);      // leave the histograms cleared: lfdm_sampler_step_f32 relies on that when it is handed the same workspace
   return lfdm_check_launch("abs_quantile");
 }
 
@@ -709,18 +704,10 @@ namespace {
 // argument check of the known-frame operands; on success fills kf
 int make_known(const char* what, const float* known, const float* known_noise, const unsigned char* frame_mask, const float* level,
                int64_t n, int frames, int64_t frame_elems, KnownOps<true>* kf) {
-  char msg[160];
-  if (!known || !known_noise || !frame_mask || !level) {
-    snprintf(msg, sizeof msg, "%s: known, known_noise, frame_mask and level must all be given", what);
-    lfdm_set_error(msg);
-    return LFDM_EINVAL;
-  }
-  if (frames <= 0 || frame_elems <= 0 || n <= 0 || n >= (1 << 24) || n % ((int64_t)frames * frame_elems) != 0) {
-    snprintf(msg, sizeof msg, "%s: n = %lld must be a multiple of frames * frame_elems = %d * %lld (n < 2^24)", what, (long long)n, frames,
-             (long long)frame_elems);
-    lfdm_set_error(msg);
-    return LFDM_EINVAL;
-  }
+  if (!known || !known_noise || !frame_mask || !level)
+    return lfdm_fail(LFDM_EINVAL, "%s: known, known_noise, frame_mask and level must all be given", what);
+  if (frames <= 0 || frame_elems <= 0 || n <= 0 || n >= (1 << 24) || n % ((int64_t)frames * frame_elems) != 0)
+    return lfdm_fail(LFDM_EINVAL, "%s: n = %lld must be a multiple of frames * frame_elems = %d * %lld (n < 2^24)", what, (long long)n, frames, (long long)frame_elems);
   kf->known = known;
   kf->known_noise = known_noise;
   kf->mask = frame_mask;
@@ -733,17 +720,10 @@ int make_known(const char* what, const float* known, const float* known_noise, c
 // argument check of the element-mask operands (no frame split: the mask has n bytes per sample); on success fills kf
 int make_known_elem(const char* what, const float* known, const float* known_noise, const unsigned char* elem_mask, const float* level,
                     int64_t n, KnownOps<true, true>* kf) {
-  char msg[160];
-  if (!known || !known_noise || !elem_mask || !level) {
-    snprintf(msg, sizeof msg, "%s: known, known_noise, elem_mask and level must all be given", what);
-    lfdm_set_error(msg);
-    return LFDM_EINVAL;
-  }
-  if (n <= 0 || n >= (1 << 24)) {
-    snprintf(msg, sizeof msg, "%s: n = %lld must lie in (0, 2^24)", what, (long long)n);
-    lfdm_set_error(msg);
-    return LFDM_EINVAL;
-  }
+  if (!known || !known_noise || !elem_mask || !level)
+    return lfdm_fail(LFDM_EINVAL, "%s: known, known_noise, elem_mask and level must all be given", what);
+  if (n <= 0 || n >= (1 << 24))
+    return lfdm_fail(LFDM_EINVAL, "%s: n = %lld must lie in (0, 2^24)", what, (long long)n);
   kf->known = known;
   kf->known_noise = known_noise;
   kf->mask = elem_mask;
@@ -758,35 +738,23 @@ int run_step(const char* what, float* x, const float* eps, float* second, float*
              int32_t* step_dev, float quantile, int advance, void* ws, size_t ws_bytes, KnownOps<KNOWN, ELEM> kf, hipStream_t stream,
              GenOps<GEN> gen = GenOps<GEN>{}) {
   static_assert(!(MS && GEN), "the multistep update draws nothing");
-  char msg[160];
-  if (!x || !eps || (MS && !second) || !coef || !step_dev || batch <= 0 || n <= 0 || n >= (1 << 24)) {
-    snprintf(msg, sizeof msg, "%s: bad arguments (n < 2^24)", what);
-    lfdm_set_error(msg);
-    return LFDM_EINVAL;
-  }
-  if (!ws || ws_bytes < lfdm_sampler_ws_bytes(batch, n)) {
-    snprintf(msg, sizeof msg, "%s: workspace too small", what);
-    lfdm_set_error(msg);
-    return LFDM_EWORKSPACE;
-  }
-  unsigned* hists = reinterpret_cast<unsigned*>(ws);
-  float* x0buf = reinterpret_cast<float*>(hists + (size_t)batch * HIST_PER_SAMPLE);
+  if (!x || !eps || (MS && !second) || !coef || !step_dev || batch <= 0 || n <= 0 || n >= (1 << 24))
+    return lfdm_fail(LFDM_EINVAL, "%s: bad arguments (n < 2^24)", what);
+  const SamplerWs w = carve_sampler_ws(ws, batch, n);
+  if (!ws || ws_bytes < w.bytes)
+    return lfdm_fail(LFDM_EWORKSPACE, "%s: workspace too small", what);
+  unsigned* hists = w.hists;
+  float* x0buf = w.x0buf;
+  unsigned* ticket = w.ticket;
   const bool dynamic = quantile >= 0.f;           // quantile < 0: static clipping to [-1, 1] (GaussianDiffusion's own default)
-  if (dynamic && quantile > 1.f) {
-    snprintf(msg, sizeof msg, "%s: quantile must lie in [0, 1] (or be negative for the static clamp to [-1, 1])", what);
-    lfdm_set_error(msg);
-    return LFDM_EINVAL;
-  }
+  if (dynamic && quantile > 1.f)
+    return lfdm_fail(LFDM_EINVAL, "%s: quantile must lie in [0, 1] (or be negative for the static clamp to [-1, 1])", what);
   Ranks rk = make_ranks(n, dynamic ? quantile : 0.f);
   if (!dynamic) rk.frac = -1.f;
   // the histograms are clear on entry: lfdm_sampler_ws_init, then the last workgroup of every update kernel - for one or two samples
   // (a single workgroup clearing more would lengthen the kernel's tail: larger batches keep the clearing launch)
   const bool fold_clear = batch <= 2;
-  if (!fold_clear) {
-    const int64_t nz = (int64_t)batch * HIST_PER_SAMPLE;
-    LFDM_LAUNCH(zero_u32_kernel, dim3((unsigned)((nz + 255) / 256 > 64 ? 64 : (nz + 255) / 256)), dim3(256), 0, stream, hists, nz);
-  }
-  unsigned* ticket = reinterpret_cast<unsigned*>(x0buf + (size_t)batch * n);
+  if (!fold_clear) clear_hists(hists, batch, stream);
   const dim3 grid(blocks_for(n), batch), block(256);
   LFDM_LAUNCH(quantile_pass0_kernel, grid, block, 0, stream, (const float*)x, eps, x0buf, n, coef,
               (const int32_t*)step_dev, hists);         // (also the x0 = c_x*x - c_eps*eps pass: columns 0-1 of either table)
@@ -844,10 +812,8 @@ extern "C" int lfdm_known_blend_f32(float* x, const float* known, const float* k
                                     float s, int batch, int64_t n, int frames, int64_t frame_elems, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   KnownOps<true> kf;
-  if (!x || batch <= 0) {
-    lfdm_set_error("known_blend: bad arguments");
-    return LFDM_EINVAL;
-  }
+  if (!x || batch <= 0)
+    return lfdm_fail(LFDM_EINVAL, "known_blend: bad arguments");
   if (int rc = make_known("known_blend", known, known_noise, frame_mask, /*level: not an operand*/ known, n, frames, frame_elems, &kf)) return rc;
   LFDM_LAUNCH(known_blend_kernel, dim3(blocks_for(n), batch), dim3(256), 0, stream, x, known, known_noise, frame_mask, a, s, (unsigned)n,
               kf.frames, kf.frame_elems);
@@ -878,10 +844,8 @@ extern "C" int lfdm_known_blend_elem_f32(float* x, const float* known, const flo
                                          float s, int batch, int64_t n, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   KnownOps<true, true> kf;
-  if (!x || batch <= 0) {
-    lfdm_set_error("known_blend_elem: bad arguments");
-    return LFDM_EINVAL;
-  }
+  if (!x || batch <= 0)
+    return lfdm_fail(LFDM_EINVAL, "known_blend_elem: bad arguments");
   if (int rc = make_known_elem("known_blend_elem", known, known_noise, elem_mask, /*level: not an operand*/ known, n, &kf)) return rc;
   LFDM_LAUNCH(known_blend_elem_kernel, dim3(blocks_for(n), batch), dim3(256), 0, stream, x, known, known_noise, elem_mask, a, s, (unsigned)n);
   return lfdm_check_launch("known_blend_elem");
@@ -900,10 +864,7 @@ extern "C" int lfdm_philox_bits_u32(uint32_t* out, const uint64_t* seeds, int ba
 namespace {
 int make_gen(const char* what, const uint64_t* seeds, const uint32_t* window, GenOps<true>* gen) {
   if (!seeds || !window) {
-    char msg[160];
-    snprintf(msg, sizeof msg, "%s: seeds (batch 64-bit words) and window (one 32-bit word) must both be given, on the device", what);
-    lfdm_set_error(msg);
-    return LFDM_EINVAL;
+    return lfdm_fail(LFDM_EINVAL, "%s: seeds (batch 64-bit words) and window (one 32-bit word) must both be given, on the device", what);
   }
   gen->seeds = seeds;
   gen->window = window;

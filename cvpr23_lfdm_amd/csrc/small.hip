@@ -120,16 +120,9 @@ __global__ __launch_bounds__(256) void conv_planar_in_kernel(
 #pragma unroll
     for (int j4 = 0; j4 < 8; ++j4) {
       float4 v = make_float4(acc[4 * j4], acc[4 * j4 + 1], acc[4 * j4 + 2], acc[4 * j4 + 3]);
-      if (bias) {
-        const float4 bb = *reinterpret_cast<const float4*>(bias + cbase + 4 * j4);
-        v.x += bb.x; v.y += bb.y; v.z += bb.z; v.w += bb.w;
-      }
-      if (arow) {
-        const float4 aa = *reinterpret_cast<const float4*>(arow + 4 * j4);
-        v.x += aa.x; v.y += aa.y; v.z += aa.z; v.w += aa.w;
-      }
-      v.x = apply_act(v.x, act); v.y = apply_act(v.y, act); v.z = apply_act(v.z, act); v.w = apply_act(v.w, act);
-      *reinterpret_cast<float4*>(orow + 4 * j4) = v;
+      if (bias) add4(v, *reinterpret_cast<const float4*>(bias + cbase + 4 * j4));
+      if (arow) add4(v, *reinterpret_cast<const float4*>(arow + 4 * j4));
+      *reinterpret_cast<float4*>(orow + 4 * j4) = map4([act](float e) { return apply_act(e, act); }, v);
     }
   } else {
 #pragma unroll
@@ -177,9 +170,9 @@ __global__ __launch_bounds__(256) void heads_kernel(const float* __restrict__ y_
     const float4 w0 = reinterpret_cast<const float4*>(wl)[i];
     const float4 w1 = reinterpret_cast<const float4*>(wl + channels)[i];
     const float4 w2 = reinterpret_cast<const float4*>(wl + 2 * channels)[i];
-    s0 += (a.x * w0.x + a.y * w0.y) + (a.z * w0.z + a.w * w0.w);
-    s1 += (a.x * w1.x + a.y * w1.y) + (a.z * w1.z + a.w * w1.w);
-    s2 += (o.x * w2.x + o.y * w2.y) + (o.z * w2.z + o.w * w2.w);
+    s0 += dot4(a, w0);
+    s1 += dot4(a, w1);
+    s2 += dot4(o, w2);
   }
   if (EXTRA) {
     const int ce = c0 + c1;
@@ -191,9 +184,9 @@ __global__ __launch_bounds__(256) void heads_kernel(const float* __restrict__ y_
         const float4 w0 = *reinterpret_cast<const float4*>(we + base + 4 * i);
         const float4 w1 = *reinterpret_cast<const float4*>(we + ce + base + 4 * i);
         const float4 w2 = *reinterpret_cast<const float4*>(we + 2 * ce + base + 4 * i);
-        s0 += (a.x * w0.x + a.y * w0.y) + (a.z * w0.z + a.w * w0.w);
-        s1 += (a.x * w1.x + a.y * w1.y) + (a.z * w1.z + a.w * w1.w);
-        s2 += (a.x * w2.x + a.y * w2.y) + (a.z * w2.z + a.w * w2.w);
+        s0 += dot4(a, w0);
+        s1 += dot4(a, w1);
+        s2 += dot4(a, w2);
       }
     }
   }
@@ -249,9 +242,10 @@ __global__ __launch_bounds__(256) void heads_gn_kernel(const float* __restrict__
   const int cg = c2 / groups;
   for (int c = tid; c < c2; c += 256) {
     const int g = c / cg;
-    const float a = s_rstd[g] * (c == tid ? pre_gamma : gamma[c]);
-    s_a[c] = a;
-    s_b[c] = (c == tid ? pre_beta : beta[c]) - s_mean[g] * a;
+    float ga, gb;
+    gn_affine(s_mean[g], s_rstd[g], c == tid ? pre_gamma : gamma[c], c == tid ? pre_beta : beta[c], ga, gb);
+    s_a[c] = ga;
+    s_b[c] = gb;
   }
   __syncthreads();
   const int r8 = tid >> 3, seg = tid & 7;
@@ -304,6 +298,9 @@ __global__ __launch_bounds__(256) void heads_gn_kernel(const float* __restrict__
       float s0 = 0.f, s1 = 0.f, s2 = 0.f;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
+        // (written out on purpose: through map4 / fma4 / dot4 of norm_core.h this loop takes 170 instead of 168 VGPRs and the kernel drops from
+        // three waves per SIMD to two, and the generic path below comes out with other result bits - hipcc contracts the products of a
+        // float4 passed by value differently; DESIGN.md section 3, "Normalisation")
         const float t0 = silu_fast_(fmaf(v[j].x, ra[j].x, rb[j].x)), t1 = silu_fast_(fmaf(v[j].y, ra[j].y, rb[j].y));
         const float t2 = silu_fast_(fmaf(v[j].z, ra[j].z, rb[j].z)), t3 = silu_fast_(fmaf(v[j].w, ra[j].w, rb[j].w));
         s0 += (t0 * w0[j].x + t1 * w0[j].y) + (t2 * w0[j].z + t3 * w0[j].w);
@@ -312,9 +309,9 @@ __global__ __launch_bounds__(256) void heads_gn_kernel(const float* __restrict__
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        s0 += (xv[j].x * e0[j].x + xv[j].y * e0[j].y) + (xv[j].z * e0[j].z + xv[j].w * e0[j].w);
-        s1 += (xv[j].x * e1[j].x + xv[j].y * e1[j].y) + (xv[j].z * e1[j].z + xv[j].w * e1[j].w);
-        s2 += (xv[j].x * e2[j].x + xv[j].y * e2[j].y) + (xv[j].z * e2[j].z + xv[j].w * e2[j].w);
+        s0 += dot4(xv[j], e0[j]);
+        s1 += dot4(xv[j], e1[j]);
+        s2 += dot4(xv[j], e2[j]);
       }
       finish(pix, s0, s1, s2);
     }
@@ -402,13 +399,9 @@ extern "C" int lfdm_step_cond_f32(const float* step_table, const float* batch_ba
                                   const int32_t* step_dev, float* out, int batch, int n,
                                   lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!step_table || !batch_base || !step_dev || !out || batch <= 0 || n <= 0) {
-    lfdm_set_error("step_cond: bad arguments");
-    return LFDM_EINVAL;
-  }
-  int64_t nb = ((int64_t)batch * n + 255) / 256;
-  if (nb > 1024) nb = 1024;
-  LFDM_LAUNCH(step_cond_kernel, dim3((unsigned)nb), dim3(256), 0, stream, step_table, batch_base,
+  if (!step_table || !batch_base || !step_dev || !out || batch <= 0 || n <= 0)
+    return lfdm_fail(LFDM_EINVAL, "step_cond: bad arguments");
+  LFDM_LAUNCH(step_cond_kernel, dim3(lfdm_blocks((int64_t)batch * n, 256, 1024)), dim3(256), 0, stream, step_table, batch_base,
               step_dev, out, batch, n);
   return lfdm_check_launch("step_cond");
 }
@@ -417,10 +410,8 @@ extern "C" int lfdm_linear_small_f32(const float* x, const float* w, const float
                                      int batch, int k, int n, int ldx, int ldw, int ldy,
                                      int act_in, int act_out, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!x || !w || !y || batch <= 0 || k <= 0 || n <= 0 || ldx < k || ldw < k || ldy < n) {
-    lfdm_set_error("linear_small: bad arguments");
-    return LFDM_EINVAL;
-  }
+  if (!x || !w || !y || batch <= 0 || k <= 0 || n <= 0 || ldx < k || ldw < k || ldy < n)
+    return lfdm_fail(LFDM_EINVAL, "linear_small: bad arguments");
   LFDM_LAUNCH(linear_small_kernel, dim3((n + 3) / 4, batch), dim3(256), 0, stream, x, w, bias, y, k,
               n, ldx, ldw, ldy, act_in, act_out);
   return lfdm_check_launch("linear_small");
@@ -429,10 +420,8 @@ extern "C" int lfdm_linear_small_f32(const float* x, const float* w, const float
 extern "C" int lfdm_sinusoidal_f32(const int32_t* t_dev, int t_stride, const float* freqs,
                                    float* out, int batch, int dim, int ldo, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!t_dev || !freqs || !out || batch <= 0 || dim < 4 || (dim & 1) || ldo < dim) {
-    lfdm_set_error("sinusoidal: bad arguments");
-    return LFDM_EINVAL;
-  }
+  if (!t_dev || !freqs || !out || batch <= 0 || dim < 4 || (dim & 1) || ldo < dim)
+    return lfdm_fail(LFDM_EINVAL, "sinusoidal: bad arguments");
   LFDM_LAUNCH(sinusoidal_kernel, dim3(batch), dim3(64), 0, stream, t_dev, t_stride, freqs, out, dim, ldo);
   return lfdm_check_launch("sinusoidal");
 }
@@ -575,15 +564,13 @@ extern "C" int lfdm_conv_planar_in_cl_f32(const float* x, int batch, int cin, in
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !wgt || !out || batch <= 0 || cin <= 0 || cin > cin_total || frames <= 0 || h <= 0 ||
       w <= 0 || kh <= 0 || kw <= 0 || !(kh & 1) || !(kw & 1) || cout <= 0 || cout % 64 != 0 ||
-      kh * kw * cin > CPI_MAX_K || ldo < cout) {
-    lfdm_set_error("conv_planar_in: unsupported shape (odd kernel, kh*kw*cin<=196, cout%64==0)");
-    return LFDM_EINVAL;
-  }
+      kh * kw * cin > CPI_MAX_K || ldo < cout)
+    return lfdm_fail(LFDM_EINVAL, "%s", "conv_planar_in: unsupported shape (odd kernel, kh*kw*cin<=196, cout%64==0)");
   const int64_t total = (int64_t)batch * frames * h * w;
   static const bool mfma_off = [] { const char* e = lfdm_knob("LFDM_STEM_MFMA"); return e && e[0] == '0'; }();
   const int tiles_x = (w + CPM_COLS - 1) / CPM_COLS, tiles_y = (h + CPM_ROWS - 1) / CPM_ROWS;
   const int64_t nblk = (int64_t)batch * frames * tiles_x * tiles_y;
-  if (!mfma_off && cin <= 8 && kh <= 7 && kw <= 7 && (cout & 3) == 0 && ((((uintptr_t)wgt) & 15) == 0) && nblk < (1ll << 31)) {
+  if (!mfma_off && cin <= 8 && kh <= 7 && kw <= 7 && (cout & 3) == 0 && lfdm_aligned16(wgt) && nblk < (1ll << 31)) {
     LFDM_LAUNCH(conv_planar_in_mfma_kernel, dim3((unsigned)nblk, cout / 64), dim3(256), 0, stream, x, batch, cin, cin_total, frames, h,
                 w, wgt, kh, kw, cout, bias, add_term, out, ldo, act, tiles_x, tiles_y);
     return lfdm_check_launch("conv_planar_in_mfma");
@@ -601,10 +588,8 @@ extern "C" int lfdm_heads_cl_to_planar_f32(const float* y_flow, const float* y_o
   hipStream_t stream = (hipStream_t)stream_;
   if (!y_flow || !y_occ || !w_flow || !b_flow || !w_occ || !b_occ || !out || channels <= 0 ||
       channels > 256 || channels % 4 != 0 || ld < channels || ld % 4 != 0 || batch <= 0 || frames <= 0 || hw <= 0 ||
-      (((uintptr_t)y_flow | (uintptr_t)y_occ) & 15) != 0) {
-    lfdm_set_error("heads: bad arguments (C % 4 == 0, C <= 256, ld % 4 == 0, 16-byte aligned rows)");
-    return LFDM_EINVAL;
-  }
+      !lfdm_aligned16(y_flow, y_occ))
+    return lfdm_fail(LFDM_EINVAL, "%s", "heads: bad arguments (C % 4 == 0, C <= 256, ld % 4 == 0, 16-byte aligned rows)");
   const int64_t total = (int64_t)batch * frames * hw;
   LFDM_LAUNCH(heads_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, y_flow,
               y_occ, channels, ld, w_flow, b_flow, w_occ, b_occ, out, batch, frames, hw, (const float*)nullptr, 0, 0, (const float*)nullptr, 0, 0,
@@ -620,10 +605,8 @@ extern "C" int lfdm_heads_res_cl_to_planar_f32(const float* y_flow, const float*
   if (!y_flow || !y_occ || !w_flow || !b_flow || !w_occ || !b_occ || !out || !x0 || !w_extra || channels <= 0 || channels > 256 ||
       channels % 4 != 0 || ld < channels || ld % 4 != 0 || batch <= 0 || frames <= 0 || hw <= 0 || c0 <= 0 || c0 % 4 != 0 || ld0 < c0 ||
       ld0 % 4 != 0 || c1 < 0 || c1 % 4 != 0 || (c1 > 0 && (!x1 || ld1 < c1 || ld1 % 4 != 0)) || c0 + c1 > 512 ||
-      (((uintptr_t)y_flow | (uintptr_t)y_occ | (uintptr_t)x0 | (uintptr_t)x1) & 15) != 0) {
-    lfdm_set_error("heads_res: bad arguments (C % 4 == 0, c0 + c1 <= 512, 16-byte aligned rows)");
-    return LFDM_EINVAL;
-  }
+      !lfdm_aligned16(y_flow, y_occ, x0, x1))
+    return lfdm_fail(LFDM_EINVAL, "%s", "heads_res: bad arguments (C % 4 == 0, c0 + c1 <= 512, 16-byte aligned rows)");
   const int64_t total = (int64_t)batch * frames * hw;
   LFDM_LAUNCH(heads_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, y_flow, y_occ, channels, ld, w_flow, b_flow,
               w_occ, b_occ, out, batch, frames, hw, x0, ld0, c0, x1 ? x1 : x0, ld1, c1, w_extra);
@@ -639,10 +622,8 @@ extern "C" int lfdm_heads_gn_res_cl_to_planar_f32(const float* y, int ld, int ch
   if (!y || !partial || !gamma || !beta || !w_flow || !b_flow || !w_occ || !b_occ || !out || !x0 || !w_extra || channels <= 0 || c2 > 512 ||
       channels % 4 != 0 || ld < c2 || ld % 4 != 0 || batch <= 0 || batch > 65535 || frames <= 0 || hw <= 0 || nchunk <= 0 || groups <= 0 || groups > 64 ||
       c2 % groups != 0 || c0 <= 0 || c0 % 4 != 0 || ld0 < c0 || ld0 % 4 != 0 || c1 < 0 || c1 % 4 != 0 ||
-      (c1 > 0 && (!x1 || ld1 < c1 || ld1 % 4 != 0)) || c0 + c1 > 512 || (((uintptr_t)y | (uintptr_t)x0 | (uintptr_t)x1) & 15) != 0) {
-    lfdm_set_error("heads_gn_res: bad arguments (2C <= 512 and % groups == 0, C % 4 == 0, c0 + c1 <= 512, 16-byte aligned rows, <= 65535 samples)");
-    return LFDM_EINVAL;
-  }
+      (c1 > 0 && (!x1 || ld1 < c1 || ld1 % 4 != 0)) || c0 + c1 > 512 || !lfdm_aligned16(y, x0, x1))
+    return lfdm_fail(LFDM_EINVAL, "%s", "heads_gn_res: bad arguments (2C <= 512 and % groups == 0, C % 4 == 0, c0 + c1 <= 512, 16-byte aligned rows, <= 65535 samples)");
   const int64_t pixels = (int64_t)frames * hw;
   const int rows_per_wg = pixels >= 32768 ? 128 : 32;                         // four passes per workgroup once that still leaves >= 256 workgroups per sample
   LFDM_LAUNCH(heads_gn_kernel, dim3((unsigned)((pixels + rows_per_wg - 1) / rows_per_wg), (unsigned)batch), dim3(256), 0, stream, y, ld, channels, partial,
@@ -654,10 +635,8 @@ extern "C" int lfdm_pack_conv_weight_f32(const float* w, int n_o, int n_i, int t
                                          int mode, float* out, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!w || !out || n_o <= 0 || n_i <= 0 || taps <= 0 || mode < 0 || mode > 2 || (mode == 2 && taps != 16) ||
-      stride_o <= 0 || stride_i <= 0) {
-    lfdm_set_error("pack_conv_weight: bad arguments (mode 0 conv, 1 data gradient, 2 ConvTranspose k4 s2 p1 parity packs)");
-    return LFDM_EINVAL;
-  }
+      stride_o <= 0 || stride_i <= 0)
+    return lfdm_fail(LFDM_EINVAL, "pack_conv_weight: bad arguments (mode 0 conv, 1 data gradient, 2 ConvTranspose k4 s2 p1 parity packs)");
   const int K = mode == 0 ? taps * n_i : mode == 1 ? taps * n_o : 4 * n_o;
   const int N = mode == 0 ? n_o : n_i;
   const int np = (N + 31) / 32 * 32;

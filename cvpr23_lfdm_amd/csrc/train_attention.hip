@@ -569,8 +569,7 @@ extern "C" int lfdm_attention_bwd_cl_f32(const float* qkv, const float* dout, fl
   const int L = mode == 0 ? frames : hw;
   if (!qkv || !dout || !dqkv || batch <= 0 || frames <= 0 || hw <= 0 || (mode != 0 && mode != 1) || L > 64 ||
       ((rot_cos == nullptr) != (rot_sin == nullptr)) || ((bias == nullptr) != (dbias == nullptr))) {
-    lfdm_set_error("attention_bwd: unsupported arguments (sequence length must be <= 64; dbias iff bias)");
-    return LFDM_EINVAL;
+    return lfdm_fail(LFDM_EINVAL, "attention_bwd: unsupported arguments (sequence length must be <= 64; dbias iff bias)");
   }
   const bool rows40 = L > 32 && L <= 40 && attn_bwd_rows40_enabled();      // the 40-frame videos: 40-row tiles (10 instead of 12 k-steps in the token-contraction GEMMs)
   const int wpb = L > 48 ? 2 : 4;
@@ -578,10 +577,8 @@ extern "C" int lfdm_attention_bwd_cl_f32(const float* qkv, const float* dout, fl
   const int nb = attn_bwd_blocks(nseq * HEADS, wpb);
   float* part = nullptr;
   if (dbias) {
-    if (!ws || ws_bytes < lfdm_attention_bwd_ws_bytes(batch, frames, hw, mode)) {
-      lfdm_set_error("attention_bwd: workspace too small");
-      return LFDM_EWORKSPACE;
-    }
+    if (!ws || ws_bytes < lfdm_attention_bwd_ws_bytes(batch, frames, hw, mode))
+      return lfdm_fail(LFDM_EWORKSPACE, "attention_bwd: workspace too small");
     part = (float*)ws;
   }
   const dim3 grid(nb), block(64 * wpb);
@@ -606,14 +603,10 @@ extern "C" size_t lfdm_linear_attention_bwd_ws_bytes(int n_frames) {
 extern "C" int lfdm_linear_attention_bwd_cl_f32(const float* qkv, const float* dout, float* dqkv, int n_frames,
                                                 int hw, void* ws, size_t ws_bytes, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!qkv || !dout || !dqkv || n_frames <= 0 || hw <= 0) {
-    lfdm_set_error("linear_attention_bwd: bad arguments");
-    return LFDM_EINVAL;
-  }
-  if (!ws || ws_bytes < lfdm_linear_attention_bwd_ws_bytes(n_frames)) {
-    lfdm_set_error("linear_attention_bwd: workspace too small");
-    return LFDM_EWORKSPACE;
-  }
+  if (!qkv || !dout || !dqkv || n_frames <= 0 || hw <= 0)
+    return lfdm_fail(LFDM_EINVAL, "linear_attention_bwd: bad arguments");
+  if (!ws || ws_bytes < lfdm_linear_attention_bwd_ws_bytes(n_frames))
+    return lfdm_fail(LFDM_EWORKSPACE, "linear_attention_bwd: workspace too small");
   LFDM_LAUNCH(linattn_bwd_context_kernel, dim3(n_frames * HEADS), dim3(256), 0, stream, qkv, dout, hw, (float*)ws);
   LFDM_LAUNCH(linattn_bwd_apply_kernel, dim3((hw + LA_TOK - 1) / LA_TOK, n_frames), dim3(256), 0, stream, qkv, dout,
               (const float*)ws, hw, dqkv);

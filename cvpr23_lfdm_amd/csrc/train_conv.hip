@@ -541,49 +541,38 @@ extern "C" size_t lfdm_conv2d_wgrad_ws_bytes(const lfdm_wgrad_params* p) {
 
 extern "C" int lfdm_sum_leading_f32(const float* in, float* out, int64_t n, int s, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!in || !out || n <= 0 || s <= 0) { lfdm_set_error("sum_leading: bad arguments"); return LFDM_EINVAL; }
-  if (n % 4 == 0 && ((((uintptr_t)in) | ((uintptr_t)out)) & 15) == 0) {
-    int64_t nb = (n / 4 + 255) / 256;
-    if (nb > 65536) nb = 65536;
-    LFDM_LAUNCH(sum_leading4_kernel, dim3((unsigned)nb), dim3(256), 0, stream, reinterpret_cast<const float4*>(in),
+  if (!in || !out || n <= 0 || s <= 0) return lfdm_fail(LFDM_EINVAL, "sum_leading: bad arguments");
+  if (n % 4 == 0 && lfdm_aligned16(in, out)) {
+    LFDM_LAUNCH(sum_leading4_kernel, dim3(lfdm_blocks(n / 4, 256, 65536)), dim3(256), 0, stream, reinterpret_cast<const float4*>(in),
                 reinterpret_cast<float4*>(out), n / 4, s);
     return lfdm_check_launch("sum_leading");
   }
-  int64_t nb = (n + 255) / 256;
-  if (nb > 65536) nb = 65536;
-  LFDM_LAUNCH(sum_leading_kernel, dim3((unsigned)nb), dim3(256), 0, stream, in, out, n, s);
+  LFDM_LAUNCH(sum_leading_kernel, dim3(lfdm_blocks(n, 256, 65536)), dim3(256), 0, stream, in, out, n, s);
   return lfdm_check_launch("sum_leading");
 }
 
 extern "C" int lfdm_conv2d_wgrad_cl_f32(const lfdm_wgrad_params* pp, void* ws, size_t ws_bytes, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!pp) { lfdm_set_error("wgrad: null params"); return LFDM_EINVAL; }
+  if (!pp) return lfdm_fail(LFDM_EINVAL, "wgrad: null params");
   const lfdm_wgrad_params p = *pp;
   const int64_t M = (int64_t)p.n_img * p.hq * p.wq;
   const int64_t in_rows = (int64_t)p.n_img * p.hi * p.wi;
   if (!p.x || !p.dy || !p.dw || p.cin <= 0 || p.cout <= 0 || p.n_img <= 0 || p.hi <= 0 || p.wi <= 0 || p.hq <= 0 ||
       p.wq <= 0 || p.kh <= 0 || p.kw <= 0 || p.stride <= 0 || p.ldx < p.cin || p.lddy < p.cout || M >= (1ll << 31) ||
-      in_rows >= (1ll << 31)) {
-    lfdm_set_error("wgrad: invalid geometry");
-    return LFDM_EINVAL;
-  }
-  if (p.cin % 4 || p.cout % 4 || p.ldx % 4 || p.lddy % 4 || (((uintptr_t)p.x) & 15) || (((uintptr_t)p.dy) & 15) ||
-      in_rows * p.ldx * 4 >= (1ll << 32) - 64 || M * p.lddy * 4 >= (1ll << 32) - 64) {
-    lfdm_set_error("wgrad: channels and row strides must be multiples of 4, buffers 16-byte aligned and < 4 GiB");
-    return LFDM_EINVAL;
-  }
+      in_rows >= (1ll << 31))
+    return lfdm_fail(LFDM_EINVAL, "wgrad: invalid geometry");
+  if (p.cin % 4 || p.cout % 4 || p.ldx % 4 || p.lddy % 4 || !lfdm_aligned16(p.x) || !lfdm_aligned16(p.dy) ||
+      in_rows * p.ldx * 4 >= (1ll << 32) - 64 || M * p.lddy * 4 >= (1ll << 32) - 64)
+    return lfdm_fail(LFDM_EINVAL, "wgrad: channels and row strides must be multiples of 4, buffers 16-byte aligned and < 4 GiB");
   const int taps = p.kh * p.kw;
-  if (p.dw_layout != 0 && p.dw_layout != 1) { lfdm_set_error("wgrad: dw_layout must be 0 (tap-major) or 1 (reference layout)"); return LFDM_EINVAL; }
+  if (p.dw_layout != 0 && p.dw_layout != 1) return lfdm_fail(LFDM_EINVAL, "wgrad: dw_layout must be 0 (tap-major) or 1 (reference layout)");
   if (p.dw_layout == 1 && (taps > 16 || p.dw_cin_total < p.dw_ci_off + p.cin || p.dw_ci_off < 0)) {
-    lfdm_set_error("wgrad: the reference layout covers filters of up to 16 taps; dw_ci_off + cin must fit dw_cin_total");
-    return LFDM_EINVAL;
+    return lfdm_fail(LFDM_EINVAL, "wgrad: the reference layout covers filters of up to 16 taps; dw_ci_off + cin must fit dw_cin_total");
   }
   const WgradPlan pl = wgrad_plan(p);
   const size_t need = lfdm_conv2d_wgrad_ws_bytes(&p);
-  if (need > 0 && (!ws || ws_bytes < need || (((uintptr_t)ws) & 15))) {
-    lfdm_set_error("wgrad: workspace too small or not 16-byte aligned (lfdm_conv2d_wgrad_ws_bytes)");
-    return LFDM_EWORKSPACE;
-  }
+  if (need > 0 && (!ws || ws_bytes < need || !lfdm_aligned16(ws)))
+    return lfdm_fail(LFDM_EWORKSPACE, "wgrad: workspace too small or not 16-byte aligned (lfdm_conv2d_wgrad_ws_bytes)");
   const bool slabs = wgrad_needs_slabs(p, pl);
   const int64_t n_dw = (int64_t)taps * p.cin * p.cout;
   float* dst = slabs ? (float*)ws : p.dw;
@@ -634,12 +623,12 @@ extern "C" size_t lfdm_colsum_ws_bytes(int64_t rows, int c) {
 extern "C" int lfdm_colsum_f32(const float* x, int64_t rows, int c, int ld, float* out, void* ws, size_t ws_bytes,
                                lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!x || !out || rows <= 0 || c <= 0 || ld < c) { lfdm_set_error("colsum: bad arguments"); return LFDM_EINVAL; }
+  if (!x || !out || rows <= 0 || c <= 0 || ld < c) return lfdm_fail(LFDM_EINVAL, "colsum: bad arguments");
   int64_t nblk = (rows + 1023) / 1024;
   if (nblk > 512) nblk = 512;
-  if (!ws || ws_bytes < (size_t)nblk * c * sizeof(float)) { lfdm_set_error("colsum: workspace too small"); return LFDM_EWORKSPACE; }
+  if (!ws || ws_bytes < (size_t)nblk * c * sizeof(float)) return lfdm_fail(LFDM_EWORKSPACE, "colsum: workspace too small");
   const int rows_per_blk = (int)((rows + nblk - 1) / nblk);
-  if (c % 4 == 0 && ld % 4 == 0 && (((uintptr_t)x) & 15) == 0)
+  if (c % 4 == 0 && ld % 4 == 0 && lfdm_aligned16(x))
     LFDM_LAUNCH(colsum4_kernel, dim3((unsigned)((c + 63) / 64), (unsigned)nblk), dim3(256), 0, stream, x, rows, c, ld, (float*)ws,
                 rows_per_blk);
   else
@@ -654,14 +643,11 @@ extern "C" int lfdm_upsample2_pad_cl_f32(const float* x, float* out, int n_img, 
                                          int reflect, int backward, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !out || n_img <= 0 || h <= 0 || w <= 0 || channels <= 0 || channels % 4 != 0 || pad < 0 || pad > 1 ||
-      (reflect && pad == 1 && (h < 1 || w < 1))) {
-    lfdm_set_error("upsample2_pad: bad arguments (C % 4 == 0, pad in {0,1})");
-    return LFDM_EINVAL;
-  }
+      (reflect && pad == 1 && (h < 1 || w < 1)))
+    return lfdm_fail(LFDM_EINVAL, "%s", "upsample2_pad: bad arguments (C % 4 == 0, pad in {0,1})");
   const int64_t rows = backward ? (int64_t)n_img * h * w : (int64_t)n_img * (2 * h + 2 * pad) * (2 * w + 2 * pad);
-  int64_t nb = (rows * (channels / 4) + 255) / 256;
-  if (nb > 65536) nb = 65536;
-  if (backward) LFDM_LAUNCH(upsample_pad_bwd_kernel, dim3((unsigned)nb), dim3(256), 0, stream, x, out, n_img, h, w, channels, pad, reflect);
-  else LFDM_LAUNCH(upsample_pad_fwd_kernel, dim3((unsigned)nb), dim3(256), 0, stream, x, out, n_img, h, w, channels, pad, reflect);
+  const dim3 grid(lfdm_blocks(rows * (channels / 4), 256, 65536));
+  if (backward) LFDM_LAUNCH(upsample_pad_bwd_kernel, grid, dim3(256), 0, stream, x, out, n_img, h, w, channels, pad, reflect);
+  else LFDM_LAUNCH(upsample_pad_fwd_kernel, grid, dim3(256), 0, stream, x, out, n_img, h, w, channels, pad, reflect);
   return lfdm_check_launch("upsample2_pad");
 }

@@ -979,8 +979,6 @@ __global__ __launch_bounds__(256) void im2col_cl_kernel(const float* __restrict_
   }
 }
 
-bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 }  // namespace
 
 // =====================================================================================================================================
@@ -997,18 +995,15 @@ namespace {
 int bn_fill(BnArgs& a, const float* x, int64_t rows, int channels, int segments, int ldx, const float* gamma, const float* beta, void* ws,
             size_t ws_bytes, unsigned* tickets, const char* who) {
   if (!x || !gamma || !beta || !ws || !tickets || rows <= 0 || channels <= 0 || channels % 4 != 0 || channels > 64 * 32 || ldx % 4 != 0 ||
-      segments <= 0 || segments > 64 || ldx < channels || !aligned16(x) || !aligned16(gamma) || !aligned16(beta) ||
+      segments <= 0 || segments > 64 || ldx < channels || !lfdm_aligned16(x) || !lfdm_aligned16(gamma) || !lfdm_aligned16(beta) ||
       ws_bytes < lfdm_batchnorm_train_ws_bytes(rows, channels, segments)) {
     (void)who;
-    lfdm_set_error("batchnorm_train: rows > 0 (per segment), 1..64 segments, channels % 4 == 0 (<= 2048), 16-byte aligned x / gamma / beta, "
+    return lfdm_fail(LFDM_EINVAL, "%s", "batchnorm_train: rows > 0 (per segment), 1..64 segments, channels % 4 == 0 (<= 2048), 16-byte aligned x / gamma / beta, "
                    "workspace of lfdm_batchnorm_train_ws_bytes and a zeroed ticket array of LFDM_BN_TICKETS words");
-    return LFDM_EINVAL;
   }
   const BnGeom g = bn_geom(rows, channels);
-  if ((int64_t)segments * g.ctiles * g.ngroups > LFDM_BN_TICKETS) {
-    lfdm_set_error("batchnorm_train: segments x channel tiles x chunk groups exceeds LFDM_BN_TICKETS");
-    return LFDM_EINVAL;
-  }
+  if ((int64_t)segments * g.ctiles * g.ngroups > LFDM_BN_TICKETS)
+    return lfdm_fail(LFDM_EINVAL, "batchnorm_train: segments x channel tiles x chunk groups exceeds LFDM_BN_TICKETS");
   a.segments = segments;
   a.seg_p1 = (int64_t)g.ctiles * g.nchunk * 2 * g.tw;
   a.seg_p2 = (int64_t)g.ctiles * g.ngroups * 2 * g.tw;
@@ -1031,10 +1026,9 @@ extern "C" int lfdm_batchnorm_train_fwd_cl_f32(const float* x, float* y, int64_t
   BnArgs a = {};
   const int rc = bn_fill(a, x, rows, channels, segments, ldx, gamma, beta, ws, ws_bytes, tickets, "batchnorm_train_fwd");
   if (rc) return rc;
-  if (!y || !stat || ldy % 4 != 0 || ldy < channels || !aligned16(y) || ((running_mean == nullptr) != (running_var == nullptr))) {
-    lfdm_set_error("batchnorm_train_fwd: y (16-byte aligned, ldy % 4 == 0) and stat (segments * 2 * channels floats) are required; running_mean and "
+  if (!y || !stat || ldy % 4 != 0 || ldy < channels || !lfdm_aligned16(y) || ((running_mean == nullptr) != (running_var == nullptr))) {
+    return lfdm_fail(LFDM_EINVAL, "%s", "batchnorm_train_fwd: y (16-byte aligned, ldy % 4 == 0) and stat (segments * 2 * channels floats) are required; running_mean and "
                    "running_var come together");
-    return LFDM_EINVAL;
   }
   a.out = y; a.ldo = ldy; a.stat = stat; a.running_mean = running_mean; a.running_var = running_var; a.momentum = momentum; a.eps = eps;
   a.relu = relu;
@@ -1052,15 +1046,11 @@ extern "C" int lfdm_batchnorm_train_bwd_cl_f32(const float* x, const float* dy, 
   BnArgs a = {};
   const int rc = bn_fill(a, x, rows, channels, segments, ldx, gamma, beta, ws, ws_bytes, tickets, "batchnorm_train_bwd");
   if (rc) return rc;
-  if (!dy || !dx || !stat || lddy % 4 != 0 || lddx % 4 != 0 || lddy < channels || lddx < channels || !aligned16(dy) || !aligned16(dx) ||
-      !aligned16(stat)) {
-    lfdm_set_error("batchnorm_train_bwd: dy, dx (16-byte aligned, leading dimensions % 4 == 0) and the forward's stat are required");
-    return LFDM_EINVAL;
-  }
-  if (dx_add && (ldadd % 4 != 0 || ldadd < channels || !aligned16(dx_add))) {
-    lfdm_set_error("batchnorm_train_bwd: dx_add must be 16-byte aligned with a leading dimension % 4 == 0");
-    return LFDM_EINVAL;
-  }
+  if (!dy || !dx || !stat || lddy % 4 != 0 || lddx % 4 != 0 || lddy < channels || lddx < channels || !lfdm_aligned16(dy) || !lfdm_aligned16(dx) ||
+      !lfdm_aligned16(stat))
+    return lfdm_fail(LFDM_EINVAL, "%s", "batchnorm_train_bwd: dy, dx (16-byte aligned, leading dimensions % 4 == 0) and the forward's stat are required");
+  if (dx_add && (ldadd % 4 != 0 || ldadd < channels || !lfdm_aligned16(dx_add)))
+    return lfdm_fail(LFDM_EINVAL, "%s", "batchnorm_train_bwd: dx_add must be 16-byte aligned with a leading dimension % 4 == 0");
   a.add = dx_add; a.ldadd = ldadd;
   a.dy = dy; a.lddy = lddy; a.out = dx; a.ldo = lddx; a.stat = const_cast<float*>(stat); a.relu = relu; a.dgamma = dgamma; a.dbeta = dbeta;
   const BnGeom g = bn_geom(rows, channels);
@@ -1075,11 +1065,10 @@ int blur_fill(BlurArgs& a, const lfdm_blur_params* p, bool bwd) {
   if (!p || !p->wgt || p->n_img <= 0 || p->n_img > 65535 || p->channels <= 0 || p->c_store < p->channels || p->c_store > 65535 || p->h <= 0 ||
       p->w <= 0 || p->k <= 0 || p->k * p->k > BLUR_MAX_TAPS || p->stride <= 0 || p->pad_lo < 0 || p->pad_hi < 0 ||
       (bwd ? (!p->dy || !p->dx) : (!p->x || !p->out))) {
-    lfdm_set_error("blur_down: bad arguments (n_img, c_store <= 65535; k*k <= 1024)");
-    return LFDM_EINVAL;
+    return lfdm_fail(LFDM_EINVAL, "blur_down: bad arguments (n_img, c_store <= 65535; k*k <= 1024)");
   }
   const int hf = p->h + p->pad_lo + p->pad_hi - p->k + 1, wf = p->w + p->pad_lo + p->pad_hi - p->k + 1;
-  if (hf <= 0 || wf <= 0) { lfdm_set_error("blur_down: kernel larger than the padded input"); return LFDM_EINVAL; }
+  if (hf <= 0 || wf <= 0) return lfdm_fail(LFDM_EINVAL, "blur_down: kernel larger than the padded input");
   a.x = p->x; a.wgt = p->wgt; a.out = p->out; a.dy = p->dy; a.dx = p->dx;
   a.xs_n = p->xs_n; a.xs_c = p->xs_c; a.xs_h = p->xs_h; a.xs_w = p->xs_w;
   a.os_n = p->os_n; a.os_c = p->os_c; a.os_h = p->os_h; a.os_w = p->os_w;
@@ -1110,38 +1099,29 @@ extern "C" int lfdm_blur_down_bwd_f32(const lfdm_blur_params* p, lfdm_stream_t s
 
 extern "C" int lfdm_absmax_f32(const float* x, int64_t rows, int channels, int64_t ld, unsigned* out_bits, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!x || !out_bits || rows <= 0 || channels <= 0 || ld < channels) { lfdm_set_error("absmax: bad arguments"); return LFDM_EINVAL; }
-  int64_t blocks = (rows * channels + 256 * 16 - 1) / (256 * 16);
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  LFDM_LAUNCH(absmax_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, x, rows, channels, ld, out_bits);
+  if (!x || !out_bits || rows <= 0 || channels <= 0 || ld < channels) return lfdm_fail(LFDM_EINVAL, "absmax: bad arguments");
+  LFDM_LAUNCH(absmax_kernel, dim3(lfdm_blocks(rows * channels, 256 * 16, 2048)), dim3(256), 0, stream, x, rows, channels, ld, out_bits);
   return lfdm_check_launch("absmax");
 }
 
 extern "C" int lfdm_warp_bwd_f32(const lfdm_warp_bwd_params* pp, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!pp) { lfdm_set_error("warp_bwd: null params"); return LFDM_EINVAL; }
+  if (!pp) return lfdm_fail(LFDM_EINVAL, "warp_bwd: null params");
   const lfdm_warp_bwd_params& p = *pp;
   if (!p.src || !p.dout || !p.flow_x || !p.flow_y || !p.dmaps || p.n_img <= 0 || p.n_img > 65535 || p.h <= 0 || p.w <= 0 || p.c <= 0 || p.fh <= 0 ||
-      p.fw <= 0 || p.n_div <= 0) {
-    lfdm_set_error("warp_bwd: src, dout, flow_x, flow_y, dmaps and positive sizes are required (n_img <= 65535)");
-    return LFDM_EINVAL;
-  }
+      p.fw <= 0 || p.n_div <= 0)
+    return lfdm_fail(LFDM_EINVAL, "warp_bwd: src, dout, flow_x, flow_y, dmaps and positive sizes are required (n_img <= 65535)");
   const int hw = p.h * p.w;
   if (p.layout_cl) {
     const int g = p.c / 4;
     if (p.c % 4 != 0 || g > 64 || (g & (g - 1)) != 0 || (256 % g) != 0 || p.n_div != 1 || p.ld_src % 4 != 0 || p.ld_dout % 4 != 0 ||
-        (p.prev && p.ld_prev % 4 != 0) || (p.dprev && p.ld_dprev % 4 != 0) || !aligned16(p.src) || !aligned16(p.dout) ||
-        (p.prev && !aligned16(p.prev)) || (p.dprev && !aligned16(p.dprev)) || (p.dsrc_fix && (!p.amax_bits || (((uintptr_t)p.dsrc_fix) & 7))) ||
-        (int64_t)hw * g > 0x7fffffff) {
-      lfdm_set_error("warp_bwd (channels-last): C / 4 a power of two <= 64, 16-byte aligned rows, n_div == 1, dsrc_fix needs amax_bits");
-      return LFDM_EINVAL;
-    }
-    int64_t blocks = ((int64_t)hw * g + 255) / 256;
-    if (blocks > 65535) blocks = 65535;
-    LFDM_LAUNCH(warp_bwd_cl_kernel, dim3((unsigned)blocks, (unsigned)p.n_img), dim3(256), 0, stream, p);
+        (p.prev && p.ld_prev % 4 != 0) || (p.dprev && p.ld_dprev % 4 != 0) || !lfdm_aligned16(p.src) || !lfdm_aligned16(p.dout) ||
+        (p.prev && !lfdm_aligned16(p.prev)) || (p.dprev && !lfdm_aligned16(p.dprev)) || (p.dsrc_fix && (!p.amax_bits || !lfdm_aligned<8>(p.dsrc_fix))) ||
+        (int64_t)hw * g > 0x7fffffff)
+      return lfdm_fail(LFDM_EINVAL, "warp_bwd (channels-last): C / 4 a power of two <= 64, 16-byte aligned rows, n_div == 1, dsrc_fix needs amax_bits");
+    LFDM_LAUNCH(warp_bwd_cl_kernel, dim3(lfdm_blocks((int64_t)hw * g, 256, 65535), (unsigned)p.n_img), dim3(256), 0, stream, p);
   } else {
-    if (p.dsrc_fix) { lfdm_set_error("warp_bwd (strided): the gradient of the sampled tensor is only produced by the channels-last form"); return LFDM_EINVAL; }
+    if (p.dsrc_fix) return lfdm_fail(LFDM_EINVAL, "warp_bwd (strided): the gradient of the sampled tensor is only produced by the channels-last form");
     LFDM_LAUNCH(warp_bwd_px_kernel, dim3((unsigned)((hw + 255) / 256), (unsigned)p.n_img), dim3(256), 0, stream, p);
   }
   return lfdm_check_launch("warp_bwd");
@@ -1150,23 +1130,16 @@ extern "C" int lfdm_warp_bwd_f32(const lfdm_warp_bwd_params* pp, lfdm_stream_t s
 extern "C" int lfdm_fix_finalize_f32(long long* acc, float* out, int64_t rows, int channels, int64_t ld, unsigned* amax_bits, int64_t count,
                                      unsigned* ticket, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!acc || !out || !amax_bits || !ticket || rows <= 0 || channels <= 0 || ld < channels || count <= 0) {
-    lfdm_set_error("fix_finalize: bad arguments");
-    return LFDM_EINVAL;
-  }
-  int64_t blocks = (rows * channels + 256 * 8 - 1) / (256 * 8);
-  if (blocks > 4096) blocks = 4096;
-  if (blocks < 1) blocks = 1;
-  LFDM_LAUNCH(fix_finalize_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, acc, out, rows, channels, ld, amax_bits, count, ticket);
+  if (!acc || !out || !amax_bits || !ticket || rows <= 0 || channels <= 0 || ld < channels || count <= 0)
+    return lfdm_fail(LFDM_EINVAL, "fix_finalize: bad arguments");
+  LFDM_LAUNCH(fix_finalize_kernel, dim3(lfdm_blocks(rows * channels, 256 * 8, 4096)), dim3(256), 0, stream, acc, out, rows, channels, ld, amax_bits, count, ticket);
   return lfdm_check_launch("fix_finalize");
 }
 
 extern "C" int lfdm_resize_adjoint_f32(const float* dhigh, float* dlow, int planes, int h, int w, int fh, int fw, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!dhigh || !dlow || planes <= 0 || planes > 65535 || h <= 0 || w <= 0 || fh <= 0 || fw <= 0) {
-    lfdm_set_error("resize_adjoint: bad arguments (planes <= 65535)");
-    return LFDM_EINVAL;
-  }
+  if (!dhigh || !dlow || planes <= 0 || planes > 65535 || h <= 0 || w <= 0 || fh <= 0 || fw <= 0)
+    return lfdm_fail(LFDM_EINVAL, "resize_adjoint: bad arguments (planes <= 65535)");
   LFDM_LAUNCH(resize_adjoint_kernel, dim3((unsigned)((fh * fw + 255) / 256), (unsigned)planes), dim3(256), 0, stream, dhigh, dlow, h, w, fh, fw);
   return lfdm_check_launch("resize_adjoint");
 }
@@ -1174,10 +1147,8 @@ extern "C" int lfdm_resize_adjoint_f32(const float* dhigh, float* dlow, int plan
 namespace {
 int gs_fill(GsArgs& a, const lfdm_grid_sample_params* p, bool bwd) {
   if (!p || !p->x || !p->grid || p->n_img <= 0 || p->n_img > 65535 || p->channels <= 0 || p->h <= 0 || p->w <= 0 || p->ho <= 0 || p->wo <= 0 ||
-      p->n_div <= 0 || p->pad_mode < 0 || p->pad_mode > 1 || (bwd ? (!p->dout || !p->dgrid) : !p->out)) {
-    lfdm_set_error("grid_sample: bad arguments (n_img <= 65535, pad_mode 0 zeros / 1 reflection)");
-    return LFDM_EINVAL;
-  }
+      p->n_div <= 0 || p->pad_mode < 0 || p->pad_mode > 1 || (bwd ? (!p->dout || !p->dgrid) : !p->out))
+    return lfdm_fail(LFDM_EINVAL, "grid_sample: bad arguments (n_img <= 65535, pad_mode 0 zeros / 1 reflection)");
   a.x = p->x; a.grid = p->grid; a.out = p->out; a.dout = p->dout; a.dgrid = p->dgrid;
   a.xs_n = p->xs_n; a.xs_c = p->xs_c; a.xs_h = p->xs_h; a.xs_w = p->xs_w;
   a.os_n = p->os_n; a.os_c = p->os_c; a.os_h = p->os_h; a.os_w = p->os_w;
@@ -1200,7 +1171,7 @@ extern "C" int lfdm_grid_sample_bwd_f32(const lfdm_grid_sample_params* p, lfdm_s
   GsArgs a = {};
   const int rc = gs_fill(a, p, true);
   if (rc) return rc;
-  if (p->pad_mode != 0) { lfdm_set_error("grid_sample_bwd: zeros padding only (the reflection warp of model.py:118-122 has no gradient)"); return LFDM_EINVAL; }
+  if (p->pad_mode != 0) return lfdm_fail(LFDM_EINVAL, "grid_sample_bwd: zeros padding only (the reflection warp of model.py:118-122 has no gradient)");
   LFDM_LAUNCH((grid_sample_kernel<true>), dim3((unsigned)((a.ho * a.wo + 255) / 256), (unsigned)p->n_img), dim3(256), 0, stream, a);
   return lfdm_check_launch("grid_sample_bwd");
 }
@@ -1208,7 +1179,7 @@ extern "C" int lfdm_grid_sample_bwd_f32(const lfdm_grid_sample_params* p, lfdm_s
 extern "C" int lfdm_svd2x2_sym_bwd_f32(const float* u, const float* s, const float* gu, const float* gs, float* ga, int64_t n,
                                        lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!u || !s || !ga || n <= 0 || (!gu && !gs)) { lfdm_set_error("svd2x2_sym_bwd: u, s, ga and at least one of gu / gs are required"); return LFDM_EINVAL; }
+  if (!u || !s || !ga || n <= 0 || (!gu && !gs)) return lfdm_fail(LFDM_EINVAL, "svd2x2_sym_bwd: u, s, ga and at least one of gu / gs are required");
   LFDM_LAUNCH(svd2x2_sym_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, u, s, gu, gs, ga, n);
   return lfdm_check_launch("svd2x2_sym_bwd");
 }
@@ -1217,14 +1188,10 @@ extern "C" int lfdm_pool2_cl_f32(const float* x, const float* aux, float* out, i
                                  lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !out || n_img <= 0 || h <= 0 || w <= 0 || (h & 1) || (w & 1) || channels <= 0 || channels % 4 != 0 || mode < 0 || mode > 5 ||
-      (mode == 5 && !aux) || !aligned16(x) || !aligned16(out) || (aux && !aligned16(aux))) {
-    lfdm_set_error("pool2: even fine resolution (h, w), channels % 4 == 0, mode 0..5 (5 needs aux = dy), 16-byte aligned rows");
-    return LFDM_EINVAL;
-  }
+      (mode == 5 && !aux) || !lfdm_aligned16(x) || !lfdm_aligned16(out) || (aux && !lfdm_aligned16(aux)))
+    return lfdm_fail(LFDM_EINVAL, "%s", "pool2: even fine resolution (h, w), channels % 4 == 0, mode 0..5 (5 needs aux = dy), 16-byte aligned rows");
   const int64_t total = (int64_t)n_img * (h / 2) * (w / 2) * (channels / 4);
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > 65535 * 4) blocks = 65535 * 4;
-  const dim3 grid((unsigned)blocks);
+  const dim3 grid(lfdm_blocks(total, 256, 65535 * 4));
   switch (mode) {
     case 0: LFDM_LAUNCH((pool2_kernel<0>), grid, dim3(256), 0, stream, x, aux, out, n_img, h, w, channels); break;
     case 1: LFDM_LAUNCH((pool2_kernel<1>), grid, dim3(256), 0, stream, x, aux, out, n_img, h, w, channels); break;
@@ -1238,13 +1205,9 @@ extern "C" int lfdm_pool2_cl_f32(const float* x, const float* aux, float* out, i
 
 extern "C" int lfdm_relu_bwd_f32(const float* y, const float* dy, float* out, int64_t n, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!y || !dy || !out || n <= 0 || n % 4 != 0 || !aligned16(y) || !aligned16(dy) || !aligned16(out)) {
-    lfdm_set_error("relu_bwd: n % 4 == 0 and 16-byte aligned tensors");
-    return LFDM_EINVAL;
-  }
-  int64_t blocks = (n / 4 + 255) / 256;
-  if (blocks > 65535 * 4) blocks = 65535 * 4;
-  LFDM_LAUNCH(relu_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, reinterpret_cast<const float4*>(y), reinterpret_cast<const float4*>(dy),
+  if (!y || !dy || !out || n <= 0 || n % 4 != 0 || !lfdm_aligned16(y) || !lfdm_aligned16(dy) || !lfdm_aligned16(out))
+    return lfdm_fail(LFDM_EINVAL, "%s", "relu_bwd: n % 4 == 0 and 16-byte aligned tensors");
+  LFDM_LAUNCH(relu_bwd_kernel, dim3(lfdm_blocks(n / 4, 256, 65535 * 4)), dim3(256), 0, stream, reinterpret_cast<const float4*>(y), reinterpret_cast<const float4*>(dy),
               reinterpret_cast<float4*>(out), n / 4);
   return lfdm_check_launch("relu_bwd");
 }
@@ -1252,27 +1215,18 @@ extern "C" int lfdm_relu_bwd_f32(const float* y, const float* dy, float* out, in
 extern "C" int lfdm_l1_mean_fwd_f32(const float* x, const float* y, int64_t n, float weight, float* out, void* ws, size_t ws_bytes,
                                     unsigned* ticket, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!x || !y || !out || !ws || !ticket || n <= 0 || n % 4 != 0 || ws_bytes < L1_BLOCKS * sizeof(unsigned long long) || (((uintptr_t)ws) & 7) || !aligned16(x) || !aligned16(y)) {
-    lfdm_set_error("l1_mean_fwd: n % 4 == 0, 16-byte aligned x / y, an 8 KB workspace (8-byte aligned) and one zeroed ticket word");
-    return LFDM_EINVAL;
-  }
-  int64_t blocks = (n / 4 + 256 * 8 - 1) / (256 * 8);
-  if (blocks > L1_BLOCKS) blocks = L1_BLOCKS;
-  if (blocks < 1) blocks = 1;
-  LFDM_LAUNCH(l1_mean_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, reinterpret_cast<const float4*>(x), reinterpret_cast<const float4*>(y),
+  if (!x || !y || !out || !ws || !ticket || n <= 0 || n % 4 != 0 || ws_bytes < L1_BLOCKS * sizeof(unsigned long long) || !lfdm_aligned<8>(ws) || !lfdm_aligned16(x) || !lfdm_aligned16(y))
+    return lfdm_fail(LFDM_EINVAL, "%s", "l1_mean_fwd: n % 4 == 0, 16-byte aligned x / y, an 8 KB workspace (8-byte aligned) and one zeroed ticket word");
+  LFDM_LAUNCH(l1_mean_fwd_kernel, dim3(lfdm_blocks(n / 4, 256 * 8, L1_BLOCKS)), dim3(256), 0, stream, reinterpret_cast<const float4*>(x), reinterpret_cast<const float4*>(y),
               n / 4, weight / (float)n, reinterpret_cast<float*>(ws), ticket, out);
   return lfdm_check_launch("l1_mean_fwd");
 }
 
 extern "C" int lfdm_l1_mean_bwd_f32(const float* x, const float* y, int64_t n, float weight, const float* gout, float* dx, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!x || !y || !gout || !dx || n <= 0 || n % 4 != 0 || !aligned16(x) || !aligned16(y) || !aligned16(dx)) {
-    lfdm_set_error("l1_mean_bwd: n % 4 == 0 and 16-byte aligned tensors");
-    return LFDM_EINVAL;
-  }
-  int64_t blocks = (n / 4 + 255) / 256;
-  if (blocks > 65535 * 4) blocks = 65535 * 4;
-  LFDM_LAUNCH(l1_mean_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, reinterpret_cast<const float4*>(x), reinterpret_cast<const float4*>(y),
+  if (!x || !y || !gout || !dx || n <= 0 || n % 4 != 0 || !lfdm_aligned16(x) || !lfdm_aligned16(y) || !lfdm_aligned16(dx))
+    return lfdm_fail(LFDM_EINVAL, "%s", "l1_mean_bwd: n % 4 == 0 and 16-byte aligned tensors");
+  LFDM_LAUNCH(l1_mean_bwd_kernel, dim3(lfdm_blocks(n / 4, 256, 65535 * 4)), dim3(256), 0, stream, reinterpret_cast<const float4*>(x), reinterpret_cast<const float4*>(y),
               n / 4, weight / (float)n, gout, reinterpret_cast<float4*>(dx));
   return lfdm_check_launch("l1_mean_bwd");
 }
@@ -1281,13 +1235,9 @@ extern "C" int lfdm_im2col_cl_f32(const float* x, float* out, int n_img, int h, 
   hipStream_t stream = (hipStream_t)stream_;
   const int hq = h + 2 * pad - k + 1, wq = w + 2 * pad - k + 1;
   if (!x || !out || n_img <= 0 || h <= 0 || w <= 0 || channels <= 0 || channels % 4 != 0 || channels > 16 || ldx % 4 != 0 || ldx < channels ||
-      k <= 0 || pad < 0 || hq <= 0 || wq <= 0 || !aligned16(x) || !aligned16(out)) {
-    lfdm_set_error("im2col_cl: channels % 4 == 0 and <= 16, 16-byte aligned rows, stride 1");
-    return LFDM_EINVAL;
-  }
+      k <= 0 || pad < 0 || hq <= 0 || wq <= 0 || !lfdm_aligned16(x) || !lfdm_aligned16(out))
+    return lfdm_fail(LFDM_EINVAL, "%s", "im2col_cl: channels % 4 == 0 and <= 16, 16-byte aligned rows, stride 1");
   const int64_t total = (int64_t)n_img * hq * wq * k * k * (channels / 4);
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > 65535 * 8) blocks = 65535 * 8;
-  LFDM_LAUNCH(im2col_cl_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, x, out, n_img, h, w, channels, ldx, k, pad, hq, wq);
+  LFDM_LAUNCH(im2col_cl_kernel, dim3(lfdm_blocks(total, 256, 65535 * 8)), dim3(256), 0, stream, x, out, n_img, h, w, channels, ldx, k, pad, hq, wq);
   return lfdm_check_launch("im2col_cl");
 }

@@ -200,16 +200,13 @@ __global__ __launch_bounds__(256) void multi_linear_dx_reduce_kernel(const float
 
 int ml_check(const lfdm_multi_linear_params& p, const char* who) {
   if (p.n_blocks <= 0 || p.n_blocks > ML_MAX || p.rows <= 0 || p.rows > ML_ROWS || p.k <= 0 || p.k % 4 != 0 || p.k > ML_KMAX || !p.x ||
-      p.act < 0 || p.act > 2 || (((uintptr_t)p.x) & 15)) {
+      p.act < 0 || p.act > 2 || !lfdm_aligned16(p.x)) {
     (void)who;
-    lfdm_set_error("multi_linear: 1..32 blocks, 1..16 rows, input features a multiple of 4 up to 1024, x 16-byte aligned, act in {0, 1, 2}");
-    return LFDM_EINVAL;
+    return lfdm_fail(LFDM_EINVAL, "multi_linear: 1..32 blocks, 1..16 rows, input features a multiple of 4 up to 1024, x 16-byte aligned, act in {0, 1, 2}");
   }
   for (int j = 0; j < p.n_blocks; ++j)
-    if (!p.w[j] || p.n[j] <= 0 || (((uintptr_t)p.w[j]) & 15)) {
-      lfdm_set_error("multi_linear: every block needs a 16-byte aligned weight and n > 0");
-      return LFDM_EINVAL;
-    }
+    if (!p.w[j] || p.n[j] <= 0 || !lfdm_aligned16(p.w[j]))
+      return lfdm_fail(LFDM_EINVAL, "multi_linear: every block needs a 16-byte aligned weight and n > 0");
   return LFDM_OK;
 }
 
@@ -217,7 +214,7 @@ int ml_check(const lfdm_multi_linear_params& p, const char* who) {
 
 extern "C" int lfdm_multi_linear_f32(const lfdm_multi_linear_params* pp, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!pp) { lfdm_set_error("multi_linear: null params"); return LFDM_EINVAL; }
+  if (!pp) return lfdm_fail(LFDM_EINVAL, "multi_linear: null params");
   const lfdm_multi_linear_params& p = *pp;
   int rc = ml_check(p, "multi_linear");
   if (rc) return rc;
@@ -225,7 +222,7 @@ extern "C" int lfdm_multi_linear_f32(const lfdm_multi_linear_params* pp, lfdm_st
   a.x = p.x; a.nblk = p.n_blocks; a.rows = p.rows; a.k = p.k; a.act = p.act;
   a.col0[0] = 0;
   for (int j = 0; j < p.n_blocks; ++j) {
-    if (!p.y[j]) { lfdm_set_error("multi_linear: a block has no output tensor"); return LFDM_EINVAL; }
+    if (!p.y[j]) return lfdm_fail(LFDM_EINVAL, "multi_linear: a block has no output tensor");
     a.w[j] = p.w[j]; a.bias[j] = p.bias[j]; a.y[j] = p.y[j];
     a.col0[j + 1] = a.col0[j] + p.n[j];
   }
@@ -244,7 +241,7 @@ extern "C" size_t lfdm_multi_linear_bwd_ws_bytes(const lfdm_multi_linear_params*
 
 extern "C" int lfdm_multi_linear_bwd_f32(const lfdm_multi_linear_params* pp, void* ws, size_t ws_bytes, lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!pp) { lfdm_set_error("multi_linear_bwd: null params"); return LFDM_EINVAL; }
+  if (!pp) return lfdm_fail(LFDM_EINVAL, "multi_linear_bwd: null params");
   const lfdm_multi_linear_params& p = *pp;
   int rc = ml_check(p, "multi_linear_bwd");
   if (rc) return rc;
@@ -253,7 +250,7 @@ extern "C" int lfdm_multi_linear_bwd_f32(const lfdm_multi_linear_params* pp, voi
   a.col0[0] = 0;
   bool any_dw = false;
   for (int j = 0; j < p.n_blocks; ++j) {
-    if (p.dw[j] && (((uintptr_t)p.dw[j]) & 15)) { lfdm_set_error("multi_linear_bwd: a dw tensor is not 16-byte aligned"); return LFDM_EINVAL; }
+    if (p.dw[j] && !lfdm_aligned16(p.dw[j])) return lfdm_fail(LFDM_EINVAL, "multi_linear_bwd: a dw tensor is not 16-byte aligned");
     a.w[j] = p.w[j]; a.dy[j] = p.dy[j]; a.dw[j] = p.dw[j]; a.dbias[j] = p.dbias[j];
     a.col0[j + 1] = a.col0[j] + p.n[j];
     any_dw = any_dw || p.dw[j] || p.dbias[j];
@@ -267,10 +264,8 @@ extern "C" int lfdm_multi_linear_bwd_f32(const lfdm_multi_linear_params* pp, voi
   }
   if (p.dx) {
     const size_t need = lfdm_multi_linear_bwd_ws_bytes(pp);
-    if (!ws || ws_bytes < need || (((uintptr_t)ws) & 15) || (((uintptr_t)p.dx) & 15)) {
-      lfdm_set_error("multi_linear_bwd: workspace too small or unaligned (lfdm_multi_linear_bwd_ws_bytes)");
-      return LFDM_EWORKSPACE;
-    }
+    if (!ws || ws_bytes < need || !lfdm_aligned16(ws) || !lfdm_aligned16(p.dx))
+      return lfdm_fail(LFDM_EWORKSPACE, "multi_linear_bwd: workspace too small or unaligned (lfdm_multi_linear_bwd_ws_bytes)");
     const int nparts = (total + 63) / 64;
     if (p.rows <= 8) LFDM_LAUNCH((multi_linear_dx_partial_kernel<8>), dim3((unsigned)nparts), dim3(256), 0, stream, a, (float*)ws);
     else LFDM_LAUNCH((multi_linear_dx_partial_kernel<16>), dim3((unsigned)nparts), dim3(256), 0, stream, a, (float*)ws);

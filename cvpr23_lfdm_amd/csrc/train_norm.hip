@@ -17,7 +17,6 @@
 
 namespace {
 
-constexpr int GNB_MAX_C = 1024;
 constexpr int GNB_MAX_CHUNKS = 256;
 
 __host__ __device__ inline int gnb_num_chunks(int pixels) {
@@ -53,7 +52,9 @@ struct GnArgs {
   int silu;
 };
 
-// per-channel forward coefficients in LDS: z = x*A + B, n = x*Rn + Mn
+// per-channel forward coefficients in LDS: z = x*A + B, n = x*Rn + Mn.  Own association, gamma * (scale + 1) first, where the forward
+// (gn_stats.h: gn_affine, gn_affine_ss) forms rstd * gamma first: the z recomputed here is the forward's z to rounding, not bit for bit.
+// Harmless (dact is smooth), recorded in DESIGN.md section 3, not changed.
 __device__ __forceinline__ void channel_coeffs(const GnArgs& a, int b, const float* s_mean, const float* s_rstd,
                                                float* s_A, float* s_B, float* s_Rn, float* s_Mn) {
   const int cg = a.channels / a.groups;
@@ -75,7 +76,7 @@ __device__ __forceinline__ void channel_coeffs(const GnArgs& a, int b, const flo
 // pass 1: grid (nchunk2, B).  part2[b][chunk][c] = (S1, S2) over the chunk's pixels.
 __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(GnArgs a, float* __restrict__ part2) {
   __shared__ float s_mean[64], s_rstd[64];
-  __shared__ __attribute__((aligned(16))) float s_A[GNB_MAX_C], s_B[GNB_MAX_C], s_Rn[GNB_MAX_C], s_Mn[GNB_MAX_C];
+  __shared__ __attribute__((aligned(16))) float s_A[GN_MAX_C], s_B[GN_MAX_C], s_Rn[GN_MAX_C], s_Mn[GN_MAX_C];
   __shared__ __attribute__((aligned(16))) float red1[1024], red2[1024];
   const int b = blockIdx.y, tid = threadIdx.x;
   group_stats(a.partial, a.nchunk, b, a.groups, a.pixels, a.channels, a.eps, s_mean, s_rstd);
@@ -100,6 +101,7 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(GnArgs a, float* __r
         const int64_t off = ((int64_t)b * a.pixels + p) * a.channels + 4 * c4;
         const float4 xv = *reinterpret_cast<const float4*>(a.x + off);
         const float4 gv = *reinterpret_cast<const float4*>(a.dy + off);
+        // (written out: through map4 / mul4 / add4 hipcc packs these into v_pk_fma_f32 and fuses dz into the s1 sums too - other result bits)
         float dz;
         dz = gv.x * dact(fmaf(xv.x, A.x, B.x), a.silu); s1.x += dz; s2.x += dz * fmaf(xv.x, R.x, Mn.x);
         dz = gv.y * dact(fmaf(xv.y, A.y, B.y), a.silu); s1.y += dz; s2.y += dz * fmaf(xv.y, R.y, Mn.y);
@@ -114,10 +116,8 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(GnArgs a, float* __r
     if (tid < cols) {
       float4 t1 = make_float4(0.f, 0.f, 0.f, 0.f), t2 = t1;
       for (int r = 0; r < rows_per_iter; ++r) {
-        const float4 u = *reinterpret_cast<const float4*>(red1 + 4 * (r * cols + tid));
-        const float4 v = *reinterpret_cast<const float4*>(red2 + 4 * (r * cols + tid));
-        t1.x += u.x; t1.y += u.y; t1.z += u.z; t1.w += u.w;
-        t2.x += v.x; t2.y += v.y; t2.z += v.z; t2.w += v.w;
+        add4(t1, *reinterpret_cast<const float4*>(red1 + 4 * (r * cols + tid)));
+        add4(t2, *reinterpret_cast<const float4*>(red2 + 4 * (r * cols + tid)));
       }
       float* dst = part2 + (((int64_t)b * nchunk2 + chunk) * a.channels + 4 * (cbase + tid)) * 2;
       dst[0] = t1.x; dst[1] = t2.x; dst[2] = t1.y; dst[3] = t2.y;
@@ -177,7 +177,7 @@ __global__ __launch_bounds__(256) void gn_bwd_finalize_kernel(GnArgs a, const fl
 // pass 3: grid (blocks, B).  dx = dz*K1[c] - (C0[g] + x*C1[g])
 __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(GnArgs a, const float* __restrict__ sums, float* __restrict__ dx) {
   __shared__ float s_mean[64], s_rstd[64], s_g1[64], s_g2[64];
-  __shared__ __attribute__((aligned(16))) float s_A[GNB_MAX_C], s_B[GNB_MAX_C], s_K1[GNB_MAX_C], s_C0[GNB_MAX_C], s_C1[GNB_MAX_C];
+  __shared__ __attribute__((aligned(16))) float s_A[GN_MAX_C], s_B[GN_MAX_C], s_K1[GN_MAX_C], s_C0[GN_MAX_C], s_C1[GN_MAX_C];
   const int b = blockIdx.y, tid = threadIdx.x;
   group_stats(a.partial, a.nchunk, b, a.groups, a.pixels, a.channels, a.eps, s_mean, s_rstd);
   __syncthreads();
@@ -216,7 +216,7 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(GnArgs a, const float
     const float4 A = *reinterpret_cast<const float4*>(s_A + c), B = *reinterpret_cast<const float4*>(s_B + c);
     const float4 K1 = *reinterpret_cast<const float4*>(s_K1 + c);
     const float4 C0 = *reinterpret_cast<const float4*>(s_C0 + c), C1 = *reinterpret_cast<const float4*>(s_C1 + c);
-    float4 o;
+    float4 o;      // (written out, as the reduce pass above)
     o.x = gv.x * dact(fmaf(xv.x, A.x, B.x), a.silu) * K1.x - fmaf(xv.x, C1.x, C0.x);
     o.y = gv.y * dact(fmaf(xv.y, A.y, B.y), a.silu) * K1.y - fmaf(xv.y, C1.y, C0.y);
     o.z = gv.z * dact(fmaf(xv.z, A.z, B.z), a.silu) * K1.z - fmaf(xv.z, C1.z, C0.z);
@@ -233,7 +233,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
                                                             float* __restrict__ dx, int64_t rows, int channels,
                                                             const float* __restrict__ gamma, float eps,
                                                             float* __restrict__ part, const float* __restrict__ dx_add) {
-  __shared__ __attribute__((aligned(16))) float red[4][GNB_MAX_C];
+  __shared__ __attribute__((aligned(16))) float red[4][GN_MAX_C];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c4n = channels >> 2;
   float4 dg[4];
@@ -243,7 +243,6 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
     const float4* xr = reinterpret_cast<const float4*>(x + row * channels);
     const float4* gr = reinterpret_cast<const float4*>(dy + row * channels);
     float4 v[4], g[4];
-    float s = 0.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int f = lane + 64 * i;
@@ -252,21 +251,10 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
       if (f < c4n) {
         v[i] = xr[f];
         g[i] = gr[f];
-        s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
       }
     }
-    const float mean = wave_sum(s) / (float)channels;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int f = lane + 64 * i;
-      if (f < c4n) {
-        const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
-        q += (a * a + b * b) + (c * c + d * d);
-      }
-    }
-    const float var = wave_sum(q) / (float)channels;
-    const float inv = 1.0f / sqrtf(var + eps);
+    const ln_stats st = ln_row_stats_wave(v, lane, c4n, channels);
+    const float mean = st.mean, inv = 1.0f / sqrtf(st.var + eps);      // (the forward divides by the root, norm.hip)
     float m1 = 0.f, m2 = 0.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -274,12 +262,11 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
       if (f < c4n) {
         const float4 gm = reinterpret_cast<const float4*>(gamma)[f];
         // v <- nh (normalised), g stays dy; dn = dy*gamma
-        v[i].x = (v[i].x - mean) * inv; v[i].y = (v[i].y - mean) * inv;
-        v[i].z = (v[i].z - mean) * inv; v[i].w = (v[i].w - mean) * inv;
-        dg[i].x += g[i].x * v[i].x; dg[i].y += g[i].y * v[i].y; dg[i].z += g[i].z * v[i].z; dg[i].w += g[i].w * v[i].w;
-        g[i].x *= gm.x; g[i].y *= gm.y; g[i].z *= gm.z; g[i].w *= gm.w;
-        m1 += (g[i].x + g[i].y) + (g[i].z + g[i].w);
-        m2 += (g[i].x * v[i].x + g[i].y * v[i].y) + (g[i].z * v[i].z + g[i].w * v[i].w);
+        v[i] = map4([=](float e) { return (e - mean) * inv; }, v[i]);
+        add4(dg[i], mul4(g[i], v[i]));
+        g[i] = mul4(g[i], gm);
+        m1 += hsum4(g[i]);
+        m2 += dot4(g[i], v[i]);
       }
     }
     m1 = wave_sum(m1) / (float)channels;
@@ -289,15 +276,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
     for (int i = 0; i < 4; ++i) {
       const int f = lane + 64 * i;
       if (f < c4n) {
-        float4 o;
-        o.x = (g[i].x - m1 - v[i].x * m2) * inv;
-        o.y = (g[i].y - m1 - v[i].y * m2) * inv;
-        o.z = (g[i].z - m1 - v[i].z * m2) * inv;
-        o.w = (g[i].w - m1 - v[i].w * m2) * inv;
-        if (dx_add) {
-          const float4 r = reinterpret_cast<const float4*>(dx_add + row * channels)[f];
-          o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
-        }
+        float4 o = map4([=](float dn, float nh) { return (dn - m1 - nh * m2) * inv; }, g[i], v[i]);
+        if (dx_add) add4(o, reinterpret_cast<const float4*>(dx_add + row * channels)[f]);
         orow[f] = o;
       }
     }
@@ -326,11 +306,6 @@ __global__ __launch_bounds__(256) void layernorm_bwd_small_kernel(const float* _
   const int sub = lane / C4N, f = lane % C4N;
   const float4 gm = reinterpret_cast<const float4*>(gamma)[f];
   float4 dg = make_float4(0.f, 0.f, 0.f, 0.f);
-  auto group_sum = [&](float v) {
-#pragma unroll
-    for (int m = 1; m < C4N; m <<= 1) v += __shfl_xor(v, m);
-    return v;
-  };
   const int64_t stride = (int64_t)gridDim.x * 4 * RPW * 2;
   for (int64_t row0 = ((int64_t)blockIdx.x * 4 + wave) * RPW * 2; row0 < rows; row0 += stride) {
     float4 v[2], g[2];
@@ -347,26 +322,16 @@ __global__ __launch_bounds__(256) void layernorm_bwd_small_kernel(const float* _
     }
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-      const float mean = group_sum((v[u].x + v[u].y) + (v[u].z + v[u].w)) / (float)C;
-      const float a = v[u].x - mean, b = v[u].y - mean, c = v[u].z - mean, d = v[u].w - mean;
-      const float var = group_sum((a * a + b * b) + (c * c + d * d)) / (float)C;
-      const float inv = 1.0f / sqrtf(var + eps);
-      float4 nh = make_float4(a * inv, b * inv, c * inv, d * inv);
-      float4 dn = g[u];
-      dg.x += dn.x * nh.x; dg.y += dn.y * nh.y; dg.z += dn.z * nh.z; dg.w += dn.w * nh.w;      // (rows past the end: dy = 0)
-      dn.x *= gm.x; dn.y *= gm.y; dn.z *= gm.z; dn.w *= gm.w;
-      const float m1 = group_sum((dn.x + dn.y) + (dn.z + dn.w)) / (float)C;
-      const float m2 = group_sum((dn.x * nh.x + dn.y * nh.y) + (dn.z * nh.z + dn.w * nh.w)) / (float)C;
+      float4 nh;
+      const float inv = 1.0f / sqrtf(ln_row_stats_group<C4N>(v[u], nh).var + eps);      // (the forward divides by the root, norm.hip)
+      nh = map4([inv](float e) { return e * inv; }, nh);
+      add4(dg, mul4(g[u], nh));      // (rows past the end: dy = 0)
+      const float4 dn = mul4(g[u], gm);
+      const float m1 = group_sum<C4N>(hsum4(dn)) / (float)C;
+      const float m2 = group_sum<C4N>(dot4(dn, nh)) / (float)C;
       if (live[u]) {
-        float4 o;
-        o.x = (dn.x - m1 - nh.x * m2) * inv;
-        o.y = (dn.y - m1 - nh.y * m2) * inv;
-        o.z = (dn.z - m1 - nh.z * m2) * inv;
-        o.w = (dn.w - m1 - nh.w * m2) * inv;
-        if (dx_add) {
-          const float4 r = reinterpret_cast<const float4*>(dx_add + (row0 + u * RPW + sub) * C)[f];
-          o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
-        }
+        float4 o = map4([=](float d, float n) { return (d - m1 - n * m2) * inv; }, dn, nh);
+        if (dx_add) add4(o, reinterpret_cast<const float4*>(dx_add + (row0 + u * RPW + sub) * C)[f]);
         reinterpret_cast<float4*>(dx + (row0 + u * RPW + sub) * C)[f] = o;
       }
     }
@@ -381,20 +346,26 @@ __global__ __launch_bounds__(256) void layernorm_bwd_small_kernel(const float* _
   }
 }
 
-int ln_bwd_blocks(int64_t rows) {
-  int64_t nb = (rows + 3) / 4;
-  if (nb > 512) nb = 512;
-  return (int)nb;
+int ln_bwd_blocks(int64_t rows) { return (int)lfdm_blocks(rows, 4, 512); }
+
+// The GroupNorm backward workspace: part2[b][chunk][c][2] | sums[b][c][2] | dgb[b][2 C]
+struct GnBwdWs {
+  float *part2, *sums, *dgb;
+  size_t bytes;
+};
+GnBwdWs carve_gn_bwd_ws(void* ws, int batch, int pixels, int channels) {
+  lfdm_carver c(ws);
+  GnBwdWs w;
+  w.part2 = c.take<float>((size_t)batch * gnb_num_chunks(pixels) * channels * 2);
+  w.sums = c.take<float>((size_t)batch * channels * 2);
+  w.dgb = c.take<float>((size_t)batch * channels * 2);
+  w.bytes = c.bytes;
+  return w;
 }
 
 }  // namespace
 
-extern "C" size_t lfdm_groupnorm_bwd_ws_bytes(int batch, int pixels, int channels) {
-  const size_t part2 = (size_t)batch * gnb_num_chunks(pixels) * channels * 2;
-  const size_t sums = (size_t)batch * channels * 2;
-  const size_t dgb = (size_t)batch * channels * 2;
-  return (part2 + sums + dgb) * sizeof(float);
-}
+extern "C" size_t lfdm_groupnorm_bwd_ws_bytes(int batch, int pixels, int channels) { return carve_gn_bwd_ws(nullptr, batch, pixels, channels).bytes; }
 
 extern "C" int lfdm_groupnorm_silu_bwd_cl_f32(const float* x, const float* dy, float* dx, int batch, int pixels,
                                               int channels, int groups, const float* gamma, const float* beta,
@@ -404,24 +375,17 @@ extern "C" int lfdm_groupnorm_silu_bwd_cl_f32(const float* x, const float* dy, f
                                               lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !dy || !dx || !gamma || !beta || !partial || !dgamma_dbeta || nchunk <= 0 || batch <= 0 || pixels <= 0 ||
-      channels <= 0 || channels > GNB_MAX_C || groups <= 0 || groups > 64 || channels % groups != 0 || channels % 4 != 0 ||
+      channels <= 0 || channels > GN_MAX_C || groups <= 0 || groups > 64 || channels % groups != 0 || channels % 4 != 0 ||
       (scale_shift && (ss_ld < 2 * channels || !dscale_shift || dss_ld < 2 * channels)) ||
-      !((channels / 4) >= 256 ? (channels / 4) % 256 == 0 : 256 % (channels / 4) == 0)) {
-    lfdm_set_error("groupnorm_bwd: bad arguments (C%4==0, C<=1024, C/4 divides 256)");
-    return LFDM_EINVAL;
-  }
-  if (((((uintptr_t)x) | ((uintptr_t)dy) | ((uintptr_t)dx)) & 15) != 0 || (((uintptr_t)partial) & 7) != 0) {      // (the reduce and dx kernels walk the rows as float4)
-    lfdm_set_error("groupnorm_bwd: x, dy and dx must be 16-byte aligned (dense rows of C floats, read and written as float4), partial 8-byte");
-    return LFDM_EINVAL;
-  }
-  if (!ws || ws_bytes < lfdm_groupnorm_bwd_ws_bytes(batch, pixels, channels)) {
-    lfdm_set_error("groupnorm_bwd: workspace too small");
-    return LFDM_EWORKSPACE;
-  }
+      !((channels / 4) >= 256 ? (channels / 4) % 256 == 0 : 256 % (channels / 4) == 0))
+    return lfdm_fail(LFDM_EINVAL, "%s", "groupnorm_bwd: bad arguments (C%4==0, C<=1024, C/4 divides 256)");
+  if (!lfdm_aligned16(x, dy, dx) || !lfdm_aligned<8>(partial))      // (the reduce and dx kernels walk the rows as float4)
+    return lfdm_fail(LFDM_EINVAL, "groupnorm_bwd: x, dy and dx must be 16-byte aligned (dense rows of C floats, read and written as float4), partial 8-byte");
+  const GnBwdWs w = carve_gn_bwd_ws(ws, batch, pixels, channels);
+  if (!ws || ws_bytes < w.bytes)
+    return lfdm_fail(LFDM_EWORKSPACE, "groupnorm_bwd: workspace too small");
   const int nchunk2 = gnb_num_chunks(pixels);
-  float* part2 = (float*)ws;
-  float* sums = part2 + (size_t)batch * nchunk2 * channels * 2;
-  float* dgb = sums + (size_t)batch * channels * 2;
+  float *part2 = w.part2, *sums = w.sums, *dgb = w.dgb;
   GnArgs a;
   a.x = x; a.dy = dy; a.pixels = pixels; a.channels = channels; a.groups = groups; a.partial = partial;
   a.nchunk = nchunk; a.gamma = gamma; a.beta = beta; a.scale_shift = scale_shift; a.ss_ld = ss_ld; a.eps = eps;
@@ -432,10 +396,7 @@ extern "C" int lfdm_groupnorm_silu_bwd_cl_f32(const float* x, const float* dy, f
   int rc = lfdm_sum_leading_f32(dgb, dgamma_dbeta, 2 * (int64_t)channels, batch, stream_);
   if (rc) return rc;
   const int64_t per_b = (int64_t)pixels * (channels / 4);
-  int64_t nb = (per_b + 255) / 256;
-  const int64_t cap = batch >= 8 ? 128 : 1024 / batch;
-  if (nb > cap) nb = cap;
-  LFDM_LAUNCH(gn_bwd_apply_kernel, dim3((unsigned)nb, batch), dim3(256), 0, stream, a, (const float*)sums, dx);
+  LFDM_LAUNCH(gn_bwd_apply_kernel, dim3(lfdm_blocks(per_b, 256, batch >= 8 ? 128 : 1024 / batch), batch), dim3(256), 0, stream, a, (const float*)sums, dx);
   return lfdm_check_launch("groupnorm_bwd");
 }
 
@@ -453,22 +414,15 @@ extern "C" int lfdm_layernorm_bwd_add_cl_f32(const float* x, const float* dy, co
                                              const float* gamma, float eps, float* dgamma, void* ws, size_t ws_bytes,
                                              lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!x || !dy || !dx || !gamma || !dgamma || rows <= 0 || channels <= 0 || channels % 4 != 0 || channels > GNB_MAX_C) {
-    lfdm_set_error("layernorm_bwd: unsupported shape (C%4==0, C<=1024)");
-    return LFDM_EINVAL;
-  }
-  if (!ws || ws_bytes < lfdm_layernorm_bwd_ws_bytes(rows, channels)) {
-    lfdm_set_error("layernorm_bwd: workspace too small");
-    return LFDM_EWORKSPACE;
-  }
+  if (!x || !dy || !dx || !gamma || !dgamma || rows <= 0 || channels <= 0 || channels % 4 != 0 || channels > GN_MAX_C)
+    return lfdm_fail(LFDM_EINVAL, "%s", "layernorm_bwd: unsupported shape (C%4==0, C<=1024)");
+  if (!ws || ws_bytes < lfdm_layernorm_bwd_ws_bytes(rows, channels))
+    return lfdm_fail(LFDM_EWORKSPACE, "layernorm_bwd: workspace too small");
   const int nb = ln_bwd_blocks(rows);
-  const bool al16 = ((((uintptr_t)x) | ((uintptr_t)dy) | ((uintptr_t)dx) | ((uintptr_t)gamma) | ((uintptr_t)dx_add)) & 15) == 0;
-  if (!al16) {      // (all three kernels read x / dy / gamma / dx_add and write dx as float4: there is no scalar form)
-    lfdm_set_error("layernorm_bwd: x, dy, dx, gamma and dx_add must be 16-byte aligned");
-    return LFDM_EINVAL;
-  }
-  if (channels == 64 && al16) LFDM_LAUNCH((layernorm_bwd_small_kernel<16>), dim3(nb), dim3(256), 0, stream, x, dy, dx, rows, gamma, eps, (float*)ws, dx_add);
-  else if (channels == 128 && al16) LFDM_LAUNCH((layernorm_bwd_small_kernel<32>), dim3(nb), dim3(256), 0, stream, x, dy, dx, rows, gamma, eps, (float*)ws, dx_add);
+  if (!lfdm_aligned16(x, dy, dx, gamma, dx_add))      // (all three kernels read x / dy / gamma / dx_add and write dx as float4: there is no scalar form)
+    return lfdm_fail(LFDM_EINVAL, "layernorm_bwd: x, dy, dx, gamma and dx_add must be 16-byte aligned");
+  if (channels == 64) LFDM_LAUNCH((layernorm_bwd_small_kernel<16>), dim3(nb), dim3(256), 0, stream, x, dy, dx, rows, gamma, eps, (float*)ws, dx_add);
+  else if (channels == 128) LFDM_LAUNCH((layernorm_bwd_small_kernel<32>), dim3(nb), dim3(256), 0, stream, x, dy, dx, rows, gamma, eps, (float*)ws, dx_add);
   else LFDM_LAUNCH(layernorm_bwd_kernel, dim3(nb), dim3(256), 0, stream, x, dy, dx, rows, channels, gamma, eps, (float*)ws, dx_add);
   int rc = lfdm_check_launch("layernorm_bwd");
   if (rc) return rc;

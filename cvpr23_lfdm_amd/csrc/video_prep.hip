@@ -242,32 +242,20 @@ extern "C" int lfdm_video_prep_u8(const unsigned char* store, int64_t store_fram
                                   int store_size, int image_size, int jitter, int launches, void* ws, size_t ws_bytes,
                                   lfdm_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (!store || !frame_index || !mean || !out || ((uintptr_t)store & 3) || ((uintptr_t)out & 15)) {
-    lfdm_set_error("video_prep: null store / frame_index / mean / out, or store not 4-byte / out not 16-byte aligned");
-    return LFDM_EINVAL;
-  }
+  if (!store || !frame_index || !mean || !out || !lfdm_aligned<4>(store) || !lfdm_aligned16(out))
+    return lfdm_fail(LFDM_EINVAL, "video_prep: null store / frame_index / mean / out, or store not 4-byte / out not 16-byte aligned");
   if (batch < 1 || frames < 1 || store_frames < 1 || store_size < 4 || image_size < 4 || store_size > 4096 ||
-      (int64_t)batch * frames > 0x7fffffff) {
-    lfdm_set_error("video_prep: batch, frames, store_frames >= 1 and 4 <= image_size <= store_size <= 4096");
-    return LFDM_EINVAL;
-  }
-  if ((store_size & 3) || (image_size & 3)) {
-    lfdm_set_error("video_prep: store_size and image_size must be multiples of 4");
-    return LFDM_EINVAL;
-  }
+      (int64_t)batch * frames > 0x7fffffff)
+    return lfdm_fail(LFDM_EINVAL, "video_prep: batch, frames, store_frames >= 1 and 4 <= image_size <= store_size <= 4096");
+  if ((store_size & 3) || (image_size & 3))
+    return lfdm_fail(LFDM_EINVAL, "video_prep: store_size and image_size must be multiples of 4");
   const int k = store_size / image_size;
-  if (k * image_size != store_size || (k != 1 && k != 2 && k != 4)) {
-    lfdm_set_error("video_prep: store_size / image_size must be 1, 2 or 4");
-    return LFDM_EINVAL;
-  }
-  if (!(launches & (LFDM_PREP_STATS | LFDM_PREP_MAIN)) || (launches & ~(LFDM_PREP_STATS | LFDM_PREP_MAIN))) {
-    lfdm_set_error("video_prep: launches is LFDM_PREP_STATS | LFDM_PREP_MAIN or one of them");
-    return LFDM_EINVAL;
-  }
-  if (jitter && (!params || !hue_shift || !ws || ((uintptr_t)ws & 3) || ws_bytes < lfdm_video_prep_ws_bytes(batch, frames))) {
-    lfdm_set_error("video_prep: jitter needs params, hue_shift and a workspace of lfdm_video_prep_ws_bytes bytes (4-byte aligned)");
-    return LFDM_EINVAL;
-  }
+  if (k * image_size != store_size || (k != 1 && k != 2 && k != 4))
+    return lfdm_fail(LFDM_EINVAL, "video_prep: store_size / image_size must be 1, 2 or 4");
+  if (!(launches & (LFDM_PREP_STATS | LFDM_PREP_MAIN)) || (launches & ~(LFDM_PREP_STATS | LFDM_PREP_MAIN)))
+    return lfdm_fail(LFDM_EINVAL, "video_prep: launches is LFDM_PREP_STATS | LFDM_PREP_MAIN or one of them");
+  if (jitter && (!params || !hue_shift || !ws || !lfdm_aligned<4>(ws) || ws_bytes < lfdm_video_prep_ws_bytes(batch, frames)))
+    return lfdm_fail(LFDM_EINVAL, "video_prep: jitter needs params, hue_shift and a workspace of lfdm_video_prep_ws_bytes bytes (4-byte aligned)");
   PrepArgs a;
   a.store = store;
   a.frame_index = frame_index;
@@ -282,10 +270,8 @@ extern "C" int lfdm_video_prep_u8(const unsigned char* store, int64_t store_fram
   a.H = image_size;
   a.n_groups = (int64_t)batch * frames * image_size * (image_size / kGroup);
   const int64_t blocks = (a.n_groups + kPrepBlock - 1) / kPrepBlock;
-  if (blocks > 0x7fffffff) {
-    lfdm_set_error("video_prep: the batch has more than 2^41 pixels");
-    return LFDM_EINVAL;
-  }
+  if (blocks > 0x7fffffff)
+    return lfdm_fail(LFDM_EINVAL, "video_prep: the batch has more than 2^41 pixels");
   if (jitter && (launches & LFDM_PREP_STATS)) {
     LFDM_LAUNCH(prep_stats_kernel, dim3((unsigned)(batch * frames)), dim3(kPrepBlock), 0, stream, a);
     const int rc = lfdm_check_launch("video_prep (stats)");

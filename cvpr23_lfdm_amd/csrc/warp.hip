@@ -254,10 +254,8 @@ __global__ __launch_bounds__(256) void warp_planar_pixel_kernel(lfdm_warp_params
 
 static int check_warp(const lfdm_warp_params* p, const char* who) {
   if (!p || !p->src || !p->out || !p->flow_x || !p->flow_y || p->batch <= 0 || p->frames <= 0 ||
-      p->h <= 0 || p->w <= 0 || p->c <= 0 || p->fh <= 0 || p->fw <= 0) {
-    lfdm_set_error(who);
-    return LFDM_EINVAL;
-  }
+      p->h <= 0 || p->w <= 0 || p->c <= 0 || p->fh <= 0 || p->fw <= 0)
+    return lfdm_fail(LFDM_EINVAL, "%s", who);
   return LFDM_OK;
 }
 
@@ -267,22 +265,16 @@ extern "C" int lfdm_warp_cl_f32(const lfdm_warp_params* pp, lfdm_stream_t stream
   if (rc) return rc;
   lfdm_warp_params p = *pp;
   if (p.c % 4 != 0 || p.ld_src % 4 != 0 || p.ld_out % 4 != 0 || (p.prev && p.ld_prev % 4 != 0) ||
-      p.ld_src < p.c || p.ld_out < p.c || (((uintptr_t)p.src | (uintptr_t)p.out | (uintptr_t)p.prev) & 15) != 0) {
-    lfdm_set_error("warp_cl: channels and row strides must be multiples of 4, src / out / prev 16-byte aligned (float4 accesses)");
-    return LFDM_EINVAL;
-  }
+      p.ld_src < p.c || p.ld_out < p.c || !lfdm_aligned16(p.src, p.out, p.prev))
+    return lfdm_fail(LFDM_EINVAL, "warp_cl: channels and row strides must be multiples of 4, src / out / prev 16-byte aligned (float4 accesses)");
   int r = (p.c % 16 == 0) ? 4 : (p.c % 8 == 0 ? 2 : 1);
   if (const char* e = lfdm_knob("LFDM_WARP_R")) {      // experiment knob (bench.py warp object): lanes per pixel = C / (4 r)
     const int v = atoi(e);
     if ((v == 1 || v == 2 || v == 4) && p.c % (4 * v) == 0) r = v;
   }
   const int64_t per_frame = (int64_t)p.h * p.w * (p.c / (4 * r));
-  if (per_frame >= (1ll << 31) - 256 * 65536) { lfdm_set_error("warp_cl: frame too large"); return LFDM_EINVAL; }
-  int64_t nbx = (per_frame + 255) / 256;
-  if (nbx > 65536) nbx = 65536;
-  int64_t nby = (int64_t)p.batch * p.frames;
-  if (nby > 65535) nby = 65535;
-  const dim3 grid((unsigned)nbx, (unsigned)nby);
+  if (per_frame >= (1ll << 31) - 256 * 65536) return lfdm_fail(LFDM_EINVAL, "warp_cl: frame too large");
+  const dim3 grid(lfdm_blocks(per_frame, 256, 65536), lfdm_blocks((int64_t)p.batch * p.frames, 1, 65535));
   if (r == 4) LFDM_LAUNCH((warp_cl_kernel<4>), grid, dim3(256), 0, stream, p);
   else if (r == 2) LFDM_LAUNCH((warp_cl_kernel<2>), grid, dim3(256), 0, stream, p);
   else LFDM_LAUNCH((warp_cl_kernel<1>), grid, dim3(256), 0, stream, p);
@@ -305,7 +297,7 @@ extern "C" int lfdm_warp_planar_f32(const lfdm_warp_params* pp, lfdm_stream_t st
     return lfdm_check_launch("warp_planar");
   }
   const dim3 grid((p.frames + fpb - 1) / fpb, p.c, p.batch), block(256);
-  const bool staged = hw <= PLANE_MAX && (hw % 4) == 0 && (((uintptr_t)p.src & 15) == 0);
+  const bool staged = hw <= PLANE_MAX && (hw % 4) == 0 && lfdm_aligned16(p.src);
   if (staged) LFDM_LAUNCH((warp_planar_kernel<true>), grid, block, 0, stream, p, fpb);
   else LFDM_LAUNCH((warp_planar_kernel<false>), grid, block, 0, stream, p, fpb);
   return lfdm_check_launch("warp_planar");

@@ -2,17 +2,17 @@
 """Same bits?  Runs a fixed list of calls on seeded inputs under ONE build of the kernels and writes one line per output tensor -
 name, shape, SHA-256 of its bytes - so that two builds (a refactor and its parent commit) can be compared line by line.
 
-    tools/ab_bits.py run OUT.txt [--emu [LIB]] [--set conv|attention]
+    tools/ab_bits.py run OUT.txt [--emu [LIB]] [--set conv|attention|norm]
                                                          this process, the library LFDM_HIP_LIB names (default: the in-tree one) on the GPU,
                                                          or an emulator library on the CPU (default: the in-tree one)
     tools/ab_bits.py diff A.txt B.txt                    exit status 1 when any line differs or is missing
-    tools/ab_bits.py ab BASE_LIB OUT_DIR [--emu] [--new LIB] [--timeout S] [--set conv|attention]
+    tools/ab_bits.py ab BASE_LIB OUT_DIR [--emu] [--new LIB] [--timeout S] [--set conv|attention|norm]
                                                          `run` under BASE_LIB, then under the in-tree library (or --new), each in a fresh child
                                                          process with its own time limit, one after the other; stops at the first non-zero
                                                          exit status; then `diff`
 
 The calls are the suite's own: the listed tests of tests/ run in-process (their case lists cannot go stale here) with every function of
-cvpr23_lfdm_amd.ops / train_ops wrapped - each tensor a call returns, and the gn_partial buffer it was handed, becomes a line.  `extra` below adds
+cvpr23_lfdm_amd.ops / train_ops / lfae_ops wrapped - each tensor a call returns, and the gn_partial buffer it was handed, becomes a line.  `extra` below adds
 the few cells no test reaches.  Nothing but tensor bytes is looked at."""
 import argparse
 import hashlib
@@ -23,6 +23,7 @@ import sys
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # (file, -k expression) per --set.  conv: the smallest shapes that reach every epilogue / GroupNorm hand-off of the convolution family;
+# norm: the GroupNorm / LayerNorm / BatchNorm kernels forward and backward, the heads kernels and the kernels that share csrc/norm_core.h;
 # attention: every entry point that goes through csrc/attn_core.h (the short-sequence core, the fused temporal kernels, the low-resolution
 # kernel), the long-sequence kernels beside them, the fast-math cases and the per-tile-order cases.
 SETS = {
@@ -43,6 +44,15 @@ SETS = {
         ("tests/test_attention_long.py", "test_forward or test_backward"),
         ("tests/test_attend_pipeline.py", "test_block or test_core"),
     ], "not refuses"),
+    "norm": ([
+        ("tests/test_ops_parity.py",
+         "test_groupnorm_silu or test_groupnorm_apply_many_partials or test_conv_fused_groupnorm_stats or "
+         "test_conv_pointwise_residual_groupnorm or test_layernorm or test_conv_planar_in_and_heads or test_heads_with_groupnorm_folded"),
+        ("tests/test_train_ops.py", "test_groupnorm_bwd or test_layernorm_bwd"),
+        ("tests/test_train_edges.py", "test_groupnorm_bwd_edges or test_layernorm_bwd_edges or test_colsum_block_cap"),
+        ("tests/test_lfae_ops.py", "test_batchnorm_relu or test_batchnorm_relu_segments or test_batchnorm_fork_and_channel_slices"),
+        ("tests/test_norm_edges.py", "test_layernorm or test_groupnorm or test_heads"),
+    ], "not gpu_only and not bigTrue and not refuses"),
 }
 
 
@@ -90,11 +100,12 @@ class Recorder:
 
     def pytest_sessionstart(self, session):
         sys.path.insert(0, R)
-        from cvpr23_lfdm_amd import _build, ops, train_ops
+        from cvpr23_lfdm_amd import _build, lfae_ops, ops, train_ops
         if self.emu_lib:
             _build.build_emu = lambda force=False: self.emu_lib      # (the suite's `backend` fixture asks the build for the emulator library)
         self.wrap(ops)
         self.wrap(train_ops)
+        self.wrap(lfae_ops)
 
     def pytest_runtest_setup(self, item):
         self.test, self.ncall = item.nodeid.split("::", 1)[1], 0
