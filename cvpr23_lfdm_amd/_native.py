@@ -250,6 +250,8 @@ _SIGNATURES = {
     "lfdm_video_prep_ws_bytes": (sz, [i32, i32]),
     "lfdm_video_prep_u8": (i32, [C.c_void_p, i64, C.c_void_p, f32p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), f32p, i32, i32, i32, i32,
                                  i32, i32, C.c_void_p, sz, stream_t]),
+    "lfdm_frame_pairs_prep_u8": (i32, [C.c_void_p, i64, C.c_void_p, f32p, C.c_void_p, C.c_void_p, C.c_void_p, f32p, f32p, i32, i32, i32, i32,
+                                       C.c_void_p, sz, stream_t]),
     # ---- temporal resampling of a sampled latent (additive, ABI stays 12)
     "lfdm_latent_resample_f32": (i32, [f32p, C.c_void_p, f32p, f32p, f32p, f32p, f32p, i32, i32, i32, i32, i32, i32, i32, i32, stream_t]),
     "lfdm_depthwise_down_planar_f32": (i32, [f32p, f32p, f32p, i32, i32, i32, i32, i32, i32, i32, i32, stream_t]),

@@ -4,7 +4,9 @@
 // the transpose to (B, 3, T, H, W).  The arithmetic is PIL's and numpy's, restated operation by operation so that the floats are the host's:
 //   prep_stats_kernel        one workgroup per (b, t): the contrast grey level of the frame after brightness (integer sums, no atomics)
 //   prep_kernel<K, JITTER>   one thread per 4 adjacent output pixels: K rows of 12 K source bytes in, 16 bytes per channel plane out
-// Off the training step: nothing here is launched unless a loader asks for it (video_store.DevicePrep).
+//   prep_kernel<K, JITTER, true>  the same for lfae_train.FramePairs' (source, driving) pairs (lfdm_frame_pairs_prep_u8): T = 2, frame t
+//                            to output t (B, 3, H, H), / 255 only, a horizontal flip per item
+// Off the training step: nothing here is launched unless a loader asks for it (video_store.DevicePrep, DevicePairPrep).
 #include "lfdm_device.h"
 #include "../../include/lfdm_hip.h"
 
@@ -32,6 +34,9 @@ struct PrepArgs {
   float mean[3];
   int frames, S, H;
   int64_t n_groups;                    // B * T * H * H / 4
+  // the pair form only (T = 2, no mean): out is source, frame 1 goes to driving, both (B, 3, H, H)
+  const int* flip;                     // (B) 0 or 1: mirror the rows of both frames of the item
+  float* driving;
 };
 
 __device__ __forceinline__ int luma(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 0x8000) >> 16; }
@@ -157,7 +162,10 @@ __global__ __launch_bounds__(kPrepBlock) void prep_stats_kernel(PrepArgs a) {
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Thread q makes output pixels 4 xg .. 4 xg + 3 of row y of frame (b, t): K source rows of 4 K pixels = 3 K dwords each (S % 4 == 0, so
 // every such run starts on a dword), each pixel jittered, K x K byte sums per channel, one conversion, one float4 per channel plane.
-template <int K, bool JITTER>
+// PAIRS: where flip[b] is set the row is mirrored, out[y][x] = shrunk[y][H - 1 - x]: the thread computes group H / 4 - 1 - xg exactly as
+// otherwise - the valid rectangle stays in unflipped store coordinates, so the padding moves with the picture - and stores its four
+// values in reversed order.  The flag is per item: the threads of one frame all take the same side.
+template <int K, bool JITTER, bool PAIRS = false>
 __global__ __launch_bounds__(kPrepBlock) void prep_kernel(PrepArgs a) {
   const int64_t q = (int64_t)blockIdx.x * kPrepBlock + threadIdx.x;
   if (q >= a.n_groups) return;
@@ -168,6 +176,8 @@ __global__ __launch_bounds__(kPrepBlock) void prep_kernel(PrepArgs a) {
   const int bt = (int)(row / H), y = (int)(row - (int64_t)bt * H);
   const int b = bt / T, t = bt - b * T;
   const unsigned char* frame = a.store + (int64_t)a.frame_index[bt] * S * S * 3;
+  const bool mirror = PAIRS && a.flip[b] != 0;
+  const int src_xg = mirror ? groups_per_row - 1 - xg : xg;
   Jitter jit = {1.f, 1.f, 1.f, 0, 0};
   int y0 = 0, x0 = 0, vh = S, vw = S;
   if (JITTER) {
@@ -189,7 +199,7 @@ __global__ __launch_bounds__(kPrepBlock) void prep_kernel(PrepArgs a) {
   // with jitter the row loop stays rolled: 4 K inlined copies of the jitter are code enough, 4 K * K of them spill
 #pragma unroll(JITTER ? 1 : K)
   for (int dy = 0; dy < K; ++dy) {
-    const int sy = y * K + dy, sx = xg * kGroup * K;
+    const int sy = y * K + dy, sx = src_xg * kGroup * K;
     const uint32_t* src = reinterpret_cast<const uint32_t*>(frame + ((int64_t)sy * S + sx) * 3);
     uint32_t w[3 * K];
 #pragma unroll
@@ -209,6 +219,22 @@ __global__ __launch_bounds__(kPrepBlock) void prep_kernel(PrepArgs a) {
     }
   }
   const int64_t plane = (int64_t)H * H;
+  if (PAIRS) {
+    float* o = (t ? a.driving : a.out) + (int64_t)b * 3 * plane + (int64_t)y * H + xg * kGroup;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      // lfae_train.FramePairs has no mean: numpy's  x / 255.0  is the one division
+      const float v0 = __fdiv_rn((float)sum[0][c] / (float)(K * K), 255.0f), v1 = __fdiv_rn((float)sum[1][c] / (float)(K * K), 255.0f),
+                  v2 = __fdiv_rn((float)sum[2][c] / (float)(K * K), 255.0f), v3 = __fdiv_rn((float)sum[3][c] / (float)(K * K), 255.0f);
+      float4 v;
+      v.x = mirror ? v3 : v0;
+      v.y = mirror ? v2 : v1;
+      v.z = mirror ? v1 : v2;
+      v.w = mirror ? v0 : v3;
+      *reinterpret_cast<float4*>(o + (int64_t)c * plane) = v;
+    }
+    return;
+  }
   float* o = a.out + ((int64_t)b * 3 * T + t) * plane + (int64_t)y * H + xg * kGroup;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -222,12 +248,22 @@ __global__ __launch_bounds__(kPrepBlock) void prep_kernel(PrepArgs a) {
   }
 }
 
-template <int K>
+template <int K, bool PAIRS>
 void launch_prep(const PrepArgs& a, bool jitter, unsigned blocks, hipStream_t stream) {
   if (jitter)
-    LFDM_LAUNCH((prep_kernel<K, true>), dim3(blocks), dim3(kPrepBlock), 0, stream, a);
+    LFDM_LAUNCH((prep_kernel<K, true, PAIRS>), dim3(blocks), dim3(kPrepBlock), 0, stream, a);
   else
-    LFDM_LAUNCH((prep_kernel<K, false>), dim3(blocks), dim3(kPrepBlock), 0, stream, a);
+    LFDM_LAUNCH((prep_kernel<K, false, PAIRS>), dim3(blocks), dim3(kPrepBlock), 0, stream, a);
+}
+
+template <bool PAIRS>
+void launch_prep_ratio(int k, const PrepArgs& a, bool jitter, unsigned blocks, hipStream_t stream) {
+  if (k == 1)
+    launch_prep<1, PAIRS>(a, jitter, blocks, stream);
+  else if (k == 2)
+    launch_prep<2, PAIRS>(a, jitter, blocks, stream);
+  else
+    launch_prep<4, PAIRS>(a, jitter, blocks, stream);
 }
 
 }  // namespace
@@ -269,6 +305,8 @@ extern "C" int lfdm_video_prep_u8(const unsigned char* store, int64_t store_fram
   a.S = store_size;
   a.H = image_size;
   a.n_groups = (int64_t)batch * frames * image_size * (image_size / kGroup);
+  a.flip = nullptr;
+  a.driving = nullptr;
   const int64_t blocks = (a.n_groups + kPrepBlock - 1) / kPrepBlock;
   if (blocks > 0x7fffffff)
     return lfdm_fail(LFDM_EINVAL, "video_prep: the batch has more than 2^41 pixels");
@@ -278,13 +316,52 @@ extern "C" int lfdm_video_prep_u8(const unsigned char* store, int64_t store_fram
     if (rc) return rc;
   }
   if (launches & LFDM_PREP_MAIN) {
-    if (k == 1)
-      launch_prep<1>(a, jitter != 0, (unsigned)blocks, stream);
-    else if (k == 2)
-      launch_prep<2>(a, jitter != 0, (unsigned)blocks, stream);
-    else
-      launch_prep<4>(a, jitter != 0, (unsigned)blocks, stream);
+    launch_prep_ratio<false>(k, a, jitter != 0, (unsigned)blocks, stream);
     return lfdm_check_launch("video_prep");
   }
   return 0;
+}
+
+extern "C" int lfdm_frame_pairs_prep_u8(const unsigned char* store, int64_t store_frames, const int* pair_index, const float* params,
+                                        const int* hue_shift, const int* valid, const int* flip, float* source, float* driving, int batch,
+                                        int store_size, int image_size, int jitter, void* ws, size_t ws_bytes, lfdm_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!store || !pair_index || !flip || !source || !driving || !lfdm_aligned<4>(store) || !lfdm_aligned16(source) || !lfdm_aligned16(driving))
+    return lfdm_fail(LFDM_EINVAL,
+                     "frame_pairs_prep: null store / pair_index / flip / source / driving, or store not 4-byte / an output not 16-byte aligned");
+  if (batch < 1 || store_frames < 1 || store_size < 4 || image_size < 4 || store_size > 4096 || (int64_t)batch * 2 > 0x7fffffff)
+    return lfdm_fail(LFDM_EINVAL, "frame_pairs_prep: batch, store_frames >= 1 and 4 <= image_size <= store_size <= 4096");
+  if ((store_size & 3) || (image_size & 3))
+    return lfdm_fail(LFDM_EINVAL, "frame_pairs_prep: store_size and image_size must be multiples of 4");
+  const int k = store_size / image_size;
+  if (k * image_size != store_size || (k != 1 && k != 2 && k != 4))
+    return lfdm_fail(LFDM_EINVAL, "frame_pairs_prep: store_size / image_size must be 1, 2 or 4");
+  if (jitter && (!params || !hue_shift || !ws || !lfdm_aligned<4>(ws) || ws_bytes < lfdm_video_prep_ws_bytes(batch, 2)))
+    return lfdm_fail(LFDM_EINVAL,
+                     "frame_pairs_prep: jitter needs params, hue_shift and a workspace of lfdm_video_prep_ws_bytes(batch, 2) bytes (4-byte aligned)");
+  PrepArgs a;
+  a.store = store;
+  a.frame_index = pair_index;
+  a.params = params;
+  a.hue_shift = hue_shift;
+  a.valid = valid;
+  a.grey = (int*)ws;
+  a.out = source;
+  a.mean[0] = a.mean[1] = a.mean[2] = 0.f;
+  a.frames = 2;
+  a.S = store_size;
+  a.H = image_size;
+  a.n_groups = (int64_t)batch * 2 * image_size * (image_size / kGroup);
+  a.flip = flip;
+  a.driving = driving;
+  const int64_t blocks = (a.n_groups + kPrepBlock - 1) / kPrepBlock;
+  if (blocks > 0x7fffffff)
+    return lfdm_fail(LFDM_EINVAL, "frame_pairs_prep: the batch has more than 2^41 pixels");
+  if (jitter) {
+    LFDM_LAUNCH(prep_stats_kernel, dim3((unsigned)(batch * 2)), dim3(kPrepBlock), 0, stream, a);
+    const int rc = lfdm_check_launch("frame_pairs_prep (stats)");
+    if (rc) return rc;
+  }
+  launch_prep_ratio<true>(k, a, jitter != 0, (unsigned)blocks, stream);
+  return lfdm_check_launch("frame_pairs_prep");
 }

@@ -1482,6 +1482,65 @@ PREP_RATIOS = (1, 2, 4)
 PREP_STATS, PREP_MAIN = 1, 2          # LFDM_PREP_*
 
 
+def _prep_operands(what, rows_name, store_u8, rows, params, hue_shift, valid, image_size, jitter, outs, frames=None):
+    """The operand checks video_prep and frame_pairs_prep share: the store, the (B, T) table of store rows (T == frames when given), every
+    row range-checked on the host, and with jitter the factor tables and the valid rectangles.  Uploads the small tables and allocates
+    the stats workspace.  -> (lib, N, S, H, B, T, device, rows, params, hue_shift, valid, ws, ws_bytes)."""
+    lib = _lib()
+    if not isinstance(store_u8, torch.Tensor) or store_u8.dtype != torch.uint8 or store_u8.dim() != 4 or store_u8.shape[3] != 3 \
+            or store_u8.shape[1] != store_u8.shape[2] or not store_u8.is_contiguous():
+        raise ValueError("%s: store_u8 must be a contiguous uint8 (N, S, S, 3) tensor, got %s %s"
+                         % (what, getattr(store_u8, "dtype", type(store_u8)), tuple(getattr(store_u8, "shape", ()))))
+    _chk_dev(lib, store_u8, *[o for o in outs if isinstance(o, torch.Tensor)])
+    n, s = int(store_u8.shape[0]), int(store_u8.shape[1])
+    h = int(image_size)
+    if s % 4 != 0 or h % 4 != 0 or h < 4:
+        raise ValueError("%s: store_size %d and image_size %d must be multiples of 4" % (what, s, h))
+    if h * (s // h) != s or s // h not in PREP_RATIOS:
+        raise ValueError("%s: store_size / image_size must be 1, 2 or 4, got %d / %d" % (what, s, h))
+    if n < 1:
+        raise ValueError("%s: the store is empty" % what)
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or rows.dim() != 2 or rows.numel() == 0 \
+            or (frames is not None and rows.shape[1] != frames):
+        raise ValueError("%s: %s must be a non-empty int32 (B, %s) tensor, got %s %s"
+                         % (what, rows_name, "T" if frames is None else frames, getattr(rows, "dtype", type(rows)),
+                            tuple(getattr(rows, "shape", ()))))
+    b, t = int(rows.shape[0]), int(rows.shape[1])
+    lo, hi = int(rows.min()), int(rows.max())
+    if lo < 0 or hi >= n:
+        raise IndexError("%s: %s holds %d .. %d, the store has rows 0 .. %d" % (what, rows_name, lo, hi, n - 1))
+    dev = store_u8.device
+
+    def table(name, x):          # the small per-batch tables may come from the host: checked there, then uploaded
+        if x is None or x.device == dev:
+            return x if x is None else x.contiguous()
+        if x.is_cuda:
+            raise ValueError("%s: %s is on %s, the store on %s" % (what, name, x.device, dev))
+        return x.contiguous().to(dev, non_blocking=True)
+
+    rows = table(rows_name, rows)
+    ws, ws_bytes = None, 0
+    if jitter:
+        if not isinstance(params, torch.Tensor) or params.dtype != torch.float32 or tuple(params.shape) != (b, 3):
+            raise ValueError("%s: params must be a float32 (%d, 3) tensor" % (what, b))
+        if not bool(torch.isfinite(params).all()):          # a NaN or inf factor would reach the kernel's float -> int conversion
+            raise ValueError("%s: params holds a NaN or an infinity" % what)
+        if not isinstance(hue_shift, torch.Tensor) or hue_shift.dtype != torch.int32 or tuple(hue_shift.shape) != (b,):
+            raise ValueError("%s: hue_shift must be an int32 (%d,) tensor" % (what, b))
+        if valid is not None:
+            if not isinstance(valid, torch.Tensor) or valid.dtype != torch.int32 or tuple(valid.shape) != (b, 4):
+                raise ValueError("%s: valid must be an int32 (%d, 4) tensor of (y0, x0, h, w)" % (what, b))
+            vv = valid.cpu()
+            if bool((vv < 0).any()) or bool((vv[:, 2:] < 1).any()) or bool(((vv[:, :2] + vv[:, 2:]) > s).any()):
+                raise ValueError("%s: a valid rectangle is empty or leaves the %d x %d stored frame" % (what, s, s))
+        params, hue_shift, valid = table("params", params), table("hue_shift", hue_shift), table("valid", valid)
+        ws_bytes = lib.lfdm_video_prep_ws_bytes(b, t)
+        ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
+    else:
+        params = hue_shift = valid = None
+    return lib, n, s, h, b, t, dev, rows, params, hue_shift, valid, ws, ws_bytes
+
+
 def video_prep(store_u8, frame_index, params, hue_shift, mean, image_size, jitter, out=None, *, valid=None,
                launches=PREP_STATS | PREP_MAIN):
     """lfdm_video_prep_u8: gathers frames from store_u8 (N, S, S, 3) uint8 by frame_index (B, T) int32 and returns the training batch
@@ -1492,69 +1551,57 @@ def video_prep(store_u8, frame_index, params, hue_shift, mean, image_size, jitte
     contrast mean see only it.  frame_index may have repeats and any order; every entry is range-checked here, on the host.  The four
     small tables (frame_index, params, hue_shift, valid) may be host tensors - they are checked there and uploaded - which avoids the
     read-back that checking a device tensor costs.  launches: measurement only (tools/bench_video_prep.py)."""
-    lib = _lib()
-    if not isinstance(store_u8, torch.Tensor) or store_u8.dtype != torch.uint8 or store_u8.dim() != 4 or store_u8.shape[3] != 3 \
-            or store_u8.shape[1] != store_u8.shape[2] or not store_u8.is_contiguous():
-        raise ValueError("video_prep: store_u8 must be a contiguous uint8 (N, S, S, 3) tensor, got %s %s"
-                         % (getattr(store_u8, "dtype", type(store_u8)), tuple(getattr(store_u8, "shape", ()))))
-    _chk_dev(lib, store_u8, out)
-    n, s = int(store_u8.shape[0]), int(store_u8.shape[1])
-    h = int(image_size)
-    if s % 4 != 0 or h % 4 != 0 or h < 4:
-        raise ValueError("video_prep: store_size %d and image_size %d must be multiples of 4" % (s, h))
-    if h * (s // h) != s or s // h not in PREP_RATIOS:
-        raise ValueError("video_prep: store_size / image_size must be 1, 2 or 4, got %d / %d" % (s, h))
-    if n < 1:
-        raise ValueError("video_prep: the store is empty")
-    if not isinstance(frame_index, torch.Tensor) or frame_index.dtype != torch.int32 or frame_index.dim() != 2 or frame_index.numel() == 0:
-        raise ValueError("video_prep: frame_index must be a non-empty int32 (B, T) tensor, got %s %s"
-                         % (getattr(frame_index, "dtype", type(frame_index)), tuple(getattr(frame_index, "shape", ()))))
-    b, t = int(frame_index.shape[0]), int(frame_index.shape[1])
-    lo, hi = int(frame_index.min()), int(frame_index.max())
-    if lo < 0 or hi >= n:
-        raise IndexError("video_prep: frame_index holds %d .. %d, the store has rows 0 .. %d" % (lo, hi, n - 1))
-    dev = store_u8.device
-
-    def table(name, x):          # the small per-batch tables may come from the host: checked there, then uploaded
-        if x is None or x.device == dev:
-            return x if x is None else x.contiguous()
-        if x.is_cuda:
-            raise ValueError("video_prep: %s is on %s, the store on %s" % (name, x.device, dev))
-        return x.contiguous().to(dev, non_blocking=True)
-
-    frame_index = table("frame_index", frame_index)
+    lib, n, s, h, b, t, dev, frame_index, params, hue_shift, valid, ws, ws_bytes = _prep_operands(
+        "video_prep", "frame_index", store_u8, frame_index, params, hue_shift, valid, image_size, jitter, (out,))
     mean = [float(m) for m in mean]
     if len(mean) != 3:
         raise ValueError("video_prep: mean has three channels")
-    jitter = bool(jitter)
-    ws, ws_bytes = None, 0
-    if jitter:
-        if not isinstance(params, torch.Tensor) or params.dtype != torch.float32 or tuple(params.shape) != (b, 3):
-            raise ValueError("video_prep: params must be a float32 (%d, 3) tensor" % b)
-        if not bool(torch.isfinite(params).all()):          # a NaN or inf factor would reach the kernel's float -> int conversion
-            raise ValueError("video_prep: params holds a NaN or an infinity")
-        if not isinstance(hue_shift, torch.Tensor) or hue_shift.dtype != torch.int32 or tuple(hue_shift.shape) != (b,):
-            raise ValueError("video_prep: hue_shift must be an int32 (%d,) tensor" % b)
-        if valid is not None:
-            if not isinstance(valid, torch.Tensor) or valid.dtype != torch.int32 or tuple(valid.shape) != (b, 4):
-                raise ValueError("video_prep: valid must be an int32 (%d, 4) tensor of (y0, x0, h, w)" % b)
-            vv = valid.cpu()
-            if bool((vv < 0).any()) or bool((vv[:, 2:] < 1).any()) or bool(((vv[:, :2] + vv[:, 2:]) > s).any()):
-                raise ValueError("video_prep: a valid rectangle is empty or leaves the %d x %d stored frame" % (s, s))
-        params, hue_shift, valid = table("params", params), table("hue_shift", hue_shift), table("valid", valid)
-        ws_bytes = lib.lfdm_video_prep_ws_bytes(b, t)
-        ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
-    else:
-        params = hue_shift = valid = None
     shape = (b, 3, t, h, h)
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=dev)
     elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != dev:
         raise ValueError("video_prep: out must be a contiguous float32 %s tensor on the store's device" % (shape,))
     lib.check(lib.lfdm_video_prep_u8(_p(store_u8), n, _p(frame_index), _p(params), _p(hue_shift), _p(valid), (C.c_float * 3)(*mean),
-                                     _p(out), b, t, s, h, int(jitter), int(launches), _p(ws), ws_bytes, _stream(lib)),
+                                     _p(out), b, t, s, h, int(bool(jitter)), int(launches), _p(ws), ws_bytes, _stream(lib)),
               "lfdm_video_prep_u8")
     return out
+
+
+def frame_pairs_prep(store_u8, pair_index, params, hue_shift, flip, image_size, jitter, out=None, *, valid=None):
+    """lfdm_frame_pairs_prep_u8: LFAE stage-1 training pairs from store_u8 (N, S, S, 3) uint8 - returns (source, driving), each
+    (B, 3, H, H) float32, bit for bit what lfae_train.FramePairs makes of the same pixels.  pair_index (B, 2) int32: the store rows of
+    (source, driving), equal rows and any order allowed.  params, hue_shift, valid and jitter as in video_prep: one jitter per pair.
+    flip (B,) int32 of 0 / 1: mirror both frames of the item left to right after shrink and padding (valid stays in unflipped
+    coordinates).  No mean: / 255 only.  out: a pair of contiguous (B, 3, H, H) float32 tensors to write into.  The checks, and the
+    small tables that may be host tensors, are video_prep's."""
+    outs = (None, None) if out is None else tuple(out)
+    if len(outs) != 2:
+        raise ValueError("frame_pairs_prep: out is a (source, driving) pair of tensors")
+    lib, n, s, h, b, _, dev, pair_index, params, hue_shift, valid, ws, ws_bytes = _prep_operands(
+        "frame_pairs_prep", "pair_index", store_u8, pair_index, params, hue_shift, valid, image_size, jitter, outs, frames=2)
+    if not isinstance(flip, torch.Tensor) or flip.dtype != torch.int32 or tuple(flip.shape) != (b,):
+        raise ValueError("frame_pairs_prep: flip must be an int32 (%d,) tensor of 0 / 1" % b)
+    if bool(((flip != 0) & (flip != 1)).any()):
+        raise ValueError("frame_pairs_prep: flip holds a value other than 0 and 1")
+    if flip.device != dev:
+        if flip.is_cuda:
+            raise ValueError("frame_pairs_prep: flip is on %s, the store on %s" % (flip.device, dev))
+        flip = flip.to(dev, non_blocking=True)
+    flip = flip.contiguous()
+    shape = (b, 3, h, h)
+    res = []
+    for name, o in zip(("source", "driving"), outs):
+        if o is None:
+            o = torch.empty(shape, dtype=torch.float32, device=dev)
+        elif not isinstance(o, torch.Tensor) or o.dtype != torch.float32 or tuple(o.shape) != shape or not o.is_contiguous() \
+                or o.device != dev or o.data_ptr() % 16 != 0:
+            raise ValueError("frame_pairs_prep: out (%s) must be a contiguous, 16-byte aligned float32 %s tensor on the store's device"
+                             % (name, shape))
+        res.append(o)
+    lib.check(lib.lfdm_frame_pairs_prep_u8(_p(store_u8), n, _p(pair_index), _p(params), _p(hue_shift), _p(valid), _p(flip), _p(res[0]),
+                                           _p(res[1]), b, s, h, int(bool(jitter)), _p(ws), ws_bytes, _stream(lib)),
+              "lfdm_frame_pairs_prep_u8")
+    return res[0], res[1]
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1,10 +1,13 @@
-"""Packed uint8 frame store and on-device batch preparation for the DM trainer - an opt-in input path beside
-data.FrameFolderVideos, which stays the definition of what a batch is.
+"""Packed uint8 frame store and on-device batch preparation for the two trainers - an opt-in input path beside
+data.FrameFolderVideos and lfae_train.FramePairs, which stay the definitions of what a batch is.
 
     pack_frame_folders(root, out_dir, store_size)      decode every frame of root/<label>/<video>/*.jpg|png ONCE, area-resize it to
-                                                       store_size (1, 2 or 4 x the training size) -> frames.u8 + index.json
+                                                       store_size (1, 2 or 4 x the training size) -> frames.u8 + index.json;
+                                                       layout="any": every folder of frames at any depth, as FramePairs walks
     PackedVideos(out_dir, image_size, ...)             Dataset over the store: an item is bytes and four jitter numbers, no arithmetic
     DevicePrep(dataset)                                collated batch -> real_vids (B, 3, T, H, W) float32 on the device (ops.video_prep)
+    PackedFramePairs(out_dir, frame_shape, ...)        LFAE stage 1: FramePairs' draws over the store, an item is two frames' bytes or rows
+    DevicePairPrep(dataset)                            collated batch -> {"source", "driving"} (B, 3, H, W) (ops.frame_pairs_prep)
 
 Colour jitter, the area shrink, the mean and the / 255 run in csrc/video_prep.hip, bit for bit what FrameFolderVideos computes from the
 stored bytes.  The approximation is the store itself.  A source larger than store_size is rounded to a byte once, when packed: without
@@ -22,6 +25,7 @@ from torch.utils import data as tdata
 
 from . import _native, ops
 from .data import FrameFolderVideos, _rgb, sample_indices
+from .lfae_train import FramePairs
 from .io_compat import INTER_AREA, imread, resize
 
 FRAMES_FILE, INDEX_FILE = "frames.u8", "index.json"
@@ -46,13 +50,37 @@ def _picture_rect(shape, store_size):
     return [(store_size - h) // 2, (store_size - w) // 2, h, w]
 
 
-def pack_frame_folders(root, out_dir, store_size):
-    """Walks root/<label>/<video>/*.jpg|png like FrameFolderVideos and writes out_dir/frames.u8, a flat (N_frames, S, S, 3) uint8 array of
+PACK_LAYOUTS = ("label/video", "any")
+
+
+def _walk_any(root):
+    """Every folder under root that holds at least one *.jpg|jpeg|png frame, at any depth, in the order lfae_train.FramePairs walks
+    (sorted by folder path) -> [(label, video, paths)]: label is the first path component below root and video the rest of the relative
+    path; a folder directly under root (MHAD's and NATOPS' flat layout) has label "" and its own name as video, root itself "" and ""."""
+    videos = []
+    for folder, _, files in sorted(os.walk(root)):
+        frames = sorted(f for f in files if f.lower().endswith(("jpg", "jpeg", "png")))
+        if not frames:
+            continue
+        rel = os.path.relpath(folder, root)
+        parts = [] if rel == os.curdir else rel.split(os.sep)
+        label, vid = ("", "/".join(parts)) if len(parts) < 2 else (parts[0], "/".join(parts[1:]))
+        videos.append((label, vid, [os.path.join(folder, f) for f in frames]))
+    if not videos:
+        raise FileNotFoundError("no folders with *.jpg|png frames under %r" % (root,))
+    return videos
+
+
+def pack_frame_folders(root, out_dir, store_size, layout="label/video"):
+    """Walks root/<label>/<video>/*.jpg|png like FrameFolderVideos - or, layout="any", folders of any depth like lfae_train.FramePairs
+    (_walk_any) - and writes out_dir/frames.u8, a flat (N_frames, S, S, 3) uint8 array of
     io_compat.resize(data._rgb(frame), store_size, INTER_AREA) (rounded to a byte, zero-padded to a square), and out_dir/index.json
     (labels, names, first frame, frame count, picture rectangle, store_size).  Returns the index."""
     store_size = int(store_size)
     _check_sizes(store_size)
-    videos = FrameFolderVideos(root).videos
+    if layout not in PACK_LAYOUTS:
+        raise ValueError("layout is one of %s, got %r" % (PACK_LAYOUTS, layout))
+    videos = FrameFolderVideos(root).videos if layout == "label/video" else _walk_any(root)
     total = sum(len(paths) for _, _, paths in videos)
     os.makedirs(out_dir, exist_ok=True)
     # a raw file, not .npy: np.memmap reads it back with the index's shape
@@ -87,6 +115,28 @@ def draw_jitter(rnd=random, bright=64. / 255, contrast=0.25, sat=0.25, hue=0.04)
     return np.array([bf, cf, sf], np.float32), int(hf * 255)
 
 
+def _open_store(store_dir, image_size):
+    """What every data set over a store checks and opens -> (index, store_size, frames memmap (N, S, S, 3))."""
+    with open(os.path.join(store_dir, INDEX_FILE)) as f:
+        index = json.load(f)
+    if index.get("version") != STORE_VERSION:
+        raise ValueError("%s: store version %r, this code reads %d" % (store_dir, index.get("version"), STORE_VERSION))
+    s = int(index["store_size"])
+    _check_sizes(s, image_size)
+    if not index["videos"]:
+        raise FileNotFoundError("no videos in %r" % (store_dir,))
+    # the device shrinks the padded square, the host shrinks the picture and then centres it: the same thing only when the picture
+    # starts and ends on a k x k cell
+    k = s // image_size
+    for v in index["videos"]:
+        if any(x % k for x in v["valid"]):
+            raise ValueError("%s: video %s/%s has its picture at (y0, x0, h, w) = %s inside the %d x %d stored frame, not on multiples "
+                             "of store_size / image_size = %d: a %d x %d cell would mix picture and padding; pack at store_size == "
+                             "image_size" % (store_dir, v["label"], v["video"], tuple(v["valid"]), s, s, k, k, k))
+    frames = np.memmap(os.path.join(store_dir, FRAMES_FILE), dtype=np.uint8, mode="r", shape=(int(index["frames"]), s, s, 3))
+    return index, s, frames
+
+
 class PackedVideos(tdata.Dataset):
     """Item = (frames uint8 (T, S, S, 3), params float32[3] = (bf, cf, sf), hue_shift int32, label, name, valid int32[4]); with
     resident=True the first entry is the (T,) int32 rows of the store instead of their pixels (DevicePrep holds the store on the
@@ -94,28 +144,10 @@ class PackedVideos(tdata.Dataset):
     `self.jitter` False, which makes DevicePrep skip the jitter arithmetic altogether (PIL's HSV round trip is lossy even at shift 0)."""
 
     def __init__(self, store_dir, image_size=128, num_frames=40, sampling="uniform", mean=(0, 0, 0), jitter=False, resident=False):
-        with open(os.path.join(store_dir, INDEX_FILE)) as f:
-            self.index = json.load(f)
-        if self.index.get("version") != STORE_VERSION:
-            raise ValueError("%s: store version %r, this code reads %d" % (store_dir, self.index.get("version"), STORE_VERSION))
-        self.store_size = int(self.index["store_size"])
-        _check_sizes(self.store_size, int(image_size))
+        self.index, self.store_size, self.frames = _open_store(store_dir, int(image_size))
         self.image_size, self.num_frames, self.sampling, self.jitter, self.resident = int(image_size), num_frames, sampling, jitter, resident
         self.mean = np.asarray(mean, np.float32)
         self.videos = self.index["videos"]
-        if not self.videos:
-            raise FileNotFoundError("no videos in %r" % (store_dir,))
-        # the device shrinks the padded square, the host shrinks the picture and then centres it: the same thing only when the picture
-        # starts and ends on a k x k cell
-        k = self.store_size // self.image_size
-        for v in self.videos:
-            if any(x % k for x in v["valid"]):
-                raise ValueError("%s: video %s/%s has its picture at (y0, x0, h, w) = %s inside the %d x %d stored frame, not on multiples "
-                                 "of store_size / image_size = %d: a %d x %d cell would mix picture and padding; pack at store_size == "
-                                 "image_size" % (store_dir, v["label"], v["video"], tuple(v["valid"]), self.store_size, self.store_size,
-                                                 k, k, k))
-        s = self.store_size
-        self.frames = np.memmap(os.path.join(store_dir, FRAMES_FILE), dtype=np.uint8, mode="r", shape=(int(self.index["frames"]), s, s, 3))
 
     def __len__(self):
         return len(self.videos)
@@ -131,10 +163,9 @@ class PackedVideos(tdata.Dataset):
         return first, params, np.array(shift, np.int32), v["label"], "%s_%s" % (v["label"], v["video"]), np.asarray(v["valid"], np.int32)
 
 
-class DevicePrep:
-    """Callable on a collated PackedVideos batch: returns real_vids (B, 3, T, H, W) float32 on the device; the reference frame is
-    real_vids[:, :, 0].  Staged batches cross as bytes through two reused pinned buffers (non_blocking; a buffer is refilled only after
-    its last copy has finished); a resident dataset's store is uploaded here, once, and a batch is then a table of row numbers."""
+class _DeviceStore:
+    """What DevicePrep and DevicePairPrep share: the device, the resident store (uploaded here, once) and the staging of a batch's bytes
+    (_rows_of)."""
     _CHUNK = 1 << 28
 
     def __init__(self, dataset, device=None):
@@ -173,13 +204,73 @@ class DevicePrep:
         self._events[k].record()
         return dev
 
+    def _rows_of(self, first):
+        """A collated batch's first entry - (B, T) rows of the resident store, or (B, T, S, S, 3) bytes - as (store, rows (B, T) int32)."""
+        if self.ds.resident:
+            return self.store, first.to(torch.int32)
+        store = self._stage(first)
+        return store, torch.arange(first.shape[0] * first.shape[1], dtype=torch.int32).view(first.shape[0], first.shape[1])
+
+
+class DevicePrep(_DeviceStore):
+    """Callable on a collated PackedVideos batch: returns real_vids (B, 3, T, H, W) float32 on the device; the reference frame is
+    real_vids[:, :, 0].  Staged batches cross as bytes through two reused pinned buffers (non_blocking; a buffer is refilled only after
+    its last copy has finished); a resident dataset's store is uploaded here, once, and a batch is then a table of row numbers."""
+
     def __call__(self, batch):
         first, params, shift, valid = batch[0], batch[1], batch[2], batch[5]
-        if self.ds.resident:
-            store, rows = self.store, first.to(torch.int32)
-        else:
-            store = self._stage(first)
-            rows = torch.arange(first.shape[0] * first.shape[1], dtype=torch.int32).view(first.shape[0], first.shape[1])
+        store, rows = self._rows_of(first)
         jitter = bool(self.ds.jitter)
         return ops.video_prep(store, rows, params.to(torch.float32) if jitter else None, shift.to(torch.int32) if jitter else None,
                               self.ds.mean.tolist(), self.ds.image_size, jitter, valid=valid.to(torch.int32) if jitter else None)
+
+
+class PackedFramePairs(tdata.Dataset):
+    """LFAE stage-1 items over a store: lfae_train.FramePairs' draws, in its order and from its sources - the two frame numbers and the
+    two flips from FramePairs._generator (one generator per process and DataLoader worker, mixed with `seed`), the four jitter factors
+    from `random` with FramePairs' keys and defaults - over the videos of the store that have at least 2 frames, in index order.
+    Item = (first, params float32[3], hue_shift int32, flip int32, valid int32[4]): first is the two frames' bytes uint8 (2, S, S, 3),
+    or with resident=True their rows int32 (2,) of the store; the time flip has exchanged the two already, the horizontal flip is the
+    flag DevicePairPrep hands to the kernel.  No pixel arithmetic.  jitter: None, or the yaml's jitter_param dict."""
+    _generator = FramePairs._generator
+
+    def __init__(self, store_dir, frame_shape=128, horizontal_flip=True, time_flip=True, jitter=None, seed=None, resident=False):
+        self.index, self.store_size, self.frames = _open_store(store_dir, int(frame_shape))
+        self.frame_shape, self.resident = int(frame_shape), resident
+        self.horizontal_flip, self.time_flip, self.jitter = horizontal_flip, time_flip, jitter
+        self.seed = seed
+        self._rng, self._rng_key = None, None
+        self.videos = [v for v in self.index["videos"] if v["count"] >= 2]
+        if not self.videos:
+            raise FileNotFoundError("no videos with >= 2 frames in %r" % (store_dir,))
+
+    def __len__(self):
+        return len(self.videos)
+
+    def __getitem__(self, index):
+        v = self.videos[index]
+        rng = self._generator()
+        rows = v["first"] + np.sort(rng.choice(v["count"], size=2, replace=True))
+        if self.jitter:
+            params, shift = draw_jitter(random, bright=self.jitter.get("brightness", 0.1), contrast=self.jitter.get("contrast", 0.1),
+                                        sat=self.jitter.get("saturation", 0.1), hue=self.jitter.get("hue", 0.1))
+        else:
+            params, shift = np.ones(3, np.float32), 0
+        flip = int(bool(self.horizontal_flip and rng.random() < 0.5))
+        if self.time_flip and rng.random() < 0.5:
+            rows = rows[::-1]
+        first = np.ascontiguousarray(rows, np.int32) if self.resident else np.stack([self.frames[i] for i in rows])
+        return first, params, np.array(shift, np.int32), np.array(flip, np.int32), np.asarray(v["valid"], np.int32)
+
+
+class DevicePairPrep(_DeviceStore):
+    """Callable on a collated PackedFramePairs batch: returns {"source", "driving"}, (B, 3, H, W) float32 on the device - what
+    lfae_train.FramePairs' loader yields.  Staging and the resident store as DevicePrep's."""
+
+    def __call__(self, batch):
+        first, params, shift, flip, valid = batch
+        store, rows = self._rows_of(first)
+        jitter = bool(self.ds.jitter)
+        src, drv = ops.frame_pairs_prep(store, rows, params.to(torch.float32) if jitter else None, shift.to(torch.int32) if jitter else None,
+                                        flip.to(torch.int32), self.ds.frame_shape, jitter, valid=valid.to(torch.int32) if jitter else None)
+        return {"source": src, "driving": drv}

@@ -1051,6 +1051,19 @@ size_t lfdm_video_prep_ws_bytes(int batch, int frames);
 int lfdm_video_prep_u8(const unsigned char* store, int64_t store_frames, const int* frame_index, const float* params,
                        const int* hue_shift, const int* valid, const float* mean, float* out, int batch, int frames, int store_size,
                        int image_size, int jitter, int launches, void* ws, size_t ws_bytes, lfdm_stream_t stream);
+/* lfdm_frame_pairs_prep_u8 (additive under ABI 12): the same for LFAE stage-1 training pairs - what lfae_train.FramePairs makes of two
+ * frames of one video.  pair_index: DEVICE (batch, 2) int32 rows of store = (source, driving), checked BY THE CALLER like frame_index
+ * (the two may be equal, in any order).  source, driving: (batch, 3, H, H) planar fp32 each, frame t of item b goes to output t:
+ * fl32(avg / 255.f) - no mean.  params, hue_shift, valid as above: one jitter per pair, the contrast grey level m per frame (the stats
+ * launch above with two frames per item; ws: lfdm_video_prep_ws_bytes(batch, 2) bytes).  flip: DEVICE (batch) int32, never NULL; where
+ * flip[b] != 0 both frames of item b are mirrored left to right AFTER shrink and padding: out[y][x] = shrunk[y][H - 1 - x].  valid
+ * stays in unflipped store coordinates; the padding moves with the picture.  The thread for output pixels 4 g .. 4 g + 3 computes
+ * pixels H - 4 - 4 g .. H - 1 - 4 g exactly as without a flip and stores them in reversed order: whole dword loads and one 16-byte
+ * store per channel plane either way, no atomics, no LDS beyond the stats launch's. */
+/* Layout: store, pair_index, params, hue_shift, valid, flip dense; source, driving dense (batch, 3, H, H), 16 B each. */
+int lfdm_frame_pairs_prep_u8(const unsigned char* store, int64_t store_frames, const int* pair_index, const float* params,
+                             const int* hue_shift, const int* valid, const int* flip, float* source, float* driving, int batch,
+                             int store_size, int image_size, int jitter, void* ws, size_t ws_bytes, lfdm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Temporal resampling of a sampled flow latent (additive under ABI 12): frames at other instants than the sampled ones -

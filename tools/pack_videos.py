@@ -2,6 +2,8 @@
 """Decode a frame-folder data set ONCE into a packed uint8 store for `tools/train_dm.py --packed`.
 
     python tools/pack_videos.py ROOT OUT --store-size 128        # ROOT/<label>/<video>/*.jpg|png -> OUT/frames.u8 + OUT/index.json
+    python tools/pack_videos.py ROOT OUT --layout any            # every folder of frames at any depth (MUG's <subject>/<expression>/<take>,
+                                                                 # MHAD's / NATOPS' flat folders), for `tools/train_lfae.py --packed`
 
 --store-size is 1, 2 or 4 times the training size (--size of train_dm.py) and a multiple of 4.  Equal to the training size, the store
 holds exactly the bytes the host loader would feed the colour jitter when the sources are already that size; larger sources are
@@ -16,7 +18,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from cvpr23_lfdm_amd.video_store import pack_frame_folders  # noqa: E402
+from cvpr23_lfdm_amd.video_store import PACK_LAYOUTS, pack_frame_folders  # noqa: E402
 
 
 def main(argv=None):
@@ -24,8 +26,10 @@ def main(argv=None):
     ap.add_argument("root")
     ap.add_argument("out")
     ap.add_argument("--store-size", type=int, default=128)
+    ap.add_argument("--layout", choices=PACK_LAYOUTS, default=PACK_LAYOUTS[0], help="label/video: ROOT/<label>/<video>/ as the DM loader "
+                    "walks; any: every folder with frames at any depth, in the order lfae_train.FramePairs walks")
     args = ap.parse_args(argv)
-    index = pack_frame_folders(args.root, args.out, args.store_size)
+    index = pack_frame_folders(args.root, args.out, args.store_size, layout=args.layout)
     size = index["frames"] * index["store_size"] ** 2 * 3
     print("%d videos, %d frames at %d x %d: %.1f MB in %s" % (len(index["videos"]), index["frames"], index["store_size"],
                                                               index["store_size"], size / 1e6, args.out))
