@@ -122,6 +122,23 @@ class GridSampleParams(C.Structure):
     ]
 
 
+class KnownOperands(C.Structure):
+    _fields_ = [
+        ("known", f32p), ("known_noise", f32p), ("frame_mask", C.c_void_p), ("elem_mask", C.c_void_p), ("level", f32p),
+        ("frames", i32), ("frame_elems", i64),
+    ]
+
+
+class SamplerStepParams(C.Structure):
+    _fields_ = [
+        ("x", f32p), ("eps", f32p), ("noise", f32p), ("hist", f32p), ("seeds", C.c_void_p), ("window", C.c_void_p), ("x0_out", f32p),
+        ("batch", i32), ("n", i64), ("coef", f32p), ("step_dev", C.c_void_p), ("quantile", f32), ("advance", i32),
+        ("ws", C.c_void_p), ("ws_bytes", sz),
+        ("multistep", i32),
+        ("known", KnownOperands),
+    ]
+
+
 BN_TICKETS = 1024
 OPTIM_PLAN_BYTES = 64      # LFDM_OPTIM_PLAN_BYTES: lfdm_optim_plan = [apply i32 | - | clip_coef, total_norm, bias1, bias2_sqrt, ema_decay, 1 - ema_decay f32 | applied_steps, skipped_steps i64 | -]
 
@@ -177,30 +194,11 @@ _SIGNATURES = {
                                                  f32p, f32p, i32, i32, i32, stream_t]),
     "lfdm_sampler_ws_bytes": (sz, [i32, i64]),
     "lfdm_sampler_ws_init": (i32, [C.c_void_p, sz, i32, i64, stream_t]),
-    "lfdm_sampler_step_f32": (i32, [f32p, f32p, f32p, f32p, i32, i64, f32p, C.c_void_p, f32, i32,
-                                   C.c_void_p, sz, stream_t]),
-    "lfdm_sampler_step_ms_f32": (i32, [f32p, f32p, f32p, f32p, i32, i64, f32p, C.c_void_p, f32, i32,
-                                      C.c_void_p, sz, stream_t]),
-    "lfdm_sampler_step_known_f32": (i32, [f32p, f32p, f32p, f32p, i32, i64, f32p, C.c_void_p, f32, i32,
-                                         C.c_void_p, sz, f32p, f32p, C.c_void_p, f32p, i32, i64, stream_t]),
-    "lfdm_sampler_step_ms_known_f32": (i32, [f32p, f32p, f32p, f32p, i32, i64, f32p, C.c_void_p, f32, i32,
-                                            C.c_void_p, sz, f32p, f32p, C.c_void_p, f32p, i32, i64, stream_t]),
-    "lfdm_known_blend_f32": (i32, [f32p, f32p, f32p, C.c_void_p, f32, f32, i32, i64, i32, i64, stream_t]),
-    # ---- per-element known masks (additive, ABI stays 12)
-    "lfdm_sampler_step_elem_f32": (i32, [f32p, f32p, f32p, f32p, i32, i64, f32p, C.c_void_p, f32, i32,
-                                        C.c_void_p, sz, f32p, f32p, C.c_void_p, f32p, stream_t]),
-    "lfdm_sampler_step_ms_elem_f32": (i32, [f32p, f32p, f32p, f32p, i32, i64, f32p, C.c_void_p, f32, i32,
-                                           C.c_void_p, sz, f32p, f32p, C.c_void_p, f32p, stream_t]),
-    "lfdm_sampler_step_counter_elem_f32": (i32, [f32p, f32p, C.c_void_p, C.c_void_p, f32p, i32, i64, f32p, C.c_void_p, f32, i32,
-                                                C.c_void_p, sz, f32p, f32p, C.c_void_p, f32p, stream_t]),
-    "lfdm_known_blend_elem_f32": (i32, [f32p, f32p, f32p, C.c_void_p, f32, f32, i32, i64, stream_t]),
-    # ---- counter-based noise: fill kernels and the generating sampler step (additive, ABI stays 12)
+    "lfdm_sampler_step_f32": (i32, [C.POINTER(SamplerStepParams), stream_t]),
+    "lfdm_known_blend_f32": (i32, [f32p, C.POINTER(KnownOperands), f32, f32, i32, i64, stream_t]),
+    # ---- counter-based noise: fill kernels
     "lfdm_philox_normal_f32": (i32, [f32p, C.c_void_p, i32, i64, i64, C.c_uint, C.c_uint, C.c_uint, stream_t]),
     "lfdm_philox_bits_u32": (i32, [C.c_void_p, C.c_void_p, i32, i64, i64, C.c_uint, C.c_uint, C.c_uint, stream_t]),
-    "lfdm_sampler_step_counter_f32": (i32, [f32p, f32p, C.c_void_p, C.c_void_p, f32p, i32, i64, f32p, C.c_void_p, f32, i32,
-                                           C.c_void_p, sz, stream_t]),
-    "lfdm_sampler_step_counter_known_f32": (i32, [f32p, f32p, C.c_void_p, C.c_void_p, f32p, i32, i64, f32p, C.c_void_p, f32, i32,
-                                                 C.c_void_p, sz, f32p, f32p, C.c_void_p, f32p, i32, i64, stream_t]),
     "lfdm_cfg_combine_f32": (i32, [f32p, f32p, f32, f32p, i64, stream_t]),
     "lfdm_abs_quantile_f32": (i32, [f32p, i32, i64, f32, f32p, C.c_void_p, sz, stream_t]),
     "lfdm_warp_cl_f32": (i32, [C.POINTER(WarpParams), stream_t]),

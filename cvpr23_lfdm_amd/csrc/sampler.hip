@@ -196,6 +196,25 @@ __device__ float resolve_quantile(const unsigned* hs, Ranks rk, unsigned* s_part
   return rk.frac < 0.5f ? fmaf(rk.frac, d, lo) : fmaf(-d, 1.0f - rk.frac, hi);
 }
 
+// End-of-step housekeeping of both update kernels, by the workgroup that finishes last (every workgroup has read the histograms and the step
+// counter before it takes its ticket): clear the histograms for the next step and advance the step counter - two launches (zero_u32,
+// advance_step) of every replayed step otherwise.  The ticket word is left at zero again.  (all threads of a block)
+__device__ __forceinline__ void end_of_step(unsigned* ticket, unsigned* hists, int hist_samples, int32_t* advance_dev, unsigned* s_res) {
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned total = gridDim.x * gridDim.y;
+    const bool last = lfdm_ticket_take(ticket) == total - 1;
+    if (last) lfdm_ticket_reset(ticket);
+    s_res[0] = last ? 1u : 0u;
+  }
+  __syncthreads();
+  if (s_res[0]) {
+    const int64_t nz = (int64_t)hist_samples * HIST_PER_SAMPLE;
+    for (int64_t i = threadIdx.x; i < nz; i += 256) hists[i] = 0u;
+    if (advance_dev && threadIdx.x == 0) *advance_dev += 1;
+  }
+}
+
 __global__ __launch_bounds__(256) void quantile_out_kernel(Ranks rk, const unsigned* __restrict__ hists,
                                                            float* __restrict__ q_out) {
   __shared__ unsigned s_part[256], s_res[4];
@@ -204,9 +223,9 @@ __global__ __launch_bounds__(256) void quantile_out_kernel(Ranks rk, const unsig
   if (threadIdx.x == 0) q_out[b] = q;
 }
 
-// Known-frame conditioning (replacement method; lfdm_sampler_step_known_f32): the operands of the update kernels' KNOWN variant.
+// Known-frame conditioning (replacement method; lfdm_known_operands.frame_mask): the operands of the update kernels' KNOWN variant.
 // The plain instantiations carry the empty form as their last argument, so everything in front of it sits where it sat.
-// ELEM (lfdm_sampler_step_elem_f32): one mask byte per ELEMENT instead of one per frame - no frames, no frame_elems, no division.
+// ELEM (lfdm_known_operands.elem_mask): one mask byte per ELEMENT instead of one per frame - no frames, no frame_elems, no division.
 template <bool KNOWN, bool ELEM = false>
 struct KnownOps {};
 template <>
@@ -254,20 +273,29 @@ struct KnownPre {
   __device__ __forceinline__ float pick(int, float v) const { return v; }
   __device__ __forceinline__ float tail(const KnownOps<KNOWN, ELEM>&, int64_t, float v) { return v; }
 };
+// what the frame and the element form share: the level pair, the sample's offset and mask byte / known / known_noise of the PRE prefetched elements
 template <int PRE>
-struct KnownPre<true, false, PRE> {
+struct KnownPreBase {
   float a, s, kn[PRE], kz[PRE];
   unsigned mk[PRE];
   int64_t off;
+  __device__ __forceinline__ void head(const float* level, const int32_t* step_dev, int b, int64_t n) {
+    const float* lv = level + 2 * ((int64_t)(*step_dev) + 1);
+    a = lv[0];
+    s = lv[1];
+    off = (int64_t)b * n;
+  }
+  __device__ __forceinline__ float pick(int k, float v) const { return mk[k] ? a * kn[k] + s * kz[k] : v; }
+};
+template <int PRE>
+struct KnownPre<true, false, PRE> : KnownPreBase<PRE> {
+  using KnownPreBase<PRE>::a, KnownPreBase<PRE>::s, KnownPreBase<PRE>::kn, KnownPreBase<PRE>::kz, KnownPreBase<PRE>::mk, KnownPreBase<PRE>::off;
   const unsigned char* mb;
   // Frame of the thread's current element, kept incrementally: the thread walks i0, i0 + stride, ... (n < 2^24, 32-bit), so one division per
   // thread and one of the (uniform) stride replace a division and a modulo per element - sixteen of them stood in front of the prefetch loads.
   unsigned fr, rem, d_fr, d_rem;
   __device__ __forceinline__ void head(const KnownOps<true>& kf, const int32_t* step_dev, int b, int64_t n) {
-    const float* lv = kf.level + 2 * ((int64_t)(*step_dev) + 1);
-    a = lv[0];
-    s = lv[1];
-    off = (int64_t)b * n;
+    KnownPreBase<PRE>::head(kf.level, step_dev, b, n);
     mb = kf.mask + (int64_t)b * kf.frames;
     const unsigned i0 = blockIdx.x * 256u + threadIdx.x, stride = gridDim.x * 256u;
     fr = (i0 / kf.frame_elems) % kf.frames;
@@ -290,7 +318,6 @@ struct KnownPre<true, false, PRE> {
     kz[k] = in ? kf.known_noise[off + u] : 0.f;
     next(kf);
   }
-  __device__ __forceinline__ float pick(int k, float v) const { return mk[k] ? a * kn[k] + s * kz[k] : v; }
   __device__ __forceinline__ float tail(const KnownOps<true>& kf, int64_t i, float v) {
     if (mb[fr]) v = a * kf.known[off + i] + s * kf.known_noise[off + i];
     next(kf);
@@ -301,15 +328,10 @@ struct KnownPre<true, false, PRE> {
 // ELEM: the mask byte sits where the element sits - the frame variant's walk (fr, rem, next) has no counterpart, the byte is one more load of
 // the prefetch batch at the element's own index.
 template <int PRE>
-struct KnownPre<true, true, PRE> {
-  float a, s, kn[PRE], kz[PRE];
-  unsigned mk[PRE];
-  int64_t off;
+struct KnownPre<true, true, PRE> : KnownPreBase<PRE> {
+  using KnownPreBase<PRE>::a, KnownPreBase<PRE>::s, KnownPreBase<PRE>::kn, KnownPreBase<PRE>::kz, KnownPreBase<PRE>::mk, KnownPreBase<PRE>::off;
   __device__ __forceinline__ void head(const KnownOps<true, true>& kf, const int32_t* step_dev, int b, int64_t n) {
-    const float* lv = kf.level + 2 * ((int64_t)(*step_dev) + 1);
-    a = lv[0];
-    s = lv[1];
-    off = (int64_t)b * n;
+    KnownPreBase<PRE>::head(kf.level, step_dev, b, n);
   }
   __device__ __forceinline__ void load(const KnownOps<true, true>& kf, int k, bool in, int64_t i) {
     const unsigned u = in ? (unsigned)i : 0u;
@@ -317,14 +339,13 @@ struct KnownPre<true, true, PRE> {
     kn[k] = in ? kf.known[off + u] : 0.f;
     kz[k] = in ? kf.known_noise[off + u] : 0.f;
   }
-  __device__ __forceinline__ float pick(int k, float v) const { return mk[k] ? a * kn[k] + s * kz[k] : v; }
   __device__ __forceinline__ float tail(const KnownOps<true, true>& kf, int64_t i, float v) {
     if (kf.mask[off + i]) v = a * kf.known[off + i] + s * kf.known_noise[off + i];
     return v;
   }
 };
 
-// Counter-based step noise (lfdm_sampler_step_counter_f32): the operands of the update kernel's GENERATING variant, which
+// Counter-based step noise (lfdm_sampler_step_params.seeds / .window): the operands of the update kernel's GENERATING variant, which
 // computes noise[b, i] = lfdm_noise_element(seeds[b], i, step, 2, *window) in registers instead of loading it.  Empty for the loading variants.
 template <bool GEN>
 struct GenOps {};
@@ -412,6 +433,7 @@ __global__ __launch_bounds__(256) void sampler_update_kernel(float* __restrict__
       p_n[k] = (in && nb) ? nb[i] : 0.f;
     kp.load(kf, k, in, i);
   }
+  // (written out in both update kernels: behind a shared inline function three KNOWN instantiations schedule differently - DESIGN.md section 3)
   float s = 1.0f;                       // rk.frac < 0: static clipping, x0.clamp(-1, 1) (use_dynamic_thres=False, :729-732)
   if (rk.frac >= 0.f) {
     s = resolve_quantile(hists + (int64_t)b * HIST_PER_SAMPLE, rk, s_part, s_res);
@@ -446,25 +468,10 @@ __global__ __launch_bounds__(256) void sampler_update_kernel(float* __restrict__
     v = kp.tail(kf, i, v);
     xb[i] = v;
   }
-  // End-of-step housekeeping by the workgroup that finishes last (every workgroup has read the histograms and the step counter before
-  // it takes its ticket): clear the histograms for the next step and advance the step counter - two launches (zero_u32, advance_step)
-  // of every replayed step otherwise.  The ticket word is left at zero again.
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned total = gridDim.x * gridDim.y;
-    const bool last = lfdm_ticket_take(ticket) == total - 1;
-    if (last) lfdm_ticket_reset(ticket);
-    s_res[0] = last ? 1u : 0u;
-  }
-  __syncthreads();
-  if (s_res[0]) {
-    const int64_t nz = (int64_t)hist_samples * HIST_PER_SAMPLE;
-    for (int64_t i = threadIdx.x; i < nz; i += 256) hists[i] = 0u;
-    if (advance_dev && threadIdx.x == 0) *advance_dev += 1;
-  }
+  end_of_step(ticket, hists, hist_samples, advance_dev, s_res);
 }
 
-// Multistep form of the update (lfdm_sampler_step_ms_f32: DPM-Solver++ on the thresholded data prediction m = clamp(x0,-s,s)/s):
+// Multistep form of the update (lfdm_sampler_step_params.multistep: DPM-Solver++ on the thresholded data prediction m = clamp(x0,-s,s)/s):
 //   x <- k_x*x + k_m*m + k_prev*m_prev,   hist <- m       coef[step] = { c_x, c_eps, k_x, k_m, k_prev, - }
 // m_prev is the previous step's m, read from hist and replaced by this step's m by the same thread (one buffer suffices).  eps is not an
 // operand any more (pass 0 consumed it).  k_prev == 0 / k_x == 0 skip their operand: on a first-order step hist may be uninitialised
@@ -530,20 +537,7 @@ __global__ __launch_bounds__(256) void sampler_update_ms_kernel(float* __restric
     hb[i] = m;
     xb[i] = v;
   }
-  // end-of-step housekeeping by the workgroup that finishes last, exactly as in sampler_update_kernel
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned total = gridDim.x * gridDim.y;
-    const bool last = lfdm_ticket_take(ticket) == total - 1;
-    if (last) lfdm_ticket_reset(ticket);
-    s_res[0] = last ? 1u : 0u;
-  }
-  __syncthreads();
-  if (s_res[0]) {
-    const int64_t nz = (int64_t)hist_samples * HIST_PER_SAMPLE;
-    for (int64_t i = threadIdx.x; i < nz; i += 256) hists[i] = 0u;
-    if (advance_dev && threadIdx.x == 0) *advance_dev += 1;
-  }
+  end_of_step(ticket, hists, hist_samples, advance_dev, s_res);
 }
 
 // classifier-free guidance: out = null + (cond - null) * scale   (reference :525-526)
@@ -699,158 +693,6 @@ extern "C" int lfdm_abs_quantile_f32(const float* x, int batch, int64_t n, float
   return lfdm_check_launch("abs_quantile");
 }
 
-namespace {
-
-// argument check of the known-frame operands; on success fills kf
-int make_known(const char* what, const float* known, const float* known_noise, const unsigned char* frame_mask, const float* level,
-               int64_t n, int frames, int64_t frame_elems, KnownOps<true>* kf) {
-  if (!known || !known_noise || !frame_mask || !level)
-    return lfdm_fail(LFDM_EINVAL, "%s: known, known_noise, frame_mask and level must all be given", what);
-  if (frames <= 0 || frame_elems <= 0 || n <= 0 || n >= (1 << 24) || n % ((int64_t)frames * frame_elems) != 0)
-    return lfdm_fail(LFDM_EINVAL, "%s: n = %lld must be a multiple of frames * frame_elems = %d * %lld (n < 2^24)", what, (long long)n, frames, (long long)frame_elems);
-  kf->known = known;
-  kf->known_noise = known_noise;
-  kf->mask = frame_mask;
-  kf->level = level;
-  kf->frames = (unsigned)frames;
-  kf->frame_elems = (unsigned)frame_elems;
-  return 0;
-}
-
-// argument check of the element-mask operands (no frame split: the mask has n bytes per sample); on success fills kf
-int make_known_elem(const char* what, const float* known, const float* known_noise, const unsigned char* elem_mask, const float* level,
-                    int64_t n, KnownOps<true, true>* kf) {
-  if (!known || !known_noise || !elem_mask || !level)
-    return lfdm_fail(LFDM_EINVAL, "%s: known, known_noise, elem_mask and level must all be given", what);
-  if (n <= 0 || n >= (1 << 24))
-    return lfdm_fail(LFDM_EINVAL, "%s: n = %lld must lie in (0, 2^24)", what, (long long)n);
-  kf->known = known;
-  kf->known_noise = known_noise;
-  kf->mask = elem_mask;
-  kf->level = level;
-  return 0;
-}
-
-// The one launch sequence of every sampler step: [histogram clear for batch > 2] pass 0, two select passes, update.  MS: the multistep update
-// (second = hist) instead of the DDIM / DDPM one (second = noise); KNOWN: the update kernel's known-frame instantiation, ELEM: its element-mask one.
-template <bool MS, bool KNOWN, bool GEN = false, bool ELEM = false>
-int run_step(const char* what, float* x, const float* eps, float* second, float* x0_out, int batch, int64_t n, const float* coef,
-             int32_t* step_dev, float quantile, int advance, void* ws, size_t ws_bytes, KnownOps<KNOWN, ELEM> kf, hipStream_t stream,
-             GenOps<GEN> gen = GenOps<GEN>{}) {
-  static_assert(!(MS && GEN), "the multistep update draws nothing");
-  if (!x || !eps || (MS && !second) || !coef || !step_dev || batch <= 0 || n <= 0 || n >= (1 << 24))
-    return lfdm_fail(LFDM_EINVAL, "%s: bad arguments (n < 2^24)", what);
-  const SamplerWs w = carve_sampler_ws(ws, batch, n);
-  if (!ws || ws_bytes < w.bytes)
-    return lfdm_fail(LFDM_EWORKSPACE, "%s: workspace too small", what);
-  unsigned* hists = w.hists;
-  float* x0buf = w.x0buf;
-  unsigned* ticket = w.ticket;
-  const bool dynamic = quantile >= 0.f;           // quantile < 0: static clipping to [-1, 1] (GaussianDiffusion's own default)
-  if (dynamic && quantile > 1.f)
-    return lfdm_fail(LFDM_EINVAL, "%s: quantile must lie in [0, 1] (or be negative for the static clamp to [-1, 1])", what);
-  Ranks rk = make_ranks(n, dynamic ? quantile : 0.f);
-  if (!dynamic) rk.frac = -1.f;
-  // the histograms are clear on entry: lfdm_sampler_ws_init, then the last workgroup of every update kernel - for one or two samples
-  // (a single workgroup clearing more would lengthen the kernel's tail: larger batches keep the clearing launch)
-  const bool fold_clear = batch <= 2;
-  if (!fold_clear) clear_hists(hists, batch, stream);
-  const dim3 grid(blocks_for(n), batch), block(256);
-  LFDM_LAUNCH(quantile_pass0_kernel, grid, block, 0, stream, (const float*)x, eps, x0buf, n, coef,
-              (const int32_t*)step_dev, hists);         // (also the x0 = c_x*x - c_eps*eps pass: columns 0-1 of either table)
-  if (dynamic) run_select(x0buf, batch, n, rk, hists, stream);
-  if constexpr (MS)
-    LFDM_LAUNCH((sampler_update_ms_kernel<KNOWN, ELEM>), grid, block, 0, stream, x, second, (const float*)x0buf, x0_out, n, coef,
-                (const int32_t*)step_dev, rk, hists, fold_clear ? batch : 0, ticket, advance ? step_dev : (int32_t*)nullptr, kf);
-  else if constexpr (!MS)
-    LFDM_LAUNCH((sampler_update_kernel<KNOWN, GEN, ELEM>), grid, block, 0, stream, x, eps, (const float*)second, x0buf, x0_out, n, coef,
-                (const int32_t*)step_dev, rk, hists, fold_clear ? batch : 0, ticket, advance ? step_dev : (int32_t*)nullptr,
-                StepOps<KNOWN, GEN, ELEM>{kf, gen});
-  return lfdm_check_launch(what);
-}
-
-}  // namespace
-
-extern "C" int lfdm_sampler_step_f32(float* x, const float* eps, const float* noise, float* x0_out,
-                                     int batch, int64_t n, const float* coef, int32_t* step_dev,
-                                     float quantile, int advance, void* ws, size_t ws_bytes,
-                                     lfdm_stream_t stream_) {
-  return run_step<false, false>("sampler_step", x, eps, const_cast<float*>(noise), x0_out, batch, n, coef, step_dev, quantile, advance, ws,
-                                ws_bytes, KnownOps<false>{}, (hipStream_t)stream_);
-}
-
-extern "C" int lfdm_sampler_step_ms_f32(float* x, const float* eps, float* hist, float* x0_out, int batch, int64_t n,
-                                        const float* coef, int32_t* step_dev, float quantile, int advance, void* ws,
-                                        size_t ws_bytes, lfdm_stream_t stream_) {
-  return run_step<true, false>("sampler_step_ms", x, eps, hist, x0_out, batch, n, coef, step_dev, quantile, advance, ws, ws_bytes,
-                               KnownOps<false>{}, (hipStream_t)stream_);
-}
-
-extern "C" int lfdm_sampler_step_known_f32(float* x, const float* eps, const float* noise, float* x0_out, int batch, int64_t n,
-                                           const float* coef, int32_t* step_dev, float quantile, int advance, void* ws,
-                                           size_t ws_bytes, const float* known, const float* known_noise,
-                                           const unsigned char* frame_mask, const float* level, int frames, int64_t frame_elems,
-                                           lfdm_stream_t stream_) {
-  KnownOps<true> kf;
-  if (int rc = make_known("sampler_step_known", known, known_noise, frame_mask, level, n, frames, frame_elems, &kf)) return rc;
-  return run_step<false, true>("sampler_step_known", x, eps, const_cast<float*>(noise), x0_out, batch, n, coef, step_dev, quantile,
-                               advance, ws, ws_bytes, kf, (hipStream_t)stream_);
-}
-
-extern "C" int lfdm_sampler_step_ms_known_f32(float* x, const float* eps, float* hist, float* x0_out, int batch, int64_t n,
-                                              const float* coef, int32_t* step_dev, float quantile, int advance, void* ws,
-                                              size_t ws_bytes, const float* known, const float* known_noise,
-                                              const unsigned char* frame_mask, const float* level, int frames, int64_t frame_elems,
-                                              lfdm_stream_t stream_) {
-  KnownOps<true> kf;
-  if (int rc = make_known("sampler_step_ms_known", known, known_noise, frame_mask, level, n, frames, frame_elems, &kf)) return rc;
-  return run_step<true, true>("sampler_step_ms_known", x, eps, hist, x0_out, batch, n, coef, step_dev, quantile, advance, ws, ws_bytes, kf,
-                              (hipStream_t)stream_);
-}
-
-extern "C" int lfdm_known_blend_f32(float* x, const float* known, const float* known_noise, const unsigned char* frame_mask, float a,
-                                    float s, int batch, int64_t n, int frames, int64_t frame_elems, lfdm_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  KnownOps<true> kf;
-  if (!x || batch <= 0)
-    return lfdm_fail(LFDM_EINVAL, "known_blend: bad arguments");
-  if (int rc = make_known("known_blend", known, known_noise, frame_mask, /*level: not an operand*/ known, n, frames, frame_elems, &kf)) return rc;
-  LFDM_LAUNCH(known_blend_kernel, dim3(blocks_for(n), batch), dim3(256), 0, stream, x, known, known_noise, frame_mask, a, s, (unsigned)n,
-              kf.frames, kf.frame_elems);
-  return lfdm_check_launch("known_blend");
-}
-
-extern "C" int lfdm_sampler_step_elem_f32(float* x, const float* eps, const float* noise, float* x0_out, int batch, int64_t n,
-                                          const float* coef, int32_t* step_dev, float quantile, int advance, void* ws, size_t ws_bytes,
-                                          const float* known, const float* known_noise, const unsigned char* elem_mask, const float* level,
-                                          lfdm_stream_t stream_) {
-  KnownOps<true, true> kf;
-  if (int rc = make_known_elem("sampler_step_elem", known, known_noise, elem_mask, level, n, &kf)) return rc;
-  return run_step<false, true, false, true>("sampler_step_elem", x, eps, const_cast<float*>(noise), x0_out, batch, n, coef, step_dev, quantile,
-                                            advance, ws, ws_bytes, kf, (hipStream_t)stream_);
-}
-
-extern "C" int lfdm_sampler_step_ms_elem_f32(float* x, const float* eps, float* hist, float* x0_out, int batch, int64_t n, const float* coef,
-                                             int32_t* step_dev, float quantile, int advance, void* ws, size_t ws_bytes, const float* known,
-                                             const float* known_noise, const unsigned char* elem_mask, const float* level,
-                                             lfdm_stream_t stream_) {
-  KnownOps<true, true> kf;
-  if (int rc = make_known_elem("sampler_step_ms_elem", known, known_noise, elem_mask, level, n, &kf)) return rc;
-  return run_step<true, true, false, true>("sampler_step_ms_elem", x, eps, hist, x0_out, batch, n, coef, step_dev, quantile, advance, ws,
-                                           ws_bytes, kf, (hipStream_t)stream_);
-}
-
-extern "C" int lfdm_known_blend_elem_f32(float* x, const float* known, const float* known_noise, const unsigned char* elem_mask, float a,
-                                         float s, int batch, int64_t n, lfdm_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  KnownOps<true, true> kf;
-  if (!x || batch <= 0)
-    return lfdm_fail(LFDM_EINVAL, "known_blend_elem: bad arguments");
-  if (int rc = make_known_elem("known_blend_elem", known, known_noise, elem_mask, /*level: not an operand*/ known, n, &kf)) return rc;
-  LFDM_LAUNCH(known_blend_elem_kernel, dim3(blocks_for(n), batch), dim3(256), 0, stream, x, known, known_noise, elem_mask, a, s, (unsigned)n);
-  return lfdm_check_launch("known_blend_elem");
-}
-
 extern "C" int lfdm_philox_normal_f32(float* out, const uint64_t* seeds, int batch, int64_t n, int64_t row_stride, unsigned stream_id,
                                       unsigned step, unsigned window, lfdm_stream_t stream_) {
   return run_philox_fill<false>("philox_normal", out, seeds, batch, n, row_stride, stream_id, step, window, (hipStream_t)stream_);
@@ -862,46 +704,154 @@ extern "C" int lfdm_philox_bits_u32(uint32_t* out, const uint64_t* seeds, int ba
 }
 
 namespace {
-int make_gen(const char* what, const uint64_t* seeds, const uint32_t* window, GenOps<true>* gen) {
-  if (!seeds || !window) {
-    return lfdm_fail(LFDM_EINVAL, "%s: seeds (batch 64-bit words) and window (one 32-bit word) must both be given, on the device", what);
+
+// The one check of lfdm_known_operands, for the step (with_level) and the blend (host scalars: level is not looked at): the form the fields
+// select, or a refusal (negative).
+enum { KNOWN_NONE = 0, KNOWN_FRAME = 1, KNOWN_ELEM = 2 };
+int check_known(const char* what, const lfdm_known_operands& k, int64_t n, bool with_level) {
+  const bool mask = k.frame_mask || k.elem_mask, level = with_level && k.level;
+  if (!k.known && !k.known_noise && !mask && !level && !k.frames && !k.frame_elems) return KNOWN_NONE;
+  if (!k.known || !k.known_noise || !mask || (with_level && !k.level))
+    return lfdm_fail(LFDM_EINVAL, "%s: known, known_noise, a mask (frame_mask or elem_mask)%s must all be given", what, with_level ? " and level" : "");
+  if (k.frame_mask && k.elem_mask)
+    return lfdm_fail(LFDM_EINVAL, "%s: frame_mask and elem_mask exclude each other", what);
+  if (n <= 0 || n >= (1 << 24))
+    return lfdm_fail(LFDM_EINVAL, "%s: n = %lld must lie in (0, 2^24)", what, (long long)n);
+  if (k.elem_mask) {
+    if (k.frames || k.frame_elems)
+      return lfdm_fail(LFDM_EINVAL, "%s: elem_mask has no frame split (frames and frame_elems must be 0)", what);
+    return KNOWN_ELEM;
   }
-  gen->seeds = seeds;
-  gen->window = window;
-  return 0;
+  if (k.frames <= 0 || k.frame_elems <= 0 || k.frames > n || k.frame_elems > n || n % ((int64_t)k.frames * k.frame_elems) != 0)
+    return lfdm_fail(LFDM_EINVAL, "%s: n = %lld must be a multiple of frames * frame_elems = %d * %lld", what, (long long)n, k.frames, (long long)k.frame_elems);
+  return KNOWN_FRAME;
 }
+
+// The one check of the generating operands: 0 = the loading update, 1 = the generating one, or a refusal (negative).
+int check_gen(const char* what, const lfdm_sampler_step_params& p) {
+  if (!p.seeds && !p.window) return 0;
+  if (!p.seeds || !p.window)
+    return lfdm_fail(LFDM_EINVAL, "%s: seeds (batch 64-bit words) and window (one 32-bit word) must both be given, on the device", what);
+  if (p.multistep)
+    return lfdm_fail(LFDM_EINVAL, "%s: seeds with multistep: the multistep update draws nothing", what);
+  if (p.noise)
+    return lfdm_fail(LFDM_EINVAL, "%s: seeds (the noise is computed in the kernel) and noise exclude each other", what);
+  return 1;
+}
+
+template <bool KNOWN, bool ELEM>
+KnownOps<KNOWN, ELEM> known_ops(const lfdm_known_operands& k) {
+  KnownOps<KNOWN, ELEM> kf;
+  if constexpr (KNOWN) {
+    kf.known = k.known;
+    kf.known_noise = k.known_noise;
+    kf.mask = ELEM ? k.elem_mask : k.frame_mask;
+    kf.level = k.level;
+    if constexpr (!ELEM) {
+      kf.frames = (unsigned)k.frames;
+      kf.frame_elems = (unsigned)k.frame_elems;
+    }
+  }
+  return kf;
+}
+
+// what the update launch takes besides the caller's parameters
+struct UpdateLaunch {
+  dim3 grid;
+  float* x0buf;
+  Ranks rk;
+  unsigned* hists;
+  int hist_samples;
+  unsigned* ticket;
+  hipStream_t stream;
+};
+
+// MS: the multistep update (hist) instead of the DDIM / DDPM one (noise); KNOWN: the update kernel's known-frame instantiation, ELEM: its
+// element-mask one; GEN: the generating one.
+template <bool MS, bool KNOWN, bool GEN, bool ELEM>
+void launch_update(const lfdm_sampler_step_params& p, const UpdateLaunch& u) {
+  static_assert(!(MS && GEN), "the multistep update draws nothing");
+  const KnownOps<KNOWN, ELEM> kf = known_ops<KNOWN, ELEM>(p.known);
+  int32_t* advance_dev = p.advance ? p.step_dev : nullptr;
+  if constexpr (MS) {
+    LFDM_LAUNCH((sampler_update_ms_kernel<KNOWN, ELEM>), u.grid, dim3(256), 0, u.stream, p.x, p.hist, (const float*)u.x0buf, p.x0_out, p.n, p.coef,
+                (const int32_t*)p.step_dev, u.rk, u.hists, u.hist_samples, u.ticket, advance_dev, kf);
+  } else {
+    GenOps<GEN> gen;
+    if constexpr (GEN) {
+      gen.seeds = p.seeds;
+      gen.window = p.window;
+    }
+    LFDM_LAUNCH((sampler_update_kernel<KNOWN, GEN, ELEM>), u.grid, dim3(256), 0, u.stream, p.x, p.eps, p.noise, u.x0buf, p.x0_out, p.n,
+                p.coef, (const int32_t*)p.step_dev, u.rk, u.hists, u.hist_samples, u.ticket, advance_dev, StepOps<KNOWN, GEN, ELEM>{kf, gen});
+  }
+}
+
+// the nine instantiations in use: {plain, frame, element} x {DDIM / DDPM loading, DDIM / DDPM generating, multistep}
+template <bool KNOWN, bool ELEM>
+void launch_update(const lfdm_sampler_step_params& p, bool gen, const UpdateLaunch& u) {
+  if (p.multistep)
+    launch_update<true, KNOWN, false, ELEM>(p, u);
+  else if (gen)
+    launch_update<false, KNOWN, true, ELEM>(p, u);
+  else
+    launch_update<false, KNOWN, false, ELEM>(p, u);
+}
+
 }  // namespace
 
-extern "C" int lfdm_sampler_step_counter_f32(float* x, const float* eps, const uint64_t* seeds, const uint32_t* window, float* x0_out,
-                                             int batch, int64_t n, const float* coef, int32_t* step_dev, float quantile, int advance,
-                                             void* ws, size_t ws_bytes, lfdm_stream_t stream_) {
-  GenOps<true> gen;
-  if (int rc = make_gen("sampler_step_counter", seeds, window, &gen)) return rc;
-  return run_step<false, false, true>("sampler_step_counter", x, eps, nullptr, x0_out, batch, n, coef, step_dev, quantile, advance, ws,
-                                      ws_bytes, KnownOps<false>{}, (hipStream_t)stream_, gen);
+// The one launch sequence of every sampler step: [histogram clear for batch > 2] pass 0, two select passes, update.
+extern "C" int lfdm_sampler_step_f32(const lfdm_sampler_step_params* pp, lfdm_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const char* what = "sampler_step";
+  if (!pp) return lfdm_fail(LFDM_EINVAL, "%s: null parameters", what);
+  const lfdm_sampler_step_params& p = *pp;
+  const int gen = check_gen(what, p);
+  if (gen < 0) return gen;
+  const int known = check_known(what, p.known, p.n, true);
+  if (known < 0) return known;
+  if (!p.x || !p.eps || (p.multistep && !p.hist) || !p.coef || !p.step_dev || p.batch <= 0 || p.n <= 0 || p.n >= (1 << 24))
+    return lfdm_fail(LFDM_EINVAL, "%s: bad arguments (n < 2^24)", what);
+  const SamplerWs w = carve_sampler_ws(p.ws, p.batch, p.n);
+  if (!p.ws || p.ws_bytes < w.bytes)
+    return lfdm_fail(LFDM_EWORKSPACE, "%s: workspace too small", what);
+  const bool dynamic = p.quantile >= 0.f;         // quantile < 0: static clipping to [-1, 1] (GaussianDiffusion's own default)
+  if (dynamic && p.quantile > 1.f)
+    return lfdm_fail(LFDM_EINVAL, "%s: quantile must lie in [0, 1] (or be negative for the static clamp to [-1, 1])", what);
+  Ranks rk = make_ranks(p.n, dynamic ? p.quantile : 0.f);
+  if (!dynamic) rk.frac = -1.f;
+  // the histograms are clear on entry: lfdm_sampler_ws_init, then the last workgroup of every update kernel - for one or two samples
+  // (a single workgroup clearing more would lengthen the kernel's tail: larger batches keep the clearing launch)
+  const bool fold_clear = p.batch <= 2;
+  if (!fold_clear) clear_hists(w.hists, p.batch, stream);
+  const dim3 grid(blocks_for(p.n), p.batch), block(256);
+  LFDM_LAUNCH(quantile_pass0_kernel, grid, block, 0, stream, (const float*)p.x, p.eps, w.x0buf, p.n, p.coef,
+              (const int32_t*)p.step_dev, w.hists);     // (also the x0 = c_x*x - c_eps*eps pass: columns 0-1 of either table)
+  if (dynamic) run_select(w.x0buf, p.batch, p.n, rk, w.hists, stream);
+  const UpdateLaunch u = {grid, w.x0buf, rk, w.hists, fold_clear ? p.batch : 0, w.ticket, stream};
+  if (known == KNOWN_ELEM)
+    launch_update<true, true>(p, gen != 0, u);
+  else if (known == KNOWN_FRAME)
+    launch_update<true, false>(p, gen != 0, u);
+  else
+    launch_update<false, false>(p, gen != 0, u);
+  return lfdm_check_launch(what);
 }
 
-extern "C" int lfdm_sampler_step_counter_known_f32(float* x, const float* eps, const uint64_t* seeds, const uint32_t* window, float* x0_out,
-                                                   int batch, int64_t n, const float* coef, int32_t* step_dev, float quantile,
-                                                   int advance, void* ws, size_t ws_bytes, const float* known, const float* known_noise,
-                                                   const unsigned char* frame_mask, const float* level, int frames, int64_t frame_elems,
-                                                   lfdm_stream_t stream_) {
-  GenOps<true> gen;
-  if (int rc = make_gen("sampler_step_counter_known", seeds, window, &gen)) return rc;
-  KnownOps<true> kf;
-  if (int rc = make_known("sampler_step_counter_known", known, known_noise, frame_mask, level, n, frames, frame_elems, &kf)) return rc;
-  return run_step<false, true, true>("sampler_step_counter_known", x, eps, nullptr, x0_out, batch, n, coef, step_dev, quantile, advance,
-                                     ws, ws_bytes, kf, (hipStream_t)stream_, gen);
-}
-
-extern "C" int lfdm_sampler_step_counter_elem_f32(float* x, const float* eps, const uint64_t* seeds, const uint32_t* window, float* x0_out,
-                                                  int batch, int64_t n, const float* coef, int32_t* step_dev, float quantile, int advance,
-                                                  void* ws, size_t ws_bytes, const float* known, const float* known_noise,
-                                                  const unsigned char* elem_mask, const float* level, lfdm_stream_t stream_) {
-  GenOps<true> gen;
-  if (int rc = make_gen("sampler_step_counter_elem", seeds, window, &gen)) return rc;
-  KnownOps<true, true> kf;
-  if (int rc = make_known_elem("sampler_step_counter_elem", known, known_noise, elem_mask, level, n, &kf)) return rc;
-  return run_step<false, true, true, true>("sampler_step_counter_elem", x, eps, nullptr, x0_out, batch, n, coef, step_dev, quantile, advance,
-                                           ws, ws_bytes, kf, (hipStream_t)stream_, gen);
+extern "C" int lfdm_known_blend_f32(float* x, const lfdm_known_operands* k, float a, float s, int batch, int64_t n, lfdm_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!x || !k || batch <= 0)
+    return lfdm_fail(LFDM_EINVAL, "known_blend: bad arguments");
+  const int known = check_known("known_blend", *k, n, false);
+  if (known < 0) return known;
+  if (known == KNOWN_NONE)
+    return lfdm_fail(LFDM_EINVAL, "known_blend: known, known_noise and a mask (frame_mask or elem_mask) must all be given");
+  const dim3 grid(blocks_for(n), batch), block(256);
+  if (known == KNOWN_ELEM) {
+    LFDM_LAUNCH(known_blend_elem_kernel, grid, block, 0, stream, x, k->known, k->known_noise, k->elem_mask, a, s, (unsigned)n);
+  } else {
+    LFDM_LAUNCH(known_blend_kernel, grid, block, 0, stream, x, k->known, k->known_noise, k->frame_mask, a, s, (unsigned)n, (unsigned)k->frames,
+                (unsigned)k->frame_elems);
+  }
+  return lfdm_check_launch("known_blend");
 }

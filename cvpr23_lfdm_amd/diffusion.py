@@ -288,7 +288,7 @@ class GaussianDiffusion(nn.Module):
         return times, torch.stack(rows).float().contiguous(), draws
 
     def _ms_step_tables(self, sampler):
-        """Timestep list and the (steps, 6) table {c_x, c_eps, k_x, k_m, k_prev, 0} of lfdm_sampler_step_ms_f32 for "dpmpp_2m" / "dpmpp_1":
+        """Timestep list and the (steps, 6) table {c_x, c_eps, k_x, k_m, k_prev, 0} of the multistep lfdm_sampler_step_f32 for "dpmpp_2m" / "dpmpp_1":
             m_i = threshold(c_x x - c_eps eps);   x <- k_x x + k_m m_i + k_prev m_{i-1}
         Nodes: the DDIM grid `ddim_times()`.  The node at timestep `time` sits at a = alphas_cumprod[time] - the level the UNet is conditioned
         on and x0 is predicted with (c_x, c_eps: the same two buffers as `_step_tables`) - and the end of the last step (time_next = 0) at

@@ -905,68 +905,55 @@ def sampler_ws(batch, n, device):
     return ws
 
 
-def _known_operands(what, x, known, known_noise, frame_mask, level, frames, need_level=True):
-    """The known-frame operands of sampler_step / sampler_step_ms / known_blend: all of them or none.  -> None, or (frames, frame_elems) after
-    the shape / dtype checks (frame_mask: (B, frames) bool or uint8, used as bytes)."""
-    given = [known is not None, known_noise is not None, frame_mask is not None, frames is not None]
+def _known_operands(what, x, known, known_noise, frame_mask, level, frames, elem_mask, need_level=True):
+    """The known operands of sampler_step / sampler_step_ms / known_blend / known_blend_elem as the filled _native.KnownOperands (zeroed: no
+    conditioning): all of them or none, in ONE of the two forms - frame_mask (B, frames) with frames, or elem_mask of x's shape (one byte per
+    element); both masks are bool or uint8, used as bytes."""
+    k = _native.KnownOperands()
+    elem = elem_mask is not None
+    if elem and (frame_mask is not None or frames is not None):
+        raise ValueError("%s: elem_mask and frame_mask / frames exclude each other" % what)
+    operands = dict(known=known, known_noise=known_noise, **(dict(elem_mask=elem_mask) if elem else dict(frame_mask=frame_mask, frames=frames)))
     if need_level:
-        given.append(level is not None)
-    if not any(given):
-        return None
-    if not all(given):
-        raise ValueError("%s: known, known_noise, frame_mask, %sframes go together (all of them or none)" % (what, "level, " if need_level else ""))
+        operands["level"] = level
+    if all(v is None for v in operands.values()):
+        return k
+    if any(v is None for v in operands.values()):
+        raise ValueError("%s: %s go together (all of them or none)" % (what, ", ".join(operands)))
     batch = x.shape[0]
     n = x.numel() // batch
-    frames = int(frames)
-    if frames < 1 or n % frames != 0:
-        raise ValueError("%s: frames = %d does not divide the sample's %d elements" % (what, frames, n))
-    if x.dim() >= 4:                                     # planar (B, C, T, ...): a frame is everything behind T
-        if x.shape[2] != frames:
-            raise ValueError("%s: x has %d frames, frames = %d" % (what, x.shape[2], frames))
-        frame_elems = x[0, 0, 0].numel()
-    elif x.dim() == 3:                                   # (B, C * T, hw)
-        frame_elems = x.shape[2]
+    for name, t in (("known", known), ("known_noise", known_noise)):
+        if t.dtype != torch.float32 or t.numel() != x.numel() or not t.is_contiguous() or t.device != x.device:
+            raise ValueError("%s: %s must be a contiguous float32 tensor of x's %d elements on x's device" % (what, name, x.numel()))
+    if need_level and (level.dtype != torch.float32 or level.dim() != 2 or level.shape[1] != 2 or not level.is_contiguous()
+                       or level.device != x.device):
+        raise ValueError("%s: level must be a contiguous (steps + 1, 2) float32 tensor on x's device" % what)
+    mask = elem_mask if elem else frame_mask
+    if mask.dtype not in (torch.bool, torch.uint8) or not mask.is_contiguous() or mask.device != x.device:
+        raise ValueError("%s: the mask must be a contiguous bool / uint8 tensor on x's device" % what)
+    if elem:
+        if tuple(elem_mask.shape) != tuple(x.shape):
+            raise ValueError("%s: elem_mask must have x's shape %s, got %s" % (what, tuple(x.shape), tuple(elem_mask.shape)))
+        k.elem_mask = _p(elem_mask)
     else:
-        raise ValueError("%s: x must be (B, C, T, ...) or (B, C * T, hw) for known frames" % what)
-    if n % (frames * frame_elems) != 0:
-        raise ValueError("%s: %d elements per sample are no multiple of %d frames x %d" % (what, n, frames, frame_elems))
-    for name, t in (("known", known), ("known_noise", known_noise)):
-        if t.dtype != torch.float32 or t.numel() != x.numel() or not t.is_contiguous() or t.device != x.device:
-            raise ValueError("%s: %s must be a contiguous float32 tensor of x's %d elements on x's device" % (what, name, x.numel()))
-    if frame_mask.dtype not in (torch.bool, torch.uint8) or tuple(frame_mask.shape) != (batch, frames) or not frame_mask.is_contiguous() \
-            or frame_mask.device != x.device:
-        raise ValueError("%s: frame_mask must be a contiguous (%d, %d) bool / uint8 tensor on x's device" % (what, batch, frames))
-    if need_level and (level.dtype != torch.float32 or level.dim() != 2 or level.shape[1] != 2 or not level.is_contiguous()
-                       or level.device != x.device):
-        raise ValueError("%s: level must be a contiguous (steps + 1, 2) float32 tensor on x's device" % what)
-    return frames, frame_elems
-
-
-def _known_elem_operands(what, x, known, known_noise, elem_mask, level, need_level=True):
-    """The element-mask form of the known operands: known, known_noise, elem_mask [, level], all of them.  elem_mask: bool /
-    uint8 with x's shape (one byte per element).  -> the marker "elem" that `_sampler_step` takes in place of (frames, frame_elems)."""
-    given = [known is not None, known_noise is not None] + ([level is not None] if need_level else [])
-    if not all(given):
-        raise ValueError("%s: known, known_noise, elem_mask%s go together (all of them or none)" % (what, ", level" if need_level else ""))
-    for name, t in (("known", known), ("known_noise", known_noise)):
-        if t.dtype != torch.float32 or t.numel() != x.numel() or not t.is_contiguous() or t.device != x.device:
-            raise ValueError("%s: %s must be a contiguous float32 tensor of x's %d elements on x's device" % (what, name, x.numel()))
-    if elem_mask.dtype not in (torch.bool, torch.uint8) or tuple(elem_mask.shape) != tuple(x.shape) or not elem_mask.is_contiguous() \
-            or elem_mask.device != x.device:
-        raise ValueError("%s: elem_mask must be a contiguous bool / uint8 tensor of x's shape %s on x's device" % (what, tuple(x.shape)))
-    if need_level and (level.dtype != torch.float32 or level.dim() != 2 or level.shape[1] != 2 or not level.is_contiguous()
-                       or level.device != x.device):
-        raise ValueError("%s: level must be a contiguous (steps + 1, 2) float32 tensor on x's device" % what)
-    return "elem"
-
-
-def _known_either(what, x, known, known_noise, frame_mask, level, frames, elem_mask):
-    """frame_mask= / frames= or elem_mask=: one of the two forms, never both."""
-    if elem_mask is None:
-        return _known_operands(what, x, known, known_noise, frame_mask, level, frames), frame_mask
-    if frame_mask is not None or frames is not None:
-        raise ValueError("%s: elem_mask and frame_mask / frames exclude each other" % what)
-    return _known_elem_operands(what, x, known, known_noise, elem_mask, level), elem_mask
+        frames = int(frames)
+        if frames < 1 or n % frames != 0:
+            raise ValueError("%s: frames = %d does not divide the sample's %d elements" % (what, frames, n))
+        if x.dim() >= 4:                                     # planar (B, C, T, ...): a frame is everything behind T
+            if x.shape[2] != frames:
+                raise ValueError("%s: x has %d frames, frames = %d" % (what, x.shape[2], frames))
+            frame_elems = x[0, 0, 0].numel()
+        elif x.dim() == 3:                                   # (B, C * T, hw)
+            frame_elems = x.shape[2]
+        else:
+            raise ValueError("%s: x must be (B, C, T, ...) or (B, C * T, hw) for known frames" % what)
+        if n % (frames * frame_elems) != 0:
+            raise ValueError("%s: %d elements per sample are no multiple of %d frames x %d" % (what, n, frames, frame_elems))
+        if tuple(frame_mask.shape) != (batch, frames):
+            raise ValueError("%s: frame_mask must be (%d, %d), got %s" % (what, batch, frames, tuple(frame_mask.shape)))
+        k.frame_mask, k.frames, k.frame_elems = _p(frame_mask), frames, frame_elems
+    k.known, k.known_noise, k.level = _p(known), _p(known_noise), _p(level) if need_level else None
+    return k
 
 
 NOISE_STREAM_XT, NOISE_STREAM_KNOWN, NOISE_STREAM_STEP = 0, 1, 2       # counter word `stream` of the counter-based noise (csrc/lfdm_philox.h)
@@ -1043,96 +1030,76 @@ def philox_bits(out, seeds, *, stream, step=0, window=0):
     return _philox_fill("philox_bits", out, seeds, stream, step, window)
 
 
-_SAMPLER_STEP = {      # (multistep, counter noise, known frames) -> C entry point
-    (False, False, False): "lfdm_sampler_step_f32", (False, False, True): "lfdm_sampler_step_known_f32",
-    (False, True, False): "lfdm_sampler_step_counter_f32", (False, True, True): "lfdm_sampler_step_counter_known_f32",
-    (True, False, False): "lfdm_sampler_step_ms_f32", (True, False, True): "lfdm_sampler_step_ms_known_f32",
-    (False, False, "elem"): "lfdm_sampler_step_elem_f32", (False, True, "elem"): "lfdm_sampler_step_counter_elem_f32",
-    (True, False, "elem"): "lfdm_sampler_step_ms_elem_f32"}
-
-
-def _sampler_step(lib, multistep, x, eps, third, coef, step_dev, quantile, advance, x0_out, ws, kf, known_operands, seeds=None, window=None):
-    """The one call behind sampler_step / sampler_step_ms (operands already checked): the common argument list, with (seeds, window) in
-    place of the third tensor (noise / hist) in counter mode and the known-frame tail when kf = (frames, frame_elems) is given - or the
-    element-mask tail (no frame split) when kf = "elem"."""
+def _sampler_step(lib, x, eps, coef, step_dev, quantile, advance, x0_out, ws, known, **operands):
+    """The one call behind sampler_step / sampler_step_ms (operands already checked): fills lfdm_sampler_step_params - `known` the checked
+    KnownOperands, `operands` the fields that select the update (noise | hist, multistep | seeds, window)."""
     batch = x.shape[0]
+    n = x.numel() // batch
     if ws is None:
-        ws = sampler_ws(batch, x.numel() // batch, x.device)
-    name = _SAMPLER_STEP[(multistep, seeds is not None, "elem" if kf == "elem" else kf is not None)]
-    args = [_p(x), _p(eps)] + ([_p(third)] if seeds is None else [_p(seeds), _p(window)])
-    args += [_p(x0_out), batch, x.numel() // batch, _p(coef), _p(step_dev), quantile, int(advance), _p(ws), ws.numel() * 4]
-    if kf is not None:
-        args += [_p(t) for t in known_operands] + ([] if kf == "elem" else [kf[0], kf[1]])
-    lib.check(getattr(lib, name)(*args, _stream(lib)), name)
+        ws = sampler_ws(batch, n, x.device)
+    p = _native.SamplerStepParams(x=_p(x), eps=_p(eps), x0_out=_p(x0_out), batch=batch, n=n, coef=_p(coef), step_dev=_p(step_dev),
+                                  quantile=quantile, advance=int(advance), ws=_p(ws), ws_bytes=ws.numel() * 4, known=known, **operands)
+    lib.check(lib.lfdm_sampler_step_f32(C.byref(p), _stream(lib)), "lfdm_sampler_step_f32")
     return x
 
 
 def sampler_step(x, eps, noise, coef, step_dev, *, quantile=0.9, advance=True, x0_out=None, ws=None,
                  known=None, known_noise=None, frame_mask=None, level=None, frames=None, seeds=None, window=None, elem_mask=None):
-    """lfdm_sampler_step_f32; with the five known-frame keywords (all or none) lfdm_sampler_step_known_f32: frames whose frame_mask[b, t] is set
+    """lfdm_sampler_step_f32, the DDIM / DDPM update.  With the five known-frame keywords (all or none): frames whose frame_mask[b, t] is set
     are stored as level[step + 1] = (a, s) applied to (known, known_noise) instead of the update's result.
-    seeds (int64 device tensor (B), ops.seeds_tensor) + window (int32 device tensor of one word), both or none, with noise=None:
-    lfdm_sampler_step_counter_f32 / _known_f32 - the step noise is computed inside the update kernel from (seeds[b], window, step) and is
-    bit for bit what philox_normal(stream=2, step=the step counter's value, window=window) writes.
-    elem_mask (bool / uint8 of x's shape) in place of frame_mask / frames: lfdm_sampler_step_elem_f32 / _counter_elem_f32 - one mask byte per
-    element; passing both forms is refused."""
+    seeds (int64 device tensor (B), ops.seeds_tensor) + window (int32 device tensor of one word), both or none, with noise=None: the step
+    noise is computed inside the update kernel from (seeds[b], window, step) and is bit for bit what
+    philox_normal(stream=2, step=the step counter's value, window=window) writes.
+    elem_mask (bool / uint8 of x's shape) in place of frame_mask / frames: one mask byte per element; passing both forms is
+    refused."""
     lib = _lib()
     _chk(lib, x, eps, noise, coef, step_dev, x0_out, ws)
-    kf, mask = _known_either("sampler_step", x, known, known_noise, frame_mask, level, frames, elem_mask)
-    batch = x.shape[0]
+    k = _known_operands("sampler_step", x, known, known_noise, frame_mask, level, frames, elem_mask)
     if (seeds is None) != (window is None):
         raise ValueError("sampler_step: seeds and window go together (both or none)")
     if seeds is not None and noise is not None:
         raise ValueError("sampler_step: seeds (noise computed in the kernel) and a noise tensor exclude each other")
     if seeds is not None:
-        seeds = _seed_operand("sampler_step", lib, seeds, batch, x.device)
+        seeds = _seed_operand("sampler_step", lib, seeds, x.shape[0], x.device)
         if not torch.is_tensor(window) or window.dtype != torch.int32 or window.numel() != 1 or window.device != x.device:
             raise ValueError("sampler_step: window must be an int32 tensor of one word on x's device")
-    return _sampler_step(lib, False, x, eps, noise, coef, step_dev, quantile, advance, x0_out, ws, kf, (known, known_noise, mask, level), seeds, window)
+    return _sampler_step(lib, x, eps, coef, step_dev, quantile, advance, x0_out, ws, k, noise=_p(noise), seeds=_p(seeds), window=_p(window))
 
 
 def sampler_step_ms(x, eps, hist, coef, step_dev, *, quantile=0.9, advance=True, x0_out=None, ws=None,
                     known=None, known_noise=None, frame_mask=None, level=None, frames=None, elem_mask=None):
-    """lfdm_sampler_step_ms_f32: x <- k_x*x + k_m*m + k_prev*hist, hist <- m (the thresholded data prediction of this step);
-    coef rows {c_x, c_eps, k_x, k_m, k_prev, 0} (GaussianDiffusion._ms_step_tables).  Known-frame keywords as sampler_step
-    (lfdm_sampler_step_ms_known_f32; elem_mask=: lfdm_sampler_step_ms_elem_f32)."""
+    """lfdm_sampler_step_f32 with multistep set: x <- k_x*x + k_m*m + k_prev*hist, hist <- m (the thresholded data prediction of this step);
+    coef rows {c_x, c_eps, k_x, k_m, k_prev, 0} (GaussianDiffusion._ms_step_tables).  Known-frame keywords as sampler_step."""
     lib = _lib()
     _chk(lib, x, eps, hist, coef, step_dev, x0_out, ws)
-    kf, mask = _known_either("sampler_step_ms", x, known, known_noise, frame_mask, level, frames, elem_mask)
-    batch = x.shape[0]
+    k = _known_operands("sampler_step_ms", x, known, known_noise, frame_mask, level, frames, elem_mask)
     if hist.numel() != x.numel():
         raise ValueError("sampler_step_ms: hist must have x's %d elements, got %d" % (x.numel(), hist.numel()))
-    return _sampler_step(lib, True, x, eps, hist, coef, step_dev, quantile, advance, x0_out, ws, kf, (known, known_noise, mask, level))
+    return _sampler_step(lib, x, eps, coef, step_dev, quantile, advance, x0_out, ws, k, hist=_p(hist), multistep=1)
+
+
+def _known_blend(what, x, a, s, known, known_noise, **mask):
+    lib = _lib()
+    _chk(lib, x, known, known_noise)
+    if known is None or known_noise is None or any(v is None for v in mask.values()):
+        raise ValueError("%s: known, known_noise and %s are required" % (what, " and ".join(mask)))
+    k = _known_operands(what, x, known, known_noise, mask.get("frame_mask"), None, mask.get("frames"), mask.get("elem_mask"), need_level=False)
+    batch = x.shape[0]
+    lib.check(lib.lfdm_known_blend_f32(_p(x), C.byref(k), float(a), float(s), batch, x.numel() // batch, _stream(lib)), "lfdm_known_blend_f32")
+    return x
 
 
 def known_blend(x, known, known_noise, frame_mask, a, s, frames):
     """lfdm_known_blend_f32: x[b, :, t] <- a * known + s * known_noise where frame_mask[b, t] (the x_T blend of a conditioned video)."""
-    lib = _lib()
-    _chk(lib, x, known, known_noise)
-    if known is None or known_noise is None or frame_mask is None:
-        raise ValueError("known_blend: known, known_noise and frame_mask are required")
-    fr, frame_elems = _known_operands("known_blend", x, known, known_noise, frame_mask, None, frames, need_level=False)
-    batch = x.shape[0]
-    lib.check(lib.lfdm_known_blend_f32(_p(x), _p(known), _p(known_noise), _p(frame_mask), float(a), float(s), batch, x.numel() // batch,
-                                       fr, frame_elems, _stream(lib)), "lfdm_known_blend_f32")
-    return x
+    return _known_blend("known_blend", x, a, s, known, known_noise, frame_mask=frame_mask, frames=frames)
 
 
 def known_blend_elem(x, known, known_noise, elem_mask, a, s):
-    """lfdm_known_blend_elem_f32: x[e] <- a * known[e] + s * known_noise[e] where elem_mask[e] (bool / uint8 of x's shape): the x_T blend of an
-    element-conditioned video and, with an all-True mask, the entry of a schedule on a given latent."""
-    lib = _lib()
-    _chk(lib, x, known, known_noise)
-    if known is None or known_noise is None or elem_mask is None:
-        raise ValueError("known_blend_elem: known, known_noise and elem_mask are required")
-    _known_elem_operands("known_blend_elem", x, known, known_noise, elem_mask, None, need_level=False)
-    for t in (known, known_noise):
-        if t.data_ptr() == x.data_ptr():
-            raise ValueError("known_blend_elem: x must not alias known or known_noise")
-    batch = x.shape[0]
-    lib.check(lib.lfdm_known_blend_elem_f32(_p(x), _p(known), _p(known_noise), _p(elem_mask), float(a), float(s), batch, x.numel() // batch,
-                                            _stream(lib)), "lfdm_known_blend_elem_f32")
-    return x
+    """lfdm_known_blend_f32 with an element mask: x[e] <- a * known[e] + s * known_noise[e] where elem_mask[e] (bool / uint8 of x's shape): the
+    x_T blend of an element-conditioned video and, with an all-True mask, the entry of a schedule on a given latent."""
+    if any(t is not None and t.data_ptr() == x.data_ptr() for t in (known, known_noise)):
+        raise ValueError("known_blend_elem: x must not alias known or known_noise")
+    return _known_blend("known_blend_elem", x, a, s, known, known_noise, elem_mask=elem_mask)
 
 
 def cfg_combine(cond_eps, null_eps, scale, out):

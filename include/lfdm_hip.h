@@ -331,76 +331,71 @@ int lfdm_heads_gn_res_cl_to_planar_f32(const float* y, int ld, int channels, con
 /* ------------------------------------------------------------------------------------------
  * Sampler step (GaussianDiffusion.ddim_sample :791-827 / p_sample :737-746): predict x0
  * (:697-701), dynamic threshold = per-sample 0.9-quantile of |x0| with linear interpolation,
- * clamp and divide (:805-818), then the DDIM or DDPM update.  Coefficients come from a device
- * table indexed by a device step counter, so the whole step can be replayed from a hipGraph:
- *   coef[step] = { c_x (sqrt_recip_alphas_cumprod), c_eps (sqrt_recipm1_alphas_cumprod),
- *                  k_x0, k_eps, k_x, k_noise }:  x <- k_x0*x0 + k_eps*eps + k_x*x + k_noise*noise
- * quantile < 0 selects the static branch of the reference instead (use_dynamic_thres=False: x0.clamp(-1, 1), :729-732).
- * x (in/out), eps, noise: planar (B, n) with n = 3*T*S*S. x0_out optional (B, n).
- * ws: lfdm_sampler_ws_bytes(batch, n), and it MUST have been cleared once by lfdm_sampler_ws_init (ABI >= 4): the step relies on
- * histograms and an end-of-step ticket word that every step leaves zeroed for the next one.  A workspace that was never initialised
- * (e.g. fresh uninitialised memory) gives wrong dynamic thresholds and a step counter that never advances - and no error code: the
- * library cannot look into device memory without a synchronisation.  advance != 0 increments *step_dev at the end.
+ * clamp and divide (:805-818), then the update.  Coefficients come from a device table indexed
+ * by a device step counter, so the whole step can be replayed from a hipGraph:
+ *   x0 = c_x*x - c_eps*eps;  s = max(1, quantile(|x0|) per sample);  m = clamp(x0, -s, s) / s
+ *   DDIM / DDPM:  coef[step] = { c_x, c_eps, k_x0, k_eps, k_x, k_noise }:  x <- k_x0*m + k_eps*eps + k_x*x + k_noise*noise
+ *   multistep:    coef[step] = { c_x, c_eps, k_x, k_m, k_prev, unused }:   x <- k_x*x + k_m*m + k_prev*hist;  hist <- m
+ * (c_x = sqrt_recip_alphas_cumprod, c_eps = sqrt_recipm1_alphas_cumprod; multistep = DPM-Solver++, Lu et al. 2022, "2M" and its first-order
+ * form, on the THRESHOLDED data prediction).  A coefficient that is exactly 0 skips its operand.
+ * One entry point, one parameter struct (ABI version 13; it replaces the nine positional lfdm_sampler_step_*_f32 forms of ABI 12 - migration
+ * table in INTEGRATION.md).  Which of the update kernel's instantiations runs follows from the fields that are set; the launch sequence
+ * (histogram clear for batch > 2, x0 pass, two select passes, update) is the same for all of them.
+ * Refusals (LFDM_EINVAL, nothing is enqueued): a null required operand or n outside (0, 2^24); exactly one of seeds / window; seeds with
+ * noise; seeds with multistep (the multistep update draws nothing); in `known`: some but not all of known / known_noise / a mask / level,
+ * both masks (they exclude each other), elem_mask with frames or frame_elems set, a frame split that does not divide n.
  */
+/* Known content for the replacement method (per element 4.11): the final store of x is replaced, where a byte mask marks it, by
+ *   x[b, i] <- a * known[b, i] + s * known_noise[b, i],   (a, s) = level[2 * (step + 1)]
+ * It is a select, never a blend: known / known_noise at unmarked positions are never read into a result and may be NaN or uninitialised.  x0, the
+ * threshold (over the whole sample), x0_out, hist and the step counter are exactly what the unconditioned step computes.
+ * All zero = no conditioning.  Otherwise known, known_noise, level and exactly ONE of the masks. */
+typedef struct lfdm_known_operands {
+  const float* known;               /* dense (B, n) */
+  const float* known_noise;         /* dense (B, n) */
+  const unsigned char* frame_mask;  /* frame form: dense (B, frames) bytes, non-zero = frame (i / frame_elems) % frames of sample b is known */
+  const unsigned char* elem_mask;   /* element form: dense (B, n) bytes, non-zero = element i of sample b is known (any subset: a region, a channel, a pixel) */
+  const float* level;               /* dense (steps + 1, 2) on the device: row 0 = the level of x_T, row i + 1 = (a, s) after step i; indexed by the
+                                       step counter like coef, read before it is advanced.  Not an operand of lfdm_known_blend_f32 (leave NULL) */
+  int frames;                       /* frame form only (0 with elem_mask): n must be a multiple of frames * frame_elems */
+  int64_t frame_elems;              /* frame form only: elements per frame (planar (C, T, S, S): S * S) */
+} lfdm_known_operands;
+typedef struct lfdm_sampler_step_params {
+  float* x;                /* dense planar (B, n), n = 3*T*S*S; in/out */
+  const float* eps;        /* dense (B, n): the model's prediction */
+  const float* noise;      /* dense (B, n) or NULL (no noise term); must be NULL with seeds; ignored with multistep */
+  float* hist;             /* multistep only, dense (B, n), in/out: m of the previous step on entry, m of this step on return (each element is
+                              read, then written, by one thread; it must not alias x, eps or x0_out).  A first-order row (k_prev == 0: the first and
+                              the last step of a video) may be handed UNINITIALISED memory, NaNs included */
+  const uint64_t* seeds;   /* counter-based step noise, with window or not at all: `batch` 64-bit words on the device.  The noise term
+                              is computed inside the update kernel, noise[b, i] = z of (seeds[b], counter (i >> 2, *step_dev, 2, *window)), element
+                              i & 3 of its quad - bit for bit what lfdm_philox_normal_f32 writes for stream_id 2, step = *step_dev */
+  const uint32_t* window;  /* one 32-bit word on the device: the window number (0 for one video); one captured graph serves every seed and window */
+  float* x0_out;           /* NULL or dense (B, n): receives m */
+  int batch;
+  int64_t n;               /* elements per sample, 0 < n < 2^24 */
+  const float* coef;       /* dense (steps, 6) on the device, rows as above */
+  int32_t* step_dev;       /* the device step counter: row index of coef and level */
+  float quantile;          /* in [0, 1]; negative = the static branch of the reference (use_dynamic_thres=False: x0.clamp(-1, 1), :729-732) */
+  int advance;             /* != 0: the step increments *step_dev at its end */
+  void* ws;                /* lfdm_sampler_ws_bytes, and it MUST have been cleared once by lfdm_sampler_ws_init: the step relies on histograms and an
+                              end-of-step ticket word that every step leaves zeroed for the next one.  A workspace that was never initialised gives
+                              wrong dynamic thresholds and a step counter that never advances - and no error code: the library cannot look into
+                              device memory without a synchronisation.  One workspace may serve every form of the step */
+  size_t ws_bytes;
+  int multistep;           /* != 0: the multistep update (hist required); seeds is refused */
+  lfdm_known_operands known;
+} lfdm_sampler_step_params;
 size_t lfdm_sampler_ws_bytes(int batch, int64_t n);
 /* once per workspace, before its first lfdm_sampler_step_f32: clears the histograms and the end-of-step ticket (every step leaves
  * them cleared again: its last workgroup does the housekeeping, incl. the step-counter increment) */
 int lfdm_sampler_ws_init(void* ws, size_t ws_bytes, int batch, int64_t n, lfdm_stream_t stream);
-int lfdm_sampler_step_f32(float* x, const float* eps, const float* noise, float* x0_out,
-                          int batch, int64_t n, const float* coef, int32_t* step_dev,
-                          float quantile, int advance, void* ws, size_t ws_bytes,
-                          lfdm_stream_t stream);
-/* Multistep sampler step (additive, ABI version unchanged): DPM-Solver++ (Lu et al. 2022; "2M", and its first-order form) on the THRESHOLDED
- * data prediction.  Pass 0, the quantile selection and the launch sequence are lfdm_sampler_step_f32's; only the update differs:
- *   x0 = c_x*x - c_eps*eps;  m = clamp(x0, -s, s) / s  (s as above);   x <- k_x*x + k_m*m + k_prev*m_prev;   hist <- m
- *   coef[step] = { c_x, c_eps, k_x, k_m, k_prev, unused }      (the same 6-float row stride, columns 0-1 with the same meaning)
- * hist (B, n), in/out: m of the previous step on entry, m of this step on return (each element is read, then written, by one thread;
- * it must not alias x, eps or x0_out).  The raw eps is not used after x0, and there is no noise operand: the rule is deterministic.
- * A coefficient that is exactly 0 skips its operand: a first-order row (k_prev == 0: the first and the last step of a video) may be
- * handed a hist of UNINITIALISED memory, NaNs included, and neither reads its values into the result nor needs it cleared.
- * x0_out optional (B, n): receives m as well.  ws, quantile, advance, step_dev: as lfdm_sampler_step_f32 (one workspace may serve both). */
-int lfdm_sampler_step_ms_f32(float* x, const float* eps, float* hist, float* x0_out, int batch, int64_t n,
-                             const float* coef, int32_t* step_dev, float quantile, int advance, void* ws,
-                             size_t ws_bytes, lfdm_stream_t stream);
-/* Known-frame conditioning (replacement method; additive, ABI version unchanged): the two steps above with the final store of x
- * replaced, at the frames a byte mask marks, by the known content on the level the step ends on:
- *   x[b, i] <- a * known[b, i] + s * known_noise[b, i]     where frame_mask[b, (i / frame_elems) % frames] != 0,   (a, s) = level[2 * (step + 1)]
- * known, known_noise (B, n) fp32; frame_mask (B, frames) bytes; level (steps + 1, 2) fp32 on the device, row 0 = the level of x_T, row i + 1 =
- * after step i, indexed by the same device step counter as coef (read before it is advanced).  n must be a multiple of frames * frame_elems
- * (planar (C, T, S, S): frame_elems = S * S).  It is a select, not a blend: values of known / known_noise at unmarked frames are never read into
- * a result and may be NaN.  x0, the threshold (quantile over the whole sample), x0_out, hist and the step counter are exactly what the plain
- * step computes; the launch sequence is the plain step's with the update kernel's conditioned instantiation.  Null known operands or a bad
- * frame split return LFDM_EINVAL. */
-int lfdm_sampler_step_known_f32(float* x, const float* eps, const float* noise, float* x0_out, int batch, int64_t n,
-                                const float* coef, int32_t* step_dev, float quantile, int advance, void* ws, size_t ws_bytes,
-                                const float* known, const float* known_noise, const unsigned char* frame_mask, const float* level,
-                                int frames, int64_t frame_elems, lfdm_stream_t stream);
-int lfdm_sampler_step_ms_known_f32(float* x, const float* eps, float* hist, float* x0_out, int batch, int64_t n,
-                                   const float* coef, int32_t* step_dev, float quantile, int advance, void* ws, size_t ws_bytes,
-                                   const float* known, const float* known_noise, const unsigned char* frame_mask, const float* level,
-                                   int frames, int64_t frame_elems, lfdm_stream_t stream);
-/* the same select with host scalars, for x_T (once per video, outside the replayed step): x <- a * known + s * known_noise at marked frames */
-int lfdm_known_blend_f32(float* x, const float* known, const float* known_noise, const unsigned char* frame_mask, float a, float s,
-                         int batch, int64_t n, int frames, int64_t frame_elems, lfdm_stream_t stream);
-/* Per-element known masks (additive, ABI version unchanged): the known select above with one mask byte per ELEMENT:
- *   x[b, i] <- a * known[b, i] + s * known_noise[b, i]     where elem_mask[b * n + i] != 0,   (a, s) = level[2 * (step + 1)]
- * There is no frame split: any subset of a sample's n elements can be marked (a region of every frame, one channel, one pixel).  Everything
- * else is lfdm_sampler_step_known_f32's: a select, never a blend (known / known_noise at unmarked elements may be NaN or uninitialised), and
- * x0, the threshold over the whole sample, x0_out, hist, the step counter and the launch sequence are the plain step's.  Null known operands
- * or n outside (0, 2^24) return LFDM_EINVAL. */
-/* Layout: x, eps, noise, x0_out, known, known_noise dense (B, n) fp32; elem_mask dense (B, n) bytes; coef, step_dev, level dense. */
-int lfdm_sampler_step_elem_f32(float* x, const float* eps, const float* noise, float* x0_out, int batch, int64_t n, const float* coef,
-                               int32_t* step_dev, float quantile, int advance, void* ws, size_t ws_bytes, const float* known,
-                               const float* known_noise, const unsigned char* elem_mask, const float* level, lfdm_stream_t stream);
-/* Layout: as lfdm_sampler_step_elem_f32, hist dense (B, n) in place of noise. */
-int lfdm_sampler_step_ms_elem_f32(float* x, const float* eps, float* hist, float* x0_out, int batch, int64_t n, const float* coef,
-                                  int32_t* step_dev, float quantile, int advance, void* ws, size_t ws_bytes, const float* known,
-                                  const float* known_noise, const unsigned char* elem_mask, const float* level, lfdm_stream_t stream);
-/* the element-mask select with host scalars (x_T of a conditioned video; with an all-set mask: x <- a * known + s * known_noise everywhere,
- * the entry of a schedule on a given latent) */
-/* Layout: x, known, known_noise dense (B, n) fp32; elem_mask dense (B, n) bytes.  x must not alias known or known_noise. */
-int lfdm_known_blend_elem_f32(float* x, const float* known, const float* known_noise, const unsigned char* elem_mask, float a, float s,
-                              int batch, int64_t n, lfdm_stream_t stream);
+/* Layout: every operand dense, as stated at its field.  The struct is read during the call only. */
+int lfdm_sampler_step_f32(const lfdm_sampler_step_params* p, lfdm_stream_t stream);
+/* the known select with host scalars, for x_T (once per video, outside the replayed step): x <- a * known + s * known_noise where the mask of
+ * `k` marks it (with an all-set elem_mask: everywhere, the entry of a schedule on a given latent).  k->level is not an operand. */
+/* Layout: x dense (B, n), the operands of k as stated at its fields.  x must not alias known or known_noise. */
+int lfdm_known_blend_f32(float* x, const lfdm_known_operands* k, float a, float s, int batch, int64_t n, lfdm_stream_t stream);
 /* Counter-based noise (additive, ABI version unchanged; DESIGN.md 4.10, csrc/lfdm_philox.h): every normal is a pure function of
  * (video seed, window, stream, step, element).  Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85,
  * ten rounds) with key = (seed & 0xffffffff, seed >> 32) and counter = (i >> 2, step, stream_id, window) gives four words r0..r3 for the quad
@@ -417,25 +412,6 @@ int lfdm_philox_normal_f32(float* out, const uint64_t* seeds, int batch, int64_t
 /* Layout: as lfdm_philox_normal_f32. */
 int lfdm_philox_bits_u32(uint32_t* out, const uint64_t* seeds, int batch, int64_t n, int64_t row_stride, unsigned stream_id, unsigned step,
                          unsigned window, lfdm_stream_t stream);
-/* lfdm_sampler_step_f32 / lfdm_sampler_step_known_f32 with the step noise COMPUTED inside the update kernel instead of read:
- *   noise[b, i] = z of (seeds[b], counter (i >> 2, *step_dev, 2, *window)), element i & 3 of its quad
- * - bit for bit the tensor lfdm_philox_normal_f32(stream_id 2, step = *step_dev, window = *window) writes, used in the same update expression.
- * seeds (batch 64-bit words) and window (one 32-bit word) live on the device, so that one captured graph serves every seed.  Everything else
- * (x0, threshold, x0_out, known frames, workspace, step counter, launch sequence) is the loading entry point's. */
-/* Layout: x, eps, x0_out, known, known_noise dense (B, n); seeds, window, coef, step_dev, frame_mask, level dense. */
-int lfdm_sampler_step_counter_f32(float* x, const float* eps, const uint64_t* seeds, const uint32_t* window, float* x0_out, int batch,
-                                  int64_t n, const float* coef, int32_t* step_dev, float quantile, int advance, void* ws, size_t ws_bytes,
-                                  lfdm_stream_t stream);
-/* Layout: as lfdm_sampler_step_counter_f32. */
-int lfdm_sampler_step_counter_known_f32(float* x, const float* eps, const uint64_t* seeds, const uint32_t* window, float* x0_out, int batch,
-                                        int64_t n, const float* coef, int32_t* step_dev, float quantile, int advance, void* ws,
-                                        size_t ws_bytes, const float* known, const float* known_noise, const unsigned char* frame_mask,
-                                        const float* level, int frames, int64_t frame_elems, lfdm_stream_t stream);
-/* Layout: as lfdm_sampler_step_counter_f32, elem_mask dense (B, n) bytes (lfdm_sampler_step_elem_f32 with the step noise computed). */
-int lfdm_sampler_step_counter_elem_f32(float* x, const float* eps, const uint64_t* seeds, const uint32_t* window, float* x0_out, int batch,
-                                       int64_t n, const float* coef, int32_t* step_dev, float quantile, int advance, void* ws,
-                                       size_t ws_bytes, const float* known, const float* known_noise, const unsigned char* elem_mask,
-                                       const float* level, lfdm_stream_t stream);
 /* classifier-free guidance combine of Unet3D.forward_with_cond_scale (:525-526):
  * out = null_eps + (cond_eps - null_eps) * scale   (out may alias an input) */
 /* Layout: dense, any; out may alias cond_eps or null_eps. */

@@ -5,6 +5,7 @@ one captured graph serving every seed; the refusals.
 
 Philox and the Box-Muller transform are written out again here in numpy (uint64 arithmetic) from the contract, not imported from the
 package.  Whole videos run on the GPU; under the emulator they are opt-in (LFDM_EMU_E2E=1) like every end-to-end test of the suite."""
+import ctypes
 import os
 
 import numpy as np
@@ -519,9 +520,12 @@ def test_ops_refuse_bad_arguments(backend):
     assert lib.lfdm_philox_normal_f32(ops._p(out), ops._p(seeds), 2, 64, 64, 3, 0, 0, ops._stream(lib)) != 0
     assert lib.lfdm_philox_bits_u32(ops._p(out), None, 2, 64, 64, 0, 0, 0, ops._stream(lib)) != 0
     ws = ops.sampler_ws(2, 192, dev)
-    args = [2, 192, ops._p(table), ops._p(step), -1.0, 1, ops._p(ws), ws.numel() * 4, ops._stream(lib)]
-    assert lib.lfdm_sampler_step_counter_f32(ops._p(x), ops._p(eps), None, ops._p(window), None, *args) != 0 and b"seeds" in lib.lfdm_last_error()
-    assert lib.lfdm_sampler_step_counter_f32(ops._p(x), ops._p(eps), ops._p(seeds), None, None, *args) != 0
+    args = dict(x=ops._p(x), eps=ops._p(eps), batch=2, n=192, coef=ops._p(table), step_dev=ops._p(step), quantile=-1.0, advance=1, ws=ops._p(ws),
+                ws_bytes=ws.numel() * 4)
+    c_step = lambda **kw: lib.lfdm_sampler_step_f32(ctypes.byref(_native.SamplerStepParams(**dict(args, **kw))), ops._stream(lib))
+    assert c_step(window=ops._p(window)) != 0 and b"seeds" in lib.lfdm_last_error()
+    assert c_step(seeds=ops._p(seeds)) != 0
+    assert int(step.cpu()[0]) == 0 and not x.cpu().any()                # nothing ran
 
 
 def test_demo_flags_parse():

@@ -4,6 +4,7 @@ with a closed-form predictor; entering the schedule on a latent; whole videos ag
 GPU; the wrapper.
 
 Every formula is written out again here (numpy / torch double) from the contract, not imported from the package."""
+import ctypes
 import math
 import os
 
@@ -223,24 +224,45 @@ def test_known_element_ops_refuse_bad_arguments(backend):
     # the C entry points check for themselves: null operands, n outside (0, 2^24)
     lib = _native.library()
     ws = ops.sampler_ws(1, 300, dev)
-    args = [ops._p(x), ops._p(eps), None, None, 1, 300, ops._p(table), ops._p(step), -1.0, 1, ops._p(ws), ws.numel() * 4]
-    known = [ops._p(good["known"]), ops._p(good["known_noise"]), ops._p(mask), ops._p(level)]
+    args = dict(x=ops._p(x), eps=ops._p(eps), batch=1, n=300, coef=ops._p(table), step_dev=ops._p(step), quantile=-1.0, advance=1, ws=ops._p(ws),
+                ws_bytes=ws.numel() * 4)
+    known = dict(known=ops._p(good["known"]), known_noise=ops._p(good["known_noise"]), elem_mask=ops._p(mask), level=ops._p(level))
     seeds, window = ops.seeds_tensor([5], dev), torch.zeros(1, dtype=torch.int32).to(dev)
-    cargs = args[:2] + [ops._p(seeds), ops._p(window)] + args[3:]
-    big_n = list(args)
-    big_n[5] = 1 << 24
+    cargs = dict(args, seeds=ops._p(seeds), window=ops._p(window))
     hist = x.clone()
-    margs = list(args)
-    margs[2] = ops._p(hist)
-    for fn, a in ((lib.lfdm_sampler_step_elem_f32, args), (lib.lfdm_sampler_step_ms_elem_f32, margs), (lib.lfdm_sampler_step_counter_elem_f32, cargs)):
-        for i in range(4):
-            part = list(known)
-            part[i] = None
-            assert fn(*a, *part, ops._stream(lib)) != 0 and b"must all be given" in lib.lfdm_last_error()
-    assert lib.lfdm_sampler_step_elem_f32(*big_n, *known, ops._stream(lib)) != 0 and b"2^24" in lib.lfdm_last_error()
-    assert lib.lfdm_known_blend_elem_f32(ops._p(x), known[0], known[1], None, 1.0, 0.0, 1, 300, ops._stream(lib)) != 0
-    assert lib.lfdm_known_blend_elem_f32(ops._p(x), known[0], known[1], known[2], 1.0, 0.0, 1, 1 << 24, ops._stream(lib)) != 0
-    assert lib.lfdm_known_blend_elem_f32(None, known[0], known[1], known[2], 1.0, 0.0, 1, 300, ops._stream(lib)) != 0
+    margs = dict(args, hist=ops._p(hist), multistep=1)
+
+    def c_step(a, k):
+        return lib.lfdm_sampler_step_f32(ctypes.byref(_native.SamplerStepParams(known=_native.KnownOperands(**k), **a)), ops._stream(lib))
+
+    def c_blend(xp, k, n):
+        return lib.lfdm_known_blend_f32(xp, ctypes.byref(_native.KnownOperands(**k)), 1.0, 0.0, 1, n, ops._stream(lib))
+
+    for a in (args, margs, cargs):
+        for drop in known:
+            assert c_step(a, dict(known, **{drop: None})) != 0 and b"must all be given" in lib.lfdm_last_error()
+    assert c_step(dict(args, n=1 << 24), known) != 0 and b"2^24" in lib.lfdm_last_error()
+    assert c_blend(ops._p(x), dict(known, elem_mask=None, level=None), 300) != 0
+    assert c_blend(ops._p(x), dict(known, level=None), 1 << 24) != 0
+    assert c_blend(None, dict(known, level=None), 300) != 0
+    # the combinations that only the parameter struct can express: each one LFDM_EINVAL
+    fmask_p = ops._p(fmask)
+    noise = x.clone()
+    for a, k, words in ((dict(args, seeds=ops._p(seeds)), {}, b"seeds"), (dict(args, window=ops._p(window)), {}, b"seeds"),
+                        (dict(cargs, noise=ops._p(noise)), {}, b"exclude each other"), (dict(cargs, noise=ops._p(noise)), known, b"exclude each other"),
+                        (dict(margs, seeds=ops._p(seeds), window=ops._p(window)), {}, b"the multistep update draws nothing"),
+                        (dict(margs, seeds=ops._p(seeds), window=ops._p(window)), known, b"the multistep update draws nothing"),
+                        (args, dict(known, frame_mask=fmask_p), b"exclude each other"),
+                        (margs, dict(known, frame_mask=fmask_p, frames=4, frame_elems=25), b"exclude each other"),
+                        (args, dict(known, frames=4), b"frames"), (cargs, dict(known, frame_elems=25), b"frame_elems"),
+                        (margs, dict(known, frames=4, frame_elems=25), b"frames"),
+                        (args, dict(frames=4, frame_elems=25), b"must all be given"), (args, dict(level=ops._p(level)), b"must all be given"),
+                        (cargs, dict(known=known["known"], known_noise=known["known_noise"], level=known["level"], frames=4, frame_elems=25),
+                         b"must all be given")):
+        assert c_step(a, k) == -1 and words in lib.lfdm_last_error(), (a, k, lib.lfdm_last_error())
+    for k in (dict(known, level=None, frame_mask=fmask_p), dict(known, level=None, frames=4), dict(known, level=None, frame_elems=25),
+              dict(frames=4, frame_elems=25), {}):
+        assert c_blend(ops._p(x), k, 300) == -1, k
     assert int(step.cpu()[0]) == 0 and not x.cpu().any()                # nothing ran
 
 

@@ -3,6 +3,7 @@ tables; one step of each op against the same call without the known operands; th
 whole videos against a loop over the oracle's own pieces; the plumbing on the GPU; long videos.
 
 Every formula is written out again here (numpy / torch double) from the contract, not imported from the package."""
+import ctypes
 import math
 import os
 
@@ -261,15 +262,23 @@ def test_known_ops_refuse_bad_arguments(backend):
     from cvpr23_lfdm_amd import _native
     lib = _native.library()
     ws = ops.sampler_ws(1, 300, dev)
-    args = [ops._p(x), ops._p(eps), None, None, 1, 300, ops._p(table), ops._p(step), -1.0, 1, ops._p(ws), ws.numel() * 4]
-    known = [ops._p(good["known"]), ops._p(good["known_noise"]), ops._p(mask), ops._p(level)]
-    assert lib.lfdm_sampler_step_known_f32(*args, *known, 4, 26, ops._stream(lib)) != 0 and b"frames" in lib.lfdm_last_error()
-    assert lib.lfdm_sampler_step_known_f32(*args, known[0], None, known[2], known[3], 4, 25, ops._stream(lib)) != 0
+    args = dict(x=ops._p(x), eps=ops._p(eps), batch=1, n=300, coef=ops._p(table), step_dev=ops._p(step), quantile=-1.0, advance=1, ws=ops._p(ws),
+                ws_bytes=ws.numel() * 4)
+    known = dict(known=ops._p(good["known"]), known_noise=ops._p(good["known_noise"]), frame_mask=ops._p(mask), level=ops._p(level))
+
+    def c_step(a, k):
+        return lib.lfdm_sampler_step_f32(ctypes.byref(_native.SamplerStepParams(known=_native.KnownOperands(**k), **a)), ops._stream(lib))
+
+    def c_blend(k):
+        return lib.lfdm_known_blend_f32(ops._p(x), ctypes.byref(_native.KnownOperands(**k)), 1.0, 0.0, 1, 300, ops._stream(lib))
+
+    assert c_step(args, dict(known, frames=4, frame_elems=26)) != 0 and b"frames" in lib.lfdm_last_error()
+    assert c_step(args, dict(known, known_noise=None, frames=4, frame_elems=25)) != 0
     hist = x.clone()
-    args[2] = ops._p(hist)
-    assert lib.lfdm_sampler_step_ms_known_f32(*args, *known, 7, 25, ops._stream(lib)) != 0 and b"frames" in lib.lfdm_last_error()
-    assert lib.lfdm_known_blend_f32(ops._p(x), known[0], known[1], None, 1.0, 0.0, 1, 300, 4, 25, ops._stream(lib)) != 0
-    assert lib.lfdm_known_blend_f32(ops._p(x), known[0], known[1], known[2], 1.0, 0.0, 1, 300, 4, 0, ops._stream(lib)) != 0
+    assert c_step(dict(args, hist=ops._p(hist), multistep=1), dict(known, frames=7, frame_elems=25)) != 0 and b"frames" in lib.lfdm_last_error()
+    assert c_blend(dict(known, level=None, frame_mask=None, frames=4, frame_elems=25)) != 0
+    assert c_blend(dict(known, level=None, frames=4, frame_elems=0)) != 0
+    assert int(step.cpu()[0]) == 0 and not x.cpu().any()                # nothing ran
 
 
 # ------------------------------------------------------------------------------------------ 3. the conditioning acts

@@ -2,18 +2,19 @@
 """Same bits?  Runs a fixed list of calls on seeded inputs under ONE build of the kernels and writes one line per output tensor -
 name, shape, SHA-256 of its bytes - so that two builds (a refactor and its parent commit) can be compared line by line.
 
-    tools/ab_bits.py run OUT.txt [--emu [LIB]] [--set conv|attention|norm]
+    tools/ab_bits.py run OUT.txt [--emu [LIB]] [--set conv|attention|norm|sampler]
                                                          this process, the library LFDM_HIP_LIB names (default: the in-tree one) on the GPU,
                                                          or an emulator library on the CPU (default: the in-tree one)
     tools/ab_bits.py diff A.txt B.txt                    exit status 1 when any line differs or is missing
-    tools/ab_bits.py ab BASE_LIB OUT_DIR [--emu] [--new LIB] [--timeout S] [--set conv|attention|norm]
+    tools/ab_bits.py ab BASE_LIB OUT_DIR [--emu] [--new LIB] [--timeout S] [--set conv|attention|norm|sampler]
                                                          `run` under BASE_LIB, then under the in-tree library (or --new), each in a fresh child
                                                          process with its own time limit, one after the other; stops at the first non-zero
                                                          exit status; then `diff`
 
 The calls are the suite's own: the listed tests of tests/ run in-process (their case lists cannot go stale here) with every function of
-cvpr23_lfdm_amd.ops / train_ops / lfae_ops wrapped - each tensor a call returns, and the gn_partial buffer it was handed, becomes a line.  `extra` below adds
-the few cells no test reaches.  Nothing but tensor bytes is looked at."""
+cvpr23_lfdm_amd.ops / train_ops / lfae_ops wrapped - each tensor a call returns, and the gn_partial buffer it was handed, becomes a line.  The
+sampler set also records every tensor ARGUMENT after the call (the step writes x, hist, x0_out and the step counter in place; the workspace is
+left out).  `extra` below adds the few cells no test reaches.  Nothing but tensor bytes is looked at."""
 import argparse
 import hashlib
 import os
@@ -25,7 +26,8 @@ R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # (file, -k expression) per --set.  conv: the smallest shapes that reach every epilogue / GroupNorm hand-off of the convolution family;
 # norm: the GroupNorm / LayerNorm / BatchNorm kernels forward and backward, the heads kernels and the kernels that share csrc/norm_core.h;
 # attention: every entry point that goes through csrc/attn_core.h (the short-sequence core, the fused temporal kernels, the low-resolution
-# kernel), the long-sequence kernels beside them, the fast-math cases and the per-tile-order cases.
+# kernel), the long-sequence kernels beside them, the fast-math cases and the per-tile-order cases; sampler: every form of the sampler step (plain,
+# multistep, known frames, known elements, counter noise), the blends and the quantile kernels under them.
 SETS = {
     "conv": ([
         ("tests/test_ops_parity.py",
@@ -53,14 +55,24 @@ SETS = {
         ("tests/test_lfae_ops.py", "test_batchnorm_relu or test_batchnorm_relu_segments or test_batchnorm_fork_and_channel_slices"),
         ("tests/test_norm_edges.py", "test_layernorm or test_groupnorm or test_heads"),
     ], "not gpu_only and not bigTrue and not refuses"),
+    "sampler": ([
+        ("tests/test_ops_parity.py", "test_sampler_step or test_abs_quantile"),
+        ("tests/test_threshold_select.py", "test_threshold_select"),
+        ("tests/test_sampler_dpmpp.py", "test_step_ms"),
+        ("tests/test_known_frames.py", "test_known_step or test_known_blend"),
+        ("tests/test_known_elements.py", "test_known_elements_step or test_known_blend_elem or test_frame_constant_element_mask_is_the_frame_mask"),
+        ("tests/test_counter_noise.py", "test_sampler_step_counter_is_the_loading_step"),
+    ], "not refuse"),
 }
+ARGUMENTS_TOO = {"sampler"}      # sets whose calls write their results in place
 
 
 class Recorder:
     """pytest plugin: wraps the ops layer for the session, names every recorded tensor test-id#call.function#index"""
 
-    def __init__(self, out_path, emu_lib):
+    def __init__(self, out_path, emu_lib, arguments_too=False):
         self.lines, self.out_path, self.emu_lib, self.test, self.ncall, self.depth = [], out_path, emu_lib, "setup", 0, 0
+        self.arguments_too = arguments_too
 
     def record(self, name, t):
         b = t.detach().cpu().contiguous().view(-1).view(dtype=__import__("torch").uint8).numpy().tobytes()
@@ -87,6 +99,8 @@ class Recorder:
                     return r
                 self.ncall += 1
                 outs = list(tensors(r)) + ([kw["gn_partial"]] if isinstance(kw.get("gn_partial"), torch.Tensor) else [])
+                if self.arguments_too:
+                    outs += list(tensors(a)) + [v for k, v in sorted(kw.items()) if isinstance(v, torch.Tensor) and k != "ws"]
                 for i, t in enumerate(outs):
                     self.record("%s#%d.%s#%d" % (self.test, self.ncall, fname, i), t)
                 return r
@@ -153,7 +167,7 @@ def run(out_path, emu, which="conv"):
     emu_lib = None
     if emu is not None:
         emu_lib = os.path.abspath(emu) if emu else os.path.join(R, "tests", "emu", "liblfdm_emu.so")
-    rec = Recorder(out_path, emu_lib)
+    rec = Recorder(out_path, emu_lib, which in ARGUMENTS_TOO)
     os.chdir(R)
     # (the F(2x2) Winograd cases run at both workgroup widths: LFDM_WINO_BN is a parameter of the suite's own tests)
     args = ["-q", "-p", "no:cacheprovider", "-x", "-m", "emu" if emu is not None else "gpu"]

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
-"""lfdm_sampler_step_f32 and lfdm_sampler_step_ms_f32, plain, with known frames (8 of the 40, lfdm_sampler_step_*_known_f32) and with known
-elements (the same 8 frames as an element mask, and a box of a quarter of every frame; lfdm_sampler_step_*_elem_f32), at the C2 latent
-(B=1, 3x40x32x32): us per step (graph replay), alternating."""
+"""lfdm_sampler_step_f32, the DDIM / DDPM update and the multistep one (lfdm_sampler_step_params.multistep), plain, with known frames (8 of
+the 40, .known.frame_mask) and with known elements (the same 8 frames as an element mask, and a box of a quarter of every frame;
+.known.elem_mask), at the C2 latent (B=1, 3x40x32x32) and two larger shapes: us per step (graph replay), alternating."""
 import os
 import statistics
 import sys
