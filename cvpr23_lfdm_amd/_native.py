@@ -278,6 +278,12 @@ _SIGNATURES = {
     "lfdm_relu_bwd_f32": (i32, [f32p, f32p, f32p, i64, stream_t]),
     "lfdm_l1_mean_fwd_f32": (i32, [f32p, f32p, i64, f32, f32p, C.c_void_p, sz, C.c_void_p, stream_t]),
     "lfdm_l1_mean_bwd_f32": (i32, [f32p, f32p, i64, f32, f32p, f32p, stream_t]),
+    # ---- DM training with known frames / elements held clean (additive, ABI stays 13)
+    "lfdm_train_qsample_f32": (i32, [f32p, f32p, C.c_void_p, f32p, f32p, i32, C.c_void_p, C.c_void_p, i32, i64, f32p, i32, i64, stream_t]),
+    "lfdm_masked_loss_ws_bytes": (sz, [i32, i64]),
+    "lfdm_masked_loss_fwd_f32": (i32, [f32p, f32p, f32p, C.c_void_p, f32p, f32p, i32, C.c_void_p, C.c_void_p, i32, i64, i32, f32p, f32p, f32p,
+                                       i32, i64, C.c_void_p, sz, C.c_void_p, stream_t]),
+    "lfdm_masked_loss_bwd_f32": (i32, [f32p, f32p, C.c_void_p, C.c_void_p, i32, i64, i32, f32p, f32p, f32p, i32, i64, stream_t]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -508,5 +508,33 @@ class Upsample2Pad(Function):
         return train_ops.upsample2_pad(_c(dy), n_img, h, w, pad, reflect, backward=True), None, None, None, None, None
 
 
+class MaskedDiffusionLoss(Function):
+    """The DM training loss over the UNKNOWN elements: (1 / B) sum_b S_b / max(N_b, 1) as a 0-dim tensor, and - not
+    differentiable - pred_x0 from the same pass.  The gradient goes to pred only.  mask: None, a (B, T) bool / uint8 frame mask or an element
+    mask of noise's shape; every operand dense."""
+
+    @staticmethod
+    def forward(ctx, pred, noise, x_noisy, t, r_tab, m_tab, mask, loss_type):
+        pred = pred.detach()
+        kw = {} if mask is None else dict(frame_mask=mask) if mask.dim() == 2 else dict(elem_mask=mask)
+        loss, inv_count, pred_x0 = ops.masked_loss_fwd(noise, pred, x_noisy, t, r_tab, m_tab, loss_type=loss_type, **kw)
+        ctx.save_for_backward(pred, noise, inv_count)
+        ctx.meta = (kw, loss_type)
+        ctx.mark_non_differentiable(pred_x0)
+        return loss.reshape(()), pred_x0
+
+    @staticmethod
+    def backward(ctx, gout, _):
+        pred, noise, inv_count = ctx.saved_tensors
+        kw, loss_type = ctx.meta
+        g = gout.detach().to(torch.float32).reshape(1).contiguous()
+        return ops.masked_loss_bwd(noise, pred, inv_count, g, loss_type=loss_type, **kw), None, None, None, None, None, None, None
+
+
+def masked_diffusion_loss(pred, noise, x_noisy, t, r_tab, m_tab, mask=None, loss_type="l1"):
+    """-> (loss, pred_x0) through MaskedDiffusionLoss."""
+    return MaskedDiffusionLoss.apply(pred, noise, x_noisy, t, r_tab, m_tab, mask, loss_type)
+
+
 def conv_cl(x0, weight, bias, *, x1=None, residual=None, **geom):
     return ConvCL.apply(x0, x1, weight, bias, residual, geom)

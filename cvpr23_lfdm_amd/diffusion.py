@@ -54,7 +54,8 @@ class Schedule:
 class Request(NamedTuple):
     """A validated sampling call (GaussianDiffusion.check_request): seeds is the list of ints under noise="counter", else None.  known_mask:
     (B, T) bool - known frames - or 5-D bool (B, C | 1, T, S, S) - known elements.  start / start_step: the latent the
-    schedule is entered on in front of step start_step (None: pure noise in front of step 0)."""
+    schedule is entered on in front of step start_step (None: pure noise in front of step 0).  known_level (no field: the class says it):
+    "noised" - the known content sits on the step's level; `CleanRequest`: "clean" - it is held clean at every step."""
     shape: tuple
     known: Optional[torch.Tensor]
     known_mask: Optional[torch.Tensor]
@@ -62,6 +63,19 @@ class Request(NamedTuple):
     window: int
     start: Optional[torch.Tensor] = None
     start_step: int = 0
+
+    @property
+    def known_level(self):
+        return "noised"
+
+
+class CleanRequest(Request):
+    """A Request whose known content is held clean at every step (known_level="clean"); `_replace` keeps the class."""
+    __slots__ = ()
+
+    @property
+    def known_level(self):
+        return "clean"
 
 
 class SampleMode(NamedTuple):
@@ -130,16 +144,65 @@ def capture_step(unet, plan, mode):
     plan.update(graph=graph, chunk_graphs={}, buf_gen=unet._buf_gen)
 
 
+class KnownMaskPolicy:
+    """Random-mask training (RaMViD, Hoeppe et al. 2022): which frames of each training video stay clean.  Per video, with
+    probability `prob` the video is conditioned; one of `kinds` is then drawn uniformly and k ~ U{1 .. max_frames}: "prefix" - frames
+    [0, k); "ends" - [0, ceil(k / 2)) and [T - floor(k / 2), T); "random" - a uniform subset of k frames.  max_frames <= T - 1: a drawn mask
+    always leaves a frame unknown.  The draws come from a CPU generator of the policy's own (the default generator's order is untouched),
+    are made for the GLOBAL batch - the same number of draws whatever they turn out to be - and sliced by the caller, as t and noise are.
+    The generator's state is in no state dict: a resumed run starts the mask stream again from `seed`."""
+    KINDS = ("prefix", "ends", "random")
+
+    def __init__(self, num_frames, prob=0.5, kinds=KINDS, max_frames=8, seed=0):
+        kinds = (kinds,) if isinstance(kinds, str) else tuple(kinds)
+        if not kinds or any(k not in self.KINDS for k in kinds):
+            raise ValueError("known_train: kinds must be a non-empty subset of %s, got %r" % (self.KINDS, kinds))
+        if isinstance(prob, bool) or not isinstance(prob, (int, float)) or not 0.0 <= prob <= 1.0:
+            raise ValueError("known_train: prob must lie in [0, 1], got %r" % (prob,))
+        if isinstance(max_frames, bool) or not isinstance(max_frames, int) or not 1 <= max_frames <= num_frames - 1:
+            raise ValueError("known_train: max_frames must lie in [1, num_frames - 1 = %d] (a mask always leaves a frame unknown), got %r"
+                             % (num_frames - 1, max_frames))
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise ValueError("known_train: seed must be an integer, got %r" % (seed,))
+        self.num_frames, self.prob, self.kinds, self.max_frames, self.seed = int(num_frames), float(prob), kinds, max_frames, seed
+        self.generator = torch.Generator(device="cpu")
+        self.generator.manual_seed(seed)
+
+    def draw(self, total):
+        """The (total, T) bool mask of one global batch on the host: four draws of fixed size, whatever their values."""
+        g, frames = self.generator, self.num_frames
+        on = torch.rand(total, generator=g) < self.prob
+        kind = torch.randint(0, len(self.kinds), (total,), generator=g).tolist()
+        k = torch.randint(1, self.max_frames + 1, (total,), generator=g).tolist()
+        order = torch.rand(total, frames, generator=g).argsort(dim=1)          # a uniform permutation per video: its first k are the subset
+        mask = torch.zeros(total, frames, dtype=torch.bool)
+        for b in range(total):
+            if not on[b]:
+                continue
+            name = self.kinds[kind[b]]
+            if name == "prefix":
+                mask[b, :k[b]] = True
+            elif name == "ends":
+                mask[b, :(k[b] + 1) // 2] = True
+                mask[b, frames - k[b] // 2:] = True
+            else:
+                mask[b, order[b, :k[b]]] = True
+        return mask
+
+
 class GaussianDiffusion(nn.Module):
     def __init__(self, denoise_fn, *, image_size, num_frames, text_use_bert_cls=False, channels=3,
                  timesteps=1000, sampling_timesteps=250, ddim_sampling_eta=1., loss_type='l1',
                  use_dynamic_thres=False, dynamic_thres_percentile=0.9, null_cond_prob=0.1,
-                 per_element_loss=False, sampler="reference", long_attention=False, noise="torch"):
+                 per_element_loss=False, sampler="reference", long_attention=False, noise="torch", known_train=None):
         """Reference signature + `sampler` (keyword): what `sample()` runs.  "reference" (default): the reference's own pair, DDIM when
         sampling_timesteps < timesteps, ancestral DDPM otherwise.  "dpmpp_2m": DPM-Solver++(2M) (Lu et al. 2022), the second-order multistep
         rule on the thresholded data prediction, one UNet evaluation per step, on the reference's DDIM time grid; "dpmpp_1": its first-order
         form on every step.  Both are deterministic: nothing is drawn after x_T and `ddim_sampling_eta` is ignored (`_ms_step_tables`)."""
         super().__init__()
+        # known_train (keyword, default None: off): dict(prob=0.5, kinds=("prefix", "ends", "random"), max_frames=8, seed=0) - the mask
+        # policy of random-mask training (KnownMaskPolicy, DESIGN.md 4.12): `forward` then draws a frame mask per step and hands it to p_losses
+        self.known_policy = None if known_train is None else KnownMaskPolicy(num_frames, **dict(known_train))
         # noise (keyword, default "torch"): where sampling noise comes from.  "torch": torch's default generator in the reference's draw order.
         # "counter": per-video seeds - every normal is a function of (video seed, window, stream, step, element) (DESIGN.md 4.10); `sample`
         # then needs `seeds`.  Training draws (t, masks, q_sample's noise) stay on torch's generator in both modes.
@@ -204,6 +267,7 @@ class GaussianDiffusion(nn.Module):
 
     SAMPLERS = ("reference", "dpmpp_1", "dpmpp_2m")
     NOISE_MODES = ("torch", "counter")
+    KNOWN_LEVELS = ("noised", "clean")
 
     @property
     def noise(self):
@@ -235,6 +299,8 @@ class GaussianDiffusion(nn.Module):
             torch.zeros((total,), device=device).float().uniform_(0, 1)
         if 0 < self.null_cond_prob < 1:
             torch.zeros((total,), device=device).float().uniform_(0, 1)
+        if self.known_policy is not None:           # (the policy's own generator: one global batch of masks, as `forward` draws)
+            self.known_policy.draw(total)
 
     # ------------------------------------------------------------------ helpers
     def _embed(self, cond, device):
@@ -353,21 +419,23 @@ class GaussianDiffusion(nn.Module):
             a = [b['alphas_cumprod'][self.num_timesteps - 1]] + [b['alphas_cumprod_prev'][t] for t in reversed(range(self.num_timesteps))]
         return torch.stack([torch.stack([v.sqrt(), (1 - v).sqrt()]) for v in a]).float().contiguous()
 
-    def _schedule_key(self, ddim, sampler, dev):
+    def _schedule_key(self, ddim, sampler, dev, clean=False):
         """Everything a schedule's tables are a function of; the buffers' stamps come last."""
-        return (bool(ddim), sampler, float(self.ddim_sampling_eta), self.sampling_timesteps, self.num_timesteps, str(dev),
+        return (bool(ddim), sampler, float(self.ddim_sampling_eta), self.sampling_timesteps, self.num_timesteps, str(dev), bool(clean),
                 tuple((k, v._version, v.data_ptr()) for k, v in self.named_buffers(recurse=False)))
 
-    def _schedule(self, ddim, sampler, dev, level=False):
+    def _schedule(self, ddim, sampler, dev, level=False, clean=False):
         """The `Schedule` of (ddim, sampler) on `dev`: `_step_tables` / `_ms_step_tables` (whose grid checks raise from here) and, once a
         conditioned call has asked with level=True, `_level_table`; kept per `_schedule_key`, a hit returns the same tensors.  The tables
         are functions of the registered buffers only, but building them reads every buffer back to the host - a host synchronisation at the
         start of EVERY video, 2.3-3.8 ms of a 258 ms video in the kernel trace (profiles/r06_af_video_gaps.txt).  A buffer written in
         place or replaced makes new entries (the old ones are dropped); an instance-level replacement of `_step_tables` (the teacher-forced
-        tests) is never kept.  Nobody writes these tensors and no graph binds them: a plan copies them into operands of its own."""
+        tests) is never kept.  Nobody writes these tensors and no graph binds them: a plan copies them into operands of its own.
+        clean=True (known_level="clean"): an entry of its own whose level table is (1, 0) in every row - known content is
+        stored as itself at every step; the "noised" entry of the same schedule keeps its table."""
         multistep = sampler != "reference"
         ddim = bool(ddim) or multistep
-        key = None if (not multistep and "_step_tables" in self.__dict__) else self._schedule_key(ddim, sampler, dev)
+        key = None if (not multistep and "_step_tables" in self.__dict__) else self._schedule_key(ddim, sampler, dev, clean)
         sch = self._schedules.get(key)
         if sch is None:
             if multistep:
@@ -380,21 +448,27 @@ class GaussianDiffusion(nn.Module):
                 self._schedules = {k: v for k, v in self._schedules.items() if k[-1] == key[-1]}
                 self._schedules[key] = sch
         if level and sch.level is None:
-            sch.level_host = self._level_table(ddim, sampler)
+            sch.level_host = torch.tensor([[1.0, 0.0]]).repeat(len(sch.times) + 1, 1) if clean else self._level_table(ddim, sampler)
             sch.level = sch.level_host.to(dev)
         return sch
 
-    def check_request(self, shape, known=None, known_mask=None, seeds=None, window=0, start=None, start_step=0, steps=None):
+    def check_request(self, shape, known=None, known_mask=None, seeds=None, window=0, start=None, start_step=0, steps=None,
+                      known_level="noised"):
         """The validated `Request` of one sampling call; ValueError before anything is launched (and before the text encoder runs).  known
         (B, C, T, S, S) float32 and known_mask (B, T) bool: both or none.  seeds: noise="counter" needs one Python int in [0, 2^64) per video
         and no noise tape next to them; noise="torch" takes neither seeds nor a window.  known_mask may also be a 5-D bool of shape
         (B, C, T, S, S) or (B, 1, T, S, S) (broadcast over the channels): known ELEMENTS.  start (B, C, T, S, S) float32 with
         0 <= start_step < steps (`steps`: of the schedule the caller runs, default `sample`'s): the latent the schedule is entered on; a
-        start_step without start is refused.  The outermost entry (FlowDiffusion.sample_one_video
+        start_step without start is refused.  known_level: "noised" (default) or "clean" - known content held clean at every step, for a
+        denoiser trained with known_train; "clean" without known content is refused.  The outermost entry (FlowDiffusion.sample_one_video
         / sample_long_video; sample / p_sample_loop / ddim_sample called directly) checks once, everything below takes the Request on trust."""
         shape = tuple(shape)
         if (known is None) != (known_mask is None):
             raise ValueError("sample: known and known_mask go together (both or none)")
+        if known_level not in self.KNOWN_LEVELS:
+            raise ValueError("sample: known_level must be one of %s, got %r" % (self.KNOWN_LEVELS, known_level))
+        if known_level == "clean" and known is None:
+            raise ValueError("sample: known_level='clean' needs known and known_mask (there is nothing to hold clean)")
         if known is not None:
             if not isinstance(known, torch.Tensor) or known.dtype != torch.float32 or tuple(known.shape) != shape:
                 raise ValueError("sample: known must be a float32 tensor of shape %s, got %s %s"
@@ -414,31 +488,35 @@ class GaussianDiffusion(nn.Module):
                 steps = self.sampling_timesteps if self.is_ddim_sampling or self.sampler != "reference" else self.num_timesteps
             if isinstance(start_step, bool) or not isinstance(start_step, int) or not 0 <= start_step < steps:
                 raise ValueError("sample: start_step must be an integer in [0, %d), got %r" % (steps, start_step))
+        request = CleanRequest if known_level == "clean" else Request
         if self.noise != "counter":
             if seeds is not None:
                 raise ValueError("sample: seeds need noise='counter' (this model draws from torch's generator: noise=%r)" % (self.noise,))
             if window != 0:
                 raise ValueError("sample: window needs noise='counter'")
-            return Request(shape, known, known_mask, None, 0, start, start_step)
+            return request(shape, known, known_mask, None, 0, start, start_step)
         if seeds is None:
             raise ValueError("sample: noise='counter' needs seeds (one integer in [0, 2^64) per video)")
         if self.noise_source is not None:
             raise ValueError("sample: a noise_source (tape) and noise='counter' exclude each other - replay counter_tape(...) under noise='torch'")
         if isinstance(window, bool) or not isinstance(window, int) or not 0 <= window < (1 << 32):
             raise ValueError("sample: window must be an integer in [0, 2^32), got %r" % (window,))
-        return Request(shape, known, known_mask, ops.check_seeds(seeds, shape[0], "sample: seeds"), window, start, start_step)
+        return request(shape, known, known_mask, ops.check_seeds(seeds, shape[0], "sample: seeds"), window, start, start_step)
 
-    def counter_tape(self, seeds, shape, ddim, window=0, known=False, start_step=0):
+    def counter_tape(self, seeds, shape, ddim, window=0, known=False, start_step=0, known_level="noised"):
         """The counter-based draws of one `sample` call as a noise tape: a callable with the `noise_source` signature that returns, in the
         default path's draw order, the tensors ops.philox_normal writes for `seeds` - x_T (stream 0), then the known-frame noise (stream 1) if
         `known`, then one tensor per drawing step of the schedule (stream 2, step = the step's index; none under the multistep samplers)
         from step `start_step` on (a video entered at that step draws nothing for the steps in front of it).
+        known_level="clean": nothing is drawn for the known content (its noise operand is a zero-filled buffer), so no stream 1 entry.
         Installed as `noise_source` of a noise="torch" model - or handed to the oracle - it reproduces the noise="counter" sample."""
+        if known_level not in self.KNOWN_LEVELS:
+            raise ValueError("counter_tape: known_level must be one of %s, got %r" % (self.KNOWN_LEVELS, known_level))
         shape = tuple(shape)
         seeds = ops.check_seeds(seeds, shape[0], "counter_tape: seeds")
         dev = "cuda" if _native.library().kind == "hip" else "cpu"
         draws = self._schedule(ddim, self.sampler, dev).draws
-        plan = [(ops.NOISE_STREAM_XT, 0)] + ([(ops.NOISE_STREAM_KNOWN, 0)] if known else [])
+        plan = [(ops.NOISE_STREAM_XT, 0)] + ([(ops.NOISE_STREAM_KNOWN, 0)] if known and known_level != "clean" else [])
         plan += [(ops.NOISE_STREAM_STEP, i) for i, d in enumerate(draws) if d and i >= start_step]
         seeds_dev = ops.seeds_tensor(seeds, dev)
         state = {"next": 0}
@@ -457,7 +535,7 @@ class GaussianDiffusion(nn.Module):
     # ------------------------------------------------------------------ sampling
     @torch.no_grad()
     def sample(self, fea, cond=None, cond_scale=1., batch_size=16, *, known=None, known_mask=None, seeds=None, window=0, start=None,
-               start_step=0):
+               start_step=0, known_level="noised"):
         """Reference :762-775.  fea: planar (B, 256, S, S); cond: (B, 768) tensor or list[str].  Runs `self.sampler`.
         known (B, C, T, S, S) float32 + known_mask (B, T) bool (keyword only, both or none): condition on known frames by the replacement
         method - frame t of sample b is kept on the trajectory of known[b, :, t] and returned bit for bit where the mask is
@@ -467,10 +545,13 @@ class GaussianDiffusion(nn.Module):
         known_mask may instead be 5-D, (B, C, T, S, S) or (B, 1, T, S, S) bool: known ELEMENTS - a region of every frame, one channel
         (DESIGN.md 4.11).  start (B, C, T, S, S) float32 + start_step k in [0, steps): the schedule is entered in front of step k on
         x = a_k start + s_k z (z: the x_T draw, (a_k, s_k): row k of the level table) and steps k .. steps - 1 run - an edit of an existing
-        video, the closer to it the later it starts.  Known content is then placed on row k."""
+        video, the closer to it the later it starts.  Known content is then placed on row k.
+        known_level="clean" (keyword only; default "noised"): the known content is held CLEAN at every step instead of on the step's level -
+        what a denoiser trained with known_train has seen; nothing is drawn for it."""
         batch = batch_size if cond is None else len(cond)
         shape = (batch, self.channels, self.num_frames, self.image_size, self.image_size)
-        return self.sample_checked(fea, cond, cond_scale, self.check_request(shape, known, known_mask, seeds, window, start, start_step))
+        return self.sample_checked(fea, cond, cond_scale, self.check_request(shape, known, known_mask, seeds, window, start, start_step,
+                                                                             known_level=known_level))
 
     @torch.no_grad()
     def sample_checked(self, fea, cond, cond_scale, req):
@@ -483,15 +564,17 @@ class GaussianDiffusion(nn.Module):
 
     @torch.no_grad()
     def p_sample_loop(self, fea, shape, cond=None, cond_scale=1., *, known=None, known_mask=None, seeds=None, window=0, start=None,
-                      start_step=0):
+                      start_step=0, known_level="noised"):
         return self._sample(fea, cond, cond_scale, False, "reference",
-                            self.check_request(shape, known, known_mask, seeds, window, start, start_step, steps=self.num_timesteps))
+                            self.check_request(shape, known, known_mask, seeds, window, start, start_step, steps=self.num_timesteps,
+                                               known_level=known_level))
 
     @torch.no_grad()
     def ddim_sample(self, fea, shape, cond=None, cond_scale=1., clip_denoised=True, *, known=None, known_mask=None, seeds=None, window=0,
-                    start=None, start_step=0):
+                    start=None, start_step=0, known_level="noised"):
         return self._sample(fea, cond, cond_scale, True, "reference",
-                            self.check_request(shape, known, known_mask, seeds, window, start, start_step, steps=self.sampling_timesteps))
+                            self.check_request(shape, known, known_mask, seeds, window, start, start_step, steps=self.sampling_timesteps,
+                                               known_level=known_level))
 
     def _sample(self, fea, cond, cond_scale, ddim, sampler, req):
         """One video batch: schedule -> this call's operand values -> the plan of its mode, refilled -> x_T -> the steps."""
@@ -517,8 +600,9 @@ class GaussianDiffusion(nn.Module):
         first = req.start_step if req.start is not None else 0
         if first > 0 and sampler == "dpmpp_2m":         # no history in front of the first step run: first order, in the plan's own copy
             plan["coef"][first].copy_(self._schedule(ddim, "dpmpp_1", dev).coef[first])
-        if mode.known:
-            plan["level"].copy_(sch.level)
+        clean = mode.known and req.known_level == "clean"
+        if mode.known:          # (the plan - and its graphs - serve both levels: the table is an operand)
+            plan["level"].copy_(self._schedule(ddim, sampler, dev, level=True, clean=True).level if clean else sch.level)
         self._draw_start(plan, mode, req, sch.level_host, first)
         return self._run_steps(unet, plan, mode, sch.draws, first)
 
@@ -573,7 +657,8 @@ class GaussianDiffusion(nn.Module):
         """x_T into plan["x"] (:753 / :788); conditioned: one more draw directly behind it (every step draw keeps its place in the order),
         then x_T's known frames / elements on the init level.  The step counter starts at 0.  With req.start: the x_T draw z goes to the
         noise buffer and x <- a start + s z on row `first` of the level table (one blend launch, all-True mask), the known content is placed
-        on that row and the step counter starts at `first`."""
+        on that row and the step counter starts at `first`.  known_level="clean": the known content is placed as itself (a = 1, s = 0), its
+        noise operand is zero-filled (the kernels multiply it by 0: it must be finite) and nothing is drawn for it."""
         x, counter = plan["x"], mode.noise == "counter"
         z = x if req.start is None else plan["noise"]
         if counter:
@@ -591,7 +676,10 @@ class GaussianDiffusion(nn.Module):
         if mode.known:
             plan["known"].copy_(req.known)
             plan["kmask"].copy_(req.known_mask)
-            if counter:
+            if req.known_level == "clean":
+                a, s = 1.0, 0.0
+                plan["known_noise"].zero_()
+            elif counter:
                 ops.philox_normal(plan["known_noise"], plan["seeds"], stream=ops.NOISE_STREAM_KNOWN, window=req.window)
             else:
                 self._draw(plan["known_noise"])
@@ -658,14 +746,47 @@ class GaussianDiffusion(nn.Module):
         return (self.sqrt_alphas_cumprod[t].reshape(shp) * x_start
                 + self.sqrt_one_minus_alphas_cumprod[t].reshape(shp) * noise)
 
-    def p_losses(self, x_start, t, fea, cond=None, noise=None, clip_denoised=True, **kwargs):
+    def _train_known_mask(self, x_start, known_mask):
+        """known_mask of p_losses as the kernels take it: (B, T) bytes - frames - or x_start's shape - elements ((B, 1, T, S, S) expanded
+        over the channels, as sampling does); the forms `check_request` accepts."""
+        shape = tuple(x_start.shape)
+        forms = ((shape[0], shape[2]), shape, (shape[0], 1) + shape[2:])
+        if not isinstance(known_mask, torch.Tensor) or known_mask.dtype != torch.bool or tuple(known_mask.shape) not in forms:
+            raise ValueError("p_losses: known_mask must be a bool tensor of shape %s (frames) or %s / %s (elements), got %s %s"
+                             % (forms + (getattr(known_mask, "dtype", type(known_mask)), tuple(getattr(known_mask, "shape", ())))))
+        known_mask = known_mask.to(x_start.device)
+        return (known_mask.expand(shape) if known_mask.dim() == 5 else known_mask).contiguous()
+
+    def _clip_pred_x0(self, pred_x0):
+        """:886-893: pred_x0 clamped to its dynamic (or static) threshold and divided by it."""
+        b = pred_x0.shape[0]
+        sthr = ops.abs_quantile(pred_x0.reshape(b, -1).contiguous(), self.dynamic_thres_percentile) \
+            if self.use_dynamic_thres else torch.ones(b, device=pred_x0.device)
+        sthr = sthr.clamp(min=1.).view(-1, *((1,) * (pred_x0.dim() - 1)))
+        return pred_x0.clamp(-sthr, sthr) / sthr
+
+    def p_losses(self, x_start, t, fea, cond=None, noise=None, clip_denoised=True, known_mask=None, **kwargs):
         """:856-895.  x_start (B,3,T,S,S), fea (B,256,T,S,S) (frame-constant when it comes from `forward`).
         In training mode with autograd enabled the denoiser runs through unet_train_forward (native forward and
         backward kernels) and the returned loss carries the graph; otherwise the forward-only sampling executor
-        evaluates the same function."""
+        evaluates the same function.
+        known_mask (keyword; default None: the reference's step, statement for statement): (B, T) bool - known frames - or 5-D bool
+        (B, C | 1, T, S, S) - known elements: those elements of x_start stay clean inside x_noisy, the loss is the mean over each sample's
+        UNKNOWN elements, then over the samples, and pred_x0 is x_start there - three launches of csrc/train_diffusion.hip
+        around the denoiser instead of the eager q_sample / loss / predict_start_from_noise."""
         if noise is None:
             noise = torch.randn_like(x_start)
-        x_noisy = self.q_sample(x_start, t, noise)
+        if known_mask is None:
+            x_noisy = self.q_sample(x_start, t, noise)
+        else:
+            if self.per_element_loss:
+                raise NotImplementedError("p_losses: known_mask with per_element_loss=True (the functional multi-GPU flavour) is not built")
+            if self.loss_type not in ops.LOSS_TYPES:
+                raise NotImplementedError()
+            known_mask = self._train_known_mask(x_start, known_mask)
+            x_start, noise, t = x_start.float().contiguous(), noise.float().contiguous(), t.to(torch.int64).contiguous()
+            x_noisy = ops.train_qsample(x_start, noise, t, self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod,
+                                        **{"frame_mask" if known_mask.dim() == 2 else "elem_mask": known_mask})
         none_cond_mask = None
         if is_list_str(cond):
             none_cond_mask = [c == "None" for c in cond]
@@ -701,6 +822,13 @@ class GaussianDiffusion(nn.Module):
                                               **kwargs)
             finally:
                 unet.train(was_training)
+        if known_mask is not None:
+            from .autograd import masked_diffusion_loss
+            loss, pred_x0 = masked_diffusion_loss(pred_noise.contiguous(), noise, x_noisy, t, self.sqrt_recip_alphas_cumprod,
+                                                  self.sqrt_recipm1_alphas_cumprod, known_mask, self.loss_type)
+            if clip_denoised:
+                self.pred_x0 = self._clip_pred_x0(pred_x0)
+            return loss
         red = "none" if self.per_element_loss else "mean"
         if self.loss_type == 'l1':
             loss = F.l1_loss(noise, pred_noise, reduction=red)
@@ -711,11 +839,7 @@ class GaussianDiffusion(nn.Module):
         with torch.no_grad():
             pred_x0 = self.predict_start_from_noise(x_noisy, t, pred_noise.detach())
             if clip_denoised:
-                b = pred_x0.shape[0]
-                sthr = ops.abs_quantile(pred_x0.reshape(b, -1).contiguous(), self.dynamic_thres_percentile) \
-                    if self.use_dynamic_thres else torch.ones(b, device=pred_x0.device)
-                sthr = sthr.clamp(min=1.).view(-1, *((1,) * (pred_x0.dim() - 1)))
-                self.pred_x0 = pred_x0.clamp(-sthr, sthr) / sthr
+                self.pred_x0 = self._clip_pred_x0(pred_x0)
         if self.per_element_loss:
             return loss, unet.null_cond_mask
         return loss
@@ -724,6 +848,10 @@ class GaussianDiffusion(nn.Module):
         """:897-903."""
         b, device = x.shape[0], x.device
         fea = fea.unsqueeze(dim=2).expand(-1, -1, x.size(2), -1, -1)      # reference: .repeat (:901); a view is enough
+        if self.known_policy is not None and kwargs.get("known_mask") is None:
+            # the policy's masks for the GLOBAL batch from its own CPU generator, this rank's rows, to the device as (B, T) bytes
+            lo, hi, total = shard_bounds(self.rank_shard, b) if self.rank_shard is not None else (0, b, b)
+            kwargs["known_mask"] = self.known_policy.draw(total)[lo:hi].to(device, non_blocking=True)
         if self.rank_shard is not None and "noise" not in kwargs:
             lo, hi, total = shard_bounds(self.rank_shard, b)
             t = torch.randint(0, self.num_timesteps, (total,), device=device).long()[lo:hi]

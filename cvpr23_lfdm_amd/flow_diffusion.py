@@ -15,7 +15,7 @@ import torch
 import yaml
 from torch import nn
 
-from .diffusion import GaussianDiffusion
+from .diffusion import CleanRequest, GaussianDiffusion, Request
 from .generator import Generator
 from .params import ParamTree, bg_predictor_spec, build_tree, region_predictor_spec
 from .optim import FlatAdam, GradAllReduce
@@ -71,7 +71,7 @@ class FlowDiffusion(nn.Module):
                  adam_betas=(0.9, 0.99), is_train=True, only_use_flow=True, use_residual_flow=False,
                  learn_null_cond=False, use_deconv=True, padding_mode="zeros", pretrained_pth="",
                  config_pth="", bert_path=None, *, conv_precision="fp32", sampler="reference", ema_decay=None, ema_start_step=0,
-                 max_grad_norm=None, skip_nonfinite=False, long_attention=False, noise="torch"):
+                 max_grad_norm=None, skip_nonfinite=False, long_attention=False, noise="torch", known_train=None):
         """Reference signature (video_flow_diffusion_model.py:19-37) + `bert_path`: a local Hugging Face directory of
         bert-base-cased for `cond=list[str]` (the reference downloads it with torch.hub; see text.py).  LFDM_BERT_PATH in
         the environment is the default, so unchanged caller scripts pick it up.
@@ -85,7 +85,10 @@ class FlowDiffusion(nn.Module):
         long_attention (keyword only, default False): Unet3D.long_attention - up to 256 frames per window (and up to 256 pixels per frame in
         the mid block) on the streaming attention kernels, for sampling and training.
         noise (keyword only, default "torch"): GaussianDiffusion.noise - "counter" gives every sampled video a seed of its own
-        (sample_one_video(seeds=...), sample_long_video(seed=...)).  Training draws stay on torch's generator."""
+        (sample_one_video(seeds=...), sample_long_video(seed=...)).  Training draws stay on torch's generator.
+        known_train (keyword only, default None: off): GaussianDiffusion.known_train - dict(prob=0.5, kinds=("prefix", "ends", "random"),
+        max_frames=8, seed=0), random-mask training: some frames of a training video stay clean and the loss counts the others, so that
+        the checkpoint can be sampled with known_level="clean" (DESIGN.md 4.12).  Not available in the functional flavour."""
         super().__init__()
         if noise not in GaussianDiffusion.NOISE_MODES:
             raise ValueError("noise must be one of %s, got %r" % (GaussianDiffusion.NOISE_MODES, noise))
@@ -119,7 +122,7 @@ class FlowDiffusion(nn.Module):
                                            sampling_timesteps=sampling_timesteps, timesteps=timesteps,
                                            loss_type='l2', use_dynamic_thres=True,
                                            null_cond_prob=null_cond_prob, ddim_sampling_eta=ddim_sampling_eta, sampler=sampler,
-                                           long_attention=self.long_attention, noise=noise)
+                                           long_attention=self.long_attention, noise=noise, known_train=known_train)
         bert_path = bert_path or os.environ.get("LFDM_BERT_PATH")
         if bert_path:
             from .text import BertTextEncoder
@@ -155,7 +158,7 @@ class FlowDiffusion(nn.Module):
 
     # ------------------------------------------------------------------ sampling (a28)
     def sample_one_video(self, cond_scale, *, known_latent=None, known_mask=None, frame_times=None, interp="linear", seeds=None,
-                         start_latent=None, strength=None):
+                         start_latent=None, strength=None, known_level="noised"):
         """Reference :190-216.  seeds (keyword only; noise="counter"): one integer in [0, 2^64) per video of the batch (GaussianDiffusion.sample).  Results land in sample_vid_grid (B,2,T,S,S), sample_vid_conf (B,1,T,S,S),
         sample_out_vid / sample_warped_vid (B,3,T,H,W), and the latent the diffusion returned (B,3,T,S,S; the residual flow when
         use_residual_flow) in sample_latent.  known_latent (B,3,T,S,S) in that same space + known_mask (B,T) bool (keyword only, both or
@@ -164,7 +167,8 @@ class FlowDiffusion(nn.Module):
         known_mask may also be 5-D, (B,3,T,S,S) or (B,1,T,S,S) bool: known ELEMENTS of the latent.  start_latent
         (B,3,T,S,S; e.g. `encode_video` of a real video, or an earlier sample_latent) + strength in (0, 1] (keyword only, both or none): the
         video is an edit of that latent - the schedule is entered at start_step = steps - ceil(strength * steps) on the latent noised to
-        that level, so strength 1 runs every step and a small strength stays close to the start."""
+        that level, so strength 1 runs every step and a small strength stays close to the start.  known_level (keyword only): "noised"
+        (default) or "clean" - the known content held clean at every step, for a denoiser trained with known_train."""
         if frame_times is not None:
             frame_times = self._check_frame_times(frame_times, interp, self.diffusion.num_frames)
         dm = self.diffusion
@@ -178,7 +182,7 @@ class FlowDiffusion(nn.Module):
             start_step = steps - int(math.ceil(strength * steps - 1e-9))        # (0.3 * 10 = 3.0000000000000004 is three steps)
         with torch.no_grad():                 # (bad known frames / seeds are refused before anything is launched)
             req = dm.check_request((self.sample_img.shape[0], dm.channels, dm.num_frames, dm.image_size, dm.image_size), known_latent, known_mask,
-                                   seeds, 0, start_latent, start_step)
+                                   seeds, 0, start_latent, start_step, known_level=known_level)
             img, skips, fea = self._source()
             self.sample_latent = pred = dm.sample_checked(fea, self.sample_text, cond_scale, req)
             self._decode_sample(img, skips, pred)
@@ -223,14 +227,15 @@ class FlowDiffusion(nn.Module):
     def _decode_sample(self, img, skips, pred):
         self._decode_pieces(img, skips, [self._maps(pred) + (pred.shape[2],)])
 
-    def sample_long_video(self, cond_scale, total_frames, overlap=8, *, frame_times=None, interp="linear", seed=None):
+    def sample_long_video(self, cond_scale, total_frames, overlap=8, *, frame_times=None, interp="linear", seed=None, known_level="noised"):
         """A video of `total_frames` frames, longer than the model's window of num_frames, as a chain of windows: the LFAE
         encoder runs ONCE; chunk 0 is a plain sample; chunk j > 0 is conditioned on the last `overlap` latent frames of chunk j - 1 placed at
         its frames 0 .. overlap-1 (same source image, features and text condition - only the latent is chained); the result keeps chunk 0 whole
         and frames overlap.. of every later chunk, cut to total_frames, and is decoded in pieces of at most num_frames frames.  Results as
         sample_one_video's, with T = total_frames.  frame_times / interp (keyword only): as sample_one_video's, times in
         [0, total_frames - 1].  seed (keyword only; noise="counter"): the long video's ONE seed - an integer in [0, 2^64), or one per video
-        of the batch; window w draws with counter word `window` = w, so a window can be made again without the ones before it."""
+        of the batch; window w draws with counter word `window` = w, so a window can be made again without the ones before it.
+        known_level (keyword only): "noised" (default) or "clean" - how the overlap frames of every later window are held."""
         nf = self.diffusion.num_frames
         total_frames, overlap = int(total_frames), int(overlap)
         if overlap < 1 or overlap >= nf:
@@ -240,6 +245,8 @@ class FlowDiffusion(nn.Module):
         if frame_times is not None:
             frame_times = self._check_frame_times(frame_times, interp, total_frames)
         dm = self.diffusion
+        if known_level not in dm.KNOWN_LEVELS:
+            raise ValueError("sample_long_video: known_level must be one of %s, got %r" % (dm.KNOWN_LEVELS, known_level))
         with torch.no_grad():
             b, seeds = self.sample_img.shape[0], seed
             if isinstance(seed, int) and not isinstance(seed, bool):
@@ -252,11 +259,12 @@ class FlowDiffusion(nn.Module):
             pieces, have = [chunk], nf
             mask = torch.zeros((b, nf), dtype=torch.bool, device=chunk.device)
             mask[:, :overlap] = True
+            request = CleanRequest if known_level == "clean" else Request          # how the later windows hold their overlap frames
             while have < total_frames:                                # (window w of a seeded video draws with counter word `window` = w)
                 known = torch.zeros_like(chunk)
                 known[:, :, :overlap] = chunk[:, :, nf - overlap:]
                 window = len(pieces) if req.seeds is not None else 0
-                chunk = dm.sample_checked(fea, self.sample_text, cond_scale, req._replace(known=known, known_mask=mask, window=window))
+                chunk = dm.sample_checked(fea, self.sample_text, cond_scale, request(*req._replace(known=known, known_mask=mask, window=window)))
                 pieces.append(chunk[:, :, overlap:])
                 have += nf - overlap
             self.sample_latent = latent = torch.cat(pieces, dim=2)[:, :, :total_frames].contiguous()
@@ -611,8 +619,8 @@ class FlowDiffusionFunctional(FlowDiffusion):
         return out
 
     def sample_one_video(self, sample_img, sample_text, cond_scale, *, known_latent=None, known_mask=None, frame_times=None, interp="linear",
-                         seeds=None, start_latent=None, strength=None):
+                         seeds=None, start_latent=None, strength=None, known_level="noised"):
         self.set_sample_input(sample_img=sample_img, sample_text=sample_text)
         FlowDiffusion.sample_one_video(self, cond_scale, known_latent=known_latent, known_mask=known_mask, frame_times=frame_times,
-                                       interp=interp, seeds=seeds, start_latent=start_latent, strength=strength)
+                                       interp=interp, seeds=seeds, start_latent=start_latent, strength=strength, known_level=known_level)
         return {k: getattr(self, k) for k in ("sample_vid_grid", "sample_vid_conf", "sample_out_vid", "sample_warped_vid", "sample_latent")}

@@ -1102,6 +1102,136 @@ def known_blend_elem(x, known, known_noise, elem_mask, a, s):
     return _known_blend("known_blend_elem", x, a, s, known, known_noise, elem_mask=elem_mask)
 
 
+# ---------------------------------------------------------------------------------------------
+# DM training with known frames / elements held clean (csrc/train_diffusion.hip)
+# ---------------------------------------------------------------------------------------------
+
+LOSS_TYPES = {"l1": 0, "l2": 1}         # LFDM_LOSS_L1 / LFDM_LOSS_L2
+_LOSS_TICKETS = {}                      # device -> the zeroed ticket word lfdm_masked_loss_fwd_f32 leaves zeroed
+
+
+def _train_operands(what, lib, like, floats, t=None, tables=()):
+    """The dense float32 (B, ...) operands of the three training entry points (all of `like`'s shape and device), the (B,) int64 device
+    tensor t and the schedule tables; -> (batch, n)."""
+    if like.dim() < 2 or like.numel() == 0:
+        raise ValueError("%s: operands must be (B, ...) and not empty" % what)
+    for name, v in floats.items():
+        if not torch.is_tensor(v) or v.dtype != torch.float32 or tuple(v.shape) != tuple(like.shape) or v.device != like.device:
+            raise ValueError("%s: %s must be a float32 tensor of shape %s on the operands' device" % (what, name, tuple(like.shape)))
+    _chk(lib, *floats.values(), *tables)
+    _dense(*floats.values(), *tables)
+    batch = like.shape[0]
+    if t is not None:
+        if not torch.is_tensor(t) or t.dtype != torch.int64 or tuple(t.shape) != (batch,) or not t.is_contiguous() or t.device != like.device:
+            raise ValueError("%s: t must be a contiguous (%d,) int64 tensor on the operands' device (it is read there)" % (what, batch))
+        if len({tuple(v.shape) for v in tables}) != 1 or tables[0].dim() != 1 or any(v.dtype != torch.float32 or v.device != like.device for v in tables):
+            raise ValueError("%s: the schedule tables must be float32 vectors of one length on the operands' device" % what)
+    return batch, like.numel() // batch
+
+
+def _train_mask(what, x, frame_mask, elem_mask, frames):
+    """(frame_mask pointer, elem_mask pointer, frames, frame_elems) of the three mask forms: none | frame_mask (B, frames) | elem_mask of
+    x's shape; bool or uint8, used as bytes.  A frame of a planar (B, C, T, ...) operand is everything behind T, of (B, C * T, hw) one row."""
+    if frame_mask is None and elem_mask is None:
+        if frames is not None:
+            raise ValueError("%s: frames needs frame_mask" % what)
+        return None, None, 0, 0
+    if frame_mask is not None and elem_mask is not None:
+        raise ValueError("%s: frame_mask and elem_mask exclude each other" % what)
+    mask = frame_mask if elem_mask is None else elem_mask
+    if not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8) or not mask.is_contiguous() or mask.device != x.device:
+        raise ValueError("%s: the mask must be a contiguous bool / uint8 tensor on the operands' device" % what)
+    batch = x.shape[0]
+    n = x.numel() // batch
+    if elem_mask is not None:
+        if frames is not None:
+            raise ValueError("%s: elem_mask has no frame split" % what)
+        if tuple(elem_mask.shape) != tuple(x.shape):
+            raise ValueError("%s: elem_mask must have the operands' shape %s, got %s" % (what, tuple(x.shape), tuple(elem_mask.shape)))
+        return None, _p(elem_mask), 0, 0
+    if x.dim() >= 4:
+        frames = x.shape[2] if frames is None else int(frames)
+        if x.shape[2] != frames:
+            raise ValueError("%s: the operands have %d frames, frames = %d" % (what, x.shape[2], frames))
+        frame_elems = x[0, 0, 0].numel()
+    elif x.dim() == 3 and frames is not None:
+        frames, frame_elems = int(frames), x.shape[2]
+    else:
+        raise ValueError("%s: operands must be (B, C, T, ...) or, with frames, (B, C * T, hw) for a frame mask" % what)
+    if frames < 1 or n % (frames * frame_elems) != 0:
+        raise ValueError("%s: %d elements per sample are no multiple of %d frames x %d" % (what, n, frames, frame_elems))
+    if tuple(frame_mask.shape) != (batch, frames):
+        raise ValueError("%s: frame_mask must be (%d, %d), got %s" % (what, batch, frames, tuple(frame_mask.shape)))
+    return _p(frame_mask), None, frames, frame_elems
+
+
+def _loss_code(what, loss_type):
+    if loss_type not in LOSS_TYPES:
+        raise ValueError("%s: loss_type must be 'l1' or 'l2', got %r" % (what, loss_type))
+    return LOSS_TYPES[loss_type]
+
+
+def _train_dest(what, t, shape, like):
+    if t is None:
+        return torch.empty(tuple(shape), dtype=torch.float32, device=like.device)
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or t.device != like.device:
+        raise ValueError("%s: a destination must be a contiguous float32 tensor of shape %s on the operands' device" % (what, tuple(shape)))
+    return t
+
+
+def train_qsample(x_start, noise, t, a_tab, s_tab, *, frame_mask=None, elem_mask=None, frames=None, out=None):
+    """lfdm_train_qsample_f32: x_noisy = known ? x_start : a_tab[t_b] * x_start + s_tab[t_b] * noise - the bits of q_sample's expression on
+    the unknown elements, the bits of x_start on the known ones.  t: (B,) int64 on the device (read there, clamped to the tables); a_tab /
+    s_tab: sqrt_alphas_cumprod / sqrt_one_minus_alphas_cumprod.  Mask: none, frame_mask (B, T) or elem_mask of x_start's shape."""
+    lib = _lib()
+    out = _train_dest("train_qsample", out, x_start.shape, x_start)
+    batch, n = _train_operands("train_qsample", lib, x_start, dict(x_start=x_start, noise=noise, out=out), t, (a_tab, s_tab))
+    fm, em, frames, frame_elems = _train_mask("train_qsample", x_start, frame_mask, elem_mask, frames)
+    lib.check(lib.lfdm_train_qsample_f32(_p(x_start), _p(noise), _p(t), _p(a_tab), _p(s_tab), a_tab.numel(), fm, em, frames, frame_elems,
+                                         _p(out), batch, n, _stream(lib)), "lfdm_train_qsample_f32")
+    return out
+
+
+def masked_loss_fwd(noise, pred, x_noisy, t, r_tab, m_tab, *, loss_type="l1", frame_mask=None, elem_mask=None, frames=None, loss=None,
+                    inv_count=None, pred_x0=None):
+    """lfdm_masked_loss_fwd_f32 -> (loss (1,), inv_count (B,), pred_x0): loss = (1 / B) sum_b S_b / max(N_b, 1) with S_b the sum of
+    |noise - pred| ('l2': squared) over the UNKNOWN elements of sample b and N_b their number; inv_count[b] = 1 / max(N_b, 1) (the
+    backward's operand); pred_x0 = r_tab[t_b] * x_noisy - m_tab[t_b] * pred, x_noisy where known (r_tab / m_tab: sqrt_recip_alphas_cumprod /
+    sqrt_recipm1_alphas_cumprod).  Fixed summation order: the same bits on every run."""
+    lib = _lib()
+    code = _loss_code("masked_loss_fwd", loss_type)
+    pred_x0 = _train_dest("masked_loss_fwd", pred_x0, noise.shape, noise)
+    batch, n = _train_operands("masked_loss_fwd", lib, noise, dict(noise=noise, pred=pred, x_noisy=x_noisy, pred_x0=pred_x0), t, (r_tab, m_tab))
+    loss = _train_dest("masked_loss_fwd", loss, (1,), noise)
+    inv_count = _train_dest("masked_loss_fwd", inv_count, (batch,), noise)
+    fm, em, frames, frame_elems = _train_mask("masked_loss_fwd", noise, frame_mask, elem_mask, frames)
+    nbytes = lib.lfdm_masked_loss_ws_bytes(batch, n)
+    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=noise.device)
+    ticket = _LOSS_TICKETS.get(noise.device)
+    if ticket is None:
+        ticket = _LOSS_TICKETS[noise.device] = torch.zeros(1, dtype=torch.int32, device=noise.device)
+    lib.check(lib.lfdm_masked_loss_fwd_f32(_p(noise), _p(pred), _p(x_noisy), _p(t), _p(r_tab), _p(m_tab), r_tab.numel(), fm, em, frames, frame_elems,
+                                           code, _p(loss), _p(inv_count), _p(pred_x0), batch, n, _p(ws), nbytes, _p(ticket), _stream(lib)),
+              "lfdm_masked_loss_fwd_f32")
+    return loss, inv_count, pred_x0
+
+
+def masked_loss_bwd(noise, pred, inv_count, gout, *, loss_type="l1", frame_mask=None, elem_mask=None, frames=None, out=None):
+    """lfdm_masked_loss_bwd_f32: dpred = -sign(noise - pred) * gout * inv_count[b] / B ('l2': 2 (pred - noise) in place of the sign), exactly
+    0.0 at every known element.  gout: one float32 on the device (read there)."""
+    lib = _lib()
+    code = _loss_code("masked_loss_bwd", loss_type)
+    out = _train_dest("masked_loss_bwd", out, noise.shape, noise)
+    batch, n = _train_operands("masked_loss_bwd", lib, noise, dict(noise=noise, pred=pred, out=out))
+    for name, v, count in (("inv_count", inv_count, batch), ("gout", gout, 1)):
+        if not torch.is_tensor(v) or v.dtype != torch.float32 or v.numel() != count or not v.is_contiguous() or v.device != noise.device:
+            raise ValueError("masked_loss_bwd: %s must be a contiguous float32 tensor of %d element(s) on the operands' device" % (name, count))
+    fm, em, frames, frame_elems = _train_mask("masked_loss_bwd", noise, frame_mask, elem_mask, frames)
+    lib.check(lib.lfdm_masked_loss_bwd_f32(_p(noise), _p(pred), fm, em, frames, frame_elems, code, _p(inv_count), _p(gout), _p(out), batch, n,
+                                           _stream(lib)), "lfdm_masked_loss_bwd_f32")
+    return out
+
+
 def cfg_combine(cond_eps, null_eps, scale, out):
     lib = _lib()
     _chk(lib, cond_eps, null_eps, out)

@@ -916,6 +916,39 @@ int lfdm_l1_mean_fwd_f32(const float* x, const float* y, int64_t n, float weight
                          lfdm_stream_t stream);
 int lfdm_l1_mean_bwd_f32(const float* x, const float* y, int64_t n, float weight, const float* gout, float* dx, lfdm_stream_t stream);
 
+/* The diffusion edge of the DM training step with known frames / elements held clean (additive, ABI version unchanged; DESIGN.md 4.12,
+ * csrc/train_diffusion.hip).  Samples are dense rows of n floats (n % 4 == 0, n < 2^31); t: (B) int64 ON THE DEVICE, clamped to
+ * [0, t_len) by the kernels; the tables are the registered fp32 buffers of t_len entries, read on the device.  Mask forms, as in the
+ * known operands of the sampler step: none (both masks NULL, frames = frame_elems = 0) | frame_mask: (B, frames) bytes, non-zero = frame
+ * (i / frame_elems) % frames of sample b is known, n a multiple of frames * frame_elems, frame_elems % 4 == 0 | elem_mask: (B, n) bytes,
+ * 4-byte aligned, frames = frame_elems = 0.  No floating-point atomics, fixed summation order: two runs give the same bits.
+ * Refusals (LFDM_EINVAL, nothing is enqueued): a null operand, n % 4 != 0, both masks, a frame split without frame_mask or one that does
+ * not divide n or whose frames are no multiple of 4 elements, t_len <= 0, loss_type outside { LFDM_LOSS_L1, LFDM_LOSS_L2 }.
+ *   qsample:  x_noisy = known ? x_start : a_tab[t_b] * x_start + s_tab[t_b] * noise  (two fp32 products and one fp32 sum, each rounded on
+ *             its own: the bits of q_sample's expression; a known element is the bits of x_start)
+ *   loss fwd: S_b = sum over the unknown elements of |noise - pred| (LFDM_LOSS_L2: squared), N_b = their number;
+ *             *loss = (1 / B) sum_b S_b / max(N_b, 1);  inv_count[b] = 1 / max(N_b, 1);  in the same pass
+ *             pred_x0 = known ? x_noisy : r_tab[t_b] * x_noisy - m_tab[t_b] * pred  (separately rounded: predict_start_from_noise).
+ *             ws: lfdm_masked_loss_ws_bytes, 8-byte aligned; ticket: one zeroed word, left zeroed (one stream at a time)
+ *   loss bwd: dpred = -sign(noise - pred) * (*gout) * inv_count[b] / B  (LFDM_LOSS_L2: 2 (pred - noise) in place of the sign); known: 0.f */
+#define LFDM_LOSS_L1 0
+#define LFDM_LOSS_L2 1
+/* Layout: x_start, noise, x_noisy dense (B, n), 16 B; t dense (B) int64; a_tab, s_tab dense (t_len); masks dense.  x_noisy must not alias an input. */
+int lfdm_train_qsample_f32(const float* x_start, const float* noise, const int64_t* t, const float* a_tab, const float* s_tab, int t_len,
+                           const unsigned char* frame_mask, const unsigned char* elem_mask, int frames, int64_t frame_elems, float* x_noisy,
+                           int batch, int64_t n, lfdm_stream_t stream);
+size_t lfdm_masked_loss_ws_bytes(int batch, int64_t n);
+/* Layout: noise, pred, x_noisy, pred_x0 dense (B, n), 16 B; t dense (B) int64; r_tab, m_tab dense (t_len); masks dense; loss 1 float,
+ * inv_count (B) floats.  pred_x0 must not alias an input. */
+int lfdm_masked_loss_fwd_f32(const float* noise, const float* pred, const float* x_noisy, const int64_t* t, const float* r_tab,
+                             const float* m_tab, int t_len, const unsigned char* frame_mask, const unsigned char* elem_mask, int frames,
+                             int64_t frame_elems, int loss_type, float* loss, float* inv_count, float* pred_x0, int batch, int64_t n, void* ws,
+                             size_t ws_bytes, unsigned* ticket, lfdm_stream_t stream);
+/* Layout: noise, pred, dpred dense (B, n), 16 B; masks dense; inv_count (B) floats and gout 1 float on the device.  dpred must not alias an input. */
+int lfdm_masked_loss_bwd_f32(const float* noise, const float* pred, const unsigned char* frame_mask, const unsigned char* elem_mask, int frames,
+                             int64_t frame_elems, int loss_type, const float* inv_count, const float* gout, float* dpred, int batch, int64_t n,
+                             lfdm_stream_t stream);
+
 /* im2col of channels-last rows with few channels (channels % 4 == 0, <= 16; stride 1, zero padding): out (n_img*hq*wq, k*k*channels),
  * column tap * channels + ch.  Lets the weight gradient of the generator's 7x7 RGB convolutions (LFAE/modules/generator.py:37,56: 3 -> 64
  * and 64 -> 3 channels) run as ONE 1x1 weight-gradient GEMM instead of 49 per-tap GEMMs that pad 4 channels to a 64-wide tile. */

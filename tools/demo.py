@@ -52,6 +52,10 @@ def build_parser():
                     help="a video of this many frames, longer than --frames, as a chain of overlapping windows conditioned on known frames "
                          "(FlowDiffusion.sample_long_video, DESIGN.md 4.3); 0 (default): off, one window of --frames")
     ap.add_argument("--overlap", type=int, default=8, help="latent frames two consecutive windows of --total-frames share")
+    ap.add_argument("--known-level", choices=("noised", "clean"), default="noised",
+                    help="how known content (--total-frames' overlap frames, --keep-box / --regen-box) is held during sampling: on the step's "
+                         "noise level (default), or clean at every step - for a checkpoint trained with tools/train_dm.py --known-prob "
+                         "(DESIGN.md 4.12)")
     ap.add_argument("--use-ema", action="store_true",
                     help="sample from the averaged weights: the checkpoint's 'diffusion_ema' entry (tools/train_dm.py --ema-decay, DESIGN.md 4.4)")
     ap.add_argument("--long-attention", action="store_true", help="windows of 65 ... 256 frames (and a mid block of up to 256 pixels per frame) on the streaming attention kernels (FlowDiffusion(long_attention=True), DESIGN.md 4.8)")
@@ -133,7 +137,7 @@ def edit_arguments(args, model, ref):
     box = args.keep_box or args.regen_box
     if box:
         mask = box_mask(tuple(latent.shape), parse_box(box, args.size // 4), keep=bool(args.keep_box))
-        kw.update(known_latent=latent, known_mask=mask.cuda())
+        kw.update(known_latent=latent, known_mask=mask.cuda(), known_level=args.known_level)
     return kw
 
 
@@ -158,6 +162,8 @@ def check_args(args):
         sys.exit("--video-seeds / --save-latents need --noise counter")
     if (args.strength is not None or args.keep_box or args.regen_box) and not args.from_video:
         sys.exit("--strength / --keep-box / --regen-box need --from-video")
+    if args.known_level == "clean" and not (args.total_frames > 0 or args.keep_box or args.regen_box):
+        sys.exit("--known-level clean needs known content: --total-frames, or --from-video with --keep-box / --regen-box")
     if args.keep_box and args.regen_box:
         sys.exit("--keep-box and --regen-box exclude each other (one is the complement of the other)")
     if args.strength is not None and not 0.0 < args.strength <= 1.0:
@@ -261,7 +267,8 @@ def main():
         ref_b = ref.expand(args.batch, -1, -1, -1).contiguous()
         model.set_sample_input(sample_img=ref_b, sample_text=[text] * args.batch)
         if args.total_frames > 0:
-            model.sample_long_video(args.cond_scale, args.total_frames, overlap=args.overlap, **({} if seeds is None else dict(seed=seeds)))
+            model.sample_long_video(args.cond_scale, args.total_frames, overlap=args.overlap, known_level=args.known_level,
+                                    **({} if seeds is None else dict(seed=seeds)))
         else:
             model.sample_one_video(cond_scale=args.cond_scale, **skw)
         if seeds is not None:           # a video's identity: its seed, a checksum of its x_T (window 0) and of the latent it gave

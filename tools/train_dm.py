@@ -63,7 +63,22 @@ def parse_args(argv=None):
                     "as bytes and colour jitter, area shrink and normalisation run there")
     ap.add_argument("--resident", action="store_true", help="with --packed: upload the whole store once; a batch is then frame numbers")
     ap.add_argument("--long-attention", action="store_true", help="windows of 65 ... 256 frames (and a mid block of up to 256 pixels per frame) on the streaming attention kernels (FlowDiffusion(long_attention=True), DESIGN.md 4.8)")
+    ap.add_argument("--known-prob", type=float, default=0.0, help="> 0: random-mask training (FlowDiffusion(known_train=...), DESIGN.md 4.12) - "
+                    "with this probability some frames of a training video stay clean and the loss counts the others; sample the "
+                    "checkpoint with known_level='clean' (tools/demo.py --known-level clean)")
+    ap.add_argument("--known-kinds", nargs="+", choices=("prefix", "ends", "random"), default=["prefix", "ends", "random"],
+                    help="--known-prob: the mask kinds drawn from")
+    ap.add_argument("--known-max-frames", type=int, default=8, help="--known-prob: at most this many known frames (at most --frames - 1)")
+    ap.add_argument("--known-seed", type=int, default=0, help="--known-prob: seed of the mask stream (not stored in checkpoints: a resumed run "
+                    "starts the stream again)")
     return ap.parse_args(argv)
+
+
+def known_train(args):
+    """The known_train option of FlowDiffusion for --known-prob / --known-kinds / --known-max-frames / --known-seed (None: off)."""
+    if args.known_prob <= 0:
+        return None
+    return dict(prob=args.known_prob, kinds=tuple(args.known_kinds), max_frames=args.known_max_frames, seed=args.known_seed)
 
 
 def make_dataset(args):
@@ -98,7 +113,7 @@ def main():
                           null_cond_prob=args.null_cond_prob, sampling_timesteps=args.preview_steps or 1000, config_pth=args.config,
                           pretrained_pth=args.lfae_ckpt, bert_path=None if args.synthetic else args.bert,     # :153-162
                           ema_decay=args.ema_decay, ema_start_step=args.ema_start_step, max_grad_norm=args.max_grad_norm,
-                          skip_nonfinite=args.skip_nonfinite, long_attention=args.long_attention)
+                          skip_nonfinite=args.skip_nonfinite, long_attention=args.long_attention, known_train=known_train(args))
     opt = model.optimizer_diff
     model.cuda()
     if args.synthetic:
@@ -167,7 +182,14 @@ def main():
                 if args.preview_steps > 0:                                      # a sampled preview, from the averaged weights when there are any
                     with (model.ema_weights() if args.ema_decay is not None else contextlib.nullcontext()):
                         model.set_sample_input(sample_img=ref_imgs[:1], sample_text=list(ref_texts)[:1])
-                        model.sample_one_video(cond_scale=1.0)
+                        pkw = {}
+                        if args.known_prob > 0:         # what the run is learning: the first frames of the video's own latent, held clean
+                            with torch.no_grad():
+                                latent = model.encode_video(real_vids[:1], ref_imgs[:1])
+                            first = torch.zeros((1, args.frames), dtype=torch.bool, device=latent.device)
+                            first[:, :max(1, args.known_max_frames // 2)] = True
+                            pkw = dict(known_latent=latent, known_mask=first, known_level="clean")
+                        model.sample_one_video(cond_scale=1.0, **pkw)
                     C.mimsave(os.path.join(args.out, "B%04d_S%06d_%s%s.gif" % (args.batch_size, step, real_names[0],
                                                                                 "_ema" if args.ema_decay is not None else "")),
                               C.video_strip(model, ref_imgs[:1]))
