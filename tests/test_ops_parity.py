@@ -1019,6 +1019,60 @@ def test_attention_lowres(backend, c, frames, s, mode):
 #                                                        test_conv_pointwise_residual_groupnorm (the table above it)
 #   whole model: tests/test_end_to_end.py::test_unet_forward_frames[1|17|64], ::test_sample_one_video_single_frame (BASELINE configs[0]),
 #   tests/test_unet_train.py::test_unet_train_grads[one_frame]; the 64-frame limit at construction: tests/test_end_to_end.py::test_frame_limit
+#
+# The LFAE entry points: forward warp (csrc/warp.hip), predictor glue (csrc/lfae_aux.hip), stage-1 training (csrc/train_lfae.hip).
+# tests/test_lfae_edges.py, float64 references (the ATen graph, or the closed formula for the predictor kernels), NaN-filled destinations, the same
+# shapes on both backends; ids without the backend:
+#   lfdm_warp_cl_f32  warp_cl_kernel<1> g = 3 (C 12), 5 (20), 1 (4, one pixel) | <2> g = 3 (24), 5 (40; maps shrunk in x, stretched in y) | <4> g = 3
+#     (48) | g = 4, the shift (64); `idx / g` for every g that is no power of two; rows of ld_src 32 / ld_prev 36 / ld_out 40 at C 24; deform only |
+#     mask | blend with prev; batch 2 x 3 frames    test_warp_cl_lane_groups[<mode>-<c>-<h>-<w>-<fh>-<fw>-<ld>]
+#   lfdm_warp_planar_f32  warp_planar_kernel<false> (hw % 4 != 0): fpb 4 > 2 frames (1030 planes), batch 2 (520) | <true>: fpb 4 over 3 frames, fpb 8
+#     over 7, blocks of 4 over 1025 frames (one left) | warp_planar_pixel_kernel: 5 channels (second quad ragged), one pixel; deform | mask | blend with
+#     planar prev | with channels-last prev (ld_prev > C)
+#                                                        test_warp_planar_frame_blocks[<mode>-<b>-<c>-<t>-<h>-<w>-<fh>-<fw>]
+#   lfae_ops.ApplyOpticalCL as a chain of entry points: lfdm_warp_cl_f32, lfdm_absmax_f32, lfdm_warp_bwd_f32 (warp_bwd_cl_kernel), lfdm_fix_finalize_f32,
+#     lfdm_resize_adjoint_f32: g = 1 | 2 | 4 | 16 | 64 (15 pixels: four workgroups, the last ragged; shuffles over dead lanes); maps equal to, smaller and
+#     LARGER than the image, one map pixel, one map row, one image pixel; all gradients | src constant (no scatter, kfix = 0) | no prev | prev constant |
+#     no occlusion plane; two cases run twice (same bits), max word / accumulator / tickets zero after every run
+#                                                        test_apply_optical_cl_edges[<subset>-<c>-<h>-<w>-<fh>-<fw>]
+#   lfae_ops.ApplyOpticalImage: lfdm_warp_planar_f32 (pixel kernel), lfdm_warp_bwd_f32 (warp_bwd_px_kernel), the same geometries at C = 1 (planar prev)
+#     and C = 3 (prev and dprev as channel rows of 4-wide channels-last tensors)
+#                                                        test_apply_optical_image_edges[<c>-<h>-<w>-<fh>-<fw>]
+#   lfdm_resize_adjoint_f32 alone: up-scaling, ragged, 600 map pixels over blocks of 256, shrinking, one map pixel, one image pixel, equal sizes; 1 | 6
+#     planes                                             test_resize_adjoint_edges[<planes>-<h>-<w>-<fh>-<fw>]
+#   lfdm_absmax_f32 (exact)  float4 path | scalar path (C 3) | ld > C | 2^21 + 1 rows of 4: the 2048-block cap, two loads in flight; maximum in the
+#     last | first element                               test_absmax_exact[<where>-<rows>-<c>-<ld>]
+#   lfdm_fix_finalize_f32 (exact)  the same shapes (the 4096-block cap); max |dout| 0 (k = 0) | 1e-30 (k clamped to 120) | 1 | 3e4 | 1e30 (k < 0)
+#                                                        test_fix_finalize_exact[<rows>-<c>-<ld>-<amax>]
+#   lfdm_batchnorm_train_{fwd,bwd}_cl_f32  y, stat, running statistics, dx, dgamma, dbeta; bn_reduce_kernel / bn_apply_kernel<0|1>: one row (variance
+#     0) | 2 | one chunk (127, 128) | two (129) | q = 4 (C 4, 16) | 8 (C 20: ragged tile) | 16 (C 36: ragged tile; 2048: 32 tiles) | 32 | 33 chunks = one |
+#     two ticket groups | the 1024-chunk cap exact and ragged (run twice) | chunks of 196 rows (the four-rows-in-flight loop at q = 4)
+#                                                        test_batchnorm_chunk_edges[<relu>-<rows>-<c>]
+#     mean >> std (the row-0 pivot), bar derived from fp32 ATen    test_batchnorm_conditioning[<mean>-<std>-<rows>-<c>]
+#     3 segments of 1 | 130 rows                         test_batchnorm_segments[<rows>-<c>]
+#     dx_add | channel slices (ld > C) of x, dy, dx_add, y, dx | both    test_batchnorm_fork_and_slices[<sliced>-<fork>]
+#     64 segments x 32 tiles (> LFDM_BN_TICKETS) | C 6 | C 2052 refused, destinations untouched    test_batchnorm_refusals[<rows>-<c>-<segments>-<msg>]
+#   lfdm_blur_down_{fwd,bwd}_f32  image smaller than the 13- / 5-tap filter | one pixel | 29 taps | ragged workgroups; contiguous | 4-channel rows with a
+#     zeroed pad channel; with | without the affine epilogue    test_blur_down_edges[<rows4>-<affine>-<scale>-<h>-<w>]
+#     filter larger than the padded input refused        test_blur_down_refuses_filter_larger_than_padded_input
+#   lfdm_grid_sample_{fwd,bwd}_f32  reflection: a few | dozens of reflections | 1 x 1 image | identity; zeros (+ dgrid): 1 x 1 image | 700 output pixels;
+#     n_div 1 | 2 | 3                                    test_grid_sample_edges[<n_div>-<reflection>-<amp>-<h>-<w>-<ho>-<wo>]
+#   lfdm_svd2x2_sym_f32 / lfdm_svd2x2_sym_bwd_f32  1 | 257 matrices (relative gap > 0.3 in every one); gu | gs | both    test_svd2x2_sym_bwd_edges[<grads>-<n>]
+#   lfdm_pool2_cl_f32  modes 0 - 5: one window | one row | one column of windows | 3 images; max: every 0 / 1 tie pattern    test_pool2_edges[<kind>-<n>-<c>-<h>-<w>]
+#   lfdm_relu_bwd_f32 (exact)  1 | 257 float4, y with +0 and -0    test_relu_bwd_exact[<n>]
+#   lfdm_l1_mean_{fwd,bwd}_f32  one float4 | two workgroups, the second with one float4 | one beyond the 1024-workgroup cap (four 256-partial trips of the
+#     last workgroup's fold); x == y elements; twice     test_l1_mean_edges[<n>]
+#   lfdm_im2col_cl_f32 (exact)  one pixel under 7 x 7 | pad 0, ldx 20 | 1 x 1 | 5 x 5 at C 12; C 20 refused    test_im2col_exact[...], test_im2col_refuses_20_channels
+#   lfdm_lfae_region_stats_f32  K 1 | 33; 4 | 255 | 256 | 600 | 4095 | 4096 pixels (1 ... 16 slots per thread, ragged); ld 1 ... 36; temperature 0.1 | 1
+#                                                        test_region_stats_edges[<temperature>-<n>-<k>-<h>-<w>-<ld>]
+#     64 x 65 | h = 1 refused                            test_region_stats_refusals[<h>-<w>]
+#   lfdm_lfae_motion_inputs_f32 + lfdm_lfae_motion_combine_f32  K 1 | 32; covariance | fixed variance; affine (+ revert_axis_swap) | identity; homography |
+#     none, one homography throwing every coordinate ~1e6 outside (`finite_ok`); 4 | 255 | 256 | 600 | 4096 pixels; pad columns zero; combine: logits x 4, one
+#     logit of 80, with | without the occlusion column   test_motion_inputs_and_combine_edges[<b>-<frames>-<k>-<h>-<w>-<covar>-<affine>-<bg>]
+#     K 33 refused                                       test_motion_inputs_refuses_33_regions
+#   NOT reached at a test-sized shape: the grid caps of warp_cl_kernel / warp_bwd_cl_kernel (65 536 / 65 535 workgroups: more than 16 M lane items per
+#   frame) and of pool2_kernel / relu_bwd_kernel / l1_mean_bwd_kernel (262 140 workgroups: more than 67 M float4), im2col_cl_kernel's (134 M float4);
+#   warp_planar_kernel<false> for a plane beyond 128 x 128 (needs 2048 such planes: 135 MB); fix_exponent's lower clamp (needs max |dout| > FLT_MAX).
 FRAME_EDGES = [1, 2, 16, 17, 32, 33, 40, 41, 48, 49, 64]
 
 
