@@ -101,6 +101,7 @@ class FlowDiffusion(nn.Module):
         checkpoint = torch.load(pretrained_pth, map_location="cpu") if pretrained_pth != "" else None
         with open(config_pth) as f:
             mp = yaml.safe_load(f)['model_params']
+        self.lfae_config = mp                     # (video_store.lfae_fingerprint: the switches no weight records)
         self.generator = Generator(num_regions=mp['num_regions'], num_channels=mp['num_channels'],
                                    revert_axis_swap=mp['revert_axis_swap'], **mp['generator_params'])
         self.region_predictor = RegionPredictor(num_regions=mp['num_regions'], num_channels=mp['num_channels'],
@@ -129,7 +130,7 @@ class FlowDiffusion(nn.Module):
             self.diffusion.text_encoder = BertTextEncoder(bert_path, use_cls=self.diffusion.text_use_bert_cls)
         for attr in ('ref_img', 'ref_img_fea', 'real_vid', 'real_out_vid', 'real_warped_vid', 'real_vid_grid',
                      'real_vid_conf', 'fake_out_vid', 'fake_warped_vid', 'fake_vid_grid', 'fake_vid_conf',
-                     'sample_out_vid', 'sample_warped_vid', 'sample_vid_grid', 'sample_vid_conf', 'sample_latent'):
+                     'sample_out_vid', 'sample_warped_vid', 'sample_vid_grid', 'sample_vid_conf', 'sample_latent', 'train_latent'):
             setattr(self, attr, None)
         self.is_train = is_train
         if self.is_train:
@@ -378,21 +379,49 @@ class FlowDiffusion(nn.Module):
         is seeded identically everywhere) and keeps its own contiguous slice - what nn.DataParallel's scatter does in the
         reference (DM/train_video_flow_diffusion_mhad_multiGPU.py:207,249)."""
         dev = next(self.unet.parameters()).device
+        ref_img, real_vid, ref_text = self._shard_of(ref_img, real_vid, ref_text)
+        self.ref_img = ref_img.to(dev)
+        self.real_vid = real_vid.to(dev)
+        self.ref_text = ref_text
+        self.train_latent = None
+
+    def _shard_of(self, ref_img, videos, ref_text):
+        """This rank's part of a global batch (set_train_input, set_train_latent): starts data parallelism when a launcher asked for it,
+        records the step's slice in `_slice` / diffusion.rank_shard and cuts the three inputs along the batch.  Without sharding the
+        inputs come back as they are."""
         self._start_auto_dp()
         self._slice = None
         if self._shard is not None:
             # torch.tensor_split semantics, like nn.DataParallel's scatter: any batch size works (the reference scripts use
             # BATCH_SIZE = 5 and no drop_last); the first b % world ranks get one video more, a rank may get none
             rank, world = self._shard
-            b = real_vid.shape[0]
+            b = videos.shape[0]
             lo = rank * (b // world) + min(rank, b % world)
             hi = lo + b // world + (1 if rank < b % world else 0)
             self._slice = (lo, hi, b)
             self.diffusion.rank_shard = self._slice
-            ref_img, real_vid = ref_img[lo:hi], real_vid[lo:hi]
+            ref_img, videos = ref_img[lo:hi], videos[lo:hi]
             ref_text = ref_text[lo:hi] if isinstance(ref_text, torch.Tensor) else list(ref_text)[lo:hi]
+        return ref_img, videos, ref_text
+
+    def set_train_latent(self, ref_img, latent, ref_text):
+        """The training input of a step from a STORED flow latent in place of set_train_input: latent (B, 3, T, S, S) in the
+        space `encode_video` returns (video_store.DeviceLatentPrep makes it from a latent store), ref_img (B, 3, H, W).  The next
+        forward() / optimize_parameters() then launches nothing of the frozen LFAE but the generator's encoder on ref_img: no region,
+        background or flow predictor, no decode (see _latent_forward).  Shards like set_train_input under data parallelism."""
+        dm = self.diffusion
+        want = (3, dm.num_frames, dm.image_size, dm.image_size)
+        if not isinstance(latent, torch.Tensor) or latent.dim() != 5 or tuple(latent.shape[1:]) != want:
+            raise ValueError("set_train_latent: latent must be a (B, %d, %d, %d, %d) tensor, got %s"
+                             % (want + (tuple(getattr(latent, "shape", ())),)))
+        if ref_img.dim() != 4 or ref_img.shape[0] != latent.shape[0]:
+            raise ValueError("set_train_latent: ref_img must be (B, 3, H, W) with the latent's batch %d, got %s"
+                             % (latent.shape[0], tuple(ref_img.shape)))
+        dev = next(self.unet.parameters()).device
+        ref_img, latent, ref_text = self._shard_of(ref_img, latent, ref_text)
         self.ref_img = ref_img.to(dev)
-        self.real_vid = real_vid.to(dev)
+        self.train_latent = latent.to(dev)
+        self.real_vid = None
         self.ref_text = ref_text
 
     def _lfae_pass(self, real_vid, ref_img, decode):
@@ -465,7 +494,9 @@ class FlowDiffusion(nn.Module):
         return out
 
     def forward(self):
-        """Reference :116-179 (inputs from set_train_input, results as attributes)."""
+        """Reference :116-179 (inputs from set_train_input, results as attributes).  After set_train_latent: _latent_forward."""
+        if self.train_latent is not None:
+            return self._latent_forward()
         out = self._train_forward(self.real_vid, self.ref_img, self.ref_text, lazy_real=self.lazy_real_decode)
         for k in ("real_vid_grid", "real_vid_conf", "ref_img_fea"):
             setattr(self, k, out[k])
@@ -479,6 +510,61 @@ class FlowDiffusion(nn.Module):
             with torch.no_grad():
                 self.rec_loss = (self.real_vid - self.fake_out_vid).abs().mean()
                 self.rec_warp_loss = (self.real_vid - self.fake_warped_vid).abs().mean()
+
+    # ------------------------------------------------------------------ the step from a stored latent
+    def _latent_forward(self):
+        """forward() after set_train_latent.  The pseudo ground truth is the stored latent, so the frozen LFAE runs only as far as the
+        diffusion's condition needs it: ref_img_fea from the generator's encoder on ref_img (the bottle_neck_feat of the online pass, bit for
+        bit), then self.diffusion(latent, ref_img_fea, ref_text) - the online step's call with the same draws in the same order, so
+        known_train, EMA, clipping and the non-finite guard work unchanged.  real_vid_grid / real_vid_conf / fake_vid_grid / fake_vid_conf
+        are set from the latent and pred_x0; the four decoded videos and the two logged numbers rec_loss / rec_warp_loss are None until
+        decode_step_logs(real_vid) is asked for them.  The backward of such a step runs on `loss` alone also with only_use_flow=False: the
+        two reconstruction terms are no_grad constants, so the gradient is the same."""
+        gen = self.generator
+        ref = self.ref_img.float().contiguous()
+        with torch.no_grad():
+            latent = self.train_latent.float().contiguous()
+            self.ref_img_fea = gen.compute_fea(ref).clone().detach()
+            maps, self.real_vid_conf = self._maps(latent)
+            self.real_vid_grid = maps[:, :2]
+        self._real_decode, self._real_out_vid, self._real_warped_vid = None, None, None
+        self.fake_out_vid = self.fake_warped_vid = None
+        self.rec_loss = self.rec_warp_loss = None
+        if self.is_train:
+            self.loss = self.diffusion(latent, self.ref_img_fea, self.ref_text)
+            with torch.no_grad():
+                maps, self.fake_vid_conf = self._maps(self.diffusion.pred_x0)
+                self.fake_vid_grid = maps[:, :2]
+
+    def decode_step_logs(self, real_vid):
+        """What a latent step leaves out, on demand (the trainer asks at --save-img-freq only): real_out_vid / real_warped_vid - the LFAE
+        decode of the stored latent -, fake_out_vid / fake_warped_vid - the decode of the step's pred_x0 - and rec_loss / rec_warp_loss
+        against real_vid (B, 3, T, H, W; the global batch under sharded data parallelism), with the expressions forward() uses for the
+        last four.  The occlusion of the real decode comes back from the latent as (ch2 + 1) * 0.5, one rounding away from the LFAE's."""
+        if self.train_latent is None or self.fake_vid_grid is None:
+            raise RuntimeError("decode_step_logs: no step from a stored latent has run - set_train_latent(...) and optimize_parameters() first")
+        gen = self.generator
+        with torch.no_grad():
+            ref = self.ref_img.float().contiguous()
+            real_vid = real_vid.to(ref.device)
+            if self._slice is not None and real_vid.shape[0] == self._slice[2]:
+                real_vid = real_vid[self._slice[0]:self._slice[1]]
+            nf, h, w = (int(v) for v in self.train_latent.shape[2:])
+            if ref.shape[0] == 0:          # a rank without videos this step
+                vid = torch.zeros(0, 3, nf, ref.shape[-2], ref.shape[-1], device=ref.device)
+                self._real_out_vid = self._real_warped_vid = self.fake_out_vid = self.fake_warped_vid = vid
+                self.rec_loss, self.rec_warp_loss = torch.zeros((), device=ref.device), torch.zeros((), device=ref.device)
+                return
+            skips = gen.encode(ref)
+            vids = []
+            for grid, latent in ((self.real_vid_grid, self.train_latent.float()), (self.fake_vid_grid, self.diffusion.pred_x0)):
+                maps = torch.cat((grid, latent[:, 2:3]), dim=1).contiguous()
+                vids.extend(gen.decode_video(ref, skips, maps[:, 0], maps[:, 1], maps[:, 2], nf, h, w, 3 * nf * h * w, h * w,
+                                             occ_scale=0.5, occ_bias=0.5))
+            self._real_decode = None
+            self._real_out_vid, self._real_warped_vid, self.fake_out_vid, self.fake_warped_vid = vids
+            self.rec_loss = (real_vid - self.fake_out_vid).abs().mean()
+            self.rec_warp_loss = (real_vid - self.fake_warped_vid).abs().mean()
 
     # real_out_vid / real_warped_vid (reference :139-140): the LFAE decode of the pseudo ground truth feeds no loss - the
     # training scripts only write it to their sample images every `save_img_freq` steps.  By default it is computed in
@@ -539,6 +625,7 @@ class FlowDiffusion(nn.Module):
         kernel) is the gradient of the mean over the global batch for any split; a rank without videos this step skips the
         model, advances the random generator like everybody else and contributes zero gradients."""
         weight, empty = 1.0, False
+        latent_step = self.train_latent is not None          # (after set_train_latent: DESIGN.md 4.13)
         if self._dp is not None and getattr(self, "_slice", None) is not None:
             lo, hi, total = self._slice
             weight, empty = (hi - lo) * self._shard[1] / float(total), hi == lo
@@ -557,6 +644,8 @@ class FlowDiffusion(nn.Module):
             self.real_vid_grid = self.fake_vid_grid = torch.zeros(0, 2, nf, s, s, device=dev)
             self.real_vid_conf = self.fake_vid_conf = torch.zeros(0, 1, nf, s, s, device=dev)
             self.ref_img_fea = torch.zeros(0, 256, s, s, device=dev)
+            if latent_step:          # as _latent_forward leaves them: decode_step_logs makes the zero-video tensors when asked
+                vid = self.rec_loss = self.rec_warp_loss = None
             self.fake_out_vid = self.fake_warped_vid = vid
             self._real_decode, self._real_out_vid, self._real_warped_vid = None, vid, vid
             self.optimizer_diff.zero_grad()
@@ -568,7 +657,8 @@ class FlowDiffusion(nn.Module):
         self.optimizer_diff.zero_grad()
         if self._dp is not None:
             self._dp.prepare()
-        total_loss = self.loss if self.only_use_flow else self.loss + self.rec_loss + self.rec_warp_loss
+        # (a latent step has no reconstruction terms: they are no_grad constants, the gradient is that of `loss` either way)
+        total_loss = self.loss if self.only_use_flow or latent_step else self.loss + self.rec_loss + self.rec_warp_loss
         (total_loss * weight if weight != 1.0 else total_loss).backward()
         if self._dp is not None:
             self._dp.finish()
@@ -608,6 +698,10 @@ class FlowDiffusionFunctional(FlowDiffusion):
         kwargs.pop("lr", None)
         super().__init__(*args, **kwargs)
         self.diffusion.per_element_loss = True
+
+    def set_train_latent(self, *args, **kwargs):
+        raise NotImplementedError("set_train_latent: the step from a stored latent is FlowDiffusion's; the functional flavour takes its "
+                                  "inputs through forward(real_vid, ref_img, ref_text)")
 
     def forward(self, real_vid, ref_img, ref_text):
         out = self._train_forward(real_vid, ref_img, ref_text)

@@ -1797,3 +1797,58 @@ def latent_resample_maps(latent, times, mode="linear", residual=False, clamp_fro
     (B, 1, T', H, W)): maps = the resampled latent, with torch.linspace(-1, 1, .) added to channels 0 (x) and 1 (y) when `residual`
     (use_residual_flow); conf = (ch2 + 1) * 0.5.  At an integer time both are _maps(latent[:, :, i]) bit for bit."""
     return _resample_call("latent_resample_maps", latent, times, mode, clamp_from, True, bool(residual), out, conf)
+
+
+# ---------------------------------------------------------------------------------------------
+# training latents gathered from a flow-latent store (csrc/latent_gather.hip, DESIGN.md 4.13)
+# ---------------------------------------------------------------------------------------------
+LATENT_DTYPES = (torch.float32, torch.float16)          # LFDM_LATENT_* = the position in this tuple
+
+
+def latent_gather(store, rows, residual, out=None):
+    """lfdm_latent_gather_f32: store (N, 3, h, w) float32 or float16, contiguous - the frozen LFAE's raw outputs per frame (grid x, grid y,
+    occlusion map) - gathered by rows (B, T) int32 into the latent (B, 3, T, h, w) float32 the diffusion denoises: bit for bit
+    FlowDiffusion._latent_of of the gathered rows (an fp16 store as store.float()) - channels 0 / 1 minus torch.linspace(-1, 1, .) when
+    `residual` (use_residual_flow), a copy otherwise; channel 2 = occ * 2 - 1.  rows may have repeats and any order and may be a host
+    tensor (checked there, then uploaded: no read-back); every entry is range-checked here, on the host, before anything is launched
+    (ValueError).  h * w % 4 == 0."""
+    lib = _lib()
+    if not isinstance(store, torch.Tensor) or store.dtype not in LATENT_DTYPES or store.dim() != 4 or store.shape[1] != 3 \
+            or not store.is_contiguous():
+        raise ValueError("latent_gather: store must be a contiguous float32 or float16 (N, 3, h, w) tensor, got %s %s"
+                         % (getattr(store, "dtype", type(store)), tuple(getattr(store, "shape", ()))))
+    _chk_dev(lib, store, out)
+    n, _, h, w = (int(v) for v in store.shape)
+    if n < 1 or h < 1 or w < 1:
+        raise ValueError("latent_gather: the store is empty, shape %s" % (tuple(store.shape),))
+    if (h * w) % 4 != 0:
+        raise ValueError("latent_gather: h * w = %d is not a multiple of 4" % (h * w))
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or rows.dim() != 2 or rows.numel() == 0:
+        raise ValueError("latent_gather: rows must be a non-empty int32 (B, T) tensor, got %s %s"
+                         % (getattr(rows, "dtype", type(rows)), tuple(getattr(rows, "shape", ()))))
+    b, t = int(rows.shape[0]), int(rows.shape[1])
+    if b > 65535 or t > 65535:
+        raise ValueError("latent_gather: at most 65535 batch elements and frames per call, got %d and %d" % (b, t))
+    lo, hi = int(rows.min()), int(rows.max())
+    if lo < 0 or hi >= n:
+        raise ValueError("latent_gather: rows holds %d .. %d, the store has rows 0 .. %d" % (lo, hi, n - 1))
+    dev = store.device
+    if rows.device != dev:
+        if rows.is_cuda:
+            raise ValueError("latent_gather: rows is on %s, the store on %s" % (rows.device, dev))
+        rows = rows.contiguous().to(dev, non_blocking=True)
+    rows = rows.contiguous()
+    shape = (b, 3, t, h, w)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() \
+            or out.device != dev:
+        raise ValueError("latent_gather: out must be a contiguous float32 %s tensor on the store's device" % (shape,))
+    for name, x in (("store", store), ("out", out)):
+        if x.data_ptr() % 16 != 0:
+            raise ValueError("latent_gather: %s is not 16-byte aligned" % name)
+    ident_x = _identity_table(w, dev) if residual else None
+    ident_y = _identity_table(h, dev) if residual else None
+    lib.check(lib.lfdm_latent_gather_f32(_p(store), LATENT_DTYPES.index(store.dtype), n, _p(rows), _p(ident_x), _p(ident_y), _p(out), b, t,
+                                         h, w, _stream(lib)), "lfdm_latent_gather_f32")
+    return out

@@ -1104,6 +1104,33 @@ int lfdm_latent_resample_f32(const float* latent, const int* idx, const float* f
                              float* out, float* conf, int batch, int channels, int frames, int out_frames, int h, int w, int mode,
                              int clamp_from, lfdm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Training latents from a flow-latent store (additive under ABI 13): the frozen LFAE's raw outputs of every frame of a
+ * data set, computed once, as a flat (store_frames, 3, h, w) array - planes: sampling grid x, grid y, occlusion map - of fp32
+ * (LFDM_LATENT_F32) or fp16 (LFDM_LATENT_F16) values.
+ *
+ * lfdm_latent_gather_f32: out (batch, 3, frames, h, w) planar fp32; out[b, :, t] is made from store[frame_index[b, t]] by what
+ * FlowDiffusion._latent_of does to the LFAE's outputs.  An fp16 value is converted to fp32 first (exact).
+ *   channels 0, 1   with ident_x (w floats) and ident_y (h floats) - DEVICE, torch.linspace(-1, 1, .) made by the caller - channel 0 is
+ *                   v - ident_x[x] and channel 1 is v - ident_y[y], one fp32 subtraction each: the residual-flow case.  Both NULL: a copy.
+ *                   One NULL and one not is refused.
+ *   channel 2       occ * 2 - 1 as two fp32 operations.  occ * 2 is exact in binary floating point, so a contracted (fused) form rounds
+ *                   the same value once all the same: the result does not depend on contraction.
+ * frame_index: DEVICE (batch, frames) int32 rows of store - a gather, repeats and any order allowed.  It is device memory the entry
+ * point cannot read: THE CALLER CHECKS that every entry lies in 0 .. store_frames - 1; the kernel clamps the row into that range, so a
+ * bad table reads a wrong frame, never outside store.  All store addressing is 64-bit (a store of 349 526 fp32 frames of 32 x 32
+ * passes 4 GiB).
+ * h * w % 4 == 0.  One thread per 4 adjacent values of one plane: one 16-byte (fp32) or 8-byte (fp16) load and one 16-byte store; grid
+ * (chunks of the 3 * h * w / 4 quads, frames, batch), frames and batch <= 65535; the row number is read once per workgroup; no atomics,
+ * no LDS, nothing depends on launch order: results are bit-identical from run to run.
+ * Refusals (LFDM_EINVAL, nothing is enqueued or written): a null or misaligned store / frame_index / out, a store_dtype that is neither
+ * code, h * w % 4 != 0, one identity table without the other, store_frames < 1, batch / frames / h / w < 1 or a grid limit exceeded. */
+/* Layout: all operands dense; store, out 16 B; frame_index, ident_x, ident_y 4 B. */
+#define LFDM_LATENT_F32 0
+#define LFDM_LATENT_F16 1
+int lfdm_latent_gather_f32(const void* store, int store_dtype, int64_t store_frames, const int* frame_index, const float* ident_x,
+                           const float* ident_y, float* out, int batch, int frames, int h, int w, lfdm_stream_t stream);
+
 /* Box calibration, not on the product path (bench.py prints it beside every timing; ABI version 7): `blocks` workgroups of four
  * wavefronts run `iters` x 4 independent v_mfma_f32_32x32x2_f32 (2 * 32 * 32 * 2 FLOP each, pseudo-random operands) and
  * record, per workgroup b, out[2b] = shader cycles and out[2b+1] = 100 MHz real-time ticks of the loop: effective clock (MHz) =

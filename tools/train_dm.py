@@ -10,6 +10,8 @@ restore semantics; one process per GPU under torchrun instead of nn.DataParallel
         # frames decoded once into a uint8 store; jitter, shrink and normalisation on the device
     python tools/train_dm.py --data DIR ... --ema-decay 0.9999 --ema-start-step 2000 --max-grad-norm 1.0 --skip-nonfinite
         # averaged weights (checkpoint entry "diffusion_ema", tools/demo.py --use-ema), clipping and the non-finite guard: DESIGN.md 4.4
+    python tools/pack_latents.py PACKED --lfae-ckpt RegionMM.pth && python tools/train_dm.py --packed PACKED --latents [--resident] ...
+        # the frozen LFAE's flow latents computed once; a step gathers them and launches no LFAE predictor or decoder
 """
 import argparse
 import contextlib
@@ -62,6 +64,10 @@ def parse_args(argv=None):
     ap.add_argument("--packed", default="", help="a store written by tools/pack_videos.py (instead of --data): batches cross to the device "
                     "as bytes and colour jitter, area shrink and normalisation run there")
     ap.add_argument("--resident", action="store_true", help="with --packed: upload the whole store once; a batch is then frame numbers")
+    ap.add_argument("--latents", action="store_true", help="with --packed: train from the flow-latent store tools/pack_latents.py wrote "
+                    "beside the frames - a step gathers the stored latents and runs nothing of the frozen LFAE but the reference frame's "
+                    "encoder; the decoded videos and loss_rec / loss_warp are computed at --save-img-freq only (DESIGN.md 4.13)")
+    ap.add_argument("--dim-mults", type=int, nargs="+", default=[1, 2, 4, 8], help="the denoiser's channel multipliers (FlowDiffusion(dim_mults=...))")
     ap.add_argument("--long-attention", action="store_true", help="windows of 65 ... 256 frames (and a mid block of up to 256 pixels per frame) on the streaming attention kernels (FlowDiffusion(long_attention=True), DESIGN.md 4.8)")
     ap.add_argument("--known-prob", type=float, default=0.0, help="> 0: random-mask training (FlowDiffusion(known_train=...), DESIGN.md 4.12) - "
                     "with this probability some frames of a training video stay clean and the loss counts the others; sample the "
@@ -81,8 +87,16 @@ def known_train(args):
     return dict(prob=args.known_prob, kinds=tuple(args.known_kinds), max_frames=args.known_max_frames, seed=args.known_seed)
 
 
-def make_dataset(args):
-    """(dataset, prep): prep is None for the host loaders, whose items are finished videos, and a video_store.DevicePrep for --packed."""
+def make_dataset(args, model=None):
+    """(dataset, prep): prep is None for the host loaders, whose items are finished videos, a video_store.DevicePrep for --packed and a
+    video_store.DeviceLatentPrep for --packed --latents (which needs `model`: the store must be its LFAE's)."""
+    if args.latents:
+        from cvpr23_lfdm_amd.video_store import DeviceLatentPrep, PackedLatents
+        if not args.packed:
+            sys.exit("--latents reads the latent store beside a packed frame store: give --packed DIR")
+        ds = PackedLatents(args.packed, image_size=args.size, num_frames=args.frames, sampling="random", jitter=True, resident=args.resident,
+                           model=model)
+        return ds, DeviceLatentPrep(ds)
     if args.packed:
         from cvpr23_lfdm_amd.video_store import DevicePrep, PackedVideos
         ds = PackedVideos(args.packed, image_size=args.size, num_frames=args.frames, sampling="random", jitter=True, resident=args.resident)
@@ -92,15 +106,23 @@ def make_dataset(args):
     return ds, None
 
 
-def main():
-    args = parse_args()
-    if not torch.cuda.is_available():
+def _emulated():
+    """True under the test suite's x86 emulation build of the kernels (tests only: the loop then runs on CPU tensors)."""
+    from cvpr23_lfdm_amd import _native
+    return _native._active is not None and _native._active.kind == "emu"
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    cuda = not _emulated()
+    if cuda and not torch.cuda.is_available():
         sys.exit("tools/train_dm.py needs a GPU: the training step is liblfdm_hip.so only")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
-    torch.cuda.set_device(local % torch.cuda.device_count())
+    if cuda:
+        torch.cuda.set_device(local % torch.cuda.device_count())
     if world > 1:
         dist.init_process_group("nccl")                      # RCCL
     # every rank must build the SAME initial UNet (parameters are initialised from torch's global generator and the
@@ -113,9 +135,11 @@ def main():
                           null_cond_prob=args.null_cond_prob, sampling_timesteps=args.preview_steps or 1000, config_pth=args.config,
                           pretrained_pth=args.lfae_ckpt, bert_path=None if args.synthetic else args.bert,     # :153-162
                           ema_decay=args.ema_decay, ema_start_step=args.ema_start_step, max_grad_norm=args.max_grad_norm,
-                          skip_nonfinite=args.skip_nonfinite, long_attention=args.long_attention, known_train=known_train(args))
+                          skip_nonfinite=args.skip_nonfinite, long_attention=args.long_attention, known_train=known_train(args),
+                          dim_mults=tuple(args.dim_mults))
     opt = model.optimizer_diff
-    model.cuda()
+    if cuda:
+        model.cuda()
     if args.synthetic:
         emb = {}
         model.diffusion.text_encoder = lambda texts: torch.stack(
@@ -139,10 +163,10 @@ def main():
     torch.manual_seed(args.seed + 1 + rank)     # per-rank streams for t / noise / null-cond mask / data order
     np.random.seed(args.seed + 1 + rank)
 
-    ds, prep = make_dataset(args)
+    ds, prep = make_dataset(args, model)
     sampler = data.distributed.DistributedSampler(ds, world, rank, shuffle=True, seed=args.seed) if world > 1 else None
     loader = data.DataLoader(ds, batch_size=args.batch_size, shuffle=sampler is None, sampler=sampler,
-                             num_workers=args.num_workers, pin_memory=True, drop_last=True)
+                             num_workers=args.num_workers, pin_memory=cuda, drop_last=True)
     per_epoch = max(1, len(loader))
     epoch = start_step // per_epoch
     sched = MultiStepLR(model.optimizer_diff, args.epoch_milestones, gamma=0.1, last_epoch=epoch - 1)         # :210-211
@@ -151,23 +175,31 @@ def main():
         if sampler is not None:
             sampler.set_epoch(epoch)
         for batch in loader:
-            if prep is None:
-                real_vids, ref_texts, real_names = batch
-                real_vids = real_vids.cuda(non_blocking=True)
+            if args.latents:                 # the stored latent and the reference frame: no video, no LFAE pass
+                (latents, ref_imgs), ref_texts, real_names, real_vids = prep(batch), batch[5], batch[6], None
+                model.set_train_latent(ref_img=ref_imgs, latent=latents, ref_text=list(ref_texts))
             else:
-                real_vids, ref_texts, real_names = prep(batch), batch[3], batch[4]
-            ref_imgs = real_vids[:, :, 0].clone().detach()                    # first frame = reference frame (:221)
-            model.set_train_input(ref_img=ref_imgs, real_vid=real_vids, ref_text=list(ref_texts))
+                if prep is None:
+                    real_vids, ref_texts, real_names = batch
+                    real_vids = real_vids.cuda(non_blocking=True)
+                else:
+                    real_vids, ref_texts, real_names = prep(batch), batch[3], batch[4]
+                ref_imgs = real_vids[:, :, 0].clone().detach()                    # first frame = reference frame (:221)
+                model.set_train_input(ref_img=ref_imgs, real_vid=real_vids, ref_text=list(ref_texts))
             model.optimize_parameters()
             step += 1
+            if args.latents and rank == 0 and step % args.save_img_freq == 0:
+                real_vids = prep.real_frames(batch)          # the batch's frames from the rows it holds, for the panel and the two logged numbers
+                model.decode_step_logs(real_vids)
             if rank == 0 and step % args.print_freq == 0:
                 dt = (timeit.default_timer() - t0) / args.print_freq
                 t0 = timeit.default_timer()
                 guard = ""                       # the device plan is read back HERE only (print frequency), never in the step
                 if opt.last_grad_norm() is not None:
                     guard = "  grad_norm %.4g  skipped %d" % (opt.last_grad_norm(), opt.skipped_steps())
+                rec = [float("nan") if v is None else float(v) for v in (model.rec_loss, model.rec_warp_loss)]      # (--latents: nan between --save-img-freq hits)
                 print("iter %d/%d  loss %.7f  loss_rec %.4f  loss_warp %.4f  lr %.2e  %.1f videos/s%s" % (
-                    step, args.final_step, float(model.loss), float(model.rec_loss), float(model.rec_warp_loss),
+                    step, args.final_step, float(model.loss), rec[0], rec[1],
                     opt.param_groups[0]["lr"], args.batch_size * world / dt, guard), flush=True)
             if rank == 0 and step % args.save_img_freq == 0:                   # the middle-frame panel of :246-275
                 mid, s = args.frames // 2, args.size
