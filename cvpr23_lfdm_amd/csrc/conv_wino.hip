@@ -438,17 +438,10 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv_wino_kernel(lfdm_co
   if (FUSE && nslab > 1) return;      // probe build only (tools/probe_wino_tail.sh; results WRONG): the launch without drain, ticket and reduce
 #endif
   if (FUSE && nslab > 1) {
-    __shared__ int s_last;
+    __shared__ unsigned s_last;
     LFDM_DRAIN_STORES();                                   // every storing wave: its slab words have left for memory
     __syncthreads();
-    if (tid == 0) {
-      unsigned* cnt = p.tile_counters + ((int64_t)by * gx + bx);
-      const bool last = lfdm_ticket_take(cnt) == (unsigned)(nslab - 1);
-      if (last) lfdm_ticket_reset(cnt);                   // ready for the next launch
-      s_last = last ? 1 : 0;
-    }
-    __syncthreads();
-    if (!s_last) return;
+    if (!lfdm_workgroup_last(p.tile_counters + ((int64_t)by * gx + bx), (unsigned)nslab, &s_last)) return;
 #if defined(LFDM_PROBE_NOTAIL) && LFDM_PROBE_NOTAIL == 2
     return;                            // probe build only: drain + ticket, but nobody reads the slabs back
 #endif

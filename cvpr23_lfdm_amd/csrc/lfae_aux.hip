@@ -261,16 +261,9 @@ __device__ Svd2 svd2x2_sym_lapack(float a, float b, float c) {
 #pragma clang fp contract(fast)
 
 __device__ __forceinline__ float block_reduce(float v, bool is_max, float* s_red /*[4]*/) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const float o = __shfl_xor(v, m);
-    v = is_max ? fmaxf(v, o) : v + o;
-  }
+  v = is_max ? wave_max(v) : wave_sum(v);
   __syncthreads();                                   // s_red free again
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const float a = s_red[0], b = s_red[1], c = s_red[2], d = s_red[3];
-  return is_max ? fmaxf(fmaxf(a, b), fmaxf(c, d)) : (a + b) + (c + d);
+  return is_max ? block4_max(v, s_red) : block4_sum(v, s_red);
 }
 
 __global__ __launch_bounds__(256) void svd2x2_sym_kernel(const float* __restrict__ abc, int64_t n, float* __restrict__ u,

@@ -226,57 +226,64 @@ __device__ __forceinline__ void lfdm_tie(f32x4& a) { asm volatile("" : "+v"(a)::
 __device__ __forceinline__ int lfdm_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 #endif
 
-// In-launch hand-off between workgroups (split-K: the last workgroup of a tile reduces the slabs).  Protocol of
-// cdna_hip_programming.md section 6 Guideline 16 (counter form): every storing wave drains its stores, one lane issues an
-// agent-scope release and takes a relaxed agent-scope ticket; the workgroup that draws the last ticket issues ONE
-// agent-scope acquire before any of its waves reads the slabs.  Placement independent (8 XCDs, non-coherent L2s).
+// In-launch hand-off between workgroups: every workgroup leaves a partial result (the payload) in global memory and takes a ticket; the
+// workgroup that draws the last ticket reads all payloads and finishes the job in a fixed order.  The protocol as the kernels run it:
+//   payload   8-byte agent-scope words, written and read ONLY through lfdm_agent_store_u64 / lfdm_agent_load_u64 (write-through sc1
+//             stores, L1-bypassing sc1 loads), or the 16-byte sc1 buffer accesses above (lfdm_buf_store_f4_sc1 / lfdm_buf_load_f4_sc1,
+//             conv_wino.hip).  Never plain stores or loads: those stay in one XCD's L2, and the 8 L2s are not coherent with each other.
+//   drain     LFDM_DRAIN_STORES() in every thread that stored payload, after its last payload store and in front of the barrier (or, with
+//             one storing thread, in front of that thread's own ticket): the stores are acknowledged at memory before the ticket moves.
+//   ticket    lfdm_ticket_last by ONE thread of the workgroup, after the barrier that follows the drains (lfdm_workgroup_last: thread 0
+//             and the broadcast of its answer).  A relaxed agent-scope RMW; no release / acquire fence anywhere.
+//   reset     the thread that draws the last ticket stores 0 into the word before anybody reads payload: the array is zero again when
+//             the launch ends, no memset between launches.
+//   stream    a ticket array belongs to ONE stream: launches that share it must be ordered.
+// WHAT THIS RESTS ON.  Relaxed agent-scope stores -> `s_waitcnt vmcnt(0)` -> relaxed ticket RMW -> relaxed agent-scope loads carry no
+// release / acquire, so the HIP / LLVM memory model promises no happens-before between payload and ticket.  The hand-off is correct on
+// gfx950 because of how that target lowers and executes it (MI355X_MICROARCH.md, "inter-workgroup visibility": sc1 stores are written
+// through and acknowledged at memory before vmcnt drops; sc1 loads and atomics are served past the per-XCD L2s; observed untorn for 8-byte
+// granules) - hardware behaviour validated on gfx950 / ROCm 7.2, not an architectural guarantee.  Hence the compile-time guard below (the
+// library is built for gfx950 only, _build.py), the 128-byte boundary lfdm_conv2d_cl_f32 rounds the split-K slab base up to (two column tiles
+// on different XCDs never share a cache line), and tests/test_ops_parity.py::test_wino_fused_reduce_stress (bit-equal to the separate
+// reduce pass over many launches under load).  Another target re-validates this or puts an agent-scope release fence in front of the
+// ticket and an agent-scope acquire fence behind the last one; no such fence is defined here because no kernel issues one.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__) && !defined(LFDM_EMU_BUILD)
+#error "fence-free hand-off (lfdm_agent_store_u64 / lfdm_agent_load_u64 / lfdm_ticket_last) validated on gfx950 only: re-validate, or add agent-scope release / acquire fences around the ticket, before building for another target"
+#endif
 #if defined(LFDM_EMU_BUILD)
 #define LFDM_DRAIN_STORES() ((void)0)
-#define LFDM_FENCE_RELEASE_AGENT() ((void)0)
-#define LFDM_FENCE_ACQUIRE_AGENT() ((void)0)
 static inline unsigned lfdm_ticket_take(unsigned* c) { return __atomic_fetch_add(c, 1u, __ATOMIC_SEQ_CST); }   // workgroups run on several OS threads
 static inline void lfdm_ticket_reset(unsigned* c) { __atomic_store_n(c, 0u, __ATOMIC_SEQ_CST); }
+static inline void lfdm_agent_store_u64(unsigned long long* p, unsigned long long v) { __atomic_store_n(p, v, __ATOMIC_SEQ_CST); }
+static inline unsigned long long lfdm_agent_load_u64(const unsigned long long* p) { return __atomic_load_n(p, __ATOMIC_SEQ_CST); }
 #else
 #define LFDM_DRAIN_STORES() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#define LFDM_FENCE_RELEASE_AGENT() __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent")
-#define LFDM_FENCE_ACQUIRE_AGENT() __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent")
 __device__ __forceinline__ unsigned lfdm_ticket_take(unsigned* c) {
   return __hip_atomic_fetch_add(c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ void lfdm_ticket_reset(unsigned* c) {
   __hip_atomic_store(c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-#endif
-
-// Agent-scope words shared by the workgroups of ONE launch without a fence (cdna_hip_programming.md section 6 Guideline 16, the "8-byte agent
-// atomics on both sides" form: write-through sc1 stores, L1-bypassing loads): payload granules and arrival counters of the cooperative
-// split-K reduce + GroupNorm kernel (norm.hip).
-// WHAT THIS RESTS ON.  Relaxed agent-scope stores -> `s_waitcnt vmcnt(0)` -> relaxed ticket RMW -> relaxed agent-scope loads carry no
-// release / acquire, so the HIP / LLVM memory model promises no happens-before between payload and ticket.  The hand-off is correct on
-// gfx950 because of how that target lowers and executes it (MI355X_MICROARCH.md, "inter-workgroup visibility": sc1 stores are written
-// through and acknowledged at memory before vmcnt drops; sc1 loads and atomics are served past the per-XCD L2s; observed untorn for 8-byte
-// granules) - hardware behaviour validated on gfx950 / ROCm 7.2, not an architectural guarantee.  Hence the compile-time guard below (the
-// library is built for gfx950 only, _build.py), the 128-byte boundary the launcher rounds every slab base up to (two column tiles on different
-// XCDs never share a cache line), and tests/test_ops_parity.py::test_wino_fused_reduce_stress (bit-equal to the separate reduce pass over
-// many launches under load).  A ticket array belongs to ONE stream: launches that share it must be ordered.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__) && !defined(LFDM_EMU_BUILD)
-#error "fence-free hand-off (lfdm_agent_store_u64 / lfdm_agent_load_u64 / lfdm_ticket_take) validated on gfx950 only: re-validate, or use LFDM_FENCE_RELEASE_AGENT / LFDM_FENCE_ACQUIRE_AGENT, before building for another target"
-#endif
-#if defined(LFDM_EMU_BUILD)
-static inline void lfdm_agent_store_u64(unsigned long long* p, unsigned long long v) { __atomic_store_n(p, v, __ATOMIC_SEQ_CST); }
-static inline unsigned long long lfdm_agent_load_u64(const unsigned long long* p) { return __atomic_load_n(p, __ATOMIC_SEQ_CST); }
-static inline unsigned lfdm_agent_load_u32(const unsigned* p) { return __atomic_load_n(p, __ATOMIC_SEQ_CST); }
-static inline void lfdm_sleep() {}
-#else
 __device__ __forceinline__ void lfdm_agent_store_u64(unsigned long long* p, unsigned long long v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ unsigned long long lfdm_agent_load_u64(const unsigned long long* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ unsigned lfdm_agent_load_u32(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void lfdm_sleep() { __builtin_amdgcn_s_sleep(2); }
 #endif
+// One thread: takes a ticket of `count`; true for the one that takes the last, which has then reset the word.
+__device__ __forceinline__ bool lfdm_ticket_last(unsigned* c, unsigned count) {
+  const bool last = lfdm_ticket_take(c) == count - 1;
+  if (last) lfdm_ticket_reset(c);
+  return last;
+}
+// All threads of a workgroup, behind the barrier that follows the drains: thread 0 takes the ticket, every thread gets its answer
+// through the LDS word `flag`.
+__device__ __forceinline__ bool lfdm_workgroup_last(unsigned* c, unsigned count, unsigned* flag) {
+  if (threadIdx.x == 0) *flag = lfdm_ticket_last(c, count) ? 1u : 0u;
+  __syncthreads();
+  return *flag != 0u;
+}
 
 // A line the instruction scheduler moves nothing across (no instruction of its own): bounds how far ahead a software pipeline written in
 // source order may be pulled - past it, hipcc requests every later stage's operands at once and pays for them in registers.
@@ -305,15 +312,45 @@ __device__ __forceinline__ void lfdm_wave_lds_sync() {
 }
 #endif
 
-__device__ __forceinline__ float wave_sum(float v) {
+// Fixed-order folds (float or double).  Wave butterfly: x + y == y + x and max is exact, so every lane ends with the same bits.
+// The fold runs in the argument's type: a double expression is reduced in double (there is no silent conversion to float), an integer
+// argument does not compile.
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
+  static_assert(std::is_floating_point<T>::value, "wave_sum: float or double");
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
   return v;
 }
-__device__ __forceinline__ float wave_max(float v) {
+__device__ __forceinline__ float lfdm_max(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ double lfdm_max(double a, double b) { return fmax(a, b); }
+template <class T>
+__device__ __forceinline__ T wave_max(T v) {
+  static_assert(std::is_floating_point<T>::value, "wave_max: float or double");
 #pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m));
+  for (int m = 32; m >= 1; m >>= 1) v = lfdm_max(v, __shfl_xor(v, m));
   return v;
+}
+// The four waves of a 256-thread workgroup through the LDS slots s[4], which nobody is still reading: `v` is the wave's result (every
+// lane holds it); every thread returns (w0 + w1) + (w2 + w3), or the maximum in the same pairing.
+__device__ __forceinline__ float block4_sum(float v, float* s) {
+  if ((threadIdx.x & (LFDM_WAVE - 1)) == 0) s[threadIdx.x / LFDM_WAVE] = v;
+  __syncthreads();
+  return (s[0] + s[1]) + (s[2] + s[3]);
+}
+__device__ __forceinline__ float block4_max(float v, float* s) {
+  if ((threadIdx.x & (LFDM_WAVE - 1)) == 0) s[threadIdx.x / LFDM_WAVE] = v;
+  __syncthreads();
+  return fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
+}
+// Fixed tree over the 256 doubles the lanes of a 256-thread workgroup stored in s[threadIdx.x]: the same pairs in the same order on
+// every run.  The sum is s[0]; ends on a barrier.
+__device__ __forceinline__ void block_tree_sum(double* s) {
+  __syncthreads();
+  for (int w = 128; w >= 1; w >>= 1) {
+    if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
+    __syncthreads();
+  }
 }
 // exp of a NON-POSITIVE argument (softmax terms exp(x - max), running-max rescales) on the hardware exponential: v_exp_f32(x * log2 e).
 // The rounding of x * log2 e grows with |x|: against expf, 1.5 ulp on [-1, 0], 8.5 ulp on [-10, -1], ~30 ulp on [-30, -10] (checked on the

@@ -45,15 +45,9 @@ __device__ __forceinline__ double metric_value(float x, double add, int domain) 
   return q == q ? (double)(int)q / 255.0 : 0.0;
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);      // x + y == y + x: every lane ends with the same bits
-  return v;
-}
-
 // Sums `v` over the workgroup: butterfly per wave, then the waves' sums in wave order.  Valid in thread 0.
 __device__ __forceinline__ double block_sum_f64(double v, double* slots) {
-  v = wave_sum_f64(v);
+  v = wave_sum(v);
   if ((threadIdx.x & (LFDM_WAVE - 1)) == 0) slots[threadIdx.x / LFDM_WAVE] = v;
   __syncthreads();
   double s = slots[0];

@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 // so the host never waits for the norm.  No floating-point atomics anywhere: the partial of workgroup b is a fixed function of
 // (g, n, gridDim) and the plan sums the partials in a fixed order, so every data-parallel rank - which holds the identical all-reduced
 // gradient buffer - derives the identical plan and applies the identical update.
-constexpr int kOptBlock = 256;
+constexpr int kOptBlock = 256;               // block4_sum / block_tree_sum (lfdm_device.h) fold four waves / 256 lanes
 constexpr int64_t kOptMaxBlocks = 4096;      // adam_kernel's launch geometry
 
 inline int64_t opt_blocks(int64_t n) { return lfdm_blocks(n >> 2, kOptBlock, kOptMaxBlocks); }
@@ -83,10 +83,8 @@ __global__ __launch_bounds__(kOptBlock) void sumsq_kernel(const float* __restric
   }
   const int64_t t = (n4 << 2) + threadIdx.x;           // tail (n % 4): the first lanes of workgroup 0
   if (blockIdx.x == 0 && t < n) a0 = fmaf(g[t], g[t], a0);
-  const float w = wave_sum((a0 + a1) + (a2 + a3));
-  if ((threadIdx.x & (LFDM_WAVE - 1)) == 0) wave_part[threadIdx.x / LFDM_WAVE] = w;
-  __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = (wave_part[0] + wave_part[1]) + (wave_part[2] + wave_part[3]);
+  const float s = block4_sum(wave_sum((a0 + a1) + (a2 + a3)), wave_part);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
 // include/lfdm_hip.h: lfdm_optim_plan (64 bytes, 16-byte aligned)
@@ -106,11 +104,7 @@ __global__ __launch_bounds__(kOptBlock) void plan_kernel(const float* __restrict
   double s = 0.0;
   for (int i = threadIdx.x; i < n_partials; i += kOptBlock) s += (double)partials[i];
   part[threadIdx.x] = s;
-  __syncthreads();
-  for (int h = kOptBlock / 2; h >= 1; h >>= 1) {
-    if ((int)threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];
-    __syncthreads();
-  }
+  block_tree_sum(part);
   if (threadIdx.x != 0) return;
   const double total_norm = (double)grad_scale * sqrt(part[0]);          // 0 when no norm pass ran (n_partials == 0)
   const bool finite = total_norm == total_norm && total_norm <= 3.4028234663852886e38;      // (inf or nan: not finite)

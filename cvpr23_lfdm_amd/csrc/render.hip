@@ -38,15 +38,6 @@ __device__ __forceinline__ void store_staged(const uint4* stage, unsigned char* 
   __syncthreads();
 }
 
-__device__ __forceinline__ double wave_max_f64(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const double o = __shfl_xor(v, m);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------------
 // io_compat.flow_to_color(warped - identity) per frame.  grid: (B, 2, T, s, s) planar, channel 0 = x; ident: linspace(-1, 1, s) as the
 // host made it (never recomputed here: the difference must be the host's, bit for bit).  The subtraction is fp32, everything behind it
@@ -82,7 +73,7 @@ __global__ __launch_bounds__(kRenderBlock) void flow_color_kernel(const float* _
     const double r = sqrt(u * u + v * v);
     m = r > m ? r : m;
   }
-  m = wave_max_f64(m);
+  m = wave_max(m);      // (m is never a NaN: `r > m` above lets none in)
   if ((threadIdx.x & (LFDM_WAVE - 1)) == 0) wave_part[threadIdx.x / LFDM_WAVE] = m;
   __syncthreads();
   double rad_max = wave_part[0];

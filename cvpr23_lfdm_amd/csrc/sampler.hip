@@ -201,14 +201,7 @@ __device__ float resolve_quantile(const unsigned* hs, Ranks rk, unsigned* s_part
 // advance_step) of every replayed step otherwise.  The ticket word is left at zero again.  (all threads of a block)
 __device__ __forceinline__ void end_of_step(unsigned* ticket, unsigned* hists, int hist_samples, int32_t* advance_dev, unsigned* s_res) {
   __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned total = gridDim.x * gridDim.y;
-    const bool last = lfdm_ticket_take(ticket) == total - 1;
-    if (last) lfdm_ticket_reset(ticket);
-    s_res[0] = last ? 1u : 0u;
-  }
-  __syncthreads();
-  if (s_res[0]) {
+  if (lfdm_workgroup_last(ticket, gridDim.x * gridDim.y, s_res)) {      // (no payload: the workgroups hand over nothing but "I am done")
     const int64_t nz = (int64_t)hist_samples * HIST_PER_SAMPLE;
     for (int64_t i = threadIdx.x; i < nz; i += 256) hists[i] = 0u;
     if (advance_dev && threadIdx.x == 0) *advance_dev += 1;

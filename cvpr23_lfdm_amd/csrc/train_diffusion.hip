@@ -11,7 +11,7 @@
 // sample (the grid-stride loop takes a second trip above TD_CAP * TD_QUADS * 256 float4 = 262 144 floats per sample).  t, the table values
 // and the first mask bytes are requested in front of the element loads; t is read on the device and clamped to the table (no host read, no
 // address outside the table whatever t holds).  No floating-point atomics, one owner per output element, no scratch.
-// The reduction (the partial-and-ticket pattern of l1_mean_fwd_kernel, train_lfae.hip): a lane sums the 16 terms of one trip in fp32 (pairwise
+// The reduction (lfdm_device.h, "In-launch hand-off between workgroups", single-writer form): a lane sums the 16 terms of one trip in fp32 (pairwise
 // inside a float4, then a chain of four) and adds that to a double; lanes -> workgroup by a fixed tree of doubles in LDS; workgroup partials
 // (S and N as doubles) are 8-byte agent-scope words; the workgroup that takes the last ticket folds each sample's partials in index order
 // and the samples in index order, in double.  Two runs on the same inputs give the same bits.
@@ -102,14 +102,7 @@ __global__ __launch_bounds__(TD_BLOCK) void train_qsample_kernel(const float* __
   }
 }
 
-// fixed tree over the 256 lanes' doubles: the same pairs in the same order on every run
-__device__ __forceinline__ void block_tree_sum(double* s) {
-  __syncthreads();
-  for (int w = TD_BLOCK / 2; w >= 1; w >>= 1) {
-    if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
-    __syncthreads();
-  }
-}
+static_assert(TD_BLOCK == 256, "block_tree_sum (lfdm_device.h) folds 256 lanes");
 
 template <bool L2>
 __device__ __forceinline__ float loss_term(float nz, float pr) {
@@ -126,7 +119,7 @@ __global__ __launch_bounds__(TD_BLOCK) void masked_loss_fwd_kernel(const float* 
                                                                    unsigned* ticket) {
   __shared__ double s_sum[TD_BLOCK];
   __shared__ double s_cnt[TD_BLOCK];
-  __shared__ int s_last;
+  __shared__ unsigned s_last;
   const unsigned b = blockIdx.y, n4 = n >> 2;
   const size_t off = (size_t)b * n;
   const int ti = table_index(t, b, t_len);
@@ -167,19 +160,16 @@ __global__ __launch_bounds__(TD_BLOCK) void masked_loss_fwd_kernel(const float* 
   s_cnt[threadIdx.x] = (double)unknown;
   block_tree_sum(s_sum);
   block_tree_sum(s_cnt);
-  // (partials as 8-byte agent-scope words: written through / read past the non-coherent L2s - no cache-wide fence, lfdm_device.h)
+  // (partials as 8-byte agent-scope words, one writer per workgroup who drains before the ticket: lfdm_device.h, "In-launch hand-off
+  // between workgroups")
   const unsigned nbx = gridDim.x, nblocks = gridDim.x * gridDim.y;
   unsigned long long* part_cnt = part + (size_t)nblocks;
   if (threadIdx.x == 0) {
     lfdm_agent_store_u64(part + (size_t)b * nbx + blockIdx.x, __builtin_bit_cast(unsigned long long, s_sum[0]));
     lfdm_agent_store_u64(part_cnt + (size_t)b * nbx + blockIdx.x, __builtin_bit_cast(unsigned long long, s_cnt[0]));
     LFDM_DRAIN_STORES();
-    const bool last = lfdm_ticket_take(ticket) == nblocks - 1;
-    if (last) lfdm_ticket_reset(ticket);
-    s_last = last ? 1 : 0;
   }
-  __syncthreads();
-  if (!s_last) return;
+  if (!lfdm_workgroup_last(ticket, nblocks, &s_last)) return;
   // the last workgroup: one lane per sample folds the sample's partials in index order, then the samples in a fixed tree
   const unsigned batch = gridDim.y;
   double mine = 0.0;

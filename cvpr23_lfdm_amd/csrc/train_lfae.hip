@@ -20,6 +20,7 @@
 #include <math.h>
 
 #include "lfdm_device.h"
+#include "warp_core.h"
 #include "../../include/lfdm_hip.h"
 
 namespace {
@@ -84,7 +85,7 @@ struct BnArgs {
 template <int MODE>
 __global__ __launch_bounds__(256) void bn_reduce_kernel(BnArgs a) {
   __shared__ float sm[2][256 * 4];
-  __shared__ int s_last;
+  __shared__ unsigned s_last;
   const int tid = threadIdx.x, q = a.q, lanes = 256 / q, tw = 4 * q;
   const int quad = tid & (q - 1), rl = tid / q;
   const int chunk = blockIdx.x, ct = blockIdx.y, seg = blockIdx.z;
@@ -154,7 +155,7 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(BnArgs a) {
   __syncthreads();
   // The chunk's (sum, sum) pair of a channel travels as ONE 8-byte agent-scope word: written through to memory by its store, read past the
   // (per-XCD, mutually non-coherent) L2s by the finalizer's load - no cache-wide release / acquire around the ticket (lfdm_device.h,
-  // guide section 6 guideline 16).  The release fence this replaces wrote back every dirty line of the XCD's L2 - the producing
+  // "In-launch hand-off between workgroups").  The release fence this replaces wrote back every dirty line of the XCD's L2 - the producing
   // convolution's output - from inside each of the 1 024+ workgroup tails: the pass ran at 0.6-1.5 TB/s (profiles/r05_p_bench_bn.txt).
   unsigned long long* p1 = reinterpret_cast<unsigned long long*>(a.part1) + ((int64_t)ct * a.nchunk + chunk) * tw;
   if (tid < tw) {
@@ -166,19 +167,12 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(BnArgs a) {
     }
     lfdm_agent_store_u64(p1 + tid, (unsigned long long)__float_as_uint(acc0) | ((unsigned long long)__float_as_uint(acc1) << 32));
   }
-  // level-1 fold by the workgroup that completes its group of BN_GROUP chunks
+  // level-1 fold by the workgroup that completes its group of BN_GROUP chunks (every storing thread drains)
   LFDM_DRAIN_STORES();
   __syncthreads();
   const int grp = chunk / BN_GROUP;
   const int c0 = grp * BN_GROUP, c1 = c0 + BN_GROUP < a.nchunk ? c0 + BN_GROUP : a.nchunk;
-  if (tid == 0) {
-    unsigned* cnt = a.tickets + ct * a.ngroups + grp;
-    const bool last = lfdm_ticket_take(cnt) == (unsigned)(c1 - c0 - 1);
-    if (last) lfdm_ticket_reset(cnt);
-    s_last = last ? 1 : 0;
-  }
-  __syncthreads();
-  if (!s_last) return;
+  if (!lfdm_workgroup_last(a.tickets + ct * a.ngroups + grp, (unsigned)(c1 - c0), &s_last)) return;
   if (tid < tw) {
     double acc0 = 0.0, acc1 = 0.0;
     const unsigned long long* base = reinterpret_cast<const unsigned long long*>(a.part1) + (int64_t)ct * a.nchunk * tw + tid;
@@ -404,31 +398,9 @@ __global__ __launch_bounds__(256) void blur_down_bwd_kernel(BlurArgs a) {
 // =====================================================================================================================================
 // grid_sample / warp backward
 // =====================================================================================================================================
-// ATen upsample_bilinear2d (align_corners=False) source index - the same arithmetic as warp.hip's forward
-__device__ __forceinline__ void resize_src(int dst, int n_in, int n_out, int& i0, int& i1, float& l1) {
-  const float scale = (float)n_in / (float)n_out;
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
-  if (src < 0.f) src = 0.f;
-  i0 = (int)src;
-  if (i0 > n_in - 1) i0 = n_in - 1;
-  i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-  l1 = src - (float)i0;
-}
-
-struct WTaps {
-  int x0, y0;
-  float wx0, wx1, wy0, wy1;
-  float occ;
-};
-
-__device__ __forceinline__ float bilerp4(const float* m, int fw, int y0, int y1, int x0, int x1, float ly, float lx) {
-  const float v00 = m[y0 * fw + x0], v01 = m[y0 * fw + x1];
-  const float v10 = m[y1 * fw + x0], v11 = m[y1 * fw + x1];
-  return (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
-}
-
-// the forward's per-pixel set-up (warp.hip: pixel_taps), frames == 1 per sample
-__device__ __forceinline__ WTaps warp_taps(const lfdm_warp_bwd_params& p, int n, int oy, int ox) {
+// the forward's per-pixel set-up (warp.hip: pixel_taps), frames == 1 per sample, the occlusion map plain (training runs the forward with
+// occ_scale 1, occ_bias 0).  Written out, like pixel_taps: see warp_core.h.
+__device__ __forceinline__ WarpTaps warp_taps(const lfdm_warp_bwd_params& p, int n, int oy, int ox, float& occ) {
   const int64_t moff = (int64_t)n * p.fsn;
   float gx, gy, o = 1.f;
   if (p.fh == p.h && p.fw == p.w) {
@@ -440,23 +412,24 @@ __device__ __forceinline__ WTaps warp_taps(const lfdm_warp_bwd_params& p, int n,
     float ly, lx;
     resize_src(oy, p.fh, p.h, y0, y1, ly);
     resize_src(ox, p.fw, p.w, x0, x1, lx);
-    gx = bilerp4(p.flow_x + moff, p.fw, y0, y1, x0, x1, ly, lx);
-    gy = bilerp4(p.flow_y + moff, p.fw, y0, y1, x0, x1, ly, lx);
-    if (p.occ) o = bilerp4(p.occ + moff, p.fw, y0, y1, x0, x1, ly, lx);
+    gx = bilerp(p.flow_x + moff, p.fw, y0, y1, x0, x1, ly, lx);
+    gy = bilerp(p.flow_y + moff, p.fw, y0, y1, x0, x1, ly, lx);
+    if (p.occ) o = bilerp(p.occ + moff, p.fw, y0, y1, x0, x1, ly, lx);
   }
+  occ = o;
+  // (taps_at(unnormalise(..)) of warp_core.h, written out: through the helpers the blends above are packed differently)
   float ix = ((gx + 1.f) * (float)p.w - 1.f) * 0.5f;
   float iy = ((gy + 1.f) * (float)p.h - 1.f) * 0.5f;
   ix = fminf(fmaxf(ix, -1.0e6f), 1.0e6f);
   iy = fminf(fmaxf(iy, -1.0e6f), 1.0e6f);
   const float fx = floorf(ix), fy = floorf(iy);
-  WTaps r;
+  WarpTaps r;
   r.x0 = (int)fx;
   r.y0 = (int)fy;
   r.wx1 = ix - fx;
   r.wx0 = (fx + 1.f) - ix;
   r.wy1 = iy - fy;
   r.wy0 = (fy + 1.f) - iy;
-  r.occ = o;
   return r;
 }
 
@@ -517,13 +490,8 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ x
       if (v > m) m = v;
     }
   }
-  m = wave_max(m);
-  if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    m = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
-    atomicMax(out, __float_as_uint(m));
-  }
+  m = block4_max(wave_max(m), s_m);
+  if (threadIdx.x == 0) atomicMax(out, __float_as_uint(m));
 }
 
 // fixed-point accumulator -> float (+= nothing: plain store), accumulator re-zeroed for the next call.  The LAST workgroup also clears
@@ -539,7 +507,7 @@ __global__ __launch_bounds__(256) void fix_finalize_kernel(long long* __restrict
     out[r * ld + (i - r * c)] = (float)ldexp((double)q, -k);
   }
   __syncthreads();
-  if (threadIdx.x == 0) {
+  if (threadIdx.x == 0) {      // lfdm_ticket_last (lfdm_device.h) written out: through the helper this kernel measured slower; no payload, no drain
     if (lfdm_ticket_take(ticket) == gridDim.x - 1) {
       lfdm_ticket_reset(ticket);
       *amax_bits = 0u;
@@ -570,8 +538,9 @@ __global__ __launch_bounds__(256) void warp_bwd_cl_kernel(lfdm_warp_bwd_params p
     const int64_t gp = (int64_t)n * hw + pix;
     float dfx = 0.f, dfy = 0.f, dob = 0.f;
     if (live) {
-      const WTaps tp = warp_taps(p, n, oy, ox);
-      const float o = tp.occ, om = 1.f - o;
+      float o;
+      const WarpTaps tp = warp_taps(p, n, oy, ox, o);
+      const float om = 1.f - o;
       float d[4], pv[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int i = 0; i < 4; ++i) d[i] = p.dout[gp * p.ld_dout + c + i * g];
@@ -583,6 +552,8 @@ __global__ __launch_bounds__(256) void warp_bwd_cl_kernel(lfdm_warp_bwd_params p
 #pragma unroll
         for (int i = 0; i < 4; ++i) p.dprev[gp * p.ld_dprev + c + i * g] = d[i] * om;
       }
+      // taps, weights and tap gradients written out (as in warp_bwd_px_kernel), not through warp_core.h's tap_* helpers: behind them
+      // the source and map gradients of both kernels changed bits on the MI355X (profiles/glue_core_refactor_ab.txt)
       float v[4][4];
       bool in[4];
 #pragma unroll
@@ -644,9 +615,10 @@ __global__ __launch_bounds__(256) void warp_bwd_px_kernel(lfdm_warp_bwd_params p
   const int pix = blockIdx.x * 256 + threadIdx.x;
   if (pix >= hw) return;
   const int oy = pix / p.w, ox = pix - oy * p.w;
-  const WTaps tp = warp_taps(p, n, oy, ox);
-  const float o = tp.occ, om = 1.f - o;
-  const float wk[4] = {tp.wx0 * tp.wy0, tp.wx1 * tp.wy0, tp.wx0 * tp.wy1, tp.wx1 * tp.wy1};
+  float o;
+  const WarpTaps tp = warp_taps(p, n, oy, ox, o);
+  const float om = 1.f - o;
+  const float wk[4] = {tp.wx0 * tp.wy0, tp.wx1 * tp.wy0, tp.wx0 * tp.wy1, tp.wx1 * tp.wy1};      // (written out: see warp_bwd_cl_kernel)
   bool in[4];
   int64_t off[4];
 #pragma unroll
@@ -745,25 +717,20 @@ __global__ __launch_bounds__(256) void grid_sample_kernel(GsArgs a) {
   if (o >= a.ho * a.wo) return;
   const int oy = o / a.wo, ox = o - oy * a.wo;
   const float* gp = a.grid + ((int64_t)n * a.ho * a.wo + o) * 2;
-  float ix = ((gp[0] + 1.f) * (float)a.w - 1.f) * 0.5f;
-  float iy = ((gp[1] + 1.f) * (float)a.h - 1.f) * 0.5f;
+  float ix = unnormalise(gp[0], a.w), iy = unnormalise(gp[1], a.h);
   if (a.pad_mode == 1) {
     ix = reflect_coord(ix, a.w);
     iy = reflect_coord(iy, a.h);
   }
-  ix = fminf(fmaxf(ix, -1.0e6f), 1.0e6f);
-  iy = fminf(fmaxf(iy, -1.0e6f), 1.0e6f);
-  const float fx = floorf(ix), fy = floorf(iy);
-  const int x0 = (int)fx, y0 = (int)fy;
-  const float wx1 = ix - fx, wx0 = (fx + 1.f) - ix, wy1 = iy - fy, wy0 = (fy + 1.f) - iy;
-  const float wk[4] = {wx0 * wy0, wx1 * wy0, wx0 * wy1, wx1 * wy1};
+  const WarpTaps tp = taps_at(ix, iy);
+  float wk[4];
   bool in[4];
   int64_t off[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const int yy = y0 + (k >> 1), xx = x0 + (k & 1);
-    in[k] = yy >= 0 && yy < a.h && xx >= 0 && xx < a.w;
-    off[k] = in[k] ? yy * a.xs_h + xx * a.xs_w : 0;
+    in[k] = tap_in(tp, k, a.h, a.w);
+    wk[k] = tap_weight(tp, k, in[k]);
+    off[k] = tap_offset(tp, k, in[k], a.xs_h, a.xs_w);
   }
   const float* sb = a.x + (int64_t)(n / a.n_div) * a.xs_n;
   float dfx = 0.f, dfy = 0.f;
@@ -774,12 +741,12 @@ __global__ __launch_bounds__(256) void grid_sample_kernel(GsArgs a) {
     if (!BWD) {
       float acc = 0.f;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) acc = fmaf(v[k], in[k] ? wk[k] : 0.f, acc);
+      for (int k = 0; k < 4; ++k) acc = fmaf(v[k], wk[k], acc);
       a.out[n * a.os_n + c * a.os_c + oy * a.os_h + ox * a.os_w] = acc;
     } else {
       const float d = a.dout[n * a.os_n + c * a.os_c + oy * a.os_h + ox * a.os_w];
-      dfx = fmaf(d, (v[1] - v[0]) * wy0 + (v[3] - v[2]) * wy1, dfx);
-      dfy = fmaf(d, (v[2] - v[0]) * wx0 + (v[3] - v[1]) * wx1, dfy);
+      dfx = fmaf(d, tap_grad_x(tp, v[0], v[1], v[2], v[3]), dfx);
+      dfy = fmaf(d, tap_grad_y(tp, v[0], v[1], v[2], v[3]), dfy);
     }
   }
   if (BWD) {
@@ -909,26 +876,21 @@ constexpr int L1_BLOCKS = 1024;
 __global__ __launch_bounds__(256) void l1_mean_fwd_kernel(const float4* __restrict__ x, const float4* __restrict__ y, int64_t n4, float scale,
                                                           float* __restrict__ partial, unsigned* ticket, float* __restrict__ out) {
   __shared__ float s_p[4];
-  __shared__ int s_last;
+  __shared__ unsigned s_last;
   float acc = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
     const float4 a = x[i], b = y[i];
     acc += (fabsf(a.x - b.x) + fabsf(a.y - b.y)) + (fabsf(a.z - b.z) + fabsf(a.w - b.w));
   }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) s_p[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  // (partials as 8-byte agent-scope words: written through / read past the non-coherent L2s - no cache-wide fence, see bn_reduce_kernel)
+  acc = block4_sum(wave_sum(acc), s_p);
+  // (partials as 8-byte agent-scope words, one writer per workgroup who drains before the ticket: lfdm_device.h, "In-launch hand-off
+  // between workgroups")
   unsigned long long* part = reinterpret_cast<unsigned long long*>(partial);
   if (threadIdx.x == 0) {
-    lfdm_agent_store_u64(part + blockIdx.x, (unsigned long long)__float_as_uint((s_p[0] + s_p[1]) + (s_p[2] + s_p[3])));
+    lfdm_agent_store_u64(part + blockIdx.x, (unsigned long long)__float_as_uint(acc));
     LFDM_DRAIN_STORES();
-    const bool last = lfdm_ticket_take(ticket) == gridDim.x - 1;
-    if (last) lfdm_ticket_reset(ticket);
-    s_last = last ? 1 : 0;
   }
-  __syncthreads();
-  if (!s_last) return;
+  if (!lfdm_workgroup_last(ticket, gridDim.x, &s_last)) return;
   double t = 0.0;
   for (unsigned i = threadIdx.x; i < gridDim.x; i += 256) t += (double)__uint_as_float((unsigned)lfdm_agent_load_u64(part + i));
   // fixed order: lane-strided partial sums folded through a wavefront reduction of doubles in LDS

@@ -13,35 +13,14 @@
 #include <stdlib.h>
 
 #include "lfdm_device.h"
+#include "warp_core.h"
 #include "../../include/lfdm_hip.h"
 
 namespace {
 
-struct PixelTaps {
-  int x0, y0;          // north-west tap (may be out of range)
-  float wx0, wx1, wy0, wy1;
-  float occ;
-};
-
-// ATen upsample_bilinear2d (align_corners=False) source index
-__device__ __forceinline__ void resize_src(int dst, int n_in, int n_out, int& i0, int& i1, float& l1) {
-  const float scale = (float)n_in / (float)n_out;
-  float src = scale * ((float)dst + 0.5f) - 0.5f;
-  if (src < 0.f) src = 0.f;
-  i0 = (int)src;
-  if (i0 > n_in - 1) i0 = n_in - 1;
-  i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-  l1 = src - (float)i0;
-}
-
-__device__ __forceinline__ float bilerp(const float* m, int fw, int y0, int y1, int x0, int x1,
-                                        float ly, float lx) {
-  const float v00 = m[y0 * fw + x0], v01 = m[y0 * fw + x1];
-  const float v10 = m[y1 * fw + x0], v11 = m[y1 * fw + x1];
-  return (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
-}
-
-__device__ __forceinline__ PixelTaps pixel_taps(const lfdm_warp_params& p, int b, int t, int oy, int ox) {
+// The taps of output pixel (oy, ox) of frame (b, t) and its occlusion (1 without a map): the sampling grid and the occlusion map resized
+// to (h, w) on the fly.  Written out, like warp_taps of train_lfae.hip: see warp_core.h.
+__device__ __forceinline__ WarpTaps pixel_taps(const lfdm_warp_params& p, int b, int t, int oy, int ox, float& occ) {
   const int64_t moff = (int64_t)b * p.fsb + (int64_t)t * p.fst;
   int y0, y1, x0, x1;
   float ly, lx;
@@ -55,8 +34,7 @@ __device__ __forceinline__ PixelTaps pixel_taps(const lfdm_warp_params& p, int b
     gx = bilerp(p.flow_x + moff, p.fw, y0, y1, x0, x1, ly, lx);
     gy = bilerp(p.flow_y + moff, p.fw, y0, y1, x0, x1, ly, lx);
   }
-  PixelTaps r;
-  r.occ = 1.f;
+  occ = 1.f;
   if (p.occ) {
     float o;
     if (p.fh == p.h && p.fw == p.w) o = p.occ[moff + oy * p.fw + ox] * p.occ_scale + p.occ_bias;
@@ -70,22 +48,9 @@ __device__ __forceinline__ PixelTaps pixel_taps(const lfdm_warp_params& p, int b
       const float v11 = m[y1 * p.fw + x1] * p.occ_scale + p.occ_bias;
       o = (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
     }
-    r.occ = o;
+    occ = o;
   }
-  // grid_sample unnormalise (align_corners=False)
-  float ix = ((gx + 1.f) * (float)p.w - 1.f) * 0.5f;
-  float iy = ((gy + 1.f) * (float)p.h - 1.f) * 0.5f;
-  // far-out-of-range samples contribute zeros either way; keep the int conversion defined
-  ix = fminf(fmaxf(ix, -1.0e6f), 1.0e6f);
-  iy = fminf(fmaxf(iy, -1.0e6f), 1.0e6f);
-  const float fx = floorf(ix), fy = floorf(iy);
-  r.x0 = (int)fx;
-  r.y0 = (int)fy;
-  r.wx1 = ix - fx;
-  r.wx0 = (fx + 1.f) - ix;
-  r.wy1 = iy - fy;
-  r.wy0 = (fy + 1.f) - iy;
-  return r;
+  return taps_at(unnormalise(gx, p.w), unnormalise(gy, p.h));
 }
 
 // ---------------- channels-last ----------------
@@ -108,17 +73,16 @@ __global__ __launch_bounds__(256) void warp_cl_kernel(lfdm_warp_params p) {
     const int64_t gp = (int64_t)n * hw + pix;   // output pixel row
     const int b = n / p.frames, t = n - b * p.frames;
     const int oy = pix / p.w, ox = pix - oy * p.w;
-    const PixelTaps tp = pixel_taps(p, b, t, oy, ox);
+    float o;
+    const WarpTaps tp = pixel_taps(p, b, t, oy, ox, o);
     const float* sb = p.src + (int64_t)b * hw * p.ld_src + c;
-    // tap offsets/weights (weight 0 + clamped address for out-of-range taps: zeros padding)
     float wgt[4];
     int64_t off[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const int yy = tp.y0 + (k >> 1), xx = tp.x0 + (k & 1);
-      const bool in = yy >= 0 && yy < p.h && xx >= 0 && xx < p.w;
-      wgt[k] = in ? ((k & 1) ? tp.wx1 : tp.wx0) * ((k >> 1) ? tp.wy1 : tp.wy0) : 0.f;
-      off[k] = in ? (int64_t)(yy * p.w + xx) * p.ld_src : 0;
+      const bool in = tap_in(tp, k, p.h, p.w);
+      wgt[k] = tap_weight(tp, k, in);
+      off[k] = (int64_t)tap_offset(tp, k, in, p.w, 1) * p.ld_src;
     }
     float4 pv[R];
     if (p.prev) {
@@ -130,7 +94,7 @@ __global__ __launch_bounds__(256) void warp_cl_kernel(lfdm_warp_params p) {
     for (int r = 0; r < R; ++r)
 #pragma unroll
       for (int k = 0; k < 4; ++k) v[r][k] = *reinterpret_cast<const float4*>(sb + off[k] + r * 4 * g);
-    const float o = tp.occ, om = 1.f - o;
+    const float om = 1.f - o;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -178,7 +142,9 @@ __global__ __launch_bounds__(256) void warp_planar_kernel(lfdm_warp_params p, in
     const int64_t obase = (((int64_t)b * p.c + c) * p.frames + t) * hw;
     for (int pix = threadIdx.x; pix < hw; pix += 256) {
       const int oy = pix / p.w, ox = pix - oy * p.w;
-      const PixelTaps tp = pixel_taps(p, b, t, oy, ox);
+      float o;
+      const WarpTaps tp = pixel_taps(p, b, t, oy, ox, o);
+      // skip form, not tap_weight's weight-0 form: an out-of-range tap is never read (LDS plane), and 0 * a non-finite S[0] is not 0
       float acc = 0.f;
 #pragma unroll
       for (int dy = 0; dy < 2; ++dy) {
@@ -193,7 +159,6 @@ __global__ __launch_bounds__(256) void warp_planar_kernel(lfdm_warp_params p, in
         }
       }
       if (p.occ) {
-        const float o = tp.occ;
         if (p.prev) {
           const float pv = p.prev_is_cl
                                ? p.prev[(((int64_t)b * p.frames + t) * hw + pix) * p.ld_prev + c]
@@ -218,19 +183,18 @@ __global__ __launch_bounds__(256) void warp_planar_pixel_kernel(lfdm_warp_params
   const int n = blockIdx.z;
   const int b = n / p.frames, t = n - b * p.frames;
   const int oy = pix / p.w, ox = pix - oy * p.w;
-  const PixelTaps tp = pixel_taps(p, b, t, oy, ox);
+  float o;
+  const WarpTaps tp = pixel_taps(p, b, t, oy, ox, o);
   float wgt[4];
   int off[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const int yy = tp.y0 + (k >> 1), xx = tp.x0 + (k & 1);
-    const bool in = yy >= 0 && yy < p.h && xx >= 0 && xx < p.w;
-    wgt[k] = in ? ((k & 1) ? tp.wx1 : tp.wx0) * ((k >> 1) ? tp.wy1 : tp.wy0) : 0.f;
-    off[k] = in ? yy * p.w + xx : 0;
+    const bool in = tap_in(tp, k, p.h, p.w);
+    wgt[k] = tap_weight(tp, k, in);
+    off[k] = tap_offset(tp, k, in, p.w, 1);
   }
   const int c0 = blockIdx.y * 4;
   const int c1 = c0 + 4 < p.c ? c0 + 4 : p.c;
-  const float o = tp.occ;
   for (int c = c0; c < c1; ++c) {
     const float* S = p.src + ((int64_t)b * p.c + c) * hw;
     float acc = 0.f;

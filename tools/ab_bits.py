@@ -2,11 +2,11 @@
 """Same bits?  Runs a fixed list of calls on seeded inputs under ONE build of the kernels and writes one line per output tensor -
 name, shape, SHA-256 of its bytes - so that two builds (a refactor and its parent commit) can be compared line by line.
 
-    tools/ab_bits.py run OUT.txt [--emu [LIB]] [--set conv|attention|norm|sampler]
+    tools/ab_bits.py run OUT.txt [--emu [LIB]] [--set conv|attention|norm|sampler|glue]
                                                          this process, the library LFDM_HIP_LIB names (default: the in-tree one) on the GPU,
                                                          or an emulator library on the CPU (default: the in-tree one)
     tools/ab_bits.py diff A.txt B.txt                    exit status 1 when any line differs or is missing
-    tools/ab_bits.py ab BASE_LIB OUT_DIR [--emu] [--new LIB] [--timeout S] [--set conv|attention|norm|sampler]
+    tools/ab_bits.py ab BASE_LIB OUT_DIR [--emu] [--new LIB] [--timeout S] [--set conv|attention|norm|sampler|glue]
                                                          `run` under BASE_LIB, then under the in-tree library (or --new), each in a fresh child
                                                          process with its own time limit, one after the other; stops at the first non-zero
                                                          exit status; then `diff`
@@ -63,6 +63,28 @@ SETS = {
         ("tests/test_known_elements.py", "test_known_elements_step or test_known_blend_elem or test_frame_constant_element_mask_is_the_frame_mask"),
         ("tests/test_counter_noise.py", "test_sampler_step_counter_is_the_loading_step"),
     ], "not refuse"),
+    # glue: the kernels around the MFMA kernels that share csrc/warp_core.h (the warps forward and backward, grid_sample, the resize
+    # adjoint) or end in the workgroup hand-off and the fixed-order folds of csrc/lfdm_device.h (BatchNorm, l1_mean, the fixed-point
+    # finalize, the masked loss, the sampler's end of step, the gradient norm, the metrics and the flow colours)
+    # The gradients are lines too: the recorder wraps forward and backward of the autograd Functions of the ops modules (dprev, the folded map
+    # gradients, the fixed-point source gradient after finalize, dgrid, dx) and FlatAdam.step (every flat buffer after the step).
+    "glue": ([
+        ("tests/test_lfae_ops.py", "test_apply_optical or test_grid_sample or test_batchnorm or test_l1_mean"),
+        ("tests/test_lfae_edges.py",
+         "test_warp_ or test_apply_optical_ or test_resize_adjoint_edges or test_grid_sample_edges or test_absmax_exact or "
+         "test_fix_finalize_exact or test_batchnorm_ or test_l1_mean_edges or test_region_stats_edges"),
+        ("tests/test_ops_parity.py", "test_warp_cl or test_warp_planar"),
+        ("tests/test_train_known.py", "test_masked_loss"),
+        ("tests/test_optim_guarded.py",
+         "test_ema_alone or test_clipping_alone or test_nonfinite_guard or test_guard_off_lets_the_value_through or "
+         "test_norm_accuracy_and_dispatch_edges or test_guarded_step_tail_elements"),
+        ("tests/test_metrics.py",
+         "test_video_metrics_match_both_references or test_uint8_domain_is_the_bytes_of_sample_img or test_identical_operands_are_exact or "
+         "test_constant_frames or test_psnr or test_deterministic_and_independent_of_the_batch or test_flow_metrics"),
+        ("tests/test_render.py",
+         "test_image_panels_are_sample_img or test_conf_panel_is_conf2fig or test_flow_colour or test_flow_panel_is_the_resized_colour_image or "
+         "test_strip_panels_land_in_their_columns or test_strip_batch_elements_are_independent"),
+    ], "not refusals"),
 }
 ARGUMENTS_TOO = {"sampler"}      # sets whose calls write their results in place
 
@@ -111,6 +133,27 @@ class Recorder:
             if (callable(f) and not fname.startswith("_") and getattr(f, "__module__", None) == mod.__name__ and not isinstance(f, type)
                     and fname not in ("empty", "conv_params", "sampler_ws")):      # (uninitialised buffers, argument records)
                 setattr(mod, fname, make(fname, f))
+            elif isinstance(f, type) and issubclass(f, torch.autograd.Function) and f.__module__ == mod.__name__:
+                # autograd looks forward / backward up on the class at every call: the gradients a backward returns become lines
+                for meth in ("forward", "backward"):
+                    setattr(f, meth, staticmethod(make("%s.%s" % (fname, meth), getattr(f, meth))))
+
+    def wrap_optimizer(self, cls):
+        """every flat buffer of the optimizer (parameters, moments, average, plan, norm partials) after each step"""
+        import torch
+        step = cls.step
+
+        def g(opt, *a, **kw):
+            r = step(opt, *a, **kw)
+            self.ncall += 1
+            before = len(self.lines)
+            for gi, fl in enumerate(opt._flat or []):
+                for key in sorted(k for k, v in fl.items() if isinstance(v, torch.Tensor) and k != "g"):
+                    self.record("%s#%d.%s.step#%d.%s" % (self.test, self.ncall, cls.__name__, gi, key), fl[key])
+            # (_flat is the optimizer's private layout: if it is renamed, stop here rather than compare nothing)
+            assert len(self.lines) - before >= 3, "%s.step: parameters and both moments not found in _flat" % cls.__name__
+            return r
+        cls.step = g
 
     def pytest_sessionstart(self, session):
         sys.path.insert(0, R)
@@ -120,6 +163,8 @@ class Recorder:
         self.wrap(ops)
         self.wrap(train_ops)
         self.wrap(lfae_ops)
+        from cvpr23_lfdm_amd.optim import FlatAdam
+        self.wrap_optimizer(FlatAdam)
 
     def pytest_runtest_setup(self, item):
         self.test, self.ncall = item.nodeid.split("::", 1)[1], 0

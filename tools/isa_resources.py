@@ -5,8 +5,12 @@ LFDM_ISA_FLAGS in the environment adds compiler flags (a probe build's -D switch
 
     tools/isa_resources.py scan OUT.json [--root DIR] file.hip ...     DIR: the checkout whose cvpr23_lfdm_amd/csrc holds the files (default: this tree)
     tools/isa_resources.py table PARENT.json TREE.json                 one line per kernel, 'a->b' where the two differ (the format of
-                                                                       profiles/conv_core_refactor_ab.txt section 1); exit status 1 when a
-                                                                       kernel gained scratch or lost a wave of occupancy"""
+                                                                       profiles/conv_core_refactor_ab.txt section 1), 'identical' where the
+                                                                       kernel body disassembles identically (comments and label numbers
+                                                                       aside), and the condition line; exit status 1 when the condition
+                                                                       is False (a kernel gained scratch, lost a wave of occupancy or
+                                                                       changed its LDS size)"""
+import hashlib
 import json
 import os
 import re
@@ -47,14 +51,16 @@ def scan(root, files):
                 "VGPRs": note("NumVgprs") if note("TotalNumVgprs") < 0 else note("TotalNumVgprs"), "scratch": note("ScratchSize"),
                 "LDS": note("LDSByteSize"), "occ": note(r"Occupancy"), "codeLen": note("codeLenInByte"), "insts": len(insts),
                 "MFMA": sum(i.startswith("v_mfma") for i in insts), "s_nop": sum(i.startswith("s_nop") for i in insts),
-                "branch": sum(i.startswith(("s_cbranch", "s_branch")) for i in insts)}
+                "branch": sum(i.startswith(("s_cbranch", "s_branch")) for i in insts),
+                # the kernel body, comments and label numbers aside: equal hashes = 'identical' in the table
+                "isa": hashlib.sha256("\n".join(re.sub(r"\.LBB\d+_\d+", ".LBB", re.sub(r"\s*;.*$", "", i)) for i in insts).encode()).hexdigest()[:16]}
     return res
 
 
 def table(pa, tr):
     A, B = json.load(open(pa)), json.load(open(tr))
-    bad = 0
-    print("%-16s %-58s " % ("file", "kernel") + " ".join("%-14s" % f for f in FIELDS))
+    bad = lds = 0
+    print("%-16s %-58s " % ("file", "kernel") + " ".join("%-14s" % f for f in FIELDS) + " ISA vs parent")
     # a kernel that gained a trailing bool template argument is set against the parent's kernel without it
     parent_of = {k: k if k in A else re.sub(r", (true|false)>$", ">", k) for k in B}
     for k in sorted(set(B) | (set(A) - set(parent_of.values()))):
@@ -64,12 +70,17 @@ def table(pa, tr):
         for fld in FIELDS:
             x, y = (a or {}).get(fld, "-"), (b or {}).get(fld, "-")
             cells.append("%-14s" % (x if x == y else "%s->%s" % (x, y)))
+        if a and b and "isa" in a and "isa" in b:
+            cells.append("identical" if a["isa"] == b["isa"] else "differs  ")
         if a and b and (b["scratch"] > a["scratch"] or b["occ"] < a["occ"]):
             bad += 1
             cells.append("WORSE")
+        if a and b and b["LDS"] != a["LDS"]:
+            lds += 1
         print("%-16s %-58s " % (f, kern) + " ".join(cells))
-    print("# %d kernels, %d gained scratch or lost occupancy" % (len(B), bad))
-    return 1 if bad else 0
+    print("# %d kernels, %d gained scratch or lost occupancy, %d with another LDS size" % (len(B), bad, lds))
+    print("condition (no kernel gains scratch, none loses a wave of occupancy, LDS equal everywhere): %s" % (bad == 0 and lds == 0))
+    return 1 if bad or lds else 0
 
 
 if __name__ == "__main__":
