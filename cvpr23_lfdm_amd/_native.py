@@ -286,6 +286,11 @@ _SIGNATURES = {
     "lfdm_masked_loss_fwd_f32": (i32, [f32p, f32p, f32p, C.c_void_p, f32p, f32p, i32, C.c_void_p, C.c_void_p, i32, i64, i32, f32p, f32p, f32p,
                                        i32, i64, C.c_void_p, sz, C.c_void_p, stream_t]),
     "lfdm_masked_loss_bwd_f32": (i32, [f32p, f32p, C.c_void_p, C.c_void_p, i32, i64, i32, f32p, f32p, f32p, i32, i64, stream_t]),
+    # ---- training objectives and loss weights (additive, ABI stays 13)
+    "lfdm_objective_loss_fwd_f32": (i32, [i32, f32p, f32p, f32p, f32p, C.c_void_p, f32p, f32p, f32p, f32p, f32p, i32, C.c_void_p, C.c_void_p,
+                                          i32, i64, i32, f32p, f32p, f32p, f32p, i32, i64, C.c_void_p, sz, C.c_void_p, stream_t]),
+    "lfdm_objective_loss_bwd_f32": (i32, [i32, f32p, f32p, f32p, C.c_void_p, f32p, f32p, f32p, i32, C.c_void_p, C.c_void_p, i32, i64, i32,
+                                          f32p, f32p, f32p, i32, i64, stream_t]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

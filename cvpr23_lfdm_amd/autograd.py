@@ -536,5 +536,37 @@ def masked_diffusion_loss(pred, noise, x_noisy, t, r_tab, m_tab, mask=None, loss
     return MaskedDiffusionLoss.apply(pred, noise, x_noisy, t, r_tab, m_tab, mask, loss_type)
 
 
+class ObjectiveDiffusionLoss(Function):
+    """MaskedDiffusionLoss for a training objective and a per-timestep weight: (1 / B) sum_b w[t_b] S_b / max(N_b, 1) as
+    a 0-dim tensor, and - not differentiable - pred_x0 and the (B,) unweighted per-sample means from the same launch.  The gradient goes to
+    `out`, the denoiser's output, only.  tabs: (a, s, r, m, w) with w None for weight 1; x_start / noise may be None where the objective
+    does not use them."""
+
+    @staticmethod
+    def forward(ctx, out, x_start, noise, x_noisy, t, tabs, mask, loss_type, objective):
+        out = out.detach()
+        kw = {} if mask is None else dict(frame_mask=mask) if mask.dim() == 2 else dict(elem_mask=mask)
+        a, s, r, m, w = tabs
+        loss, inv_count, sample_loss, pred_x0 = ops.objective_loss_fwd(objective, x_start, noise, out, x_noisy, t, a, s, r, m, w,
+                                                                       loss_type=loss_type, **kw)
+        ctx.save_for_backward(out, inv_count, t, a, s)
+        ctx.meta = (kw, loss_type, objective, x_start, noise, w)
+        ctx.mark_non_differentiable(pred_x0, sample_loss)
+        return loss.reshape(()), pred_x0, sample_loss
+
+    @staticmethod
+    def backward(ctx, gout, _x0, _sl):
+        out, inv_count, t, a, s = ctx.saved_tensors
+        kw, loss_type, objective, x_start, noise, w = ctx.meta
+        g = gout.detach().to(torch.float32).reshape(1).contiguous()
+        dout = ops.objective_loss_bwd(objective, x_start, noise, out, t, a, s, w, inv_count, g, loss_type=loss_type, **kw)
+        return dout, None, None, None, None, None, None, None, None
+
+
+def objective_diffusion_loss(out, x_start, noise, x_noisy, t, tabs, mask=None, loss_type="l1", objective="pred_noise"):
+    """-> (loss, pred_x0, sample_loss) through ObjectiveDiffusionLoss."""
+    return ObjectiveDiffusionLoss.apply(out, x_start, noise, x_noisy, t, tuple(tabs), mask, loss_type, objective)
+
+
 def conv_cl(x0, weight, bias, *, x1=None, residual=None, **geom):
     return ConvCL.apply(x0, x1, weight, bias, residual, geom)

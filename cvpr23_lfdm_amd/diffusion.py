@@ -194,12 +194,26 @@ class GaussianDiffusion(nn.Module):
     def __init__(self, denoise_fn, *, image_size, num_frames, text_use_bert_cls=False, channels=3,
                  timesteps=1000, sampling_timesteps=250, ddim_sampling_eta=1., loss_type='l1',
                  use_dynamic_thres=False, dynamic_thres_percentile=0.9, null_cond_prob=0.1,
-                 per_element_loss=False, sampler="reference", long_attention=False, noise="torch", known_train=None):
+                 per_element_loss=False, sampler="reference", long_attention=False, noise="torch", known_train=None,
+                 objective="pred_noise", min_snr_gamma=None):
         """Reference signature + `sampler` (keyword): what `sample()` runs.  "reference" (default): the reference's own pair, DDIM when
         sampling_timesteps < timesteps, ancestral DDPM otherwise.  "dpmpp_2m": DPM-Solver++(2M) (Lu et al. 2022), the second-order multistep
         rule on the thresholded data prediction, one UNet evaluation per step, on the reference's DDIM time grid; "dpmpp_1": its first-order
         form on every step.  Both are deterministic: nothing is drawn after x_T and `ddim_sampling_eta` is ignored (`_ms_step_tables`)."""
         super().__init__()
+        # objective (keyword, default "pred_noise": the reference's) - what the denoiser's output is: the noise, x_start, or
+        # v = a noise - s x_start (Salimans & Ho 2022); it decides the training target, how x0 comes back from the output, and the two x0
+        # columns of every step table (DESIGN.md 4.14).  min_snr_gamma (keyword, default None): the min-SNR-gamma weight of Hang et al. 2023
+        # on each sample's loss, `loss_weight[t]`.  None means weight 1 for EVERY objective - the plain loss on the target; this is not the
+        # denoising-diffusion-pytorch convention, which weights "pred_x0" by snr when gamma is off.
+        if objective not in self.OBJECTIVES:
+            raise ValueError("objective must be one of %s, got %r" % (self.OBJECTIVES, objective))
+        if min_snr_gamma is not None and (isinstance(min_snr_gamma, bool) or not isinstance(min_snr_gamma, (int, float))
+                                          or not math.isfinite(min_snr_gamma) or min_snr_gamma <= 0):
+            raise ValueError("min_snr_gamma must be None or a finite positive number, got %r" % (min_snr_gamma,))
+        self.objective = objective
+        self.min_snr_gamma = None if min_snr_gamma is None else float(min_snr_gamma)
+        self.sample_loss = self.sample_t = None       # after a step on the kernel route: (B,) unweighted per-sample means and their t, on the device
         # known_train (keyword, default None: off): dict(prob=0.5, kinds=("prefix", "ends", "random"), max_frames=8, seed=0) - the mask
         # policy of random-mask training (KnownMaskPolicy, DESIGN.md 4.12): `forward` then draws a frame mask per step and hands it to p_losses
         self.known_policy = None if known_train is None else KnownMaskPolicy(num_frames, **dict(known_train))
@@ -251,6 +265,7 @@ class GaussianDiffusion(nn.Module):
             ('posterior_mean_coef2', (1. - acp_prev) * torch.sqrt(alphas) / (1. - acp)),
         ):
             self.register_buffer(name, val.to(torch.float32))
+        self.register_buffer("loss_weight", self._loss_weight_table(), persistent=False)         # (no state-dict key)
         self.text_use_bert_cls = text_use_bert_cls
         self.use_dynamic_thres = use_dynamic_thres
         self.dynamic_thres_percentile = dynamic_thres_percentile
@@ -268,6 +283,19 @@ class GaussianDiffusion(nn.Module):
     SAMPLERS = ("reference", "dpmpp_1", "dpmpp_2m")
     NOISE_MODES = ("torch", "counter")
     KNOWN_LEVELS = ("noised", "clean")
+    OBJECTIVES = ("pred_noise", "pred_x0", "pred_v")
+
+    def _loss_weight_table(self):
+        """The (timesteps,) fp32 loss weight per timestep: 1 without min_snr_gamma; else, with snr = alphas_cumprod / (1 - alphas_cumprod),
+        min(snr, gamma) / snr for "pred_noise", min(snr, gamma) for "pred_x0", min(snr, gamma) / (snr + 1) for "pred_v" - the one weight
+        min(snr, gamma) on the x0 error, carried to each target.  In double from the registered fp32 alphas_cumprod, rounded once."""
+        acp = self.alphas_cumprod.detach().double().cpu()
+        if self.min_snr_gamma is None:
+            return torch.ones(acp.shape[0], dtype=torch.float32)
+        snr = acp / (1.0 - acp)
+        clipped = snr.clamp(max=self.min_snr_gamma)
+        w = clipped / snr if self.objective == "pred_noise" else clipped if self.objective == "pred_x0" else clipped / (snr + 1.0)
+        return w.float()
 
     @property
     def noise(self):
@@ -351,7 +379,31 @@ class GaussianDiffusion(nn.Module):
                                          std if t > 0 else zero]))
                 times.append(t)
                 draws.append(True)      # p_sample draws on every step, also at t == 0 (:743)
-        return times, torch.stack(rows).float().contiguous(), draws
+        coef = torch.stack(rows).float().contiguous()
+        if self.objective != "pred_noise":
+            coef = self._objective_rows(times, coef, ddim_rows=bool(ddim))
+        return times, coef, draws
+
+    def _objective_rows(self, times, coef, ddim_rows):
+        """The rows of a step table for "pred_v" / "pred_x0" (DESIGN.md 4.14): the update kernels compute x0 = c_x x - c_eps out, so only the
+        table changes.  With a = sqrt_alphas_cumprod[time], s = sqrt_one_minus_alphas_cumprod[time], the fp32 buffer values:
+            "pred_v":  c_x = a, c_eps = s (x0 = a x - s v);      "pred_x0":  c_x = 0, c_eps = -1 (0 x - (-1 out) = out exactly, x finite)
+        DDPM and "dpmpp_*" rows use the thresholded x0 only: nothing else changes.  A reference DDIM row {A, c, 0, sigma} adds c times a noise
+        estimate; for these objectives it is the one implied by the thresholded x0 on the level the denoiser was conditioned on,
+        eps_hat = (x - a x0c) / s (the denoising-diffusion-pytorch convention), so k_x0 = A - c a / s, k_eps = 0, k_x = c / s, k_noise = sigma.
+        In double from the fp32 values, rounded once."""
+        a_tab = self.sqrt_alphas_cumprod.detach().float().cpu().double()
+        s_tab = self.sqrt_one_minus_alphas_cumprod.detach().float().cpu().double()
+        rows = coef.double().clone()
+        for i, time in enumerate(times):
+            a, s = float(a_tab[time]), float(s_tab[time])
+            if ddim_rows:
+                if not s > 0.0:
+                    raise ValueError("objective %r: degenerate noise level at timestep %d" % (self.objective, time))
+                big_a, c = float(rows[i, 2]), float(rows[i, 3])
+                rows[i, 2], rows[i, 3], rows[i, 4] = big_a - c * a / s, 0.0, c / s
+            rows[i, 0], rows[i, 1] = (a, s) if self.objective == "pred_v" else (0.0, -1.0)
+        return rows.float().contiguous()
 
     def _ms_step_tables(self, sampler):
         """Timestep list and the (steps, 6) table {c_x, c_eps, k_x, k_m, k_prev, 0} of the multistep lfdm_sampler_step_f32 for "dpmpp_2m" / "dpmpp_1":
@@ -397,7 +449,10 @@ class GaussianDiffusion(nn.Module):
             h_prev = h
             rows.append([float(c_x[time]), float(c_eps[time]), k_x, k_m, k_prev, 0.0])
             times.append(time)
-        return times, torch.tensor(rows, dtype=torch.float64).float().contiguous()
+        coef = torch.tensor(rows, dtype=torch.float64).float().contiguous()
+        if self.objective != "pred_noise":          # (the multistep update reads the thresholded x0 only: the two x0 columns)
+            coef = self._objective_rows(times, coef, ddim_rows=False)
+        return times, coef
 
     def _level_table(self, ddim, sampler="reference"):
         """Known-frame conditioning: the (steps + 1, 2) fp32 host table of the level (a, s) the latent sits on - row 0: x_T's node,
@@ -422,7 +477,7 @@ class GaussianDiffusion(nn.Module):
     def _schedule_key(self, ddim, sampler, dev, clean=False):
         """Everything a schedule's tables are a function of; the buffers' stamps come last."""
         return (bool(ddim), sampler, float(self.ddim_sampling_eta), self.sampling_timesteps, self.num_timesteps, str(dev), bool(clean),
-                tuple((k, v._version, v.data_ptr()) for k, v in self.named_buffers(recurse=False)))
+                self.objective, tuple((k, v._version, v.data_ptr()) for k, v in self.named_buffers(recurse=False)))
 
     def _schedule(self, ddim, sampler, dev, level=False, clean=False):
         """The `Schedule` of (ddim, sampler) on `dev`: `_step_tables` / `_ms_step_tables` (whose grid checks raise from here) and, once a
@@ -738,6 +793,21 @@ class GaussianDiffusion(nn.Module):
         return (self.sqrt_recip_alphas_cumprod[t].reshape(shp) * x_t
                 - self.sqrt_recipm1_alphas_cumprod[t].reshape(shp) * noise)
 
+    def _at(self, name, t, like):
+        return getattr(self, name)[t].reshape((like.shape[0],) + (1,) * (like.dim() - 1))
+
+    def predict_start_from_v(self, x_t, t, v):
+        """x0 = a x_t - s v (Salimans & Ho 2022), torch's fp32 expression - what the "pred_v" loss kernel writes as pred_x0."""
+        return self._at("sqrt_alphas_cumprod", t, x_t) * x_t - self._at("sqrt_one_minus_alphas_cumprod", t, x_t) * v
+
+    def predict_v(self, x_start, t, noise):
+        """v = a noise - s x_start: the "pred_v" training target."""
+        return self._at("sqrt_alphas_cumprod", t, x_start) * noise - self._at("sqrt_one_minus_alphas_cumprod", t, x_start) * x_start
+
+    def predict_noise_from_start(self, x_t, t, x0):
+        """The noise that takes x0 to x_t: (r x_t - x0) / m."""
+        return (self._at("sqrt_recip_alphas_cumprod", t, x_t) * x_t - x0) / self._at("sqrt_recipm1_alphas_cumprod", t, x_t)
+
     def q_sample(self, x_start, t, noise=None):
         """:848-854."""
         if noise is None:
@@ -773,20 +843,28 @@ class GaussianDiffusion(nn.Module):
         known_mask (keyword; default None: the reference's step, statement for statement): (B, T) bool - known frames - or 5-D bool
         (B, C | 1, T, S, S) - known elements: those elements of x_start stay clean inside x_noisy, the loss is the mean over each sample's
         UNKNOWN elements, then over the samples, and pred_x0 is x_start there - three launches of csrc/train_diffusion.hip
-        around the denoiser instead of the eager q_sample / loss / predict_start_from_noise."""
+        around the denoiser instead of the eager q_sample / loss / predict_start_from_noise.
+        With objective != "pred_noise" or a min_snr_gamma the same three launches run with or without a mask, on the
+        objective's target and with loss_weight[t] on each sample's mean; `sample_loss` ((B,) unweighted per-sample means) and `sample_t`
+        are then left on the device, and `pred_x0` is set also with clip_denoised=False (unclipped)."""
         if noise is None:
             noise = torch.randn_like(x_start)
-        if known_mask is None:
+        # the kernel route of DESIGN.md 4.14: another objective than the reference's or a loss weight, with or without a mask
+        objective_route = self.objective != "pred_noise" or self.min_snr_gamma is not None
+        if known_mask is None and not objective_route:
             x_noisy = self.q_sample(x_start, t, noise)
         else:
             if self.per_element_loss:
-                raise NotImplementedError("p_losses: known_mask with per_element_loss=True (the functional multi-GPU flavour) is not built")
+                raise NotImplementedError("p_losses: known_mask, an objective other than 'pred_noise' or min_snr_gamma with per_element_loss=True "
+                                          "(the functional multi-GPU flavour) is not built")
             if self.loss_type not in ops.LOSS_TYPES:
                 raise NotImplementedError()
-            known_mask = self._train_known_mask(x_start, known_mask)
+            mask_kw = {}
+            if known_mask is not None:
+                known_mask = self._train_known_mask(x_start, known_mask)
+                mask_kw = {"frame_mask" if known_mask.dim() == 2 else "elem_mask": known_mask}
             x_start, noise, t = x_start.float().contiguous(), noise.float().contiguous(), t.to(torch.int64).contiguous()
-            x_noisy = ops.train_qsample(x_start, noise, t, self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod,
-                                        **{"frame_mask" if known_mask.dim() == 2 else "elem_mask": known_mask})
+            x_noisy = ops.train_qsample(x_start, noise, t, self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, **mask_kw)
         none_cond_mask = None
         if is_list_str(cond):
             none_cond_mask = [c == "None" for c in cond]
@@ -822,6 +900,15 @@ class GaussianDiffusion(nn.Module):
                                               **kwargs)
             finally:
                 unet.train(was_training)
+        if objective_route:
+            from .autograd import objective_diffusion_loss
+            tabs = (self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, self.sqrt_recip_alphas_cumprod,
+                    self.sqrt_recipm1_alphas_cumprod, None if self.min_snr_gamma is None else self.loss_weight)
+            loss, pred_x0, self.sample_loss = objective_diffusion_loss(pred_noise.contiguous(), x_start, noise, x_noisy, t, tabs, known_mask,
+                                                                       self.loss_type, self.objective)
+            self.sample_t = t
+            self.pred_x0 = self._clip_pred_x0(pred_x0) if clip_denoised else pred_x0
+            return loss
         if known_mask is not None:
             from .autograd import masked_diffusion_loss
             loss, pred_x0 = masked_diffusion_loss(pred_noise.contiguous(), noise, x_noisy, t, self.sqrt_recip_alphas_cumprod,

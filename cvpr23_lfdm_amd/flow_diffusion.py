@@ -71,7 +71,8 @@ class FlowDiffusion(nn.Module):
                  adam_betas=(0.9, 0.99), is_train=True, only_use_flow=True, use_residual_flow=False,
                  learn_null_cond=False, use_deconv=True, padding_mode="zeros", pretrained_pth="",
                  config_pth="", bert_path=None, *, conv_precision="fp32", sampler="reference", ema_decay=None, ema_start_step=0,
-                 max_grad_norm=None, skip_nonfinite=False, long_attention=False, noise="torch", known_train=None):
+                 max_grad_norm=None, skip_nonfinite=False, long_attention=False, noise="torch", known_train=None,
+                 objective="pred_noise", min_snr_gamma=None):
         """Reference signature (video_flow_diffusion_model.py:19-37) + `bert_path`: a local Hugging Face directory of
         bert-base-cased for `cond=list[str]` (the reference downloads it with torch.hub; see text.py).  LFDM_BERT_PATH in
         the environment is the default, so unchanged caller scripts pick it up.
@@ -88,7 +89,10 @@ class FlowDiffusion(nn.Module):
         (sample_one_video(seeds=...), sample_long_video(seed=...)).  Training draws stay on torch's generator.
         known_train (keyword only, default None: off): GaussianDiffusion.known_train - dict(prob=0.5, kinds=("prefix", "ends", "random"),
         max_frames=8, seed=0), random-mask training: some frames of a training video stay clean and the loss counts the others, so that
-        the checkpoint can be sampled with known_level="clean" (DESIGN.md 4.12).  Not available in the functional flavour."""
+        the checkpoint can be sampled with known_level="clean" (DESIGN.md 4.12).  Not available in the functional flavour.
+        objective / min_snr_gamma (keyword only, defaults "pred_noise" / None: the reference's step): GaussianDiffusion.objective - what the
+        denoiser predicts, "pred_noise", "pred_x0" or "pred_v" - and the min-SNR-gamma loss weight.  A checkpoint is
+        sampled with the objective it was trained with.  Not available in the functional flavour."""
         super().__init__()
         if noise not in GaussianDiffusion.NOISE_MODES:
             raise ValueError("noise must be one of %s, got %r" % (GaussianDiffusion.NOISE_MODES, noise))
@@ -123,7 +127,8 @@ class FlowDiffusion(nn.Module):
                                            sampling_timesteps=sampling_timesteps, timesteps=timesteps,
                                            loss_type='l2', use_dynamic_thres=True,
                                            null_cond_prob=null_cond_prob, ddim_sampling_eta=ddim_sampling_eta, sampler=sampler,
-                                           long_attention=self.long_attention, noise=noise, known_train=known_train)
+                                           long_attention=self.long_attention, noise=noise, known_train=known_train,
+                                           objective=objective, min_snr_gamma=min_snr_gamma)
         bert_path = bert_path or os.environ.get("LFDM_BERT_PATH")
         if bert_path:
             from .text import BertTextEncoder

@@ -251,3 +251,13 @@ def mimsave_indexed(path, index_frames, palette=STRIP_PALETTE, duration=0.1, loo
     if not ims:
         raise ValueError("mimsave_indexed: no frames")
     ims[0].save(path, save_all=True, append_images=ims[1:], duration=int(round(duration * 1000)), loop=loop, optimize=False)
+
+
+def checkpoint_objective(ck, flag=None, path="the checkpoint"):
+    """The training objective to sample a DM checkpoint with: the checkpoint's top-level "objective" ("pred_noise" where
+    there is none: the reference's checkpoints and older ones), or `flag` where there is no checkpoint (`ck` None).  A `flag` that
+    contradicts the checkpoint is a ValueError with both values - a denoiser's output means one thing only."""
+    stored = None if ck is None else ck.get("objective", "pred_noise")
+    if flag is not None and stored is not None and flag != stored:
+        raise ValueError("--objective %s contradicts %s, which was trained with objective %s" % (flag, path, stored))
+    return flag if flag is not None else stored if stored is not None else "pred_noise"

@@ -1232,6 +1232,74 @@ def masked_loss_bwd(noise, pred, inv_count, gout, *, loss_type="l1", frame_mask=
     return out
 
 
+OBJECTIVES = {"pred_noise": 0, "pred_x0": 1, "pred_v": 2}           # LFDM_OBJ_NOISE / _X0 / _V
+_OBJECTIVE_NEEDS = {"pred_noise": ("noise",), "pred_x0": ("x_start",), "pred_v": ("x_start", "noise")}
+
+
+def _objective_operands(what, lib, objective, x_start, noise, floats, t, tables, w_tab):
+    """The objective's code and (batch, n, table length): an operand the objective does not use may be None (it is never read); the
+    weight table is optional (None: weight 1)."""
+    if objective not in OBJECTIVES:
+        raise ValueError("%s: objective must be one of %s, got %r" % (what, tuple(OBJECTIVES), objective))
+    given = dict(x_start=x_start, noise=noise)
+    missing = [k for k in _OBJECTIVE_NEEDS[objective] if given[k] is None]
+    if missing:
+        raise ValueError("%s: objective %r needs %s (pred_noise: noise; pred_x0: x_start; pred_v: x_start and noise)"
+                         % (what, objective, " and ".join(missing)))
+    floats = dict({k: v for k, v in given.items() if v is not None}, **floats)
+    tables = tuple(tables) + (() if w_tab is None else (w_tab,))
+    batch, n = _train_operands(what, lib, floats["out"], floats, t, tables)
+    return OBJECTIVES[objective], batch, n, tables[0].numel()
+
+
+def objective_loss_fwd(objective, x_start, noise, out, x_noisy, t, a_tab, s_tab, r_tab, m_tab, w_tab=None, *, loss_type="l1", frame_mask=None,
+                       elem_mask=None, frames=None, loss=None, inv_count=None, sample_loss=None, pred_x0=None):
+    """lfdm_objective_loss_fwd_f32 -> (loss (1,), inv_count (B,), sample_loss (B,), pred_x0): masked_loss_fwd for a training objective
+     - `out` is the denoiser's output, target = noise | x_start | a * noise - s * x_start for "pred_noise" | "pred_x0" |
+    "pred_v", pred_x0 = r * x_noisy - m * out | out | a * x_noisy - s * out (x_noisy where known) - with the per-timestep weight w_tab[t_b]
+    (None: 1) on each sample's mean: loss = (1 / B) sum_b w_b S_b / max(N_b, 1); sample_loss[b] = S_b / max(N_b, 1), unweighted.  x_start
+    ("pred_noise") / noise ("pred_x0") may be None and are never read.  "pred_noise" without w_tab: the bits of masked_loss_fwd."""
+    lib = _lib()
+    what = "objective_loss_fwd"
+    code = _loss_code(what, loss_type)
+    pred_x0 = _train_dest(what, pred_x0, out.shape, out)
+    obj, batch, n, t_len = _objective_operands(what, lib, objective, x_start, noise, dict(out=out, x_noisy=x_noisy, pred_x0=pred_x0), t,
+                                               (a_tab, s_tab, r_tab, m_tab), w_tab)
+    loss = _train_dest(what, loss, (1,), out)
+    inv_count = _train_dest(what, inv_count, (batch,), out)
+    sample_loss = _train_dest(what, sample_loss, (batch,), out)
+    fm, em, frames, frame_elems = _train_mask(what, out, frame_mask, elem_mask, frames)
+    nbytes = lib.lfdm_masked_loss_ws_bytes(batch, n)
+    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=out.device)
+    ticket = _LOSS_TICKETS.get(out.device)
+    if ticket is None:
+        ticket = _LOSS_TICKETS[out.device] = torch.zeros(1, dtype=torch.int32, device=out.device)
+    lib.check(lib.lfdm_objective_loss_fwd_f32(obj, _p(x_start), _p(noise), _p(out), _p(x_noisy), _p(t), _p(a_tab), _p(s_tab), _p(r_tab), _p(m_tab),
+                                              _p(w_tab), t_len, fm, em, frames, frame_elems, code, _p(loss), _p(inv_count), _p(sample_loss),
+                                              _p(pred_x0), batch, n, _p(ws), nbytes, _p(ticket), _stream(lib)), "lfdm_objective_loss_fwd_f32")
+    return loss, inv_count, sample_loss, pred_x0
+
+
+def objective_loss_bwd(objective, x_start, noise, out, t, a_tab, s_tab, w_tab, inv_count, gout, *, loss_type="l1", frame_mask=None,
+                       elem_mask=None, frames=None, dout=None):
+    """lfdm_objective_loss_bwd_f32: d loss / d out = c_b * d |target - out| / d out with c_b = ((gout * inv_count[b]) * w_tab[t_b]) / B in
+    fp32 (w_tab None: no product), the target recomputed from x_start / noise; exactly 0.0 at every known element.  "pred_noise" without
+    w_tab: the bits of masked_loss_bwd."""
+    lib = _lib()
+    what = "objective_loss_bwd"
+    code = _loss_code(what, loss_type)
+    dout = _train_dest(what, dout, out.shape, out)
+    obj, batch, n, t_len = _objective_operands(what, lib, objective, x_start, noise, dict(out=out, dout=dout), t, (a_tab, s_tab), w_tab)
+    for name, v, count in (("inv_count", inv_count, batch), ("gout", gout, 1)):
+        if not torch.is_tensor(v) or v.dtype != torch.float32 or v.numel() != count or not v.is_contiguous() or v.device != out.device:
+            raise ValueError("%s: %s must be a contiguous float32 tensor of %d element(s) on the operands' device" % (what, name, count))
+    fm, em, frames, frame_elems = _train_mask(what, out, frame_mask, elem_mask, frames)
+    lib.check(lib.lfdm_objective_loss_bwd_f32(obj, _p(x_start), _p(noise), _p(out), _p(t), _p(a_tab), _p(s_tab), _p(w_tab), t_len, fm, em, frames,
+                                              frame_elems, code, _p(inv_count), _p(gout), _p(dout), batch, n, _stream(lib)),
+              "lfdm_objective_loss_bwd_f32")
+    return dout
+
+
 def cfg_combine(cond_eps, null_eps, scale, out):
     lib = _lib()
     _chk(lib, cond_eps, null_eps, out)

@@ -949,6 +949,37 @@ int lfdm_masked_loss_bwd_f32(const float* noise, const float* pred, const unsign
                              int64_t frame_elems, int loss_type, const float* inv_count, const float* gout, float* dpred, int batch, int64_t n,
                              lfdm_stream_t stream);
 
+/* The same loss for a choice of training objective and with a per-timestep weight (additive, ABI version unchanged).  `out`
+ * is the denoiser's output; (a, s, r, m, w) = (a_tab, s_tab, r_tab, m_tab, w_tab)[t_b], the tables of t_len entries on the device:
+ *   LFDM_OBJ_NOISE  target = noise                      pred_x0 = r * x_noisy - m * out   (the masked loss above)
+ *   LFDM_OBJ_X0     target = x_start                    pred_x0 = out (its bits)
+ *   LFDM_OBJ_V      target = a * noise - s * x_start    pred_x0 = a * x_noisy - s * out
+ * every expression two fp32 products and one fp32 difference, each rounded on its own; the target is never stored.  Operands the objective
+ * does not use may be NULL and are never read: x_start, a_tab, s_tab for LFDM_OBJ_NOISE; noise and all four tables for LFDM_OBJ_X0; r_tab,
+ * m_tab for LFDM_OBJ_V and in the backward.  w_tab NULL = weight 1.  Geometry, masks, alignment, workspace (lfdm_masked_loss_ws_bytes),
+ * ticket and refusals as above; an objective outside the three, or one whose operands are missing, is refused with the list of what each needs.
+ *   fwd: S_b, N_b as above over |target - out|;  inv_count[b] = 1 / max(N_b, 1);  sample_loss[b] = S_b / max(N_b, 1) (unweighted);
+ *        *loss = (1 / B) sum_b w * S_b / max(N_b, 1), the weight applied in double in the last workgroup's fold;  pred_x0 = x_noisy where
+ *        known.  With LFDM_OBJ_NOISE and w_tab NULL: the bits of lfdm_masked_loss_fwd_f32.
+ *   bwd: dout = c_b * d|target - out| / d out, c_b = (((*gout) * inv_count[b]) * w) / B in fp32 in that order (w_tab NULL: no product - with
+ *        LFDM_OBJ_NOISE the bits of lfdm_masked_loss_bwd_f32); known: 0.f */
+#define LFDM_OBJ_NOISE 0
+#define LFDM_OBJ_X0 1
+#define LFDM_OBJ_V 2
+/* Layout: x_start, noise, out, x_noisy, pred_x0 dense (B, n), 16 B; t dense (B) int64; the tables dense (t_len); masks dense; loss 1 float,
+ * inv_count, sample_loss (B) floats.  pred_x0 must not alias an input. */
+int lfdm_objective_loss_fwd_f32(int objective, const float* x_start, const float* noise, const float* out, const float* x_noisy,
+                                const int64_t* t, const float* a_tab, const float* s_tab, const float* r_tab, const float* m_tab,
+                                const float* w_tab, int t_len, const unsigned char* frame_mask, const unsigned char* elem_mask, int frames,
+                                int64_t frame_elems, int loss_type, float* loss, float* inv_count, float* sample_loss, float* pred_x0,
+                                int batch, int64_t n, void* ws, size_t ws_bytes, unsigned* ticket, lfdm_stream_t stream);
+/* Layout: x_start, noise, out, dout dense (B, n), 16 B; t dense (B) int64; the tables dense (t_len); masks dense; inv_count (B) floats and
+ * gout 1 float on the device.  dout must not alias an input. */
+int lfdm_objective_loss_bwd_f32(int objective, const float* x_start, const float* noise, const float* out, const int64_t* t,
+                                const float* a_tab, const float* s_tab, const float* w_tab, int t_len, const unsigned char* frame_mask,
+                                const unsigned char* elem_mask, int frames, int64_t frame_elems, int loss_type, const float* inv_count,
+                                const float* gout, float* dout, int batch, int64_t n, lfdm_stream_t stream);
+
 /* im2col of channels-last rows with few channels (channels % 4 == 0, <= 16; stride 1, zero padding): out (n_img*hq*wq, k*k*channels),
  * column tap * channels + ch.  Lets the weight gradient of the generator's 7x7 RGB convolutions (LFAE/modules/generator.py:37,56: 3 -> 64
  * and 64 -> 3 channels) run as ONE 1x1 weight-gradient GEMM instead of 49 per-tap GEMMs that pad 4 channels to a 64-wide tile. */

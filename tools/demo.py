@@ -56,6 +56,9 @@ def build_parser():
                     help="how known content (--total-frames' overlap frames, --keep-box / --regen-box) is held during sampling: on the step's "
                          "noise level (default), or clean at every step - for a checkpoint trained with tools/train_dm.py --known-prob "
                          "(DESIGN.md 4.12)")
+    ap.add_argument("--objective", choices=("pred_noise", "pred_x0", "pred_v"), default=None,
+                    help="what the denoiser predicts (tools/train_dm.py --objective, DESIGN.md 4.14); default: the checkpoint's own entry "
+                         "(pred_noise where it has none) - a value that contradicts the checkpoint is an error")
     ap.add_argument("--use-ema", action="store_true",
                     help="sample from the averaged weights: the checkpoint's 'diffusion_ema' entry (tools/train_dm.py --ema-decay, DESIGN.md 4.4)")
     ap.add_argument("--long-attention", action="store_true", help="windows of 65 ... 256 frames (and a mid block of up to 256 pixels per frame) on the streaming attention kernels (FlowDiffusion(long_attention=True), DESIGN.md 4.8)")
@@ -211,11 +214,16 @@ def make_model(args, *, steps=None, sampler=None, conv_precision=None, use_ema=N
     sampler = args.sampler if sampler is None else sampler
     conv_precision = args.conv_precision if conv_precision is None else conv_precision
     use_ema = args.use_ema if use_ema is None else use_ema
+    ck = torch.load(args.dm_ckpt, map_location="cpu") if args.dm_ckpt and not args.synthetic else None
+    try:
+        objective = C.checkpoint_objective(ck, getattr(args, "objective", None), args.dm_ckpt)
+    except ValueError as e:
+        sys.exit(str(e))
     model = FlowDiffusion(is_train=False, img_size=args.size // 4, num_frames=args.frames, sampling_timesteps=steps,
                           null_cond_prob=0.1, config_pth=args.config, pretrained_pth=args.lfae_ckpt,
                           bert_path=None if args.synthetic else args.bert, conv_precision=conv_precision,
                           sampler=sampler, long_attention=getattr(args, "long_attention", False),
-                          noise=getattr(args, "noise", "torch"))                                            # demo_mug.py:80-88
+                          noise=getattr(args, "noise", "torch"), objective=objective)                       # demo_mug.py:80-88
     if args.synthetic:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import synth
@@ -230,7 +238,7 @@ def make_model(args, *, steps=None, sampler=None, conv_precision=None, use_ema=N
             return torch.cat([emb[t] for t in texts])
         model.diffusion.text_encoder = encode
     elif args.dm_ckpt:
-        model.diffusion.load_state_dict(dm_state(torch.load(args.dm_ckpt, map_location="cpu"), use_ema, args.dm_ckpt))   # demo_mug.py:93-97
+        model.diffusion.load_state_dict(dm_state(ck, use_ema, args.dm_ckpt))   # demo_mug.py:93-97
     elif need_dm:
         sys.exit("give --dm-ckpt (and --lfae-ckpt), or --synthetic")
     return model

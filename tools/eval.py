@@ -58,6 +58,8 @@ def build_parser():
         p.add_argument("--sampler", choices=("reference", "dpmpp_1", "dpmpp_2m"), default="reference")
         p.add_argument("--steps", type=int, default=100)
         p.add_argument("--conv-precision", choices=("fp32", "bf16"), default="fp32")
+        p.add_argument("--objective", choices=("pred_noise", "pred_x0", "pred_v"), default=None,
+                       help="what the denoiser predicts (DESIGN.md 4.14); default: the checkpoint's own entry - a contradiction is an error")
         p.add_argument("--use-ema", action="store_true", help="sample from the checkpoint's 'diffusion_ema' entry")
         p.add_argument("--long-attention", action="store_true", help="windows of 65 ... 256 frames (and a mid block of up to 256 pixels per frame) on the streaming attention kernels (FlowDiffusion(long_attention=True), DESIGN.md 4.8)")
         p.add_argument("--cond-scale", type=float, default=1.0)

@@ -77,7 +77,38 @@ def parse_args(argv=None):
     ap.add_argument("--known-max-frames", type=int, default=8, help="--known-prob: at most this many known frames (at most --frames - 1)")
     ap.add_argument("--known-seed", type=int, default=0, help="--known-prob: seed of the mask stream (not stored in checkpoints: a resumed run "
                     "starts the stream again)")
+    ap.add_argument("--objective", choices=("pred_noise", "pred_x0", "pred_v"), default="pred_noise",
+                    help="what the denoiser predicts (FlowDiffusion(objective=...), DESIGN.md 4.14): the noise (default, the reference's), x0, "
+                         "or v = a noise - s x0; stored in the checkpoint, which tools/demo.py and tools/eval.py then sample accordingly")
+    ap.add_argument("--min-snr-gamma", type=float, default=None,
+                    help="min-SNR-gamma loss weights (Hang et al. 2023; 5 is the paper's value); default: every timestep weighs 1")
+    ap.add_argument("--log-loss-quartiles", action="store_true",
+                    help="at --print-freq also print the mean unweighted per-sample loss by quartile of the timestep (accumulated on the "
+                         "device, read back only when printed); needs --objective other than pred_noise or --min-snr-gamma")
     return ap.parse_args(argv)
+
+
+class LossQuartiles:
+    """--log-loss-quartiles: sums and counts of diffusion.sample_loss by quartile of diffusion.sample_t in one (2, 4) device tensor; `add`
+    launches and reads nothing back, `means` (at --print-freq) reads the four means and starts again."""
+
+    def __init__(self, timesteps):
+        self.timesteps, self.acc = int(timesteps), None
+
+    def add(self, sample_loss, sample_t):
+        if self.acc is None:
+            self.acc = torch.zeros(2, 4, dtype=torch.float32, device=sample_loss.device)
+        q = (sample_t * 4 // self.timesteps).clamp_(0, 3)
+        self.acc[0].index_add_(0, q, sample_loss.detach())
+        self.acc[1].index_add_(0, q, torch.ones_like(sample_loss))
+        return self
+
+    def means(self):
+        if self.acc is None:
+            return [float("nan")] * 4
+        out = (self.acc[0] / self.acc[1]).tolist()          # (an empty quartile: nan)
+        self.acc.zero_()
+        return out
 
 
 def known_train(args):
@@ -136,7 +167,12 @@ def main(argv=None):
                           pretrained_pth=args.lfae_ckpt, bert_path=None if args.synthetic else args.bert,     # :153-162
                           ema_decay=args.ema_decay, ema_start_step=args.ema_start_step, max_grad_norm=args.max_grad_norm,
                           skip_nonfinite=args.skip_nonfinite, long_attention=args.long_attention, known_train=known_train(args),
-                          dim_mults=tuple(args.dim_mults))
+                          dim_mults=tuple(args.dim_mults), objective=args.objective, min_snr_gamma=args.min_snr_gamma)
+    quartiles = None
+    if args.log_loss_quartiles:
+        if args.objective == "pred_noise" and args.min_snr_gamma is None:
+            sys.exit("--log-loss-quartiles reads the per-sample losses of the objective loss kernel: give --objective or --min-snr-gamma")
+        quartiles = LossQuartiles(model.diffusion.num_timesteps)
     opt = model.optimizer_diff
     if cuda:
         model.cuda()
@@ -150,6 +186,10 @@ def main(argv=None):
     start_step = 0
     if args.restore_from:                                                                                     # :169-184
         ck = torch.load(args.restore_from, map_location="cpu")
+        try:                                 # a run continues on the objective its checkpoint was trained with
+            C.checkpoint_objective(ck, args.objective, args.restore_from)
+        except ValueError as e:
+            sys.exit(str(e))
         if args.set_start:
             start_step = int(math.ceil(ck["example"] / (args.batch_size * world)))
         model.diffusion.load_state_dict(ck["diffusion"])
@@ -188,6 +228,8 @@ def main(argv=None):
                 model.set_train_input(ref_img=ref_imgs, real_vid=real_vids, ref_text=list(ref_texts))
             model.optimize_parameters()
             step += 1
+            if quartiles is not None:
+                quartiles.add(model.diffusion.sample_loss, model.diffusion.sample_t)
             if args.latents and rank == 0 and step % args.save_img_freq == 0:
                 real_vids = prep.real_frames(batch)          # the batch's frames from the rows it holds, for the panel and the two logged numbers
                 model.decode_step_logs(real_vids)
@@ -201,6 +243,8 @@ def main(argv=None):
                 print("iter %d/%d  loss %.7f  loss_rec %.4f  loss_warp %.4f  lr %.2e  %.1f videos/s%s" % (
                     step, args.final_step, float(model.loss), rec[0], rec[1],
                     opt.param_groups[0]["lr"], args.batch_size * world / dt, guard), flush=True)
+                if quartiles is not None:
+                    print("    loss by quartile of t (unweighted): %s" % "  ".join("%.5f" % v for v in quartiles.means()), flush=True)
             if rank == 0 and step % args.save_img_freq == 0:                   # the middle-frame panel of :246-275
                 mid, s = args.frames // 2, args.size
                 panel = np.zeros((2 * s, 4 * s, 3), np.uint8)
@@ -227,7 +271,7 @@ def main(argv=None):
                               C.video_strip(model, ref_imgs[:1]))
             if rank == 0 and (step % args.save_freq == 0 or step >= args.final_step):                         # :330-340
                 ck = {"example": step * args.batch_size * world, "diffusion": model.diffusion.state_dict(),
-                      "optimizer_diff": opt.state_dict()}
+                      "optimizer_diff": opt.state_dict(), "objective": args.objective, "min_snr_gamma": args.min_snr_gamma}
                 if args.ema_decay is not None:          # the averaged weights, shaped like "diffusion" (tools/demo.py --use-ema)
                     ck["diffusion_ema"] = model.ema_state_dict()
                 torch.save(ck,
