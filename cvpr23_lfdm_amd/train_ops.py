@@ -163,19 +163,26 @@ def attention_bwd(qkv, dout, batch, frames, hw, mode, bias=None, rot_cos=None, r
     return dqkv, dbias
 
 
-def attention_long_bwd(qkv, dout, batch, frames, hw, mode, bias=None, rot_cos=None, rot_sin=None, dqkv=None):
-    """attention_bwd over 65 .. 256 tokens per sequence -> (dqkv rows of 768, dbias (8, L, L) or None).  dqkv: optional destination
-    (nothing is written to it when the shape is refused)."""
+def attention_long_bwd(qkv, dout, batch, frames, hw, mode, bias=None, rot_cos=None, rot_sin=None, dqkv=None, dbias=None, ws=None):
+    """attention_bwd over 65 .. 256 tokens per sequence -> (dqkv rows of 768, dbias (8, L, L) or None).  dqkv, dbias: optional destinations
+    (dbias only with a bias); ws: optional float32 workspace of at least lfdm_attention_long_bwd_ws_bytes.  Nothing is written to any of
+    them when the shape is refused."""
     lib = _lib()
-    _chk(lib, qkv, dout, bias, rot_cos, rot_sin, dqkv)
+    _chk(lib, qkv, dout, bias, rot_cos, rot_sin, dqkv, dbias, ws)
     assert qkv.is_contiguous() and dout.is_contiguous() and qkv.shape[1] == 768 and dout.shape[1] == 256
     if dqkv is None:
         dqkv = torch.empty_like(qkv)
     assert dqkv.is_contiguous() and dqkv.shape == qkv.shape
     seq = frames if mode == 0 else hw
-    dbias = torch.empty(8, seq, seq, dtype=torch.float32, device=qkv.device) if bias is not None else None
+    if bias is None:
+        assert dbias is None
+    else:
+        dbias = _dest(dbias, (8, seq, seq), qkv)
     nbytes = lib.lfdm_attention_long_bwd_ws_bytes(batch, frames, hw, mode)
-    ws = _ws(nbytes, qkv)
+    if ws is None:
+        ws = _ws(nbytes, qkv)
+    else:
+        assert ws.is_contiguous() and ws.dtype == torch.float32 and ws.numel() * 4 >= nbytes
     lib.check(lib.lfdm_attention_long_bwd_cl_f32(_p(qkv), _p(dout), _p(dqkv), batch, frames, hw, mode, _p(bias), _p(rot_cos),
                                                  _p(rot_sin), _p(dbias), _p(ws), nbytes, _stream(lib)),
               "lfdm_attention_long_bwd_cl_f32")

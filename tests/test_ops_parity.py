@@ -988,6 +988,29 @@ def test_attention_lowres(backend, c, frames, s, mode):
 #     mode 1: <32,4> 260 sequences of 17 | <64,2> 257 of 64 (no prefetch)
 #                                                        tests/test_train_edges.py::test_attention_spatial_bwd_trips[<b>-<frames>-<hw>]
 #
+# Long attention, 65 ... 256 tokens (csrc/attention_long.hip; tests/test_attention_long_edges.py, float64 references, NaN-filled out / stats / dqkv /
+# dbias / workspace, dq | dk | dv | dbias each against its own scale; the shipped shapes are in tests/test_attention_long.py; ids without the backend):
+#   lfdm_attention_long_cl_f32  attention_long_kernel
+#     lengths 97, 112 (the other classes: test_attention_long.py::test_forward_temporal[<L>])      test_forward_lengths[<L>]
+#     `bias_vec` false at L % 4 == 0 (bias 4 bytes past a 16-byte boundary), 128 | 256, the aligned call's bits    test_unaligned_bias[<L>]
+#     mode 1 with bias and rotary tables, batch 2 x 3 frames, hw 65 | 100 | 256                    test_spatial_with_tables[<hw>]
+#     none | bias alone | rotary alone at 129 (96: test_attention_long.py::test_forward_temporal_without_tables)    test_forward_optional_operands_129
+#     `stats` at L 65 | 128 | 256 (mode 0), hw 100 (mode 1): every element replaced, out the same bits without    test_forward_statistics_edges[<mode>-<L>]
+#   lfdm_attention_long_bwd_cl_f32  attention_long_bwd_q_kernel + attention_long_bwd_kv_kernel<true|false>
+#     every length class 65, 80, 96, 97, 112, 127, 128, 129, 200, 255, 256 (dead second query tile, L % 16 == 0 with L % 32 != 0, scalar bias reads)
+#                                                        test_backward_length_classes[<L>]
+#     phase KV's sequence walk (long_kv_groups: 2048 waves; the bias-gradient tile carried in LDS): 50, 51, 52 (2 x 26), 103 sequences of 65
+#     (G = 51) | 33 of 128 (32) | 29 of 129 (28) | 17 of 256 (16), each twice: same bits          test_backward_kv_trips[<L>-<b>-<hw>]
+#     phase Q's scalar bias reads at L % 4 == 0, the same two tests as the forward's              test_unaligned_bias[<L>], test_spatial_with_tables[<hw>]
+#     <false> no tables | <true> bias alone (`unrotate` a no-op) | <false> rotary alone (`unrotate`), 96 | 129    test_backward_optional_operands[<L>-<which>]
+#     NaN-filled against zero-filled workspace: same bits                                         test_workspace_independence
+#   both: rot_cos without rot_sin, bias without dbias, dbias without bias, mode 2, workspace one byte short | not 16-byte aligned | absent: refused with
+#     their codes, nothing written                       test_c_level_refusals
+#   both on ill-conditioned inputs: bias + 12 on the first / last live key, 65 | 96 | 129 | 255  test_boundary_keys[<L>]
+#     q, k x 4 (scores x 16; admitted by the float32 torch formula's own error), 65 | 129 | 256   test_large_scores[<L>]
+#   autograd.AttentionCL above 64 tokens: the bits of the two entry points, 65 | 129             test_autograd_routes_long[<L>]
+#   NOT reached at a test-sized shape: `long_shape_ok`'s 2^31 workgroup limit (more than 33 M sequences).
+#
 # The other training entry points (tests/test_train_edges.py, float64 references, NaN-filled destinations; ids without the backend):
 #   lfdm_linear_attention_bwd_cl_f32  linattn_bwd_context_kernel / linattn_bwd_apply_kernel, token blocks of LA_TOK = 64, four tokens per trip:
 #     1, 2, 3 | 63, 64, 65 | 127, 130 pixels             test_linear_attention_bwd_token_edges[<hw>]
