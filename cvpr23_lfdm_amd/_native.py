@@ -200,6 +200,9 @@ _SIGNATURES = {
     "lfdm_philox_normal_f32": (i32, [f32p, C.c_void_p, i32, i64, i64, C.c_uint, C.c_uint, C.c_uint, stream_t]),
     "lfdm_philox_bits_u32": (i32, [C.c_void_p, C.c_void_p, i32, i64, i64, C.c_uint, C.c_uint, C.c_uint, stream_t]),
     "lfdm_cfg_combine_f32": (i32, [f32p, f32p, f32, f32p, i64, stream_t]),
+    # ---- guidance rescale (additive, ABI stays 13)
+    "lfdm_cfg_rescale_ws_bytes": (sz, [i32, i64]),
+    "lfdm_cfg_combine_rescale_f32": (i32, [f32p, f32p, f32, f32, f32p, f32p, i32, i64, C.c_void_p, sz, stream_t]),
     "lfdm_abs_quantile_f32": (i32, [f32p, i32, i64, f32, f32p, C.c_void_p, sz, stream_t]),
     "lfdm_warp_cl_f32": (i32, [C.POINTER(WarpParams), stream_t]),
     "lfdm_warp_planar_f32": (i32, [C.POINTER(WarpParams), stream_t]),

@@ -343,6 +343,17 @@ __device__ __forceinline__ float block4_max(float v, float* s) {
   __syncthreads();
   return fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
 }
+// Sums the double `v` over a 256-thread workgroup through the LDS slots s[4], which nobody is still reading: butterfly per wave, then the
+// four waves' sums in wave order, ((w0 + w1) + w2) + w3.  Every thread returns the sum.
+__device__ __forceinline__ double block_sum_f64(double v, double* slots) {
+  v = wave_sum(v);
+  if ((threadIdx.x & (LFDM_WAVE - 1)) == 0) slots[threadIdx.x / LFDM_WAVE] = v;
+  __syncthreads();
+  double s = slots[0];
+#pragma unroll
+  for (int w = 1; w < 4; ++w) s += slots[w];
+  return s;
+}
 // Fixed tree over the 256 doubles the lanes of a 256-thread workgroup stored in s[threadIdx.x]: the same pairs in the same order on
 // every run.  The sum is s[0]; ends on a barrier.
 __device__ __forceinline__ void block_tree_sum(double* s) {

@@ -22,6 +22,7 @@ constexpr int kTileW = 32, kTileH = 16;               // SSIM-map pixels per wor
 constexpr int kHaloW = kTileW + kWin - 1;             // 42
 constexpr int kHaloH = kTileH + kWin - 1;             // 26
 constexpr int kWaves = kMetricBlock / LFDM_WAVE;
+static_assert(kWaves == 4, "block_sum_f64 (lfdm_device.h) folds the four waves of a 256-thread workgroup");
 
 struct VideoMetricArgs {
   const float* a;                      // (B, C, T, H, W)
@@ -43,17 +44,6 @@ __device__ __forceinline__ double metric_value(float x, double add, int domain) 
   if (domain == LFDM_METRIC_UNIT) return (double)r;
   const float q = r * 255.f;
   return q == q ? (double)(int)q / 255.0 : 0.0;
-}
-
-// Sums `v` over the workgroup: butterfly per wave, then the waves' sums in wave order.  Valid in thread 0.
-__device__ __forceinline__ double block_sum_f64(double v, double* slots) {
-  v = wave_sum(v);
-  if ((threadIdx.x & (LFDM_WAVE - 1)) == 0) slots[threadIdx.x / LFDM_WAVE] = v;
-  __syncthreads();
-  double s = slots[0];
-#pragma unroll
-  for (int w = 1; w < kWaves; ++w) s += slots[w];
-  return s;
 }
 
 // Tile (ty, tx) of channel c of frame (b, t) covers SSIM-map rows ty * 16 .. + 15 and columns tx * 32 .. + 31, that is input rows

@@ -534,13 +534,122 @@ __global__ __launch_bounds__(256) void sampler_update_ms_kernel(float* __restric
 }
 
 // classifier-free guidance: out = null + (cond - null) * scale   (reference :525-526)
+__device__ __forceinline__ float cfg_guided(float cond, float null, float scale) { return null + (cond - null) * scale; }
+
 __global__ __launch_bounds__(256) void cfg_combine_kernel(const float* __restrict__ cond_eps,
                                                           const float* __restrict__ null_eps,
                                                           float scale, float* __restrict__ out,
                                                           int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const float a = null_eps[i];
-    out[i] = a + (cond_eps[i] - a) * scale;
+    out[i] = cfg_guided(cond_eps[i], a, scale);
+  }
+}
+
+// Guidance rescale (Lin et al. 2024): out = g * (phi * std(cond) / std(g) + 1 - phi), g = cfg_guided(cond, null, scale), the
+// standard deviations per sample over its n elements, unbiased.  Two launches, no atomics:
+//   cfg_rescale_stats_kernel   grid (G, batch): workgroup j of sample b strides over the sample's quads (4 adjacent elements; thread t of trip
+//                              r owns quad (r G + j) 256 + t), every thread keeps sum cond, sum cond^2, sum g, sum g^2 in double, the workgroup
+//                              folds them (block_sum_f64) and writes ONE 4-double partial
+//   cfg_rescale_apply_kernel   grid (G, batch): every workgroup folds its sample's G <= 256 partials (thread t holds partial t), forms the factor
+//                              in double, rounds it to fp32 once and streams out = g * factor over its quads
+// A quad is ONE 16-byte load / store where the sample's bases are 16-byte aligned and the quad lies inside the sample, four element accesses
+// otherwise; a thread adds its quad's elements in index order on either path, and G is a function of n alone: which thread adds what, and in
+// which order, does not depend on the batch, the addresses or the run.  The product of two floats is exact in double, so an fma contraction
+// of the accumulations changes no bit.
+constexpr int kRescaleQuadsPerBlock = 256;        // one trip of a workgroup: 256 quads = 1024 elements
+constexpr int kRescaleMaxBlocks = 256;            // G's cap: the fold of launch B is one partial per thread
+inline unsigned rescale_blocks(int64_t n) { return lfdm_blocks((n + 3) / 4, kRescaleQuadsPerBlock, kRescaleMaxBlocks); }
+
+// elements j < cnt of quad q of a sample: cnt = 4 inside the sample, n - 4 q in its ragged last quad
+__device__ __forceinline__ int rescale_load_quad(const float* __restrict__ cb, const float* __restrict__ nb, bool wide, int64_t q, int64_t n,
+                                                 float (&c)[4], float (&a)[4]) {
+  const int64_t i = 4 * q;
+  if (wide && i + 4 <= n) {
+    const float4 cv = *reinterpret_cast<const float4*>(cb + i), av = *reinterpret_cast<const float4*>(nb + i);
+    c[0] = cv.x; c[1] = cv.y; c[2] = cv.z; c[3] = cv.w;
+    a[0] = av.x; a[1] = av.y; a[2] = av.z; a[3] = av.w;
+    return 4;
+  }
+  const int cnt = n - i < 4 ? (int)(n - i) : 4;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    c[j] = j < cnt ? cb[i + j] : 0.f;
+    a[j] = j < cnt ? nb[i + j] : 0.f;
+  }
+  return cnt;
+}
+
+__global__ __launch_bounds__(256) void cfg_rescale_stats_kernel(const float* cond_eps, const float* null_eps, float scale, int64_t n,
+                                                                double* __restrict__ partial) {
+  __shared__ double slots[4][4];
+  const int b = blockIdx.y;
+  const float* cb = cond_eps + (int64_t)b * n;
+  const float* nb = null_eps + (int64_t)b * n;
+  const bool wide = ((reinterpret_cast<uintptr_t>(cb) | reinterpret_cast<uintptr_t>(nb)) & 15u) == 0;
+  const int64_t quads = (n + 3) >> 2;
+  double s[4] = {0.0, 0.0, 0.0, 0.0};               // sum cond, sum cond^2, sum g, sum g^2
+  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < quads; q += (int64_t)gridDim.x * 256) {
+    float c[4], a[4];
+    const int cnt = rescale_load_quad(cb, nb, wide, q, n, c, a);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (j < cnt) {
+        const double cd = (double)c[j], gd = (double)cfg_guided(c[j], a[j], scale);
+        s[0] += cd;
+        s[1] += cd * cd;
+        s[2] += gd;
+        s[3] += gd * gd;
+      }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) s[k] = block_sum_f64(s[k], slots[k]);
+  if (threadIdx.x == 0) {
+    double* p = partial + ((int64_t)b * gridDim.x + blockIdx.x) * 4;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) p[k] = s[k];
+  }
+}
+
+// out may alias cond_eps or null_eps (no __restrict__ on the three): a thread reads its quad before it writes it and no other thread touches it
+__global__ __launch_bounds__(256) void cfg_rescale_apply_kernel(const float* cond_eps, const float* null_eps, float scale, float phi, float* out,
+                                                                float* factor_out, int64_t n, const double* __restrict__ partial) {
+  __shared__ double slots[4][4];
+  const int b = blockIdx.y;
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
+  if (threadIdx.x < gridDim.x) {                     // (launch A ran on the same G; x + 0.0 is x in the other threads)
+    const double* p = partial + ((int64_t)b * gridDim.x + threadIdx.x) * 4;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s[k] = p[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) s[k] = block_sum_f64(s[k], slots[k]);
+  const double nd = (double)n;
+  const double var_c = fmax((s[1] - s[0] * s[0] / nd) / (nd - 1.0), 0.0);
+  const double var_g = fmax((s[3] - s[2] * s[2] / nd) / (nd - 1.0), 0.0);
+  const double std_g = sqrt(var_g);
+  const double fd = std_g == 0.0 ? 1.0 : (double)phi * (sqrt(var_c) / std_g) + (1.0 - (double)phi);
+  const float f = (float)fd;
+  if (factor_out && blockIdx.x == 0 && threadIdx.x == 0) factor_out[b] = f;
+  const float* cb = cond_eps + (int64_t)b * n;
+  const float* nb = null_eps + (int64_t)b * n;
+  float* ob = out + (int64_t)b * n;
+  const bool wide = ((reinterpret_cast<uintptr_t>(cb) | reinterpret_cast<uintptr_t>(nb) | reinterpret_cast<uintptr_t>(ob)) & 15u) == 0;
+  const int64_t quads = (n + 3) >> 2;
+  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < quads; q += (int64_t)gridDim.x * 256) {
+    float c[4], a[4];
+    const int cnt = rescale_load_quad(cb, nb, wide, q, n, c, a);
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = cfg_guided(c[j], a[j], scale) * f;
+    const int64_t i = 4 * q;
+    if (wide && cnt == 4) {
+      *reinterpret_cast<float4*>(ob + i) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < cnt) ob[i + j] = v[j];
+    }
   }
 }
 
@@ -650,6 +759,26 @@ extern "C" int lfdm_cfg_combine_f32(const float* cond_eps, const float* null_eps
   LFDM_LAUNCH(cfg_combine_kernel, dim3(lfdm_blocks(n, 256, 2048)), dim3(256), 0, stream, cond_eps, null_eps, scale,
               out, n);
   return lfdm_check_launch("cfg_combine");
+}
+
+// one 4-double partial per workgroup of launch A; 0 for arguments the entry point refuses
+extern "C" size_t lfdm_cfg_rescale_ws_bytes(int batch, int64_t n) {
+  if (batch <= 0 || n < 2) return 0;
+  return (size_t)batch * rescale_blocks(n) * 4 * sizeof(double);
+}
+
+extern "C" int lfdm_cfg_combine_rescale_f32(const float* cond_eps, const float* null_eps, float scale, float phi, float* out, float* factor_out,
+                                            int batch, int64_t n, void* ws, size_t ws_bytes, lfdm_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!cond_eps || !null_eps || !out || !ws || batch <= 0 || batch > 65535 || n < 2 || !(phi >= 0.f && phi <= 1.f))
+    return lfdm_fail(LFDM_EINVAL, "cfg_combine_rescale: bad arguments (0 < batch < 65536, n >= 2 - an unbiased deviation -, phi in [0, 1], a workspace)");
+  if (!lfdm_aligned<8>(ws) || ws_bytes < lfdm_cfg_rescale_ws_bytes(batch, n))
+    return lfdm_fail(LFDM_EINVAL, "cfg_combine_rescale: workspace too small (lfdm_cfg_rescale_ws_bytes) or not 8-byte aligned");
+  const dim3 grid(rescale_blocks(n), batch), block(256);
+  double* partial = (double*)ws;
+  LFDM_LAUNCH(cfg_rescale_stats_kernel, grid, block, 0, stream, cond_eps, null_eps, scale, n, partial);
+  LFDM_LAUNCH(cfg_rescale_apply_kernel, grid, block, 0, stream, cond_eps, null_eps, scale, phi, out, factor_out, n, (const double*)partial);
+  return lfdm_check_launch("cfg_combine_rescale");
 }
 
 extern "C" size_t lfdm_sampler_ws_bytes(int batch, int64_t n) {

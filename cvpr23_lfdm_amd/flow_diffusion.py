@@ -72,7 +72,7 @@ class FlowDiffusion(nn.Module):
                  learn_null_cond=False, use_deconv=True, padding_mode="zeros", pretrained_pth="",
                  config_pth="", bert_path=None, *, conv_precision="fp32", sampler="reference", ema_decay=None, ema_start_step=0,
                  max_grad_norm=None, skip_nonfinite=False, long_attention=False, noise="torch", known_train=None,
-                 objective="pred_noise", min_snr_gamma=None):
+                 objective="pred_noise", min_snr_gamma=None, schedule="cosine", step_grid="reference", guidance_rescale=0.0):
         """Reference signature (video_flow_diffusion_model.py:19-37) + `bert_path`: a local Hugging Face directory of
         bert-base-cased for `cond=list[str]` (the reference downloads it with torch.hub; see text.py).  LFDM_BERT_PATH in
         the environment is the default, so unchanged caller scripts pick it up.
@@ -92,7 +92,12 @@ class FlowDiffusion(nn.Module):
         the checkpoint can be sampled with known_level="clean" (DESIGN.md 4.12).  Not available in the functional flavour.
         objective / min_snr_gamma (keyword only, defaults "pred_noise" / None: the reference's step): GaussianDiffusion.objective - what the
         denoiser predicts, "pred_noise", "pred_x0" or "pred_v" - and the min-SNR-gamma loss weight.  A checkpoint is
-        sampled with the objective it was trained with.  Not available in the functional flavour."""
+        sampled with the objective it was trained with.  Not available in the functional flavour.
+        schedule / step_grid / guidance_rescale (keyword only, defaults "cosine" / "reference" / 0.0: the reference's tables and launches):
+        GaussianDiffusion's - "cosine_zsnr", the cosine schedule rescaled to zero terminal SNR (training and sampling; refused with
+        "pred_noise"; a checkpoint is sampled on the schedule it was trained on), "trailing", the step grid that starts at the last
+        timestep, and the rescale of the guided output towards the conditional output's standard deviation (sampling with cond_scale
+        other than 0 and 1), after Lin et al. 2024.  In both flavours."""
         super().__init__()
         if noise not in GaussianDiffusion.NOISE_MODES:
             raise ValueError("noise must be one of %s, got %r" % (GaussianDiffusion.NOISE_MODES, noise))
@@ -128,7 +133,8 @@ class FlowDiffusion(nn.Module):
                                            loss_type='l2', use_dynamic_thres=True,
                                            null_cond_prob=null_cond_prob, ddim_sampling_eta=ddim_sampling_eta, sampler=sampler,
                                            long_attention=self.long_attention, noise=noise, known_train=known_train,
-                                           objective=objective, min_snr_gamma=min_snr_gamma)
+                                           objective=objective, min_snr_gamma=min_snr_gamma, schedule=schedule, step_grid=step_grid,
+                                           guidance_rescale=guidance_rescale)
         bert_path = bert_path or os.environ.get("LFDM_BERT_PATH")
         if bert_path:
             from .text import BertTextEncoder

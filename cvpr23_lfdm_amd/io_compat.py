@@ -261,3 +261,14 @@ def checkpoint_objective(ck, flag=None, path="the checkpoint"):
     if flag is not None and stored is not None and flag != stored:
         raise ValueError("--objective %s contradicts %s, which was trained with objective %s" % (flag, path, stored))
     return flag if flag is not None else stored if stored is not None else "pred_noise"
+
+
+def checkpoint_schedule(ck, flag=None, path="the checkpoint"):
+    """The noise schedule to build a DM checkpoint's model with: the checkpoint's top-level "schedule" ("cosine" where there
+    is none: the reference's checkpoints and every one written before the entry existed), or `flag` where there is no checkpoint (`ck`
+    None).  A `flag` that contradicts the checkpoint is a ValueError with both values - a denoiser is sampled on the schedule it was
+    trained on."""
+    stored = None if ck is None else ck.get("schedule", "cosine")
+    if flag is not None and stored is not None and flag != stored:
+        raise ValueError("--schedule %s contradicts %s, which was trained on schedule %s" % (flag, path, stored))
+    return flag if flag is not None else stored if stored is not None else "cosine"

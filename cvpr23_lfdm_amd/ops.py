@@ -1308,6 +1308,38 @@ def cfg_combine(cond_eps, null_eps, scale, out):
     return out
 
 
+def cfg_rescale_ws(batch, n, device):
+    """Workspace of cfg_combine_rescale for (batch, n) operands: lfdm_cfg_rescale_ws_bytes, as doubles; no initialisation, no state."""
+    nbytes = _lib().lfdm_cfg_rescale_ws_bytes(batch, n)
+    if nbytes == 0:
+        raise ValueError("cfg_rescale_ws: needs batch > 0 and n >= 2 elements per sample, got batch %r, n %r" % (batch, n))
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def cfg_combine_rescale(cond, null, scale, phi, out, ws=None, factor_out=None):
+    """lfdm_cfg_combine_rescale_f32: out = g * (phi * std(cond) / std(g) + 1 - phi) with g = null + (cond - null) * scale (cfg_combine's
+    bits) and both standard deviations per sample - dim 0 - over all of its n elements, unbiased, in double (Lin et al. 2024, DESIGN.md
+    4.15).  cond / null / out: dense float32 of one shape (batch, ...); out may be cond or null.  phi in [0, 1]; 0 gives cfg_combine's
+    bits.  ws: cfg_rescale_ws(batch, n) (made here when None; any tensor of enough bytes).  factor_out: None or (batch,) float32, the
+    factor each sample was multiplied by.  Two launches, no atomics: the same bits on every run, whatever the batch around a sample."""
+    lib = _lib()
+    _chk(lib, cond, null, out, factor_out)
+    for name, t in (("cond", cond), ("null", null), ("out", out)):
+        if t.dtype != torch.float32 or t.dim() < 1 or tuple(t.shape) != tuple(cond.shape) or not t.is_contiguous():
+            raise ValueError("cfg_combine_rescale: %s must be a dense float32 tensor of cond's shape %s" % (name, tuple(cond.shape)))
+    batch = cond.shape[0]
+    n = cond.numel() // batch if batch else 0
+    if factor_out is not None and (factor_out.dtype != torch.float32 or factor_out.numel() != batch or not factor_out.is_contiguous()):
+        raise ValueError("cfg_combine_rescale: factor_out must be a dense float32 tensor of %d element(s)" % batch)
+    if ws is None:
+        ws = cfg_rescale_ws(batch, n, cond.device)
+    elif ws.device != cond.device or not ws.is_contiguous():
+        raise ValueError("cfg_combine_rescale: ws must be a dense tensor on the operands' device")
+    lib.check(lib.lfdm_cfg_combine_rescale_f32(_p(cond), _p(null), float(scale), float(phi), _p(out), _p(factor_out), batch, n, _p(ws),
+                                               ws.numel() * ws.element_size(), _stream(lib)), "lfdm_cfg_combine_rescale_f32")
+    return out
+
+
 def abs_quantile(x, quantile=0.9, ws=None):
     lib = _lib()
     batch = x.shape[0]

@@ -651,14 +651,21 @@ class Unet3D(ParamTree):
         return out
 
     # ------------------------------------------------------------------ reference-compatible API
-    def forward_with_cond_scale(self, *args, cond_scale=2., **kwargs):
-        """:511-526."""
+    def forward_with_cond_scale(self, *args, cond_scale=2., guidance_rescale=0., **kwargs):
+        """:511-526.  guidance_rescale (keyword, default 0: the reference's expression): with two passes, the guided output g is returned
+        as g (phi std(logits) / std(g) + 1 - phi), per sample and unbiased, by ops.cfg_combine_rescale; with one pass it
+        changes nothing."""
+        from .diffusion import check_guidance_rescale
+        phi = check_guidance_rescale(guidance_rescale)
         if cond_scale == 0:
             return self.forward(*args, null_cond_prob=1., **kwargs)
         logits = self.forward(*args, null_cond_prob=0., **kwargs)
         if cond_scale == 1 or not self.has_cond:
             return logits
         null_logits = self.forward(*args, null_cond_prob=1., **kwargs)
+        if phi > 0.0:
+            logits, null_logits = logits.contiguous(), null_logits.contiguous()
+            return ops.cfg_combine_rescale(logits, null_logits, cond_scale, phi, torch.empty_like(logits))
         return null_logits + (logits - null_logits) * cond_scale
 
     def forward(self, x, time, cond=None, null_cond_prob=0., none_cond_mask=None, focus_present_mask=None,

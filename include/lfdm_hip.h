@@ -417,6 +417,18 @@ int lfdm_philox_bits_u32(uint32_t* out, const uint64_t* seeds, int batch, int64_
 /* Layout: dense, any; out may alias cond_eps or null_eps. */
 int lfdm_cfg_combine_f32(const float* cond_eps, const float* null_eps, float scale, float* out,
                          int64_t n, lfdm_stream_t stream);
+/* The guidance combine with the rescale of Lin et al. 2024 (additive, ABI version unchanged):
+ *   g = null_eps + (cond_eps - null_eps) * scale  (the bits of lfdm_cfg_combine_f32),   out = g * (phi * std(cond_eps) / std(g) + 1 - phi)
+ * with both standard deviations per sample over its n elements, unbiased (n - 1), summed and formed in double; the factor is rounded to fp32
+ * once and is 1 where std(g) == 0.  phi in [0, 1]; phi = 0 gives lfdm_cfg_combine_f32's bits.  factor_out: NULL or `batch` floats, the factor
+ * of each sample.  ws: lfdm_cfg_rescale_ws_bytes(batch, n) bytes, 8-byte aligned, written and read by this call only (no state between
+ * calls).  Two launches, no atomics: the same bits on every run, and a sample's bits do not depend on the batch around it.  Refused with
+ * LFDM_EINVAL, nothing touched: n < 2, batch <= 0 (or > 65535), a null pointer, phi outside [0, 1], a workspace that is too small. */
+size_t lfdm_cfg_rescale_ws_bytes(int batch, int64_t n);
+/* Layout: cond_eps, null_eps and out dense (batch, n), any 4-byte aligned base (a sample whose bases are 16-byte aligned moves in 16-byte
+ * words, any other element by element - the same bits); out may alias cond_eps or null_eps; factor_out dense (batch). */
+int lfdm_cfg_combine_rescale_f32(const float* cond_eps, const float* null_eps, float scale, float phi, float* out, float* factor_out,
+                                 int batch, int64_t n, void* ws, size_t ws_bytes, lfdm_stream_t stream);
 /* stand-alone |x| quantile (torch.quantile semantics, :722-726) for tests: q_out[b] */
 int lfdm_abs_quantile_f32(const float* x, int batch, int64_t n, float quantile, float* q_out,
                           void* ws, size_t ws_bytes, lfdm_stream_t stream);

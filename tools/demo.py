@@ -59,6 +59,15 @@ def build_parser():
     ap.add_argument("--objective", choices=("pred_noise", "pred_x0", "pred_v"), default=None,
                     help="what the denoiser predicts (tools/train_dm.py --objective, DESIGN.md 4.14); default: the checkpoint's own entry "
                          "(pred_noise where it has none) - a value that contradicts the checkpoint is an error")
+    ap.add_argument("--schedule", choices=("cosine", "cosine_zsnr"), default=None,
+                    help="the noise schedule the checkpoint was trained on (tools/train_dm.py --schedule, DESIGN.md 4.15); default: the "
+                         "checkpoint's own entry (cosine where it has none) - a value that contradicts the checkpoint is an error")
+    ap.add_argument("--step-grid", choices=("reference", "trailing"), default="reference",
+                    help="the DDIM / --sampler time grid: the reference's (default), or trailing - it starts at the last timestep and ends on "
+                         "the clean latent (Lin et al. 2024, DESIGN.md 4.15)")
+    ap.add_argument("--guidance-rescale", type=float, default=0.0,
+                    help="phi in [0, 1]: with --cond-scale other than 0 and 1, scale the guided output towards the conditional output's "
+                         "standard deviation (Lin et al. 2024, DESIGN.md 4.15); 0 (default): off")
     ap.add_argument("--use-ema", action="store_true",
                     help="sample from the averaged weights: the checkpoint's 'diffusion_ema' entry (tools/train_dm.py --ema-decay, DESIGN.md 4.4)")
     ap.add_argument("--long-attention", action="store_true", help="windows of 65 ... 256 frames (and a mid block of up to 256 pixels per frame) on the streaming attention kernels (FlowDiffusion(long_attention=True), DESIGN.md 4.8)")
@@ -217,13 +226,19 @@ def make_model(args, *, steps=None, sampler=None, conv_precision=None, use_ema=N
     ck = torch.load(args.dm_ckpt, map_location="cpu") if args.dm_ckpt and not args.synthetic else None
     try:
         objective = C.checkpoint_objective(ck, getattr(args, "objective", None), args.dm_ckpt)
+        schedule = C.checkpoint_schedule(ck, getattr(args, "schedule", None), args.dm_ckpt)
     except ValueError as e:
         sys.exit(str(e))
-    model = FlowDiffusion(is_train=False, img_size=args.size // 4, num_frames=args.frames, sampling_timesteps=steps,
-                          null_cond_prob=0.1, config_pth=args.config, pretrained_pth=args.lfae_ckpt,
-                          bert_path=None if args.synthetic else args.bert, conv_precision=conv_precision,
-                          sampler=sampler, long_attention=getattr(args, "long_attention", False),
-                          noise=getattr(args, "noise", "torch"), objective=objective)                       # demo_mug.py:80-88
+    try:
+        model = FlowDiffusion(is_train=False, img_size=args.size // 4, num_frames=args.frames, sampling_timesteps=steps,
+                              null_cond_prob=0.1, config_pth=args.config, pretrained_pth=args.lfae_ckpt,
+                              bert_path=None if args.synthetic else args.bert, conv_precision=conv_precision,
+                              sampler=sampler, long_attention=getattr(args, "long_attention", False),
+                              noise=getattr(args, "noise", "torch"), objective=objective, schedule=schedule,
+                              step_grid=getattr(args, "step_grid", "reference"),
+                              guidance_rescale=getattr(args, "guidance_rescale", 0.0))                         # demo_mug.py:80-88
+    except ValueError as e:             # (cosine_zsnr with pred_noise, a --guidance-rescale outside [0, 1])
+        sys.exit(str(e))
     if args.synthetic:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import synth

@@ -60,6 +60,12 @@ def build_parser():
         p.add_argument("--conv-precision", choices=("fp32", "bf16"), default="fp32")
         p.add_argument("--objective", choices=("pred_noise", "pred_x0", "pred_v"), default=None,
                        help="what the denoiser predicts (DESIGN.md 4.14); default: the checkpoint's own entry - a contradiction is an error")
+        p.add_argument("--schedule", choices=("cosine", "cosine_zsnr"), default=None,
+                       help="the noise schedule the checkpoint was trained on (DESIGN.md 4.15); default: the checkpoint's own entry - a contradiction is an error")
+        p.add_argument("--step-grid", choices=("reference", "trailing"), default="reference",
+                       help="the sampler's time grid: the reference's, or trailing - from the last timestep to the clean latent (DESIGN.md 4.15)")
+        p.add_argument("--guidance-rescale", type=float, default=0.0,
+                       help="phi in [0, 1]: rescale the guided output (--cond-scale other than 0 and 1) towards the conditional output's standard deviation (DESIGN.md 4.15)")
         p.add_argument("--use-ema", action="store_true", help="sample from the checkpoint's 'diffusion_ema' entry")
         p.add_argument("--long-attention", action="store_true", help="windows of 65 ... 256 frames (and a mid block of up to 256 pixels per frame) on the streaming attention kernels (FlowDiffusion(long_attention=True), DESIGN.md 4.8)")
         p.add_argument("--cond-scale", type=float, default=1.0)

@@ -80,6 +80,10 @@ def parse_args(argv=None):
     ap.add_argument("--objective", choices=("pred_noise", "pred_x0", "pred_v"), default="pred_noise",
                     help="what the denoiser predicts (FlowDiffusion(objective=...), DESIGN.md 4.14): the noise (default, the reference's), x0, "
                          "or v = a noise - s x0; stored in the checkpoint, which tools/demo.py and tools/eval.py then sample accordingly")
+    ap.add_argument("--schedule", choices=("cosine", "cosine_zsnr"), default="cosine",
+                    help="the noise schedule (FlowDiffusion(schedule=...), DESIGN.md 4.15): the reference's cosine (default) or cosine_zsnr, the "
+                         "same rescaled to zero terminal SNR (Lin et al. 2024; needs --objective pred_v or pred_x0); stored in the checkpoint, "
+                         "which tools/demo.py and tools/eval.py then sample on")
     ap.add_argument("--min-snr-gamma", type=float, default=None,
                     help="min-SNR-gamma loss weights (Hang et al. 2023; 5 is the paper's value); default: every timestep weighs 1")
     ap.add_argument("--log-loss-quartiles", action="store_true",
@@ -162,12 +166,15 @@ def main(argv=None):
     np.random.seed(args.seed)
     os.makedirs(args.out, exist_ok=True)
 
+    if args.schedule == "cosine_zsnr" and args.objective == "pred_noise":
+        sys.exit("--schedule cosine_zsnr needs --objective pred_v or pred_x0: the noise prediction carries no information at SNR 0")
     model = FlowDiffusion(lr=args.lr, is_train=True, img_size=args.size // 4, num_frames=args.frames,
                           null_cond_prob=args.null_cond_prob, sampling_timesteps=args.preview_steps or 1000, config_pth=args.config,
                           pretrained_pth=args.lfae_ckpt, bert_path=None if args.synthetic else args.bert,     # :153-162
                           ema_decay=args.ema_decay, ema_start_step=args.ema_start_step, max_grad_norm=args.max_grad_norm,
                           skip_nonfinite=args.skip_nonfinite, long_attention=args.long_attention, known_train=known_train(args),
-                          dim_mults=tuple(args.dim_mults), objective=args.objective, min_snr_gamma=args.min_snr_gamma)
+                          dim_mults=tuple(args.dim_mults), objective=args.objective, min_snr_gamma=args.min_snr_gamma,
+                          schedule=args.schedule)
     quartiles = None
     if args.log_loss_quartiles:
         if args.objective == "pred_noise" and args.min_snr_gamma is None:
@@ -186,8 +193,9 @@ def main(argv=None):
     start_step = 0
     if args.restore_from:                                                                                     # :169-184
         ck = torch.load(args.restore_from, map_location="cpu")
-        try:                                 # a run continues on the objective its checkpoint was trained with
+        try:                                 # a run continues on the objective and the schedule its checkpoint was trained with
             C.checkpoint_objective(ck, args.objective, args.restore_from)
+            C.checkpoint_schedule(ck, args.schedule, args.restore_from)
         except ValueError as e:
             sys.exit(str(e))
         if args.set_start:
@@ -271,7 +279,8 @@ def main(argv=None):
                               C.video_strip(model, ref_imgs[:1]))
             if rank == 0 and (step % args.save_freq == 0 or step >= args.final_step):                         # :330-340
                 ck = {"example": step * args.batch_size * world, "diffusion": model.diffusion.state_dict(),
-                      "optimizer_diff": opt.state_dict(), "objective": args.objective, "min_snr_gamma": args.min_snr_gamma}
+                      "optimizer_diff": opt.state_dict(), "objective": args.objective, "min_snr_gamma": args.min_snr_gamma,
+                      "schedule": args.schedule}
                 if args.ema_decay is not None:          # the averaged weights, shaped like "diffusion" (tools/demo.py --use-ema)
                     ck["diffusion_ema"] = model.ema_state_dict()
                 torch.save(ck,
