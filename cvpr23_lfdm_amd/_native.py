@@ -294,6 +294,9 @@ _SIGNATURES = {
                                           i32, i64, i32, f32p, f32p, f32p, f32p, i32, i64, C.c_void_p, sz, C.c_void_p, stream_t]),
     "lfdm_objective_loss_bwd_f32": (i32, [i32, f32p, f32p, f32p, C.c_void_p, f32p, f32p, f32p, i32, C.c_void_p, C.c_void_p, i32, i64, i32,
                                           f32p, f32p, f32p, i32, i64, stream_t]),
+    # ---- progressive distillation: per-sample teacher step and target (additive, ABI stays 13)
+    "lfdm_distill_x0_f32": (i32, [f32p, f32p, f32p, C.c_void_p, i32, f32p, i32, i64, stream_t]),
+    "lfdm_distill_step_f32": (i32, [f32p, f32p, f32p, C.c_void_p, i32, f32p, f32p, f32p, f32p, C.c_void_p, i32, f32p, f32p, i32, i64, stream_t]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -17,7 +17,7 @@
 // inside a float4, then a chain of four) and adds that to a double; lanes -> workgroup by a fixed tree of doubles in LDS; workgroup partials
 // (S and N as doubles) are 8-byte agent-scope words; the workgroup that takes the last ticket folds each sample's partials in index order
 // and the samples in index order, in double.  Two runs on the same inputs give the same bits.
-#include "lfdm_device.h"
+#include "train_elem_core.h"
 #include "../../include/lfdm_hip.h"
 
 // a * x_start + s * noise and r * x_noisy - m * pred are torch's expressions: two products and one sum, each rounded on its own
@@ -25,9 +25,6 @@
 
 namespace {
 
-constexpr int TD_BLOCK = 256;
-constexpr int TD_QUADS = 4;          // float4 per lane and trip
-constexpr int TD_CAP = 64;           // workgroups per sample
 constexpr int MASK_NONE = 0, MASK_FRAME = 1, MASK_ELEM = 2;
 
 struct TrainMask {
@@ -46,29 +43,6 @@ __device__ __forceinline__ unsigned known_bits(const TrainMask& m, unsigned b, u
   } else {
     return 0u;
   }
-}
-
-__device__ __forceinline__ int table_index(const int64_t* t, unsigned b, int t_len) {
-  const int64_t v = t[b];
-  return (int)(v < 0 ? 0 : v >= t_len ? t_len - 1 : v);
-}
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
-// what the three kernels' loops share: the float4 slots of this lane in the current trip
-struct Trip {
-  unsigned q[TD_QUADS];
-  bool in[TD_QUADS];
-};
-__device__ __forceinline__ Trip trip_slots(unsigned q0, unsigned n4) {
-  Trip s;
-#pragma unroll
-  for (int k = 0; k < TD_QUADS; ++k) {
-    s.q[k] = q0 + (unsigned)k * TD_BLOCK;
-    s.in[k] = s.q[k] < n4;
-  }
-  return s;
 }
 
 template <int MASK>
@@ -393,8 +367,6 @@ __global__ __launch_bounds__(TD_BLOCK) void objective_loss_bwd_kernel(const floa
     }
   }
 }
-
-unsigned sample_blocks(int64_t n) { return lfdm_blocks(n / 4, TD_BLOCK * TD_QUADS, TD_CAP); }
 
 // The one check of the geometry and the mask operands; -> MASK_* or a refusal.
 int check_mask(const char* what, int batch, int64_t n, const unsigned char* frame_mask, const unsigned char* elem_mask, int frames,

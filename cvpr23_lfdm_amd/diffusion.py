@@ -372,6 +372,7 @@ class GaussianDiffusion(nn.Module):
         # (rank, world) under sharded data parallelism (FlowDiffusion.enable_data_parallel): the training step's random
         # draws are made for the GLOBAL batch on every rank (identical generators) and sliced
         self.rank_shard = None
+        self._distill, self._distill_dev = None, {}      # set_distill: the round's settings (no module, no buffer)
         self.register_load_state_dict_post_hook(self._check_loaded_schedule)
 
     @staticmethod
@@ -408,6 +409,153 @@ class GaussianDiffusion(nn.Module):
         w = clipped / snr if self.objective == "pred_noise" else clipped if self.objective == "pred_x0" else clipped / (snr + 1.0)
         return w.float()
 
+    # ------------------------------------------------------------------ progressive distillation
+    DISTILL_WEIGHTS = ("truncated_snr", "min_snr", None)
+
+    def distill_tables(self, student_steps, distill_weight="truncated_snr"):
+        """The host tables of one round of progressive distillation (Salimans & Ho 2022): an N-step student from a 2N-step teacher, both
+        on the "trailing" DDIM grid at eta = 0, N = student_steps.  A pure function of the registered buffers - in double from their fp32
+        values, rounded once; `sampling_timesteps`, `ddim_sampling_eta` and the `_schedule` cache are neither read nor written.  -> dict:
+          teacher_times (2N,) int64, teacher_coef (2N, 6) fp32;  student_times (N,), student_coef (N, 6): the rows `_objective_rows` makes,
+              {c_x, c_eps, k_x0, 0, k_x, 0}; teacher_times[2k] == student_times[k] - the N-step nodes are the even nodes of the 2N-step grid
+          target_coef (N, 4) fp32 {q0, q1, q2, q3} of student row k at its time t: q0 = 1 / k_x0, q1 = -k_x / k_x0 - x_target = q0 z'' + q1 z
+              is the x0 for which the student's own DDIM row takes z to z'', the teacher's result after two steps - and q2 = 1 / s_t,
+              q3 = -a_t / s_t - eps_target = q2 z + q3 x_target is the noise that x_target implies at z's level
+          weight (timesteps,) fp32: "truncated_snr" (default, the paper's) max(snr, 1) on the x0 error, carried to the objective as
+              `_loss_weight_table` does - max(snr, 1) for "pred_x0", max(snr, 1) / (snr + 1) for "pred_v", 1 at a zero-SNR node where
+              min-SNR gives 0; "min_snr": the model's `loss_weight`; None: 1."""
+        if self.objective not in ("pred_x0", "pred_v"):
+            raise ValueError("distillation needs objective='pred_x0' or 'pred_v', got %r: the noise-objective row cannot be inverted through the "
+                             "threshold, and the noise prediction is unsuitable at few steps (Salimans & Ho 2022, section 4) - train and "
+                             "distil a 'pred_v' model" % (self.objective,))
+        if self.step_grid != "trailing":
+            raise ValueError("distillation needs step_grid='trailing', got %r: the N-step nodes of the reference linspace grid are not nodes "
+                             "of its 2N-step grid - build the model with step_grid='trailing'" % (self.step_grid,))
+        if self.per_element_loss:
+            raise ValueError("distillation with per_element_loss=True (the functional multi-GPU flavour) is not built - use per_element_loss=False")
+        if self.known_policy is not None:
+            raise ValueError("distillation together with known_train is not built - build the model with known_train=None")
+        if distill_weight not in self.DISTILL_WEIGHTS:
+            raise ValueError("distill_weight must be one of %s, got %r" % (self.DISTILL_WEIGHTS, distill_weight))
+        n = student_steps
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1 or 2 * n > self.num_timesteps:
+            raise ValueError("student_steps must be an integer in [1, timesteps / 2 = %d] (the teacher takes 2 student_steps steps), got %r"
+                             % (self.num_timesteps // 2, n))
+        b = {k: v.detach().float().cpu() for k, v in self.named_buffers(recurse=False)}
+        out = {}
+        for who, steps in (("teacher", 2 * n), ("student", n)):
+            rows, times, _ = self._trailing_ddim_rows(self.ddim_times(steps), 0.0, b, steps)
+            rows = self._objective_rows(times, torch.stack(rows), ddim_rows=True, rounded=False)
+            rows[:, 5] = 0.0
+            out[who + "_times"], out[who + "_coef"] = torch.tensor(times, dtype=torch.int64), rows.float().contiguous()
+        t = out["student_times"]
+        a_t, s_t = b["sqrt_alphas_cumprod"].double()[t], b["sqrt_one_minus_alphas_cumprod"].double()[t]
+        k_x0, k_x = rows[:, 2], rows[:, 4]           # (the student's rows, still in double)
+        if not bool((k_x0 != 0).all()):
+            raise ValueError("distillation: a student row with k_x0 = 0 cannot be inverted (student_steps=%d)" % n)
+        out["target_coef"] = torch.stack([1.0 / k_x0, -k_x / k_x0, 1.0 / s_t, -a_t / s_t], dim=1).float().contiguous()
+        if distill_weight == "truncated_snr":
+            acp = b["alphas_cumprod"].double()
+            snr = acp / (1.0 - acp)
+            w = snr.clamp(min=1.0)
+            out["weight"] = (w if self.objective == "pred_x0" else w / (snr + 1.0)).float()
+        elif distill_weight == "min_snr":
+            out["weight"] = b["loss_weight"].clone()
+        else:
+            out["weight"] = torch.ones(self.num_timesteps, dtype=torch.float32)
+        return out
+
+    def set_distill(self, teacher, student_steps=None, teacher_cond_scale=1.0, teacher_guidance_rescale=0.0, distill_weight="truncated_snr"):
+        """Turn `forward` into one step of progressive distillation; set_distill(None) turns it off again.  teacher: the
+        frozen 2 student_steps-step denoiser - put into eval mode with requires_grad off here, held OUTSIDE the module tree (no state-dict
+        key, no parameter of this module, not moved by .to(): it has to sit on the training device already).  teacher_cond_scale w != 1:
+        every teacher output is forward_with_cond_scale(cond_scale=w, guidance_rescale=teacher_guidance_rescale) - the guided two-pass
+        teacher folded into a student that is sampled at cond_scale = 1.  The tables are checked here and made on the device at the first
+        step; nothing is registered.  The teacher always sees the step's condition; the student's condition is dropped with
+        `null_cond_prob` as in `p_losses`, so that has to be 0 while distilling (a dropped sample would learn the conditional target on the
+        null branch) and a distilled student cannot be guided at sampling: guidance is folded in through teacher_cond_scale."""
+        if teacher is None:
+            self._distill, self._distill_dev = None, {}
+            return
+        if teacher is self.denoise_fn:
+            raise ValueError("set_distill: the teacher must be a frozen copy, not the student itself (copy.deepcopy(model.unet))")
+        if isinstance(teacher_cond_scale, bool) or not isinstance(teacher_cond_scale, (int, float)) or not math.isfinite(teacher_cond_scale):
+            raise ValueError("set_distill: teacher_cond_scale must be a finite number, got %r" % (teacher_cond_scale,))
+        phi = check_guidance_rescale(teacher_guidance_rescale)
+        self.distill_tables(student_steps, distill_weight)         # (every refusal, before anything is kept)
+        teacher.eval()
+        teacher.requires_grad_(False)
+        # (inside a plain dict the teacher is no sub-module: nn.Module registers modules assigned as attributes only)
+        self._distill = dict(teacher=teacher, steps=student_steps, cond_scale=float(teacher_cond_scale), rescale=phi,
+                                         weight=distill_weight)
+        self._distill_dev = {}
+
+    def _distill_device_tables(self, dev):
+        """`distill_tables` of the current round on `dev`, kept behind a key like `_schedule_key` (the buffers' stamps last)."""
+        cfg = self._distill
+        key = (cfg["steps"], cfg["weight"], str(dev), self.objective, self.schedule, self.step_grid, self.num_timesteps, self.min_snr_gamma,
+               tuple((k, v._version, v.data_ptr()) for k, v in self.named_buffers(recurse=False)))
+        tabs = self._distill_dev.get(key)
+        if tabs is None:
+            tabs = {k: v.to(dev) for k, v in self.distill_tables(cfg["steps"], cfg["weight"]).items()}
+            self._distill_dev = {key: tabs}
+        return tabs
+
+    def _distill_forward(self, x, fea, text, noise=None, clip_denoised=True, known_mask=None, **kwargs):
+        """`forward` while a round is set: k ~ U{0 .. N-1} and the noise for the global batch (this rank's rows), t = student_times[k] gathered
+        on the device, z = q_sample(x, t); the teacher's two DDIM steps from z under no_grad on the forward-only executor (same condition, no
+        condition dropout, no draws) end in the target kernel; the student runs as in `p_losses` and is compared, through the objective's loss
+        kernels, with (x_start = x_target, noise = eps_target) under the distillation weight.  No host read-back."""
+        from .autograd import objective_diffusion_loss
+        cfg = self._distill
+        if known_mask is not None:
+            raise ValueError("distillation with a known_mask is not built - call forward without one, or set_distill(None)")
+        if self.loss_type not in ops.LOSS_TYPES:
+            raise NotImplementedError()
+        b, device = x.shape[0], x.device
+        lo, hi, total = shard_bounds(self.rank_shard, b) if self.rank_shard is not None else (0, b, b)
+        tabs = self._distill_device_tables(device)
+        k = torch.randint(0, cfg["steps"], (total,), device=device).long()[lo:hi].contiguous()
+        if noise is None:
+            noise = torch.randn_like(x.new_empty((total,) + tuple(x.shape[1:])))[lo:hi]
+        x, noise = x.float().contiguous(), noise.float().contiguous()
+        t = tabs["student_times"][k]
+        a_tab, s_tab = self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod
+        z = ops.train_qsample(x, noise, t, a_tab, s_tab)
+        cond, none_cond_mask = self._train_cond(text, device)
+        teacher, w, coef = cfg["teacher"], cfg["cond_scale"], tabs["teacher_coef"]
+        fea5 = fea if fea.dim() == 5 else fea.unsqueeze(2).expand(-1, -1, x.shape[2], -1, -1)
+
+        def teach(latent, times):
+            inp = torch.cat([latent, fea5], dim=1)
+            if w == 1.0:
+                out = teacher.forward(inp, times, cond=cond, null_cond_prob=0., none_cond_mask=none_cond_mask)
+            else:
+                out = teacher.forward_with_cond_scale(inp, times, cond=cond, none_cond_mask=none_cond_mask, cond_scale=w,
+                                                      guidance_rescale=cfg["rescale"])
+            return out.contiguous()
+
+        def threshold(latent, out, row):
+            if not self.use_dynamic_thres:
+                return None
+            return ops.abs_quantile(ops.distill_x0(latent, out, coef, row).reshape(b, -1), self.dynamic_thres_percentile)
+
+        with torch.no_grad():
+            row1 = (2 * k).contiguous()
+            row2 = row1 + 1
+            out1 = teach(z, tabs["teacher_times"][row1])
+            z1 = ops.distill_step(z, out1, coef, row1, threshold(z, out1, row1))
+            out2 = teach(z1, tabs["teacher_times"][row2])
+            _, x_target, eps_target = ops.distill_step(z1, out2, coef, row2, threshold(z1, out2, row2), None, x_ref=z,
+                                                       tcoef=tabs["target_coef"], trow=k)
+        out = self._denoise(z, t, fea, cond, none_cond_mask, kwargs)
+        loss_tabs = (a_tab, s_tab, self.sqrt_recip_alphas_cumprod, self.sqrt_recipm1_alphas_cumprod, tabs["weight"])
+        loss, pred_x0, self.sample_loss = objective_diffusion_loss(out.contiguous(), x_target, eps_target, z, t, loss_tabs, None, self.loss_type,
+                                                                   self.objective)
+        self.sample_t = t
+        self.pred_x0 = self._clip_pred_x0(pred_x0) if clip_denoised else pred_x0
+        return loss
+
     @property
     def noise(self):
         return self._noise
@@ -439,8 +587,8 @@ class GaussianDiffusion(nn.Module):
     def skip_step_draws(self, total, sample_shape, device, prob_focus_present=0.):
         """Advance the default generator exactly as one training step over `total` videos does (t :899, noise :858, the
         focus-present mask :542-543 - drawn before - and the null condition mask :55-61) without running the model - a
-        data-parallel rank whose shard is empty this step."""
-        torch.randint(0, self.num_timesteps, (total,), device=device)
+        data-parallel rank whose shard is empty this step.  While a distillation round is set the first draw is its k ~ U{0 .. N-1}."""
+        torch.randint(0, self.num_timesteps if self._distill is None else self._distill["steps"], (total,), device=device)
         torch.randn_like(torch.empty((total,) + tuple(sample_shape), device=device))
         if 0 < prob_focus_present < 1:
             torch.zeros((total,), device=device).float().uniform_(0, 1)
@@ -467,7 +615,7 @@ class GaussianDiffusion(nn.Module):
             out.normal_()
         return out
 
-    def ddim_times(self):
+    def ddim_times(self, steps=None):
         """The (time, time_next) pairs of the DDIM / multistep grid.  step_grid="reference" (:784-786): linspace(0, T, steps + 2)[:-1]
         reversed - the first node is below T - 1 (990 at T = 1000 with 100 steps, 952 with 20) and the last target is the end marker 0.
         step_grid="trailing" (Lin et al. 2024): t_i = round(T - i T / steps) - 1 for i = 0 .. steps - 1 (Python's round, half to even, as
@@ -475,14 +623,32 @@ class GaussianDiffusion(nn.Module):
         end (a = 1, s = 0); nothing is drawn on the step that reaches it.  Under "trailing" EVERY node sits on alphas_cumprod[time]: the level
         the denoiser is conditioned on, the level of the step rows and the `_level_table` of known frames - deliberately not the reference
         DDIM rows' alphas_cumprod_prev[time], one timestep cleaner than what the denoiser is told.  A grid that does not strictly decrease
-        is refused by the tables.  DDPM (sampling_timesteps == timesteps, "reference" sampler) walks every timestep: no grid, the option is ignored."""
+        is refused by the tables.  DDPM (sampling_timesteps == timesteps, "reference" sampler) walks every timestep: no grid, the option is ignored.
+        steps (default: sampling_timesteps): the "trailing" grid of another step count (`distill_tables`)."""
         if self.step_grid == "trailing":
-            total, steps = self.num_timesteps, self.sampling_timesteps
+            total, steps = self.num_timesteps, self.sampling_timesteps if steps is None else steps
             times = [round(total - i * total / steps) - 1 for i in range(steps)] + [-1]
             return list(zip(times[:-1], times[1:]))
         times = torch.linspace(0., self.num_timesteps, steps=self.sampling_timesteps + 2)[:-1]
         times = list(reversed(times.int().tolist()))
         return list(zip(times[:-1], times[1:]))
+
+    def _trailing_ddim_rows(self, pairs, eta, b, steps=None):
+        """The double rows {c_x, c_eps, k_x0, k_eps, 0, k_noise} of the "trailing" DDIM grid `pairs` at `eta` (the comment in `_step_tables`),
+        their timesteps and draw flags.  b: the registered buffers as fp32 host tensors; steps: the step count an error message names."""
+        acp = b['alphas_cumprod'].double()
+        self._check_grid(pairs, "the trailing DDIM grid", steps)
+        rows, times, draws = [], [], []
+        for time, time_next in pairs:
+            alpha, alpha_next = float(acp[time]), 1.0 if time_next < 0 else float(acp[time_next])
+            var = eta * eta * ((1.0 - alpha / alpha_next) * (1.0 - alpha_next) / (1.0 - alpha))
+            c = math.sqrt(max((1.0 - alpha_next) - var, 0.0))
+            draw = time_next >= 0
+            rows.append(torch.tensor([float(b['sqrt_recip_alphas_cumprod'][time]), float(b['sqrt_recipm1_alphas_cumprod'][time]),
+                                      math.sqrt(alpha_next), c, 0.0, math.sqrt(var) if draw else 0.0], dtype=torch.float64))
+            times.append(time)
+            draws.append(draw)
+        return rows, times, draws
 
     def _step_tables(self, ddim):
         """Per-step timestep list and the (steps, 6) coefficient table of lfdm_sampler_step_f32,
@@ -494,19 +660,7 @@ class GaussianDiffusion(nn.Module):
             # the reference's DDIM formula on alpha = alphas_cumprod[time], alpha_next = alphas_cumprod[time_next] (1 at the clean end -1), in
             # double from the fp32 buffers, rounded once; sigma^2 is formed without the square root in between, so that c is exactly 0 where
             # sigma^2 = 1 - alpha_next (eta = 1 on a node at alpha = 0: s = 1, sigma = eta sqrt(1 - alpha_next), c = sqrt((1 - alpha_next) - sigma^2))
-            eta = float(self.ddim_sampling_eta)
-            acp = b['alphas_cumprod'].double()
-            pairs = self.ddim_times()
-            self._check_grid(pairs, "the trailing DDIM grid")
-            for time, time_next in pairs:
-                alpha, alpha_next = float(acp[time]), 1.0 if time_next < 0 else float(acp[time_next])
-                var = eta * eta * ((1.0 - alpha / alpha_next) * (1.0 - alpha_next) / (1.0 - alpha))
-                c = math.sqrt(max((1.0 - alpha_next) - var, 0.0))
-                draw = time_next >= 0
-                rows.append(torch.tensor([float(b['sqrt_recip_alphas_cumprod'][time]), float(b['sqrt_recipm1_alphas_cumprod'][time]),
-                                          math.sqrt(alpha_next), c, 0.0, math.sqrt(var) if draw else 0.0], dtype=torch.float64))
-                times.append(time)
-                draws.append(draw)
+            rows, times, draws = self._trailing_ddim_rows(self.ddim_times(), float(self.ddim_sampling_eta), b)
         elif ddim:
             eta = self.ddim_sampling_eta
             for time, time_next in self.ddim_times():
@@ -531,14 +685,14 @@ class GaussianDiffusion(nn.Module):
             coef = self._objective_rows(times, coef, ddim_rows=bool(ddim))
         return times, coef, draws
 
-    def _objective_rows(self, times, coef, ddim_rows):
+    def _objective_rows(self, times, coef, ddim_rows, rounded=True):
         """The rows of a step table for "pred_v" / "pred_x0" (DESIGN.md 4.14): the update kernels compute x0 = c_x x - c_eps out, so only the
         table changes.  With a = sqrt_alphas_cumprod[time], s = sqrt_one_minus_alphas_cumprod[time], the fp32 buffer values:
             "pred_v":  c_x = a, c_eps = s (x0 = a x - s v);      "pred_x0":  c_x = 0, c_eps = -1 (0 x - (-1 out) = out exactly, x finite)
         DDPM and "dpmpp_*" rows use the thresholded x0 only: nothing else changes.  A reference DDIM row {A, c, 0, sigma} adds c times a noise
         estimate; for these objectives it is the one implied by the thresholded x0 on the level the denoiser was conditioned on,
         eps_hat = (x - a x0c) / s (the denoising-diffusion-pytorch convention), so k_x0 = A - c a / s, k_eps = 0, k_x = c / s, k_noise = sigma.
-        In double from the fp32 values, rounded once."""
+        In double from the fp32 values, rounded once (rounded=False: the double rows, for `distill_tables`)."""
         a_tab = self.sqrt_alphas_cumprod.detach().float().cpu().double()
         s_tab = self.sqrt_one_minus_alphas_cumprod.detach().float().cpu().double()
         rows = coef.double().clone()
@@ -550,16 +704,16 @@ class GaussianDiffusion(nn.Module):
                 big_a, c = float(rows[i, 2]), float(rows[i, 3])
                 rows[i, 2], rows[i, 3], rows[i, 4] = big_a - c * a / s, 0.0, c / s
             rows[i, 0], rows[i, 1] = (a, s) if self.objective == "pred_v" else (0.0, -1.0)
-        return rows.float().contiguous()
+        return rows.float().contiguous() if rounded else rows
 
-    def _check_grid(self, pairs, what):
+    def _check_grid(self, pairs, what, steps=None):
         """The grid strictly decreases inside [0, T); the last target alone may be the end marker: 0 ("reference") or -1 ("trailing")."""
         end = -1 if self.step_grid == "trailing" else 0
         for i, (time, time_next) in enumerate(pairs):
             low = end if i == len(pairs) - 1 else 0
             if not (low <= time_next < time < self.num_timesteps):
                 raise ValueError("%s needs strictly decreasing timesteps: sampling_timesteps=%d on %d timesteps gives the step %d -> %d"
-                                 % (what, self.sampling_timesteps, self.num_timesteps, time, time_next))
+                                 % (what, self.sampling_timesteps if steps is None else steps, self.num_timesteps, time, time_next))
 
     def _ms_step_tables(self, sampler):
         """Timestep list and the (steps, 6) table {c_x, c_eps, k_x, k_m, k_prev, 0} of the multistep lfdm_sampler_step_f32 for "dpmpp_2m" / "dpmpp_1":
@@ -1002,6 +1156,48 @@ class GaussianDiffusion(nn.Module):
         sthr = sthr.clamp(min=1.).view(-1, *((1,) * (pred_x0.dim() - 1)))
         return pred_x0.clamp(-sthr, sthr) / sthr
 
+    def _train_cond(self, cond, device):
+        """The condition of a training step as the denoiser takes it: -> (cond, none_cond_mask); list[str]: embedded, "None" entries masked."""
+        none_cond_mask = None
+        if is_list_str(cond):
+            none_cond_mask = [c == "None" for c in cond]
+            cond = self._embed(cond, device)
+        elif cond is not None:
+            cond = cond.to(device=device, dtype=torch.float32)
+        return cond, none_cond_mask
+
+    def _denoise(self, x_noisy, t, fea, cond, none_cond_mask, kwargs):
+        """The denoiser's output on x_noisy at t: in training mode with autograd enabled through unet_train_forward (native forward and
+        backward kernels, the output carries the graph), otherwise on the forward-only sampling executor.  kwargs: p_losses' extra keywords."""
+        unet = self.denoise_fn
+        if torch.is_grad_enabled() and unet.training and any(p.requires_grad for p in unet.parameters()):
+            from .unet_train import unet_train_forward
+            fkw = {}                            # forward(x, *args, **kwargs) -> denoise_fn(...) (:897-903, :870): the focus-present arguments
+            if "focus_present_mask" in kwargs and kwargs["focus_present_mask"] is not None:
+                fkw["focus"] = torch.as_tensor(kwargs.pop("focus_present_mask")).reshape(-1).tolist()
+            else:
+                kwargs.pop("focus_present_mask", None)
+            if "prob_focus_present" in kwargs:
+                fkw["prob_focus_present"] = float(kwargs.pop("prob_focus_present"))
+            if kwargs:
+                raise TypeError("p_losses: unexpected keyword arguments %s" % list(kwargs))
+            if fea.dim() == 5 and fea.stride(2) != 0 and fea.shape[2] > 1:
+                raise NotImplementedError("training with per-frame `fea`: the LFDM pipeline conditions on ONE reference "
+                                          "frame (video_flow_diffusion.py:901); pass the (B,256,S,S) feature map")
+            fea2d = fea[:, :, 0] if fea.dim() == 5 else fea
+            return unet_train_forward(unet, x_noisy, fea2d, t, cond, null_cond_prob=self.null_cond_prob,
+                                      none_cond_mask=none_cond_mask, rank_shard=self.rank_shard, **fkw)
+        was_training = unet.training
+        unet.eval()
+        try:
+            with torch.no_grad():
+                fea5 = fea if fea.dim() == 5 else fea.unsqueeze(2).expand(-1, -1, x_noisy.shape[2], -1, -1)
+                return unet.forward(torch.cat([x_noisy, fea5], dim=1), t, cond=cond,
+                                    null_cond_prob=self.null_cond_prob, none_cond_mask=none_cond_mask,
+                                    **kwargs)
+        finally:
+            unet.train(was_training)
+
     def p_losses(self, x_start, t, fea, cond=None, noise=None, clip_denoised=True, known_mask=None, **kwargs):
         """:856-895.  x_start (B,3,T,S,S), fea (B,256,T,S,S) (frame-constant when it comes from `forward`).
         In training mode with autograd enabled the denoiser runs through unet_train_forward (native forward and
@@ -1032,41 +1228,9 @@ class GaussianDiffusion(nn.Module):
                 mask_kw = {"frame_mask" if known_mask.dim() == 2 else "elem_mask": known_mask}
             x_start, noise, t = x_start.float().contiguous(), noise.float().contiguous(), t.to(torch.int64).contiguous()
             x_noisy = ops.train_qsample(x_start, noise, t, self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, **mask_kw)
-        none_cond_mask = None
-        if is_list_str(cond):
-            none_cond_mask = [c == "None" for c in cond]
-            cond = self._embed(cond, x_start.device)
-        elif cond is not None:
-            cond = cond.to(device=x_start.device, dtype=torch.float32)
+        cond, none_cond_mask = self._train_cond(cond, x_start.device)
         unet = self.denoise_fn
-        if torch.is_grad_enabled() and unet.training and any(p.requires_grad for p in unet.parameters()):
-            from .unet_train import unet_train_forward
-            fkw = {}                            # forward(x, *args, **kwargs) -> denoise_fn(...) (:897-903, :870): the focus-present arguments
-            if "focus_present_mask" in kwargs and kwargs["focus_present_mask"] is not None:
-                fkw["focus"] = torch.as_tensor(kwargs.pop("focus_present_mask")).reshape(-1).tolist()
-            else:
-                kwargs.pop("focus_present_mask", None)
-            if "prob_focus_present" in kwargs:
-                fkw["prob_focus_present"] = float(kwargs.pop("prob_focus_present"))
-            if kwargs:
-                raise TypeError("p_losses: unexpected keyword arguments %s" % list(kwargs))
-            if fea.dim() == 5 and fea.stride(2) != 0 and fea.shape[2] > 1:
-                raise NotImplementedError("training with per-frame `fea`: the LFDM pipeline conditions on ONE reference "
-                                          "frame (video_flow_diffusion.py:901); pass the (B,256,S,S) feature map")
-            fea2d = fea[:, :, 0] if fea.dim() == 5 else fea
-            pred_noise = unet_train_forward(unet, x_noisy, fea2d, t, cond, null_cond_prob=self.null_cond_prob,
-                                            none_cond_mask=none_cond_mask, rank_shard=self.rank_shard, **fkw)
-        else:
-            was_training = unet.training
-            unet.eval()
-            try:
-                with torch.no_grad():
-                    fea5 = fea if fea.dim() == 5 else fea.unsqueeze(2).expand(-1, -1, x_start.shape[2], -1, -1)
-                    pred_noise = unet.forward(torch.cat([x_noisy, fea5], dim=1), t, cond=cond,
-                                              null_cond_prob=self.null_cond_prob, none_cond_mask=none_cond_mask,
-                                              **kwargs)
-            finally:
-                unet.train(was_training)
+        pred_noise = self._denoise(x_noisy, t, fea, cond, none_cond_mask, kwargs)
         if objective_route:
             from .autograd import objective_diffusion_loss
             tabs = (self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod, self.sqrt_recip_alphas_cumprod,
@@ -1102,6 +1266,8 @@ class GaussianDiffusion(nn.Module):
         """:897-903."""
         b, device = x.shape[0], x.device
         fea = fea.unsqueeze(dim=2).expand(-1, -1, x.size(2), -1, -1)      # reference: .repeat (:901); a view is enough
+        if self._distill is not None:           # one step of progressive distillation (set_distill, DESIGN.md 4.16)
+            return self._distill_forward(x, fea, text, *args, **kwargs)
         if self.known_policy is not None and kwargs.get("known_mask") is None:
             # the policy's masks for the GLOBAL batch from its own CPU generator, this rank's rows, to the device as (B, T) bytes
             lo, hi, total = shard_bounds(self.rank_shard, b) if self.rank_shard is not None else (0, b, b)

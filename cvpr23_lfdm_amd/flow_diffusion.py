@@ -604,6 +604,32 @@ class FlowDiffusion(nn.Module):
     def real_warped_vid(self, v):
         self._real_warped_vid = v
 
+    # ------------------------------------------------------------------ progressive distillation
+    def begin_distill_round(self, student_steps, teacher=None, **kw):
+        """One round of progressive distillation (Salimans & Ho 2022): from here on every training step teaches `unet`, the student, to
+        reach in ONE DDIM step what the frozen teacher reaches in two, on the "trailing" grid of student_steps steps.  teacher=None: a deep
+        copy of the current `unet` - the student starts from the teacher's weights; keywords: GaussianDiffusion.set_distill's
+        (teacher_cond_scale, teacher_guidance_rescale, distill_weight).  Sampling is set to the student's schedule: sampling_timesteps =
+        student_steps, eta = 0.  forward() / optimize_parameters() are the ordinary ones - `self.diffusion(...)` is the distillation step -
+        so EMA, clipping, the non-finite guard, the stored-latent step and data parallelism work unchanged; the optimizer is the caller's
+        (tools/distill_dm.py resets its moments at each round, as the paper does).  end_distill() returns to ordinary training.  -> the teacher."""
+        if teacher is None:
+            import copy
+            caches = self.unet._pk, self.unet._bufs         # (the weight pack and the scratch arenas: the copy makes its own)
+            self.unet._pk, self.unet._bufs = None, {}
+            try:
+                teacher = copy.deepcopy(self.unet)
+            finally:
+                self.unet._pk, self.unet._bufs = caches
+        self.diffusion.set_distill(teacher, student_steps, **kw)
+        self.diffusion.sampling_timesteps = student_steps
+        self.diffusion.is_ddim_sampling = student_steps < self.diffusion.num_timesteps
+        self.diffusion.ddim_sampling_eta = 0.0
+        return teacher
+
+    def end_distill(self):
+        self.diffusion.set_distill(None)
+
     def enable_data_parallel(self, bucket_bytes=64 << 20, shard_inputs=True):
         """One process per GPU (torch.distributed initialised by the launcher): average the DM gradients over the
         ranks with a bucketed RCCL all-reduce that overlaps backward.  No-op for world size 1.

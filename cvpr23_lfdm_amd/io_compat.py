@@ -272,3 +272,31 @@ def checkpoint_schedule(ck, flag=None, path="the checkpoint"):
     if flag is not None and stored is not None and flag != stored:
         raise ValueError("--schedule %s contradicts %s, which was trained on schedule %s" % (flag, path, stored))
     return flag if flag is not None else stored if stored is not None else "cosine"
+
+
+def checkpoint_distilled_steps(ck):
+    """The step count a DM checkpoint was distilled to (tools/distill_dm.py): its top-level "distilled_steps", None where
+    there is none (`ck` None too).  Such a model is a DDIM eta-0 model of exactly that many steps on the "trailing" grid."""
+    n = None if ck is None else ck.get("distilled_steps")
+    if n is not None and (isinstance(n, bool) or not isinstance(n, int) or n < 1):
+        raise ValueError("the checkpoint's distilled_steps must be a positive integer, got %r" % (n,))
+    return n
+
+
+def distilled_sampling(ck, steps=None, step_grid=None, sampler=None, path="the checkpoint"):
+    """How to sample a DM checkpoint in view of its "distilled_steps" entry N: -> (steps, step_grid, eta | None, warning | None) from the
+    command line's --steps / --step-grid / --sampler (None: not given).  Without the entry: the flags as they are, eta None (the caller's).
+    With it: steps default to N, the grid to "trailing", eta is 0; a --step-grid other than "trailing" or a --sampler other than
+    "reference" is a ValueError (the student was trained as a DDIM step on that grid); other --steps are allowed with a warning."""
+    n = checkpoint_distilled_steps(ck)
+    if n is None:
+        return steps, step_grid, None, None
+    if step_grid not in (None, "trailing"):
+        raise ValueError("--step-grid %s contradicts %s, which was distilled to %d steps on the trailing grid" % (step_grid, path, n))
+    if sampler not in (None, "reference"):
+        raise ValueError("--sampler %s contradicts %s, which was distilled as a DDIM (--sampler reference, eta 0) model of %d steps"
+                         % (sampler, path, n))
+    warning = None
+    if steps is not None and steps != n:
+        warning = "warning: %s was distilled to %d steps; sampling it with --steps %d" % (path, n, steps)
+    return n if steps is None else steps, "trailing", 0.0, warning

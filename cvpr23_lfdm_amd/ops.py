@@ -1300,6 +1300,66 @@ def objective_loss_bwd(objective, x_start, noise, out, t, a_tab, s_tab, w_tab, i
     return dout
 
 
+# ---------------------------------------------------------------------------------------------
+# progressive distillation: the teacher's step with a row per sample and the student's target (csrc/distill.hip)
+# ---------------------------------------------------------------------------------------------
+
+def _distill_table(what, name, tab, cols, row, batch, like):
+    """A (rows, cols) float32 coefficient table and its (B,) int64 row index, both on the operands' device; -> rows."""
+    if not torch.is_tensor(tab) or tab.dtype != torch.float32 or tab.dim() != 2 or tab.shape[1] != cols or tab.shape[0] < 1 \
+            or not tab.is_contiguous() or tab.device != like.device:
+        raise ValueError("%s: %s must be a contiguous (rows >= 1, %d) float32 table on the operands' device" % (what, name, cols))
+    if not torch.is_tensor(row) or row.dtype != torch.int64 or tuple(row.shape) != (batch,) or not row.is_contiguous() or row.device != like.device:
+        raise ValueError("%s: the row index of %s must be a contiguous (%d,) int64 tensor on the operands' device (it is read there)"
+                         % (what, name, batch))
+    return tab.shape[0]
+
+
+def distill_x0(x, out, coef, row, x0=None):
+    """lfdm_distill_x0_f32: x0[b] = c_x x[b] - c_eps out[b] with (c_x, c_eps) = coef[row[b]][0:2] - the eager fp32 expression's bits; a
+    coefficient that is exactly 0 skips its operand, which may then hold NaN ("pred_x0" rows {0, -1}: the bits of out).  coef: a (rows, 6)
+    step table; row: (B,) int64 on the device (read there, clamped to the table).  The operand of `abs_quantile` under dynamic thresholding."""
+    lib = _lib()
+    x0 = _train_dest("distill_x0", x0, x.shape, x)
+    batch, n = _train_operands("distill_x0", lib, x, dict(x=x, out=out, x0=x0))
+    _chk(lib, coef)
+    rows = _distill_table("distill_x0", "coef", coef, 6, row, batch, x)
+    lib.check(lib.lfdm_distill_x0_f32(_p(x), _p(out), _p(coef), _p(row), rows, _p(x0), batch, n, _stream(lib)), "lfdm_distill_x0_f32")
+    return x0
+
+
+def distill_step(x, out, coef, row, thr=None, x_next=None, *, x_ref=None, tcoef=None, trow=None, x_target=None, eps_target=None):
+    """lfdm_distill_step_f32: one DDIM step (eta = 0) with a coefficient row per sample, {c_x, c_eps, k_x0, k_eps, k_x, -} = coef[row[b]]:
+        x0 = c_x x - c_eps out;  s = 1 (thr None: the static clamp) or max(thr[b], 1);  m = clamp(x0, -s, s) / s
+        v = k_x0 m [+ k_eps out] [+ k_x x]  -> x_next (made here when None; may be x itself)
+    thr: (B,) float32, `abs_quantile` of `distill_x0`.  Target mode - x_ref, tcoef ((rows, 4) {q0, q1, q2, q3}), trow ((B,) int64) together,
+    x_target / eps_target made here when None: xt = q0 v + q1 x_ref, et = q2 x_ref + q3 xt; x_next may then stay None and v is not stored.
+    -> x_next, or (x_next | None, x_target, eps_target) in target mode."""
+    lib = _lib()
+    what = "distill_step"
+    given = [v is not None for v in (x_ref, tcoef, trow)]
+    if any(given) != all(given) or (not any(given) and (x_target is not None or eps_target is not None)):
+        raise ValueError("%s: x_ref, tcoef and trow go together, and x_target / eps_target only with them" % what)
+    target = all(given)
+    floats = dict(x=x, out=out)
+    if not target or x_next is not None:
+        x_next = floats["x_next"] = _train_dest(what, x_next, x.shape, x)
+    if target:
+        x_target = _train_dest(what, x_target, x.shape, x)
+        eps_target = _train_dest(what, eps_target, x.shape, x)
+        floats.update(x_ref=x_ref, x_target=x_target, eps_target=eps_target)
+    batch, n = _train_operands(what, lib, x, floats)
+    _chk(lib, coef, tcoef, thr)
+    rows = _distill_table(what, "coef", coef, 6, row, batch, x)
+    trows = _distill_table(what, "tcoef", tcoef, 4, trow, batch, x) if target else 0
+    if thr is not None and (not torch.is_tensor(thr) or thr.dtype != torch.float32 or tuple(thr.shape) != (batch,) or not thr.is_contiguous()
+                            or thr.device != x.device):
+        raise ValueError("%s: thr must be a contiguous (%d,) float32 tensor on the operands' device" % (what, batch))
+    lib.check(lib.lfdm_distill_step_f32(_p(x), _p(out), _p(coef), _p(row), rows, _p(thr), _p(x_next), _p(x_ref), _p(tcoef), _p(trow), trows,
+                                        _p(x_target), _p(eps_target), batch, n, _stream(lib)), "lfdm_distill_step_f32")
+    return (x_next, x_target, eps_target) if target else x_next
+
+
 def cfg_combine(cond_eps, null_eps, scale, out):
     lib = _lib()
     _chk(lib, cond_eps, null_eps, out)

@@ -216,6 +216,22 @@ class FlatAdam(torch.optim.Optimizer):
             return None
         return float(self._plan().view(torch.float32)[3].item())
 
+    @torch.no_grad()
+    def reset_moments(self):
+        """Adam starts again on the current parameters (a new round of progressive distillation): both moments and the step count back
+        to zero, the average - where one is kept - restarted from the parameters.  Learning rate, options and skipped_steps() stay."""
+        if self._ema_live:
+            raise RuntimeError("FlatAdam.reset_moments inside ema_weights(): the parameters are the averaged ones")
+        for fl in self.ensure_flat():
+            fl["m"].zero_()
+            fl["v"].zero_()
+            for p in fl["params"]:
+                self.state[p]["step"] = torch.tensor(0.0)
+            if "ema" in fl:
+                fl["ema"].copy_(fl["p"])
+            if "plan" in fl:
+                fl["plan"].view(torch.int64)[4] = 0          # lfdm_optim_plan.applied_steps
+
     def state_dict(self):
         if self.guarded and self._flat is not None:      # the device counter is the authoritative one: the only read-back is here
             step = float(self.applied_steps())

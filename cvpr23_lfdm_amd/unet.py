@@ -155,11 +155,13 @@ class Unet3D(ParamTree):
     def _signature(self):
         """Identity of the weights the pack was built from.  `_version` sees every torch-side write (copy_, optimizer
         foreach ops, load_state_dict); writes through raw pointers (FlatAdam's fused HIP step) are invisible to it, so
-        they bump `params.weights_epoch()` instead."""
-        sig = 0
+        they bump `params.weights_epoch()` instead.  A denoiser none of whose parameters requires a gradient is in no optimizer (the tag
+        of autograd._pack_wino): the frozen teacher of a distillation round keeps its pack while the student's optimizer steps."""
+        sig, trained = 0, False
         for p in self.parameters():
             sig += p._version
-        return (sig, weights_epoch(), next(self.parameters()).device)
+            trained = trained or p.requires_grad
+        return (sig, weights_epoch() if trained else -1, next(self.parameters()).device)
 
     def _buf(self, name, rows, ch, dtype=torch.float32):
         need = rows * ch

@@ -992,6 +992,30 @@ int lfdm_objective_loss_bwd_f32(int objective, const float* x_start, const float
                                 const unsigned char* elem_mask, int frames, int64_t frame_elems, int loss_type, const float* inv_count,
                                 const float* gout, float* dout, int batch, int64_t n, lfdm_stream_t stream);
 
+/* Progressive distillation (Salimans & Ho 2022; additive, ABI version unchanged; DESIGN.md 4.16, csrc/distill.hip): the frozen teacher's
+ * DDIM step with a coefficient row PER SAMPLE, and the target one student step has to reach.  Samples are dense rows of n floats (n % 4 == 0,
+ * 0 < n < 2^24, batch <= 65 535); coef: (rows, 6) floats {c_x, c_eps, k_x0, k_eps, k_x, -} - a step table of the sampler, column 5 (the
+ * noise scale) is never read: eta = 0; row: (B) int64 ON THE DEVICE, clamped to [0, rows) by the kernels.  Every product and sum is rounded
+ * on its own; a coefficient that is exactly 0 skips its product, and an operand all of whose coefficients are 0 is never loaded (it may
+ * hold NaN, but must be a valid pointer).  No atomics, no workspace, one owner per output element: two runs give the same bits.
+ *   x0:    x0 = c_x x - c_eps out  (the bits of the eager fp32 expression; rows {0, -1}: the bits of out) - the operand of
+ *          lfdm_abs_quantile_f32 when the model thresholds dynamically
+ *   step:  x0 as above (recomputed);  s = thr ? max(thr[b], 1) : 1  (thr: (B) floats, NULL = the static clamp to [-1, 1]);
+ *          m = min(max(x0, -s), s) / s;  v = k_x0 m [+ k_eps out] [+ k_x x] -> x_next (may be x itself; NULL in target mode: v is not stored)
+ *          target mode (x_ref, tcoef, trow, x_target, eps_target: all or none; tcoef: (trows, 4) floats {q0, q1, q2, q3}, trow: (B) int64 on
+ *          the device, clamped to [0, trows)):  xt = q0 v + q1 x_ref -> x_target;  et = q2 x_ref + q3 xt -> eps_target
+ * Refusals (LFDM_EINVAL, nothing is enqueued): a null or misaligned operand, bad batch / n / rows, a partial set of target operands, trows
+ * that does not go with them, no output at all, x_ref aliasing an output, two outputs aliasing each other, an output other than x_next = x
+ * aliasing an input. */
+/* Layout: x, out, x0 dense (B, n), 16 B; coef dense (rows, 6); row dense (B) int64.  x0 must not alias out. */
+int lfdm_distill_x0_f32(const float* x, const float* out, const float* coef, const int64_t* row, int rows, float* x0, int batch, int64_t n,
+                        lfdm_stream_t stream);
+/* Layout: x, out, x_next, x_ref, x_target, eps_target dense (B, n), 16 B; coef dense (rows, 6), tcoef dense (trows, 4); row, trow dense (B)
+ * int64; thr dense (B).  x_next may be x; no other output aliases an operand or another output. */
+int lfdm_distill_step_f32(const float* x, const float* out, const float* coef, const int64_t* row, int rows, const float* thr, float* x_next,
+                          const float* x_ref, const float* tcoef, const int64_t* trow, int trows, float* x_target, float* eps_target,
+                          int batch, int64_t n, lfdm_stream_t stream);
+
 /* im2col of channels-last rows with few channels (channels % 4 == 0, <= 16; stride 1, zero padding): out (n_img*hq*wq, k*k*channels),
  * column tap * channels + ch.  Lets the weight gradient of the generator's 7x7 RGB convolutions (LFAE/modules/generator.py:37,56: 3 -> 64
  * and 64 -> 3 channels) run as ONE 1x1 weight-gradient GEMM instead of 49 per-tap GEMMs that pad 4 channels to a 64-wide tile. */

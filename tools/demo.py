@@ -29,6 +29,15 @@ sys.path.insert(0, ROOT)
 from cvpr23_lfdm_amd import FlowDiffusion, io_compat as C  # noqa: E402
 
 
+class Explicit(argparse.Action):
+    """store, and note in `namespace.explicit` that the option was given: a distilled checkpoint (tools/distill_dm.py) replaces the
+    DEFAULTS of --steps / --step-grid / --sampler and is contradicted only by what the command line really asked for."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values)
+        namespace.__dict__.setdefault("explicit", set()).add(self.dest)
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", default=os.path.join(ROOT, "configs", "lfae_128.yaml"))
@@ -39,15 +48,17 @@ def build_parser():
     ap.add_argument("--text", nargs="+", default=["happiness"])
     ap.add_argument("--frames", type=int, default=40)
     ap.add_argument("--size", type=int, default=128)
-    ap.add_argument("--steps", type=int, default=100, help="sampler steps (sampling_timesteps): DDIM, or --sampler's")
+    ap.add_argument("--steps", type=int, default=100, action=Explicit, help="sampler steps (sampling_timesteps): DDIM, or --sampler's; default 100 - for a "
+                    "checkpoint of tools/distill_dm.py the step count it was distilled to (another value is allowed, with a warning)")
     ap.add_argument("--cond-scale", type=float, default=1.0)
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--out", default="demo_out")
     ap.add_argument("--conv-precision", choices=("fp32", "bf16"), default="fp32",
                     help="operands of the UNet's Winograd 3x3 convolutions: bf16 is the faster, lower-precision sampling mode (DESIGN.md)")
-    ap.add_argument("--sampler", choices=("reference", "dpmpp_1", "dpmpp_2m"), default="reference",
-                    help="reference: DDIM / DDPM as the reference samples; dpmpp_2m: DPM-Solver++(2M), second order, for few --steps (DESIGN.md 4.2)")
+    ap.add_argument("--sampler", choices=("reference", "dpmpp_1", "dpmpp_2m"), default="reference", action=Explicit,
+                    help="reference (default): DDIM / DDPM as the reference samples; dpmpp_2m: DPM-Solver++(2M), second order, for few --steps "
+                         "(DESIGN.md 4.2); a distilled checkpoint is a DDIM model: anything but reference is an error")
     ap.add_argument("--total-frames", type=int, default=0,
                     help="a video of this many frames, longer than --frames, as a chain of overlapping windows conditioned on known frames "
                          "(FlowDiffusion.sample_long_video, DESIGN.md 4.3); 0 (default): off, one window of --frames")
@@ -62,9 +73,10 @@ def build_parser():
     ap.add_argument("--schedule", choices=("cosine", "cosine_zsnr"), default=None,
                     help="the noise schedule the checkpoint was trained on (tools/train_dm.py --schedule, DESIGN.md 4.15); default: the "
                          "checkpoint's own entry (cosine where it has none) - a value that contradicts the checkpoint is an error")
-    ap.add_argument("--step-grid", choices=("reference", "trailing"), default="reference",
+    ap.add_argument("--step-grid", choices=("reference", "trailing"), default="reference", action=Explicit,
                     help="the DDIM / --sampler time grid: the reference's (default), or trailing - it starts at the last timestep and ends on "
-                         "the clean latent (Lin et al. 2024, DESIGN.md 4.15)")
+                         "the clean latent (Lin et al. 2024, DESIGN.md 4.15); a distilled checkpoint defaults to trailing, at eta 0, and "
+                         "reference is then an error (DESIGN.md 4.16)")
     ap.add_argument("--guidance-rescale", type=float, default=0.0,
                     help="phi in [0, 1]: with --cond-scale other than 0 and 1, scale the guided output towards the conditional output's "
                          "standard deviation (Lin et al. 2024, DESIGN.md 4.15); 0 (default): off")
@@ -215,28 +227,40 @@ def dm_state(ck, use_ema, path="the checkpoint"):
     return ck["diffusion_ema"]
 
 
-def make_model(args, *, steps=None, sampler=None, conv_precision=None, use_ema=None, need_dm=True):
+def make_model(args, *, steps=None, sampler=None, conv_precision=None, use_ema=None, need_dm=True, explicit=None):
     """The FlowDiffusion of the parsed options with its weights loaded, on the host (demo_mug.py:80-97); tools/eval.py builds its models
     here too.  steps / sampler / conv_precision / use_ema override the options of the same names; need_dm=False accepts a run without
-    --dm-ckpt (an LFAE-only evaluation)."""
+    --dm-ckpt (an LFAE-only evaluation).  explicit: which of "steps" / "sampler" / "step_grid" were asked for rather than defaulted
+    (default: what the command line gave, `Explicit`, and the overrides) - a distilled checkpoint's own entry stands in for the others."""
+    if explicit is None:
+        explicit = set(getattr(args, "explicit", ())) | {k for k, v in (("steps", steps), ("sampler", sampler)) if v is not None}
     steps = args.steps if steps is None else steps
     sampler = args.sampler if sampler is None else sampler
+    step_grid = getattr(args, "step_grid", "reference")
     conv_precision = args.conv_precision if conv_precision is None else conv_precision
     use_ema = args.use_ema if use_ema is None else use_ema
     ck = torch.load(args.dm_ckpt, map_location="cpu") if args.dm_ckpt and not args.synthetic else None
     try:
         objective = C.checkpoint_objective(ck, getattr(args, "objective", None), args.dm_ckpt)
         schedule = C.checkpoint_schedule(ck, getattr(args, "schedule", None), args.dm_ckpt)
+        # a checkpoint of tools/distill_dm.py says how it is sampled: its step count, the trailing grid, eta 0 (DESIGN.md 4.16)
+        given = lambda name, value: value if name in explicit else None
+        distilled = C.distilled_sampling(ck, given("steps", steps), given("step_grid", step_grid), given("sampler", sampler), args.dm_ckpt)
     except ValueError as e:
         sys.exit(str(e))
+    eta = distilled[2]
+    if eta is not None:
+        steps, step_grid, sampler = distilled[0], distilled[1], "reference"
+        if distilled[3]:
+            print(distilled[3])
     try:
         model = FlowDiffusion(is_train=False, img_size=args.size // 4, num_frames=args.frames, sampling_timesteps=steps,
                               null_cond_prob=0.1, config_pth=args.config, pretrained_pth=args.lfae_ckpt,
                               bert_path=None if args.synthetic else args.bert, conv_precision=conv_precision,
                               sampler=sampler, long_attention=getattr(args, "long_attention", False),
                               noise=getattr(args, "noise", "torch"), objective=objective, schedule=schedule,
-                              step_grid=getattr(args, "step_grid", "reference"),
-                              guidance_rescale=getattr(args, "guidance_rescale", 0.0))                         # demo_mug.py:80-88
+                              step_grid=step_grid, guidance_rescale=getattr(args, "guidance_rescale", 0.0),
+                              **({} if eta is None else dict(ddim_sampling_eta=eta)))                         # demo_mug.py:80-88
     except ValueError as e:             # (cosine_zsnr with pred_noise, a --guidance-rescale outside [0, 1])
         sys.exit(str(e))
     if args.synthetic:

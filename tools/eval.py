@@ -55,15 +55,17 @@ def build_parser():
         p.add_argument("--size", type=int, default=128)
         p.add_argument("--frames", type=int, default=40)
         p.add_argument("--synthetic", action="store_true", help="random-init weights and synthetic videos: exercises the path without checkpoints")
-        p.add_argument("--sampler", choices=("reference", "dpmpp_1", "dpmpp_2m"), default="reference")
-        p.add_argument("--steps", type=int, default=100)
+        p.add_argument("--sampler", choices=("reference", "dpmpp_1", "dpmpp_2m"), default="reference", action=_demo().Explicit,
+                       help="default reference; a distilled checkpoint (tools/distill_dm.py) is a DDIM model: anything else is an error")
+        p.add_argument("--steps", type=int, default=100, action=_demo().Explicit, help="default 100; for a distilled checkpoint the step count it was distilled to")
         p.add_argument("--conv-precision", choices=("fp32", "bf16"), default="fp32")
         p.add_argument("--objective", choices=("pred_noise", "pred_x0", "pred_v"), default=None,
                        help="what the denoiser predicts (DESIGN.md 4.14); default: the checkpoint's own entry - a contradiction is an error")
         p.add_argument("--schedule", choices=("cosine", "cosine_zsnr"), default=None,
                        help="the noise schedule the checkpoint was trained on (DESIGN.md 4.15); default: the checkpoint's own entry - a contradiction is an error")
-        p.add_argument("--step-grid", choices=("reference", "trailing"), default="reference",
-                       help="the sampler's time grid: the reference's, or trailing - from the last timestep to the clean latent (DESIGN.md 4.15)")
+        p.add_argument("--step-grid", choices=("reference", "trailing"), default="reference", action=_demo().Explicit,
+                       help="the sampler's time grid: the reference's (default), or trailing - from the last timestep to the clean latent "
+                            "(DESIGN.md 4.15); a distilled checkpoint defaults to trailing at eta 0 and refuses reference (DESIGN.md 4.16)")
         p.add_argument("--guidance-rescale", type=float, default=0.0,
                        help="phi in [0, 1]: rescale the guided output (--cond-scale other than 0 and 1) towards the conditional output's standard deviation (DESIGN.md 4.15)")
         p.add_argument("--use-ema", action="store_true", help="sample from the checkpoint's 'diffusion_ema' entry")
@@ -137,11 +139,13 @@ def build_model(args, overrides=None):
     cfg.update(overrides or {})
     if cfg["use_ema"] and (args.synthetic or not args.dm_ckpt):
         sys.exit("use_ema needs --dm-ckpt: a checkpoint with a 'diffusion_ema' entry")
-    model = _demo().make_model(args, need_dm=args.command not in ("lfae", "interp"), **cfg)
+    explicit = set(getattr(args, "explicit", ())) | set(overrides or {})       # (asked for on the command line or by an --a / --b list)
+    model = _demo().make_model(args, need_dm=args.command not in ("lfae", "interp"), explicit=explicit, **cfg)
     if args.synthetic:          # the frozen-LFAE pass also runs the two predictors, which the demo never does
         import synth
         model.region_predictor.load_state_dict(synth.region_state())
         model.bg_predictor.load_state_dict(synth.bg_state())
+    cfg.update(sampler=model.diffusion.sampler, steps=model.diffusion.sampling_timesteps)       # (as resolved: the defaults, a distilled checkpoint's own)
     return model.to(device()).eval(), cfg
 
 

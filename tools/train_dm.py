@@ -32,8 +32,9 @@ from cvpr23_lfdm_amd import FlowDiffusion, io_compat as C  # noqa: E402
 from cvpr23_lfdm_amd.data import FrameFolderVideos, SyntheticVideos  # noqa: E402
 
 
-def parse_args(argv=None):
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+def build_parser(description=__doc__):
+    """The trainer's options (tools/distill_dm.py adds its own to the same parser)."""
+    ap = argparse.ArgumentParser(description=description, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--data", default="")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--config", default=os.path.join(ROOT, "configs", "lfae_128.yaml"))
@@ -89,7 +90,11 @@ def parse_args(argv=None):
     ap.add_argument("--log-loss-quartiles", action="store_true",
                     help="at --print-freq also print the mean unweighted per-sample loss by quartile of the timestep (accumulated on the "
                          "device, read back only when printed); needs --objective other than pred_noise or --min-snr-gamma")
-    return ap.parse_args(argv)
+    return ap
+
+
+def parse_args(argv=None):
+    return build_parser().parse_args(argv)
 
 
 class LossQuartiles:
@@ -147,6 +152,57 @@ def _emulated():
     return _native._active is not None and _native._active.kind == "emu"
 
 
+def build_model(args, cuda=True, **extra):
+    """The training model of the options (`extra`: further FlowDiffusion keywords), on the GPU; --synthetic: a text encoder of random
+    embeddings and the random-init LFAE frozen."""
+    if args.schedule == "cosine_zsnr" and args.objective == "pred_noise":
+        sys.exit("--schedule cosine_zsnr needs --objective pred_v or pred_x0: the noise prediction carries no information at SNR 0")
+    model = FlowDiffusion(lr=args.lr, is_train=True, img_size=args.size // 4, num_frames=args.frames,
+                          null_cond_prob=args.null_cond_prob, sampling_timesteps=args.preview_steps or 1000, config_pth=args.config,
+                          pretrained_pth=args.lfae_ckpt, bert_path=None if args.synthetic else args.bert,     # :153-162
+                          ema_decay=args.ema_decay, ema_start_step=args.ema_start_step, max_grad_norm=args.max_grad_norm,
+                          skip_nonfinite=args.skip_nonfinite, long_attention=args.long_attention, known_train=known_train(args),
+                          dim_mults=tuple(args.dim_mults), objective=args.objective, min_snr_gamma=args.min_snr_gamma,
+                          schedule=args.schedule, **extra)
+    if cuda:
+        model.cuda()
+    if args.synthetic:
+        emb = {}
+        model.diffusion.text_encoder = lambda texts: torch.stack(
+            [emb.setdefault(t, torch.randn(768, generator=torch.Generator().manual_seed(len(emb) + 1))) for t in texts])
+        for net in (model.generator, model.region_predictor, model.bg_predictor):
+            net.eval()
+            model.set_requires_grad(net, False)
+    return model
+
+
+def feed(model, args, prep, batch):
+    """One loader batch as the model's training input; -> (ref_imgs, real_vids | None under --latents, ref_texts, real_names)."""
+    if args.latents:                 # the stored latent and the reference frame: no video, no LFAE pass (DESIGN.md 4.13)
+        (latents, ref_imgs), ref_texts, real_names, real_vids = prep(batch), batch[5], batch[6], None
+        model.set_train_latent(ref_img=ref_imgs, latent=latents, ref_text=list(ref_texts))
+    else:
+        if prep is None:
+            real_vids, ref_texts, real_names = batch
+            real_vids = real_vids.cuda(non_blocking=True)
+        else:
+            real_vids, ref_texts, real_names = prep(batch), batch[3], batch[4]
+        ref_imgs = real_vids[:, :, 0].clone().detach()                    # first frame = reference frame (:221)
+        model.set_train_input(ref_img=ref_imgs, real_vid=real_vids, ref_text=list(ref_texts))
+    return ref_imgs, real_vids, ref_texts, real_names
+
+
+def checkpoint(model, args, step, world, **extra):
+    """The checkpoint of a step: the reference's three entries, what the model was trained as, the averaged weights where there are any."""
+    ck = {"example": step * args.batch_size * world, "diffusion": model.diffusion.state_dict(),
+          "optimizer_diff": model.optimizer_diff.state_dict(), "objective": args.objective, "min_snr_gamma": args.min_snr_gamma,
+          "schedule": args.schedule}
+    ck.update(extra)
+    if args.ema_decay is not None:          # the averaged weights, shaped like "diffusion" (tools/demo.py --use-ema)
+        ck["diffusion_ema"] = model.ema_state_dict()
+    return ck
+
+
 def main(argv=None):
     args = parse_args(argv)
     cuda = not _emulated()
@@ -166,30 +222,13 @@ def main(argv=None):
     np.random.seed(args.seed)
     os.makedirs(args.out, exist_ok=True)
 
-    if args.schedule == "cosine_zsnr" and args.objective == "pred_noise":
-        sys.exit("--schedule cosine_zsnr needs --objective pred_v or pred_x0: the noise prediction carries no information at SNR 0")
-    model = FlowDiffusion(lr=args.lr, is_train=True, img_size=args.size // 4, num_frames=args.frames,
-                          null_cond_prob=args.null_cond_prob, sampling_timesteps=args.preview_steps or 1000, config_pth=args.config,
-                          pretrained_pth=args.lfae_ckpt, bert_path=None if args.synthetic else args.bert,     # :153-162
-                          ema_decay=args.ema_decay, ema_start_step=args.ema_start_step, max_grad_norm=args.max_grad_norm,
-                          skip_nonfinite=args.skip_nonfinite, long_attention=args.long_attention, known_train=known_train(args),
-                          dim_mults=tuple(args.dim_mults), objective=args.objective, min_snr_gamma=args.min_snr_gamma,
-                          schedule=args.schedule)
+    model = build_model(args, cuda)
     quartiles = None
     if args.log_loss_quartiles:
         if args.objective == "pred_noise" and args.min_snr_gamma is None:
             sys.exit("--log-loss-quartiles reads the per-sample losses of the objective loss kernel: give --objective or --min-snr-gamma")
         quartiles = LossQuartiles(model.diffusion.num_timesteps)
     opt = model.optimizer_diff
-    if cuda:
-        model.cuda()
-    if args.synthetic:
-        emb = {}
-        model.diffusion.text_encoder = lambda texts: torch.stack(
-            [emb.setdefault(t, torch.randn(768, generator=torch.Generator().manual_seed(len(emb) + 1))) for t in texts])
-        for net in (model.generator, model.region_predictor, model.bg_predictor):
-            net.eval()
-            model.set_requires_grad(net, False)
     start_step = 0
     if args.restore_from:                                                                                     # :169-184
         ck = torch.load(args.restore_from, map_location="cpu")
@@ -223,17 +262,7 @@ def main(argv=None):
         if sampler is not None:
             sampler.set_epoch(epoch)
         for batch in loader:
-            if args.latents:                 # the stored latent and the reference frame: no video, no LFAE pass
-                (latents, ref_imgs), ref_texts, real_names, real_vids = prep(batch), batch[5], batch[6], None
-                model.set_train_latent(ref_img=ref_imgs, latent=latents, ref_text=list(ref_texts))
-            else:
-                if prep is None:
-                    real_vids, ref_texts, real_names = batch
-                    real_vids = real_vids.cuda(non_blocking=True)
-                else:
-                    real_vids, ref_texts, real_names = prep(batch), batch[3], batch[4]
-                ref_imgs = real_vids[:, :, 0].clone().detach()                    # first frame = reference frame (:221)
-                model.set_train_input(ref_img=ref_imgs, real_vid=real_vids, ref_text=list(ref_texts))
+            ref_imgs, real_vids, ref_texts, real_names = feed(model, args, prep, batch)
             model.optimize_parameters()
             step += 1
             if quartiles is not None:
@@ -278,12 +307,7 @@ def main(argv=None):
                                                                                 "_ema" if args.ema_decay is not None else "")),
                               C.video_strip(model, ref_imgs[:1]))
             if rank == 0 and (step % args.save_freq == 0 or step >= args.final_step):                         # :330-340
-                ck = {"example": step * args.batch_size * world, "diffusion": model.diffusion.state_dict(),
-                      "optimizer_diff": opt.state_dict(), "objective": args.objective, "min_snr_gamma": args.min_snr_gamma,
-                      "schedule": args.schedule}
-                if args.ema_decay is not None:          # the averaged weights, shaped like "diffusion" (tools/demo.py --use-ema)
-                    ck["diffusion_ema"] = model.ema_state_dict()
-                torch.save(ck,
+                torch.save(checkpoint(model, args, step, world),
                            os.path.join(args.out, "flowdiff_%04d_S%06d.pth" % (args.batch_size, step)))
             if step >= args.final_step:
                 break
