@@ -257,6 +257,9 @@ _SIGNATURES = {
     "lfdm_latent_resample_f32": (i32, [f32p, C.c_void_p, f32p, f32p, f32p, f32p, f32p, i32, i32, i32, i32, i32, i32, i32, i32, stream_t]),
     # ---- training latents gathered from a flow-latent store (additive, ABI stays 13)
     "lfdm_latent_gather_f32": (i32, [C.c_void_p, i32, i64, C.c_void_p, f32p, f32p, f32p, i32, i32, i32, i32, stream_t]),
+    # ---- joint sampling through overlapping windows: gather and fold (additive, ABI stays 13)
+    "lfdm_window_gather_f32": (i32, [f32p, C.c_void_p, C.c_void_p, f32p, i32, i32, i32, i32, i32, i64, stream_t]),
+    "lfdm_window_fold_f32": (i32, [f32p, C.c_void_p, C.c_void_p, C.c_void_p, f32p, C.c_void_p, f32p, i32, i32, i32, i32, i32, i64, stream_t]),
     "lfdm_depthwise_down_planar_f32": (i32, [f32p, f32p, f32p, i32, i32, i32, i32, i32, i32, i32, i32, stream_t]),
     "lfdm_upsample2_pad_cl_f32": (i32, [f32p, f32p, i32, i32, i32, i32, i32, i32, i32, stream_t]),
     "lfdm_layernorm_bwd_ws_bytes": (sz, [i64, i32]),

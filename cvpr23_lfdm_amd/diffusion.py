@@ -137,6 +137,16 @@ class SampleMode(NamedTuple):
     def rescale(self):
         return 0.0
 
+    @property
+    def joint(self):
+        """None, or the `JointGeometry` of a joint long video (no field: `JointMode` carries it)."""
+        return None
+
+    @property
+    def latent_frames(self):
+        """The frames of the latent the update runs on: `frames`, except under a joint mode (the global time line)."""
+        return self.frames
+
     def with_rescale(self, phi):
         """This mode with guidance_rescale phi: itself (as a plain SampleMode) for 0.0 - and whenever the step runs one pass, where the
         rescale is the identity and nothing new is launched - else the `RescaledMode` of the same fields."""
@@ -176,11 +186,91 @@ class RescaledMode(SampleMode):
         return SampleMode(*self)._replace(**kw).with_rescale(rescale)
 
 
+class JointGeometry(NamedTuple):
+    """The geometry of a joint long video: the frames of the global latent, the window starts, the blend profile."""
+    total_frames: int
+    starts: tuple
+    blend: str
+
+
+class JointMode(SampleMode):
+    """The SampleMode of a joint long video: `frames` is the WINDOW the UNet sees, `joint` the geometry (total_frames, starts, blend) of the
+    global latent the update runs on, `rescale` as RescaledMode's.  Neither is a field - the positional layout stays - but both are part of
+    the key: a JointMode never equals a plain or rescaled mode, nor one of another geometry."""
+
+    def __new__(cls, mode, joint, rescale=0.0):
+        self = super().__new__(cls, *mode)
+        self._joint, self._rescale = joint, float(rescale) if mode.passes > 1 else 0.0
+        return self
+
+    @property
+    def rescale(self):
+        return self._rescale
+
+    @property
+    def joint(self):
+        return self._joint
+
+    @property
+    def latent_frames(self):
+        return self._joint.total_frames
+
+    def __eq__(self, other):
+        return isinstance(other, JointMode) and tuple.__eq__(self, other) and (self._joint, self._rescale) == (other._joint, other._rescale)
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __hash__(self):
+        return hash((tuple(self), self._joint, self._rescale))
+
+    def __repr__(self):
+        return "%s, joint=%r, rescale=%r)" % (SampleMode.__repr__(SampleMode(*self))[:-1].replace("SampleMode(", "JointMode(", 1),
+                                              self._joint, self._rescale)
+
+    def _replace(self, **kw):
+        joint, rescale = kw.pop("joint", self._joint), kw.pop("rescale", self._rescale)
+        return JointMode(SampleMode(*self)._replace(**kw), joint, rescale)
+
+    def with_rescale(self, phi):
+        return JointMode(SampleMode(*self), self._joint, phi)
+
+
+def joint_denoise(unet, plan, mode):
+    """The denoiser of a joint step: the W windows of the global latent, cut by one gather launch, go through the UNet as
+    ONE batch of B W rows (2 B W for two passes, rows [cond | null]) in b W + w order; the window outputs are folded onto the global time
+    line into plan["eps"] by one launch."""
+    pk, step = plan["pk"], plan["step"]
+    frames, s = mode.frames, mode.size
+    rows = mode.batch * len(mode.joint.starts)
+    xw, epsw = plan["xw"], plan["epsw"]
+    ops.window_gather(plan["x"], plan["starts"], frames, out=xw[:rows])
+    if mode.passes == 1:
+        ops.step_cond(plan["step_part"], plan["parts"][0], step, plan["ss"])
+        r = unet.stem(pk, xw, plan["fea_term"], rows, frames, s)
+        unet.run_trunk(pk, r, plan["ss"], rows, frames, s, epsw)
+    else:
+        eps2, ss2 = plan["eps2"], plan["ss2"]
+        xw[rows:].copy_(xw[:rows])
+        for i, part in enumerate(plan["parts"]):
+            ops.step_cond(plan["step_part"], part, step, ss2[i * rows:(i + 1) * rows])
+        r = unet.stem(pk, xw, plan["fea_term"], 2 * rows, frames, s)
+        unet.run_trunk(pk, r, ss2, 2 * rows, frames, s, eps2)
+        if mode.rescale > 0.0:      # (per window row: the standard deviations run over one window of one video)
+            ops.cfg_combine_rescale(eps2[:rows], eps2[rows:], mode.cond_scale, mode.rescale, epsw, ws=plan["rescale_ws"])
+        else:
+            ops.cfg_combine(eps2[:rows], eps2[rows:], mode.cond_scale, epsw)
+    ops.window_fold(epsw, plan["table"], plan["eps"])
+
+
 def sampler_step(unet, plan, mode):
     """One sampler step on the plan's operands: [per-step cond select] -> UNet -> fused x0 / quantile / update.  This is what is captured."""
     pk, x, eps, step = plan["pk"], plan["x"], plan["eps"], plan["step"]
     b, frames, s = mode.batch, mode.frames, mode.size
-    if mode.passes == 1:
+    if mode.joint is not None:      # windows -> UNet at batch B W -> fold; the update below runs on the global latent
+        joint_denoise(unet, plan, mode)
+        frames = mode.latent_frames
+    elif mode.passes == 1:
         ops.step_cond(plan["step_part"], plan["parts"][0], step, plan["ss"])
         r = unet.stem(pk, x, plan["fea_term"], b, frames, s)
         unet.run_trunk(pk, r, plan["ss"], b, frames, s, eps)
@@ -909,7 +999,7 @@ class GaussianDiffusion(nn.Module):
     # ------------------------------------------------------------------ sampling
     @torch.no_grad()
     def sample(self, fea, cond=None, cond_scale=1., batch_size=16, *, known=None, known_mask=None, seeds=None, window=0, start=None,
-               start_step=0, known_level="noised"):
+               start_step=0, known_level="noised", total_frames=None, overlap=None, blend="ramp", window_cond=None):
         """Reference :762-775.  fea: planar (B, 256, S, S); cond: (B, 768) tensor or list[str].  Runs `self.sampler`.
         known (B, C, T, S, S) float32 + known_mask (B, T) bool (keyword only, both or none): condition on known frames by the replacement
         method - frame t of sample b is kept on the trajectory of known[b, :, t] and returned bit for bit where the mask is
@@ -921,19 +1011,72 @@ class GaussianDiffusion(nn.Module):
         x = a_k start + s_k z (z: the x_T draw, (a_k, s_k): row k of the level table) and steps k .. steps - 1 run - an edit of an existing
         video, the closer to it the later it starts.  Known content is then placed on row k.
         known_level="clean" (keyword only; default "noised"): the known content is held CLEAN at every step instead of on the step's level -
-        what a denoiser trained with known_train has seen; nothing is drawn for it."""
-        batch = batch_size if cond is None else len(cond)
-        shape = (batch, self.channels, self.num_frames, self.image_size, self.image_size)
-        return self.sample_checked(fea, cond, cond_scale, self.check_request(shape, known, known_mask, seeds, window, start, start_step,
-                                                                             known_level=known_level))
+        what a denoiser trained with known_train has seen; nothing is drawn for it.
+        total_frames + overlap (keyword only, both or none; default off) with blend ("ramp" | "uniform") and window_cond: a JOINT long video
+         - one latent of max(total_frames, num_frames) frames; at every step its overlapping windows of num_frames frames
+        (`ops.joint_windows`) go through the denoiser as one batch, their outputs are averaged onto the global time line with the blend's
+        weights and the update runs once on the global latent.  known / known_mask then have the GLOBAL shape, seeds are one per video
+        (counter word window = 0, the global element index).  window_cond: a sequence of W conditions, each what `cond` is (len B), window
+        w's rows use entry w - in place of cond.  start / start_step and window are refused with it."""
+        if total_frames is None:
+            if overlap is not None or window_cond is not None or blend != "ramp":
+                raise ValueError("sample: overlap, blend and window_cond belong to a joint video: they need total_frames")
+            batch = batch_size if cond is None else len(cond)
+            shape = (batch, self.channels, self.num_frames, self.image_size, self.image_size)
+            return self.sample_checked(fea, cond, cond_scale, self.check_request(shape, known, known_mask, seeds, window, start, start_step,
+                                                                                 known_level=known_level))
+        if window_cond is not None:
+            if cond is not None:
+                raise ValueError("sample: window_cond stands in place of cond (one condition per window), give one of them")
+            batch = len(window_cond[0]) if len(window_cond) else 0
+        else:
+            batch = batch_size if cond is None else len(cond)
+        req, joint = self.check_joint_request(batch, total_frames, overlap, blend, known, known_mask, seeds, window, start, start_step,
+                                              known_level=known_level, window_cond=window_cond)
+        return self.sample_checked(fea, cond, cond_scale, req, joint=joint, window_cond=window_cond)
+
+    def joint_geometry(self, total_frames, overlap, blend="ramp"):
+        """The `JointGeometry` of a joint video of this model's window: `ops.joint_windows`' starts and refusals (overlap, 8 contributors, the
+        sampler step's 2^24 elements) on max(total_frames, num_frames) global frames."""
+        starts, _ = ops.joint_windows(total_frames, self.num_frames, overlap, blend, channels=self.channels, size=self.image_size)
+        return JointGeometry(max(int(total_frames), self.num_frames), tuple(int(v) for v in starts), blend)
+
+    def check_joint_request(self, batch, total_frames, overlap, blend="ramp", known=None, known_mask=None, seeds=None, window=0, start=None,
+                            start_step=0, known_level="noised", window_cond=None):
+        """`check_request` of a joint long video: -> (Request of the GLOBAL shape, JointGeometry); ValueError before anything is launched."""
+        if start is not None or start_step != 0:
+            raise ValueError("sample: start / start_step with a joint video (total_frames) is not built - enter the schedule on a latent "
+                             "with a single window")
+        if window != 0:
+            raise ValueError("sample: a joint video draws with counter word window = 0, got window = %r" % (window,))
+        if overlap is None:
+            raise ValueError("sample: a joint video (total_frames) needs overlap")
+        joint = self.joint_geometry(total_frames, overlap, blend)
+        if window_cond is not None:
+            if len(window_cond) != len(joint.starts):
+                raise ValueError("sample: window_cond holds %d conditions, the video has %d windows (starts %s)"
+                                 % (len(window_cond), len(joint.starts), list(joint.starts)))
+            if any(len(c) != batch for c in window_cond):
+                raise ValueError("sample: every entry of window_cond is a condition for the %d videos of the batch" % batch)
+        shape = (batch, self.channels, joint.total_frames, self.image_size, self.image_size)
+        return self.check_request(shape, known, known_mask, seeds, 0, known_level=known_level), joint
 
     @torch.no_grad()
-    def sample_checked(self, fea, cond, cond_scale, req):
-        """`sample` of a Request that `check_request` has returned (FlowDiffusion checks before the LFAE encoder runs)."""
+    def sample_checked(self, fea, cond, cond_scale, req, joint=None, window_cond=None):
+        """`sample` of a Request that `check_request` has returned (FlowDiffusion checks before the LFAE encoder runs).  joint / window_cond:
+        what `check_joint_request` returned and checked."""
         if cond is not None and len(cond) != req.shape[0]:
             raise ValueError("fea batch %d != cond batch %d" % (req.shape[0], len(cond)))
+        dev = next(self.denoise_fn.parameters()).device
+        if joint is not None:       # one condition row per window row, b W + w order
+            windows = len(joint.starts)
+            if window_cond is not None:
+                cond = torch.stack([self._embed(c, dev) for c in window_cond], dim=1).reshape(req.shape[0] * windows, -1).contiguous()
+            elif cond is not None:
+                cond = self._embed(cond, dev).repeat_interleave(windows, dim=0).contiguous()
+            return self._sample(fea, cond, cond_scale, self.is_ddim_sampling or self.sampler != "reference", self.sampler, req, joint)
         if cond is not None:
-            cond = self._embed(cond, next(self.denoise_fn.parameters()).device)
+            cond = self._embed(cond, dev)
         return self._sample(fea, cond, cond_scale, self.is_ddim_sampling or self.sampler != "reference", self.sampler, req)
 
     @torch.no_grad()
@@ -950,26 +1093,36 @@ class GaussianDiffusion(nn.Module):
                             self.check_request(shape, known, known_mask, seeds, window, start, start_step, steps=self.sampling_timesteps,
                                                known_level=known_level))
 
-    def _sample(self, fea, cond, cond_scale, ddim, sampler, req):
-        """One video batch: schedule -> this call's operand values -> the plan of its mode, refilled -> x_T -> the steps."""
+    def _sample(self, fea, cond, cond_scale, ddim, sampler, req, joint=None):
+        """One video batch: schedule -> this call's operand values -> the plan of its mode, refilled -> x_T -> the steps.
+        joint (a `JointGeometry`; default None): req.shape is the GLOBAL latent of a joint long video, the UNet runs on its windows of
+        num_frames frames and `cond` holds one row per window row, in b W + w order."""
         unet = self.denoise_fn
         dev = next(unet.parameters()).device
         batch, _, frames, s, _ = req.shape
+        windows = 1
+        if joint is not None:
+            frames, windows = self.num_frames, len(joint.starts)
         if getattr(unet, "long_attention", False):
             unet.check_geometry(frames, s)        # (frames / mid-block pixels the streaming kernels do not take: before the first launch)
         sch = self._schedule(ddim, sampler, dev, level=req.known is not None or req.start is not None)
         pk = unet.packed()
-        values = self._step_operands(unet, pk, sch, fea, cond, cond_scale, batch, s)
+        values = self._step_operands(unet, pk, sch, fea, cond, cond_scale, batch, s, batch * windows)
         mode = SampleMode(batch, frames, s, len(values["parts"]), float(cond_scale), bool(ddim), len(sch.times), id(pk), unet.conv_precision,
                           sampler, self.noise, float(self.dynamic_thres_percentile) if self.use_dynamic_thres else -1.0, req.known is not None,
                           req.known is not None and req.known_mask.dim() == 5).with_rescale(self.guidance_rescale)
+        if joint is not None:
+            mode = JointMode(SampleMode(*mode), joint, mode.rescale)
         plan = self._plans.get(mode) or self._new_plan(mode, pk, req.shape, values)
         # the plan owns every operand a captured kernel binds: each call, eager or replayed, copies its values into them
         plan["step_part"].copy_(values["step_part"])
         for dst, src in zip(plan["parts"], values["parts"]):
             dst.copy_(src)
         for rows in plan["fea_term"].chunk(mode.passes):        # (two passes: rows of samples [cond | null])
-            rows.copy_(values["fea_term"])
+            if joint is None:
+                rows.copy_(values["fea_term"])
+            else:               # computed once per video, repeated over its windows
+                rows.view(batch, windows, -1).copy_(values["fea_term"].reshape(batch, 1, -1).expand(batch, windows, -1))
         plan["coef"].copy_(sch.coef)
         first = req.start_step if req.start is not None else 0
         if first > 0 and sampler == "dpmpp_2m":         # no history in front of the first step run: first order, in the plan's own copy
@@ -981,9 +1134,11 @@ class GaussianDiffusion(nn.Module):
         return self._run_steps(unet, plan, mode, sch.draws, first)
 
     @staticmethod
-    def _step_operands(unet, pk, sch, fea, cond, cond_scale, batch, s):
-        """What this call feeds the step: the per-step part of the scale / shift rows, the per-sample part of each UNet pass, fea's term."""
+    def _step_operands(unet, pk, sch, fea, cond, cond_scale, batch, s, rows=None):
+        """What this call feeds the step: the per-step part of the scale / shift rows, the per-sample part of each UNet pass, fea's term.
+        rows (default: batch): the UNet's rows per pass and the rows of `cond` - batch * windows under a joint mode; fea stays per video."""
         dev = sch.coef.device
+        rows = batch if rows is None else rows
         fea = fea.to(dev).float().contiguous()
         if fea.shape[0] != batch:
             raise ValueError("fea batch %d != cond batch %d" % (fea.shape[0], batch))
@@ -992,7 +1147,7 @@ class GaussianDiffusion(nn.Module):
         temb_steps = unet.time_embedding(pk, sch.t_table, len(sch.times))
         parts = []
         if unet.has_cond:
-            ones = torch.ones(batch, dtype=torch.bool, device=dev)
+            ones = torch.ones(rows, dtype=torch.bool, device=dev)
             masks = [ones] if cond_scale == 0 else [~ones] if cond_scale == 1 else [~ones, ones]
             for m in masks:
                 step_part, sample_part = unet.cond_tables(pk, temb_steps, unet.merge_cond(cond, m))
@@ -1000,7 +1155,7 @@ class GaussianDiffusion(nn.Module):
             unet.null_cond_mask = masks[-1]
         else:
             step_part = ops.linear_small(temb_steps, pk["cond.w"], pk["cond.b"], act_in=ops.ACT_SILU)
-            parts.append(torch.zeros(batch, pk["cond.n"], device=dev))
+            parts.append(torch.zeros(rows, pk["cond.n"], device=dev))
         return {"step_part": step_part, "parts": parts, "fea_term": fea_term}
 
     def _new_plan(self, mode, pk, shape, values):
@@ -1009,14 +1164,27 @@ class GaussianDiffusion(nn.Module):
         capture again for each."""
         dev, batch, steps = values["step_part"].device, mode.batch, mode.steps
         new = lambda *size, **kw: torch.empty(size, device=dev, **kw)
+        joint = mode.joint
+        windows = 1 if joint is None else len(joint.starts)
         plan = {"x": new(*shape), "eps": new(*shape), "noise": new(*shape), "step": torch.zeros(1, dtype=torch.int32, device=dev),
-                "ss": new(batch, pk["cond.n"]), "ws": ops.sampler_ws(batch, math.prod(shape[1:]), dev), "pk": pk,
+                "ss": new(batch * windows, pk["cond.n"]), "ws": ops.sampler_ws(batch, math.prod(shape[1:]), dev), "pk": pk,
                 "step_part": torch.empty_like(values["step_part"]), "parts": [torch.empty_like(v) for v in values["parts"]],
-                "fea_term": values["fea_term"].new_empty((mode.passes * values["fea_term"].shape[0],) + tuple(values["fea_term"].shape[1:])),
+                "fea_term": values["fea_term"].new_empty((mode.passes * windows * values["fea_term"].shape[0],)
+                                                         + tuple(values["fea_term"].shape[1:])),
                 "coef": new(steps, 6), "graph": None, "chunk_graphs": {}, "buf_gen": None}
-        if mode.passes > 1:
+        if joint is not None:
+            # x, eps and everything the update reads have the GLOBAL shape; the UNet's operands are window rows in b W + w order, doubled
+            # for the two-pass step; the two tables are the plan's own, so a captured graph binds their addresses
+            rows, wshape = batch * windows, (shape[1], mode.frames) + tuple(shape[3:])
+            plan.update(xw=new(mode.passes * rows, *wshape), epsw=new(rows, *wshape), starts=ops.WindowStarts(joint.starts, dev),
+                        table=ops.WindowTable(ops.fold_table(joint.total_frames, mode.frames, joint.starts, joint.blend), dev))
+            if mode.passes > 1:
+                plan.update(eps2=new(2 * rows, *wshape), ss2=new(2 * rows, pk["cond.n"]))
+            if mode.rescale > 0.0:
+                plan["rescale_ws"] = ops.cfg_rescale_ws(rows, math.prod(wshape), dev)
+        elif mode.passes > 1:
             plan.update(x2=new(2 * batch, *shape[1:]), eps2=new(2 * batch, *shape[1:]), ss2=new(2 * batch, pk["cond.n"]))
-        if mode.rescale > 0.0:              # the partials of the rescale's two launches: allocated here, in front of any capture
+        if joint is None and mode.rescale > 0.0:        # the partials of the rescale's two launches: allocated here, in front of any capture
             plan["rescale_ws"] = ops.cfg_rescale_ws(batch, math.prod(shape[1:]), dev)
         if mode.sampler != "reference":
             plan["hist"] = new(*shape)       # m_{i-1}; never cleared: the first step of a video is first order and does not read it
@@ -1024,8 +1192,9 @@ class GaussianDiffusion(nn.Module):
             plan.update(seeds=torch.zeros(batch, dtype=torch.int64, device=dev), window=torch.zeros(1, dtype=torch.int32, device=dev))
         if mode.known:                      # another mask / other frames or elements: no new capture
             plan.update(known=new(*shape), known_noise=new(*shape), level=new(steps + 1, 2),
-                        kmask=torch.zeros(tuple(shape) if mode.elem else (batch, mode.frames), dtype=torch.bool, device=dev))
-        self._plans = {k: v for k, v in self._plans.items() if (k.known, k.elem) != (mode.known, mode.elem)}
+                        kmask=torch.zeros(tuple(shape) if mode.elem else (batch, mode.latent_frames), dtype=torch.bool, device=dev))
+        kind = lambda m: (m.known, m.elem, m.joint is not None)         # (a joint plan lives beside the plain and the conditioned one)
+        self._plans = {k: v for k, v in self._plans.items() if kind(k) != kind(mode)}
         self._plans[mode] = plan
         return plan
 
@@ -1062,7 +1231,7 @@ class GaussianDiffusion(nn.Module):
             if mode.elem:
                 ops.known_blend_elem(x, plan["known"], plan["known_noise"], plan["kmask"], a, s)
             else:
-                ops.known_blend(x, plan["known"], plan["known_noise"], plan["kmask"], a, s, mode.frames)
+                ops.known_blend(x, plan["known"], plan["known_noise"], plan["kmask"], a, s, mode.latent_frames)
         plan["step"].fill_(first)
 
     def _run_steps(self, unet, plan, mode, draws, first=0):

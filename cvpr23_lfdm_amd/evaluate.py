@@ -164,18 +164,19 @@ def sample_against_real(model, real_vid, mean=(0, 0, 0), domain="unit"):
             "flow": compare_flows(model.sample_vid_grid, model.real_vid_grid, model.sample_vid_conf, model.real_vid_conf)}
 
 
-def _sample(model, sample_img, sample_text, cond_scale, seed, total_frames, overlap, seeds=None):
+def _sample(model, sample_img, sample_text, cond_scale, seed, total_frames, overlap, seeds=None, method="chain", blend="ramp"):
     torch.manual_seed(seed)
     model.set_sample_input(sample_img=sample_img, sample_text=sample_text)
     if total_frames:
-        model.sample_long_video(cond_scale, total_frames, overlap=overlap, **({} if seeds is None else dict(seed=seeds)))
+        joint = dict(method="joint", blend=blend) if method == "joint" else {}
+        model.sample_long_video(cond_scale, total_frames, overlap=overlap, **joint, **({} if seeds is None else dict(seed=seeds)))
     else:
         model.sample_one_video(cond_scale=cond_scale, **({} if seeds is None else dict(seeds=seeds)))
     return {k: getattr(model, k).clone() for k in ("sample_out_vid", "sample_vid_grid", "sample_vid_conf")}
 
 
 def ab_compare(model_a, model_b, sample_img, sample_text, cond_scale=1.0, seed=0, mean=(0, 0, 0), domain="unit", total_frames=0, overlap=8,
-               seeds=None):
+               seeds=None, methods=("chain", "chain"), blend="ramp"):
     """Two sampling configurations on one input: B's video against A's.  Both models sample from the same source image, text and
     cond_scale directly after torch.manual_seed(seed).  Every sampler's first draw from the default generator is x_T, so both start from
     the same x_T; what follows is paired only as far as the configurations draw alike: the reference sampler (DDIM with
@@ -184,9 +185,11 @@ def ab_compare(model_a, model_b, sample_img, sample_text, cond_scale=1.0, seed=0
     seeds (one integer per video; both models built with noise="counter"): both sides sample the SAME videos - x_T, the known-frame noise of
     every window and the step noise of every step index are functions of the video's seed, so everything drawn is paired: two reference-sampler
     runs of different step counts share the noise of the step indices both have, and nothing depends on torch's generator.
+    total_frames > 0: both sides sample a long video, side i by methods[i] - "chain" or "joint" (blend: the joint method's profile;
+    DESIGN.md 4.17).  The two methods share x_T only where the chain's first window and the joint latent start alike: nothing else is paired.
     -> {"video": compare_videos(B, A), "flow": compare_flows(B, A)} (image-space and latent-space tables of B against A)."""
-    a = _sample(model_a, sample_img, sample_text, cond_scale, seed, total_frames, overlap, seeds)
-    b = _sample(model_b, sample_img, sample_text, cond_scale, seed, total_frames, overlap, seeds)
+    a = _sample(model_a, sample_img, sample_text, cond_scale, seed, total_frames, overlap, seeds, methods[0], blend)
+    b = _sample(model_b, sample_img, sample_text, cond_scale, seed, total_frames, overlap, seeds, methods[1], blend)
     return {"video": compare_videos(b["sample_out_vid"], a["sample_out_vid"], mean, domain),
             "flow": compare_flows(b["sample_vid_grid"], a["sample_vid_grid"], b["sample_vid_conf"], a["sample_vid_conf"])}
 

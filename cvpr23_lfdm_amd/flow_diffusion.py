@@ -239,8 +239,37 @@ class FlowDiffusion(nn.Module):
     def _decode_sample(self, img, skips, pred):
         self._decode_pieces(img, skips, [self._maps(pred) + (pred.shape[2],)])
 
-    def sample_long_video(self, cond_scale, total_frames, overlap=8, *, frame_times=None, interp="linear", seed=None, known_level="noised"):
-        """A video of `total_frames` frames, longer than the model's window of num_frames, as a chain of windows: the LFAE
+    LONG_METHODS = ("chain", "joint")
+
+    def joint_windows(self, total_frames, overlap):
+        """The window starts of sample_long_video(method="joint") for this model's window: a list of W integers (W before window_text is
+        built); refuses what the joint method refuses (ops.joint_windows)."""
+        return list(self.diffusion.joint_geometry(int(total_frames), int(overlap)).starts)
+
+    def _sample_joint_video(self, cond_scale, total_frames, overlap, blend, window_text, known_latent, known_mask, seeds, known_level):
+        """sample_long_video(method="joint") behind its checks: GaussianDiffusion.sample's joint mode on ONE encoder pass -> the latent of
+        total_frames frames (the global latent holds num_frames frames when total_frames is smaller: cut like the chain's)."""
+        dm = self.diffusion
+        with torch.no_grad():
+            req, joint = dm.check_joint_request(self.sample_img.shape[0], total_frames, overlap, blend, known_latent, known_mask, seeds,
+                                                known_level=known_level, window_cond=window_text)
+            img, skips, fea = self._source()
+            latent = dm.sample_checked(fea, None if window_text is not None else self.sample_text, cond_scale, req, joint=joint,
+                                       window_cond=window_text)
+        return img, skips, latent[:, :, :total_frames].contiguous()
+
+    def sample_long_video(self, cond_scale, total_frames, overlap=8, *, method="chain", blend="ramp", window_text=None, known_latent=None,
+                          known_mask=None, frame_times=None, interp="linear", seed=None, known_level="noised", start_latent=None,
+                          strength=None):
+        """A video of `total_frames` frames, longer than the model's window of num_frames.  method="joint" (keyword only):
+        ONE latent of total_frames frames whose overlapping windows (joint_windows(total_frames, overlap)) are denoised jointly - at every
+        step all windows go through the UNet as one batch and their outputs are averaged onto the global time line, weights by `blend`
+        ("ramp": a window counts more towards its middle; "uniform") - so overlap frames are one set of numbers and context flows both ways.
+        It takes known_latent (B,3,F,S,S) + known_mask ((B,F) bool or 5-D, as sample_one_video's) on the GLOBAL time line,
+        F = max(total_frames, num_frames), and window_text: W conditions, each what sample_text is, window w uses entry w (cross-faded over
+        the overlaps by the blend).  seed: one per video, counter word window = 0.  Averaging window outputs is a heuristic, not a sampler
+        of a known joint distribution.  start_latent / strength are refused by both methods.
+        method="chain" (default), as a chain of windows: the LFAE
         encoder runs ONCE; chunk 0 is a plain sample; chunk j > 0 is conditioned on the last `overlap` latent frames of chunk j - 1 placed at
         its frames 0 .. overlap-1 (same source image, features and text condition - only the latent is chained); the result keeps chunk 0 whole
         and frames overlap.. of every later chunk, cut to total_frames, and is decoded in pieces of at most num_frames frames.  Results as
@@ -259,12 +288,30 @@ class FlowDiffusion(nn.Module):
         dm = self.diffusion
         if known_level not in dm.KNOWN_LEVELS:
             raise ValueError("sample_long_video: known_level must be one of %s, got %r" % (dm.KNOWN_LEVELS, known_level))
+        if method not in self.LONG_METHODS:
+            raise ValueError("sample_long_video: method must be one of %s, got %r" % (self.LONG_METHODS, method))
+        if start_latent is not None or strength is not None:
+            raise ValueError("sample_long_video: start_latent / strength are not built for long videos (sample_one_video takes them)")
+        if method == "chain" and (known_latent is not None or known_mask is not None):
+            raise ValueError("sample_long_video: known_latent / known_mask need method='joint' (the chain conditions every window on its "
+                             "predecessor's overlap frames)")
+        if method == "chain" and (window_text is not None or blend != "ramp"):
+            raise ValueError("sample_long_video: blend and window_text belong to method='joint'")
         with torch.no_grad():
             b, seeds = self.sample_img.shape[0], seed
             if isinstance(seed, int) and not isinstance(seed, bool):
                 if b != 1:
                     raise ValueError("sample_long_video: a batch of %d videos needs a sequence of %d seeds" % (b, b))
                 seeds = [seed]
+            if method == "joint":
+                img, skips, latent = self._sample_joint_video(cond_scale, total_frames, overlap, blend, window_text, known_latent, known_mask,
+                                                              seeds, known_level)
+                self.sample_latent = latent
+                self._decode_pieces(img, skips, (self._maps(latent[:, :, f0:f0 + nf].contiguous()) + (min(nf, total_frames - f0),)
+                                                 for f0 in range(0, total_frames, nf)))
+                if frame_times is not None:
+                    self.decode_at(frame_times, interp)
+                return
             req = dm.check_request((b, dm.channels, nf, dm.image_size, dm.image_size), seeds=seeds)
             img, skips, fea = self._source()
             chunk = dm.sample_checked(fea, self.sample_text, cond_scale, req)

@@ -1960,6 +1960,210 @@ def latent_resample_maps(latent, times, mode="linear", residual=False, clamp_fro
 
 
 # ---------------------------------------------------------------------------------------------
+# joint sampling of a long video through overlapping windows (csrc/window_fold.hip)
+# ---------------------------------------------------------------------------------------------
+WINDOW_BLENDS = ("ramp", "uniform")
+FOLD_MAX_CONTRIB = 8            # LFDM_FOLD_MAX_CONTRIB
+JOINT_ELEMS_LIMIT = 1 << 24     # lfdm_sampler_step_f32's bound on the elements of one sample
+
+
+def joint_windows(total_frames, frames, overlap, blend="ramp", *, channels=3, size=None):
+    """The host tables of a joint long video: `total_frames` global frames covered by windows of `frames` frames.  -> (starts, table):
+    starts (W,) int32 - 0, s, 2s, ... with s = frames - overlap while start + frames < total_frames, then one last window at
+    total_frames - frames (total_frames <= frames: the single window [0] on a global latent of `frames` frames); table: dict of count (F,)
+    int32, win / loc (F, 8) int32 and wgt (F, 8) float32 over the F = max(total_frames, frames) global frames - frame f's contributors in
+    ascending window order, window number and frame inside it, and the weight p / sum p of the window profile p(t): "ramp"
+    min(t + 1, frames - t), "uniform" 1 - formed in float64 and rounded once to fp32 (one contributor: exactly 1.0f).  Unused slots are
+    zero.  Plain integers in, numpy arrays out; no device is needed.  size (keyword; the latent's S, with channels): also refuse a global
+    latent the sampler update does not take."""
+    import numpy as np
+    for name, v in (("total_frames", total_frames), ("frames", frames), ("overlap", overlap)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError("joint_windows: %s must be an integer, got %r" % (name, v))
+    if blend not in WINDOW_BLENDS:
+        raise ValueError("joint_windows: blend must be one of %s, got %r" % (WINDOW_BLENDS, blend))
+    if total_frames < 1 or frames < 1:
+        raise ValueError("joint_windows: total_frames and frames must be at least 1, got %d and %d" % (total_frames, frames))
+    if not 1 <= overlap <= frames - 1:
+        raise ValueError("joint_windows: overlap must lie in [1, frames - 1 = %d], got %d" % (frames - 1, overlap))
+    total = max(total_frames, frames)
+    if size is not None and channels * size * size * total >= JOINT_ELEMS_LIMIT:
+        raise ValueError("joint_windows: %d frames of %d x %d x %d are %d elements per video, the sampler step takes fewer than 2^24 = %d"
+                         % (total, channels, size, size, channels * size * size * total, JOINT_ELEMS_LIMIT))
+    stride, starts = frames - overlap, [0]
+    while starts[-1] + frames < total:
+        nxt = starts[-1] + stride
+        starts.append(nxt if nxt + frames < total else total - frames)
+    return np.asarray(starts, dtype=np.int32), fold_table(total, frames, starts, blend)
+
+
+def fold_table(total_frames, frames, starts, blend="ramp"):
+    """The contributor table of `joint_windows` for given window starts (ascending, every frame of 0 .. total_frames - 1 covered)."""
+    import numpy as np
+    if blend not in WINDOW_BLENDS:
+        raise ValueError("joint_windows: blend must be one of %s, got %r" % (WINDOW_BLENDS, blend))
+    total, starts = int(total_frames), [int(s) for s in starts]
+    if any(not 0 <= s <= total - frames for s in starts) or any(a >= b for a, b in zip(starts, starts[1:])):
+        raise ValueError("joint_windows: starts must ascend inside [0, %d], got %s" % (total - frames, starts))
+    t = np.arange(frames, dtype=np.float64)
+    profile = np.minimum(t + 1.0, frames - t) if blend == "ramp" else np.ones(frames, dtype=np.float64)
+    count = np.zeros(total, dtype=np.int32)
+    win = np.zeros((total, FOLD_MAX_CONTRIB), dtype=np.int32)
+    loc = np.zeros((total, FOLD_MAX_CONTRIB), dtype=np.int32)
+    wgt = np.zeros((total, FOLD_MAX_CONTRIB), dtype=np.float32)
+    for f in range(total):
+        who = [(w, f - s) for w, s in enumerate(starts) if s <= f < s + frames]
+        if len(who) > FOLD_MAX_CONTRIB:
+            raise ValueError("joint_windows: frame %d lies in %d windows, the fold takes at most %d contributors per frame (a smaller "
+                             "overlap)" % (f, len(who), FOLD_MAX_CONTRIB))
+        p = np.array([profile[tt] for _, tt in who], dtype=np.float64)
+        count[f] = len(who)
+        win[f, :len(who)] = [w for w, _ in who]
+        loc[f, :len(who)] = [tt for _, tt in who]
+        if not who:
+            raise ValueError("joint_windows: frame %d lies in no window of starts %s" % (f, starts))
+        wgt[f, :len(who)] = (p / p.sum()).astype(np.float32)
+    return {"count": count, "win": win, "loc": loc, "wgt": wgt}
+
+
+class WindowStarts:
+    """The window starts of window_gather on a device, with the host copy the entry point checks.  A plan keeps one: a captured graph binds
+    the device table's address, `fill` rewrites both in place."""
+
+    def __init__(self, starts, device):
+        self.host = _host_i32("window_gather: starts", starts, 1)
+        self.dev = torch.from_numpy(self.host).to(device)
+
+    def fill(self, starts):
+        host = _host_i32("window_gather: starts", starts, 1)
+        if host.shape != self.host.shape:
+            raise ValueError("window_gather: %d starts into a table of %d" % (host.shape[0], self.host.shape[0]))
+        self.host[...] = host
+        self.dev.copy_(torch.from_numpy(self.host))
+        return self
+
+
+class WindowTable:
+    """The contributor table of window_fold on a device (count, win, loc, wgt of `joint_windows`), with the host copy of count the entry
+    point checks and host copies of win / loc for the checks made here.  `fill` rewrites all in place (same frame count)."""
+    KEYS = ("count", "win", "loc", "wgt")
+
+    def __init__(self, table, device):
+        self.host = self._check(table)
+        self.dev = {k: torch.from_numpy(v).to(device) for k, v in self.host.items()}
+
+    @staticmethod
+    def _check(table):
+        import numpy as np
+        count = _host_i32("window_fold: table count", table["count"], 1)
+        shape = (count.shape[0], FOLD_MAX_CONTRIB)
+        win, loc = (_host_i32("window_fold: table " + k, table[k], 2) for k in ("win", "loc"))
+        wgt = np.ascontiguousarray(np.asarray(table["wgt"], dtype=np.float32))
+        if win.shape != shape or loc.shape != shape or wgt.shape != shape:
+            raise ValueError("window_fold: win, loc and wgt must be (%d, %d) tables" % shape)
+        return {"count": count.copy(), "win": win.copy(), "loc": loc.copy(), "wgt": wgt.copy()}
+
+    def fill(self, table):
+        host = self._check(table)
+        if host["count"].shape != self.host["count"].shape:
+            raise ValueError("window_fold: a table of %d frames into one of %d" % (host["count"].shape[0], self.host["count"].shape[0]))
+        for k in self.KEYS:
+            self.host[k][...] = host[k]
+            self.dev[k].copy_(torch.from_numpy(self.host[k]))
+        return self
+
+
+def _host_i32(what, values, dim):
+    import numpy as np
+    if isinstance(values, torch.Tensor):
+        if values.is_cuda:
+            raise ValueError("%s is a host sequence or array (it is checked on the host), got a tensor on %s" % (what, values.device))
+        values = values.detach().numpy()
+    try:
+        arr = np.asarray(values)
+        if arr.dtype.kind not in "iu" or arr.ndim != dim or arr.size == 0:
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a non-empty %d-D sequence of integers" % (what, dim))
+    return np.ascontiguousarray(arr.astype(np.int32))
+
+
+def _window_operand(what, name, t, shape=None):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 5 or not t.is_contiguous() or \
+            (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError("%s: %s must be a contiguous float32 5-D tensor%s, got %s %s"
+                         % (what, name, "" if shape is None else " of shape %s" % (tuple(shape),), getattr(t, "dtype", type(t)),
+                            tuple(getattr(t, "shape", ()))))
+    if min(t.shape) < 1:
+        raise ValueError("%s: %s is empty, shape %s" % (what, name, tuple(t.shape)))
+
+
+def window_gather(x, starts, frames, out=None):
+    """lfdm_window_gather_f32: x (B, C, F, S, S') fp32, contiguous -> out (B * W, C, frames, S, S') with out[b * W + w, :, t] =
+    x[b, :, starts[w] + t]: the windows of a joint long video, rows in b * W + w order.  starts: W integers in [0, F - frames] - a host
+    sequence (uploaded by this call) or a `WindowStarts` (a plan's table: nothing is uploaded).  A pure copy; everything is checked
+    before the launch."""
+    lib = _lib()
+    what = "window_gather"
+    _window_operand(what, "x", x)
+    if not isinstance(starts, WindowStarts):
+        starts = WindowStarts(starts, x.device)
+    b, c, total, h, w = (int(v) for v in x.shape)
+    frames, nwin = int(frames), int(starts.host.shape[0])
+    if not 1 <= frames <= total:
+        raise ValueError("%s: windows of %d frames do not fit a latent of %d" % (what, frames, total))
+    if int(starts.host.min()) < 0 or int(starts.host.max()) > total - frames:
+        raise ValueError("%s: starts span %d .. %d, windows of %d frames start in [0, %d]"
+                         % (what, int(starts.host.min()), int(starts.host.max()), frames, total - frames))
+    shape = (b * nwin, c, frames, h, w)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    _window_operand(what, "out", out, shape)
+    _chk_dev(lib, x, out, starts.dev)
+    if out.device != x.device or starts.dev.device != x.device:
+        raise ValueError("%s: x, out and the starts table must share a device" % what)
+    lib.check(lib.lfdm_window_gather_f32(_p(x), _p(starts.dev), C.c_void_p(starts.host.ctypes.data), _p(out), b, nwin, c, total, frames,
+                                         h * w, _stream(lib)), "lfdm_window_gather_f32")
+    return out
+
+
+def window_fold(ew, table, out):
+    """lfdm_window_fold_f32: ew (B * W, C, T, S, S') fp32 window outputs -> out (B, C, F, S, S'), out[b, :, f] = sum_j wgt[f, j] *
+    ew[b * W + win[f, j], :, loc[f, j]] over the frame's count[f] contributors in ascending j, one product and one addition each (no
+    fma); a frame with one contributor of weight 1.0f is the window's value bit for bit.  table: the dict `joint_windows` returns (uploaded
+    by this call) or a `WindowTable` (a plan's).  W is taken from the shapes; every count, window number and frame is checked here."""
+    lib = _lib()
+    what = "window_fold"
+    _window_operand(what, "ew", ew)
+    _window_operand(what, "out", out)
+    if not isinstance(table, WindowTable):
+        table = WindowTable(table, ew.device)
+    bw, c, frames, h, w = (int(v) for v in ew.shape)
+    b, total = int(out.shape[0]), int(out.shape[2])
+    host = table.host
+    if tuple(out.shape) != (b, c, total, h, w) or bw % b != 0 or frames > total:
+        raise ValueError("%s: out %s does not go with window outputs %s" % (what, tuple(out.shape), tuple(ew.shape)))
+    nwin = bw // b
+    if host["count"].shape[0] != total:
+        raise ValueError("%s: a table of %d frames for an output of %d" % (what, host["count"].shape[0], total))
+    if int(host["count"].min()) < 1 or int(host["count"].max()) > FOLD_MAX_CONTRIB:
+        raise ValueError("%s: every frame needs 1 .. %d contributors, the table's counts span %d .. %d"
+                         % (what, FOLD_MAX_CONTRIB, int(host["count"].min()), int(host["count"].max())))
+    import numpy as np
+    used = np.arange(FOLD_MAX_CONTRIB)[None, :] < host["count"][:, None]
+    if (used & ((host["win"] < 0) | (host["win"] >= nwin) | (host["loc"] < 0) | (host["loc"] >= frames))).any():
+        raise ValueError("%s: the table names a window outside 0 .. %d or a frame outside 0 .. %d" % (what, nwin - 1, frames - 1))
+    _chk_dev(lib, ew, out, *table.dev.values())
+    if out.device != ew.device or any(t.device != ew.device for t in table.dev.values()):
+        raise ValueError("%s: ew, out and the table must share a device" % what)
+    dev = table.dev
+    lib.check(lib.lfdm_window_fold_f32(_p(ew), _p(dev["count"]), _p(dev["win"]), _p(dev["loc"]), _p(dev["wgt"]),
+                                       C.c_void_p(host["count"].ctypes.data), _p(out), b, nwin, c, total, frames, h * w, _stream(lib)),
+              "lfdm_window_fold_f32")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # training latents gathered from a flow-latent store (csrc/latent_gather.hip, DESIGN.md 4.13)
 # ---------------------------------------------------------------------------------------------
 LATENT_DTYPES = (torch.float32, torch.float16)          # LFDM_LATENT_* = the position in this tuple

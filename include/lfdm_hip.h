@@ -1198,6 +1198,42 @@ int lfdm_latent_resample_f32(const float* latent, const int* idx, const float* f
 int lfdm_latent_gather_f32(const void* store, int store_dtype, int64_t store_frames, const int* frame_index, const float* ident_x,
                            const float* ident_y, float* out, int batch, int frames, int h, int w, lfdm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Joint sampling of a long video through overlapping windows (additive under ABI 13): one latent x of total_frames
+ * frames is cut into `windows` windows of `frames` frames that go through the denoiser as one batch, and the window outputs are folded
+ * back onto the global time line.  Planar fp32; frame_elems = the floats of one frame of one channel (S * S).  Window rows are ordered
+ * b * windows + w.
+ *
+ * lfdm_window_gather_f32: xw[b * windows + w, c, t, :] = x[b, c, starts[w] + t, :] - a copy.  x (batch, channels, total_frames,
+ * frame_elems), xw (batch * windows, channels, frames, frame_elems).  starts: DEVICE (windows) int32, the table the kernel reads (a captured
+ * graph binds its address); starts_host: HOST (windows) int32, the caller's copy of the same table, which the entry point checks - every
+ * start in [0, total_frames - frames].  The kernel clamps what it reads into that range, so a device table that differs from the host
+ * copy reads other frames, never outside x.
+ *
+ * lfdm_window_fold_f32: out[b, c, f, :] = sum over j < count[f] of wgt[f, j] * ew[b * windows + win[f, j], c, loc[f, j], :], taken in
+ * ascending j as ((w0 e0 + w1 e1) + w2 e2) + ...: one fp32 product and one fp32 addition per contributor, no fma.  A frame with ONE
+ * contributor of weight 1.0f is that window's value bit for bit, and no other window is read for it (a NaN elsewhere cannot reach it).
+ * ew (batch * windows, channels, frames, frame_elems), out (batch, channels, total_frames, frame_elems).  The contributor table is DEVICE
+ * memory the caller prepares: count (total_frames) int32, win / loc (total_frames, LFDM_FOLD_MAX_CONTRIB) int32 - window number and frame
+ * inside it -, wgt (total_frames, LFDM_FOLD_MAX_CONTRIB) fp32; slots j >= count[f] are not read.  count_host: HOST (total_frames) int32, the
+ * caller's copy of count, which the entry point checks - every count in 1 .. LFDM_FOLD_MAX_CONTRIB.  THE CALLER CHECKS win and loc; the
+ * kernel clamps them (and count) into range, so a bad table reads a wrong frame, never outside ew.
+ *
+ * Both: 16-byte loads and stores where frame_elems % 4 == 0 and both float operands are 16-byte aligned, else an element path with the
+ * same values in the same order.  256-thread workgroups, one item (4 floats or 1) per thread and trip, min(ceil(items / 256), 1024)
+ * workgroups in a grid-stride loop: the grid depends on the shapes only.  No atomics, no LDS, no workspace, nothing depends on launch
+ * order: results are bit-identical from run to run.  Refusals (LFDM_EINVAL, nothing is enqueued or written): a null operand, a
+ * non-positive size, frames > total_frames, an operand of 2^40 floats or more, out / xw overlapping the input, a start outside
+ * [0, total_frames - frames], a count of 0 or above LFDM_FOLD_MAX_CONTRIB. */
+#define LFDM_FOLD_MAX_CONTRIB 8
+/* Layout: all operands dense; x, xw 4 B (16 B for the wide path); starts 4 B; starts_host is host memory; xw may not alias x. */
+int lfdm_window_gather_f32(const float* x, const int* starts, const int* starts_host, float* xw, int batch, int windows, int channels,
+                           int total_frames, int frames, int64_t frame_elems, lfdm_stream_t stream);
+/* Layout: all operands dense; ew, out 4 B (16 B for the wide path); count, win, loc, wgt 4 B; count_host is host memory; out may not alias ew. */
+int lfdm_window_fold_f32(const float* ew, const int* count, const int* win, const int* loc, const float* wgt, const int* count_host,
+                         float* out, int batch, int windows, int channels, int total_frames, int frames, int64_t frame_elems,
+                         lfdm_stream_t stream);
+
 /* Box calibration, not on the product path (bench.py prints it beside every timing; ABI version 7): `blocks` workgroups of four
  * wavefronts run `iters` x 4 independent v_mfma_f32_32x32x2_f32 (2 * 32 * 32 * 2 FLOP each, pseudo-random operands) and
  * record, per workgroup b, out[2b] = shader cycles and out[2b+1] = 100 MHz real-time ticks of the loop: effective clock (MHz) =

@@ -63,6 +63,16 @@ def build_parser():
                     help="a video of this many frames, longer than --frames, as a chain of overlapping windows conditioned on known frames "
                          "(FlowDiffusion.sample_long_video, DESIGN.md 4.3); 0 (default): off, one window of --frames")
     ap.add_argument("--overlap", type=int, default=8, help="latent frames two consecutive windows of --total-frames share")
+    ap.add_argument("--long-method", choices=("chain", "joint"), default="chain",
+                    help="how --total-frames is made: chain (default) - window after window, each conditioned on its predecessor's overlap "
+                         "frames; joint - one latent of --total-frames frames whose overlapping windows are denoised together, their outputs "
+                         "averaged per step (a heuristic; DESIGN.md 4.17)")
+    ap.add_argument("--blend", choices=("ramp", "uniform"), default="ramp",
+                    help="--long-method joint: the weight of a window's frame in the average - ramp (default): more towards the window's "
+                         "middle; uniform")
+    ap.add_argument("--window-labels", default="",
+                    help="--long-method joint: comma-separated prompts, one per window, in place of --text (cross-faded over the overlaps); "
+                         "the number of windows is printed when it does not match")
     ap.add_argument("--known-level", choices=("noised", "clean"), default="noised",
                     help="how known content (--total-frames' overlap frames, --keep-box / --regen-box) is held during sampling: on the step's "
                          "noise level (default), or clean at every step - for a checkpoint trained with tools/train_dm.py --known-prob "
@@ -192,6 +202,12 @@ def check_args(args):
         sys.exit("--keep-box and --regen-box exclude each other (one is the complement of the other)")
     if args.strength is not None and not 0.0 < args.strength <= 1.0:
         sys.exit("--strength must lie in (0, 1]")
+    if (args.long_method != "chain" or args.blend != "ramp" or args.window_labels) and args.total_frames <= 0:
+        sys.exit("--long-method / --blend / --window-labels need --total-frames")
+    if (args.blend != "ramp" or args.window_labels) and args.long_method != "joint":
+        sys.exit("--blend / --window-labels need --long-method joint")
+    if args.long_method == "joint" and args.known_level == "clean":
+        sys.exit("--known-level clean holds the chain's overlap frames: --long-method joint has none")
     if args.from_video and args.total_frames > 0:
         sys.exit("--from-video edits one window of --frames: it does not combine with --total-frames")
     for box in (args.keep_box, args.regen_box):
@@ -200,6 +216,17 @@ def check_args(args):
                 parse_box(box, args.size // 4)
             except ValueError as e:
                 sys.exit(str(e))
+
+
+def window_labels(args, windows):
+    """--window-labels as a list of `windows` prompts, or None when the option is not given."""
+    if not args.window_labels:
+        return None
+    labels = [v.strip() for v in args.window_labels.split(",")]
+    if len(labels) != windows or not all(labels):
+        sys.exit("--window-labels: %d frames at overlap %d are %d windows, one prompt each is needed, got %r"
+                 % (args.total_frames, args.overlap, windows, args.window_labels))
+    return labels
 
 
 def video_seeds(args):
@@ -313,7 +340,12 @@ def main():
         t0 = time.perf_counter()
         ref_b = ref.expand(args.batch, -1, -1, -1).contiguous()
         model.set_sample_input(sample_img=ref_b, sample_text=[text] * args.batch)
-        if args.total_frames > 0:
+        if args.total_frames > 0 and args.long_method == "joint":
+            labels = window_labels(args, len(model.joint_windows(args.total_frames, args.overlap)))
+            model.sample_long_video(args.cond_scale, args.total_frames, overlap=args.overlap, method="joint", blend=args.blend,
+                                    window_text=None if labels is None else [[label] * args.batch for label in labels],
+                                    **({} if seeds is None else dict(seed=seeds)))
+        elif args.total_frames > 0:
             model.sample_long_video(args.cond_scale, args.total_frames, overlap=args.overlap, known_level=args.known_level,
                                     **({} if seeds is None else dict(seed=seeds)))
         else:

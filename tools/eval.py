@@ -35,7 +35,7 @@ sys.path.insert(0, ROOT)
 from cvpr23_lfdm_amd import _native, datasets, evaluate as E, io_compat as C  # noqa: E402
 
 DATASETS = {"mug": datasets.MUG_test, "mhad": datasets.MHAD_test, "natops": datasets.NATOPS_test}
-AB_KEYS = {"sampler": str, "steps": int, "conv_precision": str, "use_ema": lambda v: v.lower() in ("1", "true", "yes")}
+AB_KEYS = {"sampler": str, "steps": int, "conv_precision": str, "use_ema": lambda v: v.lower() in ("1", "true", "yes"), "long_method": str}
 HELD_FIXED_COUNTER = ["source image", "text condition", "cond_scale",
                       "the video's seed (--noise counter): the same x_T, the same known-frame noise, and the same step noise at every step index "
                       "both configurations draw at"]
@@ -102,6 +102,13 @@ def build_parser():
     p.add_argument("--b", default="", help="configuration B, likewise; unset keys take the shared options")
     p.add_argument("--image", default="")
     p.add_argument("--text", default="happiness")
+    p.add_argument("--total-frames", type=int, default=0, help="both sides sample a long video of this many frames "
+                                                                "(FlowDiffusion.sample_long_video); 0 (default): one window of --frames")
+    p.add_argument("--overlap", type=int, default=8, help="latent frames two consecutive windows of --total-frames share")
+    p.add_argument("--long-method", choices=("chain", "joint"), default="chain",
+                   help="how --total-frames is made (DESIGN.md 4.3 / 4.17); a side's own long_method=... in --a / --b wins: "
+                        "--a long_method=chain --b long_method=joint compares the two")
+    p.add_argument("--blend", choices=("ramp", "uniform"), default="ramp", help="the joint method's window profile")
     return ap
 
 
@@ -137,6 +144,9 @@ def build_model(args, overrides=None):
     """The model of tools/demo.py (its make_model) for the shared options, with `overrides` (an --a / --b list) on top."""
     cfg = dict(sampler=args.sampler, steps=args.steps, conv_precision=args.conv_precision, use_ema=args.use_ema)
     cfg.update(overrides or {})
+    long_method = cfg.pop("long_method", getattr(args, "long_method", "chain"))         # (no option of the model: of how it is sampled)
+    if long_method not in ("chain", "joint"):
+        sys.exit("long_method is chain or joint, got %r" % (long_method,))
     if cfg["use_ema"] and (args.synthetic or not args.dm_ckpt):
         sys.exit("use_ema needs --dm-ckpt: a checkpoint with a 'diffusion_ema' entry")
     explicit = set(getattr(args, "explicit", ())) | set(overrides or {})       # (asked for on the command line or by an --a / --b list)
@@ -146,6 +156,8 @@ def build_model(args, overrides=None):
         model.region_predictor.load_state_dict(synth.region_state())
         model.bg_predictor.load_state_dict(synth.bg_state())
     cfg.update(sampler=model.diffusion.sampler, steps=model.diffusion.sampling_timesteps)       # (as resolved: the defaults, a distilled checkpoint's own)
+    if getattr(args, "total_frames", 0):
+        cfg.update(long_method=long_method)
     return model.to(device()).eval(), cfg
 
 
@@ -251,8 +263,11 @@ def run_ab(args):
         img = np.random.default_rng(args.seed).integers(0, 256, size=(args.size, args.size, 3), dtype=np.uint8)
     ref = torch.from_numpy(np.asarray(img, np.float32) / 255.0).permute(2, 0, 1).unsqueeze(0)
     counter = args.noise == "counter"
+    if args.total_frames <= 0 and (args.long_method != "chain" or args.blend != "ramp"):
+        sys.exit("--long-method / --blend need --total-frames")
     res = E.ab_compare(model_a, model_b, ref, [args.text], cond_scale=args.cond_scale, seed=args.seed, domain=args.domain,
-                       seeds=[args.seed % (1 << 64)] if counter else None)
+                       seeds=[args.seed % (1 << 64)] if counter else None, total_frames=max(args.total_frames, 0), overlap=args.overlap,
+                       methods=(cfg_a.get("long_method", "chain"), cfg_b.get("long_method", "chain")), blend=args.blend)
     video, flow = res["video"]["table"][0].cpu(), res["flow"]["table"][0].cpu()
     psnr = res["video"]["psnr"][0].cpu().tolist()
     print("B against A per frame:  frame        l1       mse      psnr      ssim       epe  occl.err")
