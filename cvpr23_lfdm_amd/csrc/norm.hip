@@ -441,6 +441,8 @@ extern "C" int lfdm_planar_to_cl_f32(const float* x, float* out, int n_img, int 
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !out || n_img <= 0 || channels <= 0 || hw <= 0 || ldo < channels)
     return lfdm_fail(LFDM_EINVAL, "planar_to_cl: bad arguments");
+  if (n_img > 65535 || (channels + 31) / 32 > 65535)          // grid z = images, grid y = 32-channel tiles: the launch itself would be rejected
+    return lfdm_fail(LFDM_EINVAL, "%s", "planar_to_cl: at most 65535 images and 65535 * 32 channels per call (grid limit)");
   LFDM_LAUNCH(planar_to_cl_kernel, dim3((hw + 31) / 32, (channels + 31) / 32, n_img), dim3(256), 0,
               stream, x, out, channels, hw, ldo);
   return lfdm_check_launch("planar_to_cl");
@@ -451,6 +453,8 @@ extern "C" int lfdm_cl_to_planar_f32(const float* x, float* out, int n_img, int 
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !out || n_img <= 0 || channels <= 0 || hw <= 0 || ldx < channels)
     return lfdm_fail(LFDM_EINVAL, "cl_to_planar: bad arguments");
+  if (n_img > 65535 || (channels + 31) / 32 > 65535)          // grid z = images, grid y = 32-channel tiles: the launch itself would be rejected
+    return lfdm_fail(LFDM_EINVAL, "%s", "cl_to_planar: at most 65535 images and 65535 * 32 channels per call (grid limit)");
   LFDM_LAUNCH(cl_to_planar_kernel, dim3((hw + 31) / 32, (channels + 31) / 32, n_img), dim3(256), 0,
               stream, x, out, channels, hw, ldx);
   return lfdm_check_launch("cl_to_planar");

@@ -412,6 +412,8 @@ extern "C" int lfdm_linear_small_f32(const float* x, const float* w, const float
   hipStream_t stream = (hipStream_t)stream_;
   if (!x || !w || !y || batch <= 0 || k <= 0 || n <= 0 || ldx < k || ldw < k || ldy < n)
     return lfdm_fail(LFDM_EINVAL, "linear_small: bad arguments");
+  if (batch > 65535)                                           // grid y = rows of x: the launch itself would be rejected
+    return lfdm_fail(LFDM_EINVAL, "%s", "linear_small: at most 65535 rows per call (grid limit)");
   LFDM_LAUNCH(linear_small_kernel, dim3((n + 3) / 4, batch), dim3(256), 0, stream, x, w, bias, y, k,
               n, ldx, ldw, ldy, act_in, act_out);
   return lfdm_check_launch("linear_small");

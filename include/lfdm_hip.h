@@ -267,7 +267,7 @@ int lfdm_linear_attention_cl_f32(const float* qkv, float* out, int n_frames, int
 /* ------------------------------------------------------------------------------------------
  * Small dense layers of the conditioning path (time_mlp :423-428, ResnetBlock.mlp :217-220).
  * y[b][n] = act_out( sum_k act_in(x[b][k]) * w[n][k] + bias[n] ),  w rows of stride ldw. */
-/* Layout: x (ldx), w (ldw), y (ldy), bias: any. */
+/* Layout: x (ldx), w (ldw), y (ldy), bias: any.  batch <= 65535 (grid y); more rows are refused with LFDM_EINVAL, nothing launched. */
 int lfdm_linear_small_f32(const float* x, const float* w, const float* bias, float* y,
                           int batch, int k, int n, int ldx, int ldw, int ldy, int act_in,
                           int act_out, lfdm_stream_t stream);
@@ -468,7 +468,8 @@ int lfdm_warp_planar_f32(const lfdm_warp_params* p, lfdm_stream_t stream);
  * avgpool2:   2x2 average pool (DownBlock2d, util.py:124)
  */
 /* Layout: affine_act: x (ldx), out (ldo), a, b: 16 B, ld % 4, C % 4; out may alias x.  avgpool2: x, out dense, 16 B.  planar_to_cl: out (ldo) any.
- * cl_to_planar: x (ldx) any. */
+ * cl_to_planar: x (ldx) any.  Both transposes: n_img <= 65535 (grid z) and C <= 65535 * 32 (grid y); more is refused with LFDM_EINVAL,
+ * nothing launched. */
 int lfdm_affine_act_cl_f32(const float* x, float* out, int64_t rows, int channels, int ldx,
                            int ldo, const float* a, const float* b, int act,
                            lfdm_stream_t stream);

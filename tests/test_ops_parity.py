@@ -615,8 +615,8 @@ def test_conv_planar_in_and_heads(backend):
                                 bias=bias.to(dev), add_term=to_cl(add).to(dev))
     assert_close(unet_from_cl(out.cpu(), b, t, s, s), ref, TOL, "conv_planar_in")
     # ragged patch grid (rows not a multiple of 4, more than 32 columns), 128 output channels, odd K (5*5*3 = 75), ReLU, no add term:
-    # the matrix-pipe form and the VALU form (LFDM_STEM_MFMA=0 is read once per process: the latter is covered by the emulator runs
-    # of earlier rounds' fixtures; here whichever the library selects)
+    # here whichever form the library selects (the matrix-pipe one in the shipped build); the VALU form, at shapes only it serves and at this
+    # kind of shape behind an unaligned filter, is pinned by tests/test_boundary_edges.py::test_stem_conv_valu_form and ::test_stem_conv_both_forms
     n2, h2, w2 = 2, 6, 40
     x2 = rnd(n2, 3, 1, h2, w2, seed=11)
     wt2 = rnd(128, 3, 1, 5, 5, seed=12, scale=0.1)
@@ -1096,6 +1096,38 @@ def test_attention_lowres(backend, c, frames, s, mode):
 #   NOT reached at a test-sized shape: the grid caps of warp_cl_kernel / warp_bwd_cl_kernel (65 536 / 65 535 workgroups: more than 16 M lane items per
 #   frame) and of pool2_kernel / relu_bwd_kernel / l1_mean_bwd_kernel (262 140 workgroups: more than 67 M float4), im2col_cl_kernel's (134 M float4);
 #   warp_planar_kernel<false> for a plane beyond 128 x 128 (needs 2048 such planes: 135 MB); fix_exponent's lower clamp (needs max |dout| > FLT_MAX).
+#
+# The boundary kernels on the way into and out of the model (csrc/small.hip, csrc/conv_smalln.hip, the glue kernels of csrc/norm.hip).
+# tests/test_boundary_edges.py, float64 references, operands in NaN-padded rows, NaN-filled destinations with ld > C; ids without the backend:
+#   lfdm_conv_planar_in_cl_f32
+#     conv_planar_in_mfma_kernel, generic k-walk: K = 1 (one pixel) | K = 196 = CPI_MAX_K (7x7x4, column tile one pixel wide, ragged rows) | 8 planes
+#     in `win`, two output slices | 3x5 | 7x1x3 (not the unrolled 7x7x3 walk) | 1x7x5, third column tile
+#                                                        test_stem_conv_matrix_pipe_walk[<b>-<cin>-<cin_total>-<t>-<h>-<w>-<kh>-<kw>-<cout>-<act>-<add>]
+#     conv_planar_in_kernel as the launcher selects it: cin 12 (90 pixels) | 21 (258 pixels, two slices) | 196 (1x1) | 9 (three slices, ldo 195: scalar
+#     epilogue) | 9x3 | 1x11; float4 staging, float4 epilogue elsewhere       test_stem_conv_valu_form[<the same fields>]
+#     both forms at one shape: 7x7x3 aligned (unrolled walk) | filter one float in (VALU form, scalar staging) | filter and bias one float in (scalar
+#     epilogue too); 5x5x3 x 128 with the bias one float in (matrix-pipe form)    test_stem_conv_both_forms[7x7x3-filter|5x5x3-bias]
+#   lfdm_heads_cl_to_planar_f32 heads_kernel<false> / lfdm_heads_res_cl_to_planar_f32 heads_kernel<true>: C 4 | 12 | 128 | 256; (c0, c1) (4, 0) |
+#     (256, 256) | (512, 0) | (4, 508); 1 | 255 | 258 | 514 rows    test_heads_widths_and_rows[<b>-<t>-<hw>-<C>-<c0>-<c1>]
+#   lfdm_heads_gn_res_cl_to_planar_f32  heads_gn_kernel: 2C 512 with 64 groups | 128 at (128, 0) (generic path) | 128 at (64, 64) with one group, 33
+#     pixels (register path) | 8 | 256 at (508, 4) (w_extra read in place); rows_per_wg 32 at 32 767 pixels | 128 at 32 805, generic and register path
+#                                                        test_heads_groupnorm_widths_and_rows[<b>-<t>-<hw>-<C>-<c0>-<c1>-<groups>-<nchunk>]
+#   lfdm_linear_small_f32  K 1 | 63 | 64 | 65 | 129; N 1 | 4 | 5 | 7; GELU | SiLU | ReLU in, SiLU | GELU | ReLU | sigmoid out; without bias
+#                                                        test_linear_small_lanes_and_waves[<b>-<k>-<n>-<act_in>-<act_out>-<bias>]
+#   lfdm_sinusoidal_f32  dim 4 | 6 | 130 | 512         test_sinusoidal_widths[<dim>]
+#     t_stride 2; ldo = dim + 3                          test_sinusoidal_strided_timesteps_and_wide_rows
+#   lfdm_step_cond_f32 (exact)  1 | 771 | 280 000 elements (the stride loop behind the 1024-workgroup cap); first | last table row
+#                                                        test_step_cond_exact[<table_rows>-<b>-<n>-<which>]
+#   lfdm_conv2d_smalln_cl_f32  cout 1 (k 1, one pixel) | 4 (k 5, 17 x 15) | 2 (three channel chunks) | 3 (k 7, 3 x 50)
+#                                                        test_conv2d_smalln_filters_and_tiles[<cin>-<k>-<h>-<w>-<cout>-<n>]
+#   lfdm_avgpool2_cl_f32  one output pixel | row | column    test_avgpool2_ragged[<n>-<c>-<h>-<w>]
+#   lfdm_planar_to_cl_f32 + lfdm_cl_to_planar_f32 (exact)  1 x 1 | 33 x 31 | 31 x 65, ld = C + 3    test_transposes_ragged_exact[<n>-<c>-<hw>]
+#   lfdm_affine_act_cl_f32  ld 20 -> 16, none | ReLU | sigmoid | SiLU    test_affine_act_strided_rows[<act>]
+#     2 097 153 rows of 4 (one float4 past the 8192-workgroup cap)    test_affine_act_past_block_cap
+#   refused, nothing launched: even kernel edge, K = 245, cout 32, cin > cin_total | C 260, c0 + c1 516 | 2C 520, 2C % groups | cout 5, k 9, k 4, cin 24 |
+#     dim 2, 7 | odd h                                   test_refusals
+#     65 536 images (grid z of the transposes) | 65 536 rows (grid y of linear_small)    test_grid_limit_refusals
+#   NOT reached at a test-sized shape: avgpool2_kernel's 8192-workgroup cap (a 134 MB input).
 FRAME_EDGES = [1, 2, 16, 17, 32, 33, 40, 41, 48, 49, 64]
 
 

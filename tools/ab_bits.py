@@ -2,11 +2,11 @@
 """Same bits?  Runs a fixed list of calls on seeded inputs under ONE build of the kernels and writes one line per output tensor -
 name, shape, SHA-256 of its bytes - so that two builds (a refactor and its parent commit) can be compared line by line.
 
-    tools/ab_bits.py run OUT.txt [--emu [LIB]] [--set conv|attention|norm|sampler|glue]
+    tools/ab_bits.py run OUT.txt [--emu [LIB]] [--set conv|attention|norm|boundary|sampler|glue]
                                                          this process, the library LFDM_HIP_LIB names (default: the in-tree one) on the GPU,
                                                          or an emulator library on the CPU (default: the in-tree one)
     tools/ab_bits.py diff A.txt B.txt                    exit status 1 when any line differs or is missing
-    tools/ab_bits.py ab BASE_LIB OUT_DIR [--emu] [--new LIB] [--timeout S] [--set conv|attention|norm|sampler|glue]
+    tools/ab_bits.py ab BASE_LIB OUT_DIR [--emu] [--new LIB] [--timeout S] [--set conv|attention|norm|boundary|sampler|glue]
                                                          `run` under BASE_LIB, then under the in-tree library (or --new), each in a fresh child
                                                          process with its own time limit, one after the other; stops at the first non-zero
                                                          exit status; then `diff`
@@ -27,7 +27,8 @@ R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # norm: the GroupNorm / LayerNorm / BatchNorm kernels forward and backward, the heads kernels and the kernels that share csrc/norm_core.h;
 # attention: every entry point that goes through csrc/attn_core.h (the short-sequence core, the fused temporal kernels, the low-resolution
 # kernel), the long-sequence kernels beside them, the fast-math cases and the per-tile-order cases; sampler: every form of the sampler step (plain,
-# multistep, known frames, known elements, counter noise), the blends and the quantile kernels under them.
+# multistep, known frames, known elements, counter noise), the blends and the quantile kernels under them; boundary: the kernels on the way
+# into and out of the model (csrc/small.hip, csrc/conv_smalln.hip, the element-wise / layout kernels of csrc/norm.hip) at their launch-plan edges.
 SETS = {
     "conv": ([
         ("tests/test_ops_parity.py",
@@ -55,6 +56,13 @@ SETS = {
         ("tests/test_lfae_ops.py", "test_batchnorm_relu or test_batchnorm_relu_segments or test_batchnorm_fork_and_channel_slices"),
         ("tests/test_norm_edges.py", "test_layernorm or test_groupnorm or test_heads"),
     ], "not gpu_only and not bigTrue and not refuses"),
+    "boundary": ([
+        ("tests/test_boundary_edges.py",
+         "test_stem_conv or test_heads or test_linear_small or test_sinusoidal or test_step_cond or test_conv2d_smalln or test_avgpool2 or "
+         "test_transposes or test_affine_act"),
+        ("tests/test_ops_parity.py",
+         "test_linear_small_and_sinusoidal or test_conv_planar_in_and_heads or test_conv2d_smalln or test_elementwise_and_layout"),
+    ], "not gpu_only and not bigTrue and not refusals"),
     "sampler": ([
         ("tests/test_ops_parity.py", "test_sampler_step or test_abs_quantile"),
         ("tests/test_threshold_select.py", "test_threshold_select"),
