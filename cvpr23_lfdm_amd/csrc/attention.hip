@@ -245,7 +245,7 @@ __global__ __launch_bounds__(256) void linattn_output_kernel(const float* __rest
       o.z = fmaf(c.z, q[dd], o.z);
       o.w = fmaf(c.w, q[dd], o.w);
     }
-    reinterpret_cast<float4*>(op)[e4] = o;
+    lfdm_store_f4_out<LFDM_ST_LINATTN_OUT != 0>(op + 4 * e4, o);
   }
 }
 

@@ -27,8 +27,9 @@ __device__ __forceinline__ int64_t conv_out_row(const lfdm_conv_params& p, int i
 // out4 = act((v + bias) + residual), with stats(v + bias) in between: the value GroupNorm statistics are taken of.  `stats` is the
 // caller's (per-column gn_accum4, conditional or not; the scalar fold of conv_splitk_reduce_vec_kernel).  ACT = false: no activation code
 // at all (instantiations whose callers have none); true: the run-time code `act`.  ADDENDS_FIRST: act(v + (bias + residual)) - the
-// pointwise schedule, which has no statistics.
-template <bool ACT, bool ADDENDS_FIRST = false, class Stats>
+// pointwise schedule, which has no statistics.  THROUGH: the float4 leaves as a write-through store (lfdm_device.h, lfdm_store_f4_out;
+// each schedule passes its own LFDM_ST_* switch).
+template <bool ACT, bool ADDENDS_FIRST = false, bool THROUGH = false, class Stats>
 __device__ __forceinline__ void conv_finish4(float4 v, const float4& bias, const float4& residual, int act, float* out4, Stats&& stats) {
   if (ADDENDS_FIRST) {
     float4 br = bias;
@@ -45,11 +46,11 @@ __device__ __forceinline__ void conv_finish4(float4 v, const float4& bias, const
 #ifdef LFDM_PROBE_NOSTORE      // probe build only: everything but the store
   if (v.x == 123456.789f)
 #endif
-  *reinterpret_cast<float4*>(out4) = v;
+  lfdm_store_f4_out<THROUGH>(out4, v);
 }
-template <bool ACT, bool ADDENDS_FIRST = false>
+template <bool ACT, bool ADDENDS_FIRST = false, bool THROUGH = false>
 __device__ __forceinline__ void conv_finish4(const float4& v, const float4& bias, const float4& residual, int act, float* out4) {
-  conv_finish4<ACT, ADDENDS_FIRST>(v, bias, residual, act, out4, [](const float4&) {});
+  conv_finish4<ACT, ADDENDS_FIRST, THROUGH>(v, bias, residual, act, out4, [](const float4&) {});
 }
 
 // the same tail for one value of a row that is not float4-addressable (bias / residual read in place)

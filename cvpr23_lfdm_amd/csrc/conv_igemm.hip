@@ -435,7 +435,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(lfdm_conv_params p) {
             v.x = rs * (v.x - mu * ws.x); v.y = rs * (v.y - mu * ws.y);
             v.z = rs * (v.z - mu * ws.z); v.w = rs * (v.w - mu * ws.w);
           }
-          conv_finish4<true>(v, pre_b[j], pre_r[j][it], p.act, p.out + orow * p.ldo + colbase, [&](const float4& t) {
+          conv_finish4<true, false, LFDM_ST_IGEMM != 0>(v, pre_b[j], pre_r[j][it], p.act, p.out + orow * p.ldo + colbase, [&](const float4& t) {
             if (p.gn_partial) gn_accum4(t, gs[j], gq[j]);
           });
         } else {
@@ -571,7 +571,7 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_vec_kernel(lfdm_conv_p
     float4 s = v[0];
 #pragma unroll
     for (int z = 1; z < KS; ++z) { s.x += v[z].x; s.y += v[z].y; s.z += v[z].z; s.w += v[z].w; }
-    conv_finish4<true>(s, bb, rr, p.act, p.out + (int64_t)m * p.ldo + col, [&](const float4& t) {      // (one accumulator per thread, not per column)
+    conv_finish4<true, false, LFDM_ST_IGEMM != 0>(s, bb, rr, p.act, p.out + (int64_t)m * p.ldo + col, [&](const float4& t) {      // (one accumulator per thread, not per column)
       gs += (t.x + t.y) + (t.z + t.w);
       gq += (t.x * t.x + t.y * t.y) + (t.z * t.z + t.w * t.w);
     });

@@ -279,7 +279,7 @@ __global__ __launch_bounds__(256) void conv_ksw_kernel(lfdm_conv_params p) {
 #ifdef LFDM_PROBE_NOSTORE
           if (v.x == 123456.789f)
 #endif
-          *reinterpret_cast<float4*>(p.out + orow * p.ldo + colbase) = v;
+          lfdm_store_f4_out<LFDM_ST_KSW != 0>(p.out + orow * p.ldo + colbase, v);
         }
       }
       __syncthreads();

@@ -244,7 +244,7 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(lfdm_conv_params p, int gx
         rr.x = silu_fast_(fmaf(rr.x, ga.x, gb.x)); rr.y = silu_fast_(fmaf(rr.y, ga.y, gb.y));
         rr.z = silu_fast_(fmaf(rr.z, ga.z, gb.z)); rr.w = silu_fast_(fmaf(rr.w, ga.w, gb.w));
       }
-      conv_finish4<true, true>(v, pre_b[g * TN + j], rr, p.act, p.out + (int64_t)orow * p.ldo + col);      // v + (bias + residual): this schedule alone
+      conv_finish4<true, true, LFDM_ST_PW != 0>(v, pre_b[g * TN + j], rr, p.act, p.out + (int64_t)orow * p.ldo + col);      // v + (bias + residual): this schedule alone
     }
   }
 }

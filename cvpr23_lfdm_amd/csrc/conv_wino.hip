@@ -401,8 +401,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv_wino_kernel(lfdm_co
             acc4.x += v.x; acc4.y += v.y; acc4.z += v.z; acc4.w += v.w;
           }
           const int64_t prow = ((int64_t)n * th + my_ty) * tw + my_tx;
-          *reinterpret_cast<float4*>(p.out + prow * p.ldo + co) =
-              make_float4(0.25f * acc4.x, 0.25f * acc4.y, 0.25f * acc4.z, 0.25f * acc4.w);
+          lfdm_store_f4_out<LFDM_ST_WINO != 0>(p.out + prow * p.ldo + co, make_float4(0.25f * acc4.x, 0.25f * acc4.y, 0.25f * acc4.z, 0.25f * acc4.w));
         }
         continue;
       }
@@ -417,7 +416,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv_wino_kernel(lfdm_co
             *reinterpret_cast<float4*>(p.partial + ((int64_t)bz * M + orow) * p.coutp + co) = y[q];
           }
         } else if (co < p.cout) {
-          conv_finish4<ACT>(y[q], bb, res[q], p.act, p.out + orow * p.ldo + co, [&](const float4& t) { gn_accum4(t, gs[ct], gq[ct]); });
+          conv_finish4<ACT, false, LFDM_ST_WINO != 0>(y[q], bb, res[q], p.act, p.out + orow * p.ldo + co, [&](const float4& t) { gn_accum4(t, gs[ct], gq[ct]); });
         }
       }
     }
@@ -490,7 +489,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void conv_wino_kernel(lfdm_co
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int64_t orow = orow0 + (q >> 1) * p.wq + (q & 1);
-        conv_finish4<true>(v[q], bb, res[q], p.act, p.out + orow * p.ldo + co, [&](const float4& t) { gn_accum4(t, gs[0], gq[0]); });      // (any activation at run time)
+        conv_finish4<true, false, LFDM_ST_WINO != 0>(v[q], bb, res[q], p.act, p.out + orow * p.ldo + co, [&](const float4& t) { gn_accum4(t, gs[0], gq[0]); });      // (any activation at run time)
       }
     }
   }

@@ -427,7 +427,7 @@ __global__ __launch_bounds__(256, 2) void linattn_fused_out2_kernel(const float*
         const float4 u = *reinterpret_cast<const float4*>(s_y + (w4 * 32 + tok) * LDY + c);
         v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
       }
-      *reinterpret_cast<float4*>(out + row * ldo + c) = v;
+      lfdm_store_f4_out<LFDM_ST_LINATTN_FUSED != 0>(out + row * ldo + c, v);
     }
   }
 }

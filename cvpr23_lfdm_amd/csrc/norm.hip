@@ -143,7 +143,7 @@ __global__ __launch_bounds__(NT) void gn_apply_kernel(
     float4 y = fma4(v, a, d);
     if (silu) y = map4([](float e) { return silu_fast_(e); }, y);
     if (rb) add4(y, k == 0 ? pre_r[0] : k == 1 ? pre_r[1] : rb[i]);
-    ob[i] = y;
+    lfdm_store_f4_out<LFDM_ST_GN != 0>(reinterpret_cast<float*>(ob + i), y);
   }
 }
 
