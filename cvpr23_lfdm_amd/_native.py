@@ -139,6 +139,20 @@ class SamplerStepParams(C.Structure):
     ]
 
 
+class TrainMask(C.Structure):
+    _fields_ = [("frame_mask", C.c_void_p), ("elem_mask", C.c_void_p), ("frames", i32), ("frame_elems", i64)]
+
+
+class TrainLossParams(C.Structure):
+    _fields_ = [
+        ("objective", i32), ("loss_type", i32), ("x_start", f32p), ("noise", f32p), ("out", f32p), ("x_noisy", f32p),
+        ("t", C.c_void_p), ("a_tab", f32p), ("s_tab", f32p), ("r_tab", f32p), ("m_tab", f32p), ("w_tab", f32p), ("t_len", i32),
+        ("mask", TrainMask), ("batch", i32), ("n", i64),
+        ("loss", f32p), ("inv_count", f32p), ("sample_loss", f32p), ("pred_x0", f32p), ("gout", f32p), ("dout", f32p),
+        ("ws", C.c_void_p), ("ws_bytes", sz), ("ticket", C.c_void_p),
+    ]
+
+
 BN_TICKETS = 1024
 OPTIM_PLAN_BYTES = 64      # LFDM_OPTIM_PLAN_BYTES: lfdm_optim_plan = [apply i32 | - | clip_coef, total_norm, bias1, bias2_sqrt, ema_decay, 1 - ema_decay f32 | applied_steps, skipped_steps i64 | -]
 
@@ -286,17 +300,11 @@ _SIGNATURES = {
     "lfdm_relu_bwd_f32": (i32, [f32p, f32p, f32p, i64, stream_t]),
     "lfdm_l1_mean_fwd_f32": (i32, [f32p, f32p, i64, f32, f32p, C.c_void_p, sz, C.c_void_p, stream_t]),
     "lfdm_l1_mean_bwd_f32": (i32, [f32p, f32p, i64, f32, f32p, f32p, stream_t]),
-    # ---- DM training with known frames / elements held clean (additive, ABI stays 13)
-    "lfdm_train_qsample_f32": (i32, [f32p, f32p, C.c_void_p, f32p, f32p, i32, C.c_void_p, C.c_void_p, i32, i64, f32p, i32, i64, stream_t]),
+    # ---- the diffusion edge of DM training: known frames / elements, objectives, loss weights (ABI 14)
+    "lfdm_train_qsample_f32": (i32, [f32p, f32p, C.c_void_p, f32p, f32p, i32, C.POINTER(TrainMask), f32p, i32, i64, stream_t]),
     "lfdm_masked_loss_ws_bytes": (sz, [i32, i64]),
-    "lfdm_masked_loss_fwd_f32": (i32, [f32p, f32p, f32p, C.c_void_p, f32p, f32p, i32, C.c_void_p, C.c_void_p, i32, i64, i32, f32p, f32p, f32p,
-                                       i32, i64, C.c_void_p, sz, C.c_void_p, stream_t]),
-    "lfdm_masked_loss_bwd_f32": (i32, [f32p, f32p, C.c_void_p, C.c_void_p, i32, i64, i32, f32p, f32p, f32p, i32, i64, stream_t]),
-    # ---- training objectives and loss weights (additive, ABI stays 13)
-    "lfdm_objective_loss_fwd_f32": (i32, [i32, f32p, f32p, f32p, f32p, C.c_void_p, f32p, f32p, f32p, f32p, f32p, i32, C.c_void_p, C.c_void_p,
-                                          i32, i64, i32, f32p, f32p, f32p, f32p, i32, i64, C.c_void_p, sz, C.c_void_p, stream_t]),
-    "lfdm_objective_loss_bwd_f32": (i32, [i32, f32p, f32p, f32p, C.c_void_p, f32p, f32p, f32p, i32, C.c_void_p, C.c_void_p, i32, i64, i32,
-                                          f32p, f32p, f32p, i32, i64, stream_t]),
+    "lfdm_objective_loss_fwd_f32": (i32, [C.POINTER(TrainLossParams), stream_t]),
+    "lfdm_objective_loss_bwd_f32": (i32, [C.POINTER(TrainLossParams), stream_t]),
     # ---- progressive distillation: per-sample teacher step and target (additive, ABI stays 13)
     "lfdm_distill_x0_f32": (i32, [f32p, f32p, f32p, C.c_void_p, i32, f32p, i32, i64, stream_t]),
     "lfdm_distill_step_f32": (i32, [f32p, f32p, f32p, C.c_void_p, i32, f32p, f32p, f32p, f32p, C.c_void_p, i32, f32p, f32p, i32, i64, stream_t]),

@@ -27,7 +27,7 @@ __device__ __forceinline__ float row_x0(float x, float o, float cx, float ce) {
 }
 
 __device__ __forceinline__ float4 row_x0_4(float4 x, float4 o, float cx, float ce) {
-  return make_float4(row_x0(x.x, o.x, cx, ce), row_x0(x.y, o.y, cx, ce), row_x0(x.z, o.z, cx, ce), row_x0(x.w, o.w, cx, ce));
+  return map4(x, o, [cx, ce](float xe, float oe) { return row_x0(xe, oe, cx, ce); });
 }
 
 // (x, x0 not __restrict__: nothing forbids x0 == x, each element is read by its owner before it is written)
@@ -39,7 +39,7 @@ __global__ __launch_bounds__(TD_BLOCK) void distill_x0_kernel(const float* x, co
   const float cx = c[0], ce = c[1];
   const bool use_x = cx != 0.f, use_o = ce != 0.f;
   const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (unsigned q0 = blockIdx.x * (TD_BLOCK * TD_QUADS) + threadIdx.x; q0 < n4; q0 += gridDim.x * (TD_BLOCK * TD_QUADS)) {
+  for (unsigned q0 = trip_first(); q0 < n4; q0 += trip_stride()) {
     const Trip sl = trip_slots(q0, n4);
     float4 xv[TD_QUADS], ov[TD_QUADS];
 #pragma unroll
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(TD_BLOCK) void distill_step_kernel(const float* x, 
   if (thr) r.s = fmaxf(thr[b], 1.0f);
   const bool use_x = r.cx != 0.f || r.k_x != 0.f, use_o = r.ce != 0.f || r.k_eps != 0.f;
   const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (unsigned q0 = blockIdx.x * (TD_BLOCK * TD_QUADS) + threadIdx.x; q0 < n4; q0 += gridDim.x * (TD_BLOCK * TD_QUADS)) {
+  for (unsigned q0 = trip_first(); q0 < n4; q0 += trip_stride()) {
     const Trip sl = trip_slots(q0, n4);
     float4 xv[TD_QUADS], ov[TD_QUADS], rv[TD_QUADS];
 #pragma unroll

@@ -19,7 +19,23 @@ __device__ __forceinline__ int table_index(const int64_t* t, unsigned b, int t_l
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 
-// what the kernels' loops share: the float4 slots of this lane in the current trip
+// a float4 that is loaded only where `in` holds (outside the sample, or an operand the kernel does not use: zeros, no address formed)
+__device__ __forceinline__ float4 ld4_if(bool in, const float* p, size_t at) { return in ? ld4(p + at) : make_float4(0.f, 0.f, 0.f, 0.f); }
+
+// per component: bit k of `bits` set ? a : b
+__device__ __forceinline__ float4 select4(unsigned bits, float4 a, float4 b) {
+  return make_float4((bits & 1u) ? a.x : b.x, (bits & 2u) ? a.y : b.y, (bits & 4u) ? a.z : b.z, (bits & 8u) ? a.w : b.w);
+}
+// f(a, b) per component
+template <class F>
+__device__ __forceinline__ float4 map4(float4 a, float4 b, F f) {
+  return make_float4(f(a.x, b.x), f(a.y, b.y), f(a.z, b.z), f(a.w, b.w));
+}
+
+// what the kernels' loops share: the grid-stride trips of a sample's workgroups (for (q0 = trip_first(); q0 < n4; q0 += trip_stride())) and
+// the float4 slots of this lane in the current trip
+__device__ __forceinline__ unsigned trip_first() { return blockIdx.x * (TD_BLOCK * TD_QUADS) + threadIdx.x; }
+__device__ __forceinline__ unsigned trip_stride() { return gridDim.x * (TD_BLOCK * TD_QUADS); }
 struct Trip {
   unsigned q[TD_QUADS];
   bool in[TD_QUADS];

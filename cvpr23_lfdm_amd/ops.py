@@ -1107,7 +1107,9 @@ def known_blend_elem(x, known, known_noise, elem_mask, a, s):
 # ---------------------------------------------------------------------------------------------
 
 LOSS_TYPES = {"l1": 0, "l2": 1}         # LFDM_LOSS_L1 / LFDM_LOSS_L2
-_LOSS_TICKETS = {}                      # device -> the zeroed ticket word lfdm_masked_loss_fwd_f32 leaves zeroed
+OBJECTIVES = {"pred_noise": 0, "pred_x0": 1, "pred_v": 2}           # LFDM_OBJ_NOISE / _X0 / _V
+_OBJECTIVE_NEEDS = {"pred_noise": ("noise",), "pred_x0": ("x_start",), "pred_v": ("x_start", "noise")}
+_LOSS_TICKETS = {}                      # device -> the zeroed ticket word lfdm_objective_loss_fwd_f32 leaves zeroed
 
 
 def _train_operands(what, lib, like, floats, t=None, tables=()):
@@ -1130,12 +1132,12 @@ def _train_operands(what, lib, like, floats, t=None, tables=()):
 
 
 def _train_mask(what, x, frame_mask, elem_mask, frames):
-    """(frame_mask pointer, elem_mask pointer, frames, frame_elems) of the three mask forms: none | frame_mask (B, frames) | elem_mask of
-    x's shape; bool or uint8, used as bytes.  A frame of a planar (B, C, T, ...) operand is everything behind T, of (B, C * T, hw) one row."""
+    """lfdm_train_mask of the three mask forms: none | frame_mask (B, frames) | elem_mask of x's shape; bool or uint8, used as bytes.  A
+    frame of a planar (B, C, T, ...) operand is everything behind T, of (B, C * T, hw) one row."""
     if frame_mask is None and elem_mask is None:
         if frames is not None:
             raise ValueError("%s: frames needs frame_mask" % what)
-        return None, None, 0, 0
+        return _native.TrainMask()
     if frame_mask is not None and elem_mask is not None:
         raise ValueError("%s: frame_mask and elem_mask exclude each other" % what)
     mask = frame_mask if elem_mask is None else elem_mask
@@ -1148,12 +1150,12 @@ def _train_mask(what, x, frame_mask, elem_mask, frames):
             raise ValueError("%s: elem_mask has no frame split" % what)
         if tuple(elem_mask.shape) != tuple(x.shape):
             raise ValueError("%s: elem_mask must have the operands' shape %s, got %s" % (what, tuple(x.shape), tuple(elem_mask.shape)))
-        return None, _p(elem_mask), 0, 0
+        return _native.TrainMask(elem_mask=_p(elem_mask))
     if x.dim() >= 4:
         frames = x.shape[2] if frames is None else int(frames)
         if x.shape[2] != frames:
             raise ValueError("%s: the operands have %d frames, frames = %d" % (what, x.shape[2], frames))
-        frame_elems = x[0, 0, 0].numel()
+        frame_elems = n // (x.shape[1] * frames)              # (everything behind T, without three views to count it)
     elif x.dim() == 3 and frames is not None:
         frames, frame_elems = int(frames), x.shape[2]
     else:
@@ -1162,7 +1164,7 @@ def _train_mask(what, x, frame_mask, elem_mask, frames):
         raise ValueError("%s: %d elements per sample are no multiple of %d frames x %d" % (what, n, frames, frame_elems))
     if tuple(frame_mask.shape) != (batch, frames):
         raise ValueError("%s: frame_mask must be (%d, %d), got %s" % (what, batch, frames, tuple(frame_mask.shape)))
-    return _p(frame_mask), None, frames, frame_elems
+    return _native.TrainMask(_p(frame_mask), None, frames, frame_elems)
 
 
 def _loss_code(what, loss_type):
@@ -1186,70 +1188,93 @@ def train_qsample(x_start, noise, t, a_tab, s_tab, *, frame_mask=None, elem_mask
     lib = _lib()
     out = _train_dest("train_qsample", out, x_start.shape, x_start)
     batch, n = _train_operands("train_qsample", lib, x_start, dict(x_start=x_start, noise=noise, out=out), t, (a_tab, s_tab))
-    fm, em, frames, frame_elems = _train_mask("train_qsample", x_start, frame_mask, elem_mask, frames)
-    lib.check(lib.lfdm_train_qsample_f32(_p(x_start), _p(noise), _p(t), _p(a_tab), _p(s_tab), a_tab.numel(), fm, em, frames, frame_elems,
-                                         _p(out), batch, n, _stream(lib)), "lfdm_train_qsample_f32")
+    mask = _train_mask("train_qsample", x_start, frame_mask, elem_mask, frames)
+    lib.check(lib.lfdm_train_qsample_f32(_p(x_start), _p(noise), _p(t), _p(a_tab), _p(s_tab), a_tab.numel(), C.byref(mask), _p(out), batch, n,
+                                         _stream(lib)), "lfdm_train_qsample_f32")
     return out
+
+
+def _addr(t):
+    return None if t is None else t.data_ptr()          # (a pointer field of a ctypes struct takes the integer)
+
+
+def _loss_params(what, lib, objective, loss_type, x_start, noise, out, floats, t, a_tab, s_tab, r_tab, m_tab, w_tab):
+    """What the two directions of the loss share -> lfdm_train_loss_params with the objective, the checked (B, ...) operands (`floats`: what
+    the caller calls them -> tensor, `out` among them), t and the tables filled in.  x_start / noise may be None where the objective does not
+    use them (they are never read); a table that is None stays null (w_tab None: weight 1; the masked backward reads none and has no t)."""
+    code = _loss_code(what, loss_type)
+    if objective not in OBJECTIVES:
+        raise ValueError("%s: objective must be one of %s, got %r" % (what, tuple(OBJECTIVES), objective))
+    floats.update({k: v for k, v in (("x_start", x_start), ("noise", noise)) if v is not None})
+    missing = [k for k in _OBJECTIVE_NEEDS[objective] if k not in floats]
+    if missing:
+        raise ValueError("%s: objective %r needs %s (pred_noise: noise; pred_x0: x_start; pred_v: x_start and noise)"
+                         % (what, objective, " and ".join(missing)))
+    tables = tuple(v for v in (a_tab, s_tab, r_tab, m_tab, w_tab) if v is not None)
+    batch, n = _train_operands(what, lib, out, floats, t, tables)
+    return _native.TrainLossParams(objective=OBJECTIVES[objective], loss_type=code, x_start=_addr(x_start), noise=_addr(noise), out=_addr(out),
+                                   t=_addr(t), a_tab=_addr(a_tab), s_tab=_addr(s_tab), r_tab=_addr(r_tab), m_tab=_addr(m_tab), w_tab=_addr(w_tab),
+                                   t_len=tables[0].numel() if tables else 0, batch=batch, n=n)
+
+
+def _loss_fwd(what, objective, x_start, noise, out, floats, x_noisy, t, a_tab, s_tab, r_tab, m_tab, w_tab, loss_type, frame_mask, elem_mask, frames,
+              loss, inv_count, sample_loss, pred_x0, means=True):
+    """The one forward behind masked_loss_fwd and objective_loss_fwd -> (loss, inv_count, sample_loss, pred_x0).  means=False: the per-sample
+    means go to scratch behind the workspace (sample_loss is a required output of the kernel) and None comes back in their place."""
+    lib = _lib()
+    pred_x0 = _train_dest(what, pred_x0, out.shape, out)
+    floats.update(x_noisy=x_noisy, pred_x0=pred_x0)
+    p = _loss_params(what, lib, objective, loss_type, x_start, noise, out, floats, t, a_tab, s_tab, r_tab, m_tab, w_tab)
+    batch = p.batch
+    loss, inv_count = _train_dest(what, loss, (1,), out), _train_dest(what, inv_count, (batch,), out)
+    if means:
+        sample_loss = _train_dest(what, sample_loss, (batch,), out)
+    p.mask = _train_mask(what, out, frame_mask, elem_mask, frames)
+    nbytes = lib.lfdm_masked_loss_ws_bytes(batch, p.n)
+    ws = torch.empty(nbytes // 8 + (0 if means else (batch + 1) // 2), dtype=torch.int64, device=out.device)
+    ticket = _LOSS_TICKETS.get(out.device)
+    if ticket is None:
+        ticket = _LOSS_TICKETS[out.device] = torch.zeros(1, dtype=torch.int32, device=out.device)
+    p.x_noisy, p.loss, p.inv_count, p.pred_x0 = x_noisy.data_ptr(), loss.data_ptr(), inv_count.data_ptr(), pred_x0.data_ptr()
+    p.sample_loss = sample_loss.data_ptr() if means else ws.data_ptr() + nbytes
+    p.ws, p.ws_bytes, p.ticket = ws.data_ptr(), nbytes, ticket.data_ptr()
+    lib.check(lib.lfdm_objective_loss_fwd_f32(C.byref(p), _stream(lib)), "lfdm_objective_loss_fwd_f32")
+    return loss, inv_count, sample_loss, pred_x0
+
+
+def _loss_bwd(what, objective, x_start, noise, out, floats, t, a_tab, s_tab, w_tab, inv_count, gout, loss_type, frame_mask, elem_mask, frames,
+              dout):
+    """The one backward behind masked_loss_bwd and objective_loss_bwd -> d loss / d out."""
+    lib = _lib()
+    dout = _train_dest(what, dout, out.shape, out)
+    floats.update(dout=dout)
+    p = _loss_params(what, lib, objective, loss_type, x_start, noise, out, floats, t, a_tab, s_tab, None, None, w_tab)
+    for name, v, count in (("inv_count", inv_count, p.batch), ("gout", gout, 1)):
+        if not torch.is_tensor(v) or v.dtype != torch.float32 or v.numel() != count or not v.is_contiguous() or v.device != out.device:
+            raise ValueError("%s: %s must be a contiguous float32 tensor of %d element(s) on the operands' device" % (what, name, count))
+    p.mask = _train_mask(what, out, frame_mask, elem_mask, frames)
+    p.inv_count, p.gout, p.dout = inv_count.data_ptr(), gout.data_ptr(), dout.data_ptr()
+    lib.check(lib.lfdm_objective_loss_bwd_f32(C.byref(p), _stream(lib)), "lfdm_objective_loss_bwd_f32")
+    return dout
 
 
 def masked_loss_fwd(noise, pred, x_noisy, t, r_tab, m_tab, *, loss_type="l1", frame_mask=None, elem_mask=None, frames=None, loss=None,
                     inv_count=None, pred_x0=None):
-    """lfdm_masked_loss_fwd_f32 -> (loss (1,), inv_count (B,), pred_x0): loss = (1 / B) sum_b S_b / max(N_b, 1) with S_b the sum of
-    |noise - pred| ('l2': squared) over the UNKNOWN elements of sample b and N_b their number; inv_count[b] = 1 / max(N_b, 1) (the
-    backward's operand); pred_x0 = r_tab[t_b] * x_noisy - m_tab[t_b] * pred, x_noisy where known (r_tab / m_tab: sqrt_recip_alphas_cumprod /
-    sqrt_recipm1_alphas_cumprod).  Fixed summation order: the same bits on every run."""
-    lib = _lib()
-    code = _loss_code("masked_loss_fwd", loss_type)
-    pred_x0 = _train_dest("masked_loss_fwd", pred_x0, noise.shape, noise)
-    batch, n = _train_operands("masked_loss_fwd", lib, noise, dict(noise=noise, pred=pred, x_noisy=x_noisy, pred_x0=pred_x0), t, (r_tab, m_tab))
-    loss = _train_dest("masked_loss_fwd", loss, (1,), noise)
-    inv_count = _train_dest("masked_loss_fwd", inv_count, (batch,), noise)
-    fm, em, frames, frame_elems = _train_mask("masked_loss_fwd", noise, frame_mask, elem_mask, frames)
-    nbytes = lib.lfdm_masked_loss_ws_bytes(batch, n)
-    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=noise.device)
-    ticket = _LOSS_TICKETS.get(noise.device)
-    if ticket is None:
-        ticket = _LOSS_TICKETS[noise.device] = torch.zeros(1, dtype=torch.int32, device=noise.device)
-    lib.check(lib.lfdm_masked_loss_fwd_f32(_p(noise), _p(pred), _p(x_noisy), _p(t), _p(r_tab), _p(m_tab), r_tab.numel(), fm, em, frames, frame_elems,
-                                           code, _p(loss), _p(inv_count), _p(pred_x0), batch, n, _p(ws), nbytes, _p(ticket), _stream(lib)),
-              "lfdm_masked_loss_fwd_f32")
+    """The masked loss (lfdm_objective_loss_fwd_f32 with LFDM_OBJ_NOISE and no weights) -> (loss (1,), inv_count (B,), pred_x0): loss =
+    (1 / B) sum_b S_b / max(N_b, 1) with S_b the sum of |noise - pred| ('l2': squared) over the UNKNOWN elements of sample b and N_b their
+    number; inv_count[b] = 1 / max(N_b, 1) (the backward's operand); pred_x0 = r_tab[t_b] * x_noisy - m_tab[t_b] * pred, x_noisy where known
+    (r_tab / m_tab: sqrt_recip_alphas_cumprod / sqrt_recipm1_alphas_cumprod).  Fixed summation order: the same bits on every run."""
+    loss, inv_count, _, pred_x0 = _loss_fwd("masked_loss_fwd", "pred_noise", None, noise, pred, dict(pred=pred), x_noisy, t, None, None, r_tab, m_tab,
+                                            None, loss_type, frame_mask, elem_mask, frames, loss, inv_count, None, pred_x0, means=False)
     return loss, inv_count, pred_x0
 
 
 def masked_loss_bwd(noise, pred, inv_count, gout, *, loss_type="l1", frame_mask=None, elem_mask=None, frames=None, out=None):
-    """lfdm_masked_loss_bwd_f32: dpred = -sign(noise - pred) * gout * inv_count[b] / B ('l2': 2 (pred - noise) in place of the sign), exactly
-    0.0 at every known element.  gout: one float32 on the device (read there)."""
-    lib = _lib()
-    code = _loss_code("masked_loss_bwd", loss_type)
-    out = _train_dest("masked_loss_bwd", out, noise.shape, noise)
-    batch, n = _train_operands("masked_loss_bwd", lib, noise, dict(noise=noise, pred=pred, out=out))
-    for name, v, count in (("inv_count", inv_count, batch), ("gout", gout, 1)):
-        if not torch.is_tensor(v) or v.dtype != torch.float32 or v.numel() != count or not v.is_contiguous() or v.device != noise.device:
-            raise ValueError("masked_loss_bwd: %s must be a contiguous float32 tensor of %d element(s) on the operands' device" % (name, count))
-    fm, em, frames, frame_elems = _train_mask("masked_loss_bwd", noise, frame_mask, elem_mask, frames)
-    lib.check(lib.lfdm_masked_loss_bwd_f32(_p(noise), _p(pred), fm, em, frames, frame_elems, code, _p(inv_count), _p(gout), _p(out), batch, n,
-                                           _stream(lib)), "lfdm_masked_loss_bwd_f32")
-    return out
-
-
-OBJECTIVES = {"pred_noise": 0, "pred_x0": 1, "pred_v": 2}           # LFDM_OBJ_NOISE / _X0 / _V
-_OBJECTIVE_NEEDS = {"pred_noise": ("noise",), "pred_x0": ("x_start",), "pred_v": ("x_start", "noise")}
-
-
-def _objective_operands(what, lib, objective, x_start, noise, floats, t, tables, w_tab):
-    """The objective's code and (batch, n, table length): an operand the objective does not use may be None (it is never read); the
-    weight table is optional (None: weight 1)."""
-    if objective not in OBJECTIVES:
-        raise ValueError("%s: objective must be one of %s, got %r" % (what, tuple(OBJECTIVES), objective))
-    given = dict(x_start=x_start, noise=noise)
-    missing = [k for k in _OBJECTIVE_NEEDS[objective] if given[k] is None]
-    if missing:
-        raise ValueError("%s: objective %r needs %s (pred_noise: noise; pred_x0: x_start; pred_v: x_start and noise)"
-                         % (what, objective, " and ".join(missing)))
-    floats = dict({k: v for k, v in given.items() if v is not None}, **floats)
-    tables = tuple(tables) + (() if w_tab is None else (w_tab,))
-    batch, n = _train_operands(what, lib, floats["out"], floats, t, tables)
-    return OBJECTIVES[objective], batch, n, tables[0].numel()
+    """The masked loss's backward (lfdm_objective_loss_bwd_f32 with LFDM_OBJ_NOISE and no weights): dpred = -sign(noise - pred) * gout *
+    inv_count[b] / B ('l2': 2 (pred - noise) in place of the sign), exactly 0.0 at every known element.  gout: one float32 on the device
+    (read there)."""
+    return _loss_bwd("masked_loss_bwd", "pred_noise", None, noise, pred, dict(pred=pred), None, None, None, None, inv_count, gout, loss_type,
+                     frame_mask, elem_mask, frames, out)
 
 
 def objective_loss_fwd(objective, x_start, noise, out, x_noisy, t, a_tab, s_tab, r_tab, m_tab, w_tab=None, *, loss_type="l1", frame_mask=None,
@@ -1259,25 +1284,8 @@ def objective_loss_fwd(objective, x_start, noise, out, x_noisy, t, a_tab, s_tab,
     "pred_v", pred_x0 = r * x_noisy - m * out | out | a * x_noisy - s * out (x_noisy where known) - with the per-timestep weight w_tab[t_b]
     (None: 1) on each sample's mean: loss = (1 / B) sum_b w_b S_b / max(N_b, 1); sample_loss[b] = S_b / max(N_b, 1), unweighted.  x_start
     ("pred_noise") / noise ("pred_x0") may be None and are never read.  "pred_noise" without w_tab: the bits of masked_loss_fwd."""
-    lib = _lib()
-    what = "objective_loss_fwd"
-    code = _loss_code(what, loss_type)
-    pred_x0 = _train_dest(what, pred_x0, out.shape, out)
-    obj, batch, n, t_len = _objective_operands(what, lib, objective, x_start, noise, dict(out=out, x_noisy=x_noisy, pred_x0=pred_x0), t,
-                                               (a_tab, s_tab, r_tab, m_tab), w_tab)
-    loss = _train_dest(what, loss, (1,), out)
-    inv_count = _train_dest(what, inv_count, (batch,), out)
-    sample_loss = _train_dest(what, sample_loss, (batch,), out)
-    fm, em, frames, frame_elems = _train_mask(what, out, frame_mask, elem_mask, frames)
-    nbytes = lib.lfdm_masked_loss_ws_bytes(batch, n)
-    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=out.device)
-    ticket = _LOSS_TICKETS.get(out.device)
-    if ticket is None:
-        ticket = _LOSS_TICKETS[out.device] = torch.zeros(1, dtype=torch.int32, device=out.device)
-    lib.check(lib.lfdm_objective_loss_fwd_f32(obj, _p(x_start), _p(noise), _p(out), _p(x_noisy), _p(t), _p(a_tab), _p(s_tab), _p(r_tab), _p(m_tab),
-                                              _p(w_tab), t_len, fm, em, frames, frame_elems, code, _p(loss), _p(inv_count), _p(sample_loss),
-                                              _p(pred_x0), batch, n, _p(ws), nbytes, _p(ticket), _stream(lib)), "lfdm_objective_loss_fwd_f32")
-    return loss, inv_count, sample_loss, pred_x0
+    return _loss_fwd("objective_loss_fwd", objective, x_start, noise, out, dict(out=out), x_noisy, t, a_tab, s_tab, r_tab, m_tab, w_tab, loss_type,
+                     frame_mask, elem_mask, frames, loss, inv_count, sample_loss, pred_x0)
 
 
 def objective_loss_bwd(objective, x_start, noise, out, t, a_tab, s_tab, w_tab, inv_count, gout, *, loss_type="l1", frame_mask=None,
@@ -1285,19 +1293,8 @@ def objective_loss_bwd(objective, x_start, noise, out, t, a_tab, s_tab, w_tab, i
     """lfdm_objective_loss_bwd_f32: d loss / d out = c_b * d |target - out| / d out with c_b = ((gout * inv_count[b]) * w_tab[t_b]) / B in
     fp32 (w_tab None: no product), the target recomputed from x_start / noise; exactly 0.0 at every known element.  "pred_noise" without
     w_tab: the bits of masked_loss_bwd."""
-    lib = _lib()
-    what = "objective_loss_bwd"
-    code = _loss_code(what, loss_type)
-    dout = _train_dest(what, dout, out.shape, out)
-    obj, batch, n, t_len = _objective_operands(what, lib, objective, x_start, noise, dict(out=out, dout=dout), t, (a_tab, s_tab), w_tab)
-    for name, v, count in (("inv_count", inv_count, batch), ("gout", gout, 1)):
-        if not torch.is_tensor(v) or v.dtype != torch.float32 or v.numel() != count or not v.is_contiguous() or v.device != out.device:
-            raise ValueError("%s: %s must be a contiguous float32 tensor of %d element(s) on the operands' device" % (what, name, count))
-    fm, em, frames, frame_elems = _train_mask(what, out, frame_mask, elem_mask, frames)
-    lib.check(lib.lfdm_objective_loss_bwd_f32(obj, _p(x_start), _p(noise), _p(out), _p(t), _p(a_tab), _p(s_tab), _p(w_tab), t_len, fm, em, frames,
-                                              frame_elems, code, _p(inv_count), _p(gout), _p(dout), batch, n, _stream(lib)),
-              "lfdm_objective_loss_bwd_f32")
-    return dout
+    return _loss_bwd("objective_loss_bwd", objective, x_start, noise, out, dict(out=out), t, a_tab, s_tab, w_tab, inv_count, gout, loss_type,
+                     frame_mask, elem_mask, frames, dout)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -929,69 +929,67 @@ int lfdm_l1_mean_fwd_f32(const float* x, const float* y, int64_t n, float weight
                          lfdm_stream_t stream);
 int lfdm_l1_mean_bwd_f32(const float* x, const float* y, int64_t n, float weight, const float* gout, float* dx, lfdm_stream_t stream);
 
-/* The diffusion edge of the DM training step with known frames / elements held clean (additive, ABI version unchanged; DESIGN.md 4.12,
- * csrc/train_diffusion.hip).  Samples are dense rows of n floats (n % 4 == 0, n < 2^31); t: (B) int64 ON THE DEVICE, clamped to
- * [0, t_len) by the kernels; the tables are the registered fp32 buffers of t_len entries, read on the device.  Mask forms, as in the
- * known operands of the sampler step: none (both masks NULL, frames = frame_elems = 0) | frame_mask: (B, frames) bytes, non-zero = frame
+/* The diffusion edge of the DM training step with known frames / elements held clean (ABI 14: one mask struct, one loss params struct;
+ * DESIGN.md 4.12, 4.14, csrc/train_diffusion.hip).  Samples are dense rows of n floats (n % 4 == 0, n < 2^31); t: (B) int64 ON THE DEVICE,
+ * clamped to [0, t_len) by the kernels; the tables are the registered fp32 buffers of t_len entries, read on the device.  Mask forms, as in
+ * the known operands of the sampler step: none (both masks NULL, frames = frame_elems = 0) | frame_mask: (B, frames) bytes, non-zero = frame
  * (i / frame_elems) % frames of sample b is known, n a multiple of frames * frame_elems, frame_elems % 4 == 0 | elem_mask: (B, n) bytes,
  * 4-byte aligned, frames = frame_elems = 0.  No floating-point atomics, fixed summation order: two runs give the same bits.
  * Refusals (LFDM_EINVAL, nothing is enqueued): a null operand, n % 4 != 0, both masks, a frame split without frame_mask or one that does
- * not divide n or whose frames are no multiple of 4 elements, t_len <= 0, loss_type outside { LFDM_LOSS_L1, LFDM_LOSS_L2 }.
+ * not divide n or whose frames are no multiple of 4 elements, t_len <= 0, loss_type outside { LFDM_LOSS_L1, LFDM_LOSS_L2 }, an objective
+ * outside the three or one whose operands are missing (refused with the list of what each needs).
  *   qsample:  x_noisy = known ? x_start : a_tab[t_b] * x_start + s_tab[t_b] * noise  (two fp32 products and one fp32 sum, each rounded on
- *             its own: the bits of q_sample's expression; a known element is the bits of x_start)
- *   loss fwd: S_b = sum over the unknown elements of |noise - pred| (LFDM_LOSS_L2: squared), N_b = their number;
- *             *loss = (1 / B) sum_b S_b / max(N_b, 1);  inv_count[b] = 1 / max(N_b, 1);  in the same pass
- *             pred_x0 = known ? x_noisy : r_tab[t_b] * x_noisy - m_tab[t_b] * pred  (separately rounded: predict_start_from_noise).
- *             ws: lfdm_masked_loss_ws_bytes, 8-byte aligned; ticket: one zeroed word, left zeroed (one stream at a time)
- *   loss bwd: dpred = -sign(noise - pred) * (*gout) * inv_count[b] / B  (LFDM_LOSS_L2: 2 (pred - noise) in place of the sign); known: 0.f */
-#define LFDM_LOSS_L1 0
-#define LFDM_LOSS_L2 1
-/* Layout: x_start, noise, x_noisy dense (B, n), 16 B; t dense (B) int64; a_tab, s_tab dense (t_len); masks dense.  x_noisy must not alias an input. */
-int lfdm_train_qsample_f32(const float* x_start, const float* noise, const int64_t* t, const float* a_tab, const float* s_tab, int t_len,
-                           const unsigned char* frame_mask, const unsigned char* elem_mask, int frames, int64_t frame_elems, float* x_noisy,
-                           int batch, int64_t n, lfdm_stream_t stream);
-size_t lfdm_masked_loss_ws_bytes(int batch, int64_t n);
-/* Layout: noise, pred, x_noisy, pred_x0 dense (B, n), 16 B; t dense (B) int64; r_tab, m_tab dense (t_len); masks dense; loss 1 float,
- * inv_count (B) floats.  pred_x0 must not alias an input. */
-int lfdm_masked_loss_fwd_f32(const float* noise, const float* pred, const float* x_noisy, const int64_t* t, const float* r_tab,
-                             const float* m_tab, int t_len, const unsigned char* frame_mask, const unsigned char* elem_mask, int frames,
-                             int64_t frame_elems, int loss_type, float* loss, float* inv_count, float* pred_x0, int batch, int64_t n, void* ws,
-                             size_t ws_bytes, unsigned* ticket, lfdm_stream_t stream);
-/* Layout: noise, pred, dpred dense (B, n), 16 B; masks dense; inv_count (B) floats and gout 1 float on the device.  dpred must not alias an input. */
-int lfdm_masked_loss_bwd_f32(const float* noise, const float* pred, const unsigned char* frame_mask, const unsigned char* elem_mask, int frames,
-                             int64_t frame_elems, int loss_type, const float* inv_count, const float* gout, float* dpred, int batch, int64_t n,
-                             lfdm_stream_t stream);
-
-/* The same loss for a choice of training objective and with a per-timestep weight (additive, ABI version unchanged).  `out`
- * is the denoiser's output; (a, s, r, m, w) = (a_tab, s_tab, r_tab, m_tab, w_tab)[t_b], the tables of t_len entries on the device:
- *   LFDM_OBJ_NOISE  target = noise                      pred_x0 = r * x_noisy - m * out   (the masked loss above)
+ *             its own: the bits of q_sample's expression; a known element is the bits of x_start).  mask NULL = no mask.
+ * The loss, per training objective and with a per-timestep weight.  `out`: the denoiser's output; (a, s, r, m, w) = (a_tab, .. w_tab)[t_b]:
+ *   LFDM_OBJ_NOISE  target = noise                      pred_x0 = r * x_noisy - m * out   (without w_tab: the masked loss of 4.12)
  *   LFDM_OBJ_X0     target = x_start                    pred_x0 = out (its bits)
  *   LFDM_OBJ_V      target = a * noise - s * x_start    pred_x0 = a * x_noisy - s * out
  * every expression two fp32 products and one fp32 difference, each rounded on its own; the target is never stored.  Operands the objective
  * does not use may be NULL and are never read: x_start, a_tab, s_tab for LFDM_OBJ_NOISE; noise and all four tables for LFDM_OBJ_X0; r_tab,
- * m_tab for LFDM_OBJ_V and in the backward.  w_tab NULL = weight 1.  Geometry, masks, alignment, workspace (lfdm_masked_loss_ws_bytes),
- * ticket and refusals as above; an objective outside the three, or one whose operands are missing, is refused with the list of what each needs.
- *   fwd: S_b, N_b as above over |target - out|;  inv_count[b] = 1 / max(N_b, 1);  sample_loss[b] = S_b / max(N_b, 1) (unweighted);
- *        *loss = (1 / B) sum_b w * S_b / max(N_b, 1), the weight applied in double in the last workgroup's fold;  pred_x0 = x_noisy where
- *        known.  With LFDM_OBJ_NOISE and w_tab NULL: the bits of lfdm_masked_loss_fwd_f32.
- *   bwd: dout = c_b * d|target - out| / d out, c_b = (((*gout) * inv_count[b]) * w) / B in fp32 in that order (w_tab NULL: no product - with
- *        LFDM_OBJ_NOISE the bits of lfdm_masked_loss_bwd_f32); known: 0.f */
+ * m_tab for LFDM_OBJ_V and in the backward; in the backward also t and t_len unless it reads a table (LFDM_OBJ_V, or w_tab).  w_tab NULL = 1.
+ *   fwd: S_b = sum over the unknown elements of |target - out| (LFDM_LOSS_L2: squared), N_b = their number;  inv_count[b] = 1 / max(N_b, 1);
+ *        sample_loss[b] = S_b / max(N_b, 1) (unweighted);  *loss = (1 / B) sum_b w * S_b / max(N_b, 1), the weight applied in double in the
+ *        last workgroup's fold;  in the same pass pred_x0 as above, x_noisy where known.
+ *        ws: lfdm_masked_loss_ws_bytes, 8-byte aligned (too small: LFDM_EWORKSPACE); ticket: one zeroed word, left zeroed (one stream at a time)
+ *   bwd: dout = c_b * d|target - out| / d out = -sign(target - out) c_b (LFDM_LOSS_L2: 2 (out - target) c_b), c_b = (((*gout) *
+ *        inv_count[b]) * w) / B in fp32 in that order (w_tab NULL: no product); known: 0.f */
+#define LFDM_LOSS_L1 0
+#define LFDM_LOSS_L2 1
 #define LFDM_OBJ_NOISE 0
 #define LFDM_OBJ_X0 1
 #define LFDM_OBJ_V 2
+typedef struct lfdm_train_mask {
+  const unsigned char *frame_mask, *elem_mask;
+  int frames;
+  int64_t frame_elems;
+} lfdm_train_mask;
+/* Both directions read objective .. n and inv_count (the forward writes it); an entry ignores the other direction's fields. */
+typedef struct lfdm_train_loss_params {
+  int objective, loss_type;
+  const float *x_start, *noise, *out, *x_noisy;         /* x_noisy: forward only */
+  const int64_t* t;
+  const float *a_tab, *s_tab, *r_tab, *m_tab, *w_tab;   /* r_tab, m_tab: forward only */
+  int t_len;
+  lfdm_train_mask mask;
+  int batch;
+  int64_t n;
+  float *loss, *inv_count, *sample_loss, *pred_x0;      /* forward outputs; inv_count is the backward's input */
+  const float* gout;                                    /* backward only, as dout */
+  float* dout;
+  void* ws;                                             /* forward only, as ws_bytes and ticket */
+  size_t ws_bytes;
+  unsigned* ticket;
+} lfdm_train_loss_params;
+/* Layout: x_start, noise, x_noisy dense (B, n), 16 B; t dense (B) int64; a_tab, s_tab dense (t_len); masks dense.  x_noisy must not alias an input. */
+int lfdm_train_qsample_f32(const float* x_start, const float* noise, const int64_t* t, const float* a_tab, const float* s_tab, int t_len,
+                           const lfdm_train_mask* mask, float* x_noisy, int batch, int64_t n, lfdm_stream_t stream);
+size_t lfdm_masked_loss_ws_bytes(int batch, int64_t n);
 /* Layout: x_start, noise, out, x_noisy, pred_x0 dense (B, n), 16 B; t dense (B) int64; the tables dense (t_len); masks dense; loss 1 float,
  * inv_count, sample_loss (B) floats.  pred_x0 must not alias an input. */
-int lfdm_objective_loss_fwd_f32(int objective, const float* x_start, const float* noise, const float* out, const float* x_noisy,
-                                const int64_t* t, const float* a_tab, const float* s_tab, const float* r_tab, const float* m_tab,
-                                const float* w_tab, int t_len, const unsigned char* frame_mask, const unsigned char* elem_mask, int frames,
-                                int64_t frame_elems, int loss_type, float* loss, float* inv_count, float* sample_loss, float* pred_x0,
-                                int batch, int64_t n, void* ws, size_t ws_bytes, unsigned* ticket, lfdm_stream_t stream);
+int lfdm_objective_loss_fwd_f32(const lfdm_train_loss_params* p, lfdm_stream_t stream);
 /* Layout: x_start, noise, out, dout dense (B, n), 16 B; t dense (B) int64; the tables dense (t_len); masks dense; inv_count (B) floats and
  * gout 1 float on the device.  dout must not alias an input. */
-int lfdm_objective_loss_bwd_f32(int objective, const float* x_start, const float* noise, const float* out, const int64_t* t,
-                                const float* a_tab, const float* s_tab, const float* w_tab, int t_len, const unsigned char* frame_mask,
-                                const unsigned char* elem_mask, int frames, int64_t frame_elems, int loss_type, const float* inv_count,
-                                const float* gout, float* dout, int batch, int64_t n, lfdm_stream_t stream);
+int lfdm_objective_loss_bwd_f32(const lfdm_train_loss_params* p, lfdm_stream_t stream);
 
 /* Progressive distillation (Salimans & Ho 2022; additive, ABI version unchanged; DESIGN.md 4.16, csrc/distill.hip): the frozen teacher's
  * DDIM step with a coefficient row PER SAMPLE, and the target one student step has to reach.  Samples are dense rows of n floats (n % 4 == 0,

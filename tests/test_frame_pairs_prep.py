@@ -446,7 +446,7 @@ def test_abi_stays_12_with_the_new_symbol():
     header = open(os.path.join(REPO, "include", "lfdm_hip.h")).read()
     assert "lfdm_frame_pairs_prep_u8" in _native.EXPORTED_SYMBOLS
     assert re.search(r"/\* Layout:[^*]*\*/\s*int lfdm_frame_pairs_prep_u8\(", header)
-    assert _native.NativeLibrary(_build.build_hip(), "hip").lfdm_abi_version() == 13          # (12 when the entry point was added; 13: lfdm_sampler_step_params)
+    assert _native.NativeLibrary(_build.build_hip(), "hip").lfdm_abi_version() == 14          # (12 when the entry point was added; 13: lfdm_sampler_step_params; 14: lfdm_train_loss_params)
 
 
 # ---------------------------------------------------------------------------------------------

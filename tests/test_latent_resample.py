@@ -396,7 +396,7 @@ def test_resample_entry_point_is_declared_and_the_abi_version_stays():
     decl = re.search(r"/\* Layout:([^*]*)\*/\s*(?:#define[^\n]*\n)*int lfdm_latent_resample_f32\(", header)
     assert decl and "dense" in decl.group(1) and "alias" in decl.group(1)
     lib = _native.NativeLibrary(_build.build_hip(), "hip")
-    assert lib.lfdm_abi_version() == 13          # (12 when the entry point was added; 13: lfdm_sampler_step_params)
+    assert lib.lfdm_abi_version() == 14          # (12 when the entry point was added; 13: lfdm_sampler_step_params; 14: lfdm_train_loss_params)
 
 
 # ------------------------------------------------------------------------------------------ model level

@@ -7,12 +7,14 @@ Bars.  pred_x0 and inv_count: torch.equal (separately rounded fp32 expressions).
 the fp32-rounded target and the fp32 table weight - the bar of test_train_known.py, whose derivation carries over: the weight is applied in
 double and every term is non-negative.  Backward: 1e-6 of the largest gradient magnitude - five fp32 roundings in c_b = ((g inv) w) / B
 (inv, two products, one quotient) and the l2 product, 5 * 2^-24 = 3e-7; exactly 0.0 at known elements."""
+import ctypes
 import functools
 
 import pytest
 import torch
 
 from cvpr23_lfdm_amd import GaussianDiffusion, ops
+from cvpr23_lfdm_amd._native import TrainLossParams, TrainMask
 from util import rnd
 
 NAN = float("nan")
@@ -139,7 +141,10 @@ def test_objective_loss_fwd(backend, shape, form, objective, loss_type, weighted
     if objective != "pred_v":
         for a, b2 in zip(got, _fwd(case, form, objective, loss_type, weighted, dev, unused=_nan(shape, dev))):
             assert torch.equal(a, b2), "an unused operand was read"
-    if objective == "pred_noise" and not weighted:          # the anchor: the bits of the masked loss
+    # the anchor: the bits of the masked loss.  Both fronts run one kernel, so this pins the masked front's operand mapping (r / m tables in
+    # their slots, x_start absent, sample_loss dropped); the bit identity with the two separate kernels this replaced was shown once, by
+    # tools/ab_bits.py --set train_loss against the commit before (profiles/train_loss_refactor_ab.txt)
+    if objective == "pred_noise" and not weighted:
         tab = _tables()
         anchor = ops.masked_loss_fwd(case["noise"].to(dev), case["out"].to(dev), case["x_noisy"].to(dev), case["t"].to(dev), tab[TABS[2]].to(dev),
                                      tab[TABS[3]].to(dev), loss_type=loss_type, **_mask_kw(case, form, dev))
@@ -166,7 +171,7 @@ def test_objective_loss_bwd(backend, shape, form, objective, loss_type, weighted
     assert torch.equal(got, _bwd(case, form, objective, loss_type, weighted, dev)), "two runs on the same inputs differ"
     if objective != "pred_v":
         assert torch.equal(got, _bwd(case, form, objective, loss_type, weighted, dev, unused=_nan(shape, dev))), "an unused operand was read"
-    if objective == "pred_noise" and not weighted:
+    if objective == "pred_noise" and not weighted:          # (the anchor, as in the forward: the masked front's operand mapping, no t)
         anchor = ops.masked_loss_bwd(case["noise"].to(dev), case["out"].to(dev), case["inv"].to(dev), torch.tensor([GOUT]).to(dev),
                                      loss_type=loss_type, **_mask_kw(case, form, dev))
         assert torch.equal(got, anchor)
@@ -218,10 +223,55 @@ def test_objective_loss_refusals(backend):
     assert all(bool(torch.isnan(v).all()) for v in dest.values())                  # a refused call writes nothing
     lib = ops._lib()
     p, n = ops._p, x[0].numel()
-    rc = lib.lfdm_objective_loss_bwd_f32(7, p(x), p(x), p(x), p(t), p(a), p(s), None, a.numel(), None, None, 0, 0, 0, p(a), p(a), p(dest["pred_x0"]),
-                                         2, n, ops._stream(lib))
+    bwd = dict(noise=p(x), out=p(x), t=p(t), a_tab=p(a), s_tab=p(s), t_len=a.numel(), inv_count=p(a), gout=p(a), dout=p(dest["pred_x0"]), batch=2, n=n)
+    rc = lib.lfdm_objective_loss_bwd_f32(ctypes.byref(TrainLossParams(objective=7, x_start=p(x), **bwd)), ops._stream(lib))
     assert rc == -1 and b"objective must be" in lib.lfdm_last_error()
-    rc = lib.lfdm_objective_loss_bwd_f32(2, None, p(x), p(x), p(t), p(a), p(s), None, a.numel(), None, None, 0, 0, 0, p(a), p(a), p(dest["pred_x0"]),
-                                         2, n, ops._stream(lib))
+    rc = lib.lfdm_objective_loss_bwd_f32(ctypes.byref(TrainLossParams(objective=2, **bwd)), ops._stream(lib))
     assert rc == -1 and b"LFDM_OBJ_V needs x_start, noise, a_tab and s_tab" in lib.lfdm_last_error()
     assert bool(torch.isnan(dest["pred_x0"]).all())
+
+
+def test_loss_params_refusals(backend):
+    """lfdm_train_loss_params straight through ctypes: what the Python layer never lets through.  (2, 3, 2, 2, 2), n = 24: nothing smaller
+    satisfies n % 4 == 0 with a two-frame split of 4-element frames.  Each case: the status, a word of the message, nothing written."""
+    dev, tab = backend, _tables()
+    lib = ops._lib()
+    p = ops._p
+    a, s, r, m = (tab[k].to(dev) for k in TABS)
+    t = torch.zeros(2, dtype=torch.int64, device=dev)
+    x = torch.zeros(2, 3, 2, 2, 2, device=dev)
+    n = x[0].numel()
+    fmask, emask = torch.zeros(2, 2, dtype=torch.uint8, device=dev), torch.zeros(2, n, dtype=torch.uint8, device=dev)
+    dest = dict(loss=_nan((1,), dev), inv_count=_nan((2,), dev), sample_loss=_nan((2,), dev), pred_x0=_nan(x.shape, dev), dout=_nan(x.shape, dev))
+    nbytes = lib.lfdm_masked_loss_ws_bytes(2, n)
+    ws = torch.zeros(nbytes // 8, dtype=torch.int64, device=dev)
+    ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+    gout = torch.ones(1, device=dev)
+    good = dict(objective=2, loss_type=0, x_start=p(x), noise=p(x), out=p(x), x_noisy=p(x), t=p(t), a_tab=p(a), s_tab=p(s), r_tab=p(r), m_tab=p(m),
+                t_len=a.numel(), batch=2, n=n, gout=p(gout), ws=p(ws), ws_bytes=nbytes, ticket=p(ticket), **{k: p(v) for k, v in dest.items()})
+    einval, eworkspace = -1, -3                                    # LFDM_EINVAL, LFDM_EWORKSPACE
+    cases = [                                                      # (entry, fields changed, status, a word of the message)
+        ("fwd", dict(objective=3), einval, b"objective must be"),
+        ("bwd", dict(objective=3), einval, b"objective must be"),
+        ("fwd", dict(objective=0, noise=None), einval, b"LFDM_OBJ_NOISE needs noise"),
+        ("bwd", dict(objective=0, noise=None), einval, b"LFDM_OBJ_NOISE needs noise"),
+        ("fwd", dict(objective=1, x_start=None), einval, b"LFDM_OBJ_X0 needs x_start"),
+        ("bwd", dict(objective=1, x_start=None), einval, b"LFDM_OBJ_X0 needs x_start"),
+        ("fwd", dict(objective=2, a_tab=None), einval, b"a_tab and s_tab"),
+        ("bwd", dict(objective=2, a_tab=None), einval, b"a_tab and s_tab"),
+        ("fwd", dict(objective=0, r_tab=None), einval, b"r_tab and m_tab"),
+        ("fwd", dict(mask=TrainMask(p(fmask), p(emask), 2, 4)), einval, b"exclude each other"),
+        ("bwd", dict(mask=TrainMask(p(fmask), p(emask), 2, 4)), einval, b"exclude each other"),
+        ("fwd", dict(mask=TrainMask(None, None, 2, 4)), einval, b"needs frame_mask"),
+        ("bwd", dict(mask=TrainMask(None, None, 2, 4)), einval, b"needs frame_mask"),
+        ("fwd", dict(ws_bytes=nbytes - 1), eworkspace, b"workspace of"),
+        ("fwd", dict(ticket=None), einval, b"ticket word"),
+        ("bwd", dict(gout=None), einval, b"gout"),
+    ]
+    for entry, change, status, word in cases:
+        fn = lib.lfdm_objective_loss_fwd_f32 if entry == "fwd" else lib.lfdm_objective_loss_bwd_f32
+        rc = fn(ctypes.byref(TrainLossParams(**dict(good, **change))), ops._stream(lib))
+        msg = lib.lfdm_last_error()
+        assert rc == status and word in msg and msg.startswith(b"objective_loss_%s:" % entry.encode()), (entry, change, rc, msg)
+        assert all(bool(torch.isnan(v).all()) for v in dest.values()), (entry, change)
+    assert int(ticket) == 0

@@ -180,7 +180,11 @@ def test_refusals(backend):
         ops.train_qsample(x, x, t, a[:0], s[:0], out=out)
     assert bool(torch.isnan(out).all())                                            # a refused call writes nothing
     lib = ops._lib()
-    rc = lib.lfdm_masked_loss_bwd_f32(ops._p(x), ops._p(x), None, None, 0, 0, 7, ops._p(a), ops._p(a), ops._p(out), 2, x[0].numel(), ops._stream(lib))
+    import ctypes
+    from cvpr23_lfdm_amd._native import TrainLossParams
+    params = TrainLossParams(objective=0, loss_type=7, noise=ops._p(x), out=ops._p(x), inv_count=ops._p(a), gout=ops._p(a), dout=ops._p(out), batch=2,
+                             n=x[0].numel())
+    rc = lib.lfdm_objective_loss_bwd_f32(ctypes.byref(params), ops._stream(lib))
     assert rc == -1 and b"loss_type" in lib.lfdm_last_error()
 
 

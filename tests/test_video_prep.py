@@ -429,7 +429,7 @@ def test_abi_stays_12_with_the_new_symbols():
     header = open(os.path.join(REPO, "include", "lfdm_hip.h")).read()
     for sym in ("lfdm_video_prep_u8", "lfdm_video_prep_ws_bytes"):
         assert sym in _native.EXPORTED_SYMBOLS and ("%s(" % sym) in header
-    assert _native.NativeLibrary(_build.build_hip(), "hip").lfdm_abi_version() == 13          # (12 when the entry point was added; 13: lfdm_sampler_step_params)
+    assert _native.NativeLibrary(_build.build_hip(), "hip").lfdm_abi_version() == 14          # (12 when the entry point was added; 13: lfdm_sampler_step_params; 14: lfdm_train_loss_params)
 
 
 # ---------------------------------------------------------------------------------------------

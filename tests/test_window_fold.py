@@ -383,4 +383,4 @@ def test_header_declares_the_entry_points():
 
 def test_abi_version_stays_13(backend):
     from cvpr23_lfdm_amd import _native
-    assert _native.library().lfdm_abi_version() == 13
+    assert _native.library().lfdm_abi_version() == 14          # (13 when the entries were added, hence the name; 14: lfdm_train_loss_params)

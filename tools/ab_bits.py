@@ -2,11 +2,11 @@
 """Same bits?  Runs a fixed list of calls on seeded inputs under ONE build of the kernels and writes one line per output tensor -
 name, shape, SHA-256 of its bytes - so that two builds (a refactor and its parent commit) can be compared line by line.
 
-    tools/ab_bits.py run OUT.txt [--emu [LIB]] [--set conv|attention|norm|boundary|sampler|glue]
+    tools/ab_bits.py run OUT.txt [--emu [LIB]] [--set conv|attention|norm|boundary|sampler|glue|train_loss]
                                                          this process, the library LFDM_HIP_LIB names (default: the in-tree one) on the GPU,
                                                          or an emulator library on the CPU (default: the in-tree one)
     tools/ab_bits.py diff A.txt B.txt                    exit status 1 when any line differs or is missing
-    tools/ab_bits.py ab BASE_LIB OUT_DIR [--emu] [--new LIB] [--timeout S] [--set conv|attention|norm|boundary|sampler|glue]
+    tools/ab_bits.py ab BASE_LIB OUT_DIR [--emu] [--new LIB] [--timeout S] [--set conv|attention|norm|boundary|sampler|glue|train_loss]
                                                          `run` under BASE_LIB, then under the in-tree library (or --new), each in a fresh child
                                                          process with its own time limit, one after the other; stops at the first non-zero
                                                          exit status; then `diff`
@@ -92,6 +92,14 @@ SETS = {
         ("tests/test_render.py",
          "test_image_panels_are_sample_img or test_conf_panel_is_conf2fig or test_flow_colour or test_flow_panel_is_the_resized_colour_image or "
          "test_strip_panels_land_in_their_columns or test_strip_batch_elements_are_independent"),
+    ], "not refusals"),
+    # train_loss: the diffusion edge of DM training (csrc/train_diffusion.hip) and the distillation kernels that share csrc/train_elem_core.h,
+    # forward, backward and through the autograd Functions.  When the C ABI differs between the two builds, `run` goes once in a checkout of
+    # each commit (this file copied into the older one) and `diff` compares the two files.
+    "train_loss": ([
+        ("tests/test_train_known.py", "test_train_qsample or test_masked_loss"),
+        ("tests/test_objective_loss.py", "test_objective_loss_fwd or test_objective_loss_bwd or test_objective_loss_autograd"),
+        ("tests/test_distill_ops.py", "test_distill_x0 or test_distill_step"),
     ], "not refusals"),
 }
 ARGUMENTS_TOO = {"sampler"}      # sets whose calls write their results in place
